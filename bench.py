@@ -11,6 +11,15 @@ per GPU that are already resident in HBM, followed by the RCCL all-gather of the
 that feeds the consensus step.  Frames and weights are synthetic/procedural (no dataset or checkpoint exists offline).  Rank 0
 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps, writes their outputs (--dump-outputs DIR) and prints the headline keys
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`, `caption_tokens`).  Everything else the line
+can carry - `pool_uncoalesced`, `strong_scaling`, `power`, `single_stream`, `roofline` / `kernels` / `decode`,
+`pass_rows_profile`, `encoder_only`, `latency`, `parity`, the other precisions, `cpu_baseline`, `config.also` / `summary` - is
+measured only with --full (and there as described below; --lite / --no-* trim a --full run as before).
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR     # DIR/sequences.npy, DIR/lengths.npy (float64)
+
 `value` is measured the way the product's batch entry points run (`BLIP.generate_batch` / `Captioner.caption_batch` /
 `pseudolabeler.BatchedBoxCaptioner` with `captioner.streams: 3`): the K timed steps' batches go to an EnginePool of --streams
 engines whose dynamic batching (--coalesce-rows, default 1024) merges CONSECUTIVE STEPS' batches into passes of up to 1024 rows -
@@ -18,8 +27,8 @@ engines whose dynamic batching (--coalesce-rows, default 1024) merges CONSECUTIV
 alone, in its 256-frame batch and in a merged pass (tests/test_merged_passes_gpu.py), so the captions are those of the unmerged
 steps; what a merged pass changes is the latency of a batch (its pass finishes as a whole) and the number of decode chains.
 `config.workload` / `config.pass_rows` name the pass size; the figure with every 256-frame batch as its own pass
-(--coalesce-rows 0; rounds 1-4's headline, BASELINE's "batch=256" read strictly) is on the same line as `pool_uncoalesced` and in
-`config.also`; one batch at a time on one stream is `single_stream`.
+(--coalesce-rows 0; rounds 1-4's headline, BASELINE's "batch=256" read strictly) is on the --full line as `pool_uncoalesced` and
+in `config.also`; one batch at a time on one stream is `single_stream`.
 
 The headline (`value`, `dtype`, `roofline`, `kernels`, `parity`) is the mode that holds the metric's parity clause: "f32s" =
 CAP_F32_SPLIT, fp32 values carried into every GEMM as two fp16 halves with three fp16 MFMAs per product (DESIGN.md section
@@ -111,6 +120,11 @@ def parse():
                     help="blip: decode kernels of the timed steps (engine.set_decode_path; A/B of the batch path's kernel sets)")
     ap.add_argument("--row-compaction", default="on", choices=["on", "off"],
                     help="blip: the greedy decode loop on the open captions' rows only (engine.set_row_compaction; same tokens; off = A/B)")
+    ap.add_argument("--full", action="store_true", help="blip: everything the line can carry beside the headline - the uncoalesced "
+                    "and strong-scaling figures, power, the single-stream / roofline / per-kernel / encoder-only / latency legs, golden "
+                    "parity, the other precisions and the CPU baseline.  Off: set up, warm up, time the steps, print the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path "
+                    "computed in its last step (the arrays its caller receives) as DIR/<name>.npy in float64 (integers) or float32")
     ap.add_argument("--lite", action="store_true", help="timed steps only (profiler counter passes): no roofline / "
                     "encoder-only / parity / fp32 / CPU legs")
     ap.add_argument("--no-latency", action="store_true", help="skip the small-batch `latency` block (profiler passes: its B = 1 / 8 / 64 "
@@ -184,9 +198,29 @@ class _NoPower:
         return None
 
 
-def timed_steps(eng, px, L, steps, warmup, world, gather, beams=1, dev="cuda", coalesce=0):
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: the last timed step's outputs as DIR/<name>.npy - integer tensors (token ids, lengths) as float64,
+    which holds them exactly, floating-point ones as float32 - so that two builds can be compared output for output."""
+    out = {}
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy()
+        out[name] = x.astype(np.float32 if x.dtype.kind == "f" else np.float64)
+    total = sum(x.nbytes for x in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(d, exist_ok=True)
+    for name, x in out.items():
+        np.save(os.path.join(d, f"{name}.npy"), x)
+    log(f"outputs of the last timed step written to {d}: {', '.join(f'{n} {list(x.shape)}' for n, x in out.items())}")
+
+
+def timed_steps(eng, px, L, steps, warmup, world, gather, beams=1, dev="cuda", coalesce=0, power=True):
     """`eng`: a CaptionerEngine, or an EnginePool - consecutive steps then run on the pool's engines / streams and overlap
-    (each step is still one whole batch through encoder + decode + gather; all of them finish inside the timed region)."""
+    (each step is still one whole batch through encoder + decode + gather; all of them finish inside the timed region).
+    Returns (seconds, the last step's gathered (ids, lens)); the last step's output dict is left in `timed_steps.last_out`."""
     pool = eng if hasattr(eng, "submit") else None
 
     def run(n):
@@ -194,19 +228,21 @@ def timed_steps(eng, px, L, steps, warmup, world, gather, beams=1, dev="cuda", c
             for _ in range(n):
                 out = eng.generate(px, num_beams=beams, max_length=L)
                 res = gather(out["sequences"], out["lengths"])
+            timed_steps.last_out = out
             return res
         # the batches overlap on the pool's streams; the caption all-gathers (one per step, as before) are issued in step
         # order on the caller's stream once the batches are joined - every rank issues its collectives in the same order
         outs = pool.generate_many([px] * n, threads=True, coalesce_rows=coalesce, num_beams=beams, max_length=L)   # a host thread per engine
         for out in outs:
             res = gather(out["sequences"], out["lengths"])
+        timed_steps.last_out = out
         return res
     from embodied_captioning_amd.distributed import timed_region
     # every engine of a pool runs once untimed - with dynamic batching at the timed passes' size (their merged input buffers come
     # out of the allocator's cache in the timed region)
     run(max(warmup, len(pool) * max(1, coalesce // max(1, int(px.shape[0])))) if pool is not None else warmup)
     on_gpu = dev != "cpu"
-    with (PowerSampler(torch.cuda.current_device()) if on_gpu else _NoPower()) as ps:
+    with (PowerSampler(torch.cuda.current_device()) if on_gpu and power else _NoPower()) as ps:
         # barrier + synchronise, the K steps, synchronise + barrier, MAX over ranks (distributed.timed_region)
         dt, res = timed_region(lambda: run(steps), world, torch.device("cuda", torch.cuda.current_device()) if on_gpu else None)
     timed_steps.power = ps
@@ -546,6 +582,8 @@ def main_coca(a):
         from embodied_captioning_amd.engine import EnginePool
         pool = EnginePool(arch, n=a.streams, dtype=a.dtype, max_batch=max(B, coal), max_beams=K, max_len=arch.seq_len, weights_of=eng)
     dt, _ = timed_steps(pool or eng, px, arch.seq_len, a.steps, a.warmup, 1, lambda i, l: (i, l), K, coalesce=coal)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, timed_steps.last_out)
     if pool is not None:
         pool.close()
     eng.profile(True)
@@ -601,6 +639,8 @@ def main_minilm(a):
             out = eng.embed(idd, lnd)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"embeddings": out})
     if pool is not None:
         pool.close()
     eng.profile(True)
@@ -655,6 +695,8 @@ def main_blip2(a):
         pool.close()
         pool = EnginePool(arch, n=a.streams, dtype=a.dtype, max_batch=coal, max_beams=1, max_len=arch.max_new_tokens, weights_of=eng, weight_int8=q8)
     dt, (ids, lens) = timed_steps(pool or eng, px, arch.max_new_tokens, a.steps, a.warmup, 1, lambda i, l: (i, l), coalesce=coal)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, timed_steps.last_out)
     if pool is not None:
         pool.close()
     eng.profile(True)
@@ -905,6 +947,8 @@ def main_stub(a, dev, rank, world):
     px = torch.arange(rank * B, rank * B + B, dtype=torch.int32)
     gather = make_step_gather(world, B, L, "cpu")
     dt, (ids, lens) = timed_steps(eng, px, L, a.steps, a.warmup, world, gather, 1, dev="cpu")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"sequences": ids, "lengths": lens})
     want = eng.generate(torch.arange(world * B, dtype=torch.int32))
     assert torch.equal(ids, want["sequences"]) and torch.equal(lens, want["lengths"]), "gathered records are not rank-major"
     strong = None if a.no_strong else strong_figure(a, None, eng, dev, world, L, B, stub=True)
@@ -954,6 +998,8 @@ def main():
         a.coalesce_rows, a.coalesce_defaulted = 1024, True
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.dump_outputs and (a.strong or a.latency_only):
+        raise SystemExit("--dump-outputs writes the outputs of the timed steps: --strong and --latency-only have none")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         if a.model != "blip":
             raise SystemExit(f"--gpus {a.gpus}: only the blip workload (BASELINE's metric) runs on several ranks")
@@ -1026,9 +1072,13 @@ def main():
         runner.set_decode_path(a.decode_path)
         runner.set_row_compaction(a.row_compaction == "on")
     log(f"weights loaded once, {a.streams} engine(s) / stream(s) on them; timing ({a.dtype})")
-    dt, (ids, lens) = timed_steps(runner, px, L, a.steps, a.warmup, world, gather, a.beams, coalesce=coal)
+    dt, (ids, lens) = timed_steps(runner, px, L, a.steps, a.warmup, world, gather, a.beams, coalesce=coal, power=a.full)
+    if a.dump_outputs and rank == 0:
+        last = timed_steps.last_out              # the gathered records (every rank's rows) and, with beams, rank 0's scores
+        dump_outputs(a.dump_outputs, {"sequences": ids, "lengths": lens,
+                                      **({"sequences_scores": last["sequences_scores"]} if "sequences_scores" in last else {})})
     uncoalesced = None
-    if coal and a.streams > 1 and not a.lite:
+    if a.full and coal and a.streams > 1 and not a.lite:
         # the same steps with every batch as its own pass (rounds 1-4's headline), for the record
         udt, _ = timed_steps(runner, px, L, a.steps, a.streams, world, gather, a.beams)
         uncoalesced = {"value": round(world * B * a.steps / udt, 2), "unit": "captions/s", "ms_per_step": round(1e3 * udt / a.steps, 3),
@@ -1036,7 +1086,7 @@ def main():
     decode_steps = (runner.engines[0] if a.streams > 1 else eng).last_decode_steps
     log(f"timed region: {dt:.3f}s for {a.steps} steps (max over ranks)")
     strong = None
-    if not (a.no_strong or a.lite or a.beams > 1 or arch.image_size != 224 or a.early_exit):
+    if a.full and not (a.no_strong or a.lite or a.beams > 1 or arch.image_size != 224 or a.early_exit):
         log(f"strong-scaling job: {a.frames} frames in total over {world} rank(s)")
         strong = strong_figure(a, arch, runner, dev, world, L, max(B, coal))      # micro-batches of the merged passes' size
         if coal > B:                             # and at SURVEY config 4's own micro-batch (256), every micro-batch its own pass
@@ -1087,13 +1137,13 @@ def main():
             line["config"]["early_exit_poll"] = a.early_exit
             line["config"]["eos_boost"] = a.eos_boost
             line["decode_steps_run"] = decode_steps
-        if a.beams > 1:                      # config 3 extra line: per-kernel profile of one beam generate, then stop
+        if a.full and a.beams > 1:           # config 3 extra line: per-kernel profile of one beam generate, then stop
             eng.profile(True)
             eng.generate(px, num_beams=a.beams, max_length=L)
             rep = eng.profile_report()
             eng.profile(False)
             line["kernels_ms"] = {k: round(v["ms"], 3) for k, v in sorted(rep.items(), key=lambda kv: -kv[1]["ms"])[:14]}
-        if a.lite or a.beams > 1 or S != 224:
+        if not a.full or a.lite or a.beams > 1 or S != 224:
             print(json.dumps(line))
             eng.close()
             if world > 1:                    # the other ranks are waiting at the closing barrier below

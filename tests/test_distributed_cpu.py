@@ -232,3 +232,27 @@ def test_bench_gpus_n_starts_its_own_ranks():
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--stub-engine"], env={**env, "WORLD_SIZE": "1"},
                          capture_output=True, text=True, timeout=120)
     assert bad.returncode != 0 and "WORLD_SIZE=1" in bad.stderr
+
+
+def test_bench_dump_outputs_are_the_gathered_records_of_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: the records the last timed step's all-gather returned (every rank's rows, rank-major) as float64
+    .npy files; `--steps` is the number of timed steps the line reports."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--stub-engine", "--steps", "5", "--warmup", "1",
+                        "--batch", "8", "--max-length", "6", "--no-strong", "--dump-outputs", str(d)], env=env, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert line["steps"] == 5 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(d)) == ["lengths.npy", "sequences.npy"]
+    ids, lens = np.load(d / "sequences.npy"), np.load(d / "lengths.npy")
+    assert ids.dtype == np.float64 and lens.dtype == np.float64
+    frames = np.arange(16)
+    assert np.array_equal(ids, np.stack([(frames * 7 + j) % 1000 for j in range(6)], axis=1))
+    assert np.array_equal(lens, frames % 5 + 2)
