@@ -27,9 +27,14 @@ def derive_coca_tensors(sd: Dict[str, torch.Tensor], a: CocaArch) -> Dict[str, t
     out: Dict[str, torch.Tensor] = {}
     p = "visual.attn_pool."
     bias = sd[p + "attn.in_proj_bias"].float()
+    if p + "attn.q_proj_weight" in sd:
+        wq, wk, wv = (sd[p + f"attn.{n}_proj_weight"].float() for n in "qkv")
+    else:
+        # nn.MultiheadAttention keeps ONE packed [3E, E] in_proj when kdim == vdim == embed_dim (pooler width = vision width)
+        wq, wk, wv = sd[p + "attn.in_proj_weight"].float().split(E, 0)
     q = F.layer_norm(sd[p + "query"].float(), (E,), sd[p + "ln_q.weight"].float(), sd[p + "ln_q.bias"].float(), a.eps)
-    out["derived.pool_q"] = F.linear(q, sd[p + "attn.q_proj_weight"].float(), bias[:E]).contiguous()
-    out["derived.pool_kv.weight"] = torch.cat([sd[p + "attn.k_proj_weight"].float(), sd[p + "attn.v_proj_weight"].float()], 0)
+    out["derived.pool_q"] = F.linear(q, wq, bias[:E]).contiguous()
+    out["derived.pool_kv.weight"] = torch.cat([wk, wv], 0)
     out["derived.pool_kv.bias"] = bias[E:].contiguous()
     ws, bs = [], []
     for i in range(a.mm_layers):

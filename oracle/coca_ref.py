@@ -1,10 +1,10 @@
-"""CPU restatement of the CoCa captioning path.  TEST INFRASTRUCTURE - NOT PRODUCT CODE.  **PARITY UNPINNED.**
+"""CPU restatement of the CoCa captioning path.  TEST INFRASTRUCTURE - NOT PRODUCT CODE.
 
 The reference's CoCa (``experimenting_env/captioner/models/coca/coca_model.py``) builds its towers from `open_clip`
 (``open_clip.transformer.{VisionTransformer, TextTransformer, MultimodalTransformer}``, unpinned in
 ``requirements.txt:15``), which is not installed in the build container and has no wheel offline; the reference's own
 `generate` additionally asserts on transformers >= 5 (``coca_model.py:20-46,227``: `BeamSearchScorer` is gone).  So no
-golden vector can be produced here.  This file restates, from the published open_clip (v2.2x) algorithm:
+golden vector comes from open_clip itself.  This file restates, from the published open_clip (v2.2x) algorithm:
 
   * VisionTransformer(attentional_pool=True, output_tokens=True): conv patch-embed (no bias) + cls + abs-pos, ln_pre,
     pre-LN blocks (nn.MultiheadAttention in_proj, exact GELU MLP), AttentionalPooler (256 learned queries, 8 heads,
@@ -18,9 +18,17 @@ and the decode loop that IS in the reference tree (``coca_model.py:205-333``, ge
 ``captioner/models/coca/coca.py:29`` calls it): MinLength(min_seq_len, eos), forced EOS at cur_len + 1 == seq_len,
 rows whose last token is EOS/pad emit pad, per-step logits of the active rows.
 
-What the tests can establish for CoCa is therefore self-consistency (KV-cached step == full-prefix recompute, the
-reference's way), HIP-vs-this-restatement parity, and identity of the building blocks (`_mha`, `_block`) with the torch.nn
-modules open_clip composes (tests/test_coca_cpu.py) - not identity of the whole composition with open_clip's code.
+What is pinned, and to what (tests/golden/coca_*.npz, float64, tools/make_goldens_coca.py; tests/test_coca_golden_cpu.py
+holds this file to them, tests/test_coca_golden_gpu.py the HIP path):
+  * vision trunk (patch embed, cls, positions, ln_pre, every block) and unimodal text tower: HuggingFace CLIPVisionModel /
+    CLIPTextModel, the same pre-LN CLIP blocks open_clip builds;
+  * attentional pooler and multimodal decoder composition: torch.nn modules (LayerNorm, MultiheadAttention with
+    kdim = vdim = vision width, TransformerEncoderLayer(norm_first) + cross-attention blocks with ln_1_kv, ln_final);
+  * greedy (top-k 1) decode loop: still this file's restatement of the reference loop (the golden loop is written from the
+    same rules, with full-prefix recompute) - and beam / group-beam search (below) are UNPINNED: nothing independent of
+    them can be run here.
+Beside that: self-consistency (KV-cached step == full-prefix recompute, the reference's way), HIP-vs-this-restatement
+parity, and the building blocks (`_mha`, `_block`) against the torch.nn modules (tests/test_coca_cpu.py).
 """
 from __future__ import annotations
 
@@ -310,7 +318,7 @@ def generate_beamsearch_groups(sd, a, pixels: Tensor, num_beams: int = 6, num_be
     `BeamSearchScorer.process(..., group_index=g)` (a `BeamHypotheses` per (image, group), :440-449), and the group's rows of
     `input_ids` reordered in place (:455-457).  `finalize` (:472-481) adds the open beams of every (image, group) that is not
     done and returns the best hypothesis over ALL groups of an image (the legacy scorer's `num_beam_hyps_to_keep = 1`).
-    No diversity processor is attached (:236-241), so nothing couples the groups.  **PARITY UNPINNED** as everything CoCa here.
+    No diversity processor is attached (:236-241), so nothing couples the groups.  **PARITY UNPINNED** as every CoCa beam search here.
     Returns {"sequences", "scores", "group_sequences": per (image, group) best hypothesis - for the test of the equivalence
     with ONE search of num_beams / num_beam_groups beams that the product relies on}."""
     seq_len = seq_len or a.seq_len

@@ -31,6 +31,36 @@ def golden_inputs(name):
     return g, meta, arch, _SD_CACHE[key], px
 
 
+_COCA_SD_CACHE = {}
+
+
+def coca_golden(name, part=""):
+    """A CoCa fixture of tools/make_goldens_coca.py -> (values with the `part` prefix stripped, meta, arch, state dict,
+    pixels).  The state dict is the one the library loads (coca_library_state_dict: derived tensors added, the position
+    table resized from `weights_image_size` to the arch's input size); it is cached per fixture."""
+    import dataclasses
+    from embodied_captioning_amd.coca_weights import coca_library_state_dict
+    from embodied_captioning_amd.config import CocaArch
+    from embodied_captioning_amd.weights import procedural_coca_state_dict
+    g = np.load(os.path.join(GOLDEN, name + ".npz"))
+    vals = {k[len(part):]: g[k] for k in g.files if k.startswith(part)}
+    meta = json.loads(str(vals["meta"]))
+    arch = CocaArch(**meta["arch"])
+    key = (name, meta["seed"], meta["eos_boost"])
+    if key not in _COCA_SD_CACHE:
+        _COCA_SD_CACHE.clear()                          # full-size dicts are GBs: keep one
+        wa = dataclasses.replace(arch, image_size=meta["weights_image_size"])
+        _COCA_SD_CACHE[key] = coca_library_state_dict(procedural_coca_state_dict(wa, meta["seed"], eos_boost=meta["eos_boost"]), arch)
+    px = synthetic_pixels(meta["batch"], arch.image_size, seed=meta["seed"])
+    return vals, meta, arch, _COCA_SD_CACHE[key], px
+
+
+def strided(x, stride):
+    """[B, ...] -> every `stride`-th value of each row, the layout of the fixtures' *_sample arrays."""
+    x = np.asarray(x)
+    return x.reshape(x.shape[0], -1)[:, ::int(stride)]
+
+
 def pad_to(seq, L, fill):
     """HF crops generated sequences at the longest row; our ABI returns [B, max_len]."""
     seq = np.asarray(seq)

@@ -1,5 +1,6 @@
-"""CPU: CoCa oracle restatement (parity UNPINNED - open_clip is not available): self-consistency, and its building blocks
-against the torch.nn modules open_clip composes."""
+"""CPU: CoCa oracle restatement (open_clip is not available): self-consistency, and its building blocks against the torch.nn
+modules open_clip composes.  The whole composition is pinned to float64 goldens in test_coca_golden_cpu.py; the beam
+searches stay unpinned."""
 import pytest
 import torch
 

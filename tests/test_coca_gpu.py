@@ -1,4 +1,5 @@
-"""GPU: CoCa through the C ABI against the CPU restatement (oracle/coca_ref.py - unpinned, see its header)."""
+"""GPU: CoCa through the C ABI against the CPU restatement (oracle/coca_ref.py).  Its towers, pooler and decoder are pinned to
+float64 goldens (test_coca_golden_gpu.py holds the HIP path to them directly); its beam and group-beam searches are unpinned."""
 import numpy as np
 import pytest
 import torch
