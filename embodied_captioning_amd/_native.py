@@ -14,6 +14,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libcaptioner_hip.so")
 
 CAP_F32, CAP_BF16, CAP_F32_SPLIT = 0, 1, 2
 CAP_PIX_F32_NCHW, CAP_PIX_U8_NHWC = 0, 1
+CAP_ARCH_CLIP = 4
+CAP_ACT_QUICK_GELU, CAP_ACT_GELU = 0, 1
 
 
 class CapConfig(C.Structure):
@@ -30,7 +32,7 @@ class CapConfig(C.Structure):
         ("min_len", C.c_int32),
         ("q_hidden", C.c_int32), ("q_layers", C.c_int32), ("q_heads", C.c_int32), ("q_ffn", C.c_int32),
         ("q_cross_freq", C.c_int32), ("num_query_tokens", C.c_int32), ("q_eps", C.c_float),
-        ("cross_kv_fp32", C.c_int32), ("weight_int8", C.c_int32),
+        ("cross_kv_fp32", C.c_int32), ("weight_int8", C.c_int32), ("hidden_act", C.c_int32),
     ]
 
 
@@ -88,6 +90,10 @@ _SIGNATURES = {
                                           C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cap_op_beam_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    "cap_clip_embed_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cap_clip_embed_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cap_clip_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
+    "cap_clip_logit_scale": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "cap_op_convert": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cap_op_convert_weight": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }

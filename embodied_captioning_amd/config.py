@@ -234,3 +234,93 @@ class Blip2Arch:
         return Blip2Arch(image_size=28, patch_size=14, v_hidden=192, v_layers=2, v_heads=8, v_mlp=256, q_hidden=128, q_layers=2,
                          q_heads=2, q_ffn=256, num_query_tokens=8, t_hidden=256, t_layers=2, t_heads=4, t_ffn=512, vocab=512,
                          max_pos=64, eos=3, image_token=511)
+
+
+@dataclasses.dataclass
+class ClipArch:
+    """HF `CLIPModel` (the reference's `--method clip` scorer: `openai/clip-vit-base-patch32`,
+    experimenting_env/captioner/pseudocaptioner.py:39-46).  Defaults = ViT-B/32: a 224 px image tower of 12 x 768 (12 heads,
+    MLP 3072, patch 32: 50 tokens), a causal text tower of 12 x 512 (8 heads, FFN 2048, 77 positions, vocab 49408), both
+    projected to 512; pre-LN, eps 1e-5, quick GELU.  `eos_token_id` decides the pooled text row (HF's rule): 2 (the legacy
+    OpenAI configs) pools at argmax(ids), anything else at the first `eos_token_id`."""
+    image_size: int = 224
+    patch_size: int = 32
+    v_hidden: int = 768
+    v_layers: int = 12
+    v_heads: int = 12
+    v_mlp: int = 3072
+    t_hidden: int = 512
+    t_layers: int = 12
+    t_heads: int = 8
+    t_ffn: int = 2048
+    vocab: int = 49408
+    max_pos: int = 77
+    projection_dim: int = 512
+    eps: float = 1e-5
+    hidden_act: str = "quick_gelu"
+    bos_token_id: int = 49406
+    eos_token_id: int = 49407
+    pad_token_id: int = 1
+
+    ACTS = ("quick_gelu", "gelu")
+
+    def __post_init__(self):
+        if self.hidden_act not in self.ACTS:
+            raise ValueError(f"CLIP hidden_act {self.hidden_act!r} is not supported (the towers run {' / '.join(self.ACTS)})")
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // self.patch_size
+
+    @property
+    def n_tokens(self) -> int:
+        return self.grid * self.grid + 1
+
+    def image_flops(self) -> float:
+        """2*MAC per image: patch GEMM + per layer q|k|v, QK^T, PV, out_proj, fc1, fc2 (+ the head)."""
+        n, d, m = self.n_tokens, self.v_hidden, self.v_mlp
+        per_layer = 2.0 * n * d * 3 * d + 2 * 2.0 * n * n * d + 2.0 * n * d * d + 2 * 2.0 * n * d * m
+        patch = 2.0 * (n - 1) * (3 * self.patch_size ** 2) * d
+        return per_layer * self.v_layers + patch + 2.0 * d * self.projection_dim
+
+    def text_flops_per_token(self) -> float:
+        """2*MAC per caption token of the text tower's GEMMs (attention excluded: it is O(L) per token)."""
+        t, f = self.t_hidden, self.t_ffn
+        return self.t_layers * (2.0 * t * 3 * t + 2.0 * t * t + 2 * 2.0 * t * f)
+
+    @staticmethod
+    def tiny() -> "ClipArch":
+        """Fixture-sized config (tests/golden/clip_tiny.npz): 32 px images with 8 px patches (17 tokens), both towers 2 x 128
+        (heads of 64), vocab 300, 16 positions, projection 64."""
+        return ClipArch(image_size=32, patch_size=8, v_hidden=128, v_layers=2, v_heads=2, v_mlp=256, t_hidden=128, t_layers=2,
+                        t_heads=2, t_ffn=256, vocab=300, max_pos=16, projection_dim=64, bos_token_id=298, eos_token_id=299,
+                        pad_token_id=0)
+
+    @staticmethod
+    def from_hf_config(path_or_dict) -> "ClipArch":
+        """Read a HF `CLIPConfig` ``config.json`` (checkpoint directory, file or parsed dict)."""
+        if isinstance(path_or_dict, (str, os.PathLike)):
+            p = path_or_dict
+            if os.path.isdir(p):
+                p = os.path.join(p, "config.json")
+            with open(p) as f:
+                cfg = json.load(f)
+        else:
+            cfg = dict(path_or_dict)
+        v = cfg.get("vision_config") or {}
+        t = cfg.get("text_config") or {}
+        d = ClipArch()
+        acts = {v.get("hidden_act", d.hidden_act), t.get("hidden_act", d.hidden_act)}
+        if len(acts) != 1:
+            raise ValueError(f"CLIP towers with different activations {sorted(acts)} are not supported")
+        return ClipArch(
+            image_size=v.get("image_size", d.image_size), patch_size=v.get("patch_size", d.patch_size),
+            v_hidden=v.get("hidden_size", d.v_hidden), v_layers=v.get("num_hidden_layers", d.v_layers),
+            v_heads=v.get("num_attention_heads", d.v_heads), v_mlp=v.get("intermediate_size", d.v_mlp),
+            t_hidden=t.get("hidden_size", d.t_hidden), t_layers=t.get("num_hidden_layers", d.t_layers),
+            t_heads=t.get("num_attention_heads", d.t_heads), t_ffn=t.get("intermediate_size", d.t_ffn),
+            vocab=t.get("vocab_size", d.vocab), max_pos=t.get("max_position_embeddings", d.max_pos),
+            projection_dim=cfg.get("projection_dim", d.projection_dim),
+            eps=v.get("layer_norm_eps", t.get("layer_norm_eps", d.eps)), hidden_act=acts.pop(),
+            bos_token_id=t.get("bos_token_id", d.bos_token_id), eos_token_id=t.get("eos_token_id", d.eos_token_id),
+            pad_token_id=t.get("pad_token_id", d.pad_token_id))

@@ -1823,9 +1823,11 @@ int launch_vit_attention(int dtype, const void* qkv, void* ctx, int B, int N, in
                                         3 * D, (long)N * 3 * D, ctx, D, (long)N * D, B, N, N, H, head_dim, causal ? 0 : -1, s, out_dtype);
     }
     const int kb = (N + 31) / 32;
-    const bool mfma_ok = dtype == CAP_DT_BF16 && (kb == 1 || kb == 7 || kb == 9 || kb == 19);
+    // kb 2: CLIP ViT-B/32's 50 tokens - with the scalar kernel, attention was 64 % of the bf16 image tower's kernel time
+    // (profiles/clip_score_bench_scalar_attention.jsonl, tools/bench_clip_score.py); profiles/clip_score_bench.jsonl is the MFMA run
+    const bool mfma_ok = dtype == CAP_DT_BF16 && (kb == 1 || kb == 2 || kb == 7 || kb == 9 || kb == 19);
     if (impl == 2 && !mfma_ok) {
-        cap_set_error("vit_attention: MFMA path needs bf16 and 1, 7, 9 or 19 key blocks (N=%d)", N);
+        cap_set_error("vit_attention: MFMA path needs bf16 and 1, 2, 7, 9 or 19 key blocks (N=%d)", N);
         return -1;
     }
     if (dtype == CAP_DT_F32 && impl != 1 && (kb == 1 || kb == 7 || kb == 9)) {      // fp32 MFMA kernel (impl 1 forces the scalar one)
@@ -1837,6 +1839,7 @@ int launch_vit_attention(int dtype, const void* qkv, void* ctx, int B, int N, in
     if (impl == 0) impl = mfma_ok ? 2 : 1;
     if (impl == 2) {
         if (kb == 1) return launch_mfma_kb<1>(qkv, ctx, B, N, H, s);
+        if (kb == 2) return launch_mfma_kb<2>(qkv, ctx, B, N, H, s);
         if (kb == 7) return launch_mfma_kb<7>(qkv, ctx, B, N, H, s);
         if (kb == 19) return launch_flash_kb<19, 5>(qkv, ctx, B, N, H, s);
         return launch_mfma_kb<9>(qkv, ctx, B, N, H, s);

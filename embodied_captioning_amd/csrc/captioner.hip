@@ -191,6 +191,12 @@ struct Captioner {
     // ---- sentence encoder (CAP_ARCH_MINILM): token-type row 0, activations [max_batch * max_len, .]
     float *tok_type = nullptr, *te_x = nullptr, *te_y = nullptr;
     void *te_xt = nullptr, *te_qkv = nullptr, *te_ctx = nullptr, *te_h = nullptr;
+    // ---- CLIP scorer (CAP_ARCH_CLIP): image tower on the encoder buffers above (vl, X, ln, qkv, ctx, mlp, delta), text tower on
+    // its own [max_batch * max_len, .] buffers; projections fp32 [embed_dim, width] for the pooled head kernel
+    std::vector<VLayer> ctl;
+    float *c_vproj = nullptr, *c_tproj = nullptr, *c_tok = nullptr, *c_lnf_g = nullptr, *c_lnf_b = nullptr, *c_logit = nullptr,
+          *c_x = nullptr, *c_delta = nullptr;
+    void *c_ln = nullptr, *c_qkv = nullptr, *c_ctx = nullptr, *c_mlp = nullptr;
     // profiling
     bool prof = false;
     std::vector<ProfTag> prof_recs;
@@ -1048,6 +1054,147 @@ int run_text_encoder(Captioner* m, const int* ids, const int* lens, int B, int L
     return launch_mean_pool_normalize(m->te_x, lens, B, L, T, out, s);
 }
 
+// ---------------------------------------------------------------------------------------------- CLIP scorer
+// HF CLIPModel state-dict names (transformers models/clip/modeling_clip.py): separate q / k / v projections land in the fused
+// q|k|v rows (as the sentence encoder's), the patch conv has no bias, the projections are fp32 for the head kernel.
+int reg_clip_layer(Captioner* m, const std::string& p, VLayer& L, int D, int F) {
+    TRY(walloc(m, &L.w_qkv, (size_t)3 * D * D * m->esz));
+    TRY(walloc(m, (void**)&L.b_qkv, (size_t)3 * D * 4));
+    const char* nm[3] = {"q_proj", "k_proj", "v_proj"};
+    for (int j = 0; j < 3; ++j) {
+        add_slot(m, p + "self_attn." + nm[j] + ".weight", (char*)L.w_qkv + (size_t)j * D * D * m->esz, m->gdt, D, D);
+        add_slot(m, p + "self_attn." + nm[j] + ".bias", L.b_qkv + (size_t)j * D, CAP_DT_F32, 1, D);
+    }
+    TRY(reg_mat(m, p + "self_attn.out_proj.weight", &L.w_proj, D, D));
+    TRY(reg_f32(m, p + "self_attn.out_proj.bias", &L.b_proj, D));
+    TRY(reg_f32(m, p + "layer_norm1.weight", &L.ln1_g, D));
+    TRY(reg_f32(m, p + "layer_norm1.bias", &L.ln1_b, D));
+    TRY(reg_mat(m, p + "mlp.fc1.weight", &L.w_fc1, F, D));
+    TRY(reg_f32(m, p + "mlp.fc1.bias", &L.b_fc1, F));
+    TRY(reg_mat(m, p + "mlp.fc2.weight", &L.w_fc2, D, F));
+    TRY(reg_f32(m, p + "mlp.fc2.bias", &L.b_fc2, D));
+    TRY(reg_f32(m, p + "layer_norm2.weight", &L.ln2_g, D));
+    TRY(reg_f32(m, p + "layer_norm2.bias", &L.ln2_b, D));
+    return 0;
+}
+
+int build_clip(Captioner* m) {
+    const CapConfig& c = m->c;
+    const int D = c.v_hidden, T = c.t_hidden, P = c.embed_dim;
+    const std::string vm = "vision_model.", tm = "text_model.";
+    TRY(reg_f32(m, vm + "embeddings.class_embedding", &m->cls, D));
+    TRY(reg_f32(m, vm + "embeddings.position_embedding.weight", &m->vpos, (int64_t)m->NT * D));
+    TRY(reg_mat(m, vm + "embeddings.patch_embedding.weight", &m->w_patch, D, m->Kpatch, m->Kpad));
+    m->b_patch = nullptr;
+    TRY(reg_f32(m, vm + "pre_layrnorm.weight", &m->ln_pre_g, D));        // (sic: HF's name)
+    TRY(reg_f32(m, vm + "pre_layrnorm.bias", &m->ln_pre_b, D));
+    m->vl.resize(c.v_layers);
+    for (int i = 0; i < c.v_layers; ++i) TRY(reg_clip_layer(m, vm + "encoder.layers." + std::to_string(i) + ".", m->vl[i], D, c.v_mlp));
+    TRY(reg_f32(m, vm + "post_layernorm.weight", &m->post_g, D));
+    TRY(reg_f32(m, vm + "post_layernorm.bias", &m->post_b, D));
+    TRY(walloc(m, (void**)&m->c_vproj, (size_t)P * D * 4));
+    add_slot(m, "visual_projection.weight", m->c_vproj, CAP_DT_F32, P, D);
+    TRY(reg_f32(m, tm + "embeddings.token_embedding.weight", &m->c_tok, (int64_t)c.vocab * T));
+    TRY(reg_f32(m, tm + "embeddings.position_embedding.weight", &m->tpos, (int64_t)c.max_pos * T));
+    m->ctl.resize(c.t_layers);
+    for (int i = 0; i < c.t_layers; ++i) TRY(reg_clip_layer(m, tm + "encoder.layers." + std::to_string(i) + ".", m->ctl[i], T, c.t_ffn));
+    TRY(reg_f32(m, tm + "final_layer_norm.weight", &m->c_lnf_g, T));
+    TRY(reg_f32(m, tm + "final_layer_norm.bias", &m->c_lnf_b, T));
+    TRY(walloc(m, (void**)&m->c_tproj, (size_t)P * T * 4));
+    add_slot(m, "text_projection.weight", m->c_tproj, CAP_DT_F32, P, T);
+    TRY(reg_f32(m, "logit_scale", &m->c_logit, 1));
+    // arena: image rows [max_batch * tokens, .], text rows [max_batch * max_len, .]
+    const size_t Bm = c.max_batch, Mi = Bm * m->NT, Mt = Bm * c.max_len, e = m->esz;
+    TRY(dev_alloc(m, &m->patches, Bm * m->P * m->Kpad * e));
+    CAP_HIP_CHECK(hipMemset(m->patches, 0, Bm * m->P * m->Kpad * e));
+    TRY(dev_alloc(m, (void**)&m->X, Mi * D * 4));
+    TRY(dev_alloc(m, &m->ln, Mi * D * e));
+    TRY(dev_alloc(m, &m->qkv, Mi * 3 * D * 4));          // 4 bytes: the split mode's fp32 q|k|v where attention cannot take G8
+    TRY(dev_alloc(m, &m->ctx, Mi * D * e));
+    TRY(dev_alloc(m, &m->mlp, Mi * c.v_mlp * e));
+    TRY(dev_alloc(m, (void**)&m->c_x, Mt * T * 4));
+    TRY(dev_alloc(m, &m->c_ln, Mt * T * e));
+    TRY(dev_alloc(m, &m->c_qkv, Mt * 3 * T * 4));
+    TRY(dev_alloc(m, &m->c_ctx, Mt * T * e));
+    TRY(dev_alloc(m, &m->c_mlp, Mt * c.t_ffn * e));
+    if (!vit_adds_in_place(m->gdt)) {
+        TRY(dev_alloc(m, (void**)&m->delta, Mi * D * 4));
+        TRY(dev_alloc(m, (void**)&m->c_delta, Mt * T * 4));
+    }
+    return 0;
+}
+
+// The pre-LN blocks of one CLIP tower over the fp32 residual stream X [B * N, D] (as run_encoder's ViT loop); on return X holds
+// the last hidden states (the exact fp32 mode's last branch output folded in).  causal: the text tower's mask - the generic
+// attention kernel, which in the split mode reads fp32 q|k|v (the G8 kernel takes no mask).
+struct ClipTags { const char *ln, *qkv, *attn, *proj, *fc1, *fc2; };
+int run_clip_blocks(Captioner* m, hipStream_t s, const std::vector<VLayer>& layers, float* X, float* delta, void* ln, void* qkv, void* ctx,
+                    void* mlp, int B, int N, int D, int H, int F, float eps, bool causal, const ClipTags& tg) {
+    const int M = B * N, act = m->c.hidden_act == CAP_ACT_GELU ? 1 : 3;
+    const bool in_place = vit_adds_in_place(m->gdt);
+    const bool g8_attn = !causal && m->gdt == CAP_DT_G8 && vit_attention_takes_g8(N);
+    bool pending = false;
+    auto add_ln = [&](const float* g, const float* b, void* out_t) -> int {
+        ProfScope ps(m, s, tg.ln, 0, (double)M * D * ((pending ? 12 : 4) + (out_t ? m->esz : 4)));
+        if (pending) return launch_reduce_layernorm(m->gdt, delta, 1, nullptr, X, g, b, eps, out_t, nullptr, X, M, D, s, false, false);
+        return launch_layernorm(m->gdt, X, D, g, b, eps, out_t, nullptr, M, D, s);
+    };
+    for (const VLayer& L : layers) {
+        TRY(add_ln(L.ln1_g, L.ln1_b, ln));
+        TRY(gemm(m, s, tg.qkv, ln, D, L.w_qkv, D, qkv, 3 * D, L.b_qkv, nullptr, M, 3 * D, D, 0, (m->gdt == CAP_DT_G8 && !g8_attn) ? 1 : 0));
+        {
+            ProfScope ps(m, s, tg.attn, (causal ? 2.0 : 4.0) * B * H * (double)N * N * 64, (double)M * 4 * D * m->esz);
+            TRY(launch_vit_attention(g8_attn ? CAP_DT_G8 : m->dt, qkv, ctx, B, N, H, 0, s, D / H, causal ? 1 : 0, m->gdt));
+        }
+        if (in_place) TRY(gemm(m, s, tg.proj, ctx, D, L.w_proj, D, X, D, L.b_proj, X, M, D, D, 0, 1));
+        else TRY(gemm(m, s, tg.proj, ctx, D, L.w_proj, D, delta, D, L.b_proj, nullptr, M, D, D, 0, 1));
+        pending = !in_place;
+        TRY(add_ln(L.ln2_g, L.ln2_b, ln));
+        TRY(gemm(m, s, tg.fc1, ln, D, L.w_fc1, D, mlp, F, L.b_fc1, nullptr, M, F, D, act, 0));
+        if (in_place) TRY(gemm(m, s, tg.fc2, mlp, F, L.w_fc2, F, X, D, L.b_fc2, X, M, D, F, 0, 1));
+        else TRY(gemm(m, s, tg.fc2, mlp, F, L.w_fc2, F, delta, D, L.b_fc2, nullptr, M, D, F, 0, 1));
+    }
+    if (pending) {      // fold the last fc2 output into X; the head kernel applies the final LayerNorm to the pooled rows
+        ProfScope ps(m, s, tg.ln, 0, (double)M * D * 12);
+        const VLayer& L = layers.back();
+        TRY(launch_reduce_layernorm(m->gdt, delta, 1, nullptr, X, L.ln2_g, L.ln2_b, eps, nullptr, nullptr, X, M, D, s, false, false));
+    }
+    return 0;
+}
+
+int run_clip_images(Captioner* m, const void* pixels, int fmt, int B, float* out, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int D = c.v_hidden, NT = m->NT;
+    {
+        ProfScope ps(m, s, "clip_patchify", 0, (double)B * 3 * c.image_size * c.image_size * (fmt ? 1 : 4) + (double)B * m->P * m->Kpad * m->esz);
+        TRY(launch_patchify(m->gdt, pixels, fmt, B, c.image_size, c.patch_size, m->Kpad, m->patches, c.pix_mean, c.pix_std, s));
+    }
+    TRY(gemm(m, s, "clip_v_gemm_patch", m->patches, m->Kpad, m->w_patch, m->Kpad, m->X, D, nullptr, nullptr, B * m->P, D, m->Kpad, 0, 1,
+             EPI_PATCH, m->P, 0, 0, 0, m->vpos));
+    TRY(launch_cls_rows(m->cls, m->vpos, m->X, B, NT, D, s));
+    {
+        ProfScope ps(m, s, "clip_v_layernorm", 0, (double)B * NT * D * 8);
+        TRY(launch_layernorm(m->dt, m->X, D, m->ln_pre_g, m->ln_pre_b, c.v_eps, nullptr, m->X, B * NT, D, s));
+    }
+    static const ClipTags tg = {"clip_v_layernorm", "clip_v_gemm_qkv", "clip_v_attention", "clip_v_gemm_proj", "clip_v_gemm_fc1", "clip_v_gemm_fc2"};
+    TRY(run_clip_blocks(m, s, m->vl, m->X, (float*)m->delta, m->ln, m->qkv, m->ctx, m->mlp, B, NT, D, c.v_heads, c.v_mlp, c.v_eps, false, tg));
+    ProfScope ps(m, s, "clip_v_head", 2.0 * B * D * c.embed_dim, (double)B * D * 4 + (double)c.embed_dim * D * 4);
+    return launch_clip_head(m->X, NT, nullptr, m->post_g, m->post_b, c.v_eps, m->c_vproj, out, B, D, c.embed_dim, s);
+}
+
+int run_clip_text(Captioner* m, const int* ids, const int* lens, int B, int L, float* out, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden;
+    {
+        ProfScope ps(m, s, "clip_t_embed", 0, (double)B * L * T * 12);
+        TRY(launch_clip_embed_text(ids, L, m->c_tok, m->tpos, m->c_x, B * L, T, c.vocab, s));
+    }
+    static const ClipTags tg = {"clip_t_layernorm", "clip_t_gemm_qkv", "clip_t_attention", "clip_t_gemm_proj", "clip_t_gemm_fc1", "clip_t_gemm_fc2"};
+    TRY(run_clip_blocks(m, s, m->ctl, m->c_x, m->c_delta, m->c_ln, m->c_qkv, m->c_ctx, m->c_mlp, B, L, T, c.t_heads, c.t_ffn, c.t_eps, true, tg));
+    ProfScope ps(m, s, "clip_t_head", 2.0 * B * T * c.embed_dim, (double)B * T * 4 + (double)c.embed_dim * T * 4);
+    return launch_clip_head(m->c_x, L, lens, m->c_lnf_g, m->c_lnf_b, c.t_eps, m->c_tproj, out, B, T, c.embed_dim, s);
+}
+
 // ---------------------------------------------------------------------------------------------- encoder
 int run_encoder(Captioner* m, const void* pixels, int fmt, int B, float* out_embeds, hipStream_t s) {
     // BLIP: final LayerNorm = post_layernorm -> image_embeds (fp32 to the caller + T for the cross-K/V GEMM).
@@ -1712,7 +1859,8 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
         cap_set_error("cap_create: CapConfig size mismatch (caller %d, library %d)", cfg->struct_size, (int)sizeof(CapConfig));
         return -1;
     }
-    if (cfg->arch != CAP_ARCH_BLIP && cfg->arch != CAP_ARCH_COCA && cfg->arch != CAP_ARCH_MINILM && cfg->arch != CAP_ARCH_BLIP2) {
+    if (cfg->arch != CAP_ARCH_BLIP && cfg->arch != CAP_ARCH_COCA && cfg->arch != CAP_ARCH_MINILM && cfg->arch != CAP_ARCH_BLIP2 &&
+        cfg->arch != CAP_ARCH_CLIP) {
         cap_set_error("cap_create: unknown arch %d", cfg->arch);
         return -1;
     }
@@ -1732,6 +1880,20 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
             cfg->max_len > 512 || cfg->vocab < 1) {
             cap_set_error("cap_create: sentence encoder needs head_dim 32 or 64, widths multiple of 64 (hidden <= 1024), "
                           "1 <= max_len <= min(max_pos, 512)");
+            return -1;
+        }
+    } else if (cfg->arch == CAP_ARCH_CLIP) {
+        if (cfg->v_heads < 1 || cfg->t_heads < 1 || cfg->v_hidden != cfg->v_heads * 64 || cfg->t_hidden != cfg->t_heads * 64 ||
+            cfg->v_hidden > 1024 || cfg->t_hidden > 1024 || cfg->v_mlp % 64 || cfg->t_ffn % 64 || cfg->v_mlp < 64 || cfg->t_ffn < 64 ||
+            cfg->v_layers < 1 || cfg->t_layers < 1 || cfg->patch_size < 1 || cfg->image_size % cfg->patch_size ||
+            cfg->embed_dim < 1 || cfg->embed_dim > 1024 || cfg->vocab < 1 || cfg->max_batch < 1 || cfg->max_len < 1 ||
+            cfg->max_len > cfg->max_pos) {
+            cap_set_error("cap_create: CLIP needs head_dim 64 in both towers (widths <= 1024), MLP widths multiple of 64, "
+                          "1 <= embed_dim <= 1024 and 1 <= max_len <= max_pos");
+            return -1;
+        }
+        if (cfg->hidden_act != CAP_ACT_QUICK_GELU && cfg->hidden_act != CAP_ACT_GELU) {
+            cap_set_error("cap_create: CLIP hidden_act %d is neither CAP_ACT_QUICK_GELU (0) nor CAP_ACT_GELU (1)", cfg->hidden_act);
             return -1;
         }
     } else if (cfg->arch == CAP_ARCH_BLIP2) {
@@ -1808,6 +1970,7 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
     m->Kpad = (m->Kpatch + 63) / 64 * 64;
     const int built = text_only ? (build_minilm(m) != 0)
                       : cfg->arch == CAP_ARCH_BLIP2 ? (build_blip2(m) != 0)
+                      : cfg->arch == CAP_ARCH_CLIP ? (build_clip(m) != 0)
                       : cfg->arch == CAP_ARCH_COCA ? (build_coca(m) != 0 || build_arena_coca(m) != 0)
                                                    : (build_blip(m) != 0 || build_arena(m) != 0);
     if (built) {
@@ -1953,6 +2116,47 @@ static int check_call(Captioner* m, int B, int K, int Lm, int fmt) {
     }
     if (fmt != CAP_PIX_F32_NCHW && fmt != CAP_PIX_U8_NHWC) { cap_set_error("unknown pixel format %d", fmt); return -1; }
     if (m->c.arch == CAP_ARCH_MINILM) { cap_set_error("this handle is a sentence encoder: use cap_embed_text"); return -1; }
+    if (m->c.arch == CAP_ARCH_CLIP) { cap_set_error("this handle is a CLIP scorer: use cap_clip_embed_images / cap_clip_embed_text"); return -1; }
+    return 0;
+}
+
+static int check_clip(Captioner* m, const char* fn) {
+    if (!m) { cap_set_error("%s: null handle", fn); return -1; }
+    if (m->c.arch != CAP_ARCH_CLIP) { cap_set_error("%s: the handle is not a CLIP scorer (CAP_ARCH_CLIP)", fn); return -1; }
+    return cap_finalize_weights((CapHandle)m) != 0 ? -1 : 0;
+}
+
+int cap_clip_embed_images(CapHandle h, const void* pixels, int pixel_fmt, int B, float* out, void* stream) {
+    Captioner* m = (Captioner*)h;
+    TRY(check_clip(m, "cap_clip_embed_images"));
+    if (!pixels || !out) { cap_set_error("cap_clip_embed_images: null buffer"); return -1; }
+    if (B < 1 || B > m->c.max_batch) { cap_set_error("cap_clip_embed_images: B=%d exceeds the handle's capacity (%d)", B, m->c.max_batch); return -1; }
+    if (pixel_fmt != CAP_PIX_F32_NCHW && pixel_fmt != CAP_PIX_U8_NHWC) { cap_set_error("unknown pixel format %d", pixel_fmt); return -1; }
+    return run_clip_images(m, pixels, pixel_fmt, B, out, (hipStream_t)stream);
+}
+
+int cap_clip_embed_text(CapHandle h, const int32_t* ids, const int32_t* lens, int B, int L, float* out, void* stream) {
+    Captioner* m = (Captioner*)h;
+    TRY(check_clip(m, "cap_clip_embed_text"));
+    if (!ids || !lens || !out) { cap_set_error("cap_clip_embed_text: null buffer"); return -1; }
+    if (B < 1 || B > m->c.max_batch || L < 1 || L > m->c.max_len) {
+        cap_set_error("cap_clip_embed_text: B=%d L=%d exceeds the handle's capacity (%d, %d)", B, L, m->c.max_batch, m->c.max_len);
+        return -1;
+    }
+    return run_clip_text(m, ids, lens, B, L, out, (hipStream_t)stream);
+}
+
+int cap_clip_logits(const float* img, const float* txt, int Ni, int Nt, int paired, float logit_scale, float* out, int embed_dim,
+                    void* stream) {
+    if (!img || !txt || !out) { cap_set_error("cap_clip_logits: null buffer"); return -1; }
+    return launch_clip_logits(img, txt, Ni, Nt, embed_dim, paired, logit_scale, out, (hipStream_t)stream);
+}
+
+int cap_clip_logit_scale(CapHandle h, float* out) {
+    Captioner* m = (Captioner*)h;
+    if (!out) { cap_set_error("cap_clip_logit_scale: null output"); return -1; }
+    TRY(check_clip(m, "cap_clip_logit_scale"));
+    CAP_HIP_CHECK(hipMemcpy(out, m->c_logit, sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 

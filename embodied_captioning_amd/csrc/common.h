@@ -148,6 +148,9 @@ __device__ __forceinline__ float gelu_erf_fast(float x) {
     const float e = 1.0f - p * t * __expf(-z * z);      // erf(|x|/sqrt2)
     return 0.5f * x * (1.0f + copysignf(e, x));
 }
+// quick GELU, x * sigmoid(1.702 x) (HF ACT2FN["quick_gelu"]: the activation of OpenAI's CLIP towers) - activation 3 of the
+// GEMM epilogues.  expf / IEEE divide in every operand type: the fp32 mode is held to fp64 HF goldens
+__device__ __forceinline__ float quick_gelu(float x) { return x / (1.0f + expf(-1.702f * x)); }
 template <typename T> __device__ __forceinline__ float gelu_for(float x);
 template <> __device__ __forceinline__ float gelu_for<float>(float x) { return gelu_erf(x); }
 template <> __device__ __forceinline__ float gelu_for<__bf16>(float x) { return gelu_erf_fast(x); }

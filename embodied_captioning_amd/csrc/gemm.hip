@@ -37,6 +37,9 @@ __device__ __forceinline__ void epi_store4(const GemmParams& p, int row, int col
     } else if (EPI != EPI_PARTIAL && p.gelu == 2) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], 0.f);
+    } else if (EPI != EPI_PARTIAL && p.gelu == 3) {   // quick GELU (CLIP)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = quick_gelu(v[i]);
     }
     size_t o; void* base = p.C;
     if constexpr (EPI == EPI_PARTIAL) {          // split-K slice z: raw fp32 partial sums, reduced by the consumer

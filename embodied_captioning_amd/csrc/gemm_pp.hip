@@ -84,7 +84,7 @@ template <int I, int N, typename F> __device__ __forceinline__ void static_for(F
 // cycle of it is matrix-pipe idle time and the instruction count per value matters:
 //   * two strips per wave slot, software pipelined: piece n + 1 is computed and written while piece n is read back and stored
 //     (waves w and w + 4 run their epilogues in different steps and share a slot);
-//   * ACT is a template parameter (0 none, 1 GELU, 2 ReLU; -1 = read p.gelu per piece, edge tiles only), interior tiles
+//   * ACT is a template parameter (0 none, 1 GELU, 2 ReLU, 3 quick GELU; -1 = read p.gelu per piece, edge tiles only), interior tiles
 //     (FULL) store unguarded through two running pointers, clamped groups are counted in a register and added to the
 //     translation unit's counter once per tile;
 //   * a G8 output piece is the strip row image [8 hi | 8 lo] per 8 columns: two 8-byte writes per four values.
@@ -113,6 +113,9 @@ __device__ __forceinline__ void pp_epilogue_body(const GemmParams& p, const f32x
                 } else if (act == 2) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                } else if (act == 3) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = quick_gelu(v[e]);
                 }
                 bf16x4 w;
 #pragma unroll
@@ -155,6 +158,9 @@ __device__ __forceinline__ void pp_epilogue_body(const GemmParams& p, const f32x
             } else if (act == 2) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+            } else if (act == 3) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = quick_gelu(v[e]);
             }
             if constexpr (F32OUT) {
                 *(f32x4*)(st + (jj * 16 + 4 * kg) * 4) = v;
@@ -327,7 +333,8 @@ __device__ __forceinline__ void pp_epilogue(const GemmParams& p, const f32x4 (&a
     if (row0 + MI * 16 <= p.M && col0 + NI * 16 <= p.N) {
         if (act == 0) pp_epilogue_body<T, OUT_F32, EPI, MI, NI, 0, true, RESID>(p, acc, biasv, strip2, row0, col0, lane);
         else if (act == 1) pp_epilogue_body<T, OUT_F32, EPI, MI, NI, 1, true, RESID>(p, acc, biasv, strip2, row0, col0, lane);
-        else pp_epilogue_body<T, OUT_F32, EPI, MI, NI, 2, true, RESID>(p, acc, biasv, strip2, row0, col0, lane);
+        else if (act == 2) pp_epilogue_body<T, OUT_F32, EPI, MI, NI, 2, true, RESID>(p, acc, biasv, strip2, row0, col0, lane);
+        else pp_epilogue_body<T, OUT_F32, EPI, MI, NI, 3, true, RESID>(p, acc, biasv, strip2, row0, col0, lane);
     } else {
         pp_epilogue_body<T, OUT_F32, EPI, MI, NI, -1, false, RESID>(p, acc, biasv, strip2, row0, col0, lane);
     }

@@ -144,6 +144,9 @@ __device__ __forceinline__ void big2_epilogue(const GemmParams& p, const f32x4 (
                 } else if (act == 2) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                } else if (act == 3) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = quick_gelu(v[e]);
                 }
                 if constexpr (F32OUT) {
                     *(f32x4*)(strip + r16 * 144 + (jj * 16 + 4 * kg) * 4) = v;

@@ -143,6 +143,16 @@ int launch_crop_resize_u8(const uint8_t* frame, int H, int W, int bgr, const int
                           const int* vb, const int* vk, int KV, int n, int S, uint8_t* out, hipStream_t s,
                           const long long* frames = nullptr);     // frames int64 [n, 3] = (byte offset in `frame`, H, W) of box b's own frame
 
+// ---- clip.hip ----------------------------------------------------------------------------------
+// CLIP text embeddings: x fp32 [M, D] = tok[ids[r]] + pos[r % L] (ids clamped to [0, V))
+int launch_clip_embed_text(const int* ids, int L, const float* tok, const float* pos, float* x, int M, int D, int V, hipStream_t s);
+// pooled head: row b * rows_per (+ lens[b] - 1 when lens is given) of x fp32 -> LayerNorm -> . W^T (fp32 [P, D]) -> L2 normalised
+// out fp32 [B, P]; one workgroup per row, sums in an order that does not depend on B
+int launch_clip_head(const float* x, int rows_per, const int* lens, const float* gamma, const float* beta, float eps, const float* W,
+                     float* out, int B, int D, int P, hipStream_t s);
+// exp(logit_scale) * img . txt^T: paired -> out [Ni] (row i against row i), else out [Ni, Nt]
+int launch_clip_logits(const float* img, const float* txt, int Ni, int Nt, int P, int paired, float logit_scale, float* out, hipStream_t s);
+
 // ---- beam.hip --------------------------------------------------------------------------------
 size_t beam_state_bytes(int B, int K, int max_len);
 int beam_candidates_only(void* state, const float* logits, int ld, int V, int B, int K, int mode, int eos_mask, float* out_val,

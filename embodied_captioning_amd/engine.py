@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import _native as N
-from .config import Blip2Arch, BlipArch, CocaArch, MiniLMArch
+from .config import Blip2Arch, BlipArch, ClipArch, CocaArch, MiniLMArch
 
 logger = logging.getLogger(__name__)
 
@@ -562,4 +562,119 @@ class TextEncoderEngine:
         with torch.cuda.device(self.device):
             N.check(self.lib.cap_embed_text(self._h, C.c_void_p(ids.data_ptr()), C.c_void_p(lens.data_ptr()), B, L,
                                             C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(self.device))), "cap_embed_text")
+        return out
+
+
+class ClipEngine:
+    """CLIP scorer replica (CAP_ARCH_CLIP handle): both towers and the image-caption logits of HF `CLIPModel`, as the
+    reference's `--method clip` uses it (experimenting_env/captioner/pseudocaptioner.py:39-46, :352-357).  Embeddings come
+    back L2-normalised, fp32 [B, projection_dim]; tokenisation stays on the host (captioner/clip_scorer.py)."""
+
+    _skip_kv16_guard = True      # no cross-attention cache
+
+    def __init__(self, arch: ClipArch, dtype: str = "f32s", max_batch: int = 256, max_len: Optional[int] = None,
+                 device: str | torch.device = "cuda:0", share_weights_with: "ClipEngine | None" = None):
+        if not torch.cuda.is_available():
+            raise N.CaptionerHipError("ClipEngine needs a GPU; there is no CPU fallback in the product path")
+        self.lib = N.load_library()
+        self.arch, self.dtype, self.device = arch, dtype, torch.device(device)
+        self.max_batch, self.max_len = max_batch, max_len or arch.max_pos
+        cfg = N.CapConfig()
+        cfg.struct_size = C.sizeof(N.CapConfig)
+        cfg.arch = N.CAP_ARCH_CLIP
+        cfg.compute_dtype = _DTYPES[dtype]
+        cfg.image_size, cfg.patch_size = arch.image_size, arch.patch_size
+        cfg.v_hidden, cfg.v_layers, cfg.v_heads, cfg.v_mlp, cfg.v_eps = arch.v_hidden, arch.v_layers, arch.v_heads, arch.v_mlp, arch.eps
+        cfg.t_hidden, cfg.t_layers, cfg.t_heads, cfg.t_ffn = arch.t_hidden, arch.t_layers, arch.t_heads, arch.t_ffn
+        cfg.vocab, cfg.max_pos, cfg.t_eps = arch.vocab, arch.max_pos, arch.eps
+        cfg.bos, cfg.eos, cfg.pad = arch.bos_token_id, arch.eos_token_id, arch.pad_token_id
+        cfg.embed_dim = arch.projection_dim
+        cfg.hidden_act = N.CAP_ACT_GELU if arch.hidden_act == "gelu" else N.CAP_ACT_QUICK_GELU
+        cfg.max_batch, cfg.max_beams, cfg.max_len = max_batch, 1, self.max_len
+        for i in range(3):
+            cfg.pix_mean[i] = OPENAI_CLIP_MEAN[i]
+            cfg.pix_std[i] = OPENAI_CLIP_STD[i]
+        self._h = C.c_void_p()
+        self.shares_weights = share_weights_with is not None
+        self.logit_scale = share_weights_with.logit_scale if share_weights_with is not None else None
+        with torch.cuda.device(self.device):
+            if share_weights_with is not None:
+                N.check(self.lib.cap_create_shared(C.byref(cfg), share_weights_with._h, C.byref(self._h)), "cap_create_shared")
+            else:
+                N.check(self.lib.cap_create(C.byref(cfg), C.byref(self._h)), "cap_create")
+
+    close = CaptionerEngine.close
+    __del__ = CaptionerEngine.__del__
+    device_bytes = CaptionerEngine.device_bytes
+    saturations = CaptionerEngine.saturations
+    profile = CaptionerEngine.profile
+    profile_report = CaptionerEngine.profile_report
+    _pixels = CaptionerEngine._pixels
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> Dict[str, object]:
+        """HF `CLIPModel` names (wrapper prefixes dropped, `*.position_ids` buffers and the absent patch bias ignored)."""
+        from .weights import strip_wrapper_prefixes
+        sd = {k: v for k, v in strip_wrapper_prefixes(sd).items()
+              if not k.endswith("position_ids") and k != "vision_model.embeddings.patch_embedding.bias"}
+        self.is_coca = False
+        rep = CaptionerEngine.load_state_dict(self, sd, strict)
+        v = C.c_float()
+        with torch.cuda.device(self.device):
+            if self.lib.cap_clip_logit_scale(self._h, C.byref(v)) == 0:
+                self.logit_scale = float(v.value)
+        return rep
+
+    def embed_images(self, pixels: torch.Tensor) -> torch.Tensor:
+        """uint8 [B, S, S, 3] RGB or normalised fp32 [B, 3, S, S] -> fp32 [B, projection_dim] (device), L2-normalised."""
+        pixels, fmt = self._pixels(pixels)
+        B = pixels.shape[0]
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"batch of {B} images outside 1..{self.max_batch} (the engine's max_batch)")
+        out = torch.empty((B, self.arch.projection_dim), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.cap_clip_embed_images(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, C.c_void_p(out.data_ptr()),
+                                                   C.c_void_p(_stream_ptr(self.device))), "cap_clip_embed_images")
+        return out
+
+    def embed_text(self, ids: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """ids int [B, L] (right padded; anything after the caption), lens int [B] = tokens up to and including the pooled EOT
+        -> fp32 [B, projection_dim] (device), L2-normalised."""
+        if ids.dim() != 2 or lens.shape != (ids.shape[0],):
+            raise ValueError(f"ids must be [B, L] and lens [B], got {tuple(ids.shape)} / {tuple(lens.shape)}")
+        B, L = ids.shape
+        if not 1 <= L <= self.max_len:
+            raise ValueError(f"{L} tokens per caption outside 1..{self.max_len} (the engine's max_len)")
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"batch of {B} captions outside 1..{self.max_batch} (the engine's max_batch)")
+        if not ids.is_cuda and not lens.is_cuda:      # host tensors: validated here; device tensors are clamped by the kernels
+            if int(lens.max()) > L or int(lens.min()) < 1:
+                raise ValueError("lens must be within 1..L")
+            if int(ids.max()) >= self.arch.vocab or int(ids.min()) < 0:
+                raise ValueError("token id outside the vocabulary")
+        ids = ids.to(self.device, torch.int32).contiguous()
+        lens = lens.to(self.device, torch.int32).contiguous()
+        out = torch.empty((B, self.arch.projection_dim), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.cap_clip_embed_text(self._h, C.c_void_p(ids.data_ptr()), C.c_void_p(lens.data_ptr()), B, L,
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(self.device))), "cap_clip_embed_text")
+        return out
+
+    def logits(self, img: torch.Tensor, txt: torch.Tensor, paired: bool = True) -> torch.Tensor:
+        """exp(logit_scale) * img . txt^T of normalised embeddings: paired -> [n] (image i against caption i), else
+        [Ni, Nt] (HF's logits_per_image)."""
+        if self.logit_scale is None:
+            raise N.CaptionerHipError("no weights loaded: logit_scale unknown")
+        P = self.arch.projection_dim
+        if img.dim() != 2 or txt.dim() != 2 or img.shape[1] != P or txt.shape[1] != P:
+            raise ValueError(f"embeddings must be [n, {P}], got {tuple(img.shape)} / {tuple(txt.shape)}")
+        if paired and img.shape[0] != txt.shape[0]:
+            raise ValueError(f"paired logits need as many images as captions ({img.shape[0]} / {txt.shape[0]})")
+        img = img.to(self.device, torch.float32).contiguous()
+        txt = txt.to(self.device, torch.float32).contiguous()
+        Ni, Nt = img.shape[0], txt.shape[0]
+        out = torch.empty((Ni,) if paired else (Ni, Nt), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.cap_clip_logits(C.c_void_p(img.data_ptr()), C.c_void_p(txt.data_ptr()), Ni, Nt, int(bool(paired)),
+                                             C.c_float(self.logit_scale), C.c_void_p(out.data_ptr()), P,
+                                             C.c_void_p(_stream_ptr(self.device))), "cap_clip_logits")
         return out

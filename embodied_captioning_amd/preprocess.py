@@ -63,6 +63,30 @@ def shorter_side_geometry(w: int, h: int, size: int) -> Tuple[int, int, int, int
     return nw, nh, (nw - size) // 2, (nh - size) // 2
 
 
+def hf_shortest_edge_geometry(w: int, h: int, size: int) -> Tuple[int, int, int, int]:
+    """HF `CLIPImageProcessorPil`: resize the shortest edge to `size` with the long side TRUNCATED, int(size * long / short)
+    (image_transforms.get_resize_output_image_size), then a centre crop at ((resized - size) // 2).  Not
+    `shorter_side_geometry`, which rounds the long side as open_clip does.  -> (resized width, resized height, left, top)."""
+    if w <= h:
+        nw, nh = size, int(size * h / w)
+    else:
+        nw, nh = int(size * w / h), size
+    return nw, nh, (nw - size) // 2, (nh - size) // 2
+
+
+GEOMETRIES = {"open_clip": shorter_side_geometry, "hf": hf_shortest_edge_geometry}
+
+
+def _geometry(ws, hs, size: int, center_crop: bool, geometry: str) -> np.ndarray:
+    if geometry not in GEOMETRIES:
+        raise ValueError(f"geometry must be one of {sorted(GEOMETRIES)}, got {geometry!r}")
+    n = len(ws)
+    if not center_crop:
+        return np.tile(np.array([size, size, 0, 0], dtype=np.int64), (n, 1))
+    f = GEOMETRIES[geometry]
+    return np.array([f(int(w), int(h), size) for w, h in zip(np.asarray(ws).tolist(), np.asarray(hs).tolist())], dtype=np.int64).reshape(n, 4)
+
+
 def _ksize(in_size: np.ndarray, out_size: np.ndarray) -> int:
     """Widest tap row any of the boxes needs: Pillow's ksize = 2 ceil(support) + 1, support = 2 max(in / out, 1)."""
     scale = np.maximum(in_size.astype(np.float64) / out_size.astype(np.float64), 1.0)
@@ -70,7 +94,8 @@ def _ksize(in_size: np.ndarray, out_size: np.ndarray) -> int:
 
 
 def crop_resize_u8(frame, rects: Sequence[Sequence[int]], size: int, bgr: bool = False,
-                   device: str | torch.device = "cuda:0", center_crop: bool = False, tables: str = "device") -> torch.Tensor:
+                   device: str | torch.device = "cuda:0", center_crop: bool = False, tables: str = "device",
+                   geometry: str = "open_clip") -> torch.Tensor:
     """frame uint8 [H, W, 3] (numpy or torch, host or device) + integer rectangles (x1, y1, x2, y2) (parts outside the
     frame read as zeros, as Image.crop pads) -> uint8 [n, size, size, 3] RGB on the device, equal to
     ``Image.fromarray(rgb).crop(r).resize((size, size), BICUBIC)`` for every rectangle; with `center_crop` to the
@@ -97,10 +122,7 @@ def crop_resize_u8(frame, rects: Sequence[Sequence[int]], size: int, bgr: bool =
     # a rectangle may leave the frame: Image.crop pads with zeros and so does the kernel (the reference's expand_box clamps
     # x to the frame height and y to its width, so this happens on non-square frames)
     ws, hs = x2 - x1, y2 - y1
-    if center_crop:
-        geom = np.array([shorter_side_geometry(int(w), int(h), size) for w, h in zip(ws.tolist(), hs.tolist())], dtype=np.int64)
-    else:
-        geom = np.tile(np.array([size, size, 0, 0], dtype=np.int64), (n, 1))
+    geom = _geometry(ws, hs, size, center_crop, geometry)
     KH, KV = _ksize(ws, geom[:, 0]), _ksize(hs, geom[:, 1])
     stream = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)   # noqa: E731
     with torch.cuda.device(dev):
@@ -139,12 +161,14 @@ def crop_resize_u8(frame, rects: Sequence[Sequence[int]], size: int, bgr: bool =
 
 
 def crop_resize_u8_frames(frames: Sequence[np.ndarray], rects_per_frame: Sequence[Sequence[Sequence[int]]], size: int, bgr: bool = False,
-                          device: str | torch.device = "cuda:0", center_crop: bool = False) -> torch.Tensor:
+                          device: str | torch.device = "cuda:0", center_crop: bool = False, geometry: str = "open_clip") -> torch.Tensor:
     """Boxes of SEVERAL frames (uint8 [H_f, W_f, 3] host arrays, any sizes) in one go: -> uint8 [n_boxes, size, size, 3] RGB on the
     device, frame-major in box order, every box equal to ``Image.fromarray(rgb).crop(r).resize((size, size), BICUBIC)`` (or the
     shorter-side + centre-crop form).  Only each box's in-frame pixels travel: they are copied into ONE pinned buffer (a box that
     leaves its frame keeps its offset inside the copied patch, the kernel pads with zeros as `Image.crop` does), uploaded once, and
-    the whole set is two launches (`cap_crop_resize_u8_frames`).  A 1280 x 1280 frame with three boxes sends ~0.5 MB instead of 4.9."""
+    the whole set is two launches (`cap_crop_resize_u8_frames`).  A 1280 x 1280 frame with three boxes sends ~0.5 MB instead of 4.9.
+    geometry (with `center_crop`): "open_clip" (default, `shorter_side_geometry`) or "hf" (`hf_shortest_edge_geometry`: HF's
+    CLIPImageProcessorPil)."""
     if not torch.cuda.is_available():
         raise N.CaptionerHipError("crop_resize_u8_frames needs a GPU; there is no CPU fallback in the product path")
     lib = N.load_library()
@@ -170,7 +194,7 @@ def crop_resize_u8_frames(frames: Sequence[np.ndarray], rects_per_frame: Sequenc
     if n == 0:
         return torch.empty((0, size, size, 3), dtype=torch.uint8, device=dev)
     groups = _byte_groups(hw)
-    outs = [_resize_patches(patches[i:j], rects[i:j], hw[i:j], size, bgr, dev, center_crop, lib) for i, j in groups]
+    outs = [_resize_patches(patches[i:j], rects[i:j], hw[i:j], size, bgr, dev, center_crop, lib, geometry) for i, j in groups]
     return outs[0] if len(outs) == 1 else torch.cat(outs)
 
 
@@ -190,7 +214,7 @@ def _byte_groups(hw):
     return groups
 
 
-def _resize_patches(patches, rects, hw, size, bgr, dev, center_crop, lib) -> torch.Tensor:
+def _resize_patches(patches, rects, hw, size, bgr, dev, center_crop, lib, geometry="open_clip") -> torch.Tensor:
     n = len(patches)
     hw = np.asarray(hw, dtype=np.int64)
     rects = np.asarray(rects, dtype=np.int64)
@@ -201,10 +225,7 @@ def _resize_patches(patches, rects, hw, size, bgr, dev, center_crop, lib) -> tor
     for i, a in enumerate(patches):
         pk[offs[i]:offs[i + 1]].reshape(a.shape)[...] = a
     ws, hs = rects[:, 2] - rects[:, 0], rects[:, 3] - rects[:, 1]
-    if center_crop:
-        geom = np.array([shorter_side_geometry(int(w), int(h), size) for w, h in zip(ws.tolist(), hs.tolist())], dtype=np.int64)
-    else:
-        geom = np.tile(np.array([size, size, 0, 0], dtype=np.int64), (n, 1))
+    geom = _geometry(ws, hs, size, center_crop, geometry)
     KH, KV = _ksize(ws, geom[:, 0]), _ksize(hs, geom[:, 1])
     ftab = np.stack([offs[:-1], hw[:, 0], hw[:, 1]], axis=1).astype(np.int64)
     stream = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)   # noqa: E731
@@ -228,7 +249,8 @@ def _resize_patches(patches, rects, hw, size, bgr, dev, center_crop, lib) -> tor
     return out
 
 
-def resize_u8_list(images: Sequence[np.ndarray], size: int, device: str | torch.device = "cuda:0", center_crop: bool = False) -> torch.Tensor:
+def resize_u8_list(images: Sequence[np.ndarray], size: int, device: str | torch.device = "cuda:0", center_crop: bool = False,
+                   geometry: str = "open_clip") -> torch.Tensor:
     """A list of uint8 RGB images [H_i, W_i, 3] of different sizes (the PIL crops `generate_batch` / `caption_batch` receive) ->
     uint8 [n, size, size, 3] on the device, every image equal to ``Image.fromarray(a).resize((size, size), BICUBIC)`` (or, with
     `center_crop`, to the shorter-side resize + centre crop of `shorter_side_geometry`): `crop_resize_u8_frames` with each image as
@@ -236,4 +258,5 @@ def resize_u8_list(images: Sequence[np.ndarray], size: int, device: str | torch.
     for i, a in enumerate(images):
         if a.ndim != 3 or a.shape[0] < 1 or a.shape[1] < 1:
             raise ValueError(f"image {i} must be uint8 [H, W, 3], got {a.dtype} {a.shape}")
-    return crop_resize_u8_frames(images, [[(0, 0, a.shape[1], a.shape[0])] for a in images], size, device=device, center_crop=center_crop)
+    return crop_resize_u8_frames(images, [[(0, 0, a.shape[1], a.shape[0])] for a in images], size, device=device, center_crop=center_crop,
+                                 geometry=geometry)

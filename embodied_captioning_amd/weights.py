@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Tuple
 import numpy as np
 import torch
 
-from .config import Blip2Arch, BlipArch, CocaArch, MiniLMArch
+from .config import Blip2Arch, BlipArch, ClipArch, CocaArch, MiniLMArch
 
 
 def blip_param_specs(a: BlipArch) -> List[Tuple[str, Tuple[int, ...], str, float]]:
@@ -205,6 +205,56 @@ def minilm_param_specs(a: MiniLMArch) -> List[Tuple[str, Tuple[int, ...], str, f
 
 def procedural_minilm_state_dict(arch: MiniLMArch, seed: int = 0) -> Dict[str, torch.Tensor]:
     return {name: torch.from_numpy(_draw(seed, name, shape, kind, scale)) for name, shape, kind, scale in minilm_param_specs(arch)}
+
+
+def clip_param_specs(a: ClipArch) -> List[Tuple[str, Tuple[int, ...], str, float]]:
+    """HF `CLIPModel` state-dict names (the `*.position_ids` buffers are not parameters and are left out)."""
+    s: List[Tuple[str, Tuple[int, ...], str, float]] = []
+
+    def tower(p, W, F, n):
+        for i in range(n):
+            q = f"{p}encoder.layers.{i}."
+            for nm in ("q_proj", "k_proj", "v_proj", "out_proj"):
+                s.append((q + f"self_attn.{nm}.weight", (W, W), "normal", 1.0 / np.sqrt(W)))
+                s.append((q + f"self_attn.{nm}.bias", (W,), "normal", 0.02))
+            s.append((q + "layer_norm1.weight", (W,), "gamma", 0.1))
+            s.append((q + "layer_norm1.bias", (W,), "normal", 0.05))
+            s.append((q + "mlp.fc1.weight", (F, W), "normal", 1.0 / np.sqrt(W)))
+            s.append((q + "mlp.fc1.bias", (F,), "normal", 0.02))
+            s.append((q + "mlp.fc2.weight", (W, F), "normal", 1.0 / np.sqrt(F)))
+            s.append((q + "mlp.fc2.bias", (W,), "normal", 0.02))
+            s.append((q + "layer_norm2.weight", (W,), "gamma", 0.1))
+            s.append((q + "layer_norm2.bias", (W,), "normal", 0.05))
+
+    D, T, Pd, ps = a.v_hidden, a.t_hidden, a.projection_dim, a.patch_size
+    vm, tm = "vision_model.", "text_model."
+    s.append((vm + "embeddings.class_embedding", (D,), "normal", 0.5))
+    s.append((vm + "embeddings.patch_embedding.weight", (D, 3, ps, ps), "normal", 1.0 / np.sqrt(3 * ps * ps)))
+    s.append((vm + "embeddings.position_embedding.weight", (a.n_tokens, D), "normal", 0.5))
+    s.append((vm + "pre_layrnorm.weight", (D,), "gamma", 0.1))
+    s.append((vm + "pre_layrnorm.bias", (D,), "normal", 0.05))
+    tower(vm, D, a.v_mlp, a.v_layers)
+    s.append((vm + "post_layernorm.weight", (D,), "gamma", 0.1))
+    s.append((vm + "post_layernorm.bias", (D,), "normal", 0.05))
+    s.append(("visual_projection.weight", (Pd, D), "normal", 1.0 / np.sqrt(D)))
+    s.append((tm + "embeddings.token_embedding.weight", (a.vocab, T), "normal", 0.5))
+    s.append((tm + "embeddings.position_embedding.weight", (a.max_pos, T), "normal", 0.2))
+    tower(tm, T, a.t_ffn, a.t_layers)
+    s.append((tm + "final_layer_norm.weight", (T,), "gamma", 0.1))
+    s.append((tm + "final_layer_norm.bias", (T,), "normal", 0.05))
+    s.append(("text_projection.weight", (Pd, T), "normal", 1.0 / np.sqrt(T)))
+    return s
+
+
+# CLIP's init value (log(1 / 0.07)); the procedural dicts use it so logits have the real model's scale
+CLIP_LOGIT_SCALE_INIT = 2.6592
+
+
+def procedural_clip_state_dict(arch: ClipArch, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded fp32 state dict with HF `CLIPModel` key names; `logit_scale` is CLIP's init value."""
+    sd = {name: torch.from_numpy(_draw(seed, name, shape, kind, scale)) for name, shape, kind, scale in clip_param_specs(arch)}
+    sd["logit_scale"] = torch.tensor(CLIP_LOGIT_SCALE_INIT, dtype=torch.float32)
+    return sd
 
 
 def blip2_param_specs(a: Blip2Arch) -> List[Tuple[str, Tuple[int, ...], str, float]]:
@@ -538,6 +588,25 @@ def load_hf_blip_checkpoint(model_dir: str) -> Tuple[BlipArch, Dict[str, torch.T
     pe = sd["vision_model.embeddings.position_embedding"]
     g = int(round((pe.shape[1] - 1) ** 0.5))
     arch.image_size = g * arch.patch_size
+    return arch, sd
+
+
+def load_hf_clip_checkpoint(model_dir: str) -> Tuple[ClipArch, Dict[str, torch.Tensor]]:
+    """HF `CLIPModel.save_pretrained` directory: config.json + model.safetensors | pytorch_model.bin.  Wrapper prefixes are
+    dropped and the `*.position_ids` buffers ignored by name; CLIP's patch conv has no bias, so a zero one is supplied (what a
+    consumer of the key reads; the device path runs the conv without one)."""
+    arch = ClipArch.from_hf_config(model_dir)
+    for fn in ("model.safetensors", "pytorch_model.bin"):
+        p = os.path.join(model_dir, fn)
+        if os.path.exists(p):
+            sd = strip_wrapper_prefixes(load_state_dict_file(p))
+            break
+    else:
+        raise RuntimeError(f"no model.safetensors / pytorch_model.bin under {model_dir}")
+    sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
+    w = sd.get("vision_model.embeddings.patch_embedding.weight")
+    if w is not None and "vision_model.embeddings.patch_embedding.bias" not in sd:
+        sd["vision_model.embeddings.patch_embedding.bias"] = torch.zeros(w.shape[0], dtype=torch.float32)
     return arch, sd
 
 

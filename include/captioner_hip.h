@@ -29,6 +29,9 @@
  *                                                                                      cap_load_weight), CapConfig.compute_dtype,
  *                                                                                      CapConfig.cross_kv_fp32 (host side:
  *                                                                                      weights.merge_peft_lora)
+ *   CLIP pseudo-caption experimenting_env/captioner/pseudocaptioner.py:39-46 (CLIPModel.from_pretrained),   cap_clip_embed_images,
+ *   scores              :352-357 `model(**processor(text=[caption], images=crop)).logits_per_image`  cap_clip_embed_text,
+ *                       (one HF call per (crop, caption) pair; here: batches of pairs, CAP_ARCH_CLIP)    cap_clip_logits
  *   device move/free    predictor_utils.py:187 `.to(...)`; object lifetime            cap_destroy
  *   errors              Python exceptions (utils_captioner.py:6, factory.py:231,309)  int return codes + cap_last_error
  *
@@ -49,7 +52,9 @@ extern "C" {
 
 typedef struct CapHandle_s* CapHandle;
 
-enum { CAP_ARCH_BLIP = 0, CAP_ARCH_COCA = 1, CAP_ARCH_MINILM = 2, CAP_ARCH_BLIP2 = 3 };
+enum { CAP_ARCH_BLIP = 0, CAP_ARCH_COCA = 1, CAP_ARCH_MINILM = 2, CAP_ARCH_BLIP2 = 3, CAP_ARCH_CLIP = 4 };
+/* activation of the MLPs (CapConfig.hidden_act, CAP_ARCH_CLIP): HF ACT2FN["quick_gelu"] x * sigmoid(1.702 x) (OpenAI CLIP) or exact GELU */
+enum { CAP_ACT_QUICK_GELU = 0, CAP_ACT_GELU = 1 };
 /* Arithmetic of the GEMM / attention operands (accumulation is fp32 in every mode):
  *   CAP_F32        fp32 operands, exact fp32 products on the fp32 MFMA pipe (v_mfma_f32_32x32x2_f32)
  *   CAP_BF16       bf16 operands on the bf16 MFMA pipe - fastest, but not token-identical to an fp32 reference
@@ -102,6 +107,8 @@ typedef struct CapConfig {
      * activation path with fp16 outlier columns is not restated: weights-only, "W8A16").  lm_head stays bf16 (HF does not
      * convert it either).  Needs OPT widths the int8 weight stream takes (opt-2.7b's 2560 / 10240 are). */
     int32_t weight_int8;
+    /* CAP_ARCH_CLIP only: CAP_ACT_QUICK_GELU (0, the OpenAI checkpoints) or CAP_ACT_GELU (1) in both towers' MLPs. */
+    int32_t hidden_act;
 } CapConfig;
 
 const char* cap_last_error(void);
@@ -219,6 +226,26 @@ int cap_generate_groups(CapHandle h, const void* pixels, int pixel_fmt, int B, i
  * -> out fp32 [B, t_hidden]: mean of the last hidden states over the valid tokens, L2-normalised
  * (sentence-transformers Pooling(mean) + Normalize).  All pointers are device pointers. */
 int cap_embed_text(CapHandle h, const int32_t* ids, const int32_t* lens, int B, int L, float* out, void* stream);
+
+/* CLIP scorer (CAP_ARCH_CLIP handle; weights by HF CLIPModel names: vision_model.*, text_model.*, visual_projection.weight,
+ * text_projection.weight, logit_scale).  The handle reads v_* (image tower), t_* (text tower), vocab, max_pos, embed_dim
+ * (projection width), eos, max_batch and max_len (tokens per caption, <= max_pos).  All pointers are device pointers.
+ *   cap_clip_embed_images: B frames in pixel_fmt (normalised with pix_mean / pix_std for CAP_PIX_U8_NHWC) -> out fp32
+ *     [B, embed_dim] = normalize(visual_projection(post_layernorm(CLS row)))  (HF get_image_features, then L2-normalised)
+ *   cap_clip_embed_text: ids int32 [B, L] (right padded, any ids after the caption), lens int32 [B] = tokens up to and
+ *     including the pooled EOT (1 <= lens[b] <= L <= max_len) -> out fp32 [B, embed_dim] = normalize(text_projection(
+ *     final_layer_norm(row lens[b] - 1))).  The mask is causal: no row at or before the EOT sees a pad, so no padding mask
+ *     exists and the result does not depend on the ids after lens[b] (nor on L).
+ *   cap_clip_logits: img [Ni, embed_dim], txt [Nt, embed_dim] (normalised embeddings) -> out = exp(logit_scale) * img . txt^T:
+ *     paired = 1 -> out [Ni] (image i against caption i, Ni == Nt: what the reference scores), paired = 0 -> out [Ni, Nt]
+ *     (HF's logits_per_image).  Needs no handle.
+ *   cap_clip_logit_scale: the checkpoint's `logit_scale` tensor (before exp) -> *out (synchronises).
+ * Other architectures' handles refuse the first two; a CLIP handle refuses cap_encode / cap_generate / cap_embed_text. */
+int cap_clip_embed_images(CapHandle h, const void* pixels, int pixel_fmt, int B, float* out, void* stream);
+int cap_clip_embed_text(CapHandle h, const int32_t* ids, const int32_t* lens, int B, int L, float* out, void* stream);
+int cap_clip_logits(const float* img, const float* txt, int Ni, int Nt, int paired, float logit_scale, float* out, int embed_dim,
+                    void* stream);
+int cap_clip_logit_scale(CapHandle h, float* out);
 
 /* Range guard of CAP_F32_SPLIT.  Weights: cap_load_weight refuses (returns -1, message names the tensor) a tensor bound for
  * a GEMM-operand slot whose max |w| exceeds 65000 / 4096 = 15.87 or that holds a NaN - nothing is clipped silently.
