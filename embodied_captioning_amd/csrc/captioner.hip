@@ -113,13 +113,26 @@ struct CBlock {            // one CoCa text block: causal self-attention (unimod
     float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
 };
 
-constexpr bool kDeltaInT = false;
 // The ViT branch GEMMs (proj, fc2) of the MFMA-staged types add their output to the residual stream X IN PLACE (gemm_pp.hip's
 // residual epilogue: C = acc + bias + C) and the next LayerNorm reads X once.  The older scheme - branch output to `delta`, the
 // add+LayerNorm kernel reads delta and X and writes X back - moves 5 x M x D x 4 bytes per (GEMM, LayerNorm) pair against 4 here,
 // and stays for the exact fp32 mode, whose stream kernels have no residual operand.  Same fp32 add of the same two operands: the
 // residual stream has the same bits either way.
-inline bool vit_adds_in_place(int gdt) { return !kDeltaInT && gdt != CAP_DT_F32; }
+inline bool vit_adds_in_place(int gdt) { return gdt != CAP_DT_F32; }
+
+// The activations of a pre-LN transformer tower over M rows (alloc_tower).
+struct Tower {
+    float* X = nullptr;          // fp32 residual stream [M, D]
+    float* delta = nullptr;      // exact fp32 mode: the branch output (proj / fc2) the next add+LayerNorm folds into X; fp32 [M, D]
+    void *ln = nullptr, *qkv = nullptr, *ctx = nullptr, *mlp = nullptr;   // [M, D], [M, 3D], [M, D], [M, F] in the compute type
+};
+// Profile tags of one tower's launches (patchify / patch: image towers only)
+struct TowerTags { const char *patchify, *patch, *ln, *qkv, *attn, *proj, *fc1, *fc2; };
+const TowerTags kEncoderTags = {"patchify", "gemm_patch", "layernorm", "gemm_qkv", "vit_attention", "gemm_proj", "gemm_fc1", "gemm_fc2"};
+const TowerTags kClipImageTags = {"clip_patchify", "clip_v_gemm_patch", "clip_v_layernorm", "clip_v_gemm_qkv", "clip_v_attention",
+                                  "clip_v_gemm_proj", "clip_v_gemm_fc1", "clip_v_gemm_fc2"};
+const TowerTags kClipTextTags = {nullptr, nullptr, "clip_t_layernorm", "clip_t_gemm_qkv", "clip_t_attention", "clip_t_gemm_proj",
+                                 "clip_t_gemm_fc1", "clip_t_gemm_fc2"};
 
 struct Captioner {
     CapConfig c;
@@ -147,8 +160,9 @@ struct Captioner {
     int compaction = 1;          // cap_set_row_compaction: 1 = the greedy batch path works on the open captions' rows only (RowMap)
     int last_compacted = 0;      // did the last cap_generate's decode loop run compacted (cap_last_row_compaction)
     int *live = nullptr, *n_live = nullptr;       // RowMap storage: int32 [max rows] + the count
-    // vision weights
-    float *cls, *vpos, *b_patch, *post_g, *post_b;
+    // vision weights (post_g / post_b: the image tower's final LayerNorm - CoCa: the pooler's ln_k)
+    float *cls, *vpos, *b_patch = nullptr, *post_g, *post_b;
+    float *ln_pre_g = nullptr, *ln_pre_b = nullptr;
     void* w_patch;
     std::vector<VLayer> vl;
     // text weights
@@ -156,11 +170,9 @@ struct Captioner {
     void *word_t, *w_ckv, *w_tr;
     std::vector<TLayer> tl;
     // arena
-    void *patches, *ln, *qkv, *ctx, *mlp, *emb_t, *cross;
-    float *X, *emb_f;
-    void* delta;                 // ViT branch output (proj / fc2), folded into X by the next add+LayerNorm; fp32, or the
-                                 // compute type when kDeltaInT (measured: -0.6 ms per 256 frames, but 77 % instead of 80 %
-                                 // of bf16 captions token-identical to the fp32 mode's - not worth it, so off)
+    void *patches, *emb_t, *cross;
+    Tower vt;                    // the image tower's activations (CLIP's text tower: ct)
+    float* emb_f;
     int *seq, *finished, *lens, *anc;
     float *dx, *dy, *logits, *dpart;
     float* dx2 = nullptr;        // fused decode paths: second fp32 LayerNorm row buffer (ping-pong with dx), as many rows as dx
@@ -169,8 +181,7 @@ struct Captioner {
     size_t cache_layer_bytes = 0;
     // ---- CoCa (CAP_ARCH_COCA)
     int Q = 0, E = 0;
-    float *ln_pre_g = nullptr, *ln_pre_b = nullptr, *lnk_g = nullptr, *lnk_b = nullptr, *lnpost_g = nullptr,
-          *lnpost_b = nullptr, *pool_q = nullptr, *b_pool_kv = nullptr, *b_pool_o = nullptr, *ones = nullptr,
+    float *lnpost_g = nullptr, *lnpost_b = nullptr, *pool_q = nullptr, *b_pool_kv = nullptr, *b_pool_o = nullptr, *ones = nullptr,
           *zeros = nullptr, *tok_emb = nullptr, *lnf_g = nullptr, *lnf_b = nullptr, *pool_o = nullptr,
           *img_tokens = nullptr;
     void *w_pool_kv = nullptr, *w_pool_o = nullptr, *w_cvocab = nullptr, *pool_kvbuf = nullptr, *pool_ctx = nullptr,
@@ -191,12 +202,11 @@ struct Captioner {
     // ---- sentence encoder (CAP_ARCH_MINILM): token-type row 0, activations [max_batch * max_len, .]
     float *tok_type = nullptr, *te_x = nullptr, *te_y = nullptr;
     void *te_xt = nullptr, *te_qkv = nullptr, *te_ctx = nullptr, *te_h = nullptr;
-    // ---- CLIP scorer (CAP_ARCH_CLIP): image tower on the encoder buffers above (vl, X, ln, qkv, ctx, mlp, delta), text tower on
-    // its own [max_batch * max_len, .] buffers; projections fp32 [embed_dim, width] for the pooled head kernel
+    // ---- CLIP scorer (CAP_ARCH_CLIP): image tower on the encoder's (vl, vt), text tower on its own [max_batch * max_len, .]
+    // rows; projections fp32 [embed_dim, width] for the pooled head kernel
     std::vector<VLayer> ctl;
-    float *c_vproj = nullptr, *c_tproj = nullptr, *c_tok = nullptr, *c_lnf_g = nullptr, *c_lnf_b = nullptr, *c_logit = nullptr,
-          *c_x = nullptr, *c_delta = nullptr;
-    void *c_ln = nullptr, *c_qkv = nullptr, *c_ctx = nullptr, *c_mlp = nullptr;
+    Tower ct;
+    float *c_vproj = nullptr, *c_tproj = nullptr, *c_tok = nullptr, *c_lnf_g = nullptr, *c_lnf_b = nullptr, *c_logit = nullptr;
     // profiling
     bool prof = false;
     std::vector<ProfTag> prof_recs;
@@ -263,33 +273,86 @@ int reg_mat_i8(Captioner* m, const std::string& name, void** p, float** scale, i
     return add_slot(m, name, *p, CAP_DT_I8W, rows, cols, 0, *scale);
 }
 
+// register the checkpoint tensors p + names[j] + "weight" / "bias" as the row ranges [j * rows, (j + 1) * rows) of one fused
+// compute-dtype weight w [n * rows, cols] and its fp32 bias b
+void reg_rows(Captioner* m, const std::string& p, const char* const* names, int n, void* w, float* b, int64_t rows, int64_t cols) {
+    for (int j = 0; j < n; ++j) {
+        add_slot(m, p + names[j] + "weight", (char*)w + (size_t)j * rows * cols * m->esz, m->gdt, rows, cols);
+        add_slot(m, p + names[j] + "bias", b + (size_t)j * rows, CAP_DT_F32, 1, rows);
+    }
+}
+// allocate such a fused weight + bias and register its n parts (n = 1: one Linear layer)
+int reg_fused(Captioner* m, const std::string& p, const char* const* names, int n, void** w, float** b, int64_t rows, int64_t cols) {
+    TRY(walloc(m, w, (size_t)n * rows * cols * m->esz));
+    TRY(walloc(m, (void**)b, (size_t)n * rows * 4));
+    reg_rows(m, p, names, n, *w, *b, rows, cols);
+    return 0;
+}
+int reg_ln(Captioner* m, const std::string& p, float** g, float** b, int64_t n) {
+    TRY(reg_f32(m, p + "weight", g, n));
+    return reg_f32(m, p + "bias", b, n);
+}
+
+// Checkpoint names of a pre-LN transformer tower; every name below ends in the separator before "weight" / "bias".  qkv: one
+// fused projection {name}, or {q, k, v} written into the rows of one fused buffer.  Stem names: image towers only (null: absent).
+struct TowerNames {
+    const char *root, *layers;                            // layer i: root + layers + i + "."
+    const char *qkv[3], *proj, *ln1, *fc1, *fc2, *ln2;
+    const char *cls, *pos, *patch;                        // (cls / pos: full names)
+    bool patch_bias;
+    const char *ln_pre, *ln_final;
+};
+// HF BLIP / BLIP-2 vision model
+const TowerNames kBlipVision = {"vision_model.", "encoder.layers.", {"self_attn.qkv."}, "self_attn.projection.", "layer_norm1.",
+                                "mlp.fc1.", "mlp.fc2.", "layer_norm2.", "embeddings.class_embedding",
+                                "embeddings.position_embedding", "embeddings.patch_embedding.", true, nullptr, "post_layernorm."};
+// open_clip CoCa ViT (the final LayerNorm is the attentional pooler's ln_k)
+const TowerNames kCocaVision = {"visual.", "transformer.resblocks.", {"attn.in_proj_"}, "attn.out_proj.", "ln_1.", "mlp.c_fc.",
+                                "mlp.c_proj.", "ln_2.", "class_embedding", "positional_embedding", "conv1.", false, "ln_pre.",
+                                "attn_pool.ln_k."};
+// HF CLIPModel towers
+const TowerNames kClipVision = {"vision_model.", "encoder.layers.", {"self_attn.q_proj.", "self_attn.k_proj.", "self_attn.v_proj."},
+                                "self_attn.out_proj.", "layer_norm1.", "mlp.fc1.", "mlp.fc2.", "layer_norm2.",
+                                "embeddings.class_embedding", "embeddings.position_embedding.weight", "embeddings.patch_embedding.",
+                                false, "pre_layrnorm.", "post_layernorm."};     // (sic: HF's name)
+const TowerNames kClipText = {"text_model.", "encoder.layers.", {"self_attn.q_proj.", "self_attn.k_proj.", "self_attn.v_proj."},
+                              "self_attn.out_proj.", "layer_norm1.", "mlp.fc1.", "mlp.fc2.", "layer_norm2.", nullptr, nullptr,
+                              nullptr, false, nullptr, "final_layer_norm."};
+
+// an image tower's stem: class row, position table, patch weight [D, Kpad] (+ bias), ln_pre
+int reg_stem(Captioner* m, const TowerNames& n) {
+    const int D = m->c.v_hidden;
+    const std::string r = n.root;
+    TRY(reg_f32(m, r + n.cls, &m->cls, D));
+    TRY(reg_f32(m, r + n.pos, &m->vpos, (int64_t)m->NT * D));
+    TRY(reg_mat(m, r + n.patch + "weight", &m->w_patch, D, m->Kpatch, m->Kpad));
+    if (n.patch_bias) TRY(reg_f32(m, r + n.patch + "bias", &m->b_patch, D));
+    if (n.ln_pre) TRY(reg_ln(m, r + n.ln_pre, &m->ln_pre_g, &m->ln_pre_b, D));
+    return 0;
+}
+
+// the blocks of a pre-LN tower (width D, MLP F) and its final LayerNorm
+int reg_tower(Captioner* m, const TowerNames& n, std::vector<VLayer>& layers, int count, int D, int F, float** lnf_g, float** lnf_b) {
+    const int nqkv = n.qkv[1] ? 3 : 1;
+    layers.resize(count);
+    for (int i = 0; i < count; ++i) {
+        VLayer& L = layers[i];
+        const std::string p = std::string(n.root) + n.layers + std::to_string(i) + ".";
+        TRY(reg_fused(m, p, n.qkv, nqkv, &L.w_qkv, &L.b_qkv, 3 * D / nqkv, D));
+        TRY(reg_fused(m, p, &n.proj, 1, &L.w_proj, &L.b_proj, D, D));
+        TRY(reg_ln(m, p + n.ln1, &L.ln1_g, &L.ln1_b, D));
+        TRY(reg_fused(m, p, &n.fc1, 1, &L.w_fc1, &L.b_fc1, F, D));
+        TRY(reg_fused(m, p, &n.fc2, 1, &L.w_fc2, &L.b_fc2, D, F));
+        TRY(reg_ln(m, p + n.ln2, &L.ln2_g, &L.ln2_b, D));
+    }
+    return reg_ln(m, std::string(n.root) + n.ln_final, lnf_g, lnf_b, D);
+}
+
 int build_blip(Captioner* m) {
     const CapConfig& c = m->c;
-    const int D = c.v_hidden, Mv = c.v_mlp, T = c.t_hidden, F = c.t_ffn, V = c.vocab;
-    const std::string vm = "vision_model.";
-    TRY(reg_f32(m, vm + "embeddings.class_embedding", &m->cls, D));
-    TRY(reg_f32(m, vm + "embeddings.position_embedding", &m->vpos, (int64_t)m->NT * D));
-    TRY(reg_mat(m, vm + "embeddings.patch_embedding.weight", &m->w_patch, D, m->Kpatch, m->Kpad));
-    TRY(reg_f32(m, vm + "embeddings.patch_embedding.bias", &m->b_patch, D));
-    m->vl.resize(c.v_layers);
-    for (int i = 0; i < c.v_layers; ++i) {
-        VLayer& L = m->vl[i];
-        const std::string p = vm + "encoder.layers." + std::to_string(i) + ".";
-        TRY(reg_mat(m, p + "self_attn.qkv.weight", &L.w_qkv, 3 * D, D));
-        TRY(reg_f32(m, p + "self_attn.qkv.bias", &L.b_qkv, 3 * D));
-        TRY(reg_mat(m, p + "self_attn.projection.weight", &L.w_proj, D, D));
-        TRY(reg_f32(m, p + "self_attn.projection.bias", &L.b_proj, D));
-        TRY(reg_f32(m, p + "layer_norm1.weight", &L.ln1_g, D));
-        TRY(reg_f32(m, p + "layer_norm1.bias", &L.ln1_b, D));
-        TRY(reg_mat(m, p + "mlp.fc1.weight", &L.w_fc1, Mv, D));
-        TRY(reg_f32(m, p + "mlp.fc1.bias", &L.b_fc1, Mv));
-        TRY(reg_mat(m, p + "mlp.fc2.weight", &L.w_fc2, D, Mv));
-        TRY(reg_f32(m, p + "mlp.fc2.bias", &L.b_fc2, D));
-        TRY(reg_f32(m, p + "layer_norm2.weight", &L.ln2_g, D));
-        TRY(reg_f32(m, p + "layer_norm2.bias", &L.ln2_b, D));
-    }
-    TRY(reg_f32(m, vm + "post_layernorm.weight", &m->post_g, D));
-    TRY(reg_f32(m, vm + "post_layernorm.bias", &m->post_b, D));
+    const int D = c.v_hidden, T = c.t_hidden, F = c.t_ffn, V = c.vocab;
+    TRY(reg_stem(m, kBlipVision));
+    TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
 
     const std::string tb = "text_decoder.bert.";
     // the embedding table is read twice: fp32 rows for the lookup, compute-dtype [V,T] as the (tied) LM-head weight
@@ -308,27 +371,18 @@ int build_blip(Captioner* m) {
     TRY(walloc(m, &m->w_ckv, (size_t)c.t_layers * 2 * T * D * m->esz));
     TRY(walloc(m, (void**)&m->b_ckv, (size_t)c.t_layers * 2 * T * 4));
     m->tl.resize(c.t_layers);
+    const char* nm[3] = {"query.", "key.", "value."};
     for (int i = 0; i < c.t_layers; ++i) {
         TLayer& L = m->tl[i];
         const std::string p = tb + "encoder.layer." + std::to_string(i) + ".";
-        TRY(walloc(m, &L.w_qkv, (size_t)3 * T * T * m->esz));
-        TRY(walloc(m, (void**)&L.b_qkv, (size_t)3 * T * 4));
-        const char* nm[3] = {"query", "key", "value"};
-        for (int j = 0; j < 3; ++j) {
-            add_slot(m, p + "attention.self." + nm[j] + ".weight", (char*)L.w_qkv + (size_t)j * T * T * m->esz, m->gdt, T, T);
-            add_slot(m, p + "attention.self." + nm[j] + ".bias", L.b_qkv + (size_t)j * T, CAP_DT_F32, 1, T);
-        }
+        TRY(reg_fused(m, p + "attention.self.", nm, 3, &L.w_qkv, &L.b_qkv, T, T));
         TRY(reg_mat(m, p + "attention.output.dense.weight", &L.w_so, T, T));
         TRY(reg_f32(m, p + "attention.output.dense.bias", &L.b_so, T));
         TRY(reg_f32(m, p + "attention.output.LayerNorm.weight", &L.so_g, T));
         TRY(reg_f32(m, p + "attention.output.LayerNorm.bias", &L.so_b, T));
         TRY(reg_mat(m, p + "crossattention.self.query.weight", &L.w_cq, T, T));
         TRY(reg_f32(m, p + "crossattention.self.query.bias", &L.b_cq, T));
-        for (int j = 0; j < 2; ++j) {
-            add_slot(m, p + "crossattention.self." + nm[j + 1] + ".weight",
-                     (char*)m->w_ckv + ((size_t)i * 2 + j) * T * D * m->esz, m->gdt, T, D);
-            add_slot(m, p + "crossattention.self." + nm[j + 1] + ".bias", m->b_ckv + ((size_t)i * 2 + j) * T, CAP_DT_F32, 1, T);
-        }
+        reg_rows(m, p + "crossattention.self.", nm + 1, 2, (char*)m->w_ckv + (size_t)i * 2 * T * D * m->esz, m->b_ckv + (size_t)i * 2 * T, T, D);
         TRY(reg_mat(m, p + "crossattention.output.dense.weight", &L.w_co, T, T));
         TRY(reg_f32(m, p + "crossattention.output.dense.bias", &L.b_co, T));
         TRY(reg_f32(m, p + "crossattention.output.LayerNorm.weight", &L.co_g, T));
@@ -376,33 +430,10 @@ int reg_block(Captioner* m, const std::string& p, CBlock& b, int E, int F, bool 
 // the host loader (embodied_captioning_amd/coca_weights.py) from the checkpoint.
 int build_coca(Captioner* m) {
     const CapConfig& c = m->c;
-    const int D = c.v_hidden, Mv = c.v_mlp, E = c.embed_dim, F = c.t_ffn, V = c.vocab, Q = c.pool_queries;
+    const int D = c.v_hidden, E = c.embed_dim, F = c.t_ffn, V = c.vocab, Q = c.pool_queries;
     m->Q = Q; m->E = E;
-    TRY(reg_f32(m, "visual.class_embedding", &m->cls, D));
-    TRY(reg_f32(m, "visual.positional_embedding", &m->vpos, (int64_t)m->NT * D));
-    TRY(reg_mat(m, "visual.conv1.weight", &m->w_patch, D, m->Kpatch, m->Kpad));
-    m->b_patch = nullptr;                                  // conv1 has no bias in open_clip's ViT
-    TRY(reg_f32(m, "visual.ln_pre.weight", &m->ln_pre_g, D));
-    TRY(reg_f32(m, "visual.ln_pre.bias", &m->ln_pre_b, D));
-    m->vl.resize(c.v_layers);
-    for (int i = 0; i < c.v_layers; ++i) {
-        VLayer& L = m->vl[i];
-        const std::string p = "visual.transformer.resblocks." + std::to_string(i) + ".";
-        TRY(reg_mat(m, p + "attn.in_proj_weight", &L.w_qkv, 3 * D, D));
-        TRY(reg_f32(m, p + "attn.in_proj_bias", &L.b_qkv, 3 * D));
-        TRY(reg_mat(m, p + "attn.out_proj.weight", &L.w_proj, D, D));
-        TRY(reg_f32(m, p + "attn.out_proj.bias", &L.b_proj, D));
-        TRY(reg_f32(m, p + "ln_1.weight", &L.ln1_g, D));
-        TRY(reg_f32(m, p + "ln_1.bias", &L.ln1_b, D));
-        TRY(reg_mat(m, p + "mlp.c_fc.weight", &L.w_fc1, Mv, D));
-        TRY(reg_f32(m, p + "mlp.c_fc.bias", &L.b_fc1, Mv));
-        TRY(reg_mat(m, p + "mlp.c_proj.weight", &L.w_fc2, D, Mv));
-        TRY(reg_f32(m, p + "mlp.c_proj.bias", &L.b_fc2, D));
-        TRY(reg_f32(m, p + "ln_2.weight", &L.ln2_g, D));
-        TRY(reg_f32(m, p + "ln_2.bias", &L.ln2_b, D));
-    }
-    TRY(reg_f32(m, "visual.attn_pool.ln_k.weight", &m->lnk_g, D));
-    TRY(reg_f32(m, "visual.attn_pool.ln_k.bias", &m->lnk_b, D));
+    TRY(reg_stem(m, kCocaVision));
+    TRY(reg_tower(m, kCocaVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
     TRY(reg_f32(m, "derived.pool_q", &m->pool_q, (int64_t)Q * E));
     TRY(reg_mat(m, "derived.pool_kv.weight", &m->w_pool_kv, 2 * E, D));
     TRY(reg_f32(m, "derived.pool_kv.bias", &m->b_pool_kv, 2 * E));
@@ -443,18 +474,28 @@ int build_coca(Captioner* m) {
     return 0;
 }
 
+// the activations of a tower of width D and MLP F over M rows
+int alloc_tower(Captioner* m, Tower& t, size_t M, size_t D, size_t F) {
+    TRY(dev_alloc(m, (void**)&t.X, M * D * 4));
+    if (!vit_adds_in_place(m->gdt)) TRY(dev_alloc(m, (void**)&t.delta, M * D * 4));
+    TRY(dev_alloc(m, &t.ln, M * D * m->esz));
+    TRY(dev_alloc(m, &t.qkv, M * 3 * D * m->esz));   // (split mode: fp32 q|k|v where the attention cannot take G8 - esz is 4 there)
+    TRY(dev_alloc(m, &t.ctx, M * D * m->esz));
+    return dev_alloc(m, &t.mlp, M * F * m->esz);
+}
+// the image tower's: patch rows (zero padding columns up to Kpad) and its activations over max_batch images
+int alloc_image_tower(Captioner* m) {
+    const size_t Bm = m->c.max_batch, bytes = Bm * m->P * m->Kpad * m->esz;
+    TRY(dev_alloc(m, &m->patches, bytes));
+    CAP_HIP_CHECK(hipMemset(m->patches, 0, bytes));
+    return alloc_tower(m, m->vt, Bm * m->NT, m->c.v_hidden, m->c.v_mlp);
+}
+
 int build_arena_coca(Captioner* m) {
     const CapConfig& c = m->c;
     const size_t Bm = c.max_batch, NT = m->NT, D = c.v_hidden, E = c.embed_dim, e = m->esz, Q = c.pool_queries;
     const size_t M = Bm * NT, R = Bm * c.max_beams, Lm = c.max_len, H = c.t_heads;     // R: decode rows (image x beam)
-    TRY(dev_alloc(m, &m->patches, Bm * m->P * m->Kpad * e));
-    CAP_HIP_CHECK(hipMemset(m->patches, 0, Bm * m->P * m->Kpad * e));
-    TRY(dev_alloc(m, (void**)&m->X, M * D * 4));
-    if (!vit_adds_in_place(m->gdt)) TRY(dev_alloc(m, (void**)&m->delta, M * D * (kDeltaInT ? m->esz : 4)));
-    TRY(dev_alloc(m, &m->ln, M * D * e));
-    TRY(dev_alloc(m, &m->qkv, M * 3 * D * e));
-    TRY(dev_alloc(m, &m->ctx, M * D * e));
-    TRY(dev_alloc(m, &m->mlp, M * c.v_mlp * e));
+    TRY(alloc_image_tower(m));
     TRY(dev_alloc(m, (void**)&m->emb_f, 256));
     TRY(dev_alloc(m, &m->emb_t, M * D * e));
     TRY(dev_alloc(m, &m->pool_kvbuf, M * 2 * E * e));
@@ -487,14 +528,7 @@ int build_arena(Captioner* m) {
     const CapConfig& c = m->c;
     const size_t Bm = c.max_batch, NT = m->NT, D = c.v_hidden, T = c.t_hidden, e = m->esz;
     const size_t M = Bm * NT, R = Bm * c.max_beams, Lm = c.max_len, H = c.t_heads;
-    TRY(dev_alloc(m, &m->patches, Bm * m->P * m->Kpad * e));
-    CAP_HIP_CHECK(hipMemset(m->patches, 0, Bm * m->P * m->Kpad * e));
-    TRY(dev_alloc(m, (void**)&m->X, M * D * 4));
-    if (!vit_adds_in_place(m->gdt)) TRY(dev_alloc(m, (void**)&m->delta, M * D * (kDeltaInT ? m->esz : 4)));
-    TRY(dev_alloc(m, &m->ln, M * D * e));
-    TRY(dev_alloc(m, &m->qkv, M * 3 * D * e));
-    TRY(dev_alloc(m, &m->ctx, M * D * e));
-    TRY(dev_alloc(m, &m->mlp, M * c.v_mlp * e));
+    TRY(alloc_image_tower(m));
     TRY(dev_alloc(m, (void**)&m->emb_f, M * D * 4));
     TRY(dev_alloc(m, &m->emb_t, M * D * e));
     TRY(dev_alloc(m, &m->cross, (size_t)c.t_layers * 2 * m->cross_block((size_t)Bm * H * NT)));
@@ -589,45 +623,18 @@ __global__ void copy_new_tokens_kernel(const int* seq, int seq_ld, int P, const 
 // query_tokens), computed once by the host loader (a constant of the checkpoint).
 int build_blip2(Captioner* m) {
     const CapConfig& c = m->c;
-    const int D = c.v_hidden, Mv = c.v_mlp, Q = c.q_hidden, F = c.q_ffn, T = c.t_hidden, G = c.t_ffn, V = c.vocab, nq = c.num_query_tokens;
-    const std::string vm = "vision_model.";
-    TRY(reg_f32(m, vm + "embeddings.class_embedding", &m->cls, D));
-    TRY(reg_f32(m, vm + "embeddings.position_embedding", &m->vpos, (int64_t)m->NT * D));
-    TRY(reg_mat(m, vm + "embeddings.patch_embedding.weight", &m->w_patch, D, m->Kpatch, m->Kpad));
-    TRY(reg_f32(m, vm + "embeddings.patch_embedding.bias", &m->b_patch, D));
-    m->vl.resize(c.v_layers);
-    for (int i = 0; i < c.v_layers; ++i) {
-        VLayer& L = m->vl[i];
-        const std::string p = vm + "encoder.layers." + std::to_string(i) + ".";
-        TRY(reg_mat(m, p + "self_attn.qkv.weight", &L.w_qkv, 3 * D, D));
-        TRY(reg_f32(m, p + "self_attn.qkv.bias", &L.b_qkv, 3 * D));
-        TRY(reg_mat(m, p + "self_attn.projection.weight", &L.w_proj, D, D));
-        TRY(reg_f32(m, p + "self_attn.projection.bias", &L.b_proj, D));
-        TRY(reg_f32(m, p + "layer_norm1.weight", &L.ln1_g, D));
-        TRY(reg_f32(m, p + "layer_norm1.bias", &L.ln1_b, D));
-        TRY(reg_mat(m, p + "mlp.fc1.weight", &L.w_fc1, Mv, D));
-        TRY(reg_f32(m, p + "mlp.fc1.bias", &L.b_fc1, Mv));
-        TRY(reg_mat(m, p + "mlp.fc2.weight", &L.w_fc2, D, Mv));
-        TRY(reg_f32(m, p + "mlp.fc2.bias", &L.b_fc2, D));
-        TRY(reg_f32(m, p + "layer_norm2.weight", &L.ln2_g, D));
-        TRY(reg_f32(m, p + "layer_norm2.bias", &L.ln2_b, D));
-    }
-    TRY(reg_f32(m, vm + "post_layernorm.weight", &m->post_g, D));
-    TRY(reg_f32(m, vm + "post_layernorm.bias", &m->post_b, D));
+    const int D = c.v_hidden, Q = c.q_hidden, F = c.q_ffn, T = c.t_hidden, G = c.t_ffn, V = c.vocab, nq = c.num_query_tokens;
+    TRY(reg_stem(m, kBlipVision));
+    TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
 
     TRY(reg_f32(m, "derived.qformer_x0", &m->q_x0, (int64_t)nq * Q));
     m->ql.resize(c.q_layers);
-    const char* nm[3] = {"query", "key", "value"};
+    const char* nm[3] = {"query.", "key.", "value."};
     for (int i = 0; i < c.q_layers; ++i) {
         QLayer& L = m->ql[i];
         L.cross = i % c.q_cross_freq == 0;
         const std::string p = "qformer.encoder.layer." + std::to_string(i) + ".";
-        TRY(walloc(m, &L.w_qkv, (size_t)3 * Q * Q * m->esz));
-        TRY(walloc(m, (void**)&L.b_qkv, (size_t)3 * Q * 4));
-        for (int j = 0; j < 3; ++j) {
-            add_slot(m, p + "attention.attention." + nm[j] + ".weight", (char*)L.w_qkv + (size_t)j * Q * Q * m->esz, m->gdt, Q, Q);
-            add_slot(m, p + "attention.attention." + nm[j] + ".bias", L.b_qkv + (size_t)j * Q, CAP_DT_F32, 1, Q);
-        }
+        TRY(reg_fused(m, p + "attention.attention.", nm, 3, &L.w_qkv, &L.b_qkv, Q, Q));
         TRY(reg_mat(m, p + "attention.output.dense.weight", &L.w_so, Q, Q));
         TRY(reg_f32(m, p + "attention.output.dense.bias", &L.b_so, Q));
         TRY(reg_f32(m, p + "attention.output.LayerNorm.weight", &L.so_g, Q));
@@ -635,12 +642,7 @@ int build_blip2(Captioner* m) {
         if (L.cross) {
             TRY(reg_mat(m, p + "crossattention.attention.query.weight", &L.w_cq, Q, Q));
             TRY(reg_f32(m, p + "crossattention.attention.query.bias", &L.b_cq, Q));
-            TRY(walloc(m, &L.w_ckv, (size_t)2 * Q * D * m->esz));
-            TRY(walloc(m, (void**)&L.b_ckv, (size_t)2 * Q * 4));
-            for (int j = 0; j < 2; ++j) {
-                add_slot(m, p + "crossattention.attention." + nm[j + 1] + ".weight", (char*)L.w_ckv + (size_t)j * Q * D * m->esz, m->gdt, Q, D);
-                add_slot(m, p + "crossattention.attention." + nm[j + 1] + ".bias", L.b_ckv + (size_t)j * Q, CAP_DT_F32, 1, Q);
-            }
+            TRY(reg_fused(m, p + "crossattention.attention.", nm + 1, 2, &L.w_ckv, &L.b_ckv, Q, D));
             TRY(reg_mat(m, p + "crossattention.output.dense.weight", &L.w_co, Q, Q));
             TRY(reg_f32(m, p + "crossattention.output.dense.bias", &L.b_co, Q));
             TRY(reg_f32(m, p + "crossattention.output.LayerNorm.weight", &L.co_g, Q));
@@ -702,14 +704,7 @@ int build_blip2(Captioner* m) {
 
     // arena
     const size_t NT = m->NT, M = Bm * NT, e = m->esz, P = nq + 1;
-    TRY(dev_alloc(m, &m->patches, Bm * m->P * m->Kpad * e));
-    CAP_HIP_CHECK(hipMemset(m->patches, 0, Bm * m->P * m->Kpad * e));
-    TRY(dev_alloc(m, (void**)&m->X, M * D * 4));
-    if (!vit_adds_in_place(m->gdt)) TRY(dev_alloc(m, (void**)&m->delta, M * D * (kDeltaInT ? e : 4)));
-    TRY(dev_alloc(m, &m->ln, M * D * e));
-    TRY(dev_alloc(m, &m->qkv, M * 3 * D * e));
-    TRY(dev_alloc(m, &m->ctx, M * D * e));
-    TRY(dev_alloc(m, &m->mlp, M * Mv * e));
+    TRY(alloc_image_tower(m));
     TRY(dev_alloc(m, (void**)&m->emb_f, M * D * 4));
     TRY(dev_alloc(m, &m->emb_t, M * D * e));
     TRY(dev_alloc(m, (void**)&m->qx, Bm * nq * Q * 4));
@@ -1054,132 +1049,105 @@ int run_text_encoder(Captioner* m, const int* ids, const int* lens, int B, int L
     return launch_mean_pool_normalize(m->te_x, lens, B, L, T, out, s);
 }
 
-// ---------------------------------------------------------------------------------------------- CLIP scorer
-// HF CLIPModel state-dict names (transformers models/clip/modeling_clip.py): separate q / k / v projections land in the fused
-// q|k|v rows (as the sentence encoder's), the patch conv has no bias, the projections are fp32 for the head kernel.
-int reg_clip_layer(Captioner* m, const std::string& p, VLayer& L, int D, int F) {
-    TRY(walloc(m, &L.w_qkv, (size_t)3 * D * D * m->esz));
-    TRY(walloc(m, (void**)&L.b_qkv, (size_t)3 * D * 4));
-    const char* nm[3] = {"q_proj", "k_proj", "v_proj"};
-    for (int j = 0; j < 3; ++j) {
-        add_slot(m, p + "self_attn." + nm[j] + ".weight", (char*)L.w_qkv + (size_t)j * D * D * m->esz, m->gdt, D, D);
-        add_slot(m, p + "self_attn." + nm[j] + ".bias", L.b_qkv + (size_t)j * D, CAP_DT_F32, 1, D);
+// ---------------------------------------------------------------------------------------------- pre-LN towers
+// Image tower stem: patchify, patch GEMM (+ position rows, + bias where the checkpoint has one), class rows, ln_pre where the
+// checkpoint has one -> vt.X [B * NT, D].
+int run_stem(Captioner* m, const void* pixels, int fmt, int B, const TowerTags& tg, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int D = c.v_hidden, NT = m->NT;
+    float* X = m->vt.X;
+    {
+        ProfScope ps(m, s, tg.patchify, 0, (double)B * 3 * c.image_size * c.image_size * (fmt ? 1 : 4) + (double)B * m->P * m->Kpad * m->esz);
+        TRY(launch_patchify(m->gdt, pixels, fmt, B, c.image_size, c.patch_size, m->Kpad, m->patches, c.pix_mean, c.pix_std, s));
     }
-    TRY(reg_mat(m, p + "self_attn.out_proj.weight", &L.w_proj, D, D));
-    TRY(reg_f32(m, p + "self_attn.out_proj.bias", &L.b_proj, D));
-    TRY(reg_f32(m, p + "layer_norm1.weight", &L.ln1_g, D));
-    TRY(reg_f32(m, p + "layer_norm1.bias", &L.ln1_b, D));
-    TRY(reg_mat(m, p + "mlp.fc1.weight", &L.w_fc1, F, D));
-    TRY(reg_f32(m, p + "mlp.fc1.bias", &L.b_fc1, F));
-    TRY(reg_mat(m, p + "mlp.fc2.weight", &L.w_fc2, D, F));
-    TRY(reg_f32(m, p + "mlp.fc2.bias", &L.b_fc2, D));
-    TRY(reg_f32(m, p + "layer_norm2.weight", &L.ln2_g, D));
-    TRY(reg_f32(m, p + "layer_norm2.bias", &L.ln2_b, D));
-    return 0;
+    TRY(gemm(m, s, tg.patch, m->patches, m->Kpad, m->w_patch, m->Kpad, X, D, m->b_patch, nullptr, B * m->P, D, m->Kpad, 0, 1,
+             EPI_PATCH, m->P, 0, 0, 0, m->vpos));
+    TRY(launch_cls_rows(m->cls, m->vpos, X, B, NT, D, s));
+    if (!m->ln_pre_g) return 0;
+    ProfScope ps(m, s, tg.ln, 0, (double)B * NT * D * 8);
+    return launch_layernorm(m->dt, X, D, m->ln_pre_g, m->ln_pre_b, c.v_eps, nullptr, X, B * NT, D, s);
 }
 
+// The pre-LN blocks of a tower over the fp32 residual stream t.X [B * N, D], then its final step: the LayerNorm (fin_g, fin_b)
+// of the last hidden states to fin_t (compute type) / fin_f (fp32, optional), or with fin_g == null no LayerNorm - X is left
+// holding the last hidden states (CLIP: the head kernel normalises the pooled rows).  act: fc1's activation (gemm.h).  causal:
+// the text tower's mask - the generic attention kernel, which in the split mode reads fp32 q|k|v (the G8 kernel takes no mask).
+// Exact fp32 mode: the two branch GEMMs (proj, fc2) write their output to t.delta; the next LayerNorm kernel folds it into X in
+// the same pass that normalises it, so the GEMM epilogues are store-only.  Other modes: they add into X themselves.
+int run_tower(Captioner* m, hipStream_t s, const std::vector<VLayer>& layers, const Tower& t, int B, int N, int D, int H, int F,
+              float eps, int act, bool causal, const TowerTags& tg, const float* fin_g, const float* fin_b, void* fin_t, float* fin_f) {
+    const int M = B * N;
+    const bool in_place = vit_adds_in_place(m->gdt);
+    float* branch_out = in_place ? t.X : t.delta;
+    const float* branch_resid = in_place ? t.X : nullptr;
+    // split mode: q|k|v stay G8 when the split-fp16 MFMA attention kernel covers this token count, else the GEMM writes fp32
+    // for the fp32 attention kernels; either way the context comes out as G8 (the proj GEMM's operand)
+    const bool g8_attn = !causal && m->gdt == CAP_DT_G8 && D / H == 64 && vit_attention_takes_g8(N);
+    bool pending = false;                                  // delta holds a branch output not yet added to X
+    auto add_ln = [&](const float* g, const float* b, void* out_t, float* out_f) -> int {
+        ProfScope ps(m, s, tg.ln, 0, (double)M * D * ((pending ? 12 : 4) + (out_t ? m->esz : 0) + (out_f ? 4 : 0)));
+        if (pending) return launch_reduce_layernorm(m->gdt, t.delta, 1, nullptr, t.X, g, b, eps, out_t, out_f, t.X, M, D, s);
+        return launch_layernorm(m->gdt, t.X, D, g, b, eps, out_t, out_f, M, D, s);
+    };
+    for (const VLayer& L : layers) {
+        TRY(add_ln(L.ln1_g, L.ln1_b, t.ln, nullptr));
+        TRY(gemm(m, s, tg.qkv, t.ln, D, L.w_qkv, D, t.qkv, 3 * D, L.b_qkv, nullptr, M, 3 * D, D, 0, (m->gdt == CAP_DT_G8 && !g8_attn) ? 1 : 0));
+        {
+            ProfScope ps(m, s, tg.attn, (causal ? 2.0 : 4.0) * B * H * (double)N * N * 64, (double)M * 4 * D * m->esz);
+            TRY(launch_vit_attention(g8_attn ? CAP_DT_G8 : m->dt, t.qkv, t.ctx, B, N, H, 0, s, D / H, causal ? 1 : 0, m->gdt));
+        }
+        TRY(gemm(m, s, tg.proj, t.ctx, D, L.w_proj, D, branch_out, D, L.b_proj, branch_resid, M, D, D, 0, 1));
+        pending = !in_place;
+        TRY(add_ln(L.ln2_g, L.ln2_b, t.ln, nullptr));
+        TRY(gemm(m, s, tg.fc1, t.ln, D, L.w_fc1, D, t.mlp, F, L.b_fc1, nullptr, M, F, D, act, 0));
+        TRY(gemm(m, s, tg.fc2, t.mlp, F, L.w_fc2, F, branch_out, D, L.b_fc2, branch_resid, M, D, F, 0, 1));
+    }
+    if (fin_g) return add_ln(fin_g, fin_b, fin_t, fin_f);
+    // no LayerNorm outputs: the pass only folds the last fc2 output into X (gamma / beta: any valid vectors)
+    return pending ? add_ln(layers.back().ln2_g, layers.back().ln2_b, nullptr, nullptr) : 0;
+}
+
+// BLIP / BLIP-2: final LayerNorm = post_layernorm -> image_embeds (fp32 to the caller + T for the cross-K/V GEMM).
+// CoCa: ln_pre after the embeddings; final LayerNorm = the pooler's ln_k -> T only (run_coca_pool continues).
+int run_encoder(Captioner* m, const void* pixels, int fmt, int B, float* out_embeds, hipStream_t s) {
+    const CapConfig& c = m->c;
+    float* emb_f = c.arch == CAP_ARCH_COCA ? nullptr : out_embeds ? out_embeds : m->emb_f;
+    TRY(run_stem(m, pixels, fmt, B, kEncoderTags, s));
+    return run_tower(m, s, m->vl, m->vt, B, m->NT, c.v_hidden, c.v_heads, c.v_mlp, c.v_eps, 1, false, kEncoderTags, m->post_g,
+                     m->post_b, m->emb_t, emb_f);
+}
+
+// ---------------------------------------------------------------------------------------------- CLIP scorer
+// HF CLIPModel state-dict names (transformers models/clip/modeling_clip.py): kClipVision / kClipText, the projections fp32 for
+// the head kernel.
 int build_clip(Captioner* m) {
     const CapConfig& c = m->c;
     const int D = c.v_hidden, T = c.t_hidden, P = c.embed_dim;
-    const std::string vm = "vision_model.", tm = "text_model.";
-    TRY(reg_f32(m, vm + "embeddings.class_embedding", &m->cls, D));
-    TRY(reg_f32(m, vm + "embeddings.position_embedding.weight", &m->vpos, (int64_t)m->NT * D));
-    TRY(reg_mat(m, vm + "embeddings.patch_embedding.weight", &m->w_patch, D, m->Kpatch, m->Kpad));
-    m->b_patch = nullptr;
-    TRY(reg_f32(m, vm + "pre_layrnorm.weight", &m->ln_pre_g, D));        // (sic: HF's name)
-    TRY(reg_f32(m, vm + "pre_layrnorm.bias", &m->ln_pre_b, D));
-    m->vl.resize(c.v_layers);
-    for (int i = 0; i < c.v_layers; ++i) TRY(reg_clip_layer(m, vm + "encoder.layers." + std::to_string(i) + ".", m->vl[i], D, c.v_mlp));
-    TRY(reg_f32(m, vm + "post_layernorm.weight", &m->post_g, D));
-    TRY(reg_f32(m, vm + "post_layernorm.bias", &m->post_b, D));
+    TRY(reg_stem(m, kClipVision));
+    TRY(reg_tower(m, kClipVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
     TRY(walloc(m, (void**)&m->c_vproj, (size_t)P * D * 4));
     add_slot(m, "visual_projection.weight", m->c_vproj, CAP_DT_F32, P, D);
-    TRY(reg_f32(m, tm + "embeddings.token_embedding.weight", &m->c_tok, (int64_t)c.vocab * T));
-    TRY(reg_f32(m, tm + "embeddings.position_embedding.weight", &m->tpos, (int64_t)c.max_pos * T));
-    m->ctl.resize(c.t_layers);
-    for (int i = 0; i < c.t_layers; ++i) TRY(reg_clip_layer(m, tm + "encoder.layers." + std::to_string(i) + ".", m->ctl[i], T, c.t_ffn));
-    TRY(reg_f32(m, tm + "final_layer_norm.weight", &m->c_lnf_g, T));
-    TRY(reg_f32(m, tm + "final_layer_norm.bias", &m->c_lnf_b, T));
+    TRY(reg_f32(m, "text_model.embeddings.token_embedding.weight", &m->c_tok, (int64_t)c.vocab * T));
+    TRY(reg_f32(m, "text_model.embeddings.position_embedding.weight", &m->tpos, (int64_t)c.max_pos * T));
+    TRY(reg_tower(m, kClipText, m->ctl, c.t_layers, T, c.t_ffn, &m->c_lnf_g, &m->c_lnf_b));
     TRY(walloc(m, (void**)&m->c_tproj, (size_t)P * T * 4));
     add_slot(m, "text_projection.weight", m->c_tproj, CAP_DT_F32, P, T);
     TRY(reg_f32(m, "logit_scale", &m->c_logit, 1));
     // arena: image rows [max_batch * tokens, .], text rows [max_batch * max_len, .]
-    const size_t Bm = c.max_batch, Mi = Bm * m->NT, Mt = Bm * c.max_len, e = m->esz;
-    TRY(dev_alloc(m, &m->patches, Bm * m->P * m->Kpad * e));
-    CAP_HIP_CHECK(hipMemset(m->patches, 0, Bm * m->P * m->Kpad * e));
-    TRY(dev_alloc(m, (void**)&m->X, Mi * D * 4));
-    TRY(dev_alloc(m, &m->ln, Mi * D * e));
-    TRY(dev_alloc(m, &m->qkv, Mi * 3 * D * 4));          // 4 bytes: the split mode's fp32 q|k|v where attention cannot take G8
-    TRY(dev_alloc(m, &m->ctx, Mi * D * e));
-    TRY(dev_alloc(m, &m->mlp, Mi * c.v_mlp * e));
-    TRY(dev_alloc(m, (void**)&m->c_x, Mt * T * 4));
-    TRY(dev_alloc(m, &m->c_ln, Mt * T * e));
-    TRY(dev_alloc(m, &m->c_qkv, Mt * 3 * T * 4));
-    TRY(dev_alloc(m, &m->c_ctx, Mt * T * e));
-    TRY(dev_alloc(m, &m->c_mlp, Mt * c.t_ffn * e));
-    if (!vit_adds_in_place(m->gdt)) {
-        TRY(dev_alloc(m, (void**)&m->delta, Mi * D * 4));
-        TRY(dev_alloc(m, (void**)&m->c_delta, Mt * T * 4));
-    }
-    return 0;
+    TRY(alloc_image_tower(m));
+    return alloc_tower(m, m->ct, (size_t)c.max_batch * c.max_len, T, c.t_ffn);
 }
 
-// The pre-LN blocks of one CLIP tower over the fp32 residual stream X [B * N, D] (as run_encoder's ViT loop); on return X holds
-// the last hidden states (the exact fp32 mode's last branch output folded in).  causal: the text tower's mask - the generic
-// attention kernel, which in the split mode reads fp32 q|k|v (the G8 kernel takes no mask).
-struct ClipTags { const char *ln, *qkv, *attn, *proj, *fc1, *fc2; };
-int run_clip_blocks(Captioner* m, hipStream_t s, const std::vector<VLayer>& layers, float* X, float* delta, void* ln, void* qkv, void* ctx,
-                    void* mlp, int B, int N, int D, int H, int F, float eps, bool causal, const ClipTags& tg) {
-    const int M = B * N, act = m->c.hidden_act == CAP_ACT_GELU ? 1 : 3;
-    const bool in_place = vit_adds_in_place(m->gdt);
-    const bool g8_attn = !causal && m->gdt == CAP_DT_G8 && vit_attention_takes_g8(N);
-    bool pending = false;
-    auto add_ln = [&](const float* g, const float* b, void* out_t) -> int {
-        ProfScope ps(m, s, tg.ln, 0, (double)M * D * ((pending ? 12 : 4) + (out_t ? m->esz : 4)));
-        if (pending) return launch_reduce_layernorm(m->gdt, delta, 1, nullptr, X, g, b, eps, out_t, nullptr, X, M, D, s, false, false);
-        return launch_layernorm(m->gdt, X, D, g, b, eps, out_t, nullptr, M, D, s);
-    };
-    for (const VLayer& L : layers) {
-        TRY(add_ln(L.ln1_g, L.ln1_b, ln));
-        TRY(gemm(m, s, tg.qkv, ln, D, L.w_qkv, D, qkv, 3 * D, L.b_qkv, nullptr, M, 3 * D, D, 0, (m->gdt == CAP_DT_G8 && !g8_attn) ? 1 : 0));
-        {
-            ProfScope ps(m, s, tg.attn, (causal ? 2.0 : 4.0) * B * H * (double)N * N * 64, (double)M * 4 * D * m->esz);
-            TRY(launch_vit_attention(g8_attn ? CAP_DT_G8 : m->dt, qkv, ctx, B, N, H, 0, s, D / H, causal ? 1 : 0, m->gdt));
-        }
-        if (in_place) TRY(gemm(m, s, tg.proj, ctx, D, L.w_proj, D, X, D, L.b_proj, X, M, D, D, 0, 1));
-        else TRY(gemm(m, s, tg.proj, ctx, D, L.w_proj, D, delta, D, L.b_proj, nullptr, M, D, D, 0, 1));
-        pending = !in_place;
-        TRY(add_ln(L.ln2_g, L.ln2_b, ln));
-        TRY(gemm(m, s, tg.fc1, ln, D, L.w_fc1, D, mlp, F, L.b_fc1, nullptr, M, F, D, act, 0));
-        if (in_place) TRY(gemm(m, s, tg.fc2, mlp, F, L.w_fc2, F, X, D, L.b_fc2, X, M, D, F, 0, 1));
-        else TRY(gemm(m, s, tg.fc2, mlp, F, L.w_fc2, F, delta, D, L.b_fc2, nullptr, M, D, F, 0, 1));
-    }
-    if (pending) {      // fold the last fc2 output into X; the head kernel applies the final LayerNorm to the pooled rows
-        ProfScope ps(m, s, tg.ln, 0, (double)M * D * 12);
-        const VLayer& L = layers.back();
-        TRY(launch_reduce_layernorm(m->gdt, delta, 1, nullptr, X, L.ln2_g, L.ln2_b, eps, nullptr, nullptr, X, M, D, s, false, false));
-    }
-    return 0;
-}
+int clip_act(const Captioner* m) { return m->c.hidden_act == CAP_ACT_GELU ? 1 : 3; }
 
 int run_clip_images(Captioner* m, const void* pixels, int fmt, int B, float* out, hipStream_t s) {
     const CapConfig& c = m->c;
     const int D = c.v_hidden, NT = m->NT;
-    {
-        ProfScope ps(m, s, "clip_patchify", 0, (double)B * 3 * c.image_size * c.image_size * (fmt ? 1 : 4) + (double)B * m->P * m->Kpad * m->esz);
-        TRY(launch_patchify(m->gdt, pixels, fmt, B, c.image_size, c.patch_size, m->Kpad, m->patches, c.pix_mean, c.pix_std, s));
-    }
-    TRY(gemm(m, s, "clip_v_gemm_patch", m->patches, m->Kpad, m->w_patch, m->Kpad, m->X, D, nullptr, nullptr, B * m->P, D, m->Kpad, 0, 1,
-             EPI_PATCH, m->P, 0, 0, 0, m->vpos));
-    TRY(launch_cls_rows(m->cls, m->vpos, m->X, B, NT, D, s));
-    {
-        ProfScope ps(m, s, "clip_v_layernorm", 0, (double)B * NT * D * 8);
-        TRY(launch_layernorm(m->dt, m->X, D, m->ln_pre_g, m->ln_pre_b, c.v_eps, nullptr, m->X, B * NT, D, s));
-    }
-    static const ClipTags tg = {"clip_v_layernorm", "clip_v_gemm_qkv", "clip_v_attention", "clip_v_gemm_proj", "clip_v_gemm_fc1", "clip_v_gemm_fc2"};
-    TRY(run_clip_blocks(m, s, m->vl, m->X, (float*)m->delta, m->ln, m->qkv, m->ctx, m->mlp, B, NT, D, c.v_heads, c.v_mlp, c.v_eps, false, tg));
+    TRY(run_stem(m, pixels, fmt, B, kClipImageTags, s));
+    TRY(run_tower(m, s, m->vl, m->vt, B, NT, D, c.v_heads, c.v_mlp, c.v_eps, clip_act(m), false, kClipImageTags, nullptr, nullptr,
+                  nullptr, nullptr));
     ProfScope ps(m, s, "clip_v_head", 2.0 * B * D * c.embed_dim, (double)B * D * 4 + (double)c.embed_dim * D * 4);
-    return launch_clip_head(m->X, NT, nullptr, m->post_g, m->post_b, c.v_eps, m->c_vproj, out, B, D, c.embed_dim, s);
+    return launch_clip_head(m->vt.X, NT, nullptr, m->post_g, m->post_b, c.v_eps, m->c_vproj, out, B, D, c.embed_dim, s);
 }
 
 int run_clip_text(Captioner* m, const int* ids, const int* lens, int B, int L, float* out, hipStream_t s) {
@@ -1187,63 +1155,12 @@ int run_clip_text(Captioner* m, const int* ids, const int* lens, int B, int L, f
     const int T = c.t_hidden;
     {
         ProfScope ps(m, s, "clip_t_embed", 0, (double)B * L * T * 12);
-        TRY(launch_clip_embed_text(ids, L, m->c_tok, m->tpos, m->c_x, B * L, T, c.vocab, s));
+        TRY(launch_clip_embed_text(ids, L, m->c_tok, m->tpos, m->ct.X, B * L, T, c.vocab, s));
     }
-    static const ClipTags tg = {"clip_t_layernorm", "clip_t_gemm_qkv", "clip_t_attention", "clip_t_gemm_proj", "clip_t_gemm_fc1", "clip_t_gemm_fc2"};
-    TRY(run_clip_blocks(m, s, m->ctl, m->c_x, m->c_delta, m->c_ln, m->c_qkv, m->c_ctx, m->c_mlp, B, L, T, c.t_heads, c.t_ffn, c.t_eps, true, tg));
+    TRY(run_tower(m, s, m->ctl, m->ct, B, L, T, c.t_heads, c.t_ffn, c.t_eps, clip_act(m), true, kClipTextTags, nullptr, nullptr,
+                  nullptr, nullptr));
     ProfScope ps(m, s, "clip_t_head", 2.0 * B * T * c.embed_dim, (double)B * T * 4 + (double)c.embed_dim * T * 4);
-    return launch_clip_head(m->c_x, L, lens, m->c_lnf_g, m->c_lnf_b, c.t_eps, m->c_tproj, out, B, T, c.embed_dim, s);
-}
-
-// ---------------------------------------------------------------------------------------------- encoder
-int run_encoder(Captioner* m, const void* pixels, int fmt, int B, float* out_embeds, hipStream_t s) {
-    // BLIP: final LayerNorm = post_layernorm -> image_embeds (fp32 to the caller + T for the cross-K/V GEMM).
-    // CoCa: ln_pre after the embeddings; final LayerNorm = the pooler's ln_k -> T only (run_coca_pool continues).
-    const bool coca = m->c.arch == CAP_ARCH_COCA;
-    const CapConfig& c = m->c;
-    const int D = c.v_hidden, NT = m->NT, M = B * NT, H = c.v_heads;
-    {
-        ProfScope ps(m, s, "patchify", 0, (double)B * 3 * c.image_size * c.image_size * (fmt ? 1 : 4) + (double)B * m->P * m->Kpad * m->esz);
-        TRY(launch_patchify(m->gdt, pixels, fmt, B, c.image_size, c.patch_size, m->Kpad, m->patches, c.pix_mean, c.pix_std, s));
-    }
-    TRY(gemm(m, s, "gemm_patch", m->patches, m->Kpad, m->w_patch, m->Kpad, m->X, D, m->b_patch, nullptr, B * m->P, D,
-             m->Kpad, 0, 1, EPI_PATCH, m->P, 0, 0, 0, m->vpos));
-    TRY(launch_cls_rows(m->cls, m->vpos, m->X, B, NT, D, s));
-    if (coca) TRY(launch_layernorm(m->dt, m->X, D, m->ln_pre_g, m->ln_pre_b, c.v_eps, nullptr, m->X, M, D, s));
-    // Pre-LN blocks.  Exact fp32 mode: the two branch GEMMs (proj, fc2) write their output to `delta`; the next LayerNorm kernel
-    // folds it into the residual stream X (fp32) in the same pass that normalises it, so the GEMM epilogues are store-only.
-    // Other modes: the branch GEMMs add into X themselves (vit_adds_in_place).
-    const bool in_place = vit_adds_in_place(m->gdt);
-    bool pending = false;                                  // delta holds a branch output not yet added to X
-    auto add_ln = [&](const float* g, const float* b, void* out_t, float* out_f) -> int {
-        ProfScope ps(m, s, "layernorm", 0, (double)M * D * ((pending ? 8 + (kDeltaInT ? m->esz : 4) : 4) + m->esz + (out_f ? 4 : 0)));
-        if (pending)
-            return launch_reduce_layernorm(m->gdt, m->delta, 1, nullptr, m->X, g, b, c.v_eps, out_t, out_f, m->X, M, D, s, false, kDeltaInT);
-        return launch_layernorm(m->gdt, m->X, D, g, b, c.v_eps, out_t, out_f, M, D, s);
-    };
-    for (int i = 0; i < c.v_layers; ++i) {
-        const VLayer& L = m->vl[i];
-        TRY(add_ln(L.ln1_g, L.ln1_b, m->ln, nullptr));
-        // split mode: q|k|v stay G8 when the split-fp16 MFMA attention kernel covers this token count, else the GEMM writes
-        // fp32 for the fp32 attention kernels; either way the context comes out as G8 (the proj GEMM's operand)
-        const bool g8_attn = m->gdt == CAP_DT_G8 && D / H == 64 && vit_attention_takes_g8(NT);
-        TRY(gemm(m, s, "gemm_qkv", m->ln, D, L.w_qkv, D, m->qkv, 3 * D, L.b_qkv, nullptr, M, 3 * D, D, 0,
-                 (m->gdt == CAP_DT_G8 && !g8_attn) ? 1 : 0));
-        {
-            ProfScope ps(m, s, "vit_attention", 4.0 * B * H * (double)NT * NT * 64, (double)M * 4 * D * m->esz);
-            TRY(launch_vit_attention(g8_attn ? CAP_DT_G8 : m->dt, m->qkv, m->ctx, B, NT, H, 0, s, D / H, 0, m->gdt));
-        }
-        if (in_place) TRY(gemm(m, s, "gemm_proj", m->ctx, D, L.w_proj, D, m->X, D, L.b_proj, m->X, M, D, D, 0, 1));
-        else TRY(gemm(m, s, "gemm_proj", m->ctx, D, L.w_proj, D, m->delta, D, L.b_proj, nullptr, M, D, D, 0, kDeltaInT ? 0 : 1));
-        pending = !in_place;
-        TRY(add_ln(L.ln2_g, L.ln2_b, m->ln, nullptr));
-        TRY(gemm(m, s, "gemm_fc1", m->ln, D, L.w_fc1, D, m->mlp, c.v_mlp, L.b_fc1, nullptr, M, c.v_mlp, D, 1, 0));
-        if (in_place) TRY(gemm(m, s, "gemm_fc2", m->mlp, c.v_mlp, L.w_fc2, c.v_mlp, m->X, D, L.b_fc2, m->X, M, D, c.v_mlp, 0, 1));
-        else TRY(gemm(m, s, "gemm_fc2", m->mlp, c.v_mlp, L.w_fc2, c.v_mlp, m->delta, D, L.b_fc2, nullptr, M, D, c.v_mlp, 0, kDeltaInT ? 0 : 1));
-    }
-    if (coca) TRY(add_ln(m->lnk_g, m->lnk_b, m->emb_t, nullptr));
-    else TRY(add_ln(m->post_g, m->post_b, m->emb_t, out_embeds ? out_embeds : m->emb_f));
-    return 0;
+    return launch_clip_head(m->ct.X, L, lens, m->c_lnf_g, m->c_lnf_b, c.t_eps, m->c_tproj, out, B, T, c.embed_dim, s);
 }
 
 // CoCa attentional pooler + ln_post, then the affine-free normalisation that feeds the folded cross-K/V projection.
@@ -1372,7 +1289,7 @@ int gemm_splitk_reduce_ln(Captioner* m, hipStream_t s, const Dec& d, const char*
     // keeps its round-5 threshold of 512 rows: a dead row costs it one wave's dispatch instead of four, and most steps of a 768-row
     // pass have far fewer live rows than that - same box, `bench.py --lite`, three interleaved pairs, 512 / 832: 6 476 / 6 460, 6 511 /
     // 6 476, 6 525 / 6 491 captions/s (+0.4 %).
-    return launch_reduce_layernorm(m->gdt, d.dpart, S, bias, resid ? resid : d.dx, g, b, eps, out_t, out_f, y_out, d.R, N, s, per_row_block, false, d.map.n);
+    return launch_reduce_layernorm(m->gdt, d.dpart, S, bias, resid ? resid : d.dx, g, b, eps, out_t, out_f, y_out, d.R, N, s, per_row_block, d.map.n);
 }
 
 // x: the fp32 LayerNorm row buffer the consumer adds as its residual and replaces (d.dx, or d.dx2 on the fused paths)
@@ -2324,7 +2241,7 @@ int cap_op_reduce_layernorm(int dtype, const float* part, int S, const float* bi
                             const float* beta, float eps, void* out_t, float* out_f, float* y_out, int M, int D,
                             int per_row_block, void* stream) {
     return launch_reduce_layernorm(dt_of(dtype), part, S, bias, resid, gamma, beta, eps, out_t, out_f, y_out, M, D,
-                                   (hipStream_t)stream, per_row_block != 0, false);
+                                   (hipStream_t)stream, per_row_block != 0);
 }
 int cap_op_gemm_skinny(const void* A, const void* W, const float* bias, int act, void* out, float* part, int M, int N, int K,
                        void* stream) {

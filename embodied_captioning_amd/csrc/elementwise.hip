@@ -92,16 +92,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 
 // Consumer of a split-K GEMM (EPI_PARTIAL): y = sum_z partial[z] + bias + resid, summed in slice order (deterministic),
 // then LayerNorm -> out_f (fp32 residual stream) and out_t (next GEMM's A operand).
-template <typename P> __device__ __forceinline__ float4 load4f(const P* p);
-template <> __device__ __forceinline__ float4 load4f<float>(const float* p) { return *(const float4*)p; }
-template <> __device__ __forceinline__ float4 load4f<bf16_t>(const bf16_t* p) {
-    const bf16x4 r = *(const bf16x4*)p;
-    return make_float4((float)r[0], (float)r[1], (float)r[2], (float)r[3]);
-}
-
-// P = element type of the partial sums: fp32 (split-K slices) or the compute type (the ViT branch outputs in `delta`).
-template <typename T, typename P, int MAXV>
-__global__ __launch_bounds__(256) void reduce_layernorm_kernel(const P* __restrict__ part, int S,
+// part: fp32 partial sums - S split-K slices, or one branch output (the ViT blocks' `delta`).
+template <typename T, int MAXV>
+__global__ __launch_bounds__(256) void reduce_layernorm_kernel(const float* __restrict__ part, int S,
                                                                 const float* __restrict__ bias,
                                                                 const float* __restrict__ resid,
                                                                 const float* __restrict__ gamma,
@@ -119,17 +112,17 @@ __global__ __launch_bounds__(256) void reduce_layernorm_kernel(const P* __restri
     for (int i = 0; i < MAXV; ++i) {
         const int c = lane * 4 + i * 256;
         if (i < nv && c < D) {
-            float4 a = load4f<P>(part + (size_t)row * D + c);
+            float4 a = *(const float4*)(part + (size_t)row * D + c);
             if (S == 4) {
-                const float4 b1 = load4f<P>(part + ((size_t)1 * M + row) * D + c);
-                const float4 b2 = load4f<P>(part + ((size_t)2 * M + row) * D + c);
-                const float4 b3 = load4f<P>(part + ((size_t)3 * M + row) * D + c);
+                const float4 b1 = *(const float4*)(part + ((size_t)1 * M + row) * D + c);
+                const float4 b2 = *(const float4*)(part + ((size_t)2 * M + row) * D + c);
+                const float4 b3 = *(const float4*)(part + ((size_t)3 * M + row) * D + c);
                 a.x = ((a.x + b1.x) + b2.x) + b3.x; a.y = ((a.y + b1.y) + b2.y) + b3.y;
                 a.z = ((a.z + b1.z) + b2.z) + b3.z; a.w = ((a.w + b1.w) + b2.w) + b3.w;
             } else {
 #pragma unroll 4
                 for (int z = 1; z < S; ++z) {
-                    const float4 b = load4f<P>(part + ((size_t)z * M + row) * D + c);
+                    const float4 b = *(const float4*)(part + ((size_t)z * M + row) * D + c);
                     a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
                 }
             }
@@ -545,25 +538,24 @@ int launch_layernorm(int dtype, const float* in, int ld_in, const float* gamma, 
     return 0;
 }
 
-int launch_reduce_layernorm(int dtype, const void* part, int S, const float* bias, const float* resid,
+int launch_reduce_layernorm(int dtype, const float* part, int S, const float* bias, const float* resid,
                             const float* gamma, const float* beta, float eps, void* out_t, float* out_f, float* y_out,
-                            int M, int D, hipStream_t s, bool per_row_block, bool part_in_t, const int* n_rows) {
+                            int M, int D, hipStream_t s, bool per_row_block, const int* n_rows) {
     if (n_rows && per_row_block && D > 1024) { cap_set_error("reduce_layernorm: the wide block kernel takes no row count from the device"); return -1; }
-    if (per_row_block && part_in_t) { cap_set_error("reduce_layernorm: the per-row-block kernel takes fp32 partial sums"); return -1; }
     if (D % 4 != 0 || D > 256 * LN_MAXV || S < 1 || (dtype == CAP_DT_G8 && D % 8 != 0)) { cap_set_error("reduce_layernorm: unsupported width %d / slices %d", D, S); return -1; }
     // per_row_block: the decoder's choice up to a few hundred rows (latency-bound).  For rows up to 1024 wide the block-per-row
     // kernel forms the wave-per-row kernel's sums in its order (slices, bias, residual; statistics: thread j + 64 i = lane j,
     // vector i) and the two agree bit for bit (tests/test_kernels_gpu.py::test_reduce_layernorm_kernels_agree_bit_for_bit), so a
     // caller may pick by row count there; the WIDE block kernel (rows beyond 1024) has its own order: by path only.
     if (per_row_block && D <= 1024) {
-#define CAP_RR(TT) hipLaunchKernelGGL(reduce_layernorm_row_kernel<TT>, dim3(M), dim3(256), 0, s, (const float*)part, S, bias, resid, gamma, beta, eps, (TT*)out_t, out_f, y_out, M, D, n_rows)
+#define CAP_RR(TT) hipLaunchKernelGGL(reduce_layernorm_row_kernel<TT>, dim3(M), dim3(256), 0, s, part, S, bias, resid, gamma, beta, eps, (TT*)out_t, out_f, y_out, M, D, n_rows)
         CAP_DISPATCH_T(dtype, CAP_RR);
 #undef CAP_RR
         CAP_HIP_CHECK(hipGetLastError());
         return 0;
     }
     if (per_row_block && D <= 3072) {     // wide rows, decode-sized row count (the caller's choice, as above)
-#define CAP_RW(TT) hipLaunchKernelGGL(reduce_layernorm_wide_kernel<TT>, dim3(M), dim3(256), 0, s, (const float*)part, S, bias, resid, gamma, beta, eps, (TT*)out_t, out_f, y_out, M, D)
+#define CAP_RW(TT) hipLaunchKernelGGL(reduce_layernorm_wide_kernel<TT>, dim3(M), dim3(256), 0, s, part, S, bias, resid, gamma, beta, eps, (TT*)out_t, out_f, y_out, M, D)
         CAP_DISPATCH_T(dtype, CAP_RW);
 #undef CAP_RW
         CAP_HIP_CHECK(hipGetLastError());
@@ -571,14 +563,11 @@ int launch_reduce_layernorm(int dtype, const void* part, int S, const float* bia
     }
     const int wpb = M >= 2048 ? 4 : 1;
     const dim3 grid((M + wpb - 1) / wpb), block(64 * wpb);
-#define CAP_RLN(TT, PP, MV)                                                                                             \
-    hipLaunchKernelGGL((reduce_layernorm_kernel<TT, PP, MV>), grid, block, 0, s, (const PP*)part, S, bias, resid, gamma,  \
-                       beta, eps, (TT*)out_t, out_f, y_out, M, D, n_rows)
-#define CAP_RLN_T(TT, PP) do { if (D <= 1024) CAP_RLN(TT, PP, 4); else if (D <= 2048) CAP_RLN(TT, PP, 8); else CAP_RLN(TT, PP, LN_MAXV); } while (0)
-    if (dtype == CAP_DT_BF16 && part_in_t) CAP_RLN_T(bf16_t, bf16_t);
-    else if (dtype == CAP_DT_BF16) CAP_RLN_T(bf16_t, float);
-    else if (dtype == CAP_DT_G8) CAP_RLN_T(g8_t, float);
-    else CAP_RLN_T(float, float);
+#define CAP_RLN(TT, MV)                                                                                                 \
+    hipLaunchKernelGGL((reduce_layernorm_kernel<TT, MV>), grid, block, 0, s, part, S, bias, resid, gamma, beta, eps,     \
+                       (TT*)out_t, out_f, y_out, M, D, n_rows)
+#define CAP_RLN_T(TT) do { if (D <= 1024) CAP_RLN(TT, 4); else if (D <= 2048) CAP_RLN(TT, 8); else CAP_RLN(TT, LN_MAXV); } while (0)
+    CAP_DISPATCH_T(dtype, CAP_RLN_T);
 #undef CAP_RLN_T
 #undef CAP_RLN
     CAP_HIP_CHECK(hipGetLastError());
