@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libcaptioner_hip.so")
 CAP_F32, CAP_BF16, CAP_F32_SPLIT = 0, 1, 2
 CAP_PIX_F32_NCHW, CAP_PIX_U8_NHWC = 0, 1
 CAP_ARCH_CLIP = 4
+CAP_ARCH_BLIP2_ITM = 5
 CAP_ACT_QUICK_GELU, CAP_ACT_GELU = 0, 1
 
 
@@ -94,6 +95,14 @@ _SIGNATURES = {
     "cap_clip_embed_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cap_clip_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     "cap_clip_logit_scale": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "cap_blip2_itm_encode_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "cap_blip2_itc_image_features": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "cap_blip2_itc_text_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cap_blip2_itc_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "cap_blip2_itm_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cap_op_generic_attention": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "cap_op_itm_self_attention": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.c_void_p]),
     "cap_op_convert": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cap_op_convert_weight": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
 }

@@ -237,6 +237,105 @@ class Blip2Arch:
 
 
 @dataclasses.dataclass
+class Blip2ItmArch:
+    """BLIP-2 image-text matching / contrastive scorer, HF `Blip2ForImageTextRetrieval` (the port of the LAVIS
+    `blip2_image_text_matching` model behind the reference's `--method blip2_itm | blip2_itc`,
+    experimenting_env/captioner/pseudocaptioner.py:34-37).  Defaults = `Salesforce/blip2-itm-vit-g`: ViT-g/14 at 224 px (39 x 1408,
+    16 heads of 88), Q-Former 12 x 768 (12 heads, 32 queries, cross-attention every 2nd layer) WITH its text side (BERT word /
+    position embeddings, vocabulary 30523, 512 positions), projections to 256.  `...-vit-g-coco` is the same at 364 px."""
+    image_size: int = 224
+    patch_size: int = 14
+    v_hidden: int = 1408
+    v_layers: int = 39
+    v_heads: int = 16
+    v_mlp: int = 6144
+    v_eps: float = 1e-6
+    q_hidden: int = 768
+    q_layers: int = 12
+    q_heads: int = 12
+    q_ffn: int = 3072
+    q_cross_freq: int = 2
+    q_eps: float = 1e-12
+    num_query_tokens: int = 32
+    vocab: int = 30523
+    max_pos: int = 512
+    pad: int = 0
+    projection_dim: int = 256
+    max_text_len: int = 32        # the reference's tokenizer call: truncation=True, max_length=32 (:292)
+
+    @property
+    def n_patches(self) -> int:
+        return (self.image_size // self.patch_size) ** 2
+
+    @property
+    def n_tokens(self) -> int:
+        return self.n_patches + 1
+
+    @staticmethod
+    def tiny() -> "Blip2ItmArch":
+        """Fixture-sized config (tests/golden/blip2_itm_tiny.npz): the tiny BLIP-2 tower (28 px, 5 tokens, heads of 24) and Q-Former
+        (2 x 128, heads of 64, 8 queries), vocabulary 300, 40 positions, projection 64."""
+        return Blip2ItmArch(image_size=28, patch_size=14, v_hidden=192, v_layers=2, v_heads=8, v_mlp=256, q_hidden=128, q_layers=2,
+                            q_heads=2, q_ffn=256, num_query_tokens=8, vocab=300, max_pos=40, projection_dim=64)
+
+    @staticmethod
+    def width(image_size: int = 224) -> "Blip2ItmArch":
+        """Production widths with two layers per tower (tests/golden/blip2_itm_width.npz)."""
+        return Blip2ItmArch(image_size=image_size, v_layers=2, q_layers=2)
+
+    def hf_config_dict(self) -> dict:
+        """The `Blip2Config` of this arch (what `from_hf_config` reads back)."""
+        return dict(
+            num_query_tokens=self.num_query_tokens, image_text_hidden_size=self.projection_dim, image_token_index=None,
+            vision_config=dict(hidden_size=self.v_hidden, num_hidden_layers=self.v_layers, num_attention_heads=self.v_heads,
+                               intermediate_size=self.v_mlp, image_size=self.image_size, patch_size=self.patch_size,
+                               layer_norm_eps=self.v_eps, hidden_act="gelu", qkv_bias=True),
+            qformer_config=dict(hidden_size=self.q_hidden, num_hidden_layers=self.q_layers, num_attention_heads=self.q_heads,
+                                intermediate_size=self.q_ffn, cross_attention_frequency=self.q_cross_freq, layer_norm_eps=self.q_eps,
+                                encoder_hidden_size=self.v_hidden, vocab_size=self.vocab, max_position_embeddings=self.max_pos,
+                                pad_token_id=self.pad, hidden_act="gelu", use_qformer_text_input=True))
+
+    @staticmethod
+    def from_hf_config(path_or_dict) -> "Blip2ItmArch":
+        """Read a HF `Blip2Config` ``config.json`` (checkpoint directory, file or parsed dict) of an image-text retrieval
+        checkpoint: `qformer_config.use_qformer_text_input` must be true and `image_token_index` absent."""
+        if isinstance(path_or_dict, (str, os.PathLike)):
+            p = path_or_dict
+            if os.path.isdir(p):
+                p = os.path.join(p, "config.json")
+            with open(p) as f:
+                cfg = json.load(f)
+        else:
+            cfg = dict(path_or_dict)
+        v = cfg.get("vision_config") or {}
+        q = cfg.get("qformer_config") or {}
+        d = Blip2ItmArch()
+        if not q.get("use_qformer_text_input", False):
+            raise ValueError("this BLIP-2 checkpoint has no Q-Former text side (qformer_config.use_qformer_text_input is false): "
+                             "it is a captioning checkpoint, not an image-text matching one")
+        if cfg.get("image_token_index") is not None:
+            raise ValueError("BLIP-2 checkpoints with image placeholder ids (image_token_index) are not supported by the scorer")
+        for name, c in (("vision_config", v), ("qformer_config", q)):
+            if c.get("hidden_act", "gelu") != "gelu":
+                raise ValueError(f"{name}.hidden_act {c.get('hidden_act')!r} is not supported (the towers run exact gelu)")
+        if not v.get("qkv_bias", True):
+            raise ValueError("vision_config.qkv_bias = false is not supported")
+        if q.get("encoder_hidden_size", v.get("hidden_size", d.v_hidden)) != v.get("hidden_size", d.v_hidden):
+            raise ValueError("qformer_config.encoder_hidden_size differs from the vision tower's width")
+        return Blip2ItmArch(
+            image_size=v.get("image_size", d.image_size), patch_size=v.get("patch_size", d.patch_size),
+            v_hidden=v.get("hidden_size", d.v_hidden), v_layers=v.get("num_hidden_layers", d.v_layers),
+            v_heads=v.get("num_attention_heads", d.v_heads), v_mlp=v.get("intermediate_size", d.v_mlp),
+            v_eps=v.get("layer_norm_eps", d.v_eps),
+            q_hidden=q.get("hidden_size", d.q_hidden), q_layers=q.get("num_hidden_layers", d.q_layers),
+            q_heads=q.get("num_attention_heads", d.q_heads), q_ffn=q.get("intermediate_size", d.q_ffn),
+            q_cross_freq=q.get("cross_attention_frequency", d.q_cross_freq), q_eps=q.get("layer_norm_eps", d.q_eps),
+            num_query_tokens=cfg.get("num_query_tokens", d.num_query_tokens), vocab=q.get("vocab_size", 30522),
+            max_pos=q.get("max_position_embeddings", d.max_pos), pad=q.get("pad_token_id", d.pad),
+            projection_dim=cfg.get("image_text_hidden_size", d.projection_dim))
+
+
+@dataclasses.dataclass
 class ClipArch:
     """HF `CLIPModel` (the reference's `--method clip` scorer: `openai/clip-vit-base-patch32`,
     experimenting_env/captioner/pseudocaptioner.py:39-46).  Defaults = ViT-B/32: a 224 px image tower of 12 x 768 (12 heads,

@@ -86,6 +86,9 @@ struct QLayer {            // BLIP-2 Q-Former layer (queries only): self-attenti
     void *w_qkv = nullptr, *w_so = nullptr, *w_cq = nullptr, *w_ckv = nullptr, *w_co = nullptr, *w_f1 = nullptr, *w_f2 = nullptr;
     float *b_qkv = nullptr, *b_so = nullptr, *so_g = nullptr, *so_b = nullptr, *b_cq = nullptr, *b_ckv = nullptr, *b_co = nullptr,
           *co_g = nullptr, *co_b = nullptr, *b_f1 = nullptr, *b_f2 = nullptr, *f_g = nullptr, *f_b = nullptr;
+    // CAP_ARCH_BLIP2_ITM: the text rows' own FFN (intermediate / output beside intermediate_query / output_query)
+    void *w_t1 = nullptr, *w_t2 = nullptr;
+    float *b_t1 = nullptr, *b_t2 = nullptr, *t_g = nullptr, *t_b = nullptr;
 };
 // int8 weights: up to this many crops per call the prompt pass (crops x 33 rows) runs on the weight-streaming kernels like a decode
 // step; beyond, it is a GEMM proper and goes to the tiled kernels (run_opt).  Within each range a crop's bits do not depend on the
@@ -207,6 +210,14 @@ struct Captioner {
     std::vector<VLayer> ctl;
     Tower ct;
     float *c_vproj = nullptr, *c_tproj = nullptr, *c_tok = nullptr, *c_lnf_g = nullptr, *c_lnf_b = nullptr, *c_logit = nullptr;
+    // ---- BLIP-2 image-text scorer (CAP_ARCH_BLIP2_ITM): image tower on (vl, vt), Q-Former layers in ql with both FFN sets; the
+    // text rows [max_batch * max_len, .] beside the query rows (qx ..); heads fp32 for the head kernels.  itm_ckv holds the cross
+    // K/V of every cross-attention layer for the itm_B images of the last cap_blip2_itm_encode_images: [layer][B * NT, 2 Q].
+    float *i_word = nullptr, *i_pos = nullptr, *i_ln_g = nullptr, *i_ln_b = nullptr, *i_vproj = nullptr, *i_vproj_b = nullptr,
+          *i_tproj = nullptr, *i_tproj_b = nullptr, *i_head = nullptr, *i_head_b = nullptr;
+    float *tx = nullptr, *ty = nullptr;
+    void *tx_t = nullptr, *tqkv = nullptr, *tctx = nullptr, *th = nullptr, *itm_ckv = nullptr;
+    int itm_B = 0;
     // profiling
     bool prof = false;
     std::vector<ProfTag> prof_recs;
@@ -619,14 +630,12 @@ __global__ void copy_new_tokens_kernel(const int* seq, int seq_ld, int P, const 
     if (out_len)
         for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) out_len[b] = min(lens[b] - P, n);
 }
-// HF `Blip2ForConditionalGeneration` state-dict names (transformers 5.x).  `derived.qformer_x0` = qformer.layernorm(
-// query_tokens), computed once by the host loader (a constant of the checkpoint).
-int build_blip2(Captioner* m) {
+// The Q-Former: `derived.qformer_x0` = qformer.layernorm(query_tokens), computed once by the host loader (a constant of the
+// checkpoint), and the layers - text_ffn: with the text rows' FFN (`intermediate` / `output`) beside the query rows' (the
+// image-text scorer; `use_qformer_text_input` checkpoints).
+int reg_qformer(Captioner* m, bool text_ffn) {
     const CapConfig& c = m->c;
-    const int D = c.v_hidden, Q = c.q_hidden, F = c.q_ffn, T = c.t_hidden, G = c.t_ffn, V = c.vocab, nq = c.num_query_tokens;
-    TRY(reg_stem(m, kBlipVision));
-    TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
-
+    const int D = c.v_hidden, Q = c.q_hidden, F = c.q_ffn, nq = c.num_query_tokens;
     TRY(reg_f32(m, "derived.qformer_x0", &m->q_x0, (int64_t)nq * Q));
     m->ql.resize(c.q_layers);
     const char* nm[3] = {"query.", "key.", "value."};
@@ -654,7 +663,25 @@ int build_blip2(Captioner* m) {
         TRY(reg_f32(m, p + "output_query.dense.bias", &L.b_f2, Q));
         TRY(reg_f32(m, p + "output_query.LayerNorm.weight", &L.f_g, Q));
         TRY(reg_f32(m, p + "output_query.LayerNorm.bias", &L.f_b, Q));
+        if (!text_ffn) continue;
+        TRY(reg_mat(m, p + "intermediate.dense.weight", &L.w_t1, F, Q));
+        TRY(reg_f32(m, p + "intermediate.dense.bias", &L.b_t1, F));
+        TRY(reg_mat(m, p + "output.dense.weight", &L.w_t2, Q, F));
+        TRY(reg_f32(m, p + "output.dense.bias", &L.b_t2, Q));
+        TRY(reg_f32(m, p + "output.LayerNorm.weight", &L.t_g, Q));
+        TRY(reg_f32(m, p + "output.LayerNorm.bias", &L.t_b, Q));
     }
+    return 0;
+}
+
+// HF `Blip2ForConditionalGeneration` state-dict names (transformers 5.x).
+int build_blip2(Captioner* m) {
+    const CapConfig& c = m->c;
+    const int D = c.v_hidden, Q = c.q_hidden, F = c.q_ffn, T = c.t_hidden, G = c.t_ffn, V = c.vocab, nq = c.num_query_tokens;
+    TRY(reg_stem(m, kBlipVision));
+    TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
+
+    TRY(reg_qformer(m, false));
     TRY(reg_mat(m, "language_projection.weight", &m->w_lproj, T, Q));
     TRY(reg_f32(m, "language_projection.bias", &m->b_lproj, T));
 
@@ -773,6 +800,121 @@ int run_qformer(Captioner* m, int B, hipStream_t s) {
         TRY(gemm(m, s, "qf_gemm_f1", m->qx_t, Q, L.w_f1, Q, m->qh, F, L.b_f1, nullptr, R, F, Q, 1, 0));
         TRY(gemm(m, s, "qf_gemm_f2", m->qh, F, L.w_f2, F, m->qy, Q, L.b_f2, m->qx, R, Q, F, 0, 1));
         TRY(launch_layernorm(m->gdt, m->qy, Q, L.f_g, L.f_b, c.q_eps, m->qx_t, m->qx, R, Q, s));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- BLIP-2 image-text scorer
+// HF `Blip2ForImageTextRetrieval` state-dict names (transformers 5.x; `image_token_index` None: the ITM checkpoints): the ViT-g
+// tower, the Q-Former with both FFN sets, the text embeddings and the three heads (fp32 for the head kernels).
+int build_blip2_itm(Captioner* m) {
+    const CapConfig& c = m->c;
+    const int D = c.v_hidden, Q = c.q_hidden, F = c.q_ffn, P = c.embed_dim, nq = c.num_query_tokens;
+    TRY(reg_stem(m, kBlipVision));
+    TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
+    TRY(reg_qformer(m, true));
+    TRY(reg_f32(m, "embeddings.word_embeddings.weight", &m->i_word, (int64_t)c.vocab * Q));
+    TRY(reg_f32(m, "embeddings.position_embeddings.weight", &m->i_pos, (int64_t)c.max_pos * Q));
+    TRY(reg_ln(m, "qformer.layernorm.", &m->i_ln_g, &m->i_ln_b, Q));
+    TRY(reg_f32(m, "vision_projection.weight", &m->i_vproj, (int64_t)P * Q));
+    TRY(reg_f32(m, "vision_projection.bias", &m->i_vproj_b, P));
+    TRY(reg_f32(m, "text_projection.weight", &m->i_tproj, (int64_t)P * Q));
+    TRY(reg_f32(m, "text_projection.bias", &m->i_tproj_b, P));
+    TRY(reg_f32(m, "itm_head.weight", &m->i_head, (int64_t)2 * Q));
+    TRY(reg_f32(m, "itm_head.bias", &m->i_head_b, 2));
+    // arena: image rows [max_batch * tokens, .], query rows [max_batch * nq, .], text rows [max_batch * max_len, .]
+    const size_t Bm = c.max_batch, M = Bm * m->NT, Rq = Bm * nq, Rt = Bm * c.max_len, e = m->esz;
+    int ncross = 0;
+    for (const QLayer& L : m->ql) ncross += L.cross;
+    TRY(alloc_image_tower(m));
+    TRY(dev_alloc(m, (void**)&m->emb_f, M * D * 4));
+    TRY(dev_alloc(m, &m->emb_t, M * D * e));
+    TRY(dev_alloc(m, &m->itm_ckv, (size_t)ncross * M * 2 * Q * e));
+    TRY(dev_alloc(m, (void**)&m->qx, Rq * Q * 4));
+    TRY(dev_alloc(m, (void**)&m->qy, Rq * Q * 4));
+    TRY(dev_alloc(m, &m->qx_t, Rq * Q * e));
+    TRY(dev_alloc(m, &m->qqkv, Rq * 3 * Q * e));
+    TRY(dev_alloc(m, &m->qctx, Rq * Q * e));
+    TRY(dev_alloc(m, &m->qh, Rq * F * e));
+    TRY(dev_alloc(m, (void**)&m->tx, Rt * Q * 4));
+    TRY(dev_alloc(m, (void**)&m->ty, Rt * Q * 4));
+    TRY(dev_alloc(m, &m->tx_t, Rt * Q * e));
+    TRY(dev_alloc(m, &m->tqkv, Rt * 3 * Q * e));
+    TRY(dev_alloc(m, &m->tctx, Rt * Q * e));
+    return dev_alloc(m, &m->th, Rt * F * e);
+}
+
+// ViT-g over B images -> emb_t [B * NT, D] (post_layernorm on every token), then the cross-attention K/V of every cross layer of
+// the Q-Former (they depend on the image alone) -> itm_ckv: what an ITC and an ITM call on this image batch both read.
+int run_itm_images(Captioner* m, const void* pixels, int fmt, int B, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int D = c.v_hidden, Q = c.q_hidden, NT = m->NT;
+    const int af = m->gdt == CAP_DT_G8 ? 1 : 0;
+    m->itm_B = 0;
+    TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
+    size_t slot = 0;
+    for (const QLayer& L : m->ql) {
+        if (!L.cross) continue;
+        void* kv = (char*)m->itm_ckv + slot++ * (size_t)c.max_batch * NT * 2 * Q * m->esz;
+        TRY(gemm(m, s, "itm_gemm_ckv", m->emb_t, D, L.w_ckv, D, kv, 2 * Q, L.b_ckv, nullptr, B * NT, 2 * Q, D, 0, af));
+    }
+    m->itm_B = B;
+    return 0;
+}
+
+// One post-LN sub-block over R rows: y = A W^T + b + x; x, x_t = LayerNorm(y)
+int itm_out_ln(Captioner* m, hipStream_t s, const char* tag, const void* A, int K, const void* W, const float* b, const float* g,
+               const float* be, float* x, float* y, void* x_t, int R) {
+    const int Q = m->c.q_hidden;
+    TRY(gemm(m, s, tag, A, K, W, K, y, Q, b, x, R, Q, K, 0, 1));
+    return launch_layernorm(m->gdt, y, Q, g, be, m->c.q_eps, x_t, x, R, Q, s);
+}
+
+// The Q-Former over B pairs with nq query rows (0: none - the ITC text pass) and L text rows (0: none - the ITC image pass) each:
+// self-attention over [queries | the pair's text], cross-attention of the query rows to the cached image K/V on the cross layers,
+// the query rows through intermediate_query / output_query and the text rows through intermediate / output.  The two kinds of
+// rows live in their own buffers (qx .. / tx ..), so every GEMM runs over contiguous rows.  Leaves the last hidden states in qx
+// [B * nq, Q] and tx [B * L, Q] (fp32).
+int run_itm_qformer(Captioner* m, int B, int nq, int L, const int* ids, const int* lens, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int Q = c.q_hidden, F = c.q_ffn, H = c.q_heads, NT = m->NT, Rq = B * nq, Rt = B * L, hd = Q / H;
+    const size_t e = m->esz;
+    const int af = m->gdt == CAP_DT_G8 ? 1 : 0;     // split mode: what the attention kernels read (q, k, v) is fp32, only GEMM operands are G8
+    if (nq) TRY(launch_rows_broadcast(m->gdt, m->q_x0, m->qx, m->qx_t, B, nq, Q, s));
+    if (L) {
+        ProfScope ps(m, s, "itm_embed_text", 0, (double)Rt * Q * (8 + 4 + e));
+        TRY(launch_itm_embed_text(m->gdt, ids, L, m->i_word, m->i_pos, m->i_ln_g, m->i_ln_b, c.q_eps, m->tx, m->tx_t, Rt, Q, c.vocab, s));
+    }
+    size_t slot = 0;
+    for (const QLayer& Ly : m->ql) {
+        if (nq) TRY(gemm(m, s, "itm_gemm_qkv_q", m->qx_t, Q, Ly.w_qkv, Q, m->qqkv, 3 * Q, Ly.b_qkv, nullptr, Rq, 3 * Q, Q, 0, af));
+        if (L) TRY(gemm(m, s, "itm_gemm_qkv_t", m->tx_t, Q, Ly.w_qkv, Q, m->tqkv, 3 * Q, Ly.b_qkv, nullptr, Rt, 3 * Q, Q, 0, af));
+        {
+            ProfScope ps(m, s, "itm_self_attn", 4.0 * B * H * (double)(nq + L) * (nq + L) * hd, (double)(Rq + Rt) * 4 * Q * e);
+            TRY(launch_itm_self_attention(m->dt, m->qqkv, m->tqkv, lens, m->qctx, m->tctx, B, nq, L, H, hd, s, m->gdt));
+        }
+        if (nq) TRY(itm_out_ln(m, s, "itm_gemm_so_q", m->qctx, Q, Ly.w_so, Ly.b_so, Ly.so_g, Ly.so_b, m->qx, m->qy, m->qx_t, Rq));
+        if (L) TRY(itm_out_ln(m, s, "itm_gemm_so_t", m->tctx, Q, Ly.w_so, Ly.b_so, Ly.so_g, Ly.so_b, m->tx, m->ty, m->tx_t, Rt));
+        if (Ly.cross) {
+            const char* kv = (const char*)m->itm_ckv + slot++ * (size_t)c.max_batch * NT * 2 * Q * e;
+            if (nq) {
+                TRY(gemm(m, s, "itm_gemm_cq", m->qx_t, Q, Ly.w_cq, Q, m->qqkv, Q, Ly.b_cq, nullptr, Rq, Q, Q, 0, af));
+                {
+                    ProfScope ps(m, s, "itm_cross_attn", 4.0 * B * H * (double)nq * NT * hd, (double)B * NT * 2 * Q * e);
+                    TRY(launch_generic_attention(m->dt, m->qqkv, Q, (long)nq * Q, kv, 2 * Q, (long)NT * 2 * Q, kv + Q * e, 2 * Q, (long)NT * 2 * Q,
+                                                 m->qctx, Q, (long)nq * Q, B, nq, NT, H, hd, -1, s, m->gdt));
+                }
+                TRY(itm_out_ln(m, s, "itm_gemm_co", m->qctx, Q, Ly.w_co, Ly.b_co, Ly.co_g, Ly.co_b, m->qx, m->qy, m->qx_t, Rq));
+            }
+        }
+        if (nq) {
+            TRY(gemm(m, s, "itm_gemm_f1_q", m->qx_t, Q, Ly.w_f1, Q, m->qh, F, Ly.b_f1, nullptr, Rq, F, Q, 1, 0));
+            TRY(itm_out_ln(m, s, "itm_gemm_f2_q", m->qh, F, Ly.w_f2, Ly.b_f2, Ly.f_g, Ly.f_b, m->qx, m->qy, m->qx_t, Rq));
+        }
+        if (L) {
+            TRY(gemm(m, s, "itm_gemm_f1_t", m->tx_t, Q, Ly.w_t1, Q, m->th, F, Ly.b_t1, nullptr, Rt, F, Q, 1, 0));
+            TRY(itm_out_ln(m, s, "itm_gemm_f2_t", m->th, F, Ly.w_t2, Ly.b_t2, Ly.t_g, Ly.t_b, m->tx, m->ty, m->tx_t, Rt));
+        }
     }
     return 0;
 }
@@ -1777,7 +1919,7 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
         return -1;
     }
     if (cfg->arch != CAP_ARCH_BLIP && cfg->arch != CAP_ARCH_COCA && cfg->arch != CAP_ARCH_MINILM && cfg->arch != CAP_ARCH_BLIP2 &&
-        cfg->arch != CAP_ARCH_CLIP) {
+        cfg->arch != CAP_ARCH_CLIP && cfg->arch != CAP_ARCH_BLIP2_ITM) {
         cap_set_error("cap_create: unknown arch %d", cfg->arch);
         return -1;
     }
@@ -1813,6 +1955,20 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
             cap_set_error("cap_create: CLIP hidden_act %d is neither CAP_ACT_QUICK_GELU (0) nor CAP_ACT_GELU (1)", cfg->hidden_act);
             return -1;
         }
+    } else if (cfg->arch == CAP_ARCH_BLIP2_ITM) {
+        const int vhd = cfg->v_heads > 0 ? cfg->v_hidden / cfg->v_heads : 0;
+        if (vhd < 8 || vhd > 128 || vhd % 8 || vhd * cfg->v_heads != cfg->v_hidden || cfg->v_hidden % 64 || cfg->v_mlp % 64 || cfg->v_mlp < 64 ||
+            cfg->v_layers < 1 || cfg->patch_size < 1 || cfg->image_size % cfg->patch_size || cfg->q_heads < 1 ||
+            cfg->q_hidden != cfg->q_heads * 64 || cfg->q_hidden > 1024 || cfg->q_ffn % 64 || cfg->q_ffn < 64 || cfg->q_layers < 1 ||
+            cfg->q_cross_freq < 1 || cfg->num_query_tokens < 1 || cfg->num_query_tokens > 32 || cfg->embed_dim < 1 ||
+            cfg->embed_dim > 1024 || cfg->vocab < 1 || cfg->max_batch < 1 || cfg->max_len < 1 || cfg->max_len > 32 ||
+            cfg->max_len > cfg->max_pos) {
+            cap_set_error("cap_create: the BLIP-2 image-text scorer needs a ViT head dim that is a multiple of 8 (<= 128), Q-Former heads of "
+                          "64 (width <= 1024), widths multiple of 64, 1..32 query tokens, 1 <= embed_dim <= 1024 and "
+                          "1 <= max_len <= min(max_pos, 32)");
+            return -1;
+        }
+        if (cfg->weight_int8) { cap_set_error("cap_create: the BLIP-2 image-text scorer has no int8 weights (CAP_F32, CAP_F32_SPLIT or CAP_BF16)"); return -1; }
     } else if (cfg->arch == CAP_ARCH_BLIP2) {
         auto hd_ok = [](int w, int h) { return h > 0 && w % h == 0 && (w / h) % 8 == 0 && w / h >= 8 && w / h <= 128; };
         if (!hd_ok(cfg->v_hidden, cfg->v_heads) || !hd_ok(cfg->q_hidden, cfg->q_heads) || !hd_ok(cfg->t_hidden, cfg->t_heads) ||
@@ -1888,6 +2044,7 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
     const int built = text_only ? (build_minilm(m) != 0)
                       : cfg->arch == CAP_ARCH_BLIP2 ? (build_blip2(m) != 0)
                       : cfg->arch == CAP_ARCH_CLIP ? (build_clip(m) != 0)
+                      : cfg->arch == CAP_ARCH_BLIP2_ITM ? (build_blip2_itm(m) != 0)
                       : cfg->arch == CAP_ARCH_COCA ? (build_coca(m) != 0 || build_arena_coca(m) != 0)
                                                    : (build_blip(m) != 0 || build_arena(m) != 0);
     if (built) {
@@ -2034,6 +2191,7 @@ static int check_call(Captioner* m, int B, int K, int Lm, int fmt) {
     if (fmt != CAP_PIX_F32_NCHW && fmt != CAP_PIX_U8_NHWC) { cap_set_error("unknown pixel format %d", fmt); return -1; }
     if (m->c.arch == CAP_ARCH_MINILM) { cap_set_error("this handle is a sentence encoder: use cap_embed_text"); return -1; }
     if (m->c.arch == CAP_ARCH_CLIP) { cap_set_error("this handle is a CLIP scorer: use cap_clip_embed_images / cap_clip_embed_text"); return -1; }
+    if (m->c.arch == CAP_ARCH_BLIP2_ITM) { cap_set_error("this handle is a BLIP-2 image-text scorer: use cap_blip2_itm_encode_images / cap_blip2_itc_* / cap_blip2_itm_logits"); return -1; }
     return 0;
 }
 
@@ -2075,6 +2233,78 @@ int cap_clip_logit_scale(CapHandle h, float* out) {
     TRY(check_clip(m, "cap_clip_logit_scale"));
     CAP_HIP_CHECK(hipMemcpy(out, m->c_logit, sizeof(float), hipMemcpyDeviceToHost));
     return 0;
+}
+
+static int check_itm(Captioner* m, const char* fn) {
+    if (!m) { cap_set_error("%s: null handle", fn); return -1; }
+    if (m->c.arch != CAP_ARCH_BLIP2_ITM) { cap_set_error("%s: the handle is not a BLIP-2 image-text scorer (CAP_ARCH_BLIP2_ITM)", fn); return -1; }
+    return cap_finalize_weights((CapHandle)m) != 0 ? -1 : 0;
+}
+// the pairs of a call are the images of the last cap_blip2_itm_encode_images, in order
+static int check_itm_resident(Captioner* m, const char* fn, int B) {
+    if (m->itm_B < 1) { cap_set_error("%s: no image batch is resident (call cap_blip2_itm_encode_images first)", fn); return -1; }
+    if (B != m->itm_B) { cap_set_error("%s: B=%d, but the resident image batch has %d images", fn, B, m->itm_B); return -1; }
+    return 0;
+}
+static int check_itm_text(Captioner* m, const char* fn, const void* ids, const void* lens, int B, int L) {
+    if (!ids || !lens) { cap_set_error("%s: null buffer", fn); return -1; }
+    if (L > m->c.max_len) { cap_set_error("%s: text of %d tokens is longer than the handle's max_len (%d): truncate on the host", fn, L, m->c.max_len); return -1; }
+    if (B > m->c.max_batch) { cap_set_error("%s: B=%d exceeds the handle's capacity (max_batch %d)", fn, B, m->c.max_batch); return -1; }
+    if (B < 1 || L < 1) { cap_set_error("%s: bad shape B=%d L=%d", fn, B, L); return -1; }
+    return 0;
+}
+
+int cap_blip2_itm_encode_images(CapHandle h, const void* pixels, int pixel_fmt, int B, void* stream) {
+    Captioner* m = (Captioner*)h;
+    TRY(check_itm(m, "cap_blip2_itm_encode_images"));
+    if (!pixels) { cap_set_error("cap_blip2_itm_encode_images: null buffer"); return -1; }
+    if (B < 1 || B > m->c.max_batch) { cap_set_error("cap_blip2_itm_encode_images: B=%d exceeds the handle's capacity (max_batch %d)", B, m->c.max_batch); return -1; }
+    if (pixel_fmt != CAP_PIX_F32_NCHW && pixel_fmt != CAP_PIX_U8_NHWC) { cap_set_error("unknown pixel format %d", pixel_fmt); return -1; }
+    return run_itm_images(m, pixels, pixel_fmt, B, (hipStream_t)stream);
+}
+
+int cap_blip2_itc_image_features(CapHandle h, int B, float* out, void* stream) {
+    Captioner* m = (Captioner*)h;
+    TRY(check_itm(m, "cap_blip2_itc_image_features"));
+    if (!out) { cap_set_error("cap_blip2_itc_image_features: null buffer"); return -1; }
+    TRY(check_itm_resident(m, "cap_blip2_itc_image_features", B));
+    const CapConfig& c = m->c;
+    hipStream_t s = (hipStream_t)stream;
+    TRY(run_itm_qformer(m, B, c.num_query_tokens, 0, nullptr, nullptr, s));
+    ProfScope ps(m, s, "itc_image_head", 2.0 * B * c.num_query_tokens * c.q_hidden * c.embed_dim, (double)B * c.num_query_tokens * (c.q_hidden + c.embed_dim) * 4);
+    return launch_itc_head(m->qx, 1, m->i_vproj, m->i_vproj_b, out, B * c.num_query_tokens, c.q_hidden, c.embed_dim, s);
+}
+
+int cap_blip2_itc_text_features(CapHandle h, const int32_t* ids, const int32_t* lens, int B, int L, float* out, void* stream) {
+    Captioner* m = (Captioner*)h;
+    TRY(check_itm(m, "cap_blip2_itc_text_features"));
+    TRY(check_itm_text(m, "cap_blip2_itc_text_features", ids, lens, B, L));
+    if (!out) { cap_set_error("cap_blip2_itc_text_features: null buffer"); return -1; }
+    const CapConfig& c = m->c;
+    hipStream_t s = (hipStream_t)stream;
+    TRY(run_itm_qformer(m, B, 0, L, ids, lens, s));
+    ProfScope ps(m, s, "itc_text_head", 2.0 * B * c.q_hidden * c.embed_dim, (double)B * (c.q_hidden + c.embed_dim) * 4);
+    return launch_itc_head(m->tx, L, m->i_tproj, m->i_tproj_b, out, B, c.q_hidden, c.embed_dim, s);
+}
+
+int cap_blip2_itc_scores(const float* img, const float* txt, int Ni, int Nt, int paired, float* out, int num_queries, int embed_dim,
+                         void* stream) {
+    if (!img || !txt || !out) { cap_set_error("cap_blip2_itc_scores: null buffer"); return -1; }
+    return launch_itc_scores(img, txt, Ni, Nt, num_queries, embed_dim, paired, out, (hipStream_t)stream);
+}
+
+int cap_blip2_itm_logits(CapHandle h, const int32_t* ids, const int32_t* lens, int B, int L, float* out_logits, float* out_prob,
+                         void* stream) {
+    Captioner* m = (Captioner*)h;
+    TRY(check_itm(m, "cap_blip2_itm_logits"));
+    TRY(check_itm_text(m, "cap_blip2_itm_logits", ids, lens, B, L));
+    if (!out_logits) { cap_set_error("cap_blip2_itm_logits: null buffer"); return -1; }
+    TRY(check_itm_resident(m, "cap_blip2_itm_logits", B));
+    const CapConfig& c = m->c;
+    hipStream_t s = (hipStream_t)stream;
+    TRY(run_itm_qformer(m, B, c.num_query_tokens, L, ids, lens, s));
+    ProfScope ps(m, s, "itm_head", 4.0 * B * c.num_query_tokens * c.q_hidden, (double)B * c.num_query_tokens * c.q_hidden * 4);
+    return launch_itm_head(m->qx, m->i_head, m->i_head_b, out_logits, out_prob, B, c.num_query_tokens, c.q_hidden, s);
 }
 
 int cap_embed_text(CapHandle h, const int32_t* ids, const int32_t* lens, int B, int L, float* out, void* stream) {
@@ -2144,7 +2374,8 @@ long long cap_g8_saturations(int reset) {
     if (hipDeviceSynchronize() != hipSuccess) { cap_set_error("cap_g8_saturations: device synchronisation failed"); return -1; }
     unsigned long long total = 0;
     if (cap_g8_clamped_gemm(&total, reset) != 0 || cap_g8_clamped_gemm_pp(&total, reset) != 0 || cap_g8_clamped_elementwise(&total, reset) != 0 ||
-        cap_g8_clamped_attention(&total, reset) != 0 || cap_g8_clamped_decode_small(&total, reset) != 0)
+        cap_g8_clamped_attention(&total, reset) != 0 || cap_g8_clamped_decode_small(&total, reset) != 0 ||
+        cap_g8_clamped_blip2_itm(&total, reset) != 0)
         return -1;
     return (long long)total;
 }
@@ -2223,6 +2454,18 @@ int cap_op_vit_attention_hd(int dtype, const void* qkv, void* ctx, int B, int N,
     // impl bit 8: causal mask (decoder prefill)
     return launch_vit_attention(in_dt_of(dtype), qkv, ctx, B, N, H, impl & 7, (hipStream_t)stream, head_dim, (impl >> 3) & 1,
                                 dt_of(dtype));
+}
+int cap_op_generic_attention(int dtype, const void* qkv, void* ctx, int B, int N, int H, int head_dim, void* stream) {
+    const long D = (long)H * head_dim;
+    const int dt = in_dt_of(dtype);
+    const char* base = (const char*)qkv;
+    const size_t e = dt == CAP_DT_BF16 ? 2 : 4;
+    return launch_generic_attention(dt, base, 3 * D, (long)N * 3 * D, base + D * e, 3 * D, (long)N * 3 * D, base + 2 * D * e, 3 * D,
+                                    (long)N * 3 * D, ctx, D, (long)N * D, B, N, N, H, head_dim, -1, (hipStream_t)stream, dt_of(dtype));
+}
+int cap_op_itm_self_attention(int dtype, const void* qkv_q, const void* qkv_t, const int32_t* lens, void* ctx_q, void* ctx_t, int B,
+                              int num_queries, int L, int H, void* stream) {
+    return launch_itm_self_attention(in_dt_of(dtype), qkv_q, qkv_t, lens, ctx_q, ctx_t, B, num_queries, L, H, 64, (hipStream_t)stream, dt_of(dtype));
 }
 int cap_crop_resize_tables(const int32_t* rects, const int32_t* geom, int n, int S, int KH, int KV, int32_t* hb, int32_t* hk,
                            int32_t* vb, int32_t* vk, void* stream) {

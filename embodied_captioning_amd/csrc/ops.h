@@ -153,6 +153,23 @@ int launch_clip_head(const float* x, int rows_per, const int* lens, const float*
 // exp(logit_scale) * img . txt^T: paired -> out [Ni] (row i against row i), else out [Ni, Nt]
 int launch_clip_logits(const float* img, const float* txt, int Ni, int Nt, int P, int paired, float logit_scale, float* out, hipStream_t s);
 
+// ---- blip2_itm.hip -----------------------------------------------------------------------------
+// Q-Former text embeddings: x = qformer.layernorm(word[ids[r]] + pos[r % L]) -> x_f fp32 and x_t (dtype) [M, D] (ids clamped to [0, V))
+int launch_itm_embed_text(int dtype, const int* ids, int L, const float* word, const float* pos, const float* gamma, const float* beta,
+                          float eps, float* x_f, void* x_t, int M, int D, int V, hipStream_t s);
+// Q-Former self-attention over [nq query rows | the first lens[b] of L text rows] per pair b, heads of 64: fused q|k|v rows
+// qkv_q [B * nq, 3 H 64] / qkv_t [B * L, 3 H 64] (dtype) -> ctx_q [B * nq, H 64] / ctx_t [B * L, H 64].  nq = 0: text alone (the ITC
+// text pass); L = 0: queries alone.  Sums ordered by nq and lens[b] only.
+int launch_itm_self_attention(int dtype, const void* qkv_q, const void* qkv_t, const int* lens, void* ctx_q, void* ctx_t, int B, int nq,
+                              int L, int H, int hd, hipStream_t s, int out_dtype = -1);   // out_dtype: see launch_vit_attention
+// ITC head: rows r * rows_per of x fp32 [., D] -> . W^T + bias (fp32 [P, D], [P]) -> L2 normalised out fp32 [n, P]
+int launch_itc_head(const float* x, int rows_per, const float* W, const float* bias, float* out, int n, int D, int P, hipStream_t s);
+// ITC score: max over the nq query rows of img [Ni, nq, P] . txt [Nt, P]: paired -> out [Ni], else out [Ni, Nt]
+int launch_itc_scores(const float* img, const float* txt, int Ni, int Nt, int nq, int P, int paired, float* out, hipStream_t s);
+// ITM head: mean over the nq query rows of x [B * nq, D] . W^T + bias (fp32 [2, D], [2]) -> logits [B, 2], prob [B] = softmax[.., 1] (may be null)
+int launch_itm_head(const float* x, const float* W, const float* bias, float* logits, float* prob, int B, int nq, int D, hipStream_t s);
+int cap_g8_clamped_blip2_itm(unsigned long long* total, int reset);
+
 // ---- beam.hip --------------------------------------------------------------------------------
 size_t beam_state_bytes(int B, int K, int max_len);
 int beam_candidates_only(void* state, const float* logits, int ld, int V, int B, int K, int mode, int eos_mask, float* out_val,

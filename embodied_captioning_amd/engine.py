@@ -13,7 +13,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import _native as N
-from .config import Blip2Arch, BlipArch, ClipArch, CocaArch, MiniLMArch
+from .config import Blip2Arch, Blip2ItmArch, BlipArch, ClipArch, CocaArch, MiniLMArch
 
 logger = logging.getLogger(__name__)
 
@@ -678,3 +678,129 @@ class ClipEngine:
                                              C.c_float(self.logit_scale), C.c_void_p(out.data_ptr()), P,
                                              C.c_void_p(_stream_ptr(self.device))), "cap_clip_logits")
         return out
+
+
+class Blip2ItmEngine:
+    """BLIP-2 image-text scorer replica (CAP_ARCH_BLIP2_ITM handle): HF `Blip2ForImageTextRetrieval`'s two scores for batches of
+    (image, caption) pairs, as the reference's `--method blip2_itm | blip2_itc` computes them one pair per call
+    (experimenting_env/captioner/pseudocaptioner.py:193-308).  `encode_images` leaves an image batch's tokens and cross-attention
+    K/V resident in the handle; `itc_image_features` and `itm` then read them without running the ViT-g again.  Tokenisation stays
+    on the host (captioner/blip2_itm_scorer.py)."""
+
+    _skip_kv16_guard = True      # the Q-Former's cross K/V are kept in the compute type, never as KV16
+
+    def __init__(self, arch: Blip2ItmArch, dtype: str = "f32s", max_batch: int = 256, max_len: Optional[int] = None,
+                 device: str | torch.device = "cuda:0", share_weights_with: "Blip2ItmEngine | None" = None):
+        if not torch.cuda.is_available():
+            raise N.CaptionerHipError("Blip2ItmEngine needs a GPU; there is no CPU fallback in the product path")
+        self.lib = N.load_library()
+        self.arch, self.dtype, self.device = arch, dtype, torch.device(device)
+        self.max_batch, self.max_len = max_batch, max_len or arch.max_text_len
+        cfg = N.CapConfig()
+        cfg.struct_size = C.sizeof(N.CapConfig)
+        cfg.arch = N.CAP_ARCH_BLIP2_ITM
+        cfg.compute_dtype = _DTYPES[dtype]
+        cfg.image_size, cfg.patch_size = arch.image_size, arch.patch_size
+        cfg.v_hidden, cfg.v_layers, cfg.v_heads, cfg.v_mlp, cfg.v_eps = arch.v_hidden, arch.v_layers, arch.v_heads, arch.v_mlp, arch.v_eps
+        cfg.q_hidden, cfg.q_layers, cfg.q_heads, cfg.q_ffn = arch.q_hidden, arch.q_layers, arch.q_heads, arch.q_ffn
+        cfg.q_cross_freq, cfg.num_query_tokens, cfg.q_eps = arch.q_cross_freq, arch.num_query_tokens, arch.q_eps
+        cfg.vocab, cfg.max_pos, cfg.pad = arch.vocab, arch.max_pos, arch.pad
+        cfg.embed_dim = arch.projection_dim
+        cfg.max_batch, cfg.max_beams, cfg.max_len = max_batch, 1, self.max_len
+        for i in range(3):
+            cfg.pix_mean[i] = OPENAI_CLIP_MEAN[i]
+            cfg.pix_std[i] = OPENAI_CLIP_STD[i]
+        self._h = C.c_void_p()
+        self.shares_weights = share_weights_with is not None
+        self.resident = 0            # images of the last encode_images
+        with torch.cuda.device(self.device):
+            if share_weights_with is not None:
+                N.check(self.lib.cap_create_shared(C.byref(cfg), share_weights_with._h, C.byref(self._h)), "cap_create_shared")
+            else:
+                N.check(self.lib.cap_create(C.byref(cfg), C.byref(self._h)), "cap_create")
+
+    close = CaptionerEngine.close
+    __del__ = CaptionerEngine.__del__
+    device_bytes = CaptionerEngine.device_bytes
+    saturations = CaptionerEngine.saturations
+    profile = CaptionerEngine.profile
+    profile_report = CaptionerEngine.profile_report
+    _pixels = CaptionerEngine._pixels
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> Dict[str, object]:
+        """HF `Blip2ForImageTextRetrieval` names (wrapper prefixes dropped, `*.position_ids` buffers ignored);
+        `derived.qformer_x0` = qformer.layernorm(query_tokens) is computed here."""
+        from .weights import strip_wrapper_prefixes
+        sd = {k: v for k, v in strip_wrapper_prefixes(sd).items() if not k.endswith("position_ids")}
+        self.is_coca, self.is_blip2 = False, True
+        return CaptionerEngine.load_state_dict(self, sd, strict)
+
+    def _text(self, ids: torch.Tensor, lens: torch.Tensor):
+        if ids.dim() != 2 or lens.shape != (ids.shape[0],):
+            raise ValueError(f"ids must be [B, L] and lens [B], got {tuple(ids.shape)} / {tuple(lens.shape)}")
+        B, L = ids.shape
+        if not ids.is_cuda and not lens.is_cuda and B and L:      # host tensors: validated here; device tensors are clamped by the kernels
+            if int(lens.max()) > L or int(lens.min()) < 1:
+                raise ValueError("lens must be within 1..L")
+            if int(ids.max()) >= self.arch.vocab or int(ids.min()) < 0:
+                raise ValueError("token id outside the vocabulary")
+        return ids.to(self.device, torch.int32).contiguous(), lens.to(self.device, torch.int32).contiguous(), B, L
+
+    def encode_images(self, pixels: torch.Tensor) -> int:
+        """uint8 [B, S, S, 3] RGB or normalised fp32 [B, 3, S, S]: runs the ViT-g and the cross K/V projections; the batch stays
+        resident for `itc_image_features` / `itm`.  Returns B."""
+        pixels, fmt = self._pixels(pixels)
+        B = pixels.shape[0]
+        self.resident = 0
+        with torch.cuda.device(self.device):
+            N.check(self.lib.cap_blip2_itm_encode_images(self._h, C.c_void_p(pixels.data_ptr()), fmt, B,
+                                                         C.c_void_p(_stream_ptr(self.device))), "cap_blip2_itm_encode_images")
+        self.resident = B
+        return B
+
+    def itc_image_features(self) -> torch.Tensor:
+        """The resident images -> fp32 [B, num_query_tokens, projection_dim] (device), each query row L2-normalised."""
+        B = self.resident
+        out = torch.empty((B, self.arch.num_query_tokens, self.arch.projection_dim), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.cap_blip2_itc_image_features(self._h, B, C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(self.device))),
+                    "cap_blip2_itc_image_features")
+        return out
+
+    def itc_text_features(self, ids: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """ids int [B, L] (right padded; anything after the caption), lens int [B] -> fp32 [B, projection_dim] (device), L2-normalised."""
+        ids, lens, B, L = self._text(ids, lens)
+        out = torch.empty((B, self.arch.projection_dim), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.cap_blip2_itc_text_features(self._h, C.c_void_p(ids.data_ptr()), C.c_void_p(lens.data_ptr()), B, L,
+                                                         C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(self.device))),
+                    "cap_blip2_itc_text_features")
+        return out
+
+    def itc_scores(self, img: torch.Tensor, txt: torch.Tensor, paired: bool = True) -> torch.Tensor:
+        """max over the queries of img [Ni, nq, P] . txt [Nt, P]: paired -> [n] (image i against caption i), else [Ni, Nt]."""
+        nq, P = self.arch.num_query_tokens, self.arch.projection_dim
+        if img.dim() != 3 or txt.dim() != 2 or tuple(img.shape[1:]) != (nq, P) or txt.shape[1] != P:
+            raise ValueError(f"features must be [n, {nq}, {P}] and [n, {P}], got {tuple(img.shape)} / {tuple(txt.shape)}")
+        if paired and img.shape[0] != txt.shape[0]:
+            raise ValueError(f"paired scores need as many images as captions ({img.shape[0]} / {txt.shape[0]})")
+        img = img.to(self.device, torch.float32).contiguous()
+        txt = txt.to(self.device, torch.float32).contiguous()
+        Ni, Nt = img.shape[0], txt.shape[0]
+        out = torch.empty((Ni,) if paired else (Ni, Nt), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.cap_blip2_itc_scores(C.c_void_p(img.data_ptr()), C.c_void_p(txt.data_ptr()), Ni, Nt, int(bool(paired)),
+                                                  C.c_void_p(out.data_ptr()), nq, P, C.c_void_p(_stream_ptr(self.device))),
+                    "cap_blip2_itc_scores")
+        return out
+
+    def itm(self, ids: torch.Tensor, lens: torch.Tensor):
+        """Resident image b against caption b -> (logits fp32 [B, 2], probability of a match fp32 [B]) on the device."""
+        ids, lens, B, L = self._text(ids, lens)
+        logits = torch.empty((B, 2), dtype=torch.float32, device=self.device)
+        prob = torch.empty((B,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            N.check(self.lib.cap_blip2_itm_logits(self._h, C.c_void_p(ids.data_ptr()), C.c_void_p(lens.data_ptr()), B, L,
+                                                  C.c_void_p(logits.data_ptr()), C.c_void_p(prob.data_ptr()),
+                                                  C.c_void_p(_stream_ptr(self.device))), "cap_blip2_itm_logits")
+        return logits, prob

@@ -1,11 +1,12 @@
-"""Pseudo-caption selection by CLIP score - the reference's `PseudoCaptioner` with `--method clip`
-(experimenting_env/captioner/pseudocaptioner.py:125-154 grouping, :345-357 crop + score, :463-489 selection), every pair of every
-group scored in batched device calls (captioner/clip_scorer.py) instead of one HF call per pair.
+"""Pseudo-caption scoring - the reference's `PseudoCaptioner` (experimenting_env/captioner/pseudocaptioner.py:125-154 grouping,
+:345-357 crop + score) with `--method clip` (:463-489 selection by CLIP score) and `--method blip2_itm | blip2_itc` (:193-308, :491-
+`blip2_score`: the BLIP-2 matching probability / contrastive similarity of every caption), every pair of every group scored in
+batched device calls (captioner/clip_scorer.py, captioner/blip2_itm_scorer.py) instead of one model call per pair.
 
     python -m embodied_captioning_amd.pseudocaptioner --file_path DIR --output_csv_path OUT.json --method clip
+    python -m embodied_captioning_amd.pseudocaptioner --file_path DIR --output_csv_path OUT.json --method blip2_itm [--model DIR]
 
-Only `clip` is built: the reference's other methods (`llm`, `blip2_itm` / `blip2_itc` through LAVIS, `mobileclip`, `openclip`
-ViT-bigG-14) are refused by name.
+The reference's other methods (`llm`, `mobileclip`, `openclip` ViT-bigG-14) are refused by name.
 """
 from __future__ import annotations
 
@@ -20,7 +21,10 @@ import numpy as np
 from .distributed import filter_caption
 from .pseudolabeler import expand_box
 
-REFUSED_METHODS = ("llm", "blip2_itm", "blip2_itc", "mobileclip", "openclip")
+REFUSED_METHODS = ("llm", "mobileclip", "openclip")
+BLIP2_METHODS = {"blip2_itm": "itm", "blip2_itc": "itc"}          # --method -> the scorer's head
+DEFAULT_MODELS = {"clip": "openai/clip-vit-base-patch32", "blip2_itm": "Salesforce/blip2-itm-vit-g-coco",
+                  "blip2_itc": "Salesforce/blip2-itm-vit-g-coco"}
 REFERENCE_FRAME = (1280, 1280)       # the reference's hard-coded image size for expand_box (:346)
 
 
@@ -41,22 +45,21 @@ def host_crops(frames: Sequence[np.ndarray], rects: Sequence[Sequence[Tuple[int,
     return [np.ascontiguousarray(f[y1:y2, x1:x2, ::-1]) for f, rs in zip(frames, rects) for x1, y1, x2, y2 in rs]
 
 
-def device_crops(scorer):
+def device_crops(scorer, center_crop: bool = True):
     """The default crop step: every box of every frame cut, swapped to RGB and resized to the scorer's image size on the device in
-    one go, with HF CLIPImageProcessorPil's geometry (bit-exact with Pillow) -> uint8 [n, S, S, 3], frame-major."""
+    one go (bit-exact with Pillow) -> uint8 [n, S, S, 3], frame-major.  center_crop: HF CLIPImageProcessorPil's geometry (the CLIP
+    scorer); False: the straight resize to S x S of LAVIS `blip_image_eval` (the BLIP-2 scorer)."""
     from .preprocess import crop_resize_u8_frames
 
     def crop(frames, rects):
-        return crop_resize_u8_frames(frames, rects, scorer.arch.image_size, bgr=True, device=scorer.device, center_crop=True,
+        return crop_resize_u8_frames(frames, rects, scorer.arch.image_size, bgr=True, device=scorer.device, center_crop=center_crop,
                                      geometry="hf")
     return crop
 
 
-def clip_pseudo_captions(grouped: Dict, scorer, expand_factor: float = 0.1, image_size=REFERENCE_FRAME, crop=None) -> Dict[str, dict]:
-    """grouped: (episode, object) -> [{'image': BGR uint8 frame, 'pred_box': (x1, y1, x2, y2), 'caption': str}, ...].
-    -> {str(key): {'captions_list': [[score, caption], ...] (by score, descending, stable), 'pseudocaption': [score, caption]}}
-    as :463-483 builds it.  crop(frames, rects) -> the images of all boxes, frame-major (default `device_crops(scorer)`: one
-    batched device crop + resize); then one `scorer.score_pairs(images, captions)` call for every pair of every group."""
+def _score_all_pairs(grouped: Dict, scorer, expand_factor, image_size, crop, **score_kw):
+    """Every pair of every group in ONE `scorer.score_pairs(images, captions, **score_kw)` call -> (keys, float64 scores in group /
+    input order), or (keys, None) when there is no pair."""
     keys = list(grouped)
     frames, rects, caps, owner = [], [], [], []
     frame_idx = {}
@@ -71,8 +74,8 @@ def clip_pseudo_captions(grouped: Dict, scorer, expand_factor: float = 0.1, imag
             caps.append(inst["caption"])
             owner.append((fi, len(rects[fi]) - 1))
     if not caps:
-        return {}
-    images = (crop or device_crops(scorer))(frames, rects)
+        return keys, None
+    images = crop(frames, rects)
     first = np.cumsum([0] + [len(r) for r in rects])
     order = [int(first[fi]) + j for fi, j in owner]               # pair i's image in the frame-major crops
     if hasattr(images, "index_select"):
@@ -80,8 +83,18 @@ def clip_pseudo_captions(grouped: Dict, scorer, expand_factor: float = 0.1, imag
         images = images.index_select(0, torch.tensor(order, device=images.device))
     else:
         images = [images[i] for i in order]
-    sc = scorer.score_pairs(images, caps)
-    scores = np.asarray(sc.double().cpu() if hasattr(sc, "cpu") else sc, dtype=np.float64)
+    sc = scorer.score_pairs(images, caps, **score_kw)
+    return keys, np.asarray(sc.double().cpu() if hasattr(sc, "cpu") else sc, dtype=np.float64)
+
+
+def clip_pseudo_captions(grouped: Dict, scorer, expand_factor: float = 0.1, image_size=REFERENCE_FRAME, crop=None) -> Dict[str, dict]:
+    """grouped: (episode, object) -> [{'image': BGR uint8 frame, 'pred_box': (x1, y1, x2, y2), 'caption': str}, ...].
+    -> {str(key): {'captions_list': [[score, caption], ...] (by score, descending, stable), 'pseudocaption': [score, caption]}}
+    as :463-483 builds it.  crop(frames, rects) -> the images of all boxes, frame-major (default `device_crops(scorer)`: one
+    batched device crop + resize); then one `scorer.score_pairs(images, captions)` call for every pair of every group."""
+    keys, scores = _score_all_pairs(grouped, scorer, expand_factor, image_size, crop or device_crops(scorer))
+    if scores is None:
+        return {}
     out: Dict[str, dict] = {}
     i = 0
     for k in keys:
@@ -93,6 +106,24 @@ def clip_pseudo_captions(grouped: Dict, scorer, expand_factor: float = 0.1, imag
             continue
         lst.sort(key=lambda x: x[0], reverse=True)       # list.sort is stable: equal scores keep input order
         out[str(k)] = {"captions_list": lst, "pseudocaption": list(lst[0])}
+    return out
+
+
+def blip2_pseudo_scores(grouped: Dict, scorer, head: str = "itm", expand_factor: float = 0.1, image_size=REFERENCE_FRAME, crop=None) -> Dict[str, dict]:
+    """grouped as for `clip_pseudo_captions` -> {str(key): {'captions': [...], 'scores': [...]}} in INPUT order (no sorting, no
+    'pseudocaption' key): what the reference's `blip2_score` writes for `--method blip2_itm` (head "itm": the matching
+    probability) and `blip2_itc` (head "itc": the contrastive similarity).  crop(frames, rects) defaults to the straight device
+    resize of `blip_image_eval`; then one `scorer.score_pairs(images, captions, head=head)` call for every pair of every group."""
+    keys, scores = _score_all_pairs(grouped, scorer, expand_factor, image_size, crop or device_crops(scorer, center_crop=False), head=head)
+    if scores is None:
+        return {}
+    out: Dict[str, dict] = {}
+    i = 0
+    for k in keys:
+        n = len(grouped[k])
+        if n:
+            out[str(k)] = {"captions": [inst["caption"] for inst in grouped[k]], "scores": [float(v) for v in scores[i:i + n]]}
+        i += n
     return out
 
 
@@ -130,20 +161,26 @@ def main(argv=None) -> int:
     ap.add_argument("--file_path", required=True, help="directory of pseudo-label records (*.npz)")
     ap.add_argument("--output_csv_path", required=True, help="JSON output (the reference's name for it)")
     ap.add_argument("--method", default="clip")
-    ap.add_argument("--model", default="openai/clip-vit-base-patch32")
+    ap.add_argument("--model", default=None, help="checkpoint directory / cached hub id (default: the method's own; BLIP-2: HF format only)")
     ap.add_argument("--dtype", default="f32s")
     ap.add_argument("--batch_size", type=int, default=256)
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     if args.method in REFUSED_METHODS:
-        raise SystemExit(f"--method {args.method} is not supported here (it needs models this project does not run); use --method clip")
-    if args.method != "clip":
-        raise SystemExit(f"unknown --method {args.method!r}; supported: clip")
-    from .captioner.clip_scorer import ClipScorer
+        raise SystemExit(f"--method {args.method} is not supported here (it needs models this project does not run); "
+                         f"use --method clip, blip2_itm or blip2_itc")
+    if args.method != "clip" and args.method not in BLIP2_METHODS:
+        raise SystemExit(f"unknown --method {args.method!r}; supported: clip, blip2_itm, blip2_itc")
+    model = args.model or DEFAULT_MODELS[args.method]
     grouped = group_records(sorted(glob.glob(os.path.join(args.file_path, "*.npz"))))
-    scorer = ClipScorer(args.model, device=args.device, dtype=args.dtype, batch_size=args.batch_size)
+    if args.method == "clip":
+        from .captioner.clip_scorer import ClipScorer
+        scorer = ClipScorer(model, device=args.device, dtype=args.dtype, batch_size=args.batch_size)
+    else:
+        from .captioner.blip2_itm_scorer import Blip2ItmScorer
+        scorer = Blip2ItmScorer(model, device=args.device, dtype=args.dtype, batch_size=args.batch_size)
     try:
-        result = clip_pseudo_captions(grouped, scorer)
+        result = clip_pseudo_captions(grouped, scorer) if args.method == "clip" else blip2_pseudo_scores(grouped, scorer, BLIP2_METHODS[args.method])
     finally:
         scorer.close()
     print("Scoring completed. Saving scores to", args.output_csv_path)

@@ -307,6 +307,33 @@ def blip2_param_specs(a: Blip2Arch) -> List[Tuple[str, Tuple[int, ...], str, flo
     return s
 
 
+def blip2_itm_param_specs(a) -> List[Tuple[str, Tuple[int, ...], str, float]]:
+    """`Blip2ForImageTextRetrieval.state_dict()` names (transformers 5.x): the BLIP-2 vision tower and Q-Former as in
+    `blip2_param_specs`, plus the Q-Former's text side (word / position embeddings, `intermediate` / `output` per layer) and the
+    three heads; no language model."""
+    lm = ("language_projection.", "language_model.")
+    as_blip2 = Blip2Arch(image_size=a.image_size, patch_size=a.patch_size, v_hidden=a.v_hidden, v_layers=a.v_layers, v_heads=a.v_heads,
+                         v_mlp=a.v_mlp, v_eps=a.v_eps, q_hidden=a.q_hidden, q_layers=a.q_layers, q_heads=a.q_heads, q_ffn=a.q_ffn,
+                         q_cross_freq=a.q_cross_freq, q_eps=a.q_eps, num_query_tokens=a.num_query_tokens, t_layers=0)
+    s = [t for t in blip2_param_specs(as_blip2) if not t[0].startswith(lm)]
+    Q, F, Pd = a.q_hidden, a.q_ffn, a.projection_dim
+    s += [("embeddings.word_embeddings.weight", (a.vocab, Q), "normal", 0.5), ("embeddings.position_embeddings.weight", (a.max_pos, Q), "normal", 0.2)]
+    for i in range(a.q_layers):
+        p = f"qformer.encoder.layer.{i}."
+        s += [(p + "intermediate.dense.weight", (F, Q), "normal", 1.0 / np.sqrt(Q)), (p + "intermediate.dense.bias", (F,), "normal", 0.02),
+              (p + "output.dense.weight", (Q, F), "normal", 1.0 / np.sqrt(F)), (p + "output.dense.bias", (Q,), "normal", 0.02),
+              (p + "output.LayerNorm.weight", (Q,), "gamma", 0.1), (p + "output.LayerNorm.bias", (Q,), "normal", 0.05)]
+    s += [("vision_projection.weight", (Pd, Q), "normal", 1.0 / np.sqrt(Q)), ("vision_projection.bias", (Pd,), "normal", 0.02),
+          ("text_projection.weight", (Pd, Q), "normal", 1.0 / np.sqrt(Q)), ("text_projection.bias", (Pd,), "normal", 0.02),
+          ("itm_head.weight", (2, Q), "normal", 1.0 / np.sqrt(Q)), ("itm_head.bias", (2,), "normal", 0.02)]
+    return s
+
+
+def procedural_blip2_itm_state_dict(arch, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded fp32 state dict with HF `Blip2ForImageTextRetrieval` key names."""
+    return {name: torch.from_numpy(_draw(seed, name, shape, kind, scale)) for name, shape, kind, scale in blip2_itm_param_specs(arch)}
+
+
 def quantize_int8_rowwise(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """bitsandbytes' vector-wise int8 quantisation of a Linear weight [out, in] (what `load_in_8bit=True` stores in a
     `Linear8bitLt`: `CB` int8 and the rows' absmax `SCB`): q = rint(w * (127 / absmax(row))) in fp32 (round-half-even), scale =
@@ -607,6 +634,37 @@ def load_hf_clip_checkpoint(model_dir: str) -> Tuple[ClipArch, Dict[str, torch.T
     w = sd.get("vision_model.embeddings.patch_embedding.weight")
     if w is not None and "vision_model.embeddings.patch_embedding.bias" not in sd:
         sd["vision_model.embeddings.patch_embedding.bias"] = torch.zeros(w.shape[0], dtype=torch.float32)
+    return arch, sd
+
+
+def load_hf_blip2_itm_checkpoint(model_dir: str):
+    """HF `Blip2ForImageTextRetrieval.save_pretrained` directory (config.json + ONE model.safetensors | pytorch_model.bin; a sharded
+    checkpoint is refused as such) -> (Blip2ItmArch, state dict).  LAVIS `.pth` checkpoints carry other key names and are refused."""
+    from .config import Blip2ItmArch
+    if os.path.isfile(model_dir) and model_dir.endswith((".pth", ".pt")):
+        raise RuntimeError(f"{model_dir} looks like a LAVIS checkpoint file: only HF-format directories (Blip2ForImageTextRetrieval) are read")
+    arch = Blip2ItmArch.from_hf_config(model_dir)
+    for fn in ("model.safetensors", "pytorch_model.bin"):
+        p = os.path.join(model_dir, fn)
+        if os.path.exists(p):
+            sd = strip_wrapper_prefixes(load_state_dict_file(p))
+            break
+    else:
+        if any(os.path.exists(os.path.join(model_dir, fn + ".index.json")) for fn in ("model.safetensors", "pytorch_model.bin")):
+            raise RuntimeError(f"{model_dir} holds a SHARDED checkpoint (*.index.json): sharded checkpoints are not read - save it "
+                               f"as one file (save_pretrained(..., max_shard_size='20GB'))")
+        raise RuntimeError(f"no model.safetensors / pytorch_model.bin under {model_dir} (LAVIS .pth key names are not read: "
+                           f"HF-format directories only)")
+    sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
+    if "itm_head.weight" not in sd or "embeddings.word_embeddings.weight" not in sd:
+        raise RuntimeError(f"{model_dir} holds no Blip2ForImageTextRetrieval weights (itm_head / embeddings missing; LAVIS key "
+                           f"names are not read: HF-format directories only)")
+    # the position table tells the image size the checkpoint runs at (no interpolation: the checkpoint's size is the size)
+    pe = sd["vision_model.embeddings.position_embedding"]
+    g = int(round((pe.shape[1] - 1) ** 0.5))
+    if g * g + 1 != pe.shape[1]:
+        raise RuntimeError(f"vision position table of {pe.shape[1]} rows is not a square grid plus the class token")
+    arch.image_size = g * arch.patch_size
     return arch, sd
 
 

@@ -32,6 +32,10 @@
  *   CLIP pseudo-caption experimenting_env/captioner/pseudocaptioner.py:39-46 (CLIPModel.from_pretrained),   cap_clip_embed_images,
  *   scores              :352-357 `model(**processor(text=[caption], images=crop)).logits_per_image`  cap_clip_embed_text,
  *                       (one HF call per (crop, caption) pair; here: batches of pairs, CAP_ARCH_CLIP)    cap_clip_logits
+ *   BLIP-2 ITM / ITC    experimenting_env/captioner/pseudocaptioner.py:34-37 (LAVIS blip2_image_text_matching),  cap_blip2_itm_encode_images,
+ *   pseudo-caption      :193-308 `model({"image", "text_input"}, match_head="itm" | "itc")` (one call and one    cap_blip2_itc_image_features,
+ *   scores              ViT-g pass per (crop, caption) pair; here: batches of pairs, CAP_ARCH_BLIP2_ITM,        cap_blip2_itc_text_features,
+ *                       arithmetic of HF `Blip2ForImageTextRetrieval.forward`)                                 cap_blip2_itc_scores, cap_blip2_itm_logits
  *   device move/free    predictor_utils.py:187 `.to(...)`; object lifetime            cap_destroy
  *   errors              Python exceptions (utils_captioner.py:6, factory.py:231,309)  int return codes + cap_last_error
  *
@@ -52,7 +56,7 @@ extern "C" {
 
 typedef struct CapHandle_s* CapHandle;
 
-enum { CAP_ARCH_BLIP = 0, CAP_ARCH_COCA = 1, CAP_ARCH_MINILM = 2, CAP_ARCH_BLIP2 = 3, CAP_ARCH_CLIP = 4 };
+enum { CAP_ARCH_BLIP = 0, CAP_ARCH_COCA = 1, CAP_ARCH_MINILM = 2, CAP_ARCH_BLIP2 = 3, CAP_ARCH_CLIP = 4, CAP_ARCH_BLIP2_ITM = 5 };
 /* activation of the MLPs (CapConfig.hidden_act, CAP_ARCH_CLIP): HF ACT2FN["quick_gelu"] x * sigmoid(1.702 x) (OpenAI CLIP) or exact GELU */
 enum { CAP_ACT_QUICK_GELU = 0, CAP_ACT_GELU = 1 };
 /* Arithmetic of the GEMM / attention operands (accumulation is fp32 in every mode):
@@ -247,6 +251,37 @@ int cap_clip_logits(const float* img, const float* txt, int Ni, int Nt, int pair
                     void* stream);
 int cap_clip_logit_scale(CapHandle h, float* out);
 
+/* BLIP-2 image-text scorer (CAP_ARCH_BLIP2_ITM handle; weights by HF `Blip2ForImageTextRetrieval` names: vision_model.*,
+ * derived.qformer_x0 [= qformer.layernorm(query_tokens), host-derived], embeddings.word_embeddings.weight,
+ * embeddings.position_embeddings.weight, qformer.layernorm.*, qformer.encoder.layer.N.{attention, crossattention, intermediate,
+ * output, intermediate_query, output_query}.*, vision_projection.*, text_projection.*, itm_head.*).  The handle reads v_* (ViT-g,
+ * head_dim any multiple of 8 up to 128), q_* (Q-Former, heads of 64), num_query_tokens (<= 32), vocab, max_pos (text positions),
+ * embed_dim (projection width), max_batch and max_len (tokens per caption, <= 32).  CAP_F32, CAP_F32_SPLIT or CAP_BF16; no int8.
+ * All pointers are device pointers.  Text: ids int32 [B, L] (right padded, any ids after the caption), lens int32 [B] = the
+ * caption's tokens (HF's attention_mask summed; clamped to 1..L); rows and keys beyond lens[b] do not influence pair b, and
+ * neither does L or the batch: the same bits alone, in a batch and padded to a longer L.
+ *   cap_blip2_itm_encode_images: B frames in pixel_fmt -> the image tokens (post_layernorm on every token) and the cross-attention
+ *     K/V of every cross layer stay RESIDENT in the handle: the ITC and ITM calls below read them, the tower runs once.
+ *   cap_blip2_itc_image_features: the B resident images -> out fp32 [B, num_query_tokens, embed_dim] =
+ *     normalize(vision_projection(Q-Former(queries, cross-attending the image)))
+ *   cap_blip2_itc_text_features: text alone through the Q-Former (no queries, no cross-attention, the text FFN) -> out fp32
+ *     [B, embed_dim] = normalize(text_projection(row 0)).  Needs no resident images; B <= max_batch.
+ *   cap_blip2_itc_scores: img [Ni, num_queries, embed_dim], txt [Nt, embed_dim] -> max over the queries of img . txt (no
+ *     temperature): paired = 1 -> out [Ni] (image i against caption i), paired = 0 -> out [Ni, Nt] (HF's logits_per_image).
+ *     Needs no handle.
+ *   cap_blip2_itm_logits: pair b = resident image b with caption b (B = the resident batch): rows [queries | text], key mask
+ *     [1 x queries | text mask], query rows cross-attend the image -> out_logits fp32 [B, 2] = mean over the query rows of
+ *     itm_head; out_prob fp32 [B] = softmax(logits)[:, 1] (the reference's score; may be NULL).
+ * Refused by message: text longer than max_len, B beyond max_batch or unequal to the resident batch, another architecture's
+ * handle; an image-text scorer handle refuses cap_encode / cap_generate / cap_embed_text / cap_clip_*. */
+int cap_blip2_itm_encode_images(CapHandle h, const void* pixels, int pixel_fmt, int B, void* stream);
+int cap_blip2_itc_image_features(CapHandle h, int B, float* out, void* stream);
+int cap_blip2_itc_text_features(CapHandle h, const int32_t* ids, const int32_t* lens, int B, int L, float* out, void* stream);
+int cap_blip2_itc_scores(const float* img, const float* txt, int Ni, int Nt, int paired, float* out, int num_queries, int embed_dim,
+                         void* stream);
+int cap_blip2_itm_logits(CapHandle h, const int32_t* ids, const int32_t* lens, int B, int L, float* out_logits, float* out_prob,
+                         void* stream);
+
 /* Range guard of CAP_F32_SPLIT.  Weights: cap_load_weight refuses (returns -1, message names the tensor) a tensor bound for
  * a GEMM-operand slot whose max |w| exceeds 65000 / 4096 = 15.87 or that holds a NaN - nothing is clipped silently.
  * Activations: every kernel that writes a GEMM operand clamps to +-65000 (fp16's range) and COUNTS what it clamped; this
@@ -284,6 +319,15 @@ int cap_op_vit_attention(int dtype, const void* qkv, void* ctx, int B, int N, in
  * impl | 8: causal mask (query i sees keys 0..i: the OPT prefill) */
 int cap_op_vit_attention_hd(int dtype, const void* qkv, void* ctx, int B, int N, int H, int head_dim, int impl,
                             void* stream);
+/* The generic attention launcher alone, unmasked self-attention over fused q|k|v rows [B * N, 3 H head_dim] -> ctx [B * N, H head_dim]:
+ * the kernel choice of launch_generic_attention (N <= 64 keys >= 16, heads <= 64 wide: the key-parallel kernel run_qformer's
+ * self-attention runs on).  Kernel tests and timing partners; nothing in the product path calls it. */
+int cap_op_generic_attention(int dtype, const void* qkv, void* ctx, int B, int N, int H, int head_dim, void* stream);
+/* The Q-Former self-attention of the BLIP-2 image-text scorer alone (csrc/blip2_itm.hip): per pair b the keys are the num_queries
+ * query rows and the first lens[b] of the L text rows; fused q|k|v rows qkv_q [B * num_queries, 3 H 64] / qkv_t [B * L, 3 H 64] ->
+ * ctx_q [B * num_queries, H 64] / ctx_t [B * L, H 64]; at most 32 rows per segment; num_queries = 0 or L = 0 drops a segment. */
+int cap_op_itm_self_attention(int dtype, const void* qkv_q, const void* qkv_t, const int32_t* lens, void* ctx_q, void* ctx_t, int B,
+                              int num_queries, int L, int H, void* stream);
 /* split-K consumer: y = sum_z part[z][M][D] + bias + resid (-> y_out, may alias resid), LayerNorm(y) -> out_t (dtype) /
  * out_f (fp32); any output may be NULL.  per_row_block: the decoder's workgroup-per-row kernels (few rows). */
 int cap_op_reduce_layernorm(int dtype, const float* part, int S, const float* bias, const float* resid,
