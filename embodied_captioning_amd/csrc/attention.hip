@@ -1307,6 +1307,21 @@ __global__ __launch_bounds__(256, 2) void decode_attention_shared_kernel(const T
     }
 }
 
+// The denominator of a lane's online softmax, l = l * c + p, summed with compensation (Kahan): `comp` carries the rounding error of the
+// running sum.  In a row with one dominant key l sits at 1 while every other key adds 1e-9 .. 1e-7 - below half an ulp of l such a
+// term is lost, just above it it counts as a whole ulp, and because every term is positive the loss grows with the key count: 6e-5 of
+// the context at 577 / 1 025 keys (tests/test_attention_kernels_gpu.py, peaked class; 5e-6 with the compensation).  The context sum o
+// has terms of both signs and stays within the reference's own error without it.
+__device__ __forceinline__ void softmax_denominator_add(float& l, float& comp, float c, float p) {
+#pragma clang fp contract(off)
+    const float ls = l * c;
+    comp *= c;
+    const float y = p - comp;
+    const float t = ls + y;
+    comp = (t - ls) - y;
+    l = t;
+}
+
 // ---- attentional pooler: Q learned queries (already layer-normed and projected on the host, identical for every
 // image) attend over the N image tokens.  One thread per query, K/V tiles broadcast from LDS, online softmax; head_dim is
 // a template parameter (CoCa ViT-L/14: 768 / 8 heads = 96).  ~1 % of the CoCa encoder's flops.
@@ -1322,7 +1337,7 @@ __global__ __launch_bounds__(64) void pool_attention_kernel(const float* __restr
     float qv[HD], o[HD];
 #pragma unroll
     for (int d = 0; d < HD; ++d) { qv[d] = qp[(size_t)qc * E + h * HD + d] * scale; o[d] = 0.f; }
-    float m = -INFINITY, l = 0.f;
+    float m = -INFINITY, l = 0.f, lc = 0.f;
     const T* base = kv + (size_t)b * N * 2 * E + h * HD;
     for (int k0 = 0; k0 < N; k0 += KT) {
         const int nk = min(KT, N - k0);
@@ -1339,14 +1354,14 @@ __global__ __launch_bounds__(64) void pool_attention_kernel(const float* __restr
             for (int d = 0; d < HD; ++d) sc = fmaf(qv[d], Ks[j][d], sc);
             const float mn = fmaxf(m, sc);
             const float c = expf(m - mn), pj = expf(sc - mn);
-            l = l * c + pj;
+            softmax_denominator_add(l, lc, c, pj);
 #pragma unroll
             for (int d = 0; d < HD; ++d) o[d] = fmaf(pj, Vs[j][d], o[d] * c);
             m = mn;
         }
     }
     if (q < Q) {
-        const float inv = 1.0f / l;
+        const float inv = 1.0f / (l - lc);
         TO* orow = out + ((size_t)b * Q + q) * E;
 #pragma unroll
         for (int d = 0; d < HD; ++d) store1(orow, h * HD + d, o[d] * inv);
@@ -1379,19 +1394,19 @@ __global__ __launch_bounds__(64) void text_attention_kernel(const T* __restrict_
         float qv[HD], o[HD];
 #pragma unroll
         for (int d = 0; d < HD; ++d) { qv[d] = to_f32(base[(size_t)q * ld + d]) * scale; o[d] = 0.f; }
-        float m = -INFINITY, l = 0.f;
+        float m = -INFINITY, l = 0.f, lc = 0.f;
         for (int j = 0; j < n; ++j) {
             float sc = 0.f;
 #pragma unroll
             for (int d = 0; d < HD; ++d) sc = fmaf(qv[d], Ks[j * HD + d], sc);
             const float mn = fmaxf(m, sc);
             const float c = expf(m - mn), pj = expf(sc - mn);
-            l = l * c + pj;
+            softmax_denominator_add(l, lc, c, pj);
 #pragma unroll
             for (int d = 0; d < HD; ++d) o[d] = fmaf(pj, Vs[j * HD + d], o[d] * c);
             m = mn;
         }
-        const float inv = 1.0f / l;
+        const float inv = 1.0f / (l - lc);
         T* op = ctx + ((size_t)b * L + q) * D + h * HD;
 #pragma unroll
         for (int d = 0; d < HD; ++d) op[d] = from_f32<T>(o[d] * inv);
@@ -1420,7 +1435,7 @@ __global__ __launch_bounds__(64) void generic_attention_kernel(const T* __restri
         qv[d] = (live && d < hd) ? to_f32(q[(size_t)b * qbs + (size_t)qi * ldq + h * hd + d]) * scale : 0.f;
         o[d] = 0.f;
     }
-    float m = -INFINITY, l = 0.f;
+    float m = -INFINITY, l = 0.f, lc = 0.f;
     const int kmax = causal_off >= 0 ? min(Lk, qb * 64 + 63 + causal_off + 1) : Lk;      // last key any query of this block sees
     for (int k0 = 0; k0 < kmax; k0 += 32) {
         __syncthreads();
@@ -1439,14 +1454,14 @@ __global__ __launch_bounds__(64) void generic_attention_kernel(const T* __restri
             for (int d = 0; d < HDP; ++d) sc = fmaf(qv[d], Ks[j * HDP + d], sc);
             const float mn = fmaxf(m, sc);
             const float c = expf(m - mn), pj = expf(sc - mn);
-            l = l * c + pj;
+            softmax_denominator_add(l, lc, c, pj);
 #pragma unroll
             for (int d = 0; d < HDP; ++d) o[d] = fmaf(pj, Vs[j * HDP + d], o[d] * c);
             m = mn;
         }
     }
     if (live) {
-        const float inv = 1.0f / l;
+        const float inv = 1.0f / (l - lc);
         TO* orow = out + (size_t)b * obs + (size_t)qi * ldo;          // row base: a multiple of 8 elements for a G8 output
 #pragma unroll
         for (int d = 0; d < HDP; ++d)
@@ -1579,7 +1594,7 @@ template <typename T, int HD8, typename TO = T>
 __global__ __launch_bounds__(64) void opt_decode_attention_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
                                                                   TO* __restrict__ out, int Tw, int H, int hd, int Lmax, int past,
                                                                   float scale) {
-    __shared__ float qs[128], ps[1024], os[4][128];
+    __shared__ float qs[128], ps[OPT_DECODE_MAX_KEYS], os[4][128];
     const int b = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x;
     const T* row = qkv + (size_t)b * 3 * Tw + h * hd;
     const T* kb = kc + (size_t)b * Lmax * Tw + h * hd;
@@ -2061,10 +2076,12 @@ int launch_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, 
         return -1;
     }
     const int hd = H > 0 ? T / H : 0;
-    if (B < 1 || H < 1 || T % H != 0 || hd % 8 != 0 || hd > 128 || past < 0 || past + 1 > 1024 || past >= Lmax) {
-        cap_set_error("opt_decode_attention: unsupported shape T=%d H=%d past=%d Lmax=%d", T, H, past, Lmax);
+    if (B < 1 || H < 1 || T % H != 0 || hd % 8 != 0 || hd < 8 || hd > 128 || past < 0 || past + 1 > OPT_DECODE_MAX_KEYS || past >= Lmax) {
+        cap_set_error("opt_decode_attention: unsupported shape T=%d H=%d past=%d Lmax=%d (head_dim a multiple of 8 up to 128, past < min(Lmax, %d))",
+                      T, H, past, Lmax, OPT_DECODE_MAX_KEYS);
         return -1;
     }
+    if (!qkv || !kc || !vc || !out) { cap_set_error("opt_decode_attention: null pointer"); return -1; }
     const float scale = 1.0f / sqrtf((float)hd);
 #define CAP_ODA(TT, H8, TO)                                                                                             \
     hipLaunchKernelGGL((opt_decode_attention_kernel<TT, H8, TO>), dim3(B * H), dim3(64), 0, s, (const TT*)qkv, (TT*)kc, (TT*)vc,  \
@@ -2093,6 +2110,10 @@ int launch_opt_token_inputs(const int* seq, int seq_ld, int cur, const float* to
     return 0;
 }
 int launch_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, hipStream_t s) {
+    if (B < 1 || L < 1 || T < 1 || pos0 < 0 || pos0 + L > Lmax || !qkv || !kc || !vc) {
+        cap_set_error("kv_append: rows %d..%d do not fit a cache of %d positions (B=%d T=%d), or a null pointer", pos0, pos0 + L - 1, Lmax, B, T);
+        return -1;
+    }
     if (dtype == CAP_DT_BF16)
         hipLaunchKernelGGL(kv_append_kernel<bf16_t>, dim3(256), dim3(256), 0, s, (const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, B, L, T, Lmax, pos0);
     else
@@ -2113,13 +2134,25 @@ int launch_rows_broadcast(int dtype, const float* src, float* dst_f, void* dst_t
 
 int launch_text_attention(int dtype, const void* qkv, const int* lens, void* ctx, int B, int L, int H, int head_dim,
                           hipStream_t s) {
-    if ((head_dim != 32 && head_dim != 64) || L < 1 || L > 512) {
-        cap_set_error("text_attention: head_dim %d / length %d unsupported (32 or 64, 1..512)", head_dim, L);
+    // K and V of one (sentence, head) sit in dynamic LDS as fp32: 2 * L * head_dim * 4 bytes, at most TEXT_ATTENTION_MAX_LDS (128 KB
+    // of the CU's 160) - 512 tokens at head_dim 32, 256 at 64.  cap_create holds the sentence encoder's max_len to the same bound.
+    if ((head_dim != 32 && head_dim != 64) || L < 1 || 2 * L * head_dim * 4 > TEXT_ATTENTION_MAX_LDS) {
+        cap_set_error("text_attention: head_dim %d / length %d unsupported (32 or 64, 1 <= length <= %d: K and V of a sentence stay in LDS)",
+                      head_dim, L, head_dim > 0 ? TEXT_ATTENTION_MAX_LDS / (8 * head_dim) : 0);
+        return -1;
+    }
+    if (B < 1 || H < 1 || !qkv || !lens || !ctx) {
+        cap_set_error("text_attention: null pointer or empty batch (B=%d H=%d)", B, H);
         return -1;
     }
     const int lds = 2 * L * head_dim * 4;
+    // more than 64 KB of dynamic LDS needs the attribute; it is set once per kernel, so to the most any length may ask for
 #define CAP_TA(TT, HDD)                                                                                                \
-    hipLaunchKernelGGL((text_attention_kernel<TT, HDD>), dim3(B * H), dim3(64), lds, s, (const TT*)qkv, lens, (TT*)ctx, L, H)
+    do {                                                                                                               \
+        auto kern = text_attention_kernel<TT, HDD>;                                                                     \
+        if (cap_kernel_setup((const void*)kern, TEXT_ATTENTION_MAX_LDS, nullptr) != 0) return -1;                       \
+        hipLaunchKernelGGL(kern, dim3(B * H), dim3(64), lds, s, (const TT*)qkv, lens, (TT*)ctx, L, H);                  \
+    } while (0)
     if (dtype == CAP_DT_BF16) { if (head_dim == 32) CAP_TA(bf16_t, 32); else CAP_TA(bf16_t, 64); }
     else { if (head_dim == 32) CAP_TA(float, 32); else CAP_TA(float, 64); }
 #undef CAP_TA
@@ -2134,9 +2167,13 @@ int launch_pool_attention(int dtype, const float* qp, const void* kv, void* out,
         cap_set_error("pool_attention: output type %d for input type %d is not supported here", out_dtype, dtype);
         return -1;
     }
-    const int hd = E / heads;
+    const int hd = heads > 0 ? E / heads : 0;
     if (hd * heads != E || (hd != 64 && hd != 96)) {
         cap_set_error("pool_attention: head_dim %d not supported (64 or 96)", hd);
+        return -1;
+    }
+    if (B < 1 || N < 1 || Q < 1 || !qp || !kv || !out) {
+        cap_set_error("pool_attention: empty shape (B=%d N=%d Q=%d) or null pointer", B, N, Q);
         return -1;
     }
     dim3 grid(B * heads, (Q + 63) / 64);

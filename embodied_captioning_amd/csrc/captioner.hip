@@ -1936,9 +1936,14 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
         const int hd = cfg->t_heads > 0 ? cfg->t_hidden / cfg->t_heads : 0;
         if ((hd != 32 && hd != 64) || hd * cfg->t_heads != cfg->t_hidden || cfg->t_hidden % 64 || cfg->t_ffn % 64 ||
             cfg->t_hidden > 1024 || cfg->t_layers < 1 || cfg->max_batch < 1 || cfg->max_len < 1 || cfg->max_len > cfg->max_pos ||
-            cfg->max_len > 512 || cfg->vocab < 1) {
+            cfg->vocab < 1) {
             cap_set_error("cap_create: sentence encoder needs head_dim 32 or 64, widths multiple of 64 (hidden <= 1024), "
-                          "1 <= max_len <= min(max_pos, 512)");
+                          "1 <= max_len <= max_pos");
+            return -1;
+        }
+        if (2 * cfg->max_len * hd * 4 > TEXT_ATTENTION_MAX_LDS) {      // what launch_text_attention takes: refused here, not at the first long sentence
+            cap_set_error("cap_create: sentence encoder max_len %d is beyond the %d tokens its attention kernel holds in LDS at head_dim %d",
+                          cfg->max_len, TEXT_ATTENTION_MAX_LDS / (8 * hd), hd);
             return -1;
         }
     } else if (cfg->arch == CAP_ARCH_CLIP) {
@@ -1978,6 +1983,11 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
             cfg->num_query_tokens + 1 + cfg->max_len > cfg->max_pos) {
             cap_set_error("cap_create: BLIP-2 needs head dims that are multiples of 8 (<= 128), widths multiple of 64 (OPT hidden <= 3072), "
                           "max_beams 1 and num_query_tokens + 1 + max_len <= max_pos");
+            return -1;
+        }
+        if (cfg->num_query_tokens + 1 + cfg->max_len > OPT_DECODE_MAX_KEYS) {      // launch_opt_decode_attention's limit: refused here, not mid-generation
+            cap_set_error("cap_create: BLIP-2 num_query_tokens + 1 + max_len = %d is beyond the %d cached positions the decode-step attention "
+                          "kernel takes", cfg->num_query_tokens + 1 + cfg->max_len, OPT_DECODE_MAX_KEYS);
             return -1;
         }
     } else {
@@ -2466,6 +2476,27 @@ int cap_op_generic_attention(int dtype, const void* qkv, void* ctx, int B, int N
 int cap_op_itm_self_attention(int dtype, const void* qkv_q, const void* qkv_t, const int32_t* lens, void* ctx_q, void* ctx_t, int B,
                               int num_queries, int L, int H, void* stream) {
     return launch_itm_self_attention(in_dt_of(dtype), qkv_q, qkv_t, lens, ctx_q, ctx_t, B, num_queries, L, H, 64, (hipStream_t)stream, dt_of(dtype));
+}
+/* the attention launchers of the BLIP-2 / CoCa / sentence-encoder paths alone (tests/test_attention_kernels_gpu.py) */
+int cap_op_attention(int dtype, const void* q, int64_t ldq, int64_t qbs, const void* k, int64_t ldk, int64_t kbs, const void* v, int64_t ldv,
+                     int64_t vbs, void* out, int64_t ldo, int64_t obs, int B, int Lq, int Lk, int H, int head_dim, int causal_off, void* stream) {
+    if (!q || !k || !v || !out) { cap_set_error("cap_op_attention: null pointer"); return -1; }
+    return launch_generic_attention(in_dt_of(dtype), q, (long)ldq, (long)qbs, k, (long)ldk, (long)kbs, v, (long)ldv, (long)vbs, out, (long)ldo,
+                                    (long)obs, B, Lq, Lk, H, head_dim, causal_off, (hipStream_t)stream, dt_of(dtype));
+}
+int cap_op_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int T, int H, int Lmax, int past,
+                                void* stream) {
+    return launch_opt_decode_attention(in_dt_of(dtype), qkv, kc, vc, out, B, T, H, Lmax, past, (hipStream_t)stream, dt_of(dtype));
+}
+int cap_op_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, void* stream) {
+    return launch_kv_append(in_dt_of(dtype), qkv, kc, vc, B, L, T, Lmax, pos0, (hipStream_t)stream);
+}
+int cap_op_pool_attention(int dtype, const float* qp, const void* kv, void* out, int B, int N, int Q, int E, int heads, void* stream) {
+    return launch_pool_attention(in_dt_of(dtype), qp, kv, out, B, N, Q, E, heads, (hipStream_t)stream, dt_of(dtype));
+}
+int cap_op_text_attention(int dtype, const void* qkv, const int32_t* lens, void* ctx, int B, int L, int H, int head_dim, void* stream) {
+    if (dtype != CAP_F32 && dtype != CAP_BF16) { cap_set_error("cap_op_text_attention: the sentence encoder takes CAP_F32 or CAP_BF16"); return -1; }
+    return launch_text_attention(in_dt_of(dtype), qkv, lens, ctx, B, L, H, head_dim, (hipStream_t)stream);
 }
 int cap_crop_resize_tables(const int32_t* rects, const int32_t* geom, int n, int S, int KH, int KV, int32_t* hb, int32_t* hk,
                            int32_t* vb, int32_t* vk, void* stream) {

@@ -41,6 +41,7 @@ int launch_embed_tokens(int dtype, const int* ids, int L, const float* word, con
                         const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int R, int D,
                         hipStream_t s, int V);   // ids outside [0, V) are clamped
 int launch_mean_pool_normalize(const float* x, const int* lens, int B, int L, int D, float* out, hipStream_t s);
+constexpr int TEXT_ATTENTION_MAX_LDS = 128 * 1024;      // bytes of LDS text_attention may ask for: 2 * L * head_dim * 4 <= this
 int launch_text_attention(int dtype, const void* qkv, const int* lens, void* ctx, int B, int L, int H, int head_dim,
                           hipStream_t s);
 int launch_embed(int dtype, const int* seq, int seq_ld, int t, const float* word, const float* pos,
@@ -82,6 +83,7 @@ int launch_opt_prefill_inputs(const float* proj, const float* tok, const float* 
 int launch_opt_token_inputs(const int* seq, int seq_ld, int cur, const float* tok, const float* pos, float* x, int B, int T,
                             hipStream_t s);
 // decode step of a pre-LN decoder: q|k|v row [B, 3T] -> appends k, v to caches [B][Lmax][T] at `past`, out [B, T]
+constexpr int OPT_DECODE_MAX_KEYS = 1024;      // cached positions (past + 1) launch_opt_decode_attention takes: its scores sit in LDS
 int launch_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int T, int H, int Lmax,
                                 int past, hipStream_t s, int out_dtype = -1);
 int launch_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, hipStream_t s);

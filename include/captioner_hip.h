@@ -328,6 +328,26 @@ int cap_op_generic_attention(int dtype, const void* qkv, void* ctx, int B, int N
  * ctx_q [B * num_queries, H 64] / ctx_t [B * L, H 64]; at most 32 rows per segment; num_queries = 0 or L = 0 drops a segment. */
 int cap_op_itm_self_attention(int dtype, const void* qkv_q, const void* qkv_t, const int32_t* lens, void* ctx_q, void* ctx_t, int B,
                               int num_queries, int L, int H, void* stream);
+/* launch_generic_attention with its whole argument list: q / k / v / out in buffers of their own, row strides ld* and batch strides
+ * *bs in elements (out: G8 containers count as elements), head h of a row at column h * head_dim.  causal_off >= 0: query i sees keys
+ * j <= i + causal_off (the cached decode step and a prompt continuation); < 0: no mask.  Kernel choice: Lq == 1 with Lk <= 1024 the
+ * one-query decode kernel, unmasked Lq <= 64 against Lk >= 16 keys at heads <= 64 wide the four-wave key-parallel kernel, everything
+ * else the lane = query kernel. */
+int cap_op_attention(int dtype, const void* q, int64_t ldq, int64_t qbs, const void* k, int64_t ldk, int64_t kbs, const void* v, int64_t ldv,
+                     int64_t vbs, void* out, int64_t ldo, int64_t obs, int B, int Lq, int Lk, int H, int head_dim, int causal_off, void* stream);
+/* The cached OPT decode step: one query per (row, head) from the fused q|k|v rows qkv [B, 3 T]; the row's k | v are written to the
+ * caches kc / vc [B][Lmax][T] at position past and the query attends to positions 0..past -> out [B, T].  head_dim = T / H a multiple
+ * of 8 up to 128, past < min(Lmax, 1024). */
+int cap_op_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int T, int H, int Lmax, int past,
+                                void* stream);
+/* k | v columns of fused rows qkv [B * L, 3 T] -> caches kc / vc [B][Lmax][T] at positions pos0 .. pos0 + L - 1 (CAP_F32_SPLIT: fp32). */
+int cap_op_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, void* stream);
+/* The CoCa attentional pooler's attention: Q projected queries qp [Q, E] (fp32, shared by the batch) over kv [B * N, 2 E] (K then V)
+ * -> out [B * Q, E]; head_dim = E / heads is 64 or 96. */
+int cap_op_pool_attention(int dtype, const float* qp, const void* kv, void* out, int B, int N, int Q, int E, int heads, void* stream);
+/* The sentence encoder's self-attention over fused rows qkv [B * L, 3 H head_dim] with the key mask j < lens[b] (clamped to 1..L) ->
+ * ctx [B * L, H head_dim]; CAP_F32 or CAP_BF16, head_dim 32 (L <= 512) or 64 (L <= 256). */
+int cap_op_text_attention(int dtype, const void* qkv, const int32_t* lens, void* ctx, int B, int L, int H, int head_dim, void* stream);
 /* split-K consumer: y = sum_z part[z][M][D] + bias + resid (-> y_out, may alias resid), LayerNorm(y) -> out_t (dtype) /
  * out_f (fp32); any output may be NULL.  per_row_block: the decoder's workgroup-per-row kernels (few rows). */
 int cap_op_reduce_layernorm(int dtype, const float* part, int S, const float* bias, const float* resid,

@@ -93,3 +93,51 @@ def test_single_kernel_entry_points_validate_shapes():
     x = torch.zeros(4, 30, device="cuda")
     assert lib.cap_op_layernorm(0, C.c_void_p(x.data_ptr()), C.c_void_p(x.data_ptr()), C.c_void_p(x.data_ptr()), C.c_float(1e-5),
                                 C.c_void_p(x.data_ptr()), None, 4, 30, s) != 0
+
+
+def test_attention_entry_points_refuse_bad_head_dims_and_null_pointers():
+    from embodied_captioning_amd import _native as N
+    lib = N.load_library()
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    x = torch.zeros(4096, device="cuda")
+    lens = torch.ones(4, dtype=torch.int32, device="cuda")
+    p = C.c_void_p(x.data_ptr())
+    att = lambda q, hd, Lq=8, Lk=8: lib.cap_op_attention(0, q, 3 * hd, 24 * hd, p, 3 * hd, 24 * hd, p, 3 * hd, 24 * hd, p, hd, 8 * hd, 1, Lq, Lk,  # noqa: E731
+                                                         1, hd, -1, s)
+    assert att(p, 4) != 0 and "head_dim 4" in N.last_error()
+    assert att(p, 136) != 0 and "head_dim 136" in N.last_error()
+    assert att(p, 64, Lk=0) != 0 and "generic_attention" in N.last_error()
+    assert att(None, 64) != 0 and "null" in N.last_error()
+    # split mode writes G8: the output rows must start on whole groups of 8
+    assert lib.cap_op_attention(2, p, 36, 288, p, 36, 288, p, 36, 288, p, 12, 96, 1, 8, 8, 1, 12, -1, s) != 0 and "output type" in N.last_error()
+    opt = lambda qkv, T, H, Lmax, past: lib.cap_op_opt_decode_attention(0, qkv, p, p, p, 1, T, H, Lmax, past, s)      # noqa: E731
+    assert opt(p, 144, 1, 8, 0) != 0 and "opt_decode_attention" in N.last_error()          # head_dim 144 > 128
+    assert opt(p, 100, 2, 8, 0) != 0 and "T=100" in N.last_error()                         # head_dim 50: not a multiple of 8
+    assert opt(p, 128, 3, 8, 0) != 0 and "H=3" in N.last_error()                           # heads do not divide the width
+    assert opt(None, 128, 2, 8, 0) != 0 and "null" in N.last_error()
+    assert lib.cap_op_kv_append(0, None, p, p, 1, 2, 64, 8, 0, s) != 0 and "kv_append" in N.last_error()
+    assert lib.cap_op_kv_append(0, p, p, p, 1, 2, 64, 8, 7, s) != 0 and "do not fit" in N.last_error()
+    assert lib.cap_op_kv_append(0, p, p, p, 1, 2, 64, 8, -1, s) != 0 and "do not fit" in N.last_error()
+    pool = lambda kv, E, heads: lib.cap_op_pool_attention(0, p, kv, p, 1, 4, 4, E, heads, s)      # noqa: E731
+    assert pool(p, 160, 2) != 0 and "head_dim 80" in N.last_error()
+    assert pool(p, 128, 0) != 0 and "head_dim" in N.last_error()
+    assert pool(None, 128, 2) != 0 and "null" in N.last_error()
+    text = lambda qkv, ln, hd, L: lib.cap_op_text_attention(0, qkv, ln, p, 1, L, 1, hd, s)      # noqa: E731
+    ln = C.c_void_p(lens.data_ptr())
+    assert text(p, ln, 48, 8) != 0 and "head_dim 48" in N.last_error()
+    assert text(p, ln, 64, 257) != 0 and "length 257" in N.last_error()
+    assert text(p, None, 32, 8) != 0 and "null" in N.last_error()
+    assert text(None, ln, 32, 8) != 0 and "null" in N.last_error()
+    torch.cuda.synchronize()
+
+
+def test_create_refuses_a_blip2_engine_longer_than_its_decode_attention():
+    """num_query_tokens + 1 + max_len positions must fit the decode-step attention kernel (1024): refused at create, not mid-generation."""
+    from embodied_captioning_amd import _native as N
+    from embodied_captioning_amd.config import Blip2Arch
+    from embodied_captioning_amd.engine import CaptionerEngine
+    import dataclasses
+    a = dataclasses.replace(Blip2Arch.tiny(), max_pos=2048)          # OPT's own table length: max_pos is not what refuses
+    with pytest.raises(N.CaptionerHipError, match="cached positions"):
+        CaptionerEngine(a, dtype="f32", max_batch=1, max_beams=1, max_len=1024 - a.num_query_tokens)
+    CaptionerEngine(a, dtype="f32", max_batch=1, max_beams=1, max_len=1023 - a.num_query_tokens).close()
