@@ -152,9 +152,13 @@ class BLIP(CaptioningPredictor):
 
     # ------------------------------------------------------------------------------------------ forward
     @torch.no_grad()
-    def generate_batch(self, images, output_logits: bool = False) -> dict:
-        """Batched extension: any number of frames -> {"texts": [str], "sequences": int32 [N, L], "lengths", "scores"}."""
+    def generate_batch(self, images, output_logits: bool = False, output_perplexity: bool = False) -> dict:
+        """Batched extension: any number of frames -> {"texts": [str], "sequences": int32 [N, L], "lengths", "scores"}.
+        output_perplexity (greedy): adds "perplexities" float64 [N] - what `forward` + `compute_perplexity()` give one crop at a
+        time - and "token_logprobs" fp32 [N, steps] / "scored_steps" int32 [N] they are computed from (engine.generate,
+        output_logprobs); the pool, its dynamic batching and the preprocessing overlap work as without it."""
         texts: List[str] = []
+        kw = {"output_logprobs": True} if output_perplexity else {}
         seqs, lens, scores, logits = [], [], [], []
         pool = getattr(self, "pool", None)
         # a long list of PIL crops on a pool: in rounds of one pass per engine, the next round's crops are preprocessed (host
@@ -173,15 +177,15 @@ class BLIP(CaptioningPredictor):
                         nxt = ex.submit(self.preprocess, groups[g + 1])
                     chunks = [px[i:i + self.batch_size].to(self._device) for i in range(0, px.shape[0], self.batch_size)]
                     outs += self.pool.generate_many(chunks, threads=True, coalesce_rows=self.coalesce_rows, num_beams=self.num_beams,
-                                                    max_length=self.max_length)
+                                                    max_length=self.max_length, **kw)
         else:
             px = self.preprocess(images)
             chunks = [px[i:i + self.batch_size].to(self._device) for i in range(0, px.shape[0], self.batch_size)]
             if pool is not None and len(chunks) > 1 and not output_logits:
                 outs = self.pool.generate_many(chunks, threads=True, coalesce_rows=self.coalesce_rows, num_beams=self.num_beams,
-                                               max_length=self.max_length)
+                                               max_length=self.max_length, **kw)
             else:
-                outs = [self.engine.generate(c, num_beams=self.num_beams, max_length=self.max_length, output_logits=output_logits)
+                outs = [self.engine.generate(c, num_beams=self.num_beams, max_length=self.max_length, output_logits=output_logits, **kw)
                         for c in chunks]
         for out in outs:
             seqs.append(out["sequences"]); lens.append(out["lengths"])
@@ -199,6 +203,11 @@ class BLIP(CaptioningPredictor):
             res["scores"] = torch.cat(scores).cpu()
         if output_logits:
             res["logits"] = logits
+        if output_perplexity:
+            from ....engine import perplexity_from_logprobs
+            res["token_logprobs"] = torch.cat([o["token_logprobs"] for o in outs]).cpu()
+            res["scored_steps"] = torch.cat([o["scored_steps"] for o in outs]).cpu()
+            res["perplexities"] = perplexity_from_logprobs(res["token_logprobs"], res["scored_steps"])
         return res
 
     @torch.no_grad()

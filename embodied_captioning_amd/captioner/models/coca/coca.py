@@ -192,8 +192,12 @@ class CoCa(CaptioningPredictor):
         return out["sequences"]
 
     @torch.no_grad()
-    def generate_batch(self, images) -> dict:
+    def generate_batch(self, images, output_perplexity: bool = False) -> dict:
+        """output_perplexity (the greedy top-k(1) loop): adds "perplexities" float64 [N] - `forward` + `compute_perplexity()` one crop
+        at a time - with the "token_logprobs" / "scored_steps" behind them (engine.generate, output_logprobs)."""
         kw = dict(num_beams=self.num_beams, max_length=self.arch.seq_len, num_beam_groups=self.num_beam_groups)
+        if output_perplexity:
+            kw["output_logprobs"] = True
         rnd = len(self.pool) * max(self.batch_size, self.coalesce_rows) if self.pool is not None else 0
         if self.pool is not None and isinstance(images, (list, tuple)) and len(images) > rnd:
             # a long list of PIL crops: in rounds of one pass per engine, the next round preprocessed by a helper thread meanwhile
@@ -220,6 +224,11 @@ class CoCa(CaptioningPredictor):
         res = {"texts": [self.decode(r[:n]) for r, n in zip(seq.tolist(), ln.tolist())], "sequences": seq, "lengths": ln}
         if all("sequences_scores" in o for o in outs):
             res["scores"] = torch.cat([o["sequences_scores"] for o in outs]).cpu()
+        if output_perplexity:
+            from ....engine import perplexity_from_logprobs
+            res["token_logprobs"] = torch.cat([o["token_logprobs"] for o in outs]).cpu()
+            res["scored_steps"] = torch.cat([o["scored_steps"] for o in outs]).cpu()
+            res["perplexities"] = perplexity_from_logprobs(res["token_logprobs"], res["scored_steps"])
         return res
 
     @torch.no_grad()

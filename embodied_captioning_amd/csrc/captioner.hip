@@ -1073,11 +1073,15 @@ int run_opt_step(Captioner* m, int B, int past, hipStream_t s) {
 }
 
 // HF Blip2ForConditionalGeneration.generate, greedy: out_ids [B, max_len] = the new tokens (pad after EOS), out_len [B] =
-// their count incl. EOS, out_step_logits [max_len, B, vocab].
+// their count incl. EOS, out_step_logits [max_len, B, vocab]; out_lp [B, max_len] / out_scored [B]: cap_generate_scored.
 int run_generate_blip2(Captioner* m, const void* pixels, int fmt, int B, int max_len, int32_t* out_ids, int32_t* out_len,
-                       float* out_step_logits, hipStream_t s) {
+                       float* out_step_logits, float* out_lp, int32_t* out_scored, hipStream_t s) {
     const CapConfig& c = m->c;
     const int T = c.t_hidden, nq = c.num_query_tokens, P = nq + 1, Lmax = P + c.max_len;
+    if (out_lp) {
+        TRY(launch_fill_f32(out_lp, 0.f, (size_t)B * max_len, s));
+        TRY(launch_fill_i32(out_scored, 0, (size_t)B, s));
+    }
     TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
     TRY(run_qformer(m, B, s));
     TRY(gemm(m, s, "b2_gemm_lproj", m->qx_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1));
@@ -1093,7 +1097,8 @@ int run_generate_blip2(Captioner* m, const void* pixels, int fmt, int B, int max
             CAP_HIP_CHECK(hipGetLastError());
         }
         // token of position P + t; a row finishes on EOS or at P + max_len tokens (greedy_select's `t` is the last filled index)
-        TRY(launch_greedy_select(m->logits, m->ldl, c.vocab, m->seq, Lmax, P - 1 + t, P + max_len, c.eos, c.pad, m->finished, m->lens, B, s, 0, 0));
+        TRY(launch_greedy_select(m->logits, m->ldl, c.vocab, m->seq, Lmax, P - 1 + t, P + max_len, c.eos, c.pad, m->finished, m->lens, B, s, 0, 0,
+                                 RowMap(), out_lp, max_len, t, out_scored));
         if (t + 1 == max_len) break;
         {
             bool done;
@@ -1809,13 +1814,20 @@ static int run_image_side(Captioner* m, const void* pixels, int fmt, int B, hipS
 }
 
 int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm, float lp, int32_t* out_ids,
-                 int32_t* out_len, float* out_scores, float* out_step_logits, hipStream_t s, bool force_beam = false) {
+                 int32_t* out_len, float* out_scores, float* out_step_logits, hipStream_t s, bool force_beam = false,
+                 float* out_lp = nullptr, int32_t* out_scored = nullptr) {
     // force_beam: K == 1 runs as a 1-beam BEAM search (the scorer's bookkeeping, no forced EOS) instead of the greedy loop -
     // what a beam group of size one is (cap_generate_groups)
+    // out_lp [B, Lm - 1] / out_scored [B] (greedy only, cap_generate_scored): per-step log max softmax from the selection kernel,
+    // indexed by the caption's row whatever the loop's compaction; zero-filled here, on the caller's stream
     const CapConfig& c = m->c;
     const int R = B * K;
     const bool coca = c.arch == CAP_ARCH_COCA;
     const bool greedy = K == 1 && !force_beam;
+    if (out_lp) {
+        TRY(launch_fill_f32(out_lp, 0.f, (size_t)R * (Lm - 1), s));
+        TRY(launch_fill_i32(out_scored, 0, (size_t)R, s));
+    }
     TRY(run_image_side(m, pixels, fmt, B, s));
     Dec d = make_slice(m, 0, B, B, K, Lm);
     // Row compaction (ops.h, RowMap): the greedy BLIP loop on the batch kernels, when nobody asked for per-step logits (their rows
@@ -1870,7 +1882,7 @@ int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm
         if (greedy)
         {
             TRY(launch_greedy_select(d.logits, m->ldl, c.vocab, d.seq, Lm, t, Lm, c.eos, c.pad, d.finished, d.lens, R, s,
-                                     coca ? c.min_len : 0, coca ? 1 : 0, d.map));
+                                     coca ? c.min_len : 0, coca ? 1 : 0, d.map, out_lp, Lm - 1, t, out_scored));
             if (compact) TRY(launch_compact_rows(d.finished, R, m->live, m->n_live, s));
         }
         else
@@ -2341,19 +2353,36 @@ int cap_encode(CapHandle h, const void* pixels, int pixel_fmt, int B, float* out
     return run_encoder(m, pixels, pixel_fmt, B, out_embeds, (hipStream_t)stream);
 }
 
-int cap_generate(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int max_len, float length_penalty,
-                 int32_t* out_ids, int32_t* out_len, float* out_scores, float* out_step_logits, void* stream) {
+int cap_generate_scored(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int max_len, float length_penalty,
+                        int32_t* out_ids, int32_t* out_len, float* out_scores, float* out_step_logits, float* out_logprobs,
+                        int32_t* out_scored, void* stream) {
     Captioner* m = (Captioner*)h;
     TRY(check_call(m, B, num_beams, max_len, pixel_fmt));
     if (!pixels || !out_ids) { cap_set_error("cap_generate: null buffer"); return -1; }
+    if ((out_logprobs != nullptr) != (out_scored != nullptr)) {
+        cap_set_error("cap_generate_scored: out_logprobs and out_scored come together (both or neither)");
+        return -1;
+    }
+    if (out_logprobs && num_beams != 1) {
+        cap_set_error("cap_generate_scored: per-step log-probs are the greedy loop's (num_beams = 1), got num_beams = %d: beam search "
+                      "returns sequences_scores", num_beams);
+        return -1;
+    }
     if (m->c.arch == CAP_ARCH_BLIP2) {
         if (num_beams != 1) { cap_set_error("cap_generate: BLIP-2 supports greedy decoding (num_beams = 1)"); return -1; }
-        return run_generate_blip2(m, pixels, pixel_fmt, B, max_len, out_ids, out_len, out_step_logits, (hipStream_t)stream);
+        return run_generate_blip2(m, pixels, pixel_fmt, B, max_len, out_ids, out_len, out_step_logits, out_logprobs, out_scored,
+                                  (hipStream_t)stream);
     }
     // CoCa: num_beams == 1 is the reference's top-k(1) loop (coca.py:29), num_beams > 1 its `_generate_beamsearch` with one
     // beam group (coca_model.py:335-482; length_penalty is the scorer's: pass 1.0 for the reference's default)
     return run_generate(m, pixels, pixel_fmt, B, num_beams, max_len, length_penalty, out_ids, out_len, out_scores,
-                        out_step_logits, (hipStream_t)stream);
+                        out_step_logits, (hipStream_t)stream, false, out_logprobs, out_scored);
+}
+
+int cap_generate(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int max_len, float length_penalty,
+                 int32_t* out_ids, int32_t* out_len, float* out_scores, float* out_step_logits, void* stream) {
+    return cap_generate_scored(h, pixels, pixel_fmt, B, num_beams, max_len, length_penalty, out_ids, out_len, out_scores,
+                               out_step_logits, nullptr, nullptr, stream);
 }
 
 int cap_generate_groups(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int num_beam_groups, int max_len,
@@ -2559,6 +2588,20 @@ int cap_op_beam_candidates(const float* logits, int ld, int V, int B, int K, int
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -1;
     (void)hipFree(st);
     return rc;
+}
+int cap_op_select_logprob(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int min_len, int force_eos,
+                          int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths,
+                          float* logprobs, int lp_ld, int32_t* scored, void* stream) {
+    // ld % 4: the kernel reads rows with 16-byte loads (the engine's logits rows are padded the same way)
+    if (!logits || !finished || !seq || !lengths || R < 1 || V < 1 || ld < V || ld % 4 != 0 || t < 0 || t + 1 >= max_len ||
+        (logprobs != nullptr) != (scored != nullptr) || (live != nullptr) != (n_live != nullptr)) {
+        cap_set_error("cap_op_select_logprob: bad arguments");
+        return -1;
+    }
+    RowMap map;
+    map.live = live; map.n = n_live;
+    return launch_greedy_select(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, min_len,
+                                force_eos, map, logprobs, lp_ld, t, scored);
 }
 int cap_op_convert(int dtype, const float* src, void* dst, size_t n, void* stream) {
     return launch_convert(dt_of(dtype), src, dst, n, (hipStream_t)stream);

@@ -341,18 +341,11 @@ __global__ __launch_bounds__(256) void mean_pool_normalize_kernel(const float* _
 // ------------------------------------------------------------------------------------------------
 // Greedy step (HF:generation/utils.py:2925-2937): next = argmax (first maximal index, like torch.argmax);
 // finished rows emit pad; a row finishes when it emits EOS or reaches max_len.
-__global__ __launch_bounds__(256) void greedy_select_kernel(const float* __restrict__ logits, int ld, int V,
-                                                            int* __restrict__ seq, int seq_ld, int t, int max_len,
-                                                            int eos, int pad, int* __restrict__ finished,
-                                                            int* __restrict__ out_len, int min_len, int force_eos, RowMap map) {
-    // min_len > 0: EOS cannot win while the row has fewer than min_len tokens (HF MinLengthLogitsProcessor, used by the
-    // reference's CoCa loop coca_model.py:235-240); force_eos (= "this is the CoCa loop"): the last position is EOS
-    // (coca_model.py:317-318) and a sampled pad id ends the row (:305)
-    const int crow = blockIdx.x, tid = threadIdx.x;      // logits row; the caption it belongs to is row map.live[crow]
-    if (map.n && crow >= *map.n) return;                 // (uniform over the block: before any barrier)
-    const int row = map.live ? map.live[crow] : crow;
-    const bool mask_eos = min_len > 0 && t + 1 < min_len;
-    const float* x = logits + (size_t)crow * ld;
+//
+// The selection is shared by greedy_select_kernel and its scoring form: block argmax over one logits row (EOS masked while
+// mask_eos), result in sv[0] / si[0] for every thread after the last barrier.
+__device__ __forceinline__ void greedy_row_argmax(const float* __restrict__ x, int V, int eos, bool mask_eos, int tid,
+                                                  float* sv, int* si) {
     float best = -INFINITY;
     int bi = 0x7fffffff;
     // 16-byte loads, 4 independent chunks in flight per thread; ascending index order inside a thread keeps "first
@@ -384,8 +377,6 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const float* __restr
         const float v = (mask_eos && i == eos) ? -INFINITY : x[i];
         if (v > best) { best = v; bi = i; }
     }
-    __shared__ float sv[256];
-    __shared__ int si[256];
     sv[tid] = best; si[tid] = bi;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
@@ -395,17 +386,107 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const float* __restr
         }
         __syncthreads();
     }
+}
+
+// One thread appends the row's token and keeps finished / out_len; returns whether the row was open at this step.
+__device__ __forceinline__ bool greedy_row_emit(int row, int best_i, int* __restrict__ seq, int seq_ld, int t, int max_len,
+                                                int eos, int pad, int* __restrict__ finished, int* __restrict__ out_len,
+                                                int force_eos) {
+    int fin = finished[row];
+    int tok = fin ? pad : best_i;
+    if (!fin && force_eos && t + 2 >= max_len) tok = eos;
+    seq[(size_t)row * seq_ld + t + 1] = tok;
+    if (!fin) {
+        if (tok == eos || t + 2 >= max_len) { finished[row] = 1; out_len[row] = t + 2; }
+        // the reference's CoCa loop also stops a row whose newest token IS the pad id (coca_model.py:305: `mask =
+        // last == eos | last == pad`; pad id 0 is an ordinary vocabulary entry there): it emits pad from then on and
+        // gets no EOS.  The row's length then excludes that pad.
+        else if (force_eos && tok == pad) { finished[row] = 1; out_len[row] = t + 1; }
+    }
+    return !fin;
+}
+
+__global__ __launch_bounds__(256) void greedy_select_kernel(const float* __restrict__ logits, int ld, int V,
+                                                            int* __restrict__ seq, int seq_ld, int t, int max_len,
+                                                            int eos, int pad, int* __restrict__ finished,
+                                                            int* __restrict__ out_len, int min_len, int force_eos, RowMap map) {
+    // min_len > 0: EOS cannot win while the row has fewer than min_len tokens (HF MinLengthLogitsProcessor, used by the
+    // reference's CoCa loop coca_model.py:235-240); force_eos (= "this is the CoCa loop"): the last position is EOS
+    // (coca_model.py:317-318) and a sampled pad id ends the row (:305)
+    const int crow = blockIdx.x, tid = threadIdx.x;      // logits row; the caption it belongs to is row map.live[crow]
+    if (map.n && crow >= *map.n) return;                 // (uniform over the block: before any barrier)
+    const int row = map.live ? map.live[crow] : crow;
+    const bool mask_eos = min_len > 0 && t + 1 < min_len;
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    greedy_row_argmax(logits + (size_t)crow * ld, V, eos, mask_eos, tid, sv, si);
+    if (tid == 0) greedy_row_emit(row, si[0], seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
+}
+
+// Scoring form: the same selection, plus log max softmax of the row as the selection sees it (EOS masked while mask_eos) -
+// the per-step term of the reference's compute_perplexity (captioning_predictor.py:34-47) - for every row open at this step:
+//   lp = z_max - logsumexp(z) = -log(1 + sum_{i != argmax} exp(z_i - z_max))
+// written to logprobs[row][lp_col]; scored[row] counts the steps written.  Rows already finished keep the caller's zeros.
+// Two reads of the row: the first is the selection above, the second (from L2: a row is at most 200 KB) sums exp(z_i - z_max)
+// over every index but the selected one, so a peaked row keeps its tail (1 + 1e-9 would round to 1) and log1pf takes it.
+// The sum is never serial across the row: thread tid owns the float4 chunks tid, tid + 256, ... (four partial sums, one per
+// component) and the tail elements tid, tid + 256, ...; the 256 thread sums meet in a fixed LDS tree.  Assignment and tree depend
+// on V alone, so a row's value does not depend on its position, the grid or the RowMap.  Accurate expf / log1pf.
+__global__ __launch_bounds__(256) void greedy_select_logprob_kernel(const float* __restrict__ logits, int ld, int V,
+                                                                    int* __restrict__ seq, int seq_ld, int t, int max_len,
+                                                                    int eos, int pad, int* __restrict__ finished,
+                                                                    int* __restrict__ out_len, int min_len, int force_eos,
+                                                                    RowMap map, float* __restrict__ logprobs, int lp_ld,
+                                                                    int lp_col, int* __restrict__ scored) {
+    const int crow = blockIdx.x, tid = threadIdx.x;
+    if (map.n && crow >= *map.n) return;
+    const int row = map.live ? map.live[crow] : crow;
+    const bool mask_eos = min_len > 0 && t + 1 < min_len;
+    const float* x = logits + (size_t)crow * ld;
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    greedy_row_argmax(x, V, eos, mask_eos, tid, sv, si);
+    const float zmax = sv[0];
+    const int imax = si[0];
+    const bool open = finished[row] == 0;                // uniform over the block; thread 0 writes it only after the barrier below
+    __syncthreads();                                     // sv[] is reused for the sums
+    float total = 0.f;
+    if (open) {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int V4 = V >> 2;
+        for (int c0 = tid; c0 < V4; c0 += 1024) {
+            float4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int c = c0 + u * 256;
+                v[u] = c < V4 ? *(const float4*)(x + 4 * c) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int i = 4 * (c0 + u * 256);
+                // the selected index is left out, and so is a masked EOS (exp(-inf) = 0); component-wise as above
+                const int skip = mask_eos ? eos : -1;
+                acc.x += (i == imax || i == skip) ? 0.f : expf(v[u].x - zmax);
+                acc.y += (i + 1 == imax || i + 1 == skip) ? 0.f : expf(v[u].y - zmax);
+                acc.z += (i + 2 == imax || i + 2 == skip) ? 0.f : expf(v[u].z - zmax);
+                acc.w += (i + 3 == imax || i + 3 == skip) ? 0.f : expf(v[u].w - zmax);
+            }
+        }
+        float tail = 0.f;
+        for (int i = (V4 << 2) + tid; i < V; i += 256)
+            tail += (i == imax || (mask_eos && i == eos)) ? 0.f : expf(x[i] - zmax);
+        sv[tid] = ((acc.x + acc.y) + (acc.z + acc.w)) + tail;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (tid < o) sv[tid] += sv[tid + o];
+            __syncthreads();
+        }
+        total = sv[0];
+    }
     if (tid == 0) {
-        int fin = finished[row];
-        int tok = fin ? pad : si[0];
-        if (!fin && force_eos && t + 2 >= max_len) tok = eos;
-        seq[(size_t)row * seq_ld + t + 1] = tok;
-        if (!fin) {
-            if (tok == eos || t + 2 >= max_len) { finished[row] = 1; out_len[row] = t + 2; }
-            // the reference's CoCa loop also stops a row whose newest token IS the pad id (coca_model.py:305: `mask =
-            // last == eos | last == pad`; pad id 0 is an ordinary vocabulary entry there): it emits pad from then on and
-            // gets no EOS.  The row's length then excludes that pad.
-            else if (force_eos && tok == pad) { finished[row] = 1; out_len[row] = t + 1; }
+        if (greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos)) {
+            logprobs[(size_t)row * lp_ld + lp_col] = -log1pf(total);
+            scored[row] += 1;
         }
     }
 }
@@ -634,9 +715,16 @@ int launch_embed(int dtype, const int* seq, int seq_ld, int t, const float* word
 }
 
 int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos,
-                         int pad, int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map) {
-    hipLaunchKernelGGL(greedy_select_kernel, dim3(R), dim3(256), 0, s, logits, ld, V, seq, seq_ld, t, max_len, eos, pad,
-                       finished, out_len, min_len, force_eos, map);
+                         int pad, int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
+                         float* logprobs, int lp_ld, int lp_col, int* scored) {
+    if (logprobs) {
+        if (!scored || lp_col < 0 || lp_col >= lp_ld) { cap_set_error("greedy_select: log-prob column %d outside [0, %d) or no step counter", lp_col, lp_ld); return -1; }
+        hipLaunchKernelGGL(greedy_select_logprob_kernel, dim3(R), dim3(256), 0, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
+                           pad, finished, out_len, min_len, force_eos, map, logprobs, lp_ld, lp_col, scored);
+    } else {
+        hipLaunchKernelGGL(greedy_select_kernel, dim3(R), dim3(256), 0, s, logits, ld, V, seq, seq_ld, t, max_len, eos, pad,
+                           finished, out_len, min_len, force_eos, map);
+    }
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -51,7 +51,10 @@ int launch_embed(int dtype, const int* seq, int seq_ld, int t, const float* word
 // greedy selection: argmax (lowest index wins ties), pad after EOS, append at seq[row][t+1], track finished/len
 int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos,
                          int pad, int* finished, int* out_len, int R, hipStream_t s, int min_len = 0, int force_eos = 0,
-                         RowMap map = RowMap());            // logits row c belongs to row map.live[c] (seq / finished / out_len)
+                         RowMap map = RowMap(),             // logits row c belongs to row map.live[c] (seq / finished / out_len)
+                         // scoring form (launched only when logprobs is given): logprobs[row*lp_ld + lp_col] = log max softmax of
+                         // the row as selected from (EOS mask applied), scored[row] += 1, for the rows open at this step
+                         float* logprobs = nullptr, int lp_ld = 0, int lp_col = 0, int* scored = nullptr);
 // live[] = the rows with finished[r] == 0 in ascending order, *n_live = their count (one workgroup; stable)
 int launch_compact_rows(const int* finished, int R, int* live, int* n_live, hipStream_t s);
 int launch_fill_i32(int* p, int v, size_t n, hipStream_t s);

@@ -30,6 +30,22 @@ def _stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def perplexity_from_logprobs(token_logprobs: torch.Tensor, scored_steps: torch.Tensor) -> torch.Tensor:
+    """Per-caption perplexity, float64 [B], from `generate(..., output_logprobs=True)`: exp(-sum_{j < scored} lp_j / scored) -
+    the reference's `compute_perplexity` (captioning_predictor.py:34-47: exp(-sum_t log max softmax(logits_t) / T)) with the
+    per-step term taken on the device.  token_logprobs [B, steps], scored_steps int [B]; entries from `scored` on (zeros after a
+    caption's end) do not enter.  Host arithmetic in float64; a caption with no scored step gives nan."""
+    lp = torch.as_tensor(token_logprobs).detach().cpu().to(torch.float64)
+    n = torch.as_tensor(scored_steps).detach().cpu().to(torch.int64)
+    if lp.dim() != 2 or n.shape != (lp.shape[0],):
+        raise ValueError(f"token_logprobs must be [B, steps] and scored_steps [B], got {tuple(lp.shape)} / {tuple(n.shape)}")
+    if lp.shape[0] and (int(n.min()) < 0 or int(n.max()) > lp.shape[1]):
+        raise ValueError(f"scored_steps must be within 0..{lp.shape[1]}")
+    keep = torch.arange(lp.shape[1])[None, :] < n[:, None]
+    total = torch.where(keep, lp, torch.zeros_like(lp)).sum(dim=1)
+    return torch.exp(-total / n.to(torch.float64))
+
+
 class CaptionerEngine:
     """One handle = one model replica on one GPU, bound to torch's current stream of `device` at each call."""
 
@@ -255,11 +271,15 @@ class CaptionerEngine:
 
     def generate(self, pixels: torch.Tensor, num_beams: int = 1, max_length: Optional[int] = None,
                  length_penalty: float = 1.0, output_logits: bool = False, num_beam_groups: Optional[int] = None,
-                 **sampling_options) -> Dict[str, torch.Tensor]:
+                 output_logprobs: bool = False, **sampling_options) -> Dict[str, torch.Tensor]:
         """Returns device tensors: sequences int32 [B, max_length] (incl. BOS), lengths int32 [B],
         sequences_scores fp32 [B] (beams only), logits fp32 [max_length-1, B*num_beams, vocab] (optional).
         BLIP-2: max_length counts NEW tokens (HF max_new_tokens); sequences are those new tokens only (no image
         placeholders / BOS), logits [max_length, B, vocab].
+        output_logprobs (greedy): token_logprobs fp32 [B, steps] = log max softmax of every step's logits row as the selection saw
+        it (steps as for logits), zero from the caption's end on, and scored_steps int32 [B] = valid entries per row - taken by the
+        selection kernel itself (cap_generate_scored): any batch size, no logits buffer, same kernels otherwise;
+        `perplexity_from_logprobs` turns them into the reference's per-caption perplexity.
         num_beam_groups (CoCa): the reference's `_generate_beamsearch` with that many beam groups (coca_model.py:335-482;
         its `generate()` defaults are 6 beams in 3 groups) - cap_generate_groups; no per-step logits in that mode.
         sampling_options: anything else a caller of the reference's / HF's `generate` may pass (top_p, top_k, temperature,
@@ -283,6 +303,15 @@ class CaptionerEngine:
             # zeros, not empty: with early exit the steps after the last executed one are never written (callers see 0, not
             # stale memory); `last_decode_steps` tells how many steps ran
             logits = torch.zeros((steps, B * num_beams, self.arch.vocab), dtype=torch.float32, device=self.device)
+        lps = scored = None
+        if output_logprobs:
+            if num_beam_groups is not None:
+                raise N.CaptionerHipError("output_logprobs is the greedy loop's (num_beams = 1): the group beam search "
+                                          f"(num_beams = {num_beams}, num_beam_groups = {num_beam_groups}) returns sequences_scores")
+            steps = L if getattr(self, "is_blip2", False) else L - 1
+            # the library zero-fills both on this stream (entries after a caption's end and steps an early exit skipped stay 0)
+            lps = torch.empty((B, steps), dtype=torch.float32, device=self.device)
+            scored = torch.empty((B,), dtype=torch.int32, device=self.device)
         if num_beam_groups is not None:
             if output_logits:
                 raise ValueError("per-step logits are not recorded by the group beam search")
@@ -292,12 +321,22 @@ class CaptionerEngine:
                                                      C.c_void_p(scores.data_ptr()), C.c_void_p(_stream_ptr(self.device))), "cap_generate_groups")
             return {"sequences": ids, "lengths": lens, "sequences_scores": scores}
         with torch.cuda.device(self.device):
-            N.check(self.lib.cap_generate(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, num_beams, L,
-                                          C.c_float(length_penalty), C.c_void_p(ids.data_ptr()),
-                                          C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
-                                          C.c_void_p(logits.data_ptr() if logits is not None else 0),
-                                          C.c_void_p(_stream_ptr(self.device))), "cap_generate")
+            if lps is not None:
+                N.check(self.lib.cap_generate_scored(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, num_beams, L,
+                                                     C.c_float(length_penalty), C.c_void_p(ids.data_ptr()),
+                                                     C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
+                                                     C.c_void_p(logits.data_ptr() if logits is not None else 0),
+                                                     C.c_void_p(lps.data_ptr()), C.c_void_p(scored.data_ptr()),
+                                                     C.c_void_p(_stream_ptr(self.device))), "cap_generate_scored")
+            else:
+                N.check(self.lib.cap_generate(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, num_beams, L,
+                                              C.c_float(length_penalty), C.c_void_p(ids.data_ptr()),
+                                              C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
+                                              C.c_void_p(logits.data_ptr() if logits is not None else 0),
+                                              C.c_void_p(_stream_ptr(self.device))), "cap_generate")
         out = {"sequences": ids, "lengths": lens}
+        if lps is not None:
+            out["token_logprobs"], out["scored_steps"] = lps, scored
         if num_beams > 1:
             out["sequences_scores"] = scores
         if logits is not None:
@@ -398,7 +437,7 @@ class EnginePool:
             cur.wait_stream(s)
 
     # outputs of `generate` whose leading dimension is the batch's rows (what a merged pass is split back by)
-    _PER_ROW_OUTPUTS = ("sequences", "lengths", "sequences_scores")
+    _PER_ROW_OUTPUTS = ("sequences", "lengths", "sequences_scores", "token_logprobs", "scored_steps")
 
     @staticmethod
     def coalesce_plan(rows: Sequence[int], n_engines: int, max_rows: int) -> List[List[int]]:
@@ -430,6 +469,22 @@ class EnginePool:
         plan.append(cur)
         return plan
 
+    @classmethod
+    def split_merged_outputs(cls, plan: Sequence[Sequence[int]], rows: Sequence[int], outs_m: Sequence[dict]) -> list:
+        """The outputs of the merged passes of `plan` (one dict per pass, every value with the pass's rows leading) cut back into one
+        dict per original batch; rows[j] = rows of batch j."""
+        outs: list = [None] * len(rows)
+        for g, om in zip(plan, outs_m):
+            unknown = sorted(set(om) - set(cls._PER_ROW_OUTPUTS))
+            if unknown:              # a new output key must say here whether it is per row - never guessed from its shape
+                raise N.CaptionerHipError(f"generate_many(coalesce_rows=): output(s) {unknown} are not in the list of per-row "
+                                          f"outputs {cls._PER_ROW_OUTPUTS}; cannot split a merged pass")
+            r0 = 0
+            for j in g:
+                outs[j] = {k: v[r0:r0 + rows[j]] for k, v in om.items()}
+                r0 += rows[j]
+        return outs
+
     def generate_many(self, batches, threads: bool = False, coalesce_rows: int = 0, **generate_kw):
         """All batches, in order.  threads=True: one host thread per engine (batch j goes to engine j % n) - needed when
         the engines poll for early exit (cap_set_early_exit synchronises its stream: from a single host thread that would
@@ -454,18 +509,7 @@ class EnginePool:
                     merged = [batches[g[0]] if len(g) == 1 else torch.cat([batches[j] for j in g], dim=0) for g in plan]
                     outs_m = self.generate_many(merged, threads=threads, **generate_kw)
                     self.last_coalesce = plan            # (the inner call cleared it)
-                    outs: list = [None] * len(batches)
-                    for g, om in zip(plan, outs_m):
-                        unknown = sorted(set(om) - set(self._PER_ROW_OUTPUTS))
-                        if unknown:              # a new output key must say here whether it is per row - never guessed from its shape
-                            raise N.CaptionerHipError(f"generate_many(coalesce_rows=): output(s) {unknown} are not in the list of per-row "
-                                                      f"outputs {self._PER_ROW_OUTPUTS}; cannot split a merged pass")
-                        r0 = 0
-                        for j in g:
-                            n_j = int(batches[j].shape[0])
-                            outs[j] = {k: v[r0:r0 + n_j] for k, v in om.items()}
-                            r0 += n_j
-                    return outs
+                    return self.split_merged_outputs(plan, [int(b.shape[0]) for b in batches], outs_m)
                 self.last_coalesce = f"not applied: {len(batches)} batches on {len(self.engines)} engines leave nothing to merge within {cap_rows} rows"
             logger.debug("generate_many(coalesce_rows=%d) %s", coalesce_rows, self.last_coalesce)
         if not threads or len(self.engines) == 1 or len(batches) <= 1:

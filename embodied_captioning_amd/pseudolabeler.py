@@ -55,11 +55,16 @@ def save_record(output_path: str, info: str, instances, image) -> str:
 class BatchedBoxCaptioner:
     """`captioner` is the plugin (`Captioner` with `caption_batch`) or any callable list[PIL] -> list[str];
     `encoder` (optional): an object with `encode(list[str], convert_to_tensor=True)` (SentenceEncoder, or the reference's
-    SentenceTransformer) - called once for the whole batch - or a plain callable caption -> vector."""
+    SentenceTransformer) - called once for the whole batch - or a plain callable caption -> vector.
+    with_perplexity: every frame's result also carries "perplexities" (float64 [n], box order; the reference's per-caption
+    `compute_perplexity()`), from `captioner.caption_batch(crops, return_perplexity=True)`."""
 
     def __init__(self, captioner, encoder: Optional[Callable[[str], torch.Tensor]] = None, expand_factor: float = 0.2,
-                 device_resize: Optional[bool] = None):
+                 device_resize: Optional[bool] = None, with_perplexity: bool = False):
         self.captioner = captioner
+        self.with_perplexity = bool(with_perplexity)
+        if self.with_perplexity and getattr(captioner, "caption_batch", None) is None:
+            raise ValueError("with_perplexity needs a captioner with caption_batch(crops, return_perplexity=True)")
         self.encoder = encoder
         self.expand_factor = expand_factor
         # Crop + bicubic resize on the device (bit-exact with the PIL path, preprocess.crop_resize_u8) when the captioner's
@@ -75,11 +80,15 @@ class BatchedBoxCaptioner:
         self.device_resize = can if device_resize is None else bool(device_resize)
         self._size = int(size) if size is not None else None
 
-    def _caption(self, crops) -> List[str]:
+    def _caption(self, crops):
+        """-> (captions, perplexities or None)"""
         if len(crops) == 0:
-            return []
+            return [], (torch.zeros(0, dtype=torch.float64) if self.with_perplexity else None)
         fn = getattr(self.captioner, "caption_batch", None)
-        return list(fn(crops)) if fn is not None else list(self.captioner(crops))
+        if self.with_perplexity:
+            texts, ppl = fn(crops, return_perplexity=True)
+            return list(texts), torch.as_tensor(ppl, dtype=torch.float64)
+        return (list(fn(crops)) if fn is not None else list(self.captioner(crops))), None
 
     def predict_captions(self, boxes_per_frame: Sequence[Sequence], frames_bgr: Sequence[np.ndarray]):
         """One captioner call for the whole dataloader batch.  Returns per frame
@@ -92,8 +101,8 @@ class BatchedBoxCaptioner:
             from .preprocess import crop_resize_u8_frames
             rects = [[expand_box(b, self.expand_factor, img.shape) for b in boxes] for boxes, img in zip(boxes_per_frame, frames_bgr)]
             if any(r[2] <= r[0] or r[3] <= r[1] for rs in rects for r in rs):      # an empty rectangle somewhere: the PIL path (raises as the reference)
-                return BatchedBoxCaptioner(self.captioner, self.encoder, self.expand_factor, device_resize=False) \
-                    .predict_captions(boxes_per_frame, frames_bgr)
+                return BatchedBoxCaptioner(self.captioner, self.encoder, self.expand_factor, device_resize=False,
+                                           with_perplexity=self.with_perplexity).predict_captions(boxes_per_frame, frames_bgr)
             dev = getattr(self.captioner, "crop_device", None) or getattr(self.captioner, "device", "cuda:0")
             for fi, rs in enumerate(rects):
                 owner += [fi] * len(rs)
@@ -105,10 +114,14 @@ class BatchedBoxCaptioner:
                     continue
                 crops.extend(crop_boxes(img, boxes, self.expand_factor))
                 owner += [fi] * len(boxes)
-        captions = self._caption(crops)
+        captions, ppl = self._caption(crops)
         out = [{"captions": [], "embeddings": torch.tensor([])} for _ in frames_bgr]
         for fi, cap in zip(owner, captions):
             out[fi]["captions"].append(cap)
+        if ppl is not None:
+            own = torch.as_tensor(owner, dtype=torch.int64)
+            for fi in range(len(out)):
+                out[fi]["perplexities"] = ppl[own == fi]
         if self.encoder is not None and captions:
             enc = getattr(self.encoder, "encode", None)
             if enc is not None:                         # SentenceEncoder / SentenceTransformer: one batched call

@@ -47,8 +47,12 @@ class Captioner(_Base):
         caption = out["text"]
         return caption
 
-    def caption_batch(self, images):
-        """Batched extension: list of PIL images / uint8 tensor -> list of captions."""
+    def caption_batch(self, images, return_perplexity: bool = False):
+        """Batched extension: list of PIL images / uint8 tensor -> list of captions; return_perplexity: -> (captions, float64 [n]
+        perplexities), the number the reference gets from `compute_perplexity()` after every one-crop call."""
+        if return_perplexity:
+            out = self.model.generate_batch(images, output_perplexity=True)
+            return out["texts"], out["perplexities"]
         return self.model.generate_batch(images)["texts"]
 
     @property

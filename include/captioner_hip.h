@@ -216,6 +216,21 @@ int cap_generate(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_
                  float length_penalty, int32_t* out_ids, int32_t* out_len, float* out_scores,
                  float* out_step_logits, void* stream);
 
+/* cap_generate that also scores the captions of the greedy loop: the per-step term of the reference's `compute_perplexity`
+ * (captioning_predictor.py:34-47), taken by the token selection kernel from the logits row it reads anyway - no per-step logits
+ * buffer, any batch size, row compaction and the decode path chosen as for cap_generate.
+ *   out_logprobs fp32 [B, steps]  log max softmax of the step's logits row as the selection saw it (CoCa: EOS at -inf while the
+ *                caption is shorter than min_len), for every step at which the caption was open; 0 after its end and for steps
+ *                an early exit never ran.  steps = max_len - 1 (BLIP, CoCa) or max_len (BLIP-2).  It is the log of the MAXIMAL
+ *                probability, not of the emitted token (they differ on CoCa's forced-EOS last step), as the reference defines it.
+ *   out_scored   int32 [B]        steps at which the caption was open = valid entries of its out_logprobs row
+ *                perplexity = exp(-sum_{j < scored} logprobs[j] / scored)
+ * Both buffers are zero-filled by the call on `stream`; both NULL = cap_generate.  num_beams must be 1 when they are given
+ * (beam search returns out_scores).  Nothing is allocated or synchronised. */
+int cap_generate_scored(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int max_len,
+                        float length_penalty, int32_t* out_ids, int32_t* out_len, float* out_scores,
+                        float* out_step_logits, float* out_logprobs, int32_t* out_scored, void* stream);
+
 /* CoCa's `_generate_beamsearch` with beam GROUPS (reference coca_model.py:335-482; `generate()` defaults num_beams = 6,
  * num_beam_groups = 3, :218-219): num_beams % num_beam_groups == 0, each group a beam search of num_beams / num_beam_groups
  * beams, the best hypothesis over an image's groups returned.  The reference attaches no diversity processor (:236-241), so
@@ -385,6 +400,15 @@ int cap_op_gemm_crosskv(int dtype, const void* A, const void* W, const float* bi
  * MinLength).  Synchronises the stream. */
 int cap_op_beam_candidates(const float* logits, int ld, int V, int B, int K, int legacy_raw, int masked_id, float* out_val,
                            int32_t* out_idx, void* stream);
+/* One step of the greedy token selection alone.  logits fp32 [R][ld] (ld % 4 == 0) are the rows of the launch; row c belongs to
+ * caption live[c] when a map is given (live int32 [R], n_live int32: rows from *n_live on are skipped), else to caption c.  Per
+ * caption (all device, caller-initialised, updated in place): seq int32 [., max_len] receives the token at column t + 1,
+ * finished int32 [.], lengths int32 [.].  min_len > 0 masks EOS while t + 1 < min_len; force_eos: CoCa's loop (EOS at the last
+ * position, a pad token ends the row).  logprobs fp32 [., lp_ld] (column t) and scored int32 [.] given: the scoring kernel of
+ * cap_generate_scored runs (open captions only: the others keep what the caller put there); both NULL: cap_generate's kernel. */
+int cap_op_select_logprob(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int min_len, int force_eos,
+                          int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths,
+                          float* logprobs, int lp_ld, int32_t* scored, void* stream);
 int cap_op_convert(int dtype, const float* src, void* dst, size_t n, void* stream);
 /* Weight upload as cap_load_weight does it: dst [rows, cols] in the GEMM-operand type of `dtype` (CAP_F32_SPLIT: G8 halves of
  * 4096 * w - the split GEMM's epilogue divides by 4096; a G8 buffer is 4 bytes per element, cols % 8 == 0). */
