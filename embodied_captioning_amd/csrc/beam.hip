@@ -541,6 +541,9 @@ const int* beam_active_flag_p(void* state, int B, int K, int max_len) {
 const int* beam_running_tokens_p(void* state, int B, int K, int max_len, int parity) {
     return (const int*)((char*)state + beam_layout(B, K, max_len).run_seq[parity]);
 }
+const float* beam_running_scores_p(void* state, int B, int K, int max_len, int parity) {
+    return (const float*)((char*)state + beam_layout(B, K, max_len).run_score[parity]);
+}
 
 // test hook (cap_op_beam_candidates): the candidate selection alone on a freshly initialised state (running scores 0 for beam
 // 0, -1e9 for the others); the lists land in out_val / out_idx [B*K][2K], best first

@@ -2589,6 +2589,57 @@ int cap_op_beam_candidates(const float* logits, int ld, int V, int B, int K, int
     (void)hipFree(st);
     return rc;
 }
+// The beam search alone over a caller-owned state block (tests/test_beam_search_gpu.py): thin wrappers of the launchers the
+// generate paths use.  One argument check for all of them; `what` names the entry in the message.
+static int beam_op_args(const char* what, const void* state, int B, int K, int max_len) {
+    if (!state) { cap_set_error("%s: state is null", what); return -1; }
+    if (K < 1 || K > 8) { cap_set_error("%s: K = %d beams (1 <= K <= 8)", what, K); return -1; }
+    if (B < 1 || max_len < 2) { cap_set_error("%s: B = %d, max_len = %d (B >= 1, max_len >= 2)", what, B, max_len); return -1; }
+    return 0;
+}
+size_t cap_op_beam_state_bytes(int B, int K, int max_len) {
+    if (K < 1 || K > 8) { cap_set_error("cap_op_beam_state_bytes: K = %d beams (1 <= K <= 8)", K); return 0; }
+    if (B < 1 || max_len < 2) { cap_set_error("cap_op_beam_state_bytes: B = %d, max_len = %d (B >= 1, max_len >= 2)", B, max_len); return 0; }
+    return beam_state_bytes(B, K, max_len);
+}
+int cap_op_beam_init(void* state, int B, int K, int max_len, int bos, int pad, int eos, int mode, void* stream) {
+    TRY(beam_op_args("cap_op_beam_init", state, B, K, max_len));
+    if (mode != BEAM_HF_V5 && mode != BEAM_LEGACY_RAW) { cap_set_error("cap_op_beam_init: mode = %d (0: HF v5, 1: legacy raw)", mode); return -1; }
+    return launch_beam_init(state, B, K, max_len, bos, pad, eos, (hipStream_t)stream, mode);
+}
+int cap_op_beam_step(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
+                     float length_penalty, int32_t* anc, int anc_ld, int mode, int min_len, void* stream) {
+    TRY(beam_op_args("cap_op_beam_step", state, B, K, max_len));
+    if (!logits) { cap_set_error("cap_op_beam_step: logits is null"); return -1; }
+    if (V < 1 || ld < V) { cap_set_error("cap_op_beam_step: ld = %d, V = %d (ld >= V >= 1)", ld, V); return -1; }
+    // cur_len is the position the step writes (the running sequences hold cur_len tokens, BOS included): step t = cur_len - 1
+    if (cur_len - 1 < 0 || cur_len - 1 >= max_len - 1) {
+        cap_set_error("cap_op_beam_step: cur_len = %d (step cur_len - 1 must satisfy 0 <= step < max_len - 1 = %d)", cur_len, max_len - 1);
+        return -1;
+    }
+    if (anc && anc_ld < 1) { cap_set_error("cap_op_beam_step: anc_ld = %d with an ancestry table (anc_ld >= 1)", anc_ld); return -1; }
+    if (mode != BEAM_HF_V5 && mode != BEAM_LEGACY_RAW) { cap_set_error("cap_op_beam_step: mode = %d (0: HF v5, 1: legacy raw)", mode); return -1; }
+    return launch_beam_step(state, logits, ld, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, (hipStream_t)stream, mode,
+                            min_len);
+}
+int cap_op_beam_finalize(void* state, int B, int K, int max_len, int32_t* out_ids, int32_t* out_len, float* out_scores, void* stream) {
+    TRY(beam_op_args("cap_op_beam_finalize", state, B, K, max_len));
+    if (!out_ids) { cap_set_error("cap_op_beam_finalize: out_ids is null"); return -1; }
+    return launch_beam_finalize(state, B, K, max_len, out_ids, out_len, out_scores, (hipStream_t)stream);
+}
+int cap_op_beam_peek(void* state, int B, int K, int max_len, int parity, int32_t* run_tokens, float* run_scores, int32_t* active,
+                     void* stream) {
+    TRY(beam_op_args("cap_op_beam_peek", state, B, K, max_len));
+    if (!run_tokens || !run_scores || !active) { cap_set_error("cap_op_beam_peek: an output pointer is null"); return -1; }
+    if (parity != 0 && parity != 1) { cap_set_error("cap_op_beam_peek: parity = %d (0 or 1)", parity); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    CAP_HIP_CHECK(hipMemcpyAsync(run_tokens, beam_running_tokens_p(state, B, K, max_len, parity), (size_t)B * K * max_len * 4,
+                                 hipMemcpyDeviceToDevice, s));
+    CAP_HIP_CHECK(hipMemcpyAsync(run_scores, beam_running_scores_p(state, B, K, max_len, parity), (size_t)B * K * 4,
+                                 hipMemcpyDeviceToDevice, s));
+    CAP_HIP_CHECK(hipMemcpyAsync(active, beam_active_flag_p(state, B, K, max_len), 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
 int cap_op_select_logprob(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int min_len, int force_eos,
                           int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths,
                           float* logprobs, int lp_ld, int32_t* scored, void* stream) {

@@ -191,3 +191,5 @@ int launch_beam_finalize(void* state, int B, int K, int max_len, int* out_ids, i
 const int* beam_active_flag_p(void* state, int B, int K, int max_len);
 // device pointer: int32 [B*K, max_len] running sequences of the given parity (= cur_len & 1)
 const int* beam_running_tokens_p(void* state, int B, int K, int max_len, int parity);
+// device pointer: fp32 [B*K] running scores of the given parity
+const float* beam_running_scores_p(void* state, int B, int K, int max_len, int parity);

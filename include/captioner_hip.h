@@ -400,6 +400,23 @@ int cap_op_gemm_crosskv(int dtype, const void* A, const void* W, const float* bi
  * MinLength).  Synchronises the stream. */
 int cap_op_beam_candidates(const float* logits, int ld, int V, int B, int K, int legacy_raw, int masked_id, float* out_val,
                            int32_t* out_idx, void* stream);
+/* The beam search alone, step by step, over a caller-owned device block of cap_op_beam_state_bytes(B, K, max_len) bytes (0 and
+ * an error for sizes outside 1 <= K <= 8, B >= 1, max_len >= 2): the launchers cap_generate runs, for the kernel tests.
+ * mode 0: HF v5 scoring and stopping, 1: the legacy CoCa scorer (raw logits, min_len masks EOS while cur_len < min_len).
+ * init: every item starts as [bos].  step: logits fp32 [B*K][ld] (ld >= V) are the rows of the running beams; cur_len is the
+ * number of tokens they hold (BOS included) = the position this step writes, 1 <= cur_len <= max_len - 1, i.e. step
+ * cur_len - 1 in [0, max_len - 1); anc int32 [2][B*K][anc_ld] (may be NULL) is the ancestry table, plane cur_len & 1 read,
+ * the other written (columns <= cur_len, < anc_ld).  A step issued after the loop's flag has dropped changes nothing.
+ * finalize: best hypothesis per item -> out_ids int32 [B][max_len], out_len int32 [B], out_scores fp32 [B] (the last two may
+ * be NULL).  peek: running sequences int32 [B*K][max_len] and scores fp32 [B*K] of the given parity (after a step at cur_len:
+ * (cur_len + 1) & 1) and the loop-still-running flag (int32 [1]), all device buffers.  Nothing synchronises. */
+size_t cap_op_beam_state_bytes(int B, int K, int max_len);
+int cap_op_beam_init(void* state, int B, int K, int max_len, int bos, int pad, int eos, int mode, void* stream);
+int cap_op_beam_step(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
+                     float length_penalty, int32_t* anc, int anc_ld, int mode, int min_len, void* stream);
+int cap_op_beam_finalize(void* state, int B, int K, int max_len, int32_t* out_ids, int32_t* out_len, float* out_scores, void* stream);
+int cap_op_beam_peek(void* state, int B, int K, int max_len, int parity, int32_t* run_tokens, float* run_scores, int32_t* active,
+                     void* stream);
 /* One step of the greedy token selection alone.  logits fp32 [R][ld] (ld % 4 == 0) are the rows of the launch; row c belongs to
  * caption live[c] when a map is given (live int32 [R], n_live int32: rows from *n_live on are skipped), else to caption c.  Per
  * caption (all device, caller-initialised, updated in place): seq int32 [., max_len] receives the token at column t + 1,
