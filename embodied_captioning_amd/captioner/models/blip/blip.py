@@ -152,13 +152,18 @@ class BLIP(CaptioningPredictor):
 
     # ------------------------------------------------------------------------------------------ forward
     @torch.no_grad()
-    def generate_batch(self, images, output_logits: bool = False, output_perplexity: bool = False) -> dict:
+    def generate_batch(self, images, output_logits: bool = False, output_perplexity: bool = False,
+                       output_vocab_maxprob: bool = False) -> dict:
         """Batched extension: any number of frames -> {"texts": [str], "sequences": int32 [N, L], "lengths", "scores"}.
         output_perplexity (greedy): adds "perplexities" float64 [N] - what `forward` + `compute_perplexity()` give one crop at a
         time - and "token_logprobs" fp32 [N, steps] / "scored_steps" int32 [N] they are computed from (engine.generate,
-        output_logprobs); the pool, its dynamic batching and the preprocessing overlap work as without it."""
+        output_logprobs); the pool, its dynamic batching and the preprocessing overlap work as without it.
+        output_vocab_maxprob (greedy): adds "vocab_maxprob" fp32 [N, vocab] ON THE DEVICE (engine.generate, output_vocab_maxprob -
+        the input of `engine.fuse_vocab_groups`) with "token_logprobs" / "scored_steps" on the host; wired as output_perplexity."""
         texts: List[str] = []
         kw = {"output_logprobs": True} if output_perplexity else {}
+        if output_vocab_maxprob:
+            kw["output_vocab_maxprob"] = True
         seqs, lens, scores, logits = [], [], [], []
         pool = getattr(self, "pool", None)
         # a long list of PIL crops on a pool: in rounds of one pass per engine, the next round's crops are preprocessed (host
@@ -208,6 +213,11 @@ class BLIP(CaptioningPredictor):
             res["token_logprobs"] = torch.cat([o["token_logprobs"] for o in outs]).cpu()
             res["scored_steps"] = torch.cat([o["scored_steps"] for o in outs]).cpu()
             res["perplexities"] = perplexity_from_logprobs(res["token_logprobs"], res["scored_steps"])
+        if output_vocab_maxprob:
+            res["vocab_maxprob"] = torch.cat([o["vocab_maxprob"] for o in outs])
+            if not output_perplexity:
+                res["token_logprobs"] = torch.cat([o["token_logprobs"] for o in outs]).cpu()
+                res["scored_steps"] = torch.cat([o["scored_steps"] for o in outs]).cpu()
         return res
 
     @torch.no_grad()

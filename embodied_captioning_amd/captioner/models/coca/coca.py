@@ -192,12 +192,16 @@ class CoCa(CaptioningPredictor):
         return out["sequences"]
 
     @torch.no_grad()
-    def generate_batch(self, images, output_perplexity: bool = False) -> dict:
+    def generate_batch(self, images, output_perplexity: bool = False, output_vocab_maxprob: bool = False) -> dict:
         """output_perplexity (the greedy top-k(1) loop): adds "perplexities" float64 [N] - `forward` + `compute_perplexity()` one crop
-        at a time - with the "token_logprobs" / "scored_steps" behind them (engine.generate, output_logprobs)."""
+        at a time - with the "token_logprobs" / "scored_steps" behind them (engine.generate, output_logprobs).
+        output_vocab_maxprob (the same loop): adds "vocab_maxprob" fp32 [N, vocab] ON THE DEVICE (engine.generate,
+        output_vocab_maxprob - the input of `engine.fuse_vocab_groups`) with "token_logprobs" / "scored_steps" on the host."""
         kw = dict(num_beams=self.num_beams, max_length=self.arch.seq_len, num_beam_groups=self.num_beam_groups)
         if output_perplexity:
             kw["output_logprobs"] = True
+        if output_vocab_maxprob:
+            kw["output_vocab_maxprob"] = True
         rnd = len(self.pool) * max(self.batch_size, self.coalesce_rows) if self.pool is not None else 0
         if self.pool is not None and isinstance(images, (list, tuple)) and len(images) > rnd:
             # a long list of PIL crops: in rounds of one pass per engine, the next round preprocessed by a helper thread meanwhile
@@ -229,6 +233,11 @@ class CoCa(CaptioningPredictor):
             res["token_logprobs"] = torch.cat([o["token_logprobs"] for o in outs]).cpu()
             res["scored_steps"] = torch.cat([o["scored_steps"] for o in outs]).cpu()
             res["perplexities"] = perplexity_from_logprobs(res["token_logprobs"], res["scored_steps"])
+        if output_vocab_maxprob:
+            res["vocab_maxprob"] = torch.cat([o["vocab_maxprob"] for o in outs])
+            if not output_perplexity:
+                res["token_logprobs"] = torch.cat([o["token_logprobs"] for o in outs]).cpu()
+                res["scored_steps"] = torch.cat([o["scored_steps"] for o in outs]).cpu()
         return res
 
     @torch.no_grad()

@@ -1075,13 +1075,15 @@ int run_opt_step(Captioner* m, int B, int past, hipStream_t s) {
 // HF Blip2ForConditionalGeneration.generate, greedy: out_ids [B, max_len] = the new tokens (pad after EOS), out_len [B] =
 // their count incl. EOS, out_step_logits [max_len, B, vocab]; out_lp [B, max_len] / out_scored [B]: cap_generate_scored.
 int run_generate_blip2(Captioner* m, const void* pixels, int fmt, int B, int max_len, int32_t* out_ids, int32_t* out_len,
-                       float* out_step_logits, float* out_lp, int32_t* out_scored, hipStream_t s) {
+                       float* out_step_logits, float* out_lp, int32_t* out_scored, hipStream_t s, float* out_vocab = nullptr,
+                       int acc_ld = 0) {
     const CapConfig& c = m->c;
     const int T = c.t_hidden, nq = c.num_query_tokens, P = nq + 1, Lmax = P + c.max_len;
     if (out_lp) {
         TRY(launch_fill_f32(out_lp, 0.f, (size_t)B * max_len, s));
         TRY(launch_fill_i32(out_scored, 0, (size_t)B, s));
     }
+    if (out_vocab) TRY(launch_fill_f32(out_vocab, 0.f, (size_t)B * acc_ld, s));
     TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
     TRY(run_qformer(m, B, s));
     TRY(gemm(m, s, "b2_gemm_lproj", m->qx_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1));
@@ -1098,7 +1100,7 @@ int run_generate_blip2(Captioner* m, const void* pixels, int fmt, int B, int max
         }
         // token of position P + t; a row finishes on EOS or at P + max_len tokens (greedy_select's `t` is the last filled index)
         TRY(launch_greedy_select(m->logits, m->ldl, c.vocab, m->seq, Lmax, P - 1 + t, P + max_len, c.eos, c.pad, m->finished, m->lens, B, s, 0, 0,
-                                 RowMap(), out_lp, max_len, t, out_scored));
+                                 RowMap(), out_lp, max_len, t, out_scored, out_vocab, acc_ld));
         if (t + 1 == max_len) break;
         {
             bool done;
@@ -1815,11 +1817,12 @@ static int run_image_side(Captioner* m, const void* pixels, int fmt, int B, hipS
 
 int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm, float lp, int32_t* out_ids,
                  int32_t* out_len, float* out_scores, float* out_step_logits, hipStream_t s, bool force_beam = false,
-                 float* out_lp = nullptr, int32_t* out_scored = nullptr) {
+                 float* out_lp = nullptr, int32_t* out_scored = nullptr, float* out_vocab = nullptr, int acc_ld = 0) {
     // force_beam: K == 1 runs as a 1-beam BEAM search (the scorer's bookkeeping, no forced EOS) instead of the greedy loop -
     // what a beam group of size one is (cap_generate_groups)
     // out_lp [B, Lm - 1] / out_scored [B] (greedy only, cap_generate_scored): per-step log max softmax from the selection kernel,
     // indexed by the caption's row whatever the loop's compaction; zero-filled here, on the caller's stream
+    // out_vocab [B, acc_ld] (cap_generate_vocab; with out_lp): per-caption maximum over its steps of the step's softmax, same rules
     const CapConfig& c = m->c;
     const int R = B * K;
     const bool coca = c.arch == CAP_ARCH_COCA;
@@ -1828,6 +1831,7 @@ int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm
         TRY(launch_fill_f32(out_lp, 0.f, (size_t)R * (Lm - 1), s));
         TRY(launch_fill_i32(out_scored, 0, (size_t)R, s));
     }
+    if (out_vocab) TRY(launch_fill_f32(out_vocab, 0.f, (size_t)R * acc_ld, s));
     TRY(run_image_side(m, pixels, fmt, B, s));
     Dec d = make_slice(m, 0, B, B, K, Lm);
     // Row compaction (ops.h, RowMap): the greedy BLIP loop on the batch kernels, when nobody asked for per-step logits (their rows
@@ -1882,7 +1886,7 @@ int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm
         if (greedy)
         {
             TRY(launch_greedy_select(d.logits, m->ldl, c.vocab, d.seq, Lm, t, Lm, c.eos, c.pad, d.finished, d.lens, R, s,
-                                     coca ? c.min_len : 0, coca ? 1 : 0, d.map, out_lp, Lm - 1, t, out_scored));
+                                     coca ? c.min_len : 0, coca ? 1 : 0, d.map, out_lp, Lm - 1, t, out_scored, out_vocab, acc_ld));
             if (compact) TRY(launch_compact_rows(d.finished, R, m->live, m->n_live, s));
         }
         else
@@ -2379,6 +2383,25 @@ int cap_generate_scored(CapHandle h, const void* pixels, int pixel_fmt, int B, i
                         out_step_logits, (hipStream_t)stream, false, out_logprobs, out_scored);
 }
 
+int cap_generate_vocab(CapHandle h, const void* pixels, int pixel_fmt, int B, int max_len, int32_t* out_ids, int32_t* out_len,
+                       float* out_step_logits, float* out_logprobs, int32_t* out_scored, float* out_vocab, int acc_ld, void* stream) {
+    Captioner* m = (Captioner*)h;
+    TRY(check_call(m, B, 1, max_len, pixel_fmt));
+    if (!pixels || !out_ids) { cap_set_error("cap_generate_vocab: null buffer"); return -1; }
+    if (!out_logprobs || !out_scored || !out_vocab) {
+        cap_set_error("cap_generate_vocab: out_logprobs, out_scored and out_vocab are all required");
+        return -1;
+    }
+    if (acc_ld < m->c.vocab) { cap_set_error("cap_generate_vocab: acc_ld (%d) is below the vocabulary size (%d)", acc_ld, m->c.vocab); return -1; }
+    if (acc_ld % 4 != 0) { cap_set_error("cap_generate_vocab: acc_ld (%d) must be a multiple of 4 (16-byte rows)", acc_ld); return -1; }
+    if (((uintptr_t)out_vocab & 15) != 0) { cap_set_error("cap_generate_vocab: out_vocab must be 16-byte aligned"); return -1; }
+    if (m->c.arch == CAP_ARCH_BLIP2)
+        return run_generate_blip2(m, pixels, pixel_fmt, B, max_len, out_ids, out_len, out_step_logits, out_logprobs, out_scored,
+                                  (hipStream_t)stream, out_vocab, acc_ld);
+    return run_generate(m, pixels, pixel_fmt, B, 1, max_len, 1.0f, out_ids, out_len, nullptr, out_step_logits, (hipStream_t)stream, false,
+                        out_logprobs, out_scored, out_vocab, acc_ld);
+}
+
 int cap_generate(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int max_len, float length_penalty,
                  int32_t* out_ids, int32_t* out_len, float* out_scores, float* out_step_logits, void* stream) {
     return cap_generate_scored(h, pixels, pixel_fmt, B, num_beams, max_len, length_penalty, out_ids, out_len, out_scores,
@@ -2653,6 +2676,42 @@ int cap_op_select_logprob(const float* logits, int ld, int V, int R, int t, int 
     map.live = live; map.n = n_live;
     return launch_greedy_select(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, min_len,
                                 force_eos, map, logprobs, lp_ld, t, scored);
+}
+int cap_op_select_vocab(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int min_len, int force_eos,
+                        int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths,
+                        float* logprobs, int lp_ld, int32_t* scored, float* vocab_acc, int acc_ld, void* stream) {
+    if (!logits || !finished || !seq || !lengths || R < 1 || V < 1 || ld < V || ld % 4 != 0 || t < 0 || t + 1 >= max_len ||
+        !logprobs || !scored || !vocab_acc || (live != nullptr) != (n_live != nullptr)) {
+        cap_set_error("cap_op_select_vocab: bad arguments");
+        return -1;
+    }
+    RowMap map;
+    map.live = live; map.n = n_live;
+    return launch_greedy_select(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, min_len,
+                                force_eos, map, logprobs, lp_ld, t, scored, vocab_acc, acc_ld);
+}
+int cap_op_vocab_group_threshold(const float* acc, int acc_ld, int V, int N, const int32_t* group_rows, int M, const int32_t* group_off,
+                                 int G, float th, int K, int32_t* out_ids, float* out_prob, int32_t* out_count, void* stream) {
+    const char* f = "cap_op_vocab_group_threshold";
+    if (!acc || !group_off || !out_ids || !out_prob || !out_count || (M > 0 && !group_rows)) { cap_set_error("%s: null buffer", f); return -1; }
+    if (V < 1 || acc_ld < V || N < 1 || M < 0 || G < 1) {
+        cap_set_error("%s: need V >= 1, acc_ld >= V, N >= 1, M >= 0, G >= 1 (got V %d, acc_ld %d, N %d, M %d, G %d)", f, V, acc_ld, N, M, G);
+        return -1;
+    }
+    if (!(th == th) || th - th != 0.f) { cap_set_error("%s: th must be finite", f); return -1; }
+    if (K < 1) { cap_set_error("%s: K (%d) must be at least 1", f, K); return -1; }
+    // the CSR arrays are checked on the host before any kernel indexes with them
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<int32_t> off((size_t)G + 1), rows((size_t)M);
+    CAP_HIP_CHECK(hipMemcpyAsync(off.data(), group_off, off.size() * 4, hipMemcpyDeviceToHost, s));
+    if (M > 0) CAP_HIP_CHECK(hipMemcpyAsync(rows.data(), group_rows, rows.size() * 4, hipMemcpyDeviceToHost, s));
+    CAP_HIP_CHECK(hipStreamSynchronize(s));
+    if (off[0] != 0 || off[G] != M) { cap_set_error("%s: group_off must start at 0 and end at M = %d (got %d .. %d)", f, M, off[0], off[G]); return -1; }
+    for (int g = 0; g < G; ++g)
+        if (off[g + 1] < off[g]) { cap_set_error("%s: group_off is not monotone at group %d (%d > %d)", f, g, off[g], off[g + 1]); return -1; }
+    for (int j = 0; j < M; ++j)
+        if (rows[j] < 0 || rows[j] >= N) { cap_set_error("%s: group_rows[%d] = %d is outside the N = %d rows", f, j, rows[j], N); return -1; }
+    return launch_vocab_group_threshold(acc, acc_ld, V, group_rows, group_off, G, th, K, out_ids, out_prob, out_count, s);
 }
 int cap_op_convert(int dtype, const float* src, void* dst, size_t n, void* stream) {
     return launch_convert(dt_of(dtype), src, dst, n, (hipStream_t)stream);

@@ -432,12 +432,21 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const float* __restr
 // The sum is never serial across the row: thread tid owns the float4 chunks tid, tid + 256, ... (four partial sums, one per
 // component) and the tail elements tid, tid + 256, ...; the 256 thread sums meet in a fixed LDS tree.  Assignment and tree depend
 // on V alone, so a row's value does not depend on its position, the grid or the RowMap.  Accurate expf / log1pf.
-__global__ __launch_bounds__(256) void greedy_select_logprob_kernel(const float* __restrict__ logits, int ld, int V,
-                                                                    int* __restrict__ seq, int seq_ld, int t, int max_len,
-                                                                    int eos, int pad, int* __restrict__ finished,
-                                                                    int* __restrict__ out_len, int min_len, int force_eos,
-                                                                    RowMap map, float* __restrict__ logprobs, int lp_ld,
-                                                                    int lp_col, int* __restrict__ scored) {
+//
+// VOCAB (greedy_select_vocab_kernel): a third read of the row (L2 again) turns it into the step's softmax with the z_max / total /
+// EOS mask just computed and keeps each vocabulary entry's maximum over the caption's steps - what the reference's probability
+// fusion takes from per-step logits (test_pseudo_caption_generation.py:28-63) - in vocab_acc[row][0..V):
+//   acc_i = max(acc_i, exp(z_i - z_max) / (1 + total))          (the selected token's own value is 1 / (1 + total))
+// A masked EOS and a -inf entry give 0.  Elementwise (accurate expf, a true division), float4 loads / stores on the chunks of the
+// sums and the same scalar tail: a value depends on the row's logits and V alone.  Columns V.. of vocab_acc are never touched.
+template <bool VOCAB>
+__device__ __forceinline__ void greedy_select_scored_body(const float* __restrict__ logits, int ld, int V,
+                                                          int* __restrict__ seq, int seq_ld, int t, int max_len,
+                                                          int eos, int pad, int* __restrict__ finished,
+                                                          int* __restrict__ out_len, int min_len, int force_eos,
+                                                          RowMap map, float* __restrict__ logprobs, int lp_ld,
+                                                          int lp_col, int* __restrict__ scored, float* __restrict__ vocab_acc,
+                                                          int acc_ld) {
     const int crow = blockIdx.x, tid = threadIdx.x;
     if (map.n && crow >= *map.n) return;
     const int row = map.live ? map.live[crow] : crow;
@@ -482,6 +491,32 @@ __global__ __launch_bounds__(256) void greedy_select_logprob_kernel(const float*
             __syncthreads();
         }
         total = sv[0];
+        if (VOCAB) {
+            float* __restrict__ a = vocab_acc + (size_t)row * acc_ld;
+            const float denom = 1.f + total;
+            const int skip = mask_eos ? eos : -1;
+            for (int c0 = tid; c0 < V4; c0 += 1024) {
+                float4 v[4], p[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int c = c0 + u * 256;
+                    if (c < V4) { v[u] = *(const float4*)(x + 4 * c); p[u] = *(const float4*)(a + 4 * c); }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int c = c0 + u * 256, i = 4 * c;
+                    if (c < V4) {
+                        p[u].x = fmaxf(p[u].x, i == skip ? 0.f : expf(v[u].x - zmax) / denom);
+                        p[u].y = fmaxf(p[u].y, i + 1 == skip ? 0.f : expf(v[u].y - zmax) / denom);
+                        p[u].z = fmaxf(p[u].z, i + 2 == skip ? 0.f : expf(v[u].z - zmax) / denom);
+                        p[u].w = fmaxf(p[u].w, i + 3 == skip ? 0.f : expf(v[u].w - zmax) / denom);
+                        *(float4*)(a + 4 * c) = p[u];
+                    }
+                }
+            }
+            for (int i = (V4 << 2) + tid; i < V; i += 256)
+                a[i] = fmaxf(a[i], i == skip ? 0.f : expf(x[i] - zmax) / denom);
+        }
     }
     if (tid == 0) {
         if (greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos)) {
@@ -489,6 +524,89 @@ __global__ __launch_bounds__(256) void greedy_select_logprob_kernel(const float*
             scored[row] += 1;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void greedy_select_logprob_kernel(const float* __restrict__ logits, int ld, int V,
+                                                                    int* __restrict__ seq, int seq_ld, int t, int max_len,
+                                                                    int eos, int pad, int* __restrict__ finished,
+                                                                    int* __restrict__ out_len, int min_len, int force_eos,
+                                                                    RowMap map, float* __restrict__ logprobs, int lp_ld,
+                                                                    int lp_col, int* __restrict__ scored) {
+    greedy_select_scored_body<false>(logits, ld, V, seq, seq_ld, t, max_len, eos, pad, finished, out_len, min_len, force_eos, map,
+                                     logprobs, lp_ld, lp_col, scored, nullptr, 0);
+}
+
+__global__ __launch_bounds__(256) void greedy_select_vocab_kernel(const float* __restrict__ logits, int ld, int V,
+                                                                  int* __restrict__ seq, int seq_ld, int t, int max_len,
+                                                                  int eos, int pad, int* __restrict__ finished,
+                                                                  int* __restrict__ out_len, int min_len, int force_eos,
+                                                                  RowMap map, float* __restrict__ logprobs, int lp_ld,
+                                                                  int lp_col, int* __restrict__ scored,
+                                                                  float* __restrict__ vocab_acc, int acc_ld) {
+    greedy_select_scored_body<true>(logits, ld, V, seq, seq_ld, t, max_len, eos, pad, finished, out_len, min_len, force_eos, map,
+                                    logprobs, lp_ld, lp_col, scored, vocab_acc, acc_ld);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Probability fusion behind the vocab form: per group of caption rows (CSR: group_rows[group_off[g] .. group_off[g + 1])), the mean
+// of the rows' vocab_acc vectors, the tokens whose mean exceeds th in ascending id order, their means, and their full count.
+//   mean(i) = (((a_0 + a_1) + a_2) + ...) / (float)n   in fp32, members in listed order; kept if mean > th (strict)
+// One workgroup per group walks the vocabulary in tiles of 1 024 tokens (four rounds of 256 consecutive ids; all loads of a tile are
+// issued before its first ballot).  The order inside a round comes from the wave64 ballot, across the four waves and the four
+// rounds from one LDS table, across tiles from the running base every thread keeps: no scratch, no atomics, and nothing depends on
+// the grid (a group's output is the same bits wherever it stands in the list).  At most K entries are written; out_count is the
+// full count.  An empty group writes count 0.
+__global__ __launch_bounds__(256) void vocab_group_threshold_kernel(const float* __restrict__ acc, int acc_ld, int V,
+                                                                    const int* __restrict__ group_rows,
+                                                                    const int* __restrict__ group_off, float th, int K,
+                                                                    int* __restrict__ out_ids, float* __restrict__ out_prob,
+                                                                    int* __restrict__ out_count) {
+    __shared__ int wsum[16];                             // [round][wave]
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r0 = group_off[g], n = group_off[g + 1] - r0;
+    int base = 0;
+    if (n > 0) {                                         // uniform over the block
+        const float fn = (float)n;
+        for (int i0 = 0; i0 < V; i0 += 1024) {
+            float mean[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int i = i0 + u * 256 + tid;
+                float s = 0.f;
+                if (i < V) {
+                    s = acc[(size_t)group_rows[r0] * acc_ld + i];
+                    for (int j = 1; j < n; ++j) s += acc[(size_t)group_rows[r0 + j] * acc_ld + i];
+                    s = s / fn;
+                }
+                mean[u] = s;
+            }
+            unsigned long long b[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                b[u] = __ballot(i0 + u * 256 + tid < V && mean[u] > th);
+                if (lane == 0) wsum[u * 4 + w] = __popcll(b[u]);
+            }
+            __syncthreads();
+            int off = base;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                for (int k = 0; k < 4; ++k) {
+                    const int c = wsum[u * 4 + k];
+                    if (k == w && ((b[u] >> lane) & 1ull)) {
+                        const int pos = off + __popcll(b[u] & ((1ull << lane) - 1ull));
+                        if (pos < K) {
+                            out_ids[(size_t)g * K + pos] = i0 + u * 256 + tid;
+                            out_prob[(size_t)g * K + pos] = mean[u];
+                        }
+                    }
+                    off += c;
+                }
+            }
+            base = off;                                  // the same number in every thread
+            __syncthreads();                             // wsum is rewritten by the next tile
+        }
+    }
+    if (tid == 0) out_count[g] = base;
 }
 
 __global__ void fill_i32_kernel(int* p, int v, size_t n) {
@@ -716,8 +834,19 @@ int launch_embed(int dtype, const int* seq, int seq_ld, int t, const float* word
 
 int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos,
                          int pad, int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
-                         float* logprobs, int lp_ld, int lp_col, int* scored) {
-    if (logprobs) {
+                         float* logprobs, int lp_ld, int lp_col, int* scored, float* vocab_acc, int acc_ld) {
+    if (vocab_acc) {
+        if (!logprobs || !scored || lp_col < 0 || lp_col >= lp_ld) {
+            cap_set_error("greedy_select: the vocabulary accumulator needs the log-prob buffers (column %d of [0, %d), step counter)", lp_col, lp_ld);
+            return -1;
+        }
+        if (acc_ld < V || acc_ld % 4 != 0 || ((uintptr_t)vocab_acc & 15) != 0) {
+            cap_set_error("greedy_select: vocab_acc needs acc_ld >= V (%d), acc_ld %% 4 == 0 (got %d) and a 16-byte aligned pointer", V, acc_ld);
+            return -1;
+        }
+        hipLaunchKernelGGL(greedy_select_vocab_kernel, dim3(R), dim3(256), 0, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
+                           pad, finished, out_len, min_len, force_eos, map, logprobs, lp_ld, lp_col, scored, vocab_acc, acc_ld);
+    } else if (logprobs) {
         if (!scored || lp_col < 0 || lp_col >= lp_ld) { cap_set_error("greedy_select: log-prob column %d outside [0, %d) or no step counter", lp_col, lp_ld); return -1; }
         hipLaunchKernelGGL(greedy_select_logprob_kernel, dim3(R), dim3(256), 0, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
                            pad, finished, out_len, min_len, force_eos, map, logprobs, lp_ld, lp_col, scored);
@@ -755,6 +884,14 @@ __global__ __launch_bounds__(1024) void compact_rows_kernel(const int* __restric
         __syncthreads();
     }
     if (tid == 0) *n_live = base;
+}
+int launch_vocab_group_threshold(const float* acc, int acc_ld, int V, const int* group_rows, const int* group_off, int G, float th,
+                                 int K, int* out_ids, float* out_prob, int* out_count, hipStream_t s) {
+    if (G < 1) return 0;
+    hipLaunchKernelGGL(vocab_group_threshold_kernel, dim3(G), dim3(256), 0, s, acc, acc_ld, V, group_rows, group_off, th, K, out_ids,
+                       out_prob, out_count);
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 int launch_compact_rows(const int* finished, int R, int* live, int* n_live, hipStream_t s) {
     hipLaunchKernelGGL(compact_rows_kernel, dim3(1), dim3(1024), 0, s, finished, R, live, n_live);

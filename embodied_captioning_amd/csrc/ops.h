@@ -54,7 +54,14 @@ int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_l
                          RowMap map = RowMap(),             // logits row c belongs to row map.live[c] (seq / finished / out_len)
                          // scoring form (launched only when logprobs is given): logprobs[row*lp_ld + lp_col] = log max softmax of
                          // the row as selected from (EOS mask applied), scored[row] += 1, for the rows open at this step
-                         float* logprobs = nullptr, int lp_ld = 0, int lp_col = 0, int* scored = nullptr);
+                         float* logprobs = nullptr, int lp_ld = 0, int lp_col = 0, int* scored = nullptr,
+                         // vocab form (launched only when vocab_acc is given; needs the scoring buffers): vocab_acc[row*acc_ld + i] =
+                         // max(itself, softmax_i of the row as selected from), i < V, for the rows open at this step
+                         float* vocab_acc = nullptr, int acc_ld = 0);
+// per group g of rows group_rows[group_off[g] .. group_off[g+1]) of acc [., acc_ld]: the tokens i < V whose fp32 mean over the
+// members (summed in listed order) exceeds th, ascending: out_ids / out_prob [G, K] (at most K written), out_count [G] (all)
+int launch_vocab_group_threshold(const float* acc, int acc_ld, int V, const int* group_rows, const int* group_off, int G, float th,
+                                 int K, int* out_ids, float* out_prob, int* out_count, hipStream_t s);
 // live[] = the rows with finished[r] == 0 in ascending order, *n_live = their count (one workgroup; stable)
 int launch_compact_rows(const int* finished, int R, int* live, int* n_live, hipStream_t s);
 int launch_fill_i32(int* p, int v, size_t n, hipStream_t s);

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import json
 import logging
+import math
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -44,6 +45,31 @@ def perplexity_from_logprobs(token_logprobs: torch.Tensor, scored_steps: torch.T
     keep = torch.arange(lp.shape[1])[None, :] < n[:, None]
     total = torch.where(keep, lp, torch.zeros_like(lp)).sum(dim=1)
     return torch.exp(-total / n.to(torch.float64))
+
+
+def vocab_group_csr(groups: Sequence[Sequence[int]], n_rows: int):
+    """Groups of row indices -> the CSR pair the group kernel takes: (group_rows int32 [M], group_off int32 [G + 1]) on the host.
+    Members keep the caller's order and need not be contiguous; an empty group is legal; a row may belong to one group only."""
+    rows: List[int] = []
+    off = [0]
+    for g, members in enumerate(groups):
+        for r in members:
+            r = int(r)
+            if not 0 <= r < n_rows:
+                raise ValueError(f"groups[{g}]: row {r} is outside the {n_rows} rows of vocab_maxprob")
+            rows.append(r)
+        off.append(len(rows))
+    if len(set(rows)) != len(rows):
+        dup = sorted({r for r in rows if rows.count(r) > 1})
+        raise ValueError(f"groups: row(s) {dup[:8]} are listed more than once (a row belongs to one group only)")
+    return torch.tensor(rows, dtype=torch.int32), torch.tensor(off, dtype=torch.int32)
+
+
+def fusion_max_tokens(steps: int, th: float, vocab: int) -> int:
+    """Capacity per group that the kept tokens cannot exceed: ceil(steps / th), at most the vocabulary (`fuse_vocab_groups`)."""
+    if not th > 0:
+        return int(vocab)
+    return max(1, min(int(vocab), int(math.ceil(steps / th))))
 
 
 class CaptionerEngine:
@@ -271,7 +297,7 @@ class CaptionerEngine:
 
     def generate(self, pixels: torch.Tensor, num_beams: int = 1, max_length: Optional[int] = None,
                  length_penalty: float = 1.0, output_logits: bool = False, num_beam_groups: Optional[int] = None,
-                 output_logprobs: bool = False, **sampling_options) -> Dict[str, torch.Tensor]:
+                 output_logprobs: bool = False, output_vocab_maxprob: bool = False, **sampling_options) -> Dict[str, torch.Tensor]:
         """Returns device tensors: sequences int32 [B, max_length] (incl. BOS), lengths int32 [B],
         sequences_scores fp32 [B] (beams only), logits fp32 [max_length-1, B*num_beams, vocab] (optional).
         BLIP-2: max_length counts NEW tokens (HF max_new_tokens); sequences are those new tokens only (no image
@@ -280,10 +306,17 @@ class CaptionerEngine:
         it (steps as for logits), zero from the caption's end on, and scored_steps int32 [B] = valid entries per row - taken by the
         selection kernel itself (cap_generate_scored): any batch size, no logits buffer, same kernels otherwise;
         `perplexity_from_logprobs` turns them into the reference's per-caption perplexity.
+        output_vocab_maxprob (greedy): vocab_maxprob fp32 [B, vocab] = every vocabulary entry's maximal softmax probability over the
+        steps at which the caption was open (`scored_steps` of them; 0 where nothing ran) - what the reference's probability fusion
+        takes from per-step logits, kept by the selection kernel instead (cap_generate_vocab).  A view without the row padding of
+        the [B, acc_ld] buffer behind it; token_logprobs / scored_steps come with it; `fuse_vocab_groups` is its consumer.
         num_beam_groups (CoCa): the reference's `_generate_beamsearch` with that many beam groups (coca_model.py:335-482;
         its `generate()` defaults are 6 beams in 3 groups) - cap_generate_groups; no per-step logits in that mode.
         sampling_options: anything else a caller of the reference's / HF's `generate` may pass (top_p, top_k, temperature,
         repetition_penalty, do_sample, ...): accepted at their neutral values, rejected BY NAME otherwise - never ignored."""
+        if output_vocab_maxprob and (num_beam_groups is not None or num_beams != 1):      # before anything is allocated or run
+            raise N.CaptionerHipError("output_vocab_maxprob is the greedy loop's (num_beams = 1): beam search "
+                                      f"(num_beams = {num_beams}, num_beam_groups = {num_beam_groups}) keeps no per-step distribution")
         if sampling_options:
             from .captioner.generation_options import reject_unsupported_generation_options, _NEUTRAL
             known = set(_NEUTRAL) | {"generation_type", "top_k", "top_p"}
@@ -303,7 +336,11 @@ class CaptionerEngine:
             # zeros, not empty: with early exit the steps after the last executed one are never written (callers see 0, not
             # stale memory); `last_decode_steps` tells how many steps ran
             logits = torch.zeros((steps, B * num_beams, self.arch.vocab), dtype=torch.float32, device=self.device)
-        lps = scored = None
+        lps = scored = vmax = None
+        if output_vocab_maxprob:
+            output_logprobs = True
+            acc_ld = (self.arch.vocab + 3) // 4 * 4
+            vmax = torch.empty((B, acc_ld), dtype=torch.float32, device=self.device)      # zero-filled by the library
         if output_logprobs:
             if num_beam_groups is not None:
                 raise N.CaptionerHipError("output_logprobs is the greedy loop's (num_beams = 1): the group beam search "
@@ -321,7 +358,14 @@ class CaptionerEngine:
                                                      C.c_void_p(scores.data_ptr()), C.c_void_p(_stream_ptr(self.device))), "cap_generate_groups")
             return {"sequences": ids, "lengths": lens, "sequences_scores": scores}
         with torch.cuda.device(self.device):
-            if lps is not None:
+            if vmax is not None:
+                N.check(self.lib.cap_generate_vocab(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, L, C.c_void_p(ids.data_ptr()),
+                                                    C.c_void_p(lens.data_ptr()),
+                                                    C.c_void_p(logits.data_ptr() if logits is not None else 0),
+                                                    C.c_void_p(lps.data_ptr()), C.c_void_p(scored.data_ptr()),
+                                                    C.c_void_p(vmax.data_ptr()), vmax.shape[1],
+                                                    C.c_void_p(_stream_ptr(self.device))), "cap_generate_vocab")
+            elif lps is not None:
                 N.check(self.lib.cap_generate_scored(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, num_beams, L,
                                                      C.c_float(length_penalty), C.c_void_p(ids.data_ptr()),
                                                      C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
@@ -337,11 +381,55 @@ class CaptionerEngine:
         out = {"sequences": ids, "lengths": lens}
         if lps is not None:
             out["token_logprobs"], out["scored_steps"] = lps, scored
+        if vmax is not None:
+            out["vocab_maxprob"] = vmax[:, :self.arch.vocab]
         if num_beams > 1:
             out["sequences_scores"] = scores
         if logits is not None:
             out["logits"] = logits
         return out
+
+    def fuse_vocab_groups(self, vocab_maxprob: torch.Tensor, groups: Sequence[Sequence[int]], th: float,
+                          max_tokens: Optional[int] = None):
+        """The group half of the probability fusion, on the device: per group of rows of `vocab_maxprob` (fp32 [N, vocab] from
+        `generate(output_vocab_maxprob=True)`, any row stride), the fp32 mean over the members in listed order and the tokens whose
+        mean exceeds `th` (strict), in ascending id order.  -> (ids int32 [G, K], probs fp32 [G, K], counts int32 [G]); row g holds
+        counts[g] entries, the rest is -1 / 0.
+        Default K = ceil(steps / th), steps = this engine's decode steps.  It cannot overflow: a step's softmax sums to 1, so for one
+        caption sum_i max_t p_t(i) <= sum_t sum_i p_t(i) = steps, a mean over captions keeps that bound, and k tokens above th need
+        k * th < steps: fewer than steps / th of them.  With a caller's smaller max_tokens a group that keeps more raises."""
+        v = vocab_maxprob
+        if v.dim() != 2 or v.dtype != torch.float32 or not v.is_cuda or v.stride(1) != 1 or v.shape[0] < 1 or v.shape[1] < 1:
+            raise ValueError(f"vocab_maxprob must be a device fp32 [N, vocab] tensor with unit column stride, got {tuple(v.shape)} {v.dtype}")
+        th = float(th)
+        if not math.isfinite(th):
+            raise ValueError(f"th must be finite, got {th}")
+        Nr, V = int(v.shape[0]), int(v.shape[1])
+        G = len(groups)
+        steps = self.max_len if getattr(self, "is_blip2", False) else self.max_len - 1
+        K = fusion_max_tokens(steps, th, V) if max_tokens is None else int(max_tokens)
+        if K < 1:
+            raise ValueError(f"max_tokens must be at least 1, got {K}")
+        ids = torch.full((G, K), -1, dtype=torch.int32, device=v.device)
+        probs = torch.zeros((G, K), dtype=torch.float32, device=v.device)
+        counts = torch.zeros((G,), dtype=torch.int32, device=v.device)
+        if G == 0:
+            return ids, probs, counts
+        rows, off = vocab_group_csr(groups, Nr)
+        rows_d, off_d = rows.to(v.device), off.to(v.device)
+        acc_ld = int(v.stride(0)) if Nr > 1 else max(int(v.stride(0)), V)
+        with torch.cuda.device(v.device):
+            N.check(self.lib.cap_op_vocab_group_threshold(C.c_void_p(v.data_ptr()), acc_ld, V, Nr, C.c_void_p(rows_d.data_ptr()),
+                                                          int(rows.numel()), C.c_void_p(off_d.data_ptr()), G, C.c_float(th), K,
+                                                          C.c_void_p(ids.data_ptr()), C.c_void_p(probs.data_ptr()),
+                                                          C.c_void_p(counts.data_ptr()), C.c_void_p(_stream_ptr(v.device))),
+                    "cap_op_vocab_group_threshold")
+        if max_tokens is not None:
+            over = (counts > K).nonzero().flatten().tolist()
+            if over:
+                raise N.CaptionerHipError(f"fuse_vocab_groups: group(s) {over[:8]} keep {counts[over[0]].item()} tokens above th = {th}, "
+                                          f"more than max_tokens = {K}")
+        return ids, probs, counts
 
     # ------------------------------------------------------------------------------------------ profiling
     def profile(self, on: bool) -> None:
@@ -437,7 +525,7 @@ class EnginePool:
             cur.wait_stream(s)
 
     # outputs of `generate` whose leading dimension is the batch's rows (what a merged pass is split back by)
-    _PER_ROW_OUTPUTS = ("sequences", "lengths", "sequences_scores", "token_logprobs", "scored_steps")
+    _PER_ROW_OUTPUTS = ("sequences", "lengths", "sequences_scores", "token_logprobs", "scored_steps", "vocab_maxprob")
 
     @staticmethod
     def coalesce_plan(rows: Sequence[int], n_engines: int, max_rows: int) -> List[List[int]]:

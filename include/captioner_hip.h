@@ -231,6 +231,20 @@ int cap_generate_scored(CapHandle h, const void* pixels, int pixel_fmt, int B, i
                         float length_penalty, int32_t* out_ids, int32_t* out_len, float* out_scores,
                         float* out_step_logits, float* out_logprobs, int32_t* out_scored, void* stream);
 
+/* The greedy loop of cap_generate_scored that also keeps, per caption, every vocabulary entry's maximal probability over the
+ * caption's steps - the vector the reference's probability fusion builds from per-step logits
+ * (captioner/test_pseudo_caption_generation.py:28-63: softmax of each step's row, maximum over the steps) - again inside the token
+ * selection kernel: no logits buffer, any batch size, early exit, the small-batch path and row compaction as for cap_generate.
+ *   out_vocab fp32 [B, acc_ld]  out_vocab[b][i] = max over the steps at which caption b was open of softmax(row as selected from)[i],
+ *             i < vocab (CoCa: 0 for EOS while it is masked); columns vocab .. acc_ld - 1 hold the zero fill.  acc_ld >= vocab,
+ *             acc_ld % 4 == 0 and a 16-byte aligned pointer (the kernel moves 16 bytes at a time) - refused otherwise.
+ *   out_logprobs / out_scored   as cap_generate_scored; required (the steps counted by out_scored are the steps maximised over).
+ *   out_step_logits             as cap_generate, or NULL.
+ * All three families, num_beams = 1.  The three output buffers are zero-filled by the call on `stream`. */
+int cap_generate_vocab(CapHandle h, const void* pixels, int pixel_fmt, int B, int max_len, int32_t* out_ids, int32_t* out_len,
+                       float* out_step_logits, float* out_logprobs, int32_t* out_scored, float* out_vocab, int acc_ld,
+                       void* stream);
+
 /* CoCa's `_generate_beamsearch` with beam GROUPS (reference coca_model.py:335-482; `generate()` defaults num_beams = 6,
  * num_beam_groups = 3, :218-219): num_beams % num_beam_groups == 0, each group a beam search of num_beams / num_beam_groups
  * beams, the best hypothesis over an image's groups returned.  The reference attaches no diversity processor (:236-241), so
@@ -426,6 +440,23 @@ int cap_op_beam_peek(void* state, int B, int K, int max_len, int parity, int32_t
 int cap_op_select_logprob(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int min_len, int force_eos,
                           int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths,
                           float* logprobs, int lp_ld, int32_t* scored, void* stream);
+/* cap_op_select_logprob with the vocabulary accumulator of cap_generate_vocab: vocab_acc fp32 [., acc_ld] (caption rows, updated
+ * in place for the open captions: entry i < V becomes the larger of itself and the row's softmax at i; acc_ld >= V, acc_ld % 4 == 0,
+ * 16-byte aligned).  logprobs / scored are required. */
+int cap_op_select_vocab(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int min_len, int force_eos,
+                        int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths,
+                        float* logprobs, int lp_ld, int32_t* scored, float* vocab_acc, int acc_ld, void* stream);
+/* The group step of the probability fusion.  acc fp32 [N, acc_ld] (device); G groups in CSR form, both arrays on the device:
+ * group_rows int32 [M] (row indices into acc, in the caller's order, need not be contiguous, each row in one group at most) and
+ * group_off int32 [G + 1] (0 = off[0] <= ... <= off[G] = M; an empty group is legal).  Per group, in fp32,
+ *   mean(i) = (((a_0 + a_1) + a_2) + ...) / n   over its members in listed order, i < V
+ * and the tokens with mean > th (strict) in ascending id order: out_ids int32 [G, K], out_prob fp32 [G, K] (their means; at most K
+ * entries written, nothing beyond min(count, K) touched), out_count int32 [G] (always the full count).  The output of a group does
+ * not depend on G or on its place in the list.  Refused by name: offsets not monotone or not within M, rows outside [0, N), th not
+ * finite, K < 1.  Copies the CSR arrays back for that check: synchronises the stream. */
+int cap_op_vocab_group_threshold(const float* acc, int acc_ld, int V, int N, const int32_t* group_rows, int M,
+                                 const int32_t* group_off, int G, float th, int K, int32_t* out_ids, float* out_prob,
+                                 int32_t* out_count, void* stream);
 int cap_op_convert(int dtype, const float* src, void* dst, size_t n, void* stream);
 /* Weight upload as cap_load_weight does it: dst [rows, cols] in the GEMM-operand type of `dtype` (CAP_F32_SPLIT: G8 halves of
  * 4096 * w - the split GEMM's epilogue divides by 4096; a G8 buffer is 4 bytes per element, cols % 8 == 0). */
