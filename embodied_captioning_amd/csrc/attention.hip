@@ -1870,10 +1870,16 @@ int launch_vit_attention(int dtype, const void* qkv, void* ctx, int B, int N, in
     return 0;
 }
 
-int launch_decode_attention(int dtype, const void* q, const void* kbase, const void* vbase, const int* anc,
-                            int anc_ld, int rows_per_kv, int kv_ld, int n_keys, void* out, int R, int H, int impl,
-                            hipStream_t s, const float* q_part, int q_S, const float* q_bias, int q_ld, int q_col0,
-                            int append_kv, int out_dtype, const int* skip_rows, int kv16, size_t kv_row0, RowMap map) {
+int launch_decode_attention(int dtype, const DecodeAttn& a, hipStream_t s) {
+    const void *q = a.q, *kbase = a.kbase, *vbase = a.vbase;
+    const int *anc = a.anc, *skip_rows = a.skip_rows;
+    const int anc_ld = a.anc_ld, rows_per_kv = a.rows_per_kv, kv_ld = a.kv_ld, n_keys = a.n_keys, R = a.R, H = a.H, impl = a.impl;
+    const float *q_part = a.q_part, *q_bias = a.q_bias;
+    const int q_S = a.q_S, q_ld = a.q_ld, q_col0 = a.q_col0, append_kv = a.append_kv, kv16 = a.kv16;
+    int out_dtype = a.out_dtype;
+    void* out = a.out;
+    const size_t kv_row0 = a.kv_row0;
+    const RowMap map = a.map;
     // kv16: kbase / vbase are the bases of KV16 blocks (common.h), the launch's first row has index kv_row0 in them
     if (out_dtype < 0) out_dtype = dtype;
     if (kv16 && !(dtype == CAP_DT_F32 && impl == 0 && !anc && !append_kv && n_keys > 32)) {

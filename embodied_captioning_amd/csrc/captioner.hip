@@ -101,19 +101,57 @@ struct OLayer {            // OPT decoder layer (pre-LN): fused q|k|v, out_proj,
     float *s_qkv = nullptr, *s_o = nullptr, *s_f1 = nullptr, *s_f2 = nullptr;   // CapConfig.weight_int8: row scales of the int8 weights
     float *b_qkv, *b_o, *b_f1, *b_f2, *ln1_g, *ln1_b, *ln2_g, *ln2_b;
 };
-struct TLayer {
-    void *w_qkv, *w_so, *w_cq, *w_co, *w_f1, *w_f2;
-    float *b_qkv, *b_so, *so_g, *so_b, *b_cq, *b_co, *co_g, *co_b, *b_f1, *b_f2, *f_g, *f_b;
-    void* self_cache;     // [2][R][H][max_len][64] (T)
+struct TLayer {            // sentence-encoder (BERT) layer: fused q|k|v, output projection, FFN; post-LN
+    void *w_qkv, *w_so, *w_f1, *w_f2;
+    float *b_qkv, *b_so, *so_g, *so_b, *b_f1, *b_f2, *f_g, *f_b;
 };
 
-struct CBlock {            // one CoCa text block: causal self-attention (unimodal / multimodal) or cross-attention
-    bool cross = false;
-    int cache = -1;        // self blocks: index of their K/V cache
-    int cross_idx = -1;    // cross blocks: multimodal layer index (cross K/V cache slot)
-    void *w_in = nullptr, *w_o = nullptr, *w_fc = nullptr, *w_pr = nullptr;   // w_in: [3E,E] self, [E,E] cross query
-    float *b_in = nullptr, *b_o = nullptr, *b_fc = nullptr, *b_pr = nullptr;
-    float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
+// The BLIP and CoCa text decoders as ONE list of sub-layers (run_step / run_step_small walk it; build_blip / build_coca fill it
+// once).  A sub-layer is two projections around its core, followed by a split-K consumer: bias + residual + ONE LayerNorm.
+//   DEC_SELF   q|k|v projection [3W, W] -> causal attention over the self cache -> output projection [W, W]
+//   DEC_CROSS  query projection [W, W]  -> attention over the image's K/V        -> output projection [W, W]
+//   DEC_FFN    fc [F, W] (GELU)                                                  -> projection back  [W, F]
+// BLIP is post-LN: [SELF, CROSS, FFN] per layer, the LayerNorm is the sub-layer's own, its output is the next operand AND the new
+// residual row.  CoCa is pre-LN: [SELF, FFN] per unimodal / multimodal self block, [CROSS, FFN] per cross block, the LayerNorm is
+// the NEXT sub-layer's (ln_2 of the block, ln_1 of the next block, ln_final after the last), the residual row is the sum.
+enum { DEC_SELF = 0, DEC_CROSS = 1, DEC_FFN = 2 };
+struct DecSub {
+    int kind = DEC_FFN;
+    void *w_in = nullptr, *w_out = nullptr;
+    float *b_in = nullptr, *b_out = nullptr;
+    float *ln_g = nullptr, *ln_b = nullptr;   // the LayerNorm applied to the sub-layer's result (see above)
+    void* cache = nullptr;                    // DEC_SELF: [k|v][R][H][max_len][64] in the activation type (arena)
+    int slot = -1;                            // DEC_CROSS: layer index inside the cross K/V cache
+};
+// Profile tags of the decoder's launches, indexed by sub-layer kind.  Batch kernels: input GEMM, attention, output GEMM; fused
+// small-batch kernels: the sub-layer's first and second launch.
+struct DecTags {
+    const char *in[3], *attn[2], *out[3], *tr, *ln, *vocab;
+    const char *s_in[3], *s_out[3], *s_tr, *s_vocab;
+};
+const DecTags kBlipDecTags = {{"dec_gemm_qkv", "dec_gemm_cq", "dec_gemm_f1"}, {"dec_self_attn", "dec_cross_attn"},
+                              {"dec_gemm_so", "dec_gemm_co", "dec_gemm_f2"}, "dec_gemm_tr", "dec_layernorm", "dec_gemm_vocab",
+                              {"dec_small_qkv", "dec_small_cross", "dec_small_f1"}, {"dec_small_so", "dec_small_co", "dec_small_f2"},
+                              "dec_small_tr", "dec_small_vocab"};
+const DecTags kCocaDecTags = {{"coca_gemm_qkv", "coca_gemm_cq", "coca_gemm_fc"}, {"coca_self_attn", "coca_cross_attn"},
+                              {"coca_gemm_o", "coca_gemm_o", "coca_gemm_pr"}, nullptr, nullptr, "coca_gemm_vocab",
+                              {"coca_small_qkv", "coca_small_cross", "coca_small_fc"}, {"coca_small_o", "coca_small_o", "coca_small_pr"},
+                              nullptr, "coca_small_vocab"};
+struct DecPlan {
+    std::vector<DecSub> subs;
+    bool pre_ln = false;          // CoCa (SmallLN::x_is_sum; the batch consumer's y_out instead of out_f)
+    bool skip_finished = false;   // BLIP greedy: ended captions' rows are left alone.  CoCa computes them: their step logits are observable
+    int W = 0;                    // width: t_hidden (BLIP), embed_dim (CoCa)
+    // cross K/V cache [slot][k|v][image][head][kv_tokens][64]: BLIP keeps the NT image tokens and attends all of them, CoCa keeps
+    // the pooler's Q tokens and skips the first (the pooled token)
+    int kv_tokens = 0, kv_first = 0, kv_keys = 0;
+    // embedding: LayerNorm(word[token] + pos[t]) with the embeddings' own LayerNorm (BLIP) or the first sub-layer's ln_1 (CoCa)
+    float *word = nullptr, *pos = nullptr, *emb_g = nullptr, *emb_b = nullptr;
+    // head: BLIP transform (dense + GELU, LayerNorm) then the vocabulary GEMM with a bias; CoCa the vocabulary GEMM alone (w_tr
+    // null: ln_final is the last sub-layer's LayerNorm)
+    void *w_tr = nullptr, *w_vocab = nullptr;
+    float *b_tr = nullptr, *tr_g = nullptr, *tr_b = nullptr, *b_vocab = nullptr;
+    const DecTags* tags = nullptr;
 };
 
 // The ViT branch GEMMs (proj, fc2) of the MFMA-staged types add their output to the residual stream X IN PLACE (gemm_pp.hip's
@@ -169,9 +207,10 @@ struct Captioner {
     void* w_patch;
     std::vector<VLayer> vl;
     // text weights
-    float *word_f32, *tpos, *emb_g, *emb_b, *b_ckv, *b_tr, *tr_g, *tr_b, *b_vocab;
-    void *word_t, *w_ckv, *w_tr;
-    std::vector<TLayer> tl;
+    float *word_f32, *tpos, *emb_g, *emb_b, *b_ckv;
+    void* w_ckv;
+    std::vector<TLayer> tl;      // (sentence encoder)
+    DecPlan dec;                 // BLIP / CoCa text decoder
     // arena
     void *patches, *emb_t, *cross;
     Tower vt;                    // the image tower's activations (CLIP's text tower: ct)
@@ -185,12 +224,8 @@ struct Captioner {
     // ---- CoCa (CAP_ARCH_COCA)
     int Q = 0, E = 0;
     float *lnpost_g = nullptr, *lnpost_b = nullptr, *pool_q = nullptr, *b_pool_kv = nullptr, *b_pool_o = nullptr, *ones = nullptr,
-          *zeros = nullptr, *tok_emb = nullptr, *lnf_g = nullptr, *lnf_b = nullptr, *pool_o = nullptr,
-          *img_tokens = nullptr;
-    void *w_pool_kv = nullptr, *w_pool_o = nullptr, *w_cvocab = nullptr, *pool_kvbuf = nullptr, *pool_ctx = nullptr,
-         *xhat = nullptr;
-    std::vector<CBlock> cb;
-    std::vector<void*> ccache;
+          *zeros = nullptr, *pool_o = nullptr, *img_tokens = nullptr;
+    void *w_pool_kv = nullptr, *w_pool_o = nullptr, *pool_kvbuf = nullptr, *pool_ctx = nullptr, *xhat = nullptr;
     int ldl;
     // ---- BLIP-2 (CAP_ARCH_BLIP2)
     std::vector<QLayer> ql;
@@ -359,81 +394,81 @@ int reg_tower(Captioner* m, const TowerNames& n, std::vector<VLayer>& layers, in
     return reg_ln(m, std::string(n.root) + n.ln_final, lnf_g, lnf_b, D);
 }
 
+// a BERT-style output block into a sub-layer: p + "dense." -> the output projection [N, K], p + "LayerNorm." -> its LayerNorm
+int reg_out_ln(Captioner* m, const std::string& p, DecSub& u, int N, int K) {
+    TRY(reg_mat(m, p + "dense.weight", &u.w_out, N, K));
+    TRY(reg_f32(m, p + "dense.bias", &u.b_out, N));
+    return reg_ln(m, p + "LayerNorm.", &u.ln_g, &u.ln_b, N);
+}
+
 int build_blip(Captioner* m) {
     const CapConfig& c = m->c;
     const int D = c.v_hidden, T = c.t_hidden, F = c.t_ffn, V = c.vocab;
     TRY(reg_stem(m, kBlipVision));
     TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
 
+    DecPlan& P = m->dec;
+    P.W = T; P.skip_finished = true; P.kv_tokens = P.kv_keys = m->NT; P.tags = &kBlipDecTags;
     const std::string tb = "text_decoder.bert.";
     // the embedding table is read twice: fp32 rows for the lookup, compute-dtype [V,T] as the (tied) LM-head weight
     TRY(walloc(m, (void**)&m->word_f32, (size_t)V * T * 4));
     add_slot(m, tb + "embeddings.word_embeddings.weight", m->word_f32, CAP_DT_F32, V, T);
     if (m->gdt == CAP_DT_F32) {
-        m->word_t = m->word_f32;
+        P.w_vocab = m->word_f32;
     } else {
-        TRY(walloc(m, &m->word_t, (size_t)V * T * m->esz));
-        add_slot(m, tb + "embeddings.word_embeddings.weight", m->word_t, m->gdt, V, T);
+        TRY(walloc(m, &P.w_vocab, (size_t)V * T * m->esz));
+        add_slot(m, tb + "embeddings.word_embeddings.weight", P.w_vocab, m->gdt, V, T);
     }
     TRY(reg_f32(m, tb + "embeddings.position_embeddings.weight", &m->tpos, (int64_t)c.max_pos * T));
-    TRY(reg_f32(m, tb + "embeddings.LayerNorm.weight", &m->emb_g, T));
-    TRY(reg_f32(m, tb + "embeddings.LayerNorm.bias", &m->emb_b, T));
+    TRY(reg_ln(m, tb + "embeddings.LayerNorm.", &m->emb_g, &m->emb_b, T));
+    P.word = m->word_f32; P.pos = m->tpos; P.emb_g = m->emb_g; P.emb_b = m->emb_b;
     // cross-attention K/V projections of all layers fused into one [L*2*T, D] weight (one GEMM per image batch)
     TRY(walloc(m, &m->w_ckv, (size_t)c.t_layers * 2 * T * D * m->esz));
     TRY(walloc(m, (void**)&m->b_ckv, (size_t)c.t_layers * 2 * T * 4));
-    m->tl.resize(c.t_layers);
+    P.subs.resize(3 * c.t_layers);
     const char* nm[3] = {"query.", "key.", "value."};
     for (int i = 0; i < c.t_layers; ++i) {
-        TLayer& L = m->tl[i];
+        DecSub &sa = P.subs[3 * i], &ca = P.subs[3 * i + 1], &ff = P.subs[3 * i + 2];
+        sa.kind = DEC_SELF; ca.kind = DEC_CROSS; ca.slot = i; ff.kind = DEC_FFN;
         const std::string p = tb + "encoder.layer." + std::to_string(i) + ".";
-        TRY(reg_fused(m, p + "attention.self.", nm, 3, &L.w_qkv, &L.b_qkv, T, T));
-        TRY(reg_mat(m, p + "attention.output.dense.weight", &L.w_so, T, T));
-        TRY(reg_f32(m, p + "attention.output.dense.bias", &L.b_so, T));
-        TRY(reg_f32(m, p + "attention.output.LayerNorm.weight", &L.so_g, T));
-        TRY(reg_f32(m, p + "attention.output.LayerNorm.bias", &L.so_b, T));
-        TRY(reg_mat(m, p + "crossattention.self.query.weight", &L.w_cq, T, T));
-        TRY(reg_f32(m, p + "crossattention.self.query.bias", &L.b_cq, T));
+        TRY(reg_fused(m, p + "attention.self.", nm, 3, &sa.w_in, &sa.b_in, T, T));
+        TRY(reg_out_ln(m, p + "attention.output.", sa, T, T));
+        TRY(reg_fused(m, p + "crossattention.self.", nm, 1, &ca.w_in, &ca.b_in, T, T));
         reg_rows(m, p + "crossattention.self.", nm + 1, 2, (char*)m->w_ckv + (size_t)i * 2 * T * D * m->esz, m->b_ckv + (size_t)i * 2 * T, T, D);
-        TRY(reg_mat(m, p + "crossattention.output.dense.weight", &L.w_co, T, T));
-        TRY(reg_f32(m, p + "crossattention.output.dense.bias", &L.b_co, T));
-        TRY(reg_f32(m, p + "crossattention.output.LayerNorm.weight", &L.co_g, T));
-        TRY(reg_f32(m, p + "crossattention.output.LayerNorm.bias", &L.co_b, T));
-        TRY(reg_mat(m, p + "intermediate.dense.weight", &L.w_f1, F, T));
-        TRY(reg_f32(m, p + "intermediate.dense.bias", &L.b_f1, F));
-        TRY(reg_mat(m, p + "output.dense.weight", &L.w_f2, T, F));
-        TRY(reg_f32(m, p + "output.dense.bias", &L.b_f2, T));
-        TRY(reg_f32(m, p + "output.LayerNorm.weight", &L.f_g, T));
-        TRY(reg_f32(m, p + "output.LayerNorm.bias", &L.f_b, T));
+        TRY(reg_out_ln(m, p + "crossattention.output.", ca, T, T));
+        const char* fc = "intermediate.dense.";
+        TRY(reg_fused(m, p, &fc, 1, &ff.w_in, &ff.b_in, F, T));
+        TRY(reg_out_ln(m, p + "output.", ff, T, F));
     }
     const std::string cp = "text_decoder.cls.predictions.";
-    TRY(reg_mat(m, cp + "transform.dense.weight", &m->w_tr, T, T));
-    TRY(reg_f32(m, cp + "transform.dense.bias", &m->b_tr, T));
-    TRY(reg_f32(m, cp + "transform.LayerNorm.weight", &m->tr_g, T));
-    TRY(reg_f32(m, cp + "transform.LayerNorm.bias", &m->tr_b, T));
-    TRY(reg_f32(m, cp + "bias", &m->b_vocab, V));
+    TRY(reg_mat(m, cp + "transform.dense.weight", &P.w_tr, T, T));
+    TRY(reg_f32(m, cp + "transform.dense.bias", &P.b_tr, T));
+    TRY(reg_ln(m, cp + "transform.LayerNorm.", &P.tr_g, &P.tr_b, T));
+    TRY(reg_f32(m, cp + "bias", &P.b_vocab, V));
     return 0;
 }
 
-int reg_block(Captioner* m, const std::string& p, CBlock& b, int E, int F, bool cross, int idx) {
-    b.cross = cross;
-    TRY(reg_f32(m, p + ".ln_1.weight", &b.ln1_g, E));
-    TRY(reg_f32(m, p + ".ln_1.bias", &b.ln1_b, E));
-    if (!cross) {
-        TRY(reg_mat(m, p + ".attn.in_proj_weight", &b.w_in, 3 * E, E));
-        TRY(reg_f32(m, p + ".attn.in_proj_bias", &b.b_in, 3 * E));
+// One CoCa text block = an attention sub-layer (causal self-attention, or cross-attention over cache slot `slot` >= 0) and an FFN
+// sub-layer.  Pre-LN: the block's ln_1 is the LayerNorm of whatever comes BEFORE it (ln1_g / ln1_b: the previous FFN sub-layer's,
+// the embedding's for the first block), its ln_2 the attention sub-layer's; the FFN sub-layer's is left to the next block.
+int reg_block(Captioner* m, const std::string& p, DecSub& at, DecSub& ff, float** ln1_g, float** ln1_b, int E, int F, int slot) {
+    at.kind = slot < 0 ? DEC_SELF : DEC_CROSS; at.slot = slot; ff.kind = DEC_FFN;
+    TRY(reg_ln(m, p + ".ln_1.", ln1_g, ln1_b, E));
+    if (slot < 0) {
+        TRY(reg_mat(m, p + ".attn.in_proj_weight", &at.w_in, 3 * E, E));
+        TRY(reg_f32(m, p + ".attn.in_proj_bias", &at.b_in, 3 * E));
     } else {
-        const std::string d = "derived.cross_q." + std::to_string(idx);
-        TRY(reg_mat(m, d + ".weight", &b.w_in, E, E));
-        TRY(reg_f32(m, d + ".bias", &b.b_in, E));
+        const std::string d = "derived.cross_q." + std::to_string(slot);
+        TRY(reg_mat(m, d + ".weight", &at.w_in, E, E));
+        TRY(reg_f32(m, d + ".bias", &at.b_in, E));
     }
-    TRY(reg_mat(m, p + ".attn.out_proj.weight", &b.w_o, E, E));
-    TRY(reg_f32(m, p + ".attn.out_proj.bias", &b.b_o, E));
-    TRY(reg_f32(m, p + ".ln_2.weight", &b.ln2_g, E));
-    TRY(reg_f32(m, p + ".ln_2.bias", &b.ln2_b, E));
-    TRY(reg_mat(m, p + ".mlp.c_fc.weight", &b.w_fc, F, E));
-    TRY(reg_f32(m, p + ".mlp.c_fc.bias", &b.b_fc, F));
-    TRY(reg_mat(m, p + ".mlp.c_proj.weight", &b.w_pr, E, F));
-    TRY(reg_f32(m, p + ".mlp.c_proj.bias", &b.b_pr, E));
+    TRY(reg_mat(m, p + ".attn.out_proj.weight", &at.w_out, E, E));
+    TRY(reg_f32(m, p + ".attn.out_proj.bias", &at.b_out, E));
+    TRY(reg_ln(m, p + ".ln_2.", &at.ln_g, &at.ln_b, E));
+    TRY(reg_mat(m, p + ".mlp.c_fc.weight", &ff.w_in, F, E));
+    TRY(reg_f32(m, p + ".mlp.c_fc.bias", &ff.b_in, F));
+    TRY(reg_mat(m, p + ".mlp.c_proj.weight", &ff.w_out, E, F));
+    TRY(reg_f32(m, p + ".mlp.c_proj.bias", &ff.b_out, E));
     return 0;
 }
 
@@ -452,28 +487,31 @@ int build_coca(Captioner* m) {
     TRY(reg_f32(m, "visual.attn_pool.attn.out_proj.bias", &m->b_pool_o, E));
     TRY(reg_f32(m, "visual.ln_post.weight", &m->lnpost_g, E));
     TRY(reg_f32(m, "visual.ln_post.bias", &m->lnpost_b, E));
-    TRY(reg_f32(m, "text.token_embedding.weight", &m->tok_emb, (int64_t)V * E));
+    DecPlan& P = m->dec;
+    P.W = E; P.pre_ln = true; P.kv_tokens = Q; P.kv_first = 1; P.kv_keys = Q - 1; P.tags = &kCocaDecTags;
+    TRY(reg_f32(m, "text.token_embedding.weight", &P.word, (int64_t)V * E));
     TRY(reg_f32(m, "text.positional_embedding", &m->tpos, (int64_t)c.max_pos * E));
-    m->cb.resize(c.t_layers + 2 * c.mm_layers);
-    int nb = 0, ncache = 0;
-    for (int i = 0; i < c.t_layers; ++i) {
-        m->cb[nb].cache = ncache++;
-        TRY(reg_block(m, "text.transformer.resblocks." + std::to_string(i), m->cb[nb], E, F, false, i));
-        ++nb;
-    }
+    P.pos = m->tpos;
+    // unimodal blocks, then per multimodal layer i a self block and the cross block over slot i
+    P.subs.resize(2 * (c.t_layers + 2 * c.mm_layers));
+    int n = 0;
+    float **g = &P.emb_g, **b = &P.emb_b;          // where the next block's ln_1 goes
+    auto block = [&](const std::string& p, int slot) {
+        DecSub &at = P.subs[n], &ff = P.subs[n + 1];
+        n += 2;
+        const int rc = reg_block(m, p, at, ff, g, b, E, F, slot);
+        g = &ff.ln_g; b = &ff.ln_b;
+        return rc;
+    };
+    for (int i = 0; i < c.t_layers; ++i) TRY(block("text.transformer.resblocks." + std::to_string(i), -1));
     for (int i = 0; i < c.mm_layers; ++i) {
-        m->cb[nb].cache = ncache++;
-        TRY(reg_block(m, "text_decoder.resblocks." + std::to_string(i), m->cb[nb], E, F, false, i));
-        ++nb;
-        m->cb[nb].cross_idx = i;
-        TRY(reg_block(m, "text_decoder.cross_attn." + std::to_string(i), m->cb[nb], E, F, true, i));
-        ++nb;
+        TRY(block("text_decoder.resblocks." + std::to_string(i), -1));
+        TRY(block("text_decoder.cross_attn." + std::to_string(i), i));
     }
     TRY(reg_mat(m, "derived.cross_kv.weight", &m->w_ckv, (int64_t)c.mm_layers * 2 * E, E));
     TRY(reg_f32(m, "derived.cross_kv.bias", &m->b_ckv, (int64_t)c.mm_layers * 2 * E));
-    TRY(reg_f32(m, "text_decoder.ln_final.weight", &m->lnf_g, E));
-    TRY(reg_f32(m, "text_decoder.ln_final.bias", &m->lnf_b, E));
-    TRY(reg_mat(m, "derived.vocab.weight", &m->w_cvocab, V, E));
+    TRY(reg_ln(m, "text_decoder.ln_final.", g, b, E));
+    TRY(reg_mat(m, "derived.vocab.weight", &P.w_vocab, V, E));
     // constant vectors for the affine-free LayerNorm that feeds the folded cross-K/V projection
     TRY(walloc(m, (void**)&m->ones, (size_t)E * 4));
     TRY(walloc(m, (void**)&m->zeros, (size_t)E * 4));
@@ -502,6 +540,9 @@ int alloc_image_tower(Captioner* m) {
     return alloc_tower(m, m->vt, Bm * m->NT, m->c.v_hidden, m->c.v_mlp);
 }
 
+// bytes of one slot of the decoder's cross K/V cache for B images: [k|v][image][head][kv_tokens][64]
+size_t cross_slot_bytes(const Captioner* m, size_t B) { return 2 * m->cross_block(B * m->c.t_heads * m->dec.kv_tokens); }
+
 int build_arena_coca(Captioner* m) {
     const CapConfig& c = m->c;
     const size_t Bm = c.max_batch, NT = m->NT, D = c.v_hidden, E = c.embed_dim, e = m->esz, Q = c.pool_queries;
@@ -514,7 +555,7 @@ int build_arena_coca(Captioner* m) {
     TRY(dev_alloc(m, (void**)&m->pool_o, Bm * Q * E * 4));
     TRY(dev_alloc(m, (void**)&m->img_tokens, Bm * Q * E * 4));
     TRY(dev_alloc(m, &m->xhat, Bm * Q * E * e));
-    TRY(dev_alloc(m, &m->cross, (size_t)c.mm_layers * 2 * m->cross_block((size_t)Bm * H * Q)));
+    TRY(dev_alloc(m, &m->cross, (size_t)c.mm_layers * cross_slot_bytes(m, Bm)));
     TRY(dev_alloc(m, (void**)&m->seq, R * Lm * 4));
     TRY(dev_alloc(m, (void**)&m->finished, R * 4));
     TRY(dev_alloc(m, (void**)&m->lens, R * 4));
@@ -529,8 +570,8 @@ int build_arena_coca(Captioner* m) {
     TRY(dev_alloc(m, &m->dh, R * c.t_ffn * e));
     m->ldl = (c.vocab + 3) & ~3;
     TRY(dev_alloc(m, (void**)&m->logits, R * (size_t)m->ldl * 4));
-    m->ccache.resize(c.t_layers + c.mm_layers);
-    for (auto& p : m->ccache) TRY(dev_alloc(m, &p, 2 * R * H * Lm * 64 * e));
+    for (DecSub& u : m->dec.subs)
+        if (u.kind == DEC_SELF) TRY(dev_alloc(m, &u.cache, 2 * R * H * Lm * 64 * e));
     TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, (int)Lm)));      // (a 1-beam search exists: beam groups)
     return 0;
 }
@@ -542,7 +583,7 @@ int build_arena(Captioner* m) {
     TRY(alloc_image_tower(m));
     TRY(dev_alloc(m, (void**)&m->emb_f, M * D * 4));
     TRY(dev_alloc(m, &m->emb_t, M * D * e));
-    TRY(dev_alloc(m, &m->cross, (size_t)c.t_layers * 2 * m->cross_block((size_t)Bm * H * NT)));
+    TRY(dev_alloc(m, &m->cross, (size_t)c.t_layers * cross_slot_bytes(m, Bm)));
     TRY(dev_alloc(m, (void**)&m->seq, R * Lm * 4));
     TRY(dev_alloc(m, (void**)&m->finished, R * 4));
     TRY(dev_alloc(m, (void**)&m->lens, R * 4));
@@ -559,7 +600,8 @@ int build_arena(Captioner* m) {
     TRY(dev_alloc(m, &m->dh, R * c.t_ffn * e));
     m->ldl = (c.vocab + 3) & ~3;
     TRY(dev_alloc(m, (void**)&m->logits, R * (size_t)m->ldl * 4));
-    for (int i = 0; i < c.t_layers; ++i) TRY(dev_alloc(m, &m->tl[i].self_cache, 2 * R * H * Lm * 64 * e));
+    for (DecSub& u : m->dec.subs)
+        if (u.kind == DEC_SELF) TRY(dev_alloc(m, &u.cache, 2 * R * H * Lm * 64 * e));
     TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, (int)Lm)));
     return 0;
 }
@@ -1333,34 +1375,25 @@ int run_coca_pool(Captioner* m, int B, float* tokens_out, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------- decoder
-// The decode state of a contiguous range of images [b0, b0+B) with R = B*K rows; all pointers are pre-offset, row indices
-// inside the kernels are range-local.  (cap_generate decodes the whole batch as one range: row slices of ONE batch on their own
-// streams measured level at 2 and slower at 3-4 - DESIGN.md section 4 - and were removed; whole batches overlap through
-// engine.EnginePool instead.)
+// The decode state of one call: B images, R = B*K rows, the arena's buffers.  (cap_generate decodes the whole batch as one range:
+// row slices of ONE batch on their own streams measured level at 2 and slower at 3-4 - DESIGN.md section 4 - and were removed;
+// whole batches overlap through engine.EnginePool instead.)
 struct Dec {
-    int b0, B, R, Btot;
+    int B, R;
     float *dx, *dy, *logits, *dpart;
     float* dx2;           // the fused paths' second LayerNorm row buffer
-    char *dx_t, *dq, *dctx, *dh;
+    void *dx_t, *dq, *dctx, *dh;
     int *seq, *finished, *lens, *anc;
     void* beam;
-    size_t cache_off;     // byte offset of this slice's [k|v][R][H][Lm][64] block inside every layer's self cache
     RowMap map;           // compacted greedy loop: the open rows (live / count on the device); null pointers = every row
 };
 
-Dec make_slice(Captioner* m, int b0, int B, int Btot, int K, int Lm) {
-    const CapConfig& c = m->c;
-    const size_t T = c.t_hidden, F = c.t_ffn, H = c.t_heads, e = m->esz;
-    const size_t r0 = (size_t)b0 * K;
+Dec make_dec(Captioner* m, int B, int K) {
     Dec d;
-    d.b0 = b0; d.B = B; d.R = B * K; d.Btot = Btot;
-    d.dx2 = m->dx2 + r0 * T;
-    d.dx = m->dx + r0 * T; d.dy = m->dy + r0 * T; d.logits = m->logits + r0 * m->ldl; d.dpart = m->dpart + 12 * r0 * T;
-    d.dx_t = (char*)m->dx_t + r0 * T * e; d.dq = (char*)m->dq + r0 * T * e; d.dctx = (char*)m->dctx + r0 * T * e;
-    d.dh = (char*)m->dh + r0 * F * e;
-    d.seq = m->seq + r0 * Lm; d.finished = m->finished + r0; d.lens = m->lens + r0; d.anc = m->anc + 2 * r0 * Lm;
-    d.beam = m->beam;
-    d.cache_off = 2 * r0 * H * Lm * 64 * e;
+    d.B = B; d.R = B * K;
+    d.dx = m->dx; d.dy = m->dy; d.logits = m->logits; d.dpart = m->dpart; d.dx2 = m->dx2;
+    d.dx_t = m->dx_t; d.dq = m->dq; d.dctx = m->dctx; d.dh = m->dh;
+    d.seq = m->seq; d.finished = m->finished; d.lens = m->lens; d.anc = m->anc; d.beam = m->beam;
     return d;
 }
 
@@ -1411,12 +1444,12 @@ int gemm_rows(Captioner* m, hipStream_t s, const char* tag, const void* A, const
 }
 
 // Decode-sized GEMM whose consumer is a LayerNorm: split K over S blocks per tile (every block's slabs are all in flight
-// at once -> one memory round trip), partial sums to dpart, then the block-per-row kernel: y = sum + bias + resid (-> y_out)
+// at once -> one memory round trip), partial sums to dpart, then the block-per-row kernel: y = sum + bias + d.dx (-> y_out)
 // and LayerNorm(y) -> out_t / out_f.  (Running the consumer inside the GEMM kernel behind arrival counters cost more than the
 // launch it saves - cross-XCD hand-over, DESIGN.md section 4 - and was removed.)
 int gemm_splitk_reduce_ln(Captioner* m, hipStream_t s, const Dec& d, const char* tag, const void* A, const void* W,
                           const float* bias, const float* g, const float* b, float eps, int N, int K, void* out_t,
-                          float* out_f, float* y_out, const float* resid = nullptr) {
+                          float* out_f, float* y_out) {
     const int S = decode_splitk(m, N, K, 4);
     GemmParams p;
     memset(&p, 0, sizeof(p));
@@ -1438,19 +1471,32 @@ int gemm_splitk_reduce_ln(Captioner* m, hipStream_t s, const Dec& d, const char*
     // keeps its round-5 threshold of 512 rows: a dead row costs it one wave's dispatch instead of four, and most steps of a 768-row
     // pass have far fewer live rows than that - same box, `bench.py --lite`, three interleaved pairs, 512 / 832: 6 476 / 6 460, 6 511 /
     // 6 476, 6 525 / 6 491 captions/s (+0.4 %).
-    return launch_reduce_layernorm(m->gdt, d.dpart, S, bias, resid ? resid : d.dx, g, b, eps, out_t, out_f, y_out, d.R, N, s, per_row_block, d.map.n);
+    return launch_reduce_layernorm(m->gdt, d.dpart, S, bias, d.dx, g, b, eps, out_t, out_f, y_out, d.R, N, s, per_row_block, d.map.n);
 }
 
-// x: the fp32 LayerNorm row buffer the consumer adds as its residual and replaces (d.dx, or d.dx2 on the fused paths)
-int gemm_splitk_ln(Captioner* m, hipStream_t s, const Dec& d, const char* tag, const void* A, const void* W,
-                   const float* bias, const float* g, const float* b, int N, int K, float* x = nullptr) {
-    return gemm_splitk_reduce_ln(m, s, d, tag, A, W, bias, g, b, m->c.t_eps, N, K, d.dx_t, x ? x : d.dx, nullptr, x);
+// Cross K/V of cache slot `slot` in a call over B images (the slots are packed for the CALL's B).  by_row: the bases of the slot's k /
+// v blocks and the index of the first head row to attend in them - how a KV16 cache is addressed (head rows inside a block), and
+// how the fused small-batch kernel addresses every cache; otherwise the bases already moved to that row (row0 = 0).
+struct CrossKV { const char *k, *v; size_t row0; };
+CrossKV cross_kv(const Captioner* m, int slot, int B, bool by_row) {
+    const size_t blk = cross_slot_bytes(m, B) / 2, first = m->dec.kv_first;
+    const char* k = (const char*)m->cross + (size_t)slot * 2 * blk + (by_row ? 0 : first * m->kvrow);
+    return {k, k + blk, by_row ? first : 0};
 }
 
-int run_decoder_step(Captioner* m, const Dec& d, const int* tokens, int tok_ld, int t, int K, const int* anc, int Lm,
-                     hipStream_t s) {
+// One KV-cached decoder step on the batch kernels: embedding, the plan's sub-layers, head -> d.logits.  Per sub-layer: the input
+// projection (q|k|v and the cross query as split-K partial sums the attention kernel finishes - one memory round trip per kernel
+// instead of two in the GEMM; fc finished, GELU), the attention, then gemm_splitk_reduce_ln: the output projection and its
+// consumer, which adds the branch to the residual row d.dx and writes the LayerNorm to d.dx_t, the next GEMM's operand - post-LN
+// also to d.dx, pre-LN the sum itself goes to d.dx.  (The reference recomputes CoCa's whole prefix through both text towers
+// every step, coca_model.py:294-303.)
+// tokens [R, tok_ld]: newest token of every row at column t; K rows per image share the image's cross K/V; anc (beams): the
+// ancestry table of the self-attention caches (row r's history position j was written by physical row anc[r][j]).
+int run_step(Captioner* m, const Dec& d, const int* tokens, int tok_ld, int t, int K, const int* anc, int Lm, hipStream_t s) {
     const CapConfig& c = m->c;
-    const int T = c.t_hidden, F = c.t_ffn, H = c.t_heads, R = d.R, NT = m->NT;
+    const DecPlan& P = m->dec;
+    const DecTags& tg = *P.tags;
+    const int W = P.W, F = c.t_ffn, H = c.t_heads, R = d.R;
     const size_t e = m->esz;
     // greedy: a caption that has ended (d.finished, set by greedy_select one step before) is not computed any more.  Compacted
     // (d.map, the merged passes of ~1 000 rows: at that size the projections are no longer a weight stream - 47 % of the decode
@@ -1459,327 +1505,166 @@ int run_decoder_step(Captioner* m, const Dec& d, const int* tokens, int tok_ld, 
     // map.live[c]; row tiles, rows and (row, head) units from *map.n on return at once.  Without a map (beams, per-step logits
     // wanted, forced off): the attention kernels skip ended rows in place and the GEMMs cover every row.
     const bool cm = d.map.n != nullptr;
-    const int* skip = (K == 1 && !cm) ? d.finished : nullptr;
-    TRY(launch_embed(m->gdt, tokens, tok_ld, t, m->word_f32, m->tpos, m->emb_g, m->emb_b, c.t_eps, d.dx_t, d.dx, R, T, s, nullptr, d.map));
-    for (int i = 0; i < c.t_layers; ++i) {
-        const TLayer& L = m->tl[i];
-        char* kc = (char*)L.self_cache + d.cache_off;
-        char* vc = kc + (size_t)R * H * Lm * 64 * e;
-        if (t + 1 <= 32) {
-            // q/k/v projection as split-K partial sums; the attention kernel finishes the reduction, appends k/v to the
-            // cache and attends (one memory round trip per kernel instead of two in the GEMM)
-            int S = 1;
-            TRY(gemm_partial(m, s, "dec_gemm_qkv", d.dx_t, L.w_qkv, d.dpart, R, 3 * T, T, 4, &S, d.map.n));
-            ProfScope ps(m, s, "dec_self_attn", 4.0 * R * H * (t + 1) * 64, 2.0 * R * H * (t + 1) * 64 * e + (double)S * R * 3 * T * 4);
-            TRY(launch_decode_attention(m->dt, nullptr, kc, vc, anc, Lm, 1, Lm, t + 1, d.dctx, R, H, 0, s, d.dpart, S,
-                                        L.b_qkv, 3 * T, 0, 1, m->gdt, skip, 0, 0, d.map));
+    const int* skip = (P.skip_finished && K == 1 && !cm) ? d.finished : nullptr;
+    TRY(launch_embed(m->gdt, tokens, tok_ld, t, P.word, P.pos, P.emb_g, P.emb_b, c.t_eps, d.dx_t, P.pre_ln ? nullptr : d.dx, R, W, s,
+                     P.pre_ln ? d.dx : nullptr, d.map));
+    for (const DecSub& u : P.subs) {
+        const void* A = d.dctx;      // the output projection's operand [R, Kout]
+        int Kout = W, S = 1;
+        if (u.kind == DEC_FFN) {
+            TRY(gemm_rows(m, s, tg.in[DEC_FFN], d.dx_t, u.w_in, d.dh, u.b_in, R, F, W, 1, d.map.n));
+            A = d.dh; Kout = F;
         } else {
-            if (cm) { cap_set_error("run_decoder_step: the compacted loop takes up to 32 positions"); return -1; }   // (run_generate never asks)
-            TRY(gemm(m, s, "dec_gemm_qkv", d.dx_t, T, L.w_qkv, T, d.dq, T, L.b_qkv, nullptr, R, 3 * T, T, 0, 0, EPI_QKVCACHE,
-                     R, H, Lm, t, nullptr, kc));
-            ProfScope ps(m, s, "dec_self_attn", 4.0 * R * H * (t + 1) * 64, 2.0 * R * H * (t + 1) * 64 * e);
-            TRY(launch_decode_attention(m->dt, d.dq, kc, vc, anc, Lm, 1, Lm, t + 1, d.dctx, R, H, 0, s, nullptr, 0, nullptr, 0, 0, 0, m->gdt, skip));
+            DecodeAttn a;
+            memset(&a, 0, sizeof(a));
+            a.out = d.dctx; a.R = R; a.H = H; a.out_dtype = m->gdt; a.skip_rows = skip; a.map = d.map;
+            if (u.kind == DEC_SELF) {
+                a.kbase = u.cache; a.vbase = (char*)u.cache + (size_t)R * H * Lm * 64 * e;
+                a.anc = anc; a.anc_ld = Lm; a.rows_per_kv = 1; a.kv_ld = Lm; a.n_keys = t + 1;
+            } else {
+                // beam-shared cross K/V; a KV16 cache is addressed by row index: the kernel gets the block bases and the first row
+                const CrossKV kv = cross_kv(m, u.slot, d.B, m->kv16);
+                a.kbase = kv.k; a.vbase = kv.v; a.kv16 = m->kv16 ? 1 : 0; a.kv_row0 = kv.row0;
+                a.rows_per_kv = K; a.kv_ld = P.kv_tokens; a.n_keys = P.kv_keys;
+            }
+            const int self = u.kind == DEC_SELF, Nin = self ? 3 * W : W;
+            double bytes = self ? 2.0 * R * H * a.n_keys * 64 * e : 2.0 * d.B * H * a.n_keys * m->kvrow;
+            // (positions beyond 32: BLIP's un-fused branch.  CoCa has none: its step fails the attention launcher's 32-position check)
+            if (!self || t + 1 <= 32 || P.pre_ln) {
+                TRY(gemm_partial(m, s, tg.in[u.kind], d.dx_t, u.w_in, d.dpart, R, Nin, W, 4, &S, d.map.n));
+                a.q_part = d.dpart; a.q_S = S; a.q_bias = u.b_in; a.q_ld = Nin; a.append_kv = self;   // self: k / v finished and appended too
+                if (self && !P.pre_ln) bytes += (double)S * R * Nin * 4;     // (the figure CoCa reports has never counted the partial sums)
+            } else {
+                if (cm) { cap_set_error("run_step: the compacted loop takes up to 32 positions"); return -1; }   // (run_generate never asks)
+                TRY(gemm(m, s, tg.in[DEC_SELF], d.dx_t, W, u.w_in, W, d.dq, W, u.b_in, nullptr, R, 3 * W, W, 0, 0, EPI_QKVCACHE,
+                         R, H, Lm, t, nullptr, u.cache));
+                a.q = d.dq;
+            }
+            ProfScope ps(m, s, tg.attn[u.kind], 4.0 * R * H * a.n_keys * 64, bytes);
+            TRY(launch_decode_attention(m->dt, a, s));
         }
-        TRY(gemm_splitk_ln(m, s, d, "dec_gemm_so", d.dctx, L.w_so, L.b_so, L.so_g, L.so_b, T, T));
-        {
-            int S = 1;
-            TRY(gemm_partial(m, s, "dec_gemm_cq", d.dx_t, L.w_cq, d.dpart, R, T, T, 4, &S, d.map.n));
-            // beam-shared cross K/V of layer i: [k|v][image (whole batch)][head][token][64]; this slice starts at image b0.  A KV16
-            // cache is addressed by row index inside the layer's k / v block: the kernel gets the block bases and the first row
-            const size_t blk = m->cross_block((size_t)d.Btot * H * NT), row0 = (size_t)d.b0 * H * NT;
-            const char* ck = (char*)m->cross + ((size_t)i * 2 + 0) * blk + (m->kv16 ? 0 : row0 * m->kvrow);
-            const char* cv = (char*)m->cross + ((size_t)i * 2 + 1) * blk + (m->kv16 ? 0 : row0 * m->kvrow);
-            ProfScope ps(m, s, "dec_cross_attn", 4.0 * R * H * NT * 64, 2.0 * d.B * H * NT * m->kvrow);
-            TRY(launch_decode_attention(m->dt, nullptr, ck, cv, nullptr, 0, K, NT, NT, d.dctx, R, H, 0, s, d.dpart, S, L.b_cq,
-                                        T, 0, 0, m->gdt, skip, m->kv16 ? 1 : 0, m->kv16 ? row0 : 0, d.map));
-        }
-        TRY(gemm_splitk_ln(m, s, d, "dec_gemm_co", d.dctx, L.w_co, L.b_co, L.co_g, L.co_b, T, T));
-        TRY(gemm_rows(m, s, "dec_gemm_f1", d.dx_t, L.w_f1, d.dh, L.b_f1, R, F, T, 1, d.map.n));
-        TRY(gemm_splitk_ln(m, s, d, "dec_gemm_f2", d.dh, L.w_f2, L.b_f2, L.f_g, L.f_b, T, F));
+        TRY(gemm_splitk_reduce_ln(m, s, d, tg.out[u.kind], A, u.w_out, u.b_out, u.ln_g, u.ln_b, c.t_eps, W, Kout, d.dx_t,
+                                  P.pre_ln ? nullptr : d.dx, P.pre_ln ? d.dx : nullptr));
     }
-    TRY(gemm(m, s, "dec_gemm_tr", d.dx_t, T, m->w_tr, T, d.dy, T, m->b_tr, nullptr, R, T, T, 1, 1));
-    {
-        ProfScope ps(m, s, "dec_layernorm", 0, (double)R * T * (8 + e));
-        TRY(launch_layernorm(m->gdt, d.dy, T, m->tr_g, m->tr_b, c.t_eps, d.dx_t, d.dx, R, T, s));
+    if (P.w_tr) {
+        TRY(gemm(m, s, tg.tr, d.dx_t, W, P.w_tr, W, d.dy, W, P.b_tr, nullptr, R, W, W, 1, 1));
+        ProfScope ps(m, s, tg.ln, 0, (double)R * W * (8 + e));
+        TRY(launch_layernorm(m->gdt, d.dy, W, P.tr_g, P.tr_b, c.t_eps, d.dx_t, d.dx, R, W, s));
     }
-    TRY(gemm(m, s, "dec_gemm_vocab", d.dx_t, T, m->word_t, T, d.logits, m->ldl, m->b_vocab, nullptr, R, c.vocab, T, 0, 1));
-    return 0;
+    return gemm(m, s, tg.vocab, d.dx_t, W, P.w_vocab, W, d.logits, m->ldl, P.b_vocab, nullptr, R, c.vocab, W, 0, 1);
 }
 
-
 // ---------------------------------------------------------------------------------------------- small-batch decoder step
-// Up to SMALL_MAX_ROWS rows (the reference calls the captioner with ONE crop, BASELINE config 1 with 8): the same step as
-// run_decoder_step in 6 launches per layer instead of 11 - every split-K consumer / LayerNorm and the self-attention run in the
-// prologue of the kernel that needs their result, the cross-attention block (LayerNorm, query projection, attention) is one
-// kernel per (row, head) - decode_small.hip.  The sums are those of the batch kernels (same K-slice plan, same chains, same
-// LayerNorm / attention arithmetic): logits and tokens have the same bits on either path (tests/test_small_decode_gpu.py).
-// The fp32 LayerNorm rows (the batch path's dx) alternate between d.dx and d.dx2: the one workgroup that writes a row never
-// writes the buffer the others are still reading.
+// Up to SMALL_MAX_ROWS rows (the reference calls the captioners with ONE crop - coca.py:27-33 -, BASELINE config 1 with 8): the
+// same step as run_step in 2 launches per sub-layer (BLIP 6 per layer instead of 11, CoCa 4 per block instead of 7) - every
+// split-K consumer / LayerNorm and the self-attention run in the prologue of the kernel that needs their result, the first half
+// of a cross sub-layer (LayerNorm, query projection, attention) is one kernel per (row, head) - decode_small.hip.  The sums are
+// those of the batch kernels (same K-slice plan, same chains, same LayerNorm / attention arithmetic): logits and tokens have the
+// same bits on either path (tests/test_small_decode_gpu.py).  The fp32 residual rows (the batch path's dx) alternate between d.dx
+// and d.dx2: the one workgroup that writes a row never writes the buffer the others are still reading.  Post-LN the row kept is
+// the consumer's LayerNorm, pre-LN its SUM (SmallLN::x_is_sum), the LayerNorm then only feeds the GEMM.
 bool small_path_takes(const Captioner* m, const Dec& d, int t) {
     const CapConfig& c = m->c;
     if (m->gdt == CAP_DT_F32 || (c.arch != CAP_ARCH_BLIP && c.arch != CAP_ARCH_COCA) || !d.dx2) return false;
     if (d.R > SMALL_MAX_ROWS || t + 1 > 32) return false;
-    const int T = c.arch == CAP_ARCH_COCA ? m->E : c.t_hidden, F = c.t_ffn, slab = m->gdt == CAP_DT_BF16 ? 64 : 32;
+    const int T = m->dec.W, F = c.t_ffn, slab = m->gdt == CAP_DT_BF16 ? 64 : 32;
     if (T > 1024 || T != c.t_heads * 64 || T % 16 != 0 || F % 16 != 0 || T % slab != 0 || F % slab != 0) return false;
     // q|k|v partial sums sit beside the [<= 4][R][T] slabs of the other GEMMs in dpart (12 R T floats): at most 2 K slices
     return decode_splitk(m, 3 * T, T, 4) <= 2;
 }
 
-int run_decoder_step_small(Captioner* m, const Dec& d, const int* tokens, int tok_ld, int t, int K, const int* anc, int Lm,
-                           hipStream_t s) {
+int run_step_small(Captioner* m, const Dec& d, const int* tokens, int tok_ld, int t, int K, const int* anc, int Lm, hipStream_t s) {
     const CapConfig& c = m->c;
-    const int T = c.t_hidden, F = c.t_ffn, H = c.t_heads, R = d.R, NT = m->NT;
+    const DecPlan& P = m->dec;
+    const DecTags& tg = *P.tags;
+    const int W = P.W, F = c.t_ffn, H = c.t_heads, R = d.R, V = c.vocab, nk = P.kv_keys;
     const size_t e = m->esz;
-    const int* skip = K == 1 ? d.finished : nullptr;
+    const int* skip = (P.skip_finished && K == 1) ? d.finished : nullptr;
     float* xb[2] = {d.dx, d.dx2};
-    int cur = 0;                                   // xb[cur]: the LayerNorm row the next consumer adds as its residual
-    float* qkvp = d.dpart + (size_t)4 * R * T;     // q|k|v partial sums, beside the [<= 4][R][T] slabs of the other GEMMs
-    const int S_qkv = decode_splitk(m, 3 * T, T, 4), S_tt = decode_splitk(m, T, T, 4), S_f2 = decode_splitk(m, T, F, 4);
+    int cur = 0;                                   // xb[cur]: the row the next consumer adds as its residual
+    float* qkvp = d.dpart + (size_t)4 * R * W;     // q|k|v partial sums, beside the [<= 4][R][W] slabs of the other GEMMs
+    const int S_qkv = decode_splitk(m, 3 * W, W, 4), S_ww = decode_splitk(m, W, W, 4), S_f2 = decode_splitk(m, W, F, 4);
     const int kv_kind = m->kv16 ? SMALL_KV_KV16 : (m->dt == CAP_DT_BF16 ? SMALL_KV_BF16 : SMALL_KV_F32);
-    TRY(launch_embed(m->gdt, tokens, tok_ld, t, m->word_f32, m->tpos, m->emb_g, m->emb_b, c.t_eps, d.dx_t, xb[0], R, T, s));
-    SmallLN pend;                                  // the consumer the next kernel's prologue runs
+    TRY(launch_embed(m->gdt, tokens, tok_ld, t, P.word, P.pos, P.emb_g, P.emb_b, c.t_eps, d.dx_t, P.pre_ln ? nullptr : xb[0], R, W, s,
+                     P.pre_ln ? xb[0] : nullptr));
+    SmallLN pend;                                  // the consumer of the last sub-layer: the next kernel's prologue runs it
     memset(&pend, 0, sizeof(pend));
-    auto base = [&](const void* W, int N, int Kk, int S, int pro, int epi) {
+    auto base = [&](const void* Wt, int N, int Kk, int S, int pro, int epi) {
         SmallGemm g;
         memset(&g, 0, sizeof(g));
-        g.W = W; g.R = R; g.N = N; g.K = Kk; g.S = S; g.pro = pro; g.epi = epi; g.nchain = 4;
+        g.W = Wt; g.R = R; g.N = N; g.K = Kk; g.S = S; g.pro = pro; g.epi = epi; g.nchain = 4;
         return g;
     };
-    auto consume = [&](SmallLN ln, bool keep) {    // bind the pending consumer to the current residual row / the other buffer
+    auto consume = [&](bool keep) {                // bind the pending consumer to the current residual row / the other buffer
+        SmallLN ln = pend;
         ln.resid = xb[cur];
         ln.x_out = keep ? xb[cur ^ 1] : nullptr;
         if (keep) cur ^= 1;
         return ln;
     };
-    for (int i = 0; i < c.t_layers; ++i) {
-        const TLayer& L = m->tl[i];
-        char* kc = (char*)L.self_cache + d.cache_off;
-        char* vc = kc + (size_t)R * H * Lm * 64 * e;
-        {
-            SmallGemm g = base(L.w_qkv, 3 * T, T, S_qkv, i == 0 ? SMALL_PRO_GLOBAL : SMALL_PRO_LN, SMALL_EPI_PARTIAL);
-            if (i == 0) g.A = d.dx_t; else g.ln = consume(pend, true);
+    auto launch = [&](const char* tag, const SmallGemm& g, double flops, double bytes) {
+        ProfScope ps(m, s, tag, flops, bytes);
+        return launch_small_gemm(m->gdt, g, s);
+    };
+    bool first = true;                             // the first kernel reads the embedding's LayerNorm from d.dx_t
+    for (const DecSub& u : P.subs) {
+        const char *t_in = tg.s_in[u.kind], *t_out = tg.s_out[u.kind];
+        int S_out = S_ww;
+        if (u.kind == DEC_SELF) {
+            SmallGemm g = base(u.w_in, 3 * W, W, S_qkv, first ? SMALL_PRO_GLOBAL : SMALL_PRO_LN, SMALL_EPI_PARTIAL);
+            if (first) g.A = d.dx_t; else g.ln = consume(true);
             g.out_part = qkvp;
-            ProfScope ps(m, s, "dec_small_qkv", 2.0 * R * 3 * T * T, ((double)R * T + 3.0 * T * T) * e + (double)S_qkv * R * 3 * T * 4);
-            TRY(launch_small_gemm(m->gdt, g, s));
-        }
-        {
-            SmallGemm g = base(L.w_so, T, T, S_tt, SMALL_PRO_SELFATTN, SMALL_EPI_PARTIAL);
-            g.sa.qkv_part = qkvp; g.sa.qkv_bias = L.b_qkv; g.sa.qkv_S = S_qkv; g.sa.kc = kc; g.sa.vc = vc; g.sa.anc = anc; g.sa.anc_ld = Lm;
+            TRY(launch(t_in, g, 2.0 * R * 3 * W * W, ((double)R * W + 3.0 * W * W) * e + (double)S_qkv * R * 3 * W * 4));
+            g = base(u.w_out, W, W, S_ww, SMALL_PRO_SELFATTN, SMALL_EPI_PARTIAL);
+            g.sa.qkv_part = qkvp; g.sa.qkv_bias = u.b_in; g.sa.qkv_S = S_qkv; g.sa.kc = u.cache;
+            g.sa.vc = (char*)u.cache + (size_t)R * H * Lm * 64 * e; g.sa.anc = anc; g.sa.anc_ld = Lm;
             g.sa.kv_ld = Lm; g.sa.n_keys = t + 1; g.sa.H = H; g.sa.skip = skip;
             g.out_part = d.dpart;
-            ProfScope ps(m, s, "dec_small_so", 2.0 * R * T * T + 4.0 * R * H * (t + 1) * 64, ((double)R * T + (double)T * T) * e + (double)S_tt * R * T * 4);
-            TRY(launch_small_gemm(m->gdt, g, s));
-        }
-        {
+            TRY(launch(t_out, g, 2.0 * R * W * W + 4.0 * R * H * (t + 1) * 64, ((double)R * W + (double)W * W) * e + (double)S_ww * R * W * 4));
+        } else if (u.kind == DEC_CROSS) {
             SmallCross x;
             memset(&x, 0, sizeof(x));
-            x.W = L.w_cq; x.bias = L.b_cq; x.R = R; x.D = T; x.H = H; x.S = S_tt;
-            SmallLN ln;
-            memset(&ln, 0, sizeof(ln));
-            ln.part = d.dpart; ln.S = S_tt; ln.bias = L.b_so; ln.gamma = L.so_g; ln.beta = L.so_b; ln.eps = c.t_eps;
-            x.ln = consume(ln, true);
-            const size_t blk = m->cross_block((size_t)d.Btot * H * NT);
-            x.kbase = (char*)m->cross + ((size_t)i * 2 + 0) * blk;
-            x.vbase = (char*)m->cross + ((size_t)i * 2 + 1) * blk;
-            x.kv_row0 = (size_t)d.b0 * H * NT;
-            x.rows_per_kv = K; x.kv_ld = NT; x.n_keys = NT; x.kv_kind = kv_kind; x.skip = skip; x.out = d.dctx;
-            ProfScope ps(m, s, "dec_small_cross", 2.0 * R * T * T + 4.0 * R * H * NT * 64, (double)T * T * e + 2.0 * R * H * NT * m->kvrow);
-            TRY(launch_small_cross(m->gdt, x, s));
-        }
-        {
-            SmallGemm g = base(L.w_co, T, T, S_tt, SMALL_PRO_GLOBAL, SMALL_EPI_PARTIAL);
-            g.A = d.dctx; g.out_part = d.dpart;
-            ProfScope ps(m, s, "dec_small_co", 2.0 * R * T * T, ((double)R * T + (double)T * T) * e + (double)S_tt * R * T * 4);
-            TRY(launch_small_gemm(m->gdt, g, s));
-        }
-        {
-            SmallGemm g = base(L.w_f1, F, T, 1, SMALL_PRO_LN, SMALL_EPI_ACT_T);
-            SmallLN ln;
-            memset(&ln, 0, sizeof(ln));
-            ln.part = d.dpart; ln.S = S_tt; ln.bias = L.b_co; ln.gamma = L.co_g; ln.beta = L.co_b; ln.eps = c.t_eps;
-            g.ln = consume(ln, true);
-            g.bias = L.b_f1; g.act = 1; g.out = d.dh; g.ldc = F;
-            ProfScope ps(m, s, "dec_small_f1", 2.0 * R * F * T, ((double)R * T + (double)F * T + (double)R * F) * e);
-            TRY(launch_small_gemm(m->gdt, g, s));
-        }
-        {
-            SmallGemm g = base(L.w_f2, T, F, S_f2, SMALL_PRO_GLOBAL, SMALL_EPI_PARTIAL);
-            g.A = d.dh; g.out_part = d.dpart;
-            ProfScope ps(m, s, "dec_small_f2", 2.0 * R * T * F, ((double)R * F + (double)T * F) * e + (double)S_f2 * R * T * 4);
-            TRY(launch_small_gemm(m->gdt, g, s));
-        }
-        memset(&pend, 0, sizeof(pend));
-        pend.part = d.dpart; pend.S = S_f2; pend.bias = L.b_f2; pend.gamma = L.f_g; pend.beta = L.f_b; pend.eps = c.t_eps;
-    }
-    {   // prediction head transform: LayerNorm of the last layer's FFN in the prologue, bias + GELU -> fp32
-        SmallGemm g = base(m->w_tr, T, T, 1, SMALL_PRO_LN, SMALL_EPI_ACT_F32);
-        g.nchain = 1;
-        g.ln = consume(pend, false);
-        g.bias = m->b_tr; g.act = 1; g.out = d.dy; g.ldc = T;
-        ProfScope ps(m, s, "dec_small_tr", 2.0 * R * T * T, ((double)R * T + (double)T * T) * e + (double)R * T * 4);
-        TRY(launch_small_gemm(m->gdt, g, s));
-    }
-    {   // vocabulary GEMM with the transform's LayerNorm in the prologue
-        SmallGemm g = base(m->word_t, c.vocab, T, 1, SMALL_PRO_LN, SMALL_EPI_ACT_F32);
-        g.nchain = 1;
-        memset(&g.ln, 0, sizeof(g.ln));
-        g.ln.part = d.dy; g.ln.S = 1; g.ln.gamma = m->tr_g; g.ln.beta = m->tr_b; g.ln.eps = c.t_eps;
-        g.bias = m->b_vocab; g.act = 0; g.out = d.logits; g.ldc = m->ldl;
-        ProfScope ps(m, s, "dec_small_vocab", 2.0 * R * c.vocab * T, ((double)R * T + (double)c.vocab * T) * e + (double)R * c.vocab * 4);
-        TRY(launch_small_gemm(m->gdt, g, s));
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------- CoCa decoder
-// One KV-cached step through the unimodal text tower (t_layers causal blocks) and the multimodal decoder (mm_layers x
-// [causal self-attention block, cross-attention block]).  Every block is pre-LN: the residual stream x stays fp32 in
-// d.dx and each split-K consumer kernel both adds the branch to x and emits LayerNorm_next(x) as the next GEMM operand.
-// The reference recomputes the whole prefix through both towers every step (coca_model.py:294-303).
-// tokens [R, tok_ld]: newest token of every row at column t; K rows per image share the image's cross K/V; anc (beams): the
-// ancestry table of the self-attention caches (row r's history position j was written by physical row anc[r][j]).
-int run_coca_step(Captioner* m, const Dec& d, const int* tokens, int tok_ld, int t, int K, const int* anc, int Lm, hipStream_t s) {
-    const CapConfig& c = m->c;
-    const int E = m->E, F = c.t_ffn, H = c.t_heads, R = d.R, Q = m->Q;
-    const size_t e = m->esz;
-    const int nb = (int)m->cb.size();
-    // x = tok_emb[token] + pos[t]  (raw sum to d.dx), ln = LayerNorm_{block0.ln_1}(x)
-    TRY(launch_embed(m->gdt, tokens, tok_ld, t, m->tok_emb, m->tpos, m->cb[0].ln1_g, m->cb[0].ln1_b, c.t_eps, d.dx_t, nullptr, R, E, s,
-                     d.dx));
-    for (int bi = 0; bi < nb; ++bi) {
-        const CBlock& b = m->cb[bi];
-        const float* next_g = bi + 1 < nb ? m->cb[bi + 1].ln1_g : m->lnf_g;
-        const float* next_b = bi + 1 < nb ? m->cb[bi + 1].ln1_b : m->lnf_b;
-        int S = 1;
-        if (!b.cross) {
-            char* kc = (char*)m->ccache[b.cache] + d.cache_off;
-            char* vc = kc + (size_t)R * H * Lm * 64 * e;
-            TRY(gemm_partial(m, s, "coca_gemm_qkv", d.dx_t, b.w_in, d.dpart, R, 3 * E, E, 4, &S));
-            ProfScope ps(m, s, "coca_self_attn", 4.0 * R * H * (t + 1) * 64, 2.0 * R * H * (t + 1) * 64 * e);
-            TRY(launch_decode_attention(m->dt, nullptr, kc, vc, anc, Lm, 1, Lm, t + 1, d.dctx, R, H, 0, s, d.dpart, S, b.b_in,
-                                        3 * E, 0, 1, m->gdt));
-        } else {
-            TRY(gemm_partial(m, s, "coca_gemm_cq", d.dx_t, b.w_in, d.dpart, R, E, E, 4, &S));
-            // cross K/V of multimodal layer i: [k|v][image][head][Q tokens][64]; token 0 (the pooled token) is skipped
-            const size_t blk = m->cross_block((size_t)d.Btot * H * Q), row0 = (size_t)d.b0 * H * Q + 1;
-            const char* ck = (char*)m->cross + ((size_t)b.cross_idx * 2 + 0) * blk + (m->kv16 ? 0 : row0 * m->kvrow);
-            const char* cv = (char*)m->cross + ((size_t)b.cross_idx * 2 + 1) * blk + (m->kv16 ? 0 : row0 * m->kvrow);
-            ProfScope ps(m, s, "coca_cross_attn", 4.0 * R * H * (Q - 1) * 64, 2.0 * d.B * H * (Q - 1) * m->kvrow);
-            TRY(launch_decode_attention(m->dt, nullptr, ck, cv, nullptr, 0, K, Q, Q - 1, d.dctx, R, H, 0, s, d.dpart, S, b.b_in, E,
-                                        0, 0, m->gdt, nullptr, m->kv16 ? 1 : 0, m->kv16 ? row0 : 0));
-        }
-        // x += out_proj(ctx) ; ln = LayerNorm_2(x)
-        TRY(gemm_splitk_reduce_ln(m, s, d, "coca_gemm_o", d.dctx, b.w_o, b.b_o, b.ln2_g, b.ln2_b, c.t_eps, E, E, d.dx_t, nullptr, d.dx));
-        // x += c_proj(gelu(c_fc(ln))) ; ln = LayerNorm of the next block (or ln_final)
-        TRY(gemm_rows(m, s, "coca_gemm_fc", d.dx_t, b.w_fc, d.dh, b.b_fc, R, F, E, 1));
-        TRY(gemm_splitk_reduce_ln(m, s, d, "coca_gemm_pr", d.dh, b.w_pr, b.b_pr, next_g, next_b, c.t_eps, E, F, d.dx_t, nullptr, d.dx));
-    }
-    TRY(gemm(m, s, "coca_gemm_vocab", d.dx_t, E, m->w_cvocab, E, d.logits, m->ldl, nullptr, nullptr, R, c.vocab, E, 0, 1));
-    return 0;
-}
-
-
-// The same step for up to SMALL_MAX_ROWS rows (the reference calls CoCa with ONE crop, coca.py:27-33): 4 launches per block instead
-// of 7 - [consumer + LayerNorm] q|k|v GEMM, [self-attention] output projection, [consumer + LayerNorm] c_fc, c_proj; a
-// cross-attention block starts with the (row, head) kernel (LayerNorm, query columns, attention) instead of the first two.  CoCa
-// is pre-LN: the consumer's SUM is the new residual row (SmallLN::x_is_sum), its LayerNorm only feeds the next GEMM.  Same sums
-// as run_coca_step (tests/test_small_decode_gpu.py).
-int run_coca_step_small(Captioner* m, const Dec& d, const int* tokens, int tok_ld, int t, int K, const int* anc, int Lm, hipStream_t s) {
-    const CapConfig& c = m->c;
-    const int E = m->E, F = c.t_ffn, H = c.t_heads, R = d.R, Q = m->Q;
-    const size_t e = m->esz;
-    const int nb = (int)m->cb.size();
-    float* xb[2] = {d.dx, d.dx2};
-    int cur = 0;
-    float* qkvp = d.dpart + (size_t)4 * R * E;
-    const int S_qkv = decode_splitk(m, 3 * E, E, 4), S_ee = decode_splitk(m, E, E, 4), S_pr = decode_splitk(m, E, F, 4);
-    const int kv_kind = m->kv16 ? SMALL_KV_KV16 : (m->dt == CAP_DT_BF16 ? SMALL_KV_BF16 : SMALL_KV_F32);
-    TRY(launch_embed(m->gdt, tokens, tok_ld, t, m->tok_emb, m->tpos, m->cb[0].ln1_g, m->cb[0].ln1_b, c.t_eps, d.dx_t, nullptr, R, E, s,
-                     xb[0]));
-    SmallLN pend;
-    memset(&pend, 0, sizeof(pend));
-    auto base = [&](const void* W, int N, int Kk, int S, int pro, int epi) {
-        SmallGemm g;
-        memset(&g, 0, sizeof(g));
-        g.W = W; g.R = R; g.N = N; g.K = Kk; g.S = S; g.pro = pro; g.epi = epi; g.nchain = 4;
-        return g;
-    };
-    auto consume = [&](SmallLN ln, const float* gam, const float* bet, bool keep) {
-        ln.gamma = gam; ln.beta = bet; ln.eps = c.t_eps; ln.x_is_sum = 1;
-        ln.resid = xb[cur];
-        ln.x_out = keep ? xb[cur ^ 1] : nullptr;
-        if (keep) cur ^= 1;
-        return ln;
-    };
-    for (int bi = 0; bi < nb; ++bi) {
-        const CBlock& b = m->cb[bi];
-        if (!b.cross) {
-            char* kc = (char*)m->ccache[b.cache] + d.cache_off;
-            char* vc = kc + (size_t)R * H * Lm * 64 * e;
+            x.W = u.w_in; x.bias = u.b_in; x.R = R; x.D = W; x.H = H; x.S = S_ww;
+            x.ln = consume(true);
+            const CrossKV kv = cross_kv(m, u.slot, d.B, true);
+            x.kbase = kv.k; x.vbase = kv.v; x.kv_row0 = kv.row0;
+            x.rows_per_kv = K; x.kv_ld = P.kv_tokens; x.n_keys = nk; x.kv_kind = kv_kind; x.skip = skip; x.out = d.dctx;
             {
-                SmallGemm g = base(b.w_in, 3 * E, E, S_qkv, bi == 0 ? SMALL_PRO_GLOBAL : SMALL_PRO_LN, SMALL_EPI_PARTIAL);
-                if (bi == 0) g.A = d.dx_t; else g.ln = consume(pend, b.ln1_g, b.ln1_b, true);
-                g.out_part = qkvp;
-                ProfScope ps(m, s, "coca_small_qkv", 2.0 * R * 3 * E * E, ((double)R * E + 3.0 * E * E) * e + (double)S_qkv * R * 3 * E * 4);
-                TRY(launch_small_gemm(m->gdt, g, s));
-            }
-            {
-                SmallGemm g = base(b.w_o, E, E, S_ee, SMALL_PRO_SELFATTN, SMALL_EPI_PARTIAL);
-                g.sa.qkv_part = qkvp; g.sa.qkv_bias = b.b_in; g.sa.qkv_S = S_qkv; g.sa.kc = kc; g.sa.vc = vc; g.sa.anc = anc; g.sa.anc_ld = Lm;
-                g.sa.kv_ld = Lm; g.sa.n_keys = t + 1; g.sa.H = H; g.sa.skip = nullptr;
-                g.out_part = d.dpart;
-                ProfScope ps(m, s, "coca_small_o", 2.0 * R * E * E + 4.0 * R * H * (t + 1) * 64, ((double)R * E + (double)E * E) * e + (double)S_ee * R * E * 4);
-                TRY(launch_small_gemm(m->gdt, g, s));
-            }
-        } else {
-            {
-                SmallCross x;
-                memset(&x, 0, sizeof(x));
-                x.W = b.w_in; x.bias = b.b_in; x.R = R; x.D = E; x.H = H; x.S = S_ee;
-                x.ln = consume(pend, b.ln1_g, b.ln1_b, true);
-                const size_t blk = m->cross_block((size_t)d.Btot * H * Q);
-                x.kbase = (char*)m->cross + ((size_t)b.cross_idx * 2 + 0) * blk;
-                x.vbase = (char*)m->cross + ((size_t)b.cross_idx * 2 + 1) * blk;
-                x.kv_row0 = (size_t)d.b0 * H * Q + 1;                 // token 0 (the pooled token) is skipped
-                x.rows_per_kv = K; x.kv_ld = Q; x.n_keys = Q - 1; x.kv_kind = kv_kind; x.skip = nullptr; x.out = d.dctx;
-                ProfScope ps(m, s, "coca_small_cross", 2.0 * R * E * E + 4.0 * R * H * (Q - 1) * 64, (double)E * E * e + 2.0 * R * H * (Q - 1) * m->kvrow);
+                ProfScope ps(m, s, t_in, 2.0 * R * W * W + 4.0 * R * H * nk * 64, (double)W * W * e + 2.0 * R * H * nk * m->kvrow);
                 TRY(launch_small_cross(m->gdt, x, s));
             }
-            {
-                SmallGemm g = base(b.w_o, E, E, S_ee, SMALL_PRO_GLOBAL, SMALL_EPI_PARTIAL);
-                g.A = d.dctx; g.out_part = d.dpart;
-                ProfScope ps(m, s, "coca_small_o", 2.0 * R * E * E, ((double)R * E + (double)E * E) * e + (double)S_ee * R * E * 4);
-                TRY(launch_small_gemm(m->gdt, g, s));
-            }
-        }
-        {
-            SmallGemm g = base(b.w_fc, F, E, 1, SMALL_PRO_LN, SMALL_EPI_ACT_T);
-            SmallLN ln;
-            memset(&ln, 0, sizeof(ln));
-            ln.part = d.dpart; ln.S = S_ee; ln.bias = b.b_o;
-            g.ln = consume(ln, b.ln2_g, b.ln2_b, true);
-            g.bias = b.b_fc; g.act = 1; g.out = d.dh; g.ldc = F;
-            ProfScope ps(m, s, "coca_small_fc", 2.0 * R * F * E, ((double)R * E + (double)F * E + (double)R * F) * e);
-            TRY(launch_small_gemm(m->gdt, g, s));
-        }
-        {
-            SmallGemm g = base(b.w_pr, E, F, S_pr, SMALL_PRO_GLOBAL, SMALL_EPI_PARTIAL);
+            SmallGemm g = base(u.w_out, W, W, S_ww, SMALL_PRO_GLOBAL, SMALL_EPI_PARTIAL);
+            g.A = d.dctx; g.out_part = d.dpart;
+            TRY(launch(t_out, g, 2.0 * R * W * W, ((double)R * W + (double)W * W) * e + (double)S_ww * R * W * 4));
+        } else {
+            SmallGemm g = base(u.w_in, F, W, 1, SMALL_PRO_LN, SMALL_EPI_ACT_T);
+            g.ln = consume(true);
+            g.bias = u.b_in; g.act = 1; g.out = d.dh; g.ldc = F;
+            TRY(launch(t_in, g, 2.0 * R * F * W, ((double)R * W + (double)F * W + (double)R * F) * e));
+            g = base(u.w_out, W, F, S_f2, SMALL_PRO_GLOBAL, SMALL_EPI_PARTIAL);
             g.A = d.dh; g.out_part = d.dpart;
-            ProfScope ps(m, s, "coca_small_pr", 2.0 * R * E * F, ((double)R * F + (double)E * F) * e + (double)S_pr * R * E * 4);
-            TRY(launch_small_gemm(m->gdt, g, s));
+            TRY(launch(t_out, g, 2.0 * R * W * F, ((double)R * F + (double)W * F) * e + (double)S_f2 * R * W * 4));
+            S_out = S_f2;
         }
         memset(&pend, 0, sizeof(pend));
-        pend.part = d.dpart; pend.S = S_pr; pend.bias = b.b_pr;
+        pend.part = d.dpart; pend.S = S_out; pend.bias = u.b_out; pend.gamma = u.ln_g; pend.beta = u.ln_b; pend.eps = c.t_eps;
+        pend.x_is_sum = P.pre_ln ? 1 : 0;
+        first = false;
     }
-    {
-        SmallGemm g = base(m->w_cvocab, c.vocab, E, 1, SMALL_PRO_LN, SMALL_EPI_ACT_F32);
+    if (P.w_tr) {   // prediction head transform: LayerNorm of the last FFN in the prologue, bias + GELU -> fp32
+        SmallGemm g = base(P.w_tr, W, W, 1, SMALL_PRO_LN, SMALL_EPI_ACT_F32);
         g.nchain = 1;
-        g.ln = consume(pend, m->lnf_g, m->lnf_b, false);
-        g.bias = nullptr; g.act = 0; g.out = d.logits; g.ldc = m->ldl;
-        ProfScope ps(m, s, "coca_small_vocab", 2.0 * R * c.vocab * E, ((double)R * E + (double)c.vocab * E) * e + (double)R * c.vocab * 4);
-        TRY(launch_small_gemm(m->gdt, g, s));
+        g.ln = consume(false);
+        g.bias = P.b_tr; g.act = 1; g.out = d.dy; g.ldc = W;
+        TRY(launch(tg.s_tr, g, 2.0 * R * W * W, ((double)R * W + (double)W * W) * e + (double)R * W * 4));
     }
-    return 0;
+    // vocabulary GEMM with the last LayerNorm in the prologue: the transform's over d.dy, else the pending consumer's (ln_final)
+    SmallGemm g = base(P.w_vocab, V, W, 1, SMALL_PRO_LN, SMALL_EPI_ACT_F32);
+    g.nchain = 1;
+    if (P.w_tr) { g.ln.part = d.dy; g.ln.S = 1; g.ln.gamma = P.tr_g; g.ln.beta = P.tr_b; g.ln.eps = c.t_eps; }
+    else g.ln = consume(false);
+    g.bias = P.b_vocab; g.act = 0; g.out = d.logits; g.ldc = m->ldl;
+    return launch(tg.s_vocab, g, 2.0 * R * V * W, ((double)R * W + (double)V * W) * e + (double)R * V * 4);
 }
 
 __global__ void iota_rows_kernel(int* anc, int R, int L) {
@@ -1833,7 +1718,7 @@ int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm
     }
     if (out_vocab) TRY(launch_fill_f32(out_vocab, 0.f, (size_t)R * acc_ld, s));
     TRY(run_image_side(m, pixels, fmt, B, s));
-    Dec d = make_slice(m, 0, B, B, K, Lm);
+    Dec d = make_dec(m, B, K);
     // Row compaction (ops.h, RowMap): the greedy BLIP loop on the batch kernels, when nobody asked for per-step logits (their rows
     // are the batch's rows) and every position takes the fused self-attention (<= 32: the k / v append goes through map.live)
     const bool compact = greedy && c.arch == CAP_ARCH_BLIP && m->compaction && m->live && !out_step_logits && Lm - 1 <= 32 &&
@@ -1869,13 +1754,7 @@ int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm
             }
             const bool small = can && (m->decode_path == 0 || m->decode_path == 2);
             m->last_path = small ? 2 : 1;
-            if (coca) {
-                if (small) TRY(run_coca_step_small(m, d, tokens, Lm, t, K, anc, Lm, s));
-                else TRY(run_coca_step(m, d, tokens, Lm, t, K, anc, Lm, s));
-            } else {
-                if (small) TRY(run_decoder_step_small(m, d, tokens, Lm, t, K, anc, Lm, s));
-                else TRY(run_decoder_step(m, d, tokens, Lm, t, K, anc, Lm, s));
-            }
+            TRY((small ? run_step_small : run_step)(m, d, tokens, Lm, t, K, anc, Lm, s));
         }
         if (out_step_logits) {
             hipLaunchKernelGGL(copy_logits_kernel, dim3(1024), dim3(256), 0, s, d.logits, m->ldl,
@@ -2586,8 +2465,11 @@ int cap_op_decode_attention(int dtype, const void* q, const void* kbase, const v
                             int anc_ld, int rows_per_kv, int kv_ld, int n_keys, void* out, int R, int H, int impl,
                             void* stream) {
     // impl bit 16: kbase / vbase are KV16 blocks (cap_op_pack_kv16) whose row 0 is the launch's first K/V row
-    return launch_decode_attention(in_dt_of(dtype), q, kbase, vbase, anc, anc_ld, rows_per_kv, kv_ld, n_keys, out, R, H, impl & 15,
-                                   (hipStream_t)stream, nullptr, 0, nullptr, 0, 0, 0, dt_of(dtype), nullptr, (impl >> 4) & 1, 0);
+    DecodeAttn a;
+    memset(&a, 0, sizeof(a));
+    a.q = q; a.kbase = kbase; a.vbase = vbase; a.anc = anc; a.anc_ld = anc_ld; a.rows_per_kv = rows_per_kv; a.kv_ld = kv_ld;
+    a.n_keys = n_keys; a.out = out; a.R = R; a.H = H; a.impl = impl & 15; a.out_dtype = dt_of(dtype); a.kv16 = (impl >> 4) & 1;
+    return launch_decode_attention(in_dt_of(dtype), a, (hipStream_t)stream);
 }
 int cap_op_gemm_crosskv(int dtype, const void* A, const void* W, const float* bias, void* cache, int n_img, int tokens, int heads,
                         int layers, int K, int kv16, void* stream) {

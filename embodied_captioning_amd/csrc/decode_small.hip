@@ -2,7 +2,7 @@
 // (captioner/models/coca/coca.py:27-33, blip2/blip2.py:24-29, agents/goal_exploration/goal_exploration.py:95-105) and
 // BASELINE config 1 is 8.  At that size a decoder layer-step is a chain of dependent launches that each stream a few MB of
 // weights: what it costs is launches x (dispatch + first bytes + drain), so the 11 launches of the batch path
-// (captioner.hip::run_decoder_step: 6 GEMMs, 2 attentions, 3 split-K consumers) become 6 here:
+// (captioner.hip::run_step over BLIP's plan: 6 GEMMs, 2 attentions, 3 split-K consumers) become 6 here:
 //
 //   qkv   = GEMM      [prologue: split-K consumer + LayerNorm of the previous layer's FFN]        -> q|k|v partial sums
 //   so    = GEMM      [prologue: self-attention of the slice's heads, k/v appended to the cache]  -> split-K slabs

@@ -3,7 +3,7 @@
 #pragma once
 #include "common.h"
 
-// Row compaction of the greedy decode loop (captioner.hip, run_decoder_step): the rows of captions that are still open, in
+// Row compaction of the greedy decode loop (captioner.hip, run_step): the rows of captions that are still open, in
 // row order, and their count - both on the device, rebuilt after every token selection.  A kernel given a RowMap works on
 // COMPACT rows c < *n (activations, split-K slabs, logits) and reaches what a caption owns across steps - its tokens, its
 // self-attention cache rows, its image's cross K/V - through live[c]; compact rows from *n on return at once.  Null pointers =
@@ -105,15 +105,22 @@ int launch_rows_broadcast(int dtype, const float* src, float* dst_f, void* dst_t
 // Fused producer (optional, impl 0 only): q_part != nullptr -> q = sum_z q_part[z][R][q_ld][q_col0 + ...] + q_bias;
 // append_kv -> the new position's k/v are finished the same way (columns q_col0 + H*64, + 2*H*64), written to the
 // cache of the row itself and attended (self-attention with n_keys <= 32).
-int launch_decode_attention(int dtype, const void* q, const void* kbase, const void* vbase, const int* anc,
-                            int anc_ld, int rows_per_kv, int kv_ld, int n_keys, void* out, int R, int H, int impl,
-                            hipStream_t s, const float* q_part = nullptr, int q_S = 0, const float* q_bias = nullptr,
-                            int q_ld = 0, int q_col0 = 0, int append_kv = 0, int out_dtype = -1,   // out_dtype: see launch_vit_attention
-                            const int* skip_rows = nullptr,    // int32 [R] or null: rows with a non-zero flag are left untouched
-                            int kv16 = 0,                      // 1: kbase / vbase are the bases of KV16 blocks (common.h; fp32 q, no
-                            size_t kv_row0 = 0,                // ancestry, > 32 keys); kv_row0 = index of the launch's first row in them
-                            RowMap map = RowMap());            // q_part / out rows are compact, caches and ancestry belong to map.live[c]
-                                                               // (wave / online kernels, impl 0)
+struct DecodeAttn {                    // zero-initialise (memset), then fill
+    const void* q;                     // [R, H*64] (T), or null with q_part
+    const void* kbase; const void* vbase;
+    const int* anc; int anc_ld;        // ancestry table (beams) or null
+    int rows_per_kv, kv_ld, n_keys;
+    void* out;                         // [R, H*64] (out_dtype)
+    int R, H, impl;
+    const float* q_part; int q_S; const float* q_bias; int q_ld, q_col0, append_kv;   // the fused producer
+    int out_dtype;                     // type of out, always set (0 is fp32; < 0: dtype) - see launch_vit_attention: split mode is fp32 in, G8 out
+    const int* skip_rows;              // int32 [R] or null: rows with a non-zero flag are left untouched
+    int kv16;                          // 1: kbase / vbase are the bases of KV16 blocks (common.h; fp32 q, no
+    size_t kv_row0;                    // ancestry, > 32 keys); kv_row0 = index of the launch's first row in them
+    RowMap map;                        // q_part / out rows are compact, caches and ancestry belong to map.live[c]
+                                       // (wave / online kernels, impl 0)
+};
+int launch_decode_attention(int dtype, const DecodeAttn& a, hipStream_t s);
 // fp32 rows [n_rows, 64] -> one KV16 block of kv16_block_bytes(n_rows) bytes: what the cross-K/V GEMM's epilogue writes, as a
 // kernel of its own (tests)
 int launch_pack_kv16(const float* src, void* dst, size_t n_rows, hipStream_t s);

@@ -214,6 +214,32 @@ def test_coca_tiny_small_path_has_the_bits_of_the_batch_path_unpinned(boost, dty
         assert torch.equal(s["sequences"], b["sequences"]) and torch.equal(s["sequences_scores"], b["sequences_scores"]), (beams, groups)
 
 
+def test_coca_four_launches_per_block_step():
+    """The CoCa twin of test_six_launches_per_layer_step_and_early_exit: two rows take the fused path by row count, every block
+    (t_layers unimodal, then a self and a cross block per multimodal layer) is 4 launches per step, and no batch-path kernel runs."""
+    from embodied_captioning_amd.config import CocaArch
+    from embodied_captioning_amd.engine import CaptionerEngine
+    from embodied_captioning_amd.weights import procedural_coca_state_dict, synthetic_pixels
+    a = CocaArch.tiny()
+    sd = procedural_coca_state_dict(a, 1, eos_boost=0.0)
+    px = synthetic_pixels(2, a.image_size, seed=1)
+    eng = CaptionerEngine(a, dtype="f32s", max_batch=2, max_beams=1, max_len=a.seq_len)
+    eng.load_state_dict(sd)
+    eng.profile(True)
+    eng.generate(px.cuda(), num_beams=1, max_length=a.seq_len)
+    rep = eng.profile_report()
+    eng.profile(False)
+    assert eng.last_decode_path == "small"
+    steps, blocks = eng.last_decode_steps, a.t_layers + 2 * a.mm_layers
+    assert steps >= 1
+    per = sum(r["launches"] for t, r in rep.items() if t.startswith("coca_small_") and t != "coca_small_vocab")
+    assert per == 4 * blocks * steps, rep
+    assert rep["coca_small_vocab"]["launches"] == steps, rep
+    assert not any(t.startswith("coca_gemm_") or t in ("coca_self_attn", "coca_cross_attn", "dec_reduce_ln", "dec_reduce_ln_wave")
+                   for t in rep), rep
+    eng.close()
+
+
 @pytest.mark.parametrize("dtype", ["f32s", "bf16"])
 def test_coca_vit_l14_small_path_has_the_bits_of_the_batch_path_unpinned(dtype):
     """Production geometry (ViT-L/14, 12 + 12 text layers, vocabulary 49408, 255 cross-attention keys in the KV16 cache): one
