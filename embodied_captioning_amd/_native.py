@@ -17,6 +17,7 @@ CAP_PIX_F32_NCHW, CAP_PIX_U8_NHWC = 0, 1
 CAP_ARCH_CLIP = 4
 CAP_ARCH_BLIP2_ITM = 5
 CAP_ACT_QUICK_GELU, CAP_ACT_GELU = 0, 1
+CAP_MAX_PROMPT = 32      # prompt tokens per caption (BOS included) cap_generate_prompted takes
 
 
 class CapConfig(C.Structure):
@@ -34,6 +35,7 @@ class CapConfig(C.Structure):
         ("q_hidden", C.c_int32), ("q_layers", C.c_int32), ("q_heads", C.c_int32), ("q_ffn", C.c_int32),
         ("q_cross_freq", C.c_int32), ("num_query_tokens", C.c_int32), ("q_eps", C.c_float),
         ("cross_kv_fp32", C.c_int32), ("weight_int8", C.c_int32), ("hidden_act", C.c_int32),
+        ("max_prompt", C.c_int32),
     ]
 
 
@@ -52,6 +54,9 @@ _SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cap_generate_vocab": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "cap_generate_prompted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "cap_last_prefill_passes": (C.c_int, [C.c_void_p]),
     "cap_embed_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cap_crop_resize_tables": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -57,3 +57,12 @@ def reject_unsupported_generation_options(opts: Mapping[str, Any], where: str = 
             bad.append(f"{name}={opts[name]!r}")
     if bad:
         raise ValueError(f"{where}: not implemented by the MI355X captioner library (greedy / beam search only) - " + "; ".join(bad))
+
+
+def reject_prompt_keys(cfg, who: str) -> None:
+    """The text-prompt keys (`prompt`, `prompt_ids`) are BLIP's: a wrapper of another family that finds one in its configuration
+    raises, naming it - a yaml key is never dropped silently."""
+    given = [k for k in ("prompt", "prompt_ids") if getattr(cfg, k, None) is not None]
+    if given:
+        raise ValueError(f"{who}: captioner.{' / captioner.'.join(given)} - a text prompt is implemented for arch_name 'blip' only "
+                         f"(greedy decoding); it is not built for this architecture")

@@ -30,6 +30,30 @@ from ....weights import (load_hf_blip_checkpoint, load_state_dict_file, procedur
 logger = logging.getLogger(__name__)
 
 
+def resolve_prompt(prompt, prompt_ids, tokenizer, arch):
+    """The wrapper's two prompt keys -> token ids for `CaptionerEngine.generate(prompt_ids=)`, or None when neither is given.
+    prompt (str): tokenized with the checkpoint's tokenizer as HF's BlipProcessor does (`[CLS] words [SEP]`), then what HF
+    `BlipForConditionalGeneration.generate` does to it (modeling_blip.py:858-932): BOS replaces [CLS], the trailing [SEP] is dropped.
+    prompt_ids (list of ints [P], or rows [N, P]): taken as they are - for directories without a tokenizer and the procedural
+    models; column 0 must be BOS (the engine checks).  Giving both, or a string without a tokenizer, raises."""
+    if prompt is not None and prompt_ids is not None:
+        raise ValueError("captioner.prompt and captioner.prompt_ids are both given: give the prompt as a string OR as token ids")
+    if prompt is not None:
+        if not isinstance(prompt, str):
+            raise ValueError(f"captioner.prompt must be a string, got {type(prompt).__name__} (token ids go to captioner.prompt_ids)")
+        if tokenizer is None:
+            raise ValueError("captioner.prompt is a string but this model has no tokenizer (a procedural model, or a checkpoint "
+                             "directory without tokenizer files): give captioner.prompt_ids instead")
+        ids = list(tokenizer(prompt, add_special_tokens=True)["input_ids"])
+        if len(ids) < 3:
+            raise ValueError(f"captioner.prompt {prompt!r} tokenizes to no word: a prompt needs at least one token")
+        return [int(arch.bos)] + [int(i) for i in ids[1:-1]]
+    if prompt_ids is None:
+        return None
+    t = torch.as_tensor(prompt_ids)
+    return t.tolist()
+
+
 class BLIP(CaptioningPredictor):
     def __init__(self, cfg=None):
         super().__init__(cfg)
@@ -59,6 +83,21 @@ class BLIP(CaptioningPredictor):
                 self.tokenizer = AutoTokenizer.from_pretrained(model_dir)
             except Exception as e:  # noqa: BLE001
                 logger.warning("no tokenizer under %s (%s): captions are returned as space-separated token ids", model_dir, e)
+        # captioner.prompt (string) / captioner.prompt_ids (token ids): every caption starts with it (HF's conditional captioning)
+        self.prompt_ids = resolve_prompt(getattr(cfg, "prompt", None), getattr(cfg, "prompt_ids", None), self.tokenizer, self.arch)
+        if self.prompt_ids is not None and self.prompt_ids and isinstance(self.prompt_ids[0], (list, tuple)):
+            if len(self.prompt_ids) != 1:
+                raise ValueError(f"captioner.prompt_ids has {len(self.prompt_ids)} rows: the configured prompt is ONE prompt for every "
+                                 f"caption ([P] or [1, P]); one prompt per image is a per-call argument (generate_batch(prompt_ids=[N, P]))")
+            self.prompt_ids = list(self.prompt_ids[0])
+        # captioner.max_prompt: prompt capacity of the arena (a full batch prefills in one pass up to this many prompt tokens);
+        # default = the configured prompt's length, 0 without one (prompts given per call then prefill in chunks of captions)
+        mp = getattr(cfg, "max_prompt", None)
+        self.max_prompt = int(mp) if mp is not None else (len(self._prompt_row(self.prompt_ids)) if self.prompt_ids is not None else 0)
+        if self.prompt_ids is not None:
+            from ....engine import prompt_token_limit, validate_prompt_ids
+            validate_prompt_ids(self._prompt_row(self.prompt_ids), self.arch, 1, self.max_length, self.num_beams, None,
+                                prompt_token_limit(self.batch_size, self.num_beams, self.max_prompt))
         if getattr(cfg, "checkpoint_name", None):
             over = load_state_dict_file(cfg.checkpoint_name)
             for dst, src in BLIP_TIED.items():
@@ -68,7 +107,7 @@ class BLIP(CaptioningPredictor):
             logger.info("Captioner model checkpoint loaded successfully from %s", cfg.checkpoint_name)
         self.engine = CaptionerEngine(self.arch, dtype=dtype, max_batch=self.batch_size, max_beams=self.num_beams,
                                       max_len=self.max_length, device=self._device,
-                                      cross_cache=self._cross_cache_for(cfg, sd, dtype))
+                                      cross_cache=self._cross_cache_for(cfg, sd, dtype), max_prompt=self.max_prompt)
         # HF generate stops once every caption has its EOS; look every few steps (cfg early_exit_poll, 0 = never)
         poll = getattr(cfg, "early_exit_poll", None)
         poll = 4 if poll is None else int(poll)
@@ -96,7 +135,7 @@ class BLIP(CaptioningPredictor):
             self.pool = EnginePool(self.arch, n=n_streams, device=self._device, dtype=dtype,
                                    max_batch=max(self.batch_size, self.coalesce_rows),
                                    max_beams=getattr(self, "num_beams", 1), max_len=self.engine.max_len, weights_of=self.engine,
-                                   cross_cache=self.engine.cross_cache)
+                                   cross_cache=self.engine.cross_cache, max_prompt=self.max_prompt)
             self.pool.set_early_exit(poll)
         elif cr:
             logger.warning("captioner.coalesce_rows is the engine pool's dynamic batching: it needs captioner.streams > 1 - ignored")
@@ -143,6 +182,24 @@ class BLIP(CaptioningPredictor):
         frames = [np.asarray(im.convert("RGB").resize((S, S), resample=Image.BICUBIC)) for im in images]
         return torch.from_numpy(np.stack(frames))
 
+    @staticmethod
+    def _prompt_row(ids):
+        """First row of a prompt given as [P] or [N, P] (what the configuration-time checks look at)."""
+        return ids[0] if ids and isinstance(ids[0], (list, tuple)) else ids
+
+    def _call_prompt(self, prompt, prompt_ids, n_rows: int):
+        """Prompt of one call: the call's own `prompt` / `prompt_ids` when given, else the configured one -> None, or a function
+        (row0, rows) -> the ids of those rows ([P] shared, or the rows' slice of [n_rows, P])."""
+        ids = resolve_prompt(prompt, prompt_ids, self.tokenizer, self.arch) if (prompt is not None or prompt_ids is not None) \
+            else getattr(self, "prompt_ids", None)
+        if ids is None:
+            return None
+        if ids and isinstance(ids[0], (list, tuple)) and len(ids) > 1:
+            if len(ids) != n_rows:
+                raise ValueError(f"prompt_ids has {len(ids)} rows for {n_rows} images: give one prompt or one per image")
+            return lambda r0, n: ids[r0:r0 + n]
+        return lambda r0, n: ids
+
     def decode(self, ids: Sequence[int]) -> str:
         ids = [int(i) for i in ids]
         if self.tokenizer is not None:
@@ -153,8 +210,11 @@ class BLIP(CaptioningPredictor):
     # ------------------------------------------------------------------------------------------ forward
     @torch.no_grad()
     def generate_batch(self, images, output_logits: bool = False, output_perplexity: bool = False,
-                       output_vocab_maxprob: bool = False) -> dict:
-        """Batched extension: any number of frames -> {"texts": [str], "sequences": int32 [N, L], "lengths", "scores"}.
+                       output_vocab_maxprob: bool = False, prompt=None, prompt_ids=None) -> dict:
+        """prompt (string) / prompt_ids (token ids [P], or [N, P] one row per image): the text every caption starts with, for this
+        call; without them the configured captioner.prompt / captioner.prompt_ids (if any).  Texts and sequences include the prompt,
+        per-step outputs cover the generated steps.
+        Batched extension: any number of frames -> {"texts": [str], "sequences": int32 [N, L], "lengths", "scores"}.
         output_perplexity (greedy): adds "perplexities" float64 [N] - what `forward` + `compute_perplexity()` give one crop at a
         time - and "token_logprobs" fp32 [N, steps] / "scored_steps" int32 [N] they are computed from (engine.generate,
         output_logprobs); the pool, its dynamic batching and the preprocessing overlap work as without it.
@@ -166,6 +226,14 @@ class BLIP(CaptioningPredictor):
             kw["output_vocab_maxprob"] = True
         seqs, lens, scores, logits = [], [], [], []
         pool = getattr(self, "pool", None)
+        n_images = int(images.shape[0]) if isinstance(images, torch.Tensor) and images.dim() == 4 else \
+            len(images) if isinstance(images, (list, tuple)) else 1
+        pk = self._call_prompt(prompt, prompt_ids, n_images)
+        bs = self.batch_size
+
+        def pkw(row0, n_rows):      # prompt_ids of the micro-batches that cover rows row0 .. row0 + n_rows - 1 (generate_many's list form)
+            return {} if pk is None else {"prompt_ids": [pk(i, min(bs, row0 + n_rows - i)) for i in range(row0, row0 + n_rows, bs)]}
+
         # a long list of PIL crops on a pool: in rounds of one pass per engine, the next round's crops are preprocessed (host
         # `Image.convert` + pack, upload, device resize) by a helper thread while the current round generates
         rnd = len(pool) * max(self.batch_size, self.coalesce_rows) if pool is not None else 0
@@ -182,16 +250,17 @@ class BLIP(CaptioningPredictor):
                         nxt = ex.submit(self.preprocess, groups[g + 1])
                     chunks = [px[i:i + self.batch_size].to(self._device) for i in range(0, px.shape[0], self.batch_size)]
                     outs += self.pool.generate_many(chunks, threads=True, coalesce_rows=self.coalesce_rows, num_beams=self.num_beams,
-                                                    max_length=self.max_length, **kw)
+                                                    max_length=self.max_length, **kw, **pkw(g * rnd, int(px.shape[0])))
         else:
             px = self.preprocess(images)
             chunks = [px[i:i + self.batch_size].to(self._device) for i in range(0, px.shape[0], self.batch_size)]
             if pool is not None and len(chunks) > 1 and not output_logits:
                 outs = self.pool.generate_many(chunks, threads=True, coalesce_rows=self.coalesce_rows, num_beams=self.num_beams,
-                                               max_length=self.max_length, **kw)
+                                               max_length=self.max_length, **kw, **pkw(0, int(px.shape[0])))
             else:
-                outs = [self.engine.generate(c, num_beams=self.num_beams, max_length=self.max_length, output_logits=output_logits, **kw)
-                        for c in chunks]
+                outs = [self.engine.generate(c, num_beams=self.num_beams, max_length=self.max_length, output_logits=output_logits,
+                                             prompt_ids=None if pk is None else pk(i * bs, int(c.shape[0])), **kw)
+                        for i, c in enumerate(chunks)]
         for out in outs:
             seqs.append(out["sequences"]); lens.append(out["lengths"])
             if "sequences_scores" in out:
@@ -223,13 +292,16 @@ class BLIP(CaptioningPredictor):
     @torch.no_grad()
     def forward(self, inputs):
         px = self.preprocess(inputs)[:1]
+        # the configured prompt, as HF's `generate(pixel_values, input_ids=...)`: the text includes the prompt's words (HF
+        # `decode(out[0], skip_special_tokens=True)`), the logits are the generated steps
+        pr = None if self.prompt_ids is None else self._prompt_row(self.prompt_ids)
         out = self.engine.generate(px.to(self._device), num_beams=self.num_beams, max_length=self.max_length,
-                                   output_logits=True)
+                                   output_logits=True, prompt_ids=pr)
         n = int(out["lengths"][0])
         ids = out["sequences"][0, :n].tolist()
         self._range_tick()
         # new objects every call: callers keep references to outputs["logits"] across calls
         # (reference generate_pseudo_caption_from_file.py:152)
         self.outputs = {"text": self.decode(ids),
-                        "logits": tuple(out["logits"][t] for t in range(max(n - 1, 1)))}
+                        "logits": tuple(out["logits"][t] for t in range(max(n - (len(pr) if pr is not None else 1), 1)))}
         return self.outputs

@@ -101,6 +101,8 @@ class BLIP2(BLIP):
                 raise RuntimeError(f"Pretrained BLIP-2 checkpoint '{name}' not found locally (offline)")
             super().__init__(cfg)                       # a BLIP captioning checkpoint under arch_name blip2
             return
+        from ...generation_options import reject_prompt_keys
+        reject_prompt_keys(cfg, "BLIP2(cfg)")          # (a BLIP checkpoint under arch_name blip2, above, takes them)
         CaptioningPredictor.__init__(self, cfg)
         if getattr(cfg, "load_in_4bit", None):
             raise ValueError("BLIP2(cfg): load_in_4bit (bitsandbytes NF4) is not implemented by the MI355X captioner library - "

@@ -45,6 +45,8 @@ class CoCa(CaptioningPredictor):
         self.generation_options = {k: getattr(cfg, k) for k in ("generation_type", "top_k", "top_p", "temperature", "repetition_penalty")
                                    if getattr(cfg, k, None) is not None}
         reject_unsupported_generation_options(self.generation_options, "CoCa(cfg)")
+        from ...generation_options import reject_prompt_keys
+        reject_prompt_keys(cfg, "CoCa(cfg)")
         if self.generation_options.get("generation_type") == "beam_search" and self.num_beams < 2:
             raise ValueError("CoCa(cfg): generation_type='beam_search' needs num_beams >= 2 (the reference's default is 6 in 3 groups)")
         dtype = getattr(cfg, "dtype", None) or "f32s"      # fp32-grade default (token-identical to the fp32 restatement); "bf16" is ~2x faster

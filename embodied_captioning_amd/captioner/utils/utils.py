@@ -26,7 +26,7 @@ class CaptionerField:
                  early_exit_poll=None, max_new_tokens=None, num_beam_groups=None, tokenizer_dir=None,
                  generation_type=None, top_k=None, top_p=None, temperature=None, repetition_penalty=None,
                  load_in_8bit=None, load_in_4bit=None, torch_dtype=None, cross_cache=None, strict_range=False,
-                 coalesce_rows=None, device_resize=None):
+                 coalesce_rows=None, device_resize=None, prompt=None, prompt_ids=None, max_prompt=None):
         self.arch_name = arch_name
         self.model_name = model_name
         self.checkpoint_name = checkpoint_name
@@ -65,3 +65,9 @@ class CaptionerField:
         self.coalesce_rows = coalesce_rows
         # PIL inputs: the processor's bicubic resize runs on the device, bit-exact with Pillow (None / True); False = host PIL
         self.device_resize = device_resize
+        # BLIP: the text every caption starts with (HF `generate(pixel_values, input_ids=...)`): prompt = a string for the
+        # checkpoint's tokenizer, prompt_ids = token ids with BOS first (one or the other); max_prompt = prompt capacity of the
+        # arena in tokens (None: the configured prompt's length).  Other architectures refuse the keys by name.
+        self.prompt = prompt
+        self.prompt_ids = prompt_ids
+        self.max_prompt = max_prompt

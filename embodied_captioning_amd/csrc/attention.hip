@@ -1995,6 +1995,94 @@ int launch_decode_attention(int dtype, const DecodeAttn& a, hipStream_t s) {
     return 0;
 }
 
+// ---- prompt prefill: the self-attention of several known positions of every caption in one pass (captioner.hip, run_prefill).
+// Row r of the pass is position r % npos of caption row0 + r / npos.  A single step finishes the split-K k / v of its position
+// inside the attention unit and appends them; here the other positions' k / v are needed by the same launch, so the append is a
+// kernel of its own - Part8::issue / finish, the unit's own reduction, 8 lanes per (row, head) - and the attention kernel reads
+// every key from the cache.  The finished k / v are already rounded to the cache type, so the cached copy the unit loads here and
+// the registers it keeps in a single step hold the same values.
+namespace {
+template <typename T>
+__global__ __launch_bounds__(256) void prefill_kv_append_kernel(T* __restrict__ kbase, T* __restrict__ vbase, int kv_ld, int Rp, int H,
+                                                                int npos, int row0, QSource qs) {
+    const int unit = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + ((threadIdx.x & 63) >> 3);      // (row, head); 8 lanes each
+    if (unit >= Rp * H) return;
+    const int dch = threadIdx.x & 7;
+    const int crow = unit / H, h = unit - crow * H;
+    const int cap = row0 + crow / npos, p = crow - (crow / npos) * npos;
+    const int Dh = H * 64;
+    Part8 pk, pv;
+    pk.issue(qs, Rp, crow, qs.col0 + Dh + h * 64 + dch * 8);
+    pv.issue(qs, Rp, crow, qs.col0 + 2 * Dh + h * 64 + dch * 8);
+    float kn[8], vn[8];
+    pk.finish<T>(qs, kn);
+    pv.finish<T>(qs, vn);
+    const size_t o = (((size_t)cap * H + h) * kv_ld + p) * 64 + dch * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { kbase[o + e] = from_f32<T>(kn[e]); vbase[o + e] = from_f32<T>(vn[e]); }
+}
+
+// One wave per (row, head): the wave unit of the single step at the row's own position (p + 1 keys, and the unit's instantiation
+// launch_decode_attention picks for that key count), q finished from the partial sums of the pass's row, keys from the caption's row.
+// Two waves per SIMD: with the three instantiations in one kernel the fp32 forms take 207 VGPRs and no scratch (at three waves per
+// SIMD, 168 VGPRs, they spill 84-92 registers); the kernel runs once per layer of a prefill, not once per step.
+template <typename T, typename TO>
+__global__ __launch_bounds__(256, 2) void prefill_self_attention_kernel(T* __restrict__ kbase, T* __restrict__ vbase, int kv_ld,
+                                                                        TO* __restrict__ out, int Rp, int H, int npos, int row0, QSource qs) {
+    const int unit = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (unit >= Rp * H) return;
+    const int crow = unit / H, h = unit - crow * H;
+    const int cap = row0 + crow / npos, n_keys = crow - (crow / npos) * npos + 1;
+    TO* out_row = out + (size_t)crow * H * 64;
+    const int lane = threadIdx.x & 63;
+    if (n_keys <= 8)
+        decode_attention_wave_unit<T, 1, TO>(nullptr, kbase, vbase, nullptr, 0, 1, kv_ld, n_keys, out_row, Rp, H, qs, cap, h, lane, false, nullptr, crow);
+    else if (n_keys <= 16)
+        decode_attention_wave_unit<T, 2, TO>(nullptr, kbase, vbase, nullptr, 0, 1, kv_ld, n_keys, out_row, Rp, H, qs, cap, h, lane, false, nullptr, crow);
+    else
+        decode_attention_wave_unit<T, 4, TO>(nullptr, kbase, vbase, nullptr, 0, 1, kv_ld, n_keys, out_row, Rp, H, qs, cap, h, lane, false, nullptr, crow);
+}
+
+}  // namespace
+
+int launch_prefill_self_attention(int dtype, const float* part, int S, const float* bias, int part_ld, void* kbase, void* vbase,
+                                  int kv_ld, void* out, int out_dtype, int n_caps, int npos, int row0, int H, hipStream_t s) {
+    if (out_dtype < 0) out_dtype = dtype;
+    if (out_dtype != dtype && !(dtype == CAP_DT_F32 && out_dtype == CAP_DT_G8)) {
+        cap_set_error("prefill_self_attention: output type %d for input type %d is not supported here", out_dtype, dtype);
+        return -1;
+    }
+    if (dtype != CAP_DT_F32 && dtype != CAP_DT_BF16) { cap_set_error("prefill_self_attention: caches are fp32 or bf16 (got type %d)", dtype); return -1; }
+    if (!part || !bias || S < 1 || S > 4 || (part_ld & 3) || part_ld < 3 * H * 64) {
+        cap_set_error("prefill_self_attention: needs 1..4 split-K slices of fused q|k|v rows (16-byte aligned, >= %d columns) and a bias", 3 * H * 64);
+        return -1;
+    }
+    if (npos < 1 || npos > PREFILL_MAX_POS || npos > kv_ld || n_caps < 1 || row0 < 0 || H < 1) {
+        cap_set_error("prefill_self_attention: %d positions (at most %d, cache rows of %d) of %d captions from row %d", npos, PREFILL_MAX_POS,
+                      kv_ld, n_caps, row0);
+        return -1;
+    }
+    const int Rp = n_caps * npos;
+    QSource qs;
+    qs.part = part; qs.bias = bias; qs.S = S; qs.part_ld = part_ld; qs.col0 = 0; qs.append_kv = 0;
+    const dim3 ga((Rp * H + 31) / 32), gb((Rp * H + 3) / 4);
+    if (dtype == CAP_DT_BF16) {
+        hipLaunchKernelGGL(prefill_kv_append_kernel<bf16_t>, ga, dim3(256), 0, s, (bf16_t*)kbase, (bf16_t*)vbase, kv_ld, Rp, H, npos, row0, qs);
+        hipLaunchKernelGGL((prefill_self_attention_kernel<bf16_t, bf16_t>), gb, dim3(256), 0, s, (bf16_t*)kbase, (bf16_t*)vbase, kv_ld,
+                           (bf16_t*)out, Rp, H, npos, row0, qs);
+    } else {
+        hipLaunchKernelGGL(prefill_kv_append_kernel<float>, ga, dim3(256), 0, s, (float*)kbase, (float*)vbase, kv_ld, Rp, H, npos, row0, qs);
+        if (out_dtype == CAP_DT_G8)
+            hipLaunchKernelGGL((prefill_self_attention_kernel<float, g8_t>), gb, dim3(256), 0, s, (float*)kbase, (float*)vbase, kv_ld,
+                               (g8_t*)out, Rp, H, npos, row0, qs);
+        else
+            hipLaunchKernelGGL((prefill_self_attention_kernel<float, float>), gb, dim3(256), 0, s, (float*)kbase, (float*)vbase, kv_ld,
+                               (float*)out, Rp, H, npos, row0, qs);
+    }
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // fp32 rows [n_rows, 64] -> one KV16 block (common.h): what the cross-K/V GEMM's epilogue writes, as a kernel of its own (tests).
 // One wave per 4 rows: 16 lanes per row, 4 values per lane; the row maximum goes through two DPP-free shuffles.
 __global__ void pack_kv16_kernel(const float* __restrict__ src, char* __restrict__ dst, size_t n_rows) {

@@ -199,6 +199,7 @@ struct Captioner {
                                  // 1 = always the batch kernels, 2 = always the small-batch kernels (an error beyond their row limit)
     int last_path = 0;           // what the last cap_generate's decode steps ran on (cap_last_decode_path): 1 batch, 2 small-batch
     int compaction = 1;          // cap_set_row_compaction: 1 = the greedy batch path works on the open captions' rows only (RowMap)
+    int last_prefill_passes = 0; // prefill passes of the last prompted generate (cap_last_prefill_passes): 1 when the workspace held the batch
     int last_compacted = 0;      // did the last cap_generate's decode loop run compacted (cap_last_row_compaction)
     int *live = nullptr, *n_live = nullptr;       // RowMap storage: int32 [max rows] + the count
     // vision weights (post_g / post_b: the image tower's final LayerNorm - CoCa: the pooler's ln_k)
@@ -221,6 +222,7 @@ struct Captioner {
     void *dx_t, *dq, *dctx, *dh;
     void* beam = nullptr;
     size_t cache_layer_bytes = 0;
+    size_t ws_rows = 0;          // rows the decoder's pass buffers (dx, dx_t, dctx, dh, dpart) hold: the decode rows, or a whole prompt prefill's
     // ---- CoCa (CAP_ARCH_COCA)
     int Q = 0, E = 0;
     float *lnpost_g = nullptr, *lnpost_b = nullptr, *pool_q = nullptr, *b_pool_kv = nullptr, *b_pool_o = nullptr, *ones = nullptr,
@@ -590,14 +592,18 @@ int build_arena(Captioner* m) {
     TRY(dev_alloc(m, (void**)&m->live, R * 4));
     TRY(dev_alloc(m, (void**)&m->n_live, 256));
     TRY(dev_alloc(m, (void**)&m->anc, 2 * R * Lm * 4));
-    TRY(dev_alloc(m, (void**)&m->dx, R * T * 4));
+    // prompt prefill (run_prefill): max_prompt - 1 known positions of every caption go through the decoder as ONE pass of rows, so
+    // the buffers a pass over rows touches hold that many (CapConfig.max_prompt = 0: exactly the decode rows, as ever)
+    const size_t Rw = std::max(R, Bm * (size_t)std::max(c.max_prompt - 1, 0));
+    m->ws_rows = Rw;
+    TRY(dev_alloc(m, (void**)&m->dx, Rw * T * 4));
     TRY(dev_alloc(m, (void**)&m->dy, R * T * 4));
     TRY(dev_alloc(m, (void**)&m->dx2, (size_t)(R > SMALL_MAX_ROWS ? R : SMALL_MAX_ROWS) * T * 4));
-    TRY(dev_alloc(m, (void**)&m->dpart, 12 * R * T * 4));      // split-K slabs: 8 x [R,T] (ffn) or 4 x [R,3T] (qkv)
-    TRY(dev_alloc(m, &m->dx_t, R * T * e));
+    TRY(dev_alloc(m, (void**)&m->dpart, 12 * Rw * T * 4));      // split-K slabs: 8 x [R,T] (ffn) or 4 x [R,3T] (qkv)
+    TRY(dev_alloc(m, &m->dx_t, Rw * T * e));
     TRY(dev_alloc(m, &m->dq, R * T * e));
-    TRY(dev_alloc(m, &m->dctx, R * T * e));
-    TRY(dev_alloc(m, &m->dh, R * c.t_ffn * e));
+    TRY(dev_alloc(m, &m->dctx, Rw * T * e));
+    TRY(dev_alloc(m, &m->dh, Rw * c.t_ffn * e));
     m->ldl = (c.vocab + 3) & ~3;
     TRY(dev_alloc(m, (void**)&m->logits, R * (size_t)m->ldl * 4));
     for (DecSub& u : m->dec.subs)
@@ -1667,6 +1673,65 @@ int run_step_small(Captioner* m, const Dec& d, const int* tokens, int tok_ld, in
     return launch(tg.s_vocab, g, 2.0 * R * V * W, ((double)R * W + (double)V * W) * e + (double)R * V * 4);
 }
 
+// ---------------------------------------------------------------------------------------------- prompt prefill
+// Positions 0 .. npos - 1 of the captions c0 .. c0 + nc - 1 of a greedy BLIP call (tokens already in d.seq) through every sub-layer of
+// the decoder as ONE pass of nc * npos rows, caption-major: what npos calls of run_step would do to the self-attention caches, with
+// one launch sequence and one read of every weight, and without the head (nobody selects a token at a prompt position).  Row-wise
+// kernels - the split-K GEMMs (their slice plan depends on (N, K) only), the reduce + LayerNorm consumers, the FFN - are run_step's
+// own at another row count; the cross-attention is run_step's with the npos rows of an image sharing its K/V the way beams do
+// (rows_per_kv); the embedding and the self-attention are the prefill's kernels (launch_embed_prompt,
+// launch_prefill_self_attention), built on the same row / unit functions.  So the caches hold the bits of the single steps.
+// d: the CALL's decode state (d.B, d.R = its captions: the caches and the cross K/V are laid out for them).
+int run_prefill(Captioner* m, const Dec& d, int c0, int nc, int npos, int Lm, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const DecPlan& P = m->dec;
+    const int W = P.W, F = c.t_ffn, H = c.t_heads, Rp = nc * npos;
+    const size_t e = m->esz;
+    if (P.pre_ln || c.arch != CAP_ARCH_BLIP) { cap_set_error("run_prefill: the prompt prefill is built for the BLIP text decoder"); return -1; }
+    if ((size_t)Rp > m->ws_rows || c0 < 0 || c0 + nc > d.R) {
+        cap_set_error("run_prefill: %d captions x %d positions from caption %d do not fit the workspace (%zu rows, %d captions)", nc, npos, c0,
+                      m->ws_rows, d.R);
+        return -1;
+    }
+    Dec pd = d;              // the pass: Rp rows of the shared buffers, no row map
+    pd.R = Rp;
+    pd.map = RowMap();
+    {
+        ProfScope ps(m, s, "prefill_embed", 0, (double)Rp * W * (8 + e));
+        TRY(launch_embed_prompt(m->gdt, d.seq, Lm, npos, c0, P.word, P.pos, P.emb_g, P.emb_b, c.t_eps, pd.dx_t, pd.dx, nc, W, s));
+    }
+    for (const DecSub& u : P.subs) {
+        const void* A = pd.dctx;
+        int Kout = W, S = 1;
+        if (u.kind == DEC_FFN) {
+            TRY(gemm_rows(m, s, "prefill_gemm_f1", pd.dx_t, u.w_in, pd.dh, u.b_in, Rp, F, W, 1));
+            A = pd.dh; Kout = F;
+        } else if (u.kind == DEC_SELF) {
+            TRY(gemm_partial(m, s, "prefill_gemm_qkv", pd.dx_t, u.w_in, pd.dpart, Rp, 3 * W, W, 4, &S, nullptr));
+            ProfScope ps(m, s, "prefill_self_attn", 2.0 * Rp * H * (npos + 1) * 64, (double)(S + 2) * Rp * 3 * W * 4);
+            TRY(launch_prefill_self_attention(m->dt, pd.dpart, S, u.b_in, 3 * W, u.cache, (char*)u.cache + (size_t)d.R * H * Lm * 64 * e, Lm,
+                                              pd.dctx, m->gdt, nc, npos, c0, H, s));
+        } else {
+            DecodeAttn a;
+            memset(&a, 0, sizeof(a));
+            a.out = pd.dctx; a.R = Rp; a.H = H; a.out_dtype = m->gdt;
+            // the image of row r is c0 + r / npos: the slot's blocks from image c0 on
+            const CrossKV kv = cross_kv(m, u.slot, d.B, m->kv16);
+            const size_t img0 = (size_t)c0 * H * P.kv_tokens;       // head rows before image c0
+            a.kbase = m->kv16 ? kv.k : kv.k + img0 * m->kvrow; a.vbase = m->kv16 ? kv.v : kv.v + img0 * m->kvrow;
+            a.kv16 = m->kv16 ? 1 : 0; a.kv_row0 = m->kv16 ? kv.row0 + img0 : 0;
+            a.rows_per_kv = npos; a.kv_ld = P.kv_tokens; a.n_keys = P.kv_keys;
+            TRY(gemm_partial(m, s, "prefill_gemm_cq", pd.dx_t, u.w_in, pd.dpart, Rp, W, W, 4, &S, nullptr));
+            a.q_part = pd.dpart; a.q_S = S; a.q_bias = u.b_in; a.q_ld = W;
+            ProfScope ps(m, s, "prefill_cross_attn", 4.0 * Rp * H * a.n_keys * 64, 2.0 * nc * H * a.n_keys * m->kvrow);
+            TRY(launch_decode_attention(m->dt, a, s));
+        }
+        const char* tag = u.kind == DEC_FFN ? "prefill_gemm_f2" : u.kind == DEC_SELF ? "prefill_gemm_so" : "prefill_gemm_co";
+        TRY(gemm_splitk_reduce_ln(m, s, pd, tag, A, u.w_out, u.b_out, u.ln_g, u.ln_b, c.t_eps, W, Kout, pd.dx_t, pd.dx, nullptr));
+    }
+    return 0;
+}
+
 __global__ void iota_rows_kernel(int* anc, int R, int L) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 2 * R * L; i += gridDim.x * blockDim.x) anc[i] = (i / L) % R;
 }
@@ -1702,13 +1767,17 @@ static int run_image_side(Captioner* m, const void* pixels, int fmt, int B, hipS
 
 int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm, float lp, int32_t* out_ids,
                  int32_t* out_len, float* out_scores, float* out_step_logits, hipStream_t s, bool force_beam = false,
-                 float* out_lp = nullptr, int32_t* out_scored = nullptr, float* out_vocab = nullptr, int acc_ld = 0) {
+                 float* out_lp = nullptr, int32_t* out_scored = nullptr, float* out_vocab = nullptr, int acc_ld = 0,
+                 const int32_t* prompt = nullptr, int prompt_rows = 0, int Pn = 0) {
     // force_beam: K == 1 runs as a 1-beam BEAM search (the scorer's bookkeeping, no forced EOS) instead of the greedy loop -
     // what a beam group of size one is (cap_generate_groups)
     // out_lp [B, Lm - 1] / out_scored [B] (greedy only, cap_generate_scored): per-step log max softmax from the selection kernel,
     // indexed by the caption's row whatever the loop's compaction; zero-filled here, on the caller's stream
     // out_vocab [B, acc_ld] (cap_generate_vocab; with out_lp): per-caption maximum over its steps of the step's softmax, same rules
+    // prompt int32 [prompt_rows, Pn] (device; cap_generate_prompted, greedy BLIP): every caption starts with these Pn tokens; positions
+    // 0 .. Pn - 2 run as a prefill and the loop starts at t = Pn - 1, so step outputs (out_step_logits, out_lp) are indexed from there
     const CapConfig& c = m->c;
+    const int t0 = prompt ? Pn - 1 : 0;
     const int R = B * K;
     const bool coca = c.arch == CAP_ARCH_COCA;
     const bool greedy = K == 1 && !force_beam;
@@ -1725,7 +1794,8 @@ int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm
                          R > SMALL_MAX_ROWS && m->decode_path != 2;
     m->last_compacted = compact ? 1 : 0;
     if (greedy) {
-        hipLaunchKernelGGL(init_seq_kernel, dim3(64), dim3(256), 0, s, d.seq, d.finished, d.lens, R, Lm, c.bos, c.pad);
+        if (prompt) TRY(launch_init_prompt_seq(d.seq, d.finished, d.lens, R, Lm, prompt, prompt_rows, Pn, c.vocab, c.pad, s));
+        else hipLaunchKernelGGL(init_seq_kernel, dim3(64), dim3(256), 0, s, d.seq, d.finished, d.lens, R, Lm, c.bos, c.pad);
         if (compact) {
             d.map.live = m->live; d.map.n = m->n_live;
             TRY(launch_compact_rows(d.finished, R, m->live, m->n_live, s));
@@ -1740,7 +1810,16 @@ int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm
                       "it takes at most 32 (automatic selection continues on the batch kernels from position 33)", Lm, Lm - 1);
         return -1;
     }
-    for (int t = 0; t + 1 < Lm; ++t) {
+    m->last_prefill_passes = 0;
+    if (t0 > 0) {
+        // the whole batch in one pass where the workspace holds it (CapConfig.max_prompt), else as many captions at a time as it does
+        const int per = (int)std::min<size_t>((size_t)R, m->ws_rows / (size_t)t0);
+        for (int c0 = 0; c0 < R; c0 += per) {
+            TRY(run_prefill(m, d, c0, std::min(per, R - c0), t0, Lm, s));
+            ++m->last_prefill_passes;
+        }
+    }
+    for (int t = t0; t + 1 < Lm; ++t) {
         const int cur_len = t + 1;
         m->last_steps = t + 1;
         const int* tokens = greedy ? d.seq : beam_running_tokens_p(d.beam, B, K, Lm, cur_len & 1);
@@ -1758,14 +1837,14 @@ int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm
         }
         if (out_step_logits) {
             hipLaunchKernelGGL(copy_logits_kernel, dim3(1024), dim3(256), 0, s, d.logits, m->ldl,
-                               out_step_logits + (size_t)t * R * c.vocab, R, c.vocab);
+                               out_step_logits + (size_t)(t - t0) * R * c.vocab, R, c.vocab);
             CAP_HIP_CHECK(hipGetLastError());
         }
         ProfScope ps(m, s, greedy ? "greedy_select" : "beam_step", 0, (double)R * c.vocab * 4);
         if (greedy)
         {
             TRY(launch_greedy_select(d.logits, m->ldl, c.vocab, d.seq, Lm, t, Lm, c.eos, c.pad, d.finished, d.lens, R, s,
-                                     coca ? c.min_len : 0, coca ? 1 : 0, d.map, out_lp, Lm - 1, t, out_scored, out_vocab, acc_ld));
+                                     coca ? c.min_len : 0, coca ? 1 : 0, d.map, out_lp, Lm - 1, t - t0, out_scored, out_vocab, acc_ld));
             if (compact) TRY(launch_compact_rows(d.finished, R, m->live, m->n_live, s));
         }
         else
@@ -1905,6 +1984,11 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
         }
         if (cfg->v_hidden % 64 || cfg->v_mlp % 64 || cfg->t_ffn % 64) { cap_set_error("cap_create: widths must be multiples of 64"); return -1; }
     }
+    if (cfg->max_prompt != 0 && (cfg->arch != CAP_ARCH_BLIP || cfg->max_prompt < 2 || cfg->max_prompt > CAP_MAX_PROMPT)) {
+        cap_set_error("cap_create: max_prompt %d - prompt capacity is CAP_ARCH_BLIP's, 0 (none) or 2 .. %d tokens (BOS included)",
+                      cfg->max_prompt, CAP_MAX_PROMPT);
+        return -1;
+    }
     if (cfg->weight_int8) {
         const int T = cfg->t_hidden, G = cfg->t_ffn;
         if (cfg->weight_int8 != 1 || cfg->arch != CAP_ARCH_BLIP2 || cfg->compute_dtype != CAP_BF16) {
@@ -1922,7 +2006,7 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
     if (share) {
         // same model, same arithmetic, same GPU; only the capacity of the arena may differ
         CapConfig a = *cfg, b = share->c;
-        a.max_batch = b.max_batch = 0; a.max_beams = b.max_beams = 0; a.max_len = b.max_len = 0;
+        a.max_batch = b.max_batch = 0; a.max_beams = b.max_beams = 0; a.max_len = b.max_len = 0; a.max_prompt = b.max_prompt = 0;
         if (memcmp(&a, &b, sizeof(a)) != 0 || share->ws->device != dev) {
             cap_set_error("cap_create_shared: the new handle must describe the same model, compute dtype and GPU as the handle "
                           "whose weights it shares");
@@ -2280,6 +2364,53 @@ int cap_generate_vocab(CapHandle h, const void* pixels, int pixel_fmt, int B, in
     return run_generate(m, pixels, pixel_fmt, B, 1, max_len, 1.0f, out_ids, out_len, nullptr, out_step_logits, (hipStream_t)stream, false,
                         out_logprobs, out_scored, out_vocab, acc_ld);
 }
+
+int cap_generate_prompted(CapHandle h, const void* pixels, int pixel_fmt, int B, int max_len, const int32_t* prompt_ids, int prompt_rows,
+                          int prompt_len, int32_t* out_ids, int32_t* out_len, float* out_step_logits, float* out_logprobs,
+                          int32_t* out_scored, float* out_vocab, int acc_ld, void* stream) {
+    Captioner* m = (Captioner*)h;
+    TRY(check_call(m, B, 1, max_len, pixel_fmt));
+    if (!pixels || !out_ids || !prompt_ids) { cap_set_error("cap_generate_prompted: null buffer"); return -1; }
+    if (m->c.arch != CAP_ARCH_BLIP) {
+        cap_set_error("cap_generate_prompted: a text prompt is taken by CAP_ARCH_BLIP handles (this handle's arch is %d: CoCa's `text=` and "
+                      "BLIP-2's prompt are not built)", m->c.arch);
+        return -1;
+    }
+    if (prompt_rows != 1 && prompt_rows != B) {
+        cap_set_error("cap_generate_prompted: prompt_rows %d is neither 1 (shared) nor the batch size %d", prompt_rows, B);
+        return -1;
+    }
+    if (prompt_len > CAP_MAX_PROMPT) {
+        cap_set_error("cap_generate_prompted: prompt_len %d exceeds the limit of %d prompt tokens (BOS included)", prompt_len, CAP_MAX_PROMPT);
+        return -1;
+    }
+    if (prompt_len < 2 || prompt_len >= max_len) {
+        cap_set_error("cap_generate_prompted: prompt_len %d must be in [2, max_len = %d): BOS plus at least one token, and room for one "
+                      "generated token", prompt_len, max_len);
+        return -1;
+    }
+    if ((size_t)(prompt_len - 1) > m->ws_rows) {
+        cap_set_error("cap_generate_prompted: prompt_len %d exceeds the limit of %zu tokens this handle's workspace (%zu rows) takes: "
+                      "create it with CapConfig.max_prompt >= %d", prompt_len, m->ws_rows + 1, m->ws_rows, prompt_len);
+        return -1;
+    }
+    if ((out_logprobs != nullptr) != (out_scored != nullptr)) {
+        cap_set_error("cap_generate_prompted: out_logprobs and out_scored come together (both or neither)");
+        return -1;
+    }
+    if (out_vocab) {
+        if (!out_logprobs) { cap_set_error("cap_generate_prompted: out_vocab needs out_logprobs and out_scored"); return -1; }
+        if (acc_ld < m->c.vocab || acc_ld % 4 != 0 || ((uintptr_t)out_vocab & 15) != 0) {
+            cap_set_error("cap_generate_prompted: out_vocab needs acc_ld >= vocab (%d), acc_ld %% 4 == 0 (got %d) and a 16-byte aligned pointer",
+                          m->c.vocab, acc_ld);
+            return -1;
+        }
+    }
+    return run_generate(m, pixels, pixel_fmt, B, 1, max_len, 1.0f, out_ids, out_len, nullptr, out_step_logits, (hipStream_t)stream, false,
+                        out_logprobs, out_scored, out_vocab, acc_ld, prompt_ids, prompt_rows, prompt_len);
+}
+
+int cap_last_prefill_passes(CapHandle h) { return h ? ((Captioner*)h)->last_prefill_passes : -1; }
 
 int cap_generate(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int max_len, float length_penalty,
                  int32_t* out_ids, int32_t* out_len, float* out_scores, float* out_step_logits, void* stream) {

@@ -262,14 +262,12 @@ __global__ __launch_bounds__(256) void reduce_layernorm_wide_kernel(const float*
     }
 }
 
+// One decoder embedding row: LayerNorm(word[tok] + pos[t]) -> out_t / out_f row `row`, the raw sum -> y_out (pre-LN residual stream).
+// The single step (embed_kernel) and the prompt prefill (embed_prompt_kernel) both run THIS body: same loads, sums and LayerNorm.
 template <typename T>
-__global__ __launch_bounds__(256) void embed_kernel(const int* __restrict__ seq, int seq_ld, int t,
-                                                    const float* __restrict__ word, const float* __restrict__ pos,
-                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                    float eps, T* out_t, float* out_f, float* y_out, int R, int D, RowMap map) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;      // (compact) output row
-    if (row >= R || (map.n && row >= *map.n)) return;
-    const int tok = seq[(size_t)(map.live ? map.live[row] : row) * seq_ld + t];
+__device__ __forceinline__ void embed_row(int tok, int t, int row, int lane, const float* __restrict__ word, const float* __restrict__ pos,
+                                          const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* out_t,
+                                          float* out_f, float* y_out, int D) {
     const int nv = (D + 255) / 256;
     float4 v[LN_MAXV];
     const float* w = word + (size_t)tok * D;
@@ -285,6 +283,41 @@ __global__ __launch_bounds__(256) void embed_kernel(const int* __restrict__ seq,
     }
     ln_row<T>(v, nv, lane, D, gamma, beta, eps, out_t ? out_t + (size_t)row * D : nullptr,
               out_f ? out_f + (size_t)row * D : nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void embed_kernel(const int* __restrict__ seq, int seq_ld, int t,
+                                                    const float* __restrict__ word, const float* __restrict__ pos,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                    float eps, T* out_t, float* out_f, float* y_out, int R, int D, RowMap map) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;      // (compact) output row
+    if (row >= R || (map.n && row >= *map.n)) return;
+    const int tok = seq[(size_t)(map.live ? map.live[row] : row) * seq_ld + t];
+    embed_row<T>(tok, t, row, lane, word, pos, gamma, beta, eps, out_t, out_f, y_out, D);
+}
+
+// Prompt prefill (captioner.hip, run_prefill): the rows of several KNOWN positions at once.  Row r of the launch is position
+// r % npos of caption row0 + r / npos (caption-major: the npos rows of an image are adjacent, as the beams of an image are).
+template <typename T>
+__global__ __launch_bounds__(256) void embed_prompt_kernel(const int* __restrict__ seq, int seq_ld, int npos, int row0,
+                                                           const float* __restrict__ word, const float* __restrict__ pos,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float eps, T* out_t, float* out_f, float* y_out, int R, int D) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= R) return;
+    const int cap = row0 + row / npos, t = row - (row / npos) * npos;
+    embed_row<T>(seq[(size_t)cap * seq_ld + t], t, row, lane, word, pos, gamma, beta, eps, out_t, out_f, y_out, D);
+}
+
+// The sequence rows of a prompted greedy call: columns 0 .. P - 1 the prompt (one row shared by every caption, or one row per
+// caption), pad after it; ids are caller data and are clamped to the table, so nothing outside it is ever gathered.
+__global__ void init_prompt_seq_kernel(int* seq, int* fin, int* len, int R, int L, const int* __restrict__ prompt, int prompt_rows,
+                                       int P, int V, int pad) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < R * L; i += gridDim.x * blockDim.x) {
+        const int r = i / L, j = i - r * L;
+        seq[i] = j < P ? min(max(prompt[(size_t)(prompt_rows == 1 ? 0 : r) * P + j], 0), V - 1) : pad;
+    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < R; i += gridDim.x * blockDim.x) { fin[i] = 0; len[i] = L; }
 }
 
 // Sentence-encoder input embeddings (HF BertEmbeddings, HF:models/bert/modeling_bert.py `BertEmbeddings.forward`):
@@ -828,6 +861,33 @@ int launch_embed(int dtype, const int* seq, int seq_ld, int t, const float* word
 #define CAP_EM(TT) hipLaunchKernelGGL(embed_kernel<TT>, dim3((R + 3) / 4), dim3(256), 0, s, seq, seq_ld, t, word, pos, gamma, beta, eps, (TT*)out_t, out_f, y_out, R, D, map)
     CAP_DISPATCH_T(dtype, CAP_EM);
 #undef CAP_EM
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_embed_prompt(int dtype, const int* seq, int seq_ld, int npos, int row0, const float* word, const float* pos,
+                        const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int n_caps, int D,
+                        hipStream_t s, float* y_out) {
+    if (D % 4 != 0 || D > 256 * LN_MAXV) { cap_set_error("embed_prompt: unsupported width %d", D); return -1; }
+    if (npos < 1 || npos > seq_ld || n_caps < 1 || row0 < 0) {
+        cap_set_error("embed_prompt: %d positions of %d captions from row %d do not fit rows of %d tokens", npos, n_caps, row0, seq_ld);
+        return -1;
+    }
+    const int R = n_caps * npos;
+#define CAP_EMP(TT) hipLaunchKernelGGL(embed_prompt_kernel<TT>, dim3((R + 3) / 4), dim3(256), 0, s, seq, seq_ld, npos, row0, word, pos, gamma, beta, eps, (TT*)out_t, out_f, y_out, R, D)
+    CAP_DISPATCH_T(dtype, CAP_EMP);
+#undef CAP_EMP
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_init_prompt_seq(int* seq, int* finished, int* out_len, int R, int L, const int* prompt, int prompt_rows, int P, int V,
+                           int pad, hipStream_t s) {
+    if (!prompt || P < 1 || P > L || (prompt_rows != 1 && prompt_rows != R) || V < 1) {
+        cap_set_error("init_prompt_seq: a prompt of %d rows x %d tokens does not fit %d rows of %d tokens", prompt_rows, P, R, L);
+        return -1;
+    }
+    hipLaunchKernelGGL(init_prompt_seq_kernel, dim3(64), dim3(256), 0, s, seq, finished, out_len, R, L, prompt, prompt_rows, P, V, pad);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -48,6 +48,14 @@ int launch_embed(int dtype, const int* seq, int seq_ld, int t, const float* word
                  const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int R, int D,
                  hipStream_t s, float* y_out = nullptr,    // y_out: the un-normalised sum (pre-LN residual stream)
                  RowMap map = RowMap());                    // compact output row c reads the token of row map.live[c]
+// prompt prefill: launch_embed for n_caps * npos rows at once - row r = position r % npos of caption row0 + r / npos (token
+// seq[caption * seq_ld + position], absolute position embedding pos[position]); the arithmetic of launch_embed, bit for bit
+int launch_embed_prompt(int dtype, const int* seq, int seq_ld, int npos, int row0, const float* word, const float* pos,
+                        const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int n_caps, int D,
+                        hipStream_t s, float* y_out = nullptr);
+// seq [R, L] = the prompt (prompt int32 [prompt_rows, P], prompt_rows 1 or R, ids clamped to [0, V)) then pad; finished = 0, len = L
+int launch_init_prompt_seq(int* seq, int* finished, int* out_len, int R, int L, const int* prompt, int prompt_rows, int P, int V,
+                           int pad, hipStream_t s);
 // greedy selection: argmax (lowest index wins ties), pad after EOS, append at seq[row][t+1], track finished/len
 int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos,
                          int pad, int* finished, int* out_len, int R, hipStream_t s, int min_len = 0, int force_eos = 0,
@@ -121,6 +129,14 @@ struct DecodeAttn {                    // zero-initialise (memset), then fill
                                        // (wave / online kernels, impl 0)
 };
 int launch_decode_attention(int dtype, const DecodeAttn& a, hipStream_t s);
+// Self-attention of a prompt prefill: n_caps * npos rows, row r = position r % npos of caption row0 + r / npos, its fused q|k|v
+// projection as split-K partial sums part fp32 [S][n_caps * npos][part_ld] (+ bias [3 H 64]).  Two launches: every row's k / v are
+// finished and written to positions 0 .. npos - 1 of the caption's own cache row (kbase / vbase [.][H][kv_ld][64], dtype), then row
+// (c, p) attends keys 0 .. p through decode_attn.h's wave unit with the key count the single step at position p has - the context
+// and the caches have the bits npos calls of launch_decode_attention (append_kv) would have left.  npos <= PREFILL_MAX_POS.
+constexpr int PREFILL_MAX_POS = 31;
+int launch_prefill_self_attention(int dtype, const float* part, int S, const float* bias, int part_ld, void* kbase, void* vbase,
+                                  int kv_ld, void* out, int out_dtype, int n_caps, int npos, int row0, int H, hipStream_t s);
 // fp32 rows [n_rows, 64] -> one KV16 block of kv16_block_bytes(n_rows) bytes: what the cross-K/V GEMM's epilogue writes, as a
 // kernel of its own (tests)
 int launch_pack_kv16(const float* src, void* dst, size_t n_rows, hipStream_t s);

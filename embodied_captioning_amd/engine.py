@@ -9,6 +9,7 @@ import ctypes as C
 import json
 import logging
 import math
+import numbers
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -72,13 +73,73 @@ def fusion_max_tokens(steps: int, th: float, vocab: int) -> int:
     return max(1, min(int(vocab), int(math.ceil(steps / th))))
 
 
+def prompt_token_limit(max_batch: int, max_beams: int = 1, max_prompt: int = 0) -> int:
+    """Longest prompt (tokens, BOS included) an engine of that capacity takes: a prompt of P tokens runs P - 1 prefill rows per
+    caption through the decoder's pass buffers, which hold max(max_batch * max_beams, max_batch * (max_prompt - 1)) rows; never
+    more than the library's CAP_MAX_PROMPT.  With max_prompt >= P a full batch is one pass, else captions go in chunks."""
+    rows = max(int(max_batch) * int(max_beams), int(max_batch) * max(int(max_prompt) - 1, 0))
+    return min(N.CAP_MAX_PROMPT, rows + 1)
+
+
+def _arch_family(arch) -> str:
+    return "coca" if isinstance(arch, CocaArch) else "blip2" if isinstance(arch, Blip2Arch) else "blip"
+
+
+def validate_prompt_ids(prompt_ids, arch, batch: int, max_length: int, num_beams: int = 1, num_beam_groups: Optional[int] = None,
+                        limit: int = N.CAP_MAX_PROMPT) -> torch.Tensor:
+    """The host check of `generate(..., prompt_ids=)`: a list or tensor [P], [1, P] or [batch, P] -> int32 host tensor [rows, P],
+    rows 1 (shared) or batch.  Raises, naming the fault, BEFORE anything is uploaded or launched: a prompt for an architecture that
+    takes none (CoCa's `text=`, BLIP-2), beam search, an id outside [0, vocab), column 0 not BOS, EOS or pad inside the prompt, P
+    outside [2, limit] or not below max_length, a row count that is neither 1 nor the batch.  Needs no GPU."""
+    fam = _arch_family(arch)
+    if fam == "coca":
+        raise ValueError("prompt_ids: a text prompt for a CoCa handle is not built (the reference's `text=`, coca_model.py:207, stays "
+                         "refused); prompts are BLIP's")
+    if fam == "blip2":
+        raise ValueError("prompt_ids: a text prompt for a BLIP-2 handle is not built (HF `Blip2ForConditionalGeneration.generate("
+                         "input_ids=)`); prompts are BLIP's")
+    if num_beam_groups is not None or int(num_beams) != 1:
+        raise ValueError(f"prompt_ids: a prompt is taken by greedy decoding only; num_beams = {num_beams}"
+                         + (f", num_beam_groups = {num_beam_groups}" if num_beam_groups is not None else "") + " is beam search")
+    t = torch.as_tensor(prompt_ids)
+    if t.is_floating_point() or t.dtype == torch.bool or t.is_complex():
+        raise ValueError(f"prompt_ids must hold integer token ids, got dtype {t.dtype}")
+    t = t.detach().cpu().to(torch.int64)
+    if t.dim() == 1:
+        t = t[None, :]
+    if t.dim() != 2:
+        raise ValueError(f"prompt_ids must be [P], [1, P] or [batch, P], got shape {tuple(t.shape)}")
+    rows, P = int(t.shape[0]), int(t.shape[1])
+    if rows != 1 and rows != int(batch):
+        raise ValueError(f"prompt_ids has {rows} rows: the row count must be 1 (one prompt for every caption) or the batch size {batch}")
+    if P < 2:
+        raise ValueError(f"prompt_ids has {P} token(s) per row: a prompt is BOS plus at least one token (P >= 2)")
+    if P > int(limit):
+        raise ValueError(f"prompt_ids has {P} tokens per row: too long, the limit is {limit} tokens (BOS included) for this engine")
+    if P >= int(max_length):
+        raise ValueError(f"prompt_ids has {P} tokens per row but max_length is {max_length}: max_length counts the prompt and must "
+                         f"leave room for a generated token (P < max_length)")
+    lo, hi = int(t.min()), int(t.max())
+    if lo < 0 or hi >= arch.vocab:
+        raise ValueError(f"prompt_ids holds token id {lo if lo < 0 else hi}, out of range [0, {arch.vocab}) of the vocabulary")
+    if bool((t[:, 0] != arch.bos).any()):
+        raise ValueError(f"prompt_ids column 0 must be BOS ({arch.bos}) in every row, got {sorted(set(t[:, 0].tolist()))[:4]}")
+    for name, tid in (("EOS", arch.eos), ("pad", arch.pad)):
+        if bool((t[:, 1:] == tid).any()):
+            raise ValueError(f"prompt_ids holds the {name} token ({tid}) inside the prompt: a prompt is an open caption prefix")
+    return t.to(torch.int32).contiguous()
+
+
 class CaptionerEngine:
     """One handle = one model replica on one GPU, bound to torch's current stream of `device` at each call."""
 
     def __init__(self, arch: BlipArch, dtype: str = "bf16", max_batch: int = 8, max_beams: int = 1,
                  max_len: int = 20, device: str | torch.device = "cuda:0", share_weights_with: "CaptionerEngine | None" = None,
-                 cross_cache: str = "auto", weight_int8: bool = False):
-        """weight_int8 (BLIP-2, dtype "bf16" only): the reference's `load_in_8bit=True` (blip2.py:19-22) - the OPT decoder layers' Linear
+                 cross_cache: str = "auto", weight_int8: bool = False, max_prompt: int = 0):
+        """max_prompt (BLIP): prompt capacity - with max_prompt >= P the P - 1 prompt positions of a FULL batch run through the decoder
+        as one prefill pass (`generate(prompt_ids=)`); 0 reserves nothing (the arena is what it always was) and a prompted batch
+        is prefilled in chunks of as many captions as the decode rows hold (`prompt_limit` = the longest prompt taken).
+        weight_int8 (BLIP-2, dtype "bf16" only): the reference's `load_in_8bit=True` (blip2.py:19-22) - the OPT decoder layers' Linear
         weights are kept as row-quantised int8 + fp32 row scales (bitsandbytes' storage) and streamed as bytes by the decode GEMMs,
         the vision tower's Linears and language_projection pass through the same quantiser at load; activations stay bf16.
         cross_cache: "auto" = the mode's own cross-attention K/V cache ("f32s": KV16 - int16 + one scale per 64-wide head row,
@@ -94,9 +155,14 @@ class CaptionerEngine:
         self.dtype = dtype
         self.device = torch.device(device)
         self.max_batch, self.max_beams, self.max_len = max_batch, max_beams, max_len
+        self.max_prompt = int(max_prompt)
+        if self.max_prompt and (_arch_family(arch) != "blip" or not 2 <= self.max_prompt <= N.CAP_MAX_PROMPT):
+            raise ValueError(f"max_prompt = {max_prompt}: prompt capacity is BLIP's, 0 or 2..{N.CAP_MAX_PROMPT} tokens (BOS included)")
+        self.prompt_limit = prompt_token_limit(max_batch, max_beams, self.max_prompt)
         cfg = N.CapConfig()
         cfg.struct_size = C.sizeof(N.CapConfig)
         cfg.compute_dtype = _DTYPES[dtype]
+        cfg.max_prompt = self.max_prompt
         cfg.image_size, cfg.patch_size = arch.image_size, arch.patch_size
         self.is_coca = isinstance(arch, CocaArch)
         self.is_blip2 = isinstance(arch, Blip2Arch)
@@ -204,6 +270,11 @@ class CaptionerEngine:
         return int(self.lib.cap_last_row_compaction(self._h)) == 1
 
     @property
+    def last_prefill_passes(self) -> int:
+        """Prefill passes of the last prompted generate: 1 = the whole batch at once (0 after an unprompted call)."""
+        return int(self.lib.cap_last_prefill_passes(self._h))
+
+    @property
     def last_decode_path(self) -> str:
         return {0: "none", 1: "batch", 2: "small"}[int(self.lib.cap_last_decode_path(self._h))]
 
@@ -297,8 +368,14 @@ class CaptionerEngine:
 
     def generate(self, pixels: torch.Tensor, num_beams: int = 1, max_length: Optional[int] = None,
                  length_penalty: float = 1.0, output_logits: bool = False, num_beam_groups: Optional[int] = None,
-                 output_logprobs: bool = False, output_vocab_maxprob: bool = False, **sampling_options) -> Dict[str, torch.Tensor]:
-        """Returns device tensors: sequences int32 [B, max_length] (incl. BOS), lengths int32 [B],
+                 output_logprobs: bool = False, output_vocab_maxprob: bool = False, prompt_ids=None,
+                 **sampling_options) -> Dict[str, torch.Tensor]:
+        """prompt_ids (BLIP, greedy): a host list / tensor [P], [1, P] (one prompt for every caption) or [B, P] (one per caption), column
+        0 = BOS - HF `BlipForConditionalGeneration.generate(pixel_values, input_ids=...)`, whose decoder receives input_ids[:, :-1].
+        Validated on the host (`validate_prompt_ids`).  max_length counts the prompt; `sequences` start with it and `lengths`
+        include it; `logits` ([max_length - P, B, vocab]), `token_logprobs`, `scored_steps` and `vocab_maxprob` cover the GENERATED
+        steps only (entry j = the j-th generated token; the tail of a token_logprobs row stays zero).
+        Returns device tensors: sequences int32 [B, max_length] (incl. BOS), lengths int32 [B],
         sequences_scores fp32 [B] (beams only), logits fp32 [max_length-1, B*num_beams, vocab] (optional).
         BLIP-2: max_length counts NEW tokens (HF max_new_tokens); sequences are those new tokens only (no image
         placeholders / BOS), logits [max_length, B, vocab].
@@ -324,15 +401,20 @@ class CaptionerEngine:
             if unknown:
                 raise TypeError(f"generate() got unexpected keyword argument(s) {unknown}")
             reject_unsupported_generation_options(sampling_options, "CaptionerEngine.generate")
+        L = max_length or self.max_len
+        prompt = None
+        if prompt_ids is not None:               # host check first: nothing unvalidated is uploaded or gathered from
+            prompt = validate_prompt_ids(prompt_ids, self.arch, int(pixels.shape[0]), L, num_beams, num_beam_groups, self.prompt_limit)
         pixels, fmt = self._pixels(pixels)
         B = pixels.shape[0]
-        L = max_length or self.max_len
         ids = torch.empty((B, L), dtype=torch.int32, device=self.device)
         lens = torch.empty((B,), dtype=torch.int32, device=self.device)
         scores = torch.zeros((B,), dtype=torch.float32, device=self.device)
         logits = None
         if output_logits:
             steps = L if getattr(self, "is_blip2", False) else L - 1
+            if prompt is not None:
+                steps = L - int(prompt.shape[1])
             # zeros, not empty: with early exit the steps after the last executed one are never written (callers see 0, not
             # stale memory); `last_decode_steps` tells how many steps ran
             logits = torch.zeros((steps, B * num_beams, self.arch.vocab), dtype=torch.float32, device=self.device)
@@ -358,7 +440,19 @@ class CaptionerEngine:
                                                      C.c_void_p(scores.data_ptr()), C.c_void_p(_stream_ptr(self.device))), "cap_generate_groups")
             return {"sequences": ids, "lengths": lens, "sequences_scores": scores}
         with torch.cuda.device(self.device):
-            if vmax is not None:
+            if prompt is not None:
+                prompt_d = prompt.to(self.device, non_blocking=False)
+                N.check(self.lib.cap_generate_prompted(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, L, C.c_void_p(prompt_d.data_ptr()),
+                                                       int(prompt.shape[0]), int(prompt.shape[1]), C.c_void_p(ids.data_ptr()),
+                                                       C.c_void_p(lens.data_ptr()),
+                                                       C.c_void_p(logits.data_ptr() if logits is not None else 0),
+                                                       C.c_void_p(lps.data_ptr() if lps is not None else 0),
+                                                       C.c_void_p(scored.data_ptr() if scored is not None else 0),
+                                                       C.c_void_p(vmax.data_ptr() if vmax is not None else 0),
+                                                       vmax.shape[1] if vmax is not None else 0,
+                                                       C.c_void_p(_stream_ptr(self.device))), "cap_generate_prompted")
+                prompt_d.record_stream(torch.cuda.current_stream(self.device))
+            elif vmax is not None:
                 N.check(self.lib.cap_generate_vocab(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, L, C.c_void_p(ids.data_ptr()),
                                                     C.c_void_p(lens.data_ptr()),
                                                     C.c_void_p(logits.data_ptr() if logits is not None else 0),
@@ -558,6 +652,52 @@ class EnginePool:
         return plan
 
     @classmethod
+    def coalesce_plan_prompted(cls, rows: Sequence[int], n_engines: int, max_rows: int, prompt_lens: Sequence[int]) -> List[List[int]]:
+        """`coalesce_plan` for prompted batches: every row of a pass has the same prompt length, so only consecutive batches whose
+        prompt lengths agree are ever merged - each run of equal lengths is planned on its own."""
+        if len(prompt_lens) != len(rows):
+            raise ValueError(f"{len(prompt_lens)} prompt lengths for {len(rows)} batches")
+        plan: List[List[int]] = []
+        i = 0
+        while i < len(rows):
+            j = i
+            while j < len(rows) and prompt_lens[j] == prompt_lens[i]:
+                j += 1
+            plan += [[i + k for k in g] for g in cls.coalesce_plan(list(rows[i:j]), n_engines, max_rows)]
+            i = j
+        return plan
+
+    @staticmethod
+    def merge_prompts(plan: Sequence[Sequence[int]], rows: Sequence[int], prompts: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+        """The prompt of every merged pass of `plan`: prompts[j] is batch j's validated [1, P] or [rows[j], P] tensor.  A pass whose
+        batches all carry the same single row keeps that one row; otherwise every batch's prompt is expanded to its rows and the rows
+        are concatenated in plan order - the order the frames are concatenated in."""
+        out = []
+        for g in plan:
+            ps = [prompts[j] for j in g]
+            if len({int(p.shape[1]) for p in ps}) != 1:
+                raise ValueError(f"batches {list(g)} of one pass have prompts of different lengths {[int(p.shape[1]) for p in ps]}")
+            if all(p.shape[0] == 1 and torch.equal(p, ps[0]) for p in ps):
+                out.append(ps[0])
+            else:
+                out.append(torch.cat([p.expand(rows[j], p.shape[1]) if p.shape[0] == 1 else p for j, p in zip(g, ps)], dim=0).contiguous())
+        return out
+
+    @staticmethod
+    def _per_batch_prompts(prompt_ids, n_batches: int) -> list:
+        """One shared prompt - a TENSOR / array ([P] or [1, P]) or a FLAT list of ints - -> the same object for every batch.  A list /
+        tuple whose elements are not ints is ALWAYS read as one prompt per batch (each [P], [1, P] or that batch's [rows, P]) and its
+        length must be the number of batches: a shared prompt is never written as a nested list, and rows of one [B, P] prompt
+        cannot span batches (every batch brings its own rows)."""
+        if isinstance(prompt_ids, (list, tuple)) and len(prompt_ids) and not isinstance(prompt_ids[0], numbers.Integral):
+            if len(prompt_ids) != n_batches:
+                raise ValueError(f"prompt_ids is a list of {len(prompt_ids)} prompts for {n_batches} batches: a list of prompts is read "
+                                 f"as one prompt per batch; give one shared prompt as a flat list of ints or a tensor, or one prompt "
+                                 f"per batch")
+            return list(prompt_ids)
+        return [prompt_ids] * n_batches
+
+    @classmethod
     def split_merged_outputs(cls, plan: Sequence[Sequence[int]], rows: Sequence[int], outs_m: Sequence[dict]) -> list:
         """The outputs of the merged passes of `plan` (one dict per pass, every value with the pass's rows leading) cut back into one
         dict per original batch; rows[j] = rows of batch j."""
@@ -574,7 +714,9 @@ class EnginePool:
         return outs
 
     def generate_many(self, batches, threads: bool = False, coalesce_rows: int = 0, **generate_kw):
-        """All batches, in order.  threads=True: one host thread per engine (batch j goes to engine j % n) - needed when
+        """prompt_ids= (BLIP): one shared prompt as a flat list of ints or a tensor, or a list with one prompt per batch
+        (`_per_batch_prompts`); batches merge into a pass only when their prompt lengths agree.
+        All batches, in order.  threads=True: one host thread per engine (batch j goes to engine j % n) - needed when
         the engines poll for early exit (cap_set_early_exit synchronises its stream: from a single host thread that would
         stall the launches of the other streams; ctypes releases the GIL during cap_generate, so the threads do overlap).
         coalesce_rows > 0: dynamic batching - consecutive batches of the same frame shape are concatenated into passes of at most
@@ -584,6 +726,17 @@ class EnginePool:
         costs are paid once per pass: 256-frame batches on 3 engines 6 010 captions/s, merged to 1024 rows 6 600 (round 6)."""
         batches = list(batches)
         self.last_coalesce = None            # what the last call did with coalesce_rows: the plan, or why it was not applied
+        prompts = None
+        if generate_kw.get("prompt_ids") is not None:
+            # one shared prompt or one prompt per batch; validated here on the host, once, against the batch it belongs to
+            e0 = self.engines[0]
+            L = generate_kw.get("max_length") or e0.max_len
+            given = self._per_batch_prompts(generate_kw.pop("prompt_ids"), len(batches))
+            prompts = [validate_prompt_ids(p, e0.arch, int(b.shape[0]), L, generate_kw.get("num_beams", 1),
+                                           generate_kw.get("num_beam_groups"), min(e.prompt_limit for e in self.engines))
+                       for p, b in zip(given, batches)]
+        else:
+            generate_kw.pop("prompt_ids", None)
         if coalesce_rows and len(batches) > 1:
             same = all(b.shape[1:] == batches[0].shape[1:] and b.dtype == batches[0].dtype and b.device == batches[0].device for b in batches)
             cap_rows = min(coalesce_rows, min(e.max_batch for e in self.engines))
@@ -592,16 +745,21 @@ class EnginePool:
             elif not same:
                 self.last_coalesce = "not applied: the batches differ in frame shape, dtype or device"
             else:
-                plan = self.coalesce_plan([int(b.shape[0]) for b in batches], len(self.engines), cap_rows)
+                rows = [int(b.shape[0]) for b in batches]
+                plan = (self.coalesce_plan(rows, len(self.engines), cap_rows) if prompts is None else
+                        self.coalesce_plan_prompted(rows, len(self.engines), cap_rows, [int(p.shape[1]) for p in prompts]))
                 if any(len(g) > 1 for g in plan):
                     merged = [batches[g[0]] if len(g) == 1 else torch.cat([batches[j] for j in g], dim=0) for g in plan]
+                    if prompts is not None:
+                        generate_kw = dict(generate_kw, prompt_ids=self.merge_prompts(plan, rows, prompts))
                     outs_m = self.generate_many(merged, threads=threads, **generate_kw)
                     self.last_coalesce = plan            # (the inner call cleared it)
                     return self.split_merged_outputs(plan, [int(b.shape[0]) for b in batches], outs_m)
                 self.last_coalesce = f"not applied: {len(batches)} batches on {len(self.engines)} engines leave nothing to merge within {cap_rows} rows"
             logger.debug("generate_many(coalesce_rows=%d) %s", coalesce_rows, self.last_coalesce)
+        kw_of = (lambda j: generate_kw) if prompts is None else (lambda j: dict(generate_kw, prompt_ids=prompts[j]))
         if not threads or len(self.engines) == 1 or len(batches) <= 1:
-            outs = [self.submit(b, **generate_kw) for b in batches]
+            outs = [self.submit(b, **kw_of(j)) for j, b in enumerate(batches)]
             self.join()
             return outs
         import threading
@@ -616,7 +774,7 @@ class EnginePool:
             try:
                 with torch.cuda.device(self.device), torch.cuda.stream(self.streams[i]):
                     for j in range(i, len(batches), n):
-                        outs[j] = self.engines[i].generate(batches[j], **generate_kw)
+                        outs[j] = self.engines[i].generate(batches[j], **kw_of(j))
                         if batches[j].is_cuda:
                             batches[j].record_stream(self.streams[i])
             except Exception as e:  # noqa: BLE001 - re-raised on the caller's thread

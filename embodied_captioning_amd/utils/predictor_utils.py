@@ -35,7 +35,7 @@ class Captioner(_Base):
         """Get the captioner model based on the configuration settings (reference :190-202)."""
         extra = {k: getattr(cfg, k) for k in ("num_beams", "max_length", "max_new_tokens", "dtype", "batch_size", "device",
                                               "streams", "early_exit_poll", "image_size", "num_beam_groups", "tokenizer_dir",
-                                              "coalesce_rows", "cross_cache", "strict_range")
+                                              "coalesce_rows", "cross_cache", "strict_range", "prompt", "prompt_ids", "max_prompt")
                  if hasattr(cfg, k)}
         captioner_cfg = Configuration(arch_name=cfg.arch_name, model_name=cfg.model_name,
                                       checkpoint_name=getattr(cfg, "checkpoint_name", None), height=cfg.height,
@@ -47,13 +47,16 @@ class Captioner(_Base):
         caption = out["text"]
         return caption
 
-    def caption_batch(self, images, return_perplexity: bool = False):
+    def caption_batch(self, images, return_perplexity: bool = False, prompt=None, prompt_ids=None):
         """Batched extension: list of PIL images / uint8 tensor -> list of captions; return_perplexity: -> (captions, float64 [n]
-        perplexities), the number the reference gets from `compute_perplexity()` after every one-crop call."""
+        perplexities), the number the reference gets from `compute_perplexity()` after every one-crop call.
+        prompt / prompt_ids (BLIP): the text prompt of this call instead of the configured captioner.prompt / captioner.prompt_ids
+        (which every call without them uses - the box driver's included)."""
+        kw = {k: v for k, v in (("prompt", prompt), ("prompt_ids", prompt_ids)) if v is not None}
         if return_perplexity:
-            out = self.model.generate_batch(images, output_perplexity=True)
+            out = self.model.generate_batch(images, output_perplexity=True, **kw)
             return out["texts"], out["perplexities"]
-        return self.model.generate_batch(images)["texts"]
+        return self.model.generate_batch(images, **kw)["texts"]
 
     @property
     def direct_resize_size(self):

@@ -18,6 +18,9 @@
  *                       minus the 32 image placeholders and BOS), logits as HF's `output_logits`
  *   caption embedding   agents/goal_exploration/goal_exploration.py:57,102 and                cap_embed_text
  *                       detector/pseudolabeler.py:568,677 `SentenceTransformer("all-MiniLM-L6-v2").encode(caption)`  (CAP_ARCH_MINILM handle)
+ *   text prompt         HF modeling_blip.py:858-932 `generate(pixel_values, input_ids=...)`    cap_generate_prompted (CAP_ARCH_BLIP, greedy:
+ *                       ("a picture of ..."; the decoder gets input_ids[:, :-1], column 0 = BOS);   the prompt positions run as one prefill pass),
+ *                       coca_model.py:207, 280-292 `generate(text=...)` is NOT built (refused)       CapConfig.max_prompt, cap_last_prefill_passes
  *   one crop per call   coca.py:27-33, blip2.py:24-29, goal_exploration.py:95-105,     cap_generate (rows <= 16: fused
  *                       pseudolabeler.py:673-676 (the callers hand over ONE image)      launches), cap_set_decode_path
  *   greedy stopping     HF generation/utils.py:2894-2937 (a finished row keeps its slot and   cap_set_row_compaction (the open
@@ -113,7 +116,13 @@ typedef struct CapConfig {
     int32_t weight_int8;
     /* CAP_ARCH_CLIP only: CAP_ACT_QUICK_GELU (0, the OpenAI checkpoints) or CAP_ACT_GELU (1) in both towers' MLPs. */
     int32_t hidden_act;
+    /* CAP_ARCH_BLIP only: prompt capacity of the arena.  0 (default): none reserved - the handle allocates exactly what it did before
+     * the field existed; cap_generate_prompted then runs the prefill over as many captions at a time as the decode workspace
+     * (max_batch x max_beams rows) holds.  2 .. CAP_MAX_PROMPT: the buffers a decoder pass works in hold max_batch x (max_prompt - 1)
+     * rows, so the prompt positions of a full batch are ONE pass (every decoder weight read once per prefill). */
+    int32_t max_prompt;
 } CapConfig;
+enum { CAP_MAX_PROMPT = 32 };   /* prompt tokens per caption, BOS included, cap_generate_prompted takes */
 
 const char* cap_last_error(void);
 int cap_version(void);
@@ -244,6 +253,30 @@ int cap_generate_scored(CapHandle h, const void* pixels, int pixel_fmt, int B, i
 int cap_generate_vocab(CapHandle h, const void* pixels, int pixel_fmt, int B, int max_len, int32_t* out_ids, int32_t* out_len,
                        float* out_step_logits, float* out_logprobs, int32_t* out_scored, float* out_vocab, int acc_ld,
                        void* stream);
+
+/* The greedy loop of cap_generate_scored / cap_generate_vocab started from a text PROMPT instead of the lone BOS (HF
+ * `BlipForConditionalGeneration.generate(pixel_values, input_ids=...)`, modeling_blip.py:858-932: the text decoder receives
+ * input_ids[:, :-1] with column 0 = BOS).  CAP_ARCH_BLIP, num_beams = 1; other architectures are refused by name.
+ *   prompt_ids  int32 [prompt_rows, prompt_len] (device)  the tokens every caption starts with, column 0 = BOS; prompt_rows = 1 (one
+ *               prompt shared by the batch) or B (row b for caption b).  Ids are the caller's to validate (engine.py does, on the
+ *               host); the library clamps them to [0, vocab) before any gather.
+ *   prompt_len  2 <= prompt_len < max_len, <= CAP_MAX_PROMPT (32), and prompt_len - 1 <= the handle's workspace rows
+ *               (max(max_batch x max_beams, max_batch x (max_prompt - 1))) - refused at entry, before any launch, with the limit named
+ *   max_len     counts the prompt, as HF's max_length does
+ *   out_ids     int32 [B, max_len]  rows START WITH the prompt;  out_len [B] includes it
+ *   out_step_logits fp32 [max_len - prompt_len, B, vocab], out_logprobs fp32 [B, max_len - 1], out_scored, out_vocab: the GENERATED steps
+ *               only - entry j is the j-th generated token (HF's `logits` tuple); the tail of an out_logprobs row stays zero
+ * Positions 0 .. prompt_len - 2 of all captions run through the decoder as one prefill pass (caption-major rows, no vocabulary GEMM,
+ * no token selection; in chunks of captions when the workspace is smaller than B x (prompt_len - 1) rows), which leaves the
+ * self-attention caches with the BITS the single steps would have written; the loop then starts at position prompt_len - 1 with
+ * everything cap_generate has (small-batch path, row compaction, early exit).  A caption prompted with its own unprompted prefix
+ * decodes to the bits of the unprompted call (tests/test_prompt_gpu.py).  out_logprobs / out_scored / out_vocab / out_step_logits /
+ * out_len may be NULL (out_vocab needs the log-prob pair). */
+int cap_generate_prompted(CapHandle h, const void* pixels, int pixel_fmt, int B, int max_len, const int32_t* prompt_ids, int prompt_rows,
+                          int prompt_len, int32_t* out_ids, int32_t* out_len, float* out_step_logits, float* out_logprobs,
+                          int32_t* out_scored, float* out_vocab, int acc_ld, void* stream);
+/* Prefill passes the last cap_generate_prompted on this handle ran (1 = the whole batch at once; 0 after an unprompted call). */
+int cap_last_prefill_passes(CapHandle h);
 
 /* CoCa's `_generate_beamsearch` with beam GROUPS (reference coca_model.py:335-482; `generate()` defaults num_beams = 6,
  * num_beam_groups = 3, :218-219): num_beams % num_beam_groups == 0, each group a beam search of num_beams / num_beam_groups
