@@ -815,6 +815,14 @@ int build_blip2(Captioner* m) {
     return 0;
 }
 
+// One post-LN sub-block over R rows: y = A W^T + b + x; x, x_t = LayerNorm(y)
+int qf_out_ln(Captioner* m, hipStream_t s, const char* tag, const void* A, int K, const void* W, const float* b, const float* g,
+              const float* be, float* x, float* y, void* x_t, int R) {
+    const int Q = m->c.q_hidden;
+    TRY(gemm(m, s, tag, A, K, W, K, y, Q, b, x, R, Q, K, 0, 1));
+    return launch_layernorm(m->gdt, y, Q, g, be, m->c.q_eps, x_t, x, R, Q, s);
+}
+
 // Q-Former over the image tokens (emb_t [B * NT, D]) -> qx_t [B * nq, Q]
 int run_qformer(Captioner* m, int B, hipStream_t s) {
     const CapConfig& c = m->c;
@@ -831,8 +839,7 @@ int run_qformer(Captioner* m, int B, hipStream_t s) {
             TRY(launch_generic_attention(m->dt, base, 3 * Q, (long)nq * 3 * Q, base + Q * e, 3 * Q, (long)nq * 3 * Q, base + 2 * Q * e, 3 * Q,
                                          (long)nq * 3 * Q, m->qctx, Q, (long)nq * Q, B, nq, nq, H, hd, -1, s, m->gdt));
         }
-        TRY(gemm(m, s, "qf_gemm_so", m->qctx, Q, L.w_so, Q, m->qy, Q, L.b_so, m->qx, R, Q, Q, 0, 1));
-        TRY(launch_layernorm(m->gdt, m->qy, Q, L.so_g, L.so_b, c.q_eps, m->qx_t, m->qx, R, Q, s));
+        TRY(qf_out_ln(m, s, "qf_gemm_so", m->qctx, Q, L.w_so, L.b_so, L.so_g, L.so_b, m->qx, m->qy, m->qx_t, R));
         if (L.cross) {
             TRY(gemm(m, s, "qf_gemm_cq", m->qx_t, Q, L.w_cq, Q, m->qqkv, Q, L.b_cq, nullptr, R, Q, Q, 0, af));
             TRY(gemm(m, s, "qf_gemm_ckv", m->emb_t, D, L.w_ckv, D, m->qkvimg, 2 * Q, L.b_ckv, nullptr, B * NT, 2 * Q, D, 0, af));
@@ -842,12 +849,10 @@ int run_qformer(Captioner* m, int B, hipStream_t s) {
                 TRY(launch_generic_attention(m->dt, m->qqkv, Q, (long)nq * Q, kv, 2 * Q, (long)NT * 2 * Q, kv + Q * e, 2 * Q, (long)NT * 2 * Q,
                                              m->qctx, Q, (long)nq * Q, B, nq, NT, H, hd, -1, s, m->gdt));
             }
-            TRY(gemm(m, s, "qf_gemm_co", m->qctx, Q, L.w_co, Q, m->qy, Q, L.b_co, m->qx, R, Q, Q, 0, 1));
-            TRY(launch_layernorm(m->gdt, m->qy, Q, L.co_g, L.co_b, c.q_eps, m->qx_t, m->qx, R, Q, s));
+            TRY(qf_out_ln(m, s, "qf_gemm_co", m->qctx, Q, L.w_co, L.b_co, L.co_g, L.co_b, m->qx, m->qy, m->qx_t, R));
         }
         TRY(gemm(m, s, "qf_gemm_f1", m->qx_t, Q, L.w_f1, Q, m->qh, F, L.b_f1, nullptr, R, F, Q, 1, 0));
-        TRY(gemm(m, s, "qf_gemm_f2", m->qh, F, L.w_f2, F, m->qy, Q, L.b_f2, m->qx, R, Q, F, 0, 1));
-        TRY(launch_layernorm(m->gdt, m->qy, Q, L.f_g, L.f_b, c.q_eps, m->qx_t, m->qx, R, Q, s));
+        TRY(qf_out_ln(m, s, "qf_gemm_f2", m->qh, F, L.w_f2, L.b_f2, L.f_g, L.f_b, m->qx, m->qy, m->qx_t, R));
     }
     return 0;
 }
@@ -910,14 +915,6 @@ int run_itm_images(Captioner* m, const void* pixels, int fmt, int B, hipStream_t
     return 0;
 }
 
-// One post-LN sub-block over R rows: y = A W^T + b + x; x, x_t = LayerNorm(y)
-int itm_out_ln(Captioner* m, hipStream_t s, const char* tag, const void* A, int K, const void* W, const float* b, const float* g,
-               const float* be, float* x, float* y, void* x_t, int R) {
-    const int Q = m->c.q_hidden;
-    TRY(gemm(m, s, tag, A, K, W, K, y, Q, b, x, R, Q, K, 0, 1));
-    return launch_layernorm(m->gdt, y, Q, g, be, m->c.q_eps, x_t, x, R, Q, s);
-}
-
 // The Q-Former over B pairs with nq query rows (0: none - the ITC text pass) and L text rows (0: none - the ITC image pass) each:
 // self-attention over [queries | the pair's text], cross-attention of the query rows to the cached image K/V on the cross layers,
 // the query rows through intermediate_query / output_query and the text rows through intermediate / output.  The two kinds of
@@ -941,8 +938,8 @@ int run_itm_qformer(Captioner* m, int B, int nq, int L, const int* ids, const in
             ProfScope ps(m, s, "itm_self_attn", 4.0 * B * H * (double)(nq + L) * (nq + L) * hd, (double)(Rq + Rt) * 4 * Q * e);
             TRY(launch_itm_self_attention(m->dt, m->qqkv, m->tqkv, lens, m->qctx, m->tctx, B, nq, L, H, hd, s, m->gdt));
         }
-        if (nq) TRY(itm_out_ln(m, s, "itm_gemm_so_q", m->qctx, Q, Ly.w_so, Ly.b_so, Ly.so_g, Ly.so_b, m->qx, m->qy, m->qx_t, Rq));
-        if (L) TRY(itm_out_ln(m, s, "itm_gemm_so_t", m->tctx, Q, Ly.w_so, Ly.b_so, Ly.so_g, Ly.so_b, m->tx, m->ty, m->tx_t, Rt));
+        if (nq) TRY(qf_out_ln(m, s, "itm_gemm_so_q", m->qctx, Q, Ly.w_so, Ly.b_so, Ly.so_g, Ly.so_b, m->qx, m->qy, m->qx_t, Rq));
+        if (L) TRY(qf_out_ln(m, s, "itm_gemm_so_t", m->tctx, Q, Ly.w_so, Ly.b_so, Ly.so_g, Ly.so_b, m->tx, m->ty, m->tx_t, Rt));
         if (Ly.cross) {
             const char* kv = (const char*)m->itm_ckv + slot++ * (size_t)c.max_batch * NT * 2 * Q * e;
             if (nq) {
@@ -952,171 +949,120 @@ int run_itm_qformer(Captioner* m, int B, int nq, int L, const int* ids, const in
                     TRY(launch_generic_attention(m->dt, m->qqkv, Q, (long)nq * Q, kv, 2 * Q, (long)NT * 2 * Q, kv + Q * e, 2 * Q, (long)NT * 2 * Q,
                                                  m->qctx, Q, (long)nq * Q, B, nq, NT, H, hd, -1, s, m->gdt));
                 }
-                TRY(itm_out_ln(m, s, "itm_gemm_co", m->qctx, Q, Ly.w_co, Ly.b_co, Ly.co_g, Ly.co_b, m->qx, m->qy, m->qx_t, Rq));
+                TRY(qf_out_ln(m, s, "itm_gemm_co", m->qctx, Q, Ly.w_co, Ly.b_co, Ly.co_g, Ly.co_b, m->qx, m->qy, m->qx_t, Rq));
             }
         }
         if (nq) {
             TRY(gemm(m, s, "itm_gemm_f1_q", m->qx_t, Q, Ly.w_f1, Q, m->qh, F, Ly.b_f1, nullptr, Rq, F, Q, 1, 0));
-            TRY(itm_out_ln(m, s, "itm_gemm_f2_q", m->qh, F, Ly.w_f2, Ly.b_f2, Ly.f_g, Ly.f_b, m->qx, m->qy, m->qx_t, Rq));
+            TRY(qf_out_ln(m, s, "itm_gemm_f2_q", m->qh, F, Ly.w_f2, Ly.b_f2, Ly.f_g, Ly.f_b, m->qx, m->qy, m->qx_t, Rq));
         }
         if (L) {
             TRY(gemm(m, s, "itm_gemm_f1_t", m->tx_t, Q, Ly.w_t1, Q, m->th, F, Ly.b_t1, nullptr, Rt, F, Q, 1, 0));
-            TRY(itm_out_ln(m, s, "itm_gemm_f2_t", m->th, F, Ly.w_t2, Ly.b_t2, Ly.t_g, Ly.t_b, m->tx, m->ty, m->tx_t, Rt));
+            TRY(qf_out_ln(m, s, "itm_gemm_f2_t", m->th, F, Ly.w_t2, Ly.b_t2, Ly.t_g, Ly.t_b, m->tx, m->ty, m->tx_t, Rt));
         }
     }
     return 0;
 }
 
-// OPT decoder over L new positions per row (x = ox [B * L, T] fp32 with positions already added), cached prefix of `past`
-// positions; leaves the logits of each row's last new position in m->logits.
-int opt_step_gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, const void* W, const float* bias, int act, void* out_t, int B,
-                  int N, int K, bool ln, int* S_out, int out_dt, const float* wscale);
-
-int run_opt(Captioner* m, int B, int L, int past, hipStream_t s) {
-    const CapConfig& c = m->c;
-    const int T = c.t_hidden, G = c.t_ffn, H = c.t_heads, hd = T / H, R = B * L;
-    const int Lmax = c.num_query_tokens + 1 + c.max_len;
-    const size_t e = m->esz;
-    const int af = m->gdt == CAP_DT_G8 ? 1 : 0;     // split mode: q | k | v for the attention kernels and the caches are fp32
-    if (m->wq8 && B > kI8SkinnyPromptCrops) {
-        // int8 weights, a batch's prompt pass: B x 33 rows is a GEMM proper.  Each weight matrix is unpacked into a row-major bf16
-        // scratch of its INTEGERS (exact), multiplied by the tiled kernel into fp32, the row scales applied to that output, and the
-        // decode step's consumers (S = 1) finish it: (A . q^T) * scale + bias as in the weight-streaming kernels, the sums in the
-        // tiled kernel's order.  Measured at 32 crops (us per fc1 GEMM): 365 on the rows-walking weight-stream kernel, ~135 here.
-        auto tiled = [&](const char* tag, const void* A, const void* Wp, const float* wscale, int N, int K) -> int {
-            TRY(launch_dequant_i8_rowmajor(Wp, m->w8_scratch, N, K, s));
-            TRY(gemm(m, s, tag, A, K, m->w8_scratch, K, m->dpart, N, nullptr, nullptr, R, N, K, 0, 1));
-            return launch_scale_cols(m->dpart, wscale, R, N, s);
-        };
-        TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, R, T, s));
-        for (int i = 0; i < c.t_layers; ++i) {
-            const OLayer& Ly = m->ol[i];
-            TRY(tiled("opt_gemm_qkv", m->oh_t, Ly.w_qkv, Ly.s_qkv, 3 * T, T));
-            TRY(launch_reduce_bias_act(m->dt, m->dpart, 1, Ly.b_qkv, m->oqkv, R, 3 * T, 0, s));
-            TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, L, T, Lmax, past, s));
-            {
-                ProfScope ps(m, s, "opt_attn", 4.0 * B * H * (double)L * (past + L) * hd, 2.0 * B * (past + L) * T * e);
-                if (past == 0) TRY(launch_vit_attention(m->dt, m->oqkv, m->octx, B, L, H, 0, s, hd, 1, m->gdt));
-                else TRY(launch_generic_attention(m->dt, m->oqkv, 3 * T, (long)L * 3 * T, Ly.kc, T, (long)Lmax * T, Ly.vc, T, (long)Lmax * T, m->octx, T,
-                                                  (long)L * T, B, L, past + L, H, hd, past, s, m->gdt));
-            }
-            TRY(tiled("opt_gemm_o", m->octx, Ly.w_o, Ly.s_o, T, T));
-            TRY(launch_reduce_layernorm(m->gdt, m->dpart, 1, Ly.b_o, m->ox, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
-            TRY(tiled("opt_gemm_f1", m->oh_t, Ly.w_f1, Ly.s_f1, G, T));
-            TRY(launch_reduce_bias_act(m->gdt, m->dpart, 1, Ly.b_f1, m->off, R, G, 2, s));
-            const bool last = i + 1 == c.t_layers;
-            TRY(tiled("opt_gemm_f2", m->off, Ly.w_f2, Ly.s_f2, T, G));
-            TRY(launch_reduce_layernorm(m->gdt, m->dpart, 1, Ly.b_f2, m->ox, last ? m->o_lnf_g : m->ol[i + 1].ln1_g,
-                                        last ? m->o_lnf_b : m->ol[i + 1].ln1_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
-        }
-        return gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)(L - 1) * T * e, L * T, m->o_tok_t, T, m->logits, m->ldl, nullptr, nullptr, B,
-                    c.vocab, T, 0, 1);
+// ---- The OPT decoder (pre-LN blocks: what follows a residual add is always a LayerNorm).
+// One projection over `rows` rows, left for a consumer to finish: in place (ln == false: bias + act -> out_t, of type out_dt -
+// split mode: fp32 for q|k|v, G8 for a GEMM operand) or as *S_out slice sums in m->dpart for the reduce + LayerNorm consumer.
+//   int8 weights (W = fragment-ordered bytes, wscale = row scales), tiled: a batch's prompt pass, B x 33 rows, is a GEMM proper.
+//     The matrix is unpacked into a row-major bf16 scratch of its INTEGERS (exact), multiplied by the tiled kernel into fp32 and
+//     the row scales applied to that output (S = 1): (A . q^T) * scale + bias as in the weight-streaming kernel, the sums in the
+//     tiled kernel's order.  Measured at 32 crops (us per fc1 GEMM): 365 on the rows-walking weight-stream kernel, ~135 here.
+//   int8 weights otherwise: the weight-streaming kernel, which takes any row count (further row groups re-read a unit's bytes
+//     from the XCD's L2).
+//   bf16 at a shape the weight-streaming kernel takes: that kernel - at a few dozen rows every GEMM is a weight stream, so K is
+//     split over blocks (all slabs of a block in flight at once).  Otherwise the tiled split-K GEMM with a reduce kernel.
+// Apart from `tiled` the choice depends on dtype and (N, K) only - never on the row count.
+int opt_gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, const void* W, const float* bias, int act, void* out_t,
+             int rows, int N, int K, bool ln, int* S_out, int out_dt, const float* wscale, bool tiled) {
+    if (m->wq8 && !tiled) {
+        const int S8 = skinny_i8_plan(N, K, !ln);
+        ProfScope ps(m, s, tag, 2.0 * rows * N * K,
+                     (double)rows * K * 2 + (double)N * K + (ln ? (double)S8 * rows * N * 4 : (double)rows * N * 2));
+        *S_out = S8;
+        return launch_gemm_skinny_i8(A, K, W, wscale, bias, act, out_t, N, ln ? m->dpart : nullptr, rows, N, K, s) == S8 ? 0 : -1;
+    }
+    const int S = !m->wq8 && m->dt == CAP_DT_BF16 ? skinny_plan(N, K, !ln) : 0;
+    if (S >= 1) {
+        ProfScope ps(m, s, tag, 2.0 * rows * N * K,
+                     ((double)rows * K + (double)N * K) * 2 + (ln ? (double)S * rows * N * 4 : (double)rows * N * 2));
+        *S_out = S;
+        return launch_gemm_skinny(A, K, W, K, bias, act, out_t, N, ln ? m->dpart : nullptr, rows, N, K, s) == S ? 0 : -1;
     }
     if (m->wq8) {
-        // int8 weights: the prompt's rows go through the decode step's chain (the weight-streaming GEMMs take any row count: further
-        // row groups re-read a unit's bytes from the XCD's L2; out_proj / fc2 as slice sums finished by the reduce + LayerNorm
-        // consumer) with the prompt's causal attention in place of the cached one.  A one-crop prompt is 33 rows: a weight stream too.
-        int S = 1;
-        TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, R, T, s));
-        for (int i = 0; i < c.t_layers; ++i) {
-            const OLayer& Ly = m->ol[i];
-            TRY(opt_step_gemm(m, s, "opt_gemm_qkv", m->oh_t, Ly.w_qkv, Ly.b_qkv, 0, m->oqkv, R, 3 * T, T, false, &S, m->dt, Ly.s_qkv));
-            TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, L, T, Lmax, past, s));
-            {
-                ProfScope ps(m, s, "opt_attn", 4.0 * B * H * (double)L * (past + L) * hd, 2.0 * B * (past + L) * T * e);
-                if (past == 0) TRY(launch_vit_attention(m->dt, m->oqkv, m->octx, B, L, H, 0, s, hd, 1, m->gdt));
-                else TRY(launch_generic_attention(m->dt, m->oqkv, 3 * T, (long)L * 3 * T, Ly.kc, T, (long)Lmax * T, Ly.vc, T, (long)Lmax * T, m->octx, T,
-                                                  (long)L * T, B, L, past + L, H, hd, past, s, m->gdt));
-            }
-            TRY(opt_step_gemm(m, s, "opt_gemm_o", m->octx, Ly.w_o, nullptr, 0, nullptr, R, T, T, true, &S, m->gdt, Ly.s_o));
-            TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_o, m->ox, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
-            TRY(opt_step_gemm(m, s, "opt_gemm_f1", m->oh_t, Ly.w_f1, Ly.b_f1, 2, m->off, R, G, T, false, &S, m->gdt, Ly.s_f1));
-            const bool last = i + 1 == c.t_layers;
-            TRY(opt_step_gemm(m, s, "opt_gemm_f2", m->off, Ly.w_f2, nullptr, 0, nullptr, R, T, G, true, &S, m->gdt, Ly.s_f2));
-            TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_f2, m->ox, last ? m->o_lnf_g : m->ol[i + 1].ln1_g,
-                                        last ? m->o_lnf_b : m->ol[i + 1].ln1_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
-        }
-        // oh_t = final LayerNorm of every row: the tied LM head (bf16, no bias) reads each image's last position
-        return gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)(L - 1) * T * e, L * T, m->o_tok_t, T, m->logits, m->ldl, nullptr, nullptr, B,
-                    c.vocab, T, 0, 1);
+        TRY(launch_dequant_i8_rowmajor(W, m->w8_scratch, N, K, s));
+        TRY(gemm(m, s, tag, A, K, m->w8_scratch, K, m->dpart, N, nullptr, nullptr, rows, N, K, 0, 1));
+        TRY(launch_scale_cols(m->dpart, wscale, rows, N, s));
+        *S_out = 1;
+    } else {
+        TRY(gemm_partial(m, s, tag, A, W, m->dpart, rows, N, K, 8, S_out));
     }
+    if (!ln) TRY(launch_reduce_bias_act(out_dt, m->dpart, *S_out, bias, out_t, rows, N, act, s));
+    return 0;
+}
+
+// Self-attention of one layer over the fused q|k|v rows in oqkv -> octx, the new K/V rows into the layer's caches.  The prompt
+// (L positions, nothing cached): causal attention over the rows themselves (MFMA kernel for bf16 heads wider than 64).  A step
+// (L == 1): the new position against the `past` cached ones.
+int opt_attention(Captioner* m, const OLayer& Ly, int B, int L, int past, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden, H = c.t_heads, hd = T / H, Lmax = c.num_query_tokens + 1 + c.max_len;
+    if (L > 1 && past != 0) { cap_set_error("opt_attention: %d new positions behind a cached prefix (%d) are not built", L, past); return -1; }
+    if (L > 1) TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, L, T, Lmax, 0, s));
+    ProfScope ps(m, s, "opt_attn", 4.0 * B * H * (double)L * (past + L) * hd, 2.0 * B * (past + L) * T * m->esz);
+    if (L > 1) return launch_vit_attention(m->dt, m->oqkv, m->octx, B, L, H, 0, s, hd, 1, m->gdt);
+    if (hd % 8 == 0 && hd <= 128) return launch_opt_decode_attention(m->dt, m->oqkv, Ly.kc, Ly.vc, m->octx, B, T, H, Lmax, past, s, m->gdt);
+    TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, 1, T, Lmax, past, s));
+    return launch_generic_attention(m->dt, m->oqkv, 3 * T, 3 * T, Ly.kc, T, (long)Lmax * T, Ly.vc, T, (long)Lmax * T, m->octx, T, T, B, 1, past + 1,
+                                    H, hd, past, s, m->gdt);
+}
+
+// The decoder layers over L new positions per row behind `past` cached ones (x = ox [B * L, T] fp32 with the positions added,
+// oh_t = LayerNorm_1 of layer 0 already applied), then the tied LM head (bf16, no bias) on each row's last new position ->
+// m->logits.  Every decode step (L = 1), and the prompt pass with int8 weights: up to kI8SkinnyPromptCrops crops its rows go
+// through the step's weight streams (a one-crop prompt is 33 rows: a weight stream too), beyond through the tiled GEMM.  The
+// consumers finish the projections' sums - bias (+ ReLU) -> T for q|k|v and fc1; bias + residual + the NEXT LayerNorm (the
+// final one on the last layer, over every row) for out_proj and fc2.
+int run_opt(Captioner* m, int B, int L, int past, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden, G = c.t_ffn, R = B * L;
+    const bool tiled = L > 1 && B > kI8SkinnyPromptCrops;
+    int S = 1;
     for (int i = 0; i < c.t_layers; ++i) {
         const OLayer& Ly = m->ol[i];
+        const bool last = i + 1 == c.t_layers;
+        TRY(opt_gemm(m, s, "opt_gemm_qkv", m->oh_t, Ly.w_qkv, Ly.b_qkv, 0, m->oqkv, R, 3 * T, T, false, &S, m->dt, Ly.s_qkv, tiled));
+        TRY(opt_attention(m, Ly, B, L, past, s));
+        TRY(opt_gemm(m, s, "opt_gemm_o", m->octx, Ly.w_o, nullptr, 0, nullptr, R, T, T, true, &S, m->gdt, Ly.s_o, tiled));
+        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_o, m->ox, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
+        TRY(opt_gemm(m, s, "opt_gemm_f1", m->oh_t, Ly.w_f1, Ly.b_f1, 2, m->off, R, G, T, false, &S, m->gdt, Ly.s_f1, tiled));
+        TRY(opt_gemm(m, s, "opt_gemm_f2", m->off, Ly.w_f2, nullptr, 0, nullptr, R, T, G, true, &S, m->gdt, Ly.s_f2, tiled));
+        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_f2, m->ox, last ? m->o_lnf_g : m->ol[i + 1].ln1_g,
+                                    last ? m->o_lnf_b : m->ol[i + 1].ln1_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
+    }
+    return gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)(L - 1) * T * m->esz, L * T, m->o_tok_t, T, m->logits, m->ldl, nullptr,
+                nullptr, B, c.vocab, T, 0, 1);
+}
+
+// The prompt pass with plain weights (f32 / f32s / bf16): B * L rows are GEMMs proper, so bias and residual ride the tiled GEMM's
+// epilogue, every sub-block opens with its own LayerNorm, and the final one covers each row's last position only.
+int run_opt_prompt_plain(Captioner* m, int B, int L, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden, G = c.t_ffn, R = B * L;
+    const int af = m->gdt == CAP_DT_G8 ? 1 : 0;     // split mode: q | k | v for the attention kernels and the caches are fp32
+    for (const OLayer& Ly : m->ol) {
         TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln1_g, Ly.ln1_b, c.t_eps, m->oh_t, nullptr, R, T, s));
         TRY(gemm(m, s, "opt_gemm_qkv", m->oh_t, T, Ly.w_qkv, T, m->oqkv, 3 * T, Ly.b_qkv, nullptr, R, 3 * T, T, 0, af));
-        TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, L, T, Lmax, past, s));
-        {
-            ProfScope ps(m, s, "opt_attn", 4.0 * B * H * (double)L * (past + L) * hd, 2.0 * B * (past + L) * T * e);
-            if (past == 0)      // the prompt: causal self-attention over the fused q|k|v rows (MFMA kernel for bf16 heads wider than 64)
-                TRY(launch_vit_attention(m->dt, m->oqkv, m->octx, B, L, H, 0, s, hd, 1, m->gdt));
-            else
-                TRY(launch_generic_attention(m->dt, m->oqkv, 3 * T, (long)L * 3 * T, Ly.kc, T, (long)Lmax * T, Ly.vc, T, (long)Lmax * T, m->octx, T,
-                                             (long)L * T, B, L, past + L, H, hd, past, s, m->gdt));
-        }
+        TRY(opt_attention(m, Ly, B, L, 0, s));
         TRY(gemm(m, s, "opt_gemm_o", m->octx, T, Ly.w_o, T, m->ox, T, Ly.b_o, m->ox, R, T, T, 0, 1));
         TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, R, T, s));
         TRY(gemm(m, s, "opt_gemm_f1", m->oh_t, T, Ly.w_f1, T, m->off, G, Ly.b_f1, nullptr, R, G, T, 2, 0));
         TRY(gemm(m, s, "opt_gemm_f2", m->off, G, Ly.w_f2, G, m->ox, T, Ly.b_f2, m->ox, R, T, G, 0, 1));
     }
-    // final LayerNorm of each row's last new position, then the tied LM head (no bias)
     TRY(launch_layernorm(m->gdt, m->ox + (size_t)(L - 1) * T, L * T, m->o_lnf_g, m->o_lnf_b, c.t_eps, m->oh_t, nullptr, B, T, s));
-    return gemm(m, s, "opt_gemm_vocab", m->oh_t, T, m->o_tok_t, T, m->logits, m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
-}
-
-// One decode step (one new position per row, x = ox [B, T] with its position added, oh_t = LayerNorm_1 of layer 0 already
-// applied): at a few dozen rows every GEMM is a weight stream, so K is split over blocks (all slabs of a block in flight at
-// once) and the consumers finish the sums - bias (+ ReLU) -> T for q|k|v and fc1; bias + residual + the NEXT LayerNorm for
-// out_proj and fc2 (pre-LN blocks: what follows a residual add is always a LayerNorm).
-// One projection of the decode step.  bf16 at a shape the weight-streaming kernel takes: that kernel, finished in place
-// (ln == false: bias + act -> out_t) or as slice sums for the reduce+LayerNorm consumer.  Otherwise the tiled split-K GEMM
-// with a reduce kernel.  The choice depends on dtype and (N, K) only - never on the row count.
-int opt_step_gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, const void* W, const float* bias, int act,
-                  void* out_t, int B, int N, int K, bool ln, int* S_out, int out_dt,        // out_dt: type of out_t (split mode:
-                  const float* wscale = nullptr) {                                         // fp32 for q|k|v, G8 for a GEMM operand)
-    if (m->wq8) {                                       // int8 weights (load_in_8bit): W = fragment-ordered bytes, wscale = row scales
-        const int S8 = skinny_i8_plan(N, K, !ln);
-        ProfScope ps(m, s, tag, 2.0 * B * N * K, (double)B * K * 2 + (double)N * K + (ln ? (double)S8 * B * N * 4 : (double)B * N * 2));
-        *S_out = S8;
-        return launch_gemm_skinny_i8(A, K, W, wscale, bias, act, out_t, N, ln ? m->dpart : nullptr, B, N, K, s) == S8 ? 0 : -1;
-    }
-    const int S = m->dt == CAP_DT_BF16 ? skinny_plan(N, K, !ln) : 0;
-    if (S >= 1) {
-        ProfScope ps(m, s, tag, 2.0 * B * N * K, ((double)B * K + (double)N * K) * 2 + (ln ? (double)S * B * N * 4 : (double)B * N * 2));
-        *S_out = S;
-        return launch_gemm_skinny(A, K, W, K, bias, act, out_t, N, ln ? m->dpart : nullptr, B, N, K, s) == S ? 0 : -1;
-    }
-    TRY(gemm_partial(m, s, tag, A, W, m->dpart, B, N, K, 8, S_out));
-    if (!ln) TRY(launch_reduce_bias_act(out_dt, m->dpart, *S_out, bias, out_t, B, N, act, s));
-    return 0;
-}
-
-int run_opt_step(Captioner* m, int B, int past, hipStream_t s) {
-    const CapConfig& c = m->c;
-    const int T = c.t_hidden, G = c.t_ffn, H = c.t_heads, hd = T / H;
-    const int Lmax = c.num_query_tokens + 1 + c.max_len;
-    const size_t e = m->esz;
-    int S = 1;
-    for (int i = 0; i < c.t_layers; ++i) {
-        const OLayer& Ly = m->ol[i];
-        TRY(opt_step_gemm(m, s, "opt_gemm_qkv", m->oh_t, Ly.w_qkv, Ly.b_qkv, 0, m->oqkv, B, 3 * T, T, false, &S, m->dt, Ly.s_qkv));
-        {
-            ProfScope ps(m, s, "opt_attn", 4.0 * B * H * (double)(past + 1) * hd, 2.0 * B * (past + 1) * T * e);
-            if (hd % 8 == 0 && hd <= 128)
-                TRY(launch_opt_decode_attention(m->dt, m->oqkv, Ly.kc, Ly.vc, m->octx, B, T, H, Lmax, past, s, m->gdt));
-            else {
-                TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, 1, T, Lmax, past, s));
-                TRY(launch_generic_attention(m->dt, m->oqkv, 3 * T, 3 * T, Ly.kc, T, (long)Lmax * T, Ly.vc, T, (long)Lmax * T, m->octx, T, T, B, 1,
-                                             past + 1, H, hd, past, s, m->gdt));
-            }
-        }
-        TRY(opt_step_gemm(m, s, "opt_gemm_o", m->octx, Ly.w_o, nullptr, 0, nullptr, B, T, T, true, &S, m->gdt, Ly.s_o));
-        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_o, m->ox, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, m->ox, B, T, s, true));
-        TRY(opt_step_gemm(m, s, "opt_gemm_f1", m->oh_t, Ly.w_f1, Ly.b_f1, 2, m->off, B, G, T, false, &S, m->gdt, Ly.s_f1));
-        const bool last = i + 1 == c.t_layers;
-        TRY(opt_step_gemm(m, s, "opt_gemm_f2", m->off, Ly.w_f2, nullptr, 0, nullptr, B, T, G, true, &S, m->gdt, Ly.s_f2));
-        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_f2, m->ox, last ? m->o_lnf_g : m->ol[i + 1].ln1_g,
-                                    last ? m->o_lnf_b : m->ol[i + 1].ln1_b, c.t_eps, m->oh_t, nullptr, m->ox, B, T, s, true));
-    }
     return gemm(m, s, "opt_gemm_vocab", m->oh_t, T, m->o_tok_t, T, m->logits, m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
 }
 
@@ -1138,7 +1084,12 @@ int run_generate_blip2(Captioner* m, const void* pixels, int fmt, int B, int max
     TRY(launch_opt_prefill_inputs(m->lm_proj, m->o_tok, m->o_pos, m->ox, B, nq, T, c.bos, s));
     hipLaunchKernelGGL(init_seq_kernel, dim3(64), dim3(256), 0, s, m->seq, m->finished, m->lens, B, Lmax, c.bos, c.pad);
     CAP_HIP_CHECK(hipGetLastError());
-    TRY(run_opt(m, B, P, 0, s));
+    if (m->wq8) {
+        TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B * P, T, s));
+        TRY(run_opt(m, B, P, 0, s));
+    } else {
+        TRY(run_opt_prompt_plain(m, B, P, s));
+    }
     for (int t = 0; t < max_len; ++t) {
         m->last_steps = t + 1;
         if (out_step_logits) {
@@ -1157,7 +1108,7 @@ int run_generate_blip2(Captioner* m, const void* pixels, int fmt, int B, int max
         }
         TRY(launch_opt_token_inputs(m->seq, Lmax, P + t, m->o_tok, m->o_pos, m->ox, B, T, s));
         TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B, T, s));
-        TRY(run_opt_step(m, B, P + t, s));
+        TRY(run_opt(m, B, 1, P + t, s));
     }
     hipLaunchKernelGGL(copy_new_tokens_kernel, dim3(64), dim3(256), 0, s, m->seq, Lmax, P, m->lens, out_ids, out_len, B, max_len);
     CAP_HIP_CHECK(hipGetLastError());

@@ -294,7 +294,7 @@ def test_opt_decode_step_refuses_what_it_cannot_hold(lib):
 
 
 # the fallback of the step: kv_append + generic attention with one query (generic_decode_attention_kernel up to 1024 keys, the
-# lane = query kernel beyond), the layout run_opt_step passes
+# lane = query kernel beyond), the layout opt_attention passes
 OPT_FALLBACK_LK = [1, 63, 64, 65, 1024, 1025]
 
 
