@@ -39,6 +39,38 @@ class CapConfig(C.Structure):
     ]
 
 
+class CapSmallLN(C.Structure):
+    _fields_ = [
+        ("part", C.c_void_p), ("S", C.c_int32), ("bias", C.c_void_p), ("resid", C.c_void_p), ("gamma", C.c_void_p),
+        ("beta", C.c_void_p), ("eps", C.c_float), ("x_out", C.c_void_p), ("x_is_sum", C.c_int32),
+    ]
+
+
+class CapSmallSA(C.Structure):
+    _fields_ = [
+        ("qkv_part", C.c_void_p), ("qkv_bias", C.c_void_p), ("qkv_S", C.c_int32), ("kc", C.c_void_p), ("vc", C.c_void_p),
+        ("anc", C.c_void_p), ("anc_ld", C.c_int32), ("kv_ld", C.c_int32), ("n_keys", C.c_int32), ("H", C.c_int32),
+        ("skip", C.c_void_p),
+    ]
+
+
+class CapSmallGemm(C.Structure):
+    _fields_ = [
+        ("W", C.c_void_p), ("A", C.c_void_p), ("R", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("S", C.c_int32),
+        ("pro", C.c_int32), ("epi", C.c_int32), ("nchain", C.c_int32), ("ln", CapSmallLN), ("sa", CapSmallSA),
+        ("out_part", C.c_void_p), ("bias", C.c_void_p), ("act", C.c_int32), ("out", C.c_void_p), ("ldc", C.c_int32),
+    ]
+
+
+class CapSmallCross(C.Structure):
+    _fields_ = [
+        ("W", C.c_void_p), ("bias", C.c_void_p), ("R", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("S", C.c_int32),
+        ("ln", CapSmallLN), ("kbase", C.c_void_p), ("vbase", C.c_void_p), ("kv_row0", C.c_size_t),
+        ("rows_per_kv", C.c_int32), ("kv_ld", C.c_int32), ("n_keys", C.c_int32), ("kv_kind", C.c_int32),
+        ("skip", C.c_void_p), ("out", C.c_void_p),
+    ]
+
+
 _SIGNATURES = {
     "cap_last_error": (C.c_char_p, []),
     "cap_version": (C.c_int, []),
@@ -98,6 +130,11 @@ _SIGNATURES = {
                                           C.c_void_p]),
     "cap_op_decode_attention": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "cap_op_decode_attention_fused": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                C.c_int, C.c_int, C.c_void_p]),
+    "cap_op_small_gemm": (C.c_int, [C.c_int, C.POINTER(CapSmallGemm), C.c_void_p]),
+    "cap_op_small_cross": (C.c_int, [C.c_int, C.POINTER(CapSmallCross), C.c_void_p]),
     "cap_op_beam_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
     "cap_op_beam_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -2553,6 +2553,54 @@ int cap_op_decode_attention(int dtype, const void* q, const void* kbase, const v
     a.n_keys = n_keys; a.out = out; a.R = R; a.H = H; a.impl = impl & 15; a.out_dtype = dt_of(dtype); a.kv16 = (impl >> 4) & 1;
     return launch_decode_attention(in_dt_of(dtype), a, (hipStream_t)stream);
 }
+int cap_op_decode_attention_fused(int dtype, const float* q_part, int q_S, const float* q_bias, int q_ld, int q_col0, int append_kv,
+                                  void* kbase, void* vbase, const int32_t* anc, int anc_ld, int rows_per_kv, int kv_ld, int n_keys,
+                                  void* out, int R, int H, int impl, void* stream) {
+    if (!q_part || !kbase || !vbase || !out) { cap_set_error("cap_op_decode_attention_fused: null pointer"); return -1; }
+    DecodeAttn a;
+    memset(&a, 0, sizeof(a));
+    a.kbase = kbase; a.vbase = vbase; a.anc = anc; a.anc_ld = anc_ld; a.rows_per_kv = rows_per_kv; a.kv_ld = kv_ld;
+    a.n_keys = n_keys; a.out = out; a.R = R; a.H = H; a.impl = impl & 15; a.out_dtype = dt_of(dtype); a.kv16 = (impl >> 4) & 1;
+    a.q_part = q_part; a.q_S = q_S; a.q_bias = q_bias; a.q_ld = q_ld; a.q_col0 = q_col0; a.append_kv = append_kv;
+    return launch_decode_attention(in_dt_of(dtype), a, (hipStream_t)stream);
+}
+/* the small-batch decode kernels alone (tests/test_small_kernels_gpu.py): the launchers' own structs, filled field for field */
+static SmallLN small_ln_of(const CapSmallLN& l) {
+    SmallLN o;
+    memset(&o, 0, sizeof(o));
+    o.part = l.part; o.S = l.S; o.bias = l.bias; o.resid = l.resid; o.gamma = l.gamma; o.beta = l.beta; o.eps = l.eps;
+    o.x_out = l.x_out; o.x_is_sum = l.x_is_sum;
+    return o;
+}
+int cap_op_small_gemm(int dtype, const CapSmallGemm* a, void* stream) {
+    if (!a || !a->W) { cap_set_error("cap_op_small_gemm: null pointer"); return -1; }
+    SmallGemm g;
+    memset(&g, 0, sizeof(g));
+    g.W = a->W; g.A = a->A; g.R = a->R; g.N = a->N; g.K = a->K; g.S = a->S; g.pro = a->pro; g.epi = a->epi; g.nchain = a->nchain;
+    g.ln = small_ln_of(a->ln);
+    g.sa.qkv_part = a->sa.qkv_part; g.sa.qkv_bias = a->sa.qkv_bias; g.sa.qkv_S = a->sa.qkv_S; g.sa.kc = a->sa.kc; g.sa.vc = a->sa.vc;
+    g.sa.anc = a->sa.anc; g.sa.anc_ld = a->sa.anc_ld; g.sa.kv_ld = a->sa.kv_ld; g.sa.n_keys = a->sa.n_keys; g.sa.H = a->sa.H;
+    g.sa.skip = a->sa.skip;
+    g.out_part = a->out_part; g.bias = a->bias; g.act = a->act; g.out = a->out; g.ldc = a->ldc;
+    const bool ok = (g.pro != SMALL_PRO_GLOBAL || g.A) && (g.pro != SMALL_PRO_LN || (g.ln.part && g.ln.gamma && g.ln.beta)) &&
+                    (g.pro != SMALL_PRO_SELFATTN || (g.sa.qkv_part && g.sa.qkv_bias && g.sa.kc && g.sa.vc)) &&
+                    (g.epi == SMALL_EPI_PARTIAL ? g.out_part != nullptr : g.out != nullptr);
+    if (!ok) { cap_set_error("cap_op_small_gemm: null pointer"); return -1; }
+    return launch_small_gemm(dt_of(dtype), g, (hipStream_t)stream);
+}
+int cap_op_small_cross(int dtype, const CapSmallCross* a, void* stream) {
+    if (!a || !a->W || !a->bias || !a->ln.part || !a->ln.gamma || !a->ln.beta || !a->kbase || !a->vbase || !a->out) {
+        cap_set_error("cap_op_small_cross: null pointer");
+        return -1;
+    }
+    SmallCross x;
+    memset(&x, 0, sizeof(x));
+    x.W = a->W; x.bias = a->bias; x.R = a->R; x.D = a->D; x.H = a->H; x.S = a->S;
+    x.ln = small_ln_of(a->ln);
+    x.kbase = a->kbase; x.vbase = a->vbase; x.kv_row0 = a->kv_row0;
+    x.rows_per_kv = a->rows_per_kv; x.kv_ld = a->kv_ld; x.n_keys = a->n_keys; x.kv_kind = a->kv_kind; x.skip = a->skip; x.out = a->out;
+    return launch_small_cross(dt_of(dtype), x, (hipStream_t)stream);
+}
 int cap_op_gemm_crosskv(int dtype, const void* A, const void* W, const float* bias, void* cache, int n_img, int tokens, int heads,
                         int layers, int K, int kv16, void* stream) {
     GemmParams p;

@@ -15,7 +15,8 @@
 // row out of L2), and the fp32 LayerNorm output that the batch path keeps in `dx` (the post-LN residual) is written by one
 // designated workgroup into a ping-pong pair, so no workgroup reads a row another one is replacing.
 //
-// Same bits as the batch path, by construction and by test (tests/test_small_decode_gpu.py): a GEMM forms exactly the partial
+// Same bits as the batch path, by construction and by test (tests/test_small_kernels_gpu.py: each kernel alone against float64 and
+// the batch kernels' chain; tests/test_small_decode_gpu.py: whole captions): a GEMM forms exactly the partial
 // sums of gemm_rows_kernel - K slices S from the same plan (captioner.hip::decode_splitk), inside a slice slab j goes to
 // chain j % 4, a chain is the MFMA sequence [w_lo.a_hi, w_hi.a_lo, w_hi.a_hi] per slab in slab order, the four chains are
 // summed in chain order, slices in slice order, then bias, then residual - or, for the transform / vocabulary GEMMs, the one

@@ -432,6 +432,53 @@ int cap_op_gemm_skinny_i8_slices(int N, int K, int finished);
 int cap_op_decode_attention(int dtype, const void* q, const void* kbase, const void* vbase, const int32_t* anc,
                             int anc_ld, int rows_per_kv, int kv_ld, int n_keys, void* out, int R, int H, int impl,
                             void* stream);        /* impl | 16: kbase / vbase are KV16 blocks (no ancestry, > 32 keys) */
+/* cap_op_decode_attention as the decoder step launches it (impl & 15 == 0): q is not a tensor but the split-K partial sums of its
+ * projection, q_part fp32 [q_S][R][q_ld], the head's columns from q_col0 on, + q_bias - the attention unit finishes the sum and rounds
+ * it through the attention's value type.  append_kv (self-attention, n_keys <= 32): columns q_col0 + H 64 / + 2 H 64 are the new
+ * position's k / v, finished the same way, written to position n_keys - 1 of the row's own cache and attended. */
+int cap_op_decode_attention_fused(int dtype, const float* q_part, int q_S, const float* q_bias, int q_ld, int q_col0, int append_kv,
+                                  void* kbase, void* vbase, const int32_t* anc, int anc_ld, int rows_per_kv, int kv_ld, int n_keys,
+                                  void* out, int R, int H, int impl, void* stream);
+/* The small-batch decode kernels alone (csrc/decode_small.hip; at most 16 rows): the launchers' argument structs field for field
+ * (csrc/decode_small.h says what each one means).  dtype CAP_BF16: bf16 operands and caches; CAP_F32_SPLIT: G8 operands (weights
+ * through cap_op_convert_weight), fp32 self-attention caches, fp32 or KV16 cross K/V.  The hooks check pointers only: every shape
+ * is the launcher's to take or refuse. */
+typedef struct CapSmallLN {         /* the LayerNorm prologue: LayerNorm(sum of S slabs + bias + resid) */
+    const float* part; int32_t S;   /* fp32 [S][R][D] */
+    const float* bias;              /* [D] or NULL */
+    const float* resid;             /* fp32 [R][D] or NULL */
+    const float* gamma; const float* beta; float eps;
+    float* x_out;                   /* fp32 [R][D] or NULL: the LayerNorm output (x_is_sum: the sum), written by one workgroup */
+    int32_t x_is_sum;
+} CapSmallLN;
+typedef struct CapSmallSA {         /* the self-attention prologue */
+    const float* qkv_part; const float* qkv_bias; int32_t qkv_S;   /* fp32 [qkv_S][R][3 H 64], bias [3 H 64] */
+    void* kc; void* vc;             /* [R][H][kv_ld][64] in the cache type */
+    const int32_t* anc; int32_t anc_ld;
+    int32_t kv_ld, n_keys, H;
+    const int32_t* skip;
+} CapSmallSA;
+typedef struct CapSmallGemm {
+    const void* W; const void* A;   /* W [N, K]; A [R, K] (prologue 0) */
+    int32_t R, N, K, S;
+    int32_t pro, epi, nchain;       /* pro 0 global / 1 LayerNorm / 2 self-attention; epi 0 slabs / 1 act -> operand type / 2 act -> fp32 */
+    CapSmallLN ln;
+    CapSmallSA sa;
+    float* out_part;                /* epi 0: fp32 [S][R][N] */
+    const float* bias; int32_t act; /* act 0 none, 1 GELU, 2 ReLU */
+    void* out; int32_t ldc;         /* epi 1 / 2: [R, ldc] */
+} CapSmallGemm;
+typedef struct CapSmallCross {
+    const void* W; const float* bias;      /* query projection [D, D], bias [D] */
+    int32_t R, D, H, S;
+    CapSmallLN ln;
+    const void* kbase; const void* vbase; size_t kv_row0;
+    int32_t rows_per_kv, kv_ld, n_keys, kv_kind;   /* kv_kind 0 fp32 rows, 1 bf16 rows, 2 KV16 */
+    const int32_t* skip;            /* int32 [R] or NULL: rows left untouched */
+    void* out;                      /* context [R][D] in the operand type */
+} CapSmallCross;
+int cap_op_small_gemm(int dtype, const CapSmallGemm* args, void* stream);
+int cap_op_small_cross(int dtype, const CapSmallCross* args, void* stream);
 /* The split mode's cross-attention K/V cache layout: fp32 rows [n_rows, 64] -> one KV16 block: per row 64 int16 and one fp32 scale
    (x ~ q * scale, scale = max|x| / 32767 over the row), rows in groups of 32 = [32 x 128 bytes][32 scales] = 4224 bytes; dst holds
    (n_rows + 31) / 32 groups.  The cross-K/V GEMM's epilogue writes this layout; the op exists for the kernel tests. */

@@ -117,3 +117,12 @@ def g8_decode(c, scale=1.0):
     c = np.ascontiguousarray(np.asarray(c, dtype=np.float32))
     h = c.view(np.float16).reshape(*c.shape[:-1], -1, 2, 8).astype(np.float32)
     return ((h[..., 0, :] + h[..., 1, :]) / np.float32(scale)).reshape(c.shape)
+
+
+# ---- KV16: the split mode's cross-attention K/V cache layout (embodied_captioning_amd/csrc/common.h) ------------------
+def kv16_unpack(raw, rows):
+    """bytes of a KV16 block -> (int16 [rows, 64], fp32 scales [rows]); groups of 32 rows = 32 x 128 B then 32 scales."""
+    g = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 4224)
+    q = g[:, :4096].reshape(-1, 128).view(np.int16)[:rows]
+    sc = g[:, 4096:].reshape(-1, 128).view(np.float32).reshape(-1)[:rows]
+    return q.copy(), sc.copy()

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from _util import G8_WSCALE, g8_decode, g8_encode
+from _util import kv16_unpack as _kv16_unpack
 
 SPLIT = 2
 gpu = pytest.mark.gpu
@@ -411,14 +412,6 @@ def _kv16_ref(x):
     inv = np.where(am > 0, np.float32(32767.0) / np.where(am > 0, am, 1).astype(np.float32), np.float32(0)).astype(np.float32)
     q = np.rint(x * inv[:, None]).astype(np.int16)
     return q, (am * np.float32(1.0 / 32767.0)).astype(np.float32)
-
-
-def _kv16_unpack(raw, rows):
-    """bytes of a KV16 block -> (int16 [rows, 64], fp32 scales [rows]); groups of 32 rows = 32 x 128 B then 32 scales."""
-    g = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 4224)
-    q = g[:, :4096].reshape(-1, 128).view(np.int16)[:rows]
-    sc = g[:, 4096:].reshape(-1, 128).view(np.float32).reshape(-1)[:rows]
-    return q.copy(), sc.copy()
 
 
 @gpu
