@@ -2725,6 +2725,84 @@ int cap_op_vocab_group_threshold(const float* acc, int acc_ld, int V, int N, con
         if (rows[j] < 0 || rows[j] >= N) { cap_set_error("%s: group_rows[%d] = %d is outside the N = %d rows", f, j, rows[j], N); return -1; }
     return launch_vocab_group_threshold(acc, acc_ld, V, group_rows, group_off, G, th, K, out_ids, out_prob, out_count, s);
 }
+/* the helper kernels of elementwise.hip alone (tests/test_elementwise_kernels_gpu.py): pointer and count checks here, every
+ * width / layout rule is the launcher's to take or refuse */
+int cap_op_embed(int dtype, const int32_t* seq, int seq_ld, int t, const float* word, const float* pos, const float* gamma,
+                 const float* beta, float eps, void* out_t, float* out_f, float* y_out, int R, int D, const int32_t* live,
+                 const int32_t* n_live, void* stream) {
+    if (!seq || !word || !pos || !gamma || !beta || (live != nullptr) != (n_live != nullptr)) { cap_set_error("cap_op_embed: null pointer"); return -1; }
+    if (R < 1 || D < 1 || t < 0 || t >= seq_ld) { cap_set_error("cap_op_embed: R = %d, D = %d, t = %d of %d columns", R, D, t, seq_ld); return -1; }
+    RowMap map;
+    map.live = live; map.n = n_live;
+    return launch_embed(dt_of(dtype), seq, seq_ld, t, word, pos, gamma, beta, eps, out_t, out_f, R, D, (hipStream_t)stream, y_out, map);
+}
+int cap_op_embed_prompt(int dtype, const int32_t* seq, int seq_ld, int npos, int row0, const float* word, const float* pos,
+                        const float* gamma, const float* beta, float eps, void* out_t, float* out_f, float* y_out, int n_caps, int D,
+                        void* stream) {
+    if (!seq || !word || !pos || !gamma || !beta) { cap_set_error("cap_op_embed_prompt: null pointer"); return -1; }
+    if (D < 1) { cap_set_error("cap_op_embed_prompt: D = %d", D); return -1; }
+    return launch_embed_prompt(dt_of(dtype), seq, seq_ld, npos, row0, word, pos, gamma, beta, eps, out_t, out_f, n_caps, D,
+                               (hipStream_t)stream, y_out);
+}
+int cap_op_embed_tokens(int dtype, const int32_t* ids, int L, const float* word, const float* pos, const float* type0,
+                        const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int R, int D, int V, void* stream) {
+    // the kernel writes both outputs unconditionally
+    if (!ids || !word || !pos || !type0 || !gamma || !beta || !out_t || !out_f) { cap_set_error("cap_op_embed_tokens: null pointer"); return -1; }
+    if (R < 1 || L < 1 || D < 1) { cap_set_error("cap_op_embed_tokens: R = %d, L = %d, D = %d", R, L, D); return -1; }
+    return launch_embed_tokens(dt_of(dtype), ids, L, word, pos, type0, gamma, beta, eps, out_t, out_f, R, D, (hipStream_t)stream, V);
+}
+int cap_op_init_prompt_seq(int32_t* seq, int32_t* finished, int32_t* lengths, int R, int L, const int32_t* prompt, int prompt_rows,
+                           int P, int V, int pad, void* stream) {
+    if (!seq || !finished || !lengths) { cap_set_error("cap_op_init_prompt_seq: null pointer"); return -1; }
+    if (R < 1 || L < 1) { cap_set_error("cap_op_init_prompt_seq: R = %d, L = %d", R, L); return -1; }
+    return launch_init_prompt_seq(seq, finished, lengths, R, L, prompt, prompt_rows, P, V, pad, (hipStream_t)stream);
+}
+int cap_op_compact_rows(const int32_t* finished, int R, int32_t* live, int32_t* n_live, void* stream) {
+    if (!finished || !live || !n_live) { cap_set_error("cap_op_compact_rows: null pointer"); return -1; }
+    if (R < 1) { cap_set_error("cap_op_compact_rows: R = %d", R); return -1; }
+    return launch_compact_rows(finished, R, live, n_live, (hipStream_t)stream);
+}
+int cap_op_reduce_bias_act(int dtype, const float* part, int S, const float* bias, void* out, int M, int N, int act, void* stream) {
+    if (!part || !out) { cap_set_error("cap_op_reduce_bias_act: null pointer"); return -1; }
+    if (S < 1 || M < 1 || N < 1 || (act != 0 && act != 2)) { cap_set_error("cap_op_reduce_bias_act: S = %d, M = %d, N = %d, act = %d (0 or 2)", S, M, N, act); return -1; }
+    return launch_reduce_bias_act(dt_of(dtype), part, S, bias, out, M, N, act, (hipStream_t)stream);
+}
+int cap_op_mean_pool_normalize(const float* x, const int32_t* lens, int B, int L, int D, float* out, void* stream) {
+    if (!x || !lens || !out) { cap_set_error("cap_op_mean_pool_normalize: null pointer"); return -1; }
+    if (B < 1 || L < 1 || D < 1) { cap_set_error("cap_op_mean_pool_normalize: B = %d, L = %d, D = %d", B, L, D); return -1; }
+    return launch_mean_pool_normalize(x, lens, B, L, D, out, (hipStream_t)stream);
+}
+int cap_op_patchify(int dtype, const void* pixels, int fmt, int B, int img, int ps, int Kpad, void* out, const float* mean,
+                    const float* stdv, void* stream) {
+    if (!pixels || !out) { cap_set_error("cap_op_patchify: null pointer"); return -1; }
+    if ((fmt != CAP_PIX_F32_NCHW && fmt != CAP_PIX_U8_NHWC) || B < 1 || img < 1 || ps < 1) {
+        cap_set_error("cap_op_patchify: fmt = %d, B = %d, img = %d, ps = %d", fmt, B, img, ps);
+        return -1;
+    }
+    return launch_patchify(dt_of(dtype), pixels, fmt, B, img, ps, Kpad, out, mean, stdv, (hipStream_t)stream);
+}
+int cap_op_cls_rows(const float* cls, const float* pos, float* X, int B, int tokens, int D, void* stream) {
+    if (!cls || !pos || !X) { cap_set_error("cap_op_cls_rows: null pointer"); return -1; }
+    if (B < 1 || tokens < 1 || D < 1) { cap_set_error("cap_op_cls_rows: B = %d, tokens = %d, D = %d", B, tokens, D); return -1; }
+    return launch_cls_rows(cls, pos, X, B, tokens, D, (hipStream_t)stream);
+}
+int cap_op_convert2d(int dtype, const float* src, void* dst, int rows, int cols, int dst_ld, float scale, int transposed, void* stream) {
+    if (!src || !dst) { cap_set_error("cap_op_convert2d: null pointer"); return -1; }
+    if (rows < 1 || cols < 1 || dst_ld < (transposed ? rows : cols)) {
+        cap_set_error("cap_op_convert2d: rows = %d, cols = %d, dst_ld = %d", rows, cols, dst_ld);
+        return -1;
+    }
+    if (transposed) {
+        if (dst_ld != rows) { cap_set_error("cap_op_convert2d: the transposed form writes dense rows (dst_ld = %d, rows = %d)", dst_ld, rows); return -1; }
+        return launch_convert2d_t(dt_of(dtype), src, dst, rows, cols, (hipStream_t)stream, scale);
+    }
+    return launch_convert2d(dt_of(dtype), src, dst, rows, cols, dst_ld, (hipStream_t)stream, scale);
+}
+int cap_op_absmax(const float* src, size_t n, uint32_t* out_bits, void* stream) {
+    if (!src || !out_bits) { cap_set_error("cap_op_absmax: null pointer"); return -1; }
+    if (n < 1) { cap_set_error("cap_op_absmax: n = 0"); return -1; }
+    return launch_absmax_f32(src, n, out_bits, (hipStream_t)stream);
+}
 int cap_op_convert(int dtype, const float* src, void* dst, size_t n, void* stream) {
     return launch_convert(dt_of(dtype), src, dst, n, (hipStream_t)stream);
 }

@@ -376,8 +376,10 @@ __global__ __launch_bounds__(256) void mean_pool_normalize_kernel(const float* _
 // finished rows emit pad; a row finishes when it emits EOS or reaches max_len.
 //
 // The selection is shared by greedy_select_kernel and its scoring form: block argmax over one logits row (EOS masked while
-// mask_eos), result in sv[0] / si[0] for every thread after the last barrier.
-__device__ __forceinline__ void greedy_row_argmax(const float* __restrict__ x, int V, int eos, bool mask_eos, int tid,
+// mask_eos): the row's maximum in sv[0] for every thread after the last barrier, its index returned to every thread.
+// A row with no entry above -inf (all -inf, or finite only at a masked EOS) selects index 0, as torch.argmax does; a NaN never
+// compares greater, so it is never selected (ops.h, launch_greedy_select).
+__device__ __forceinline__ int greedy_row_argmax(const float* __restrict__ x, int V, int eos, bool mask_eos, int tid,
                                                   float* sv, int* si) {
     float best = -INFINITY;
     int bi = 0x7fffffff;
@@ -419,6 +421,7 @@ __device__ __forceinline__ void greedy_row_argmax(const float* __restrict__ x, i
         }
         __syncthreads();
     }
+    return si[0] == 0x7fffffff ? 0 : si[0];              // no winner: the sentinel never leaves this function
 }
 
 // One thread appends the row's token and keeps finished / out_len; returns whether the row was open at this step.
@@ -452,8 +455,8 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const float* __restr
     const bool mask_eos = min_len > 0 && t + 1 < min_len;
     __shared__ float sv[256];
     __shared__ int si[256];
-    greedy_row_argmax(logits + (size_t)crow * ld, V, eos, mask_eos, tid, sv, si);
-    if (tid == 0) greedy_row_emit(row, si[0], seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
+    const int imax = greedy_row_argmax(logits + (size_t)crow * ld, V, eos, mask_eos, tid, sv, si);
+    if (tid == 0) greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
 }
 
 // Scoring form: the same selection, plus log max softmax of the row as the selection sees it (EOS masked while mask_eos) -
@@ -487,9 +490,8 @@ __device__ __forceinline__ void greedy_select_scored_body(const float* __restric
     const float* x = logits + (size_t)crow * ld;
     __shared__ float sv[256];
     __shared__ int si[256];
-    greedy_row_argmax(x, V, eos, mask_eos, tid, sv, si);
+    const int imax = greedy_row_argmax(x, V, eos, mask_eos, tid, sv, si);
     const float zmax = sv[0];
-    const int imax = si[0];
     const bool open = finished[row] == 0;                // uniform over the block; thread 0 writes it only after the barrier below
     __syncthreads();                                     // sv[] is reused for the sums
     float total = 0.f;
@@ -730,6 +732,7 @@ int launch_patchify(int dtype, const void* pixels, int fmt, int B, int img, int 
         cap_set_error("patchify: image %d not divisible by patch %d or Kpad %d too small", img, ps, Kpad);
         return -1;
     }
+    if (dtype == CAP_DT_G8 && Kpad % 8 != 0) { cap_set_error("patchify: G8 rows need Kpad %% 8 == 0 (Kpad=%d)", Kpad); return -1; }
     const size_t n = (size_t)B * 3 * img * img;
     const float m0 = mean ? mean[0] : 0.f, m1 = mean ? mean[1] : 0.f, m2 = mean ? mean[2] : 0.f;
     const float s0 = stdv ? stdv[0] : 1.f, s1 = stdv ? stdv[1] : 1.f, s2 = stdv ? stdv[2] : 1.f;
@@ -828,6 +831,7 @@ __global__ __launch_bounds__(256) void reduce_bias_act_kernel(const float* __res
 
 int launch_reduce_bias_act(int dtype, const float* part, int S, const float* bias, void* out, int M, int N, int act, hipStream_t s) {
     if (N % 4 != 0) { cap_set_error("reduce_bias_act: N must be a multiple of 4"); return -1; }
+    if (dtype == CAP_DT_G8 && N % 8 != 0) { cap_set_error("reduce_bias_act: G8 rows need N %% 8 == 0 (N=%d)", N); return -1; }
     const int grid = (int)std::min<size_t>(((size_t)M * N / 4 + 255) / 256, 2048);
 #define CAP_RB(TT) hipLaunchKernelGGL(reduce_bias_act_kernel<TT>, dim3(grid), dim3(256), 0, s, part, S, bias, (TT*)out, M, N, act)
     CAP_DISPATCH_T(dtype, CAP_RB);
@@ -840,6 +844,7 @@ int launch_embed_tokens(int dtype, const int* ids, int L, const float* word, con
                         const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int R, int D,
                         hipStream_t s, int V) {
     if (D % 4 != 0 || D > 256 * LN_MAXV || V < 1) { cap_set_error("embed_tokens: unsupported width %d / vocabulary %d", D, V); return -1; }
+    if (dtype == CAP_DT_G8 && D % 8 != 0) { cap_set_error("embed_tokens: G8 rows need D %% 8 == 0 (D=%d)", D); return -1; }
 #define CAP_ET(TT) hipLaunchKernelGGL(embed_tokens_kernel<TT>, dim3((R + 3) / 4), dim3(256), 0, s, ids, L, word, pos, type0, gamma, beta, eps, (TT*)out_t, out_f, R, D, V)
     CAP_DISPATCH_T(dtype, CAP_ET);
 #undef CAP_ET
@@ -858,6 +863,7 @@ int launch_embed(int dtype, const int* seq, int seq_ld, int t, const float* word
                  const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int R, int D,
                  hipStream_t s, float* y_out, RowMap map) {
     if (D % 4 != 0 || D > 256 * LN_MAXV) { cap_set_error("embed: unsupported width %d", D); return -1; }
+    if (dtype == CAP_DT_G8 && D % 8 != 0) { cap_set_error("embed: G8 rows need D %% 8 == 0 (D=%d)", D); return -1; }
 #define CAP_EM(TT) hipLaunchKernelGGL(embed_kernel<TT>, dim3((R + 3) / 4), dim3(256), 0, s, seq, seq_ld, t, word, pos, gamma, beta, eps, (TT*)out_t, out_f, y_out, R, D, map)
     CAP_DISPATCH_T(dtype, CAP_EM);
 #undef CAP_EM
@@ -869,6 +875,7 @@ int launch_embed_prompt(int dtype, const int* seq, int seq_ld, int npos, int row
                         const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int n_caps, int D,
                         hipStream_t s, float* y_out) {
     if (D % 4 != 0 || D > 256 * LN_MAXV) { cap_set_error("embed_prompt: unsupported width %d", D); return -1; }
+    if (dtype == CAP_DT_G8 && D % 8 != 0) { cap_set_error("embed_prompt: G8 rows need D %% 8 == 0 (D=%d)", D); return -1; }
     if (npos < 1 || npos > seq_ld || n_caps < 1 || row0 < 0) {
         cap_set_error("embed_prompt: %d positions of %d captions from row %d do not fit rows of %d tokens", npos, n_caps, row0, seq_ld);
         return -1;
@@ -884,7 +891,7 @@ int launch_embed_prompt(int dtype, const int* seq, int seq_ld, int npos, int row
 int launch_init_prompt_seq(int* seq, int* finished, int* out_len, int R, int L, const int* prompt, int prompt_rows, int P, int V,
                            int pad, hipStream_t s) {
     if (!prompt || P < 1 || P > L || (prompt_rows != 1 && prompt_rows != R) || V < 1) {
-        cap_set_error("init_prompt_seq: a prompt of %d rows x %d tokens does not fit %d rows of %d tokens", prompt_rows, P, R, L);
+        cap_set_error("init_prompt_seq: a prompt of %d rows x %d tokens does not fit %d rows of %d tokens (vocabulary %d)", prompt_rows, P, R, L, V);
         return -1;
     }
     hipLaunchKernelGGL(init_prompt_seq_kernel, dim3(64), dim3(256), 0, s, seq, finished, out_len, R, L, prompt, prompt_rows, P, V, pad);

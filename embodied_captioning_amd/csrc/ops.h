@@ -56,7 +56,11 @@ int launch_embed_prompt(int dtype, const int* seq, int seq_ld, int npos, int row
 // seq [R, L] = the prompt (prompt int32 [prompt_rows, P], prompt_rows 1 or R, ids clamped to [0, V)) then pad; finished = 0, len = L
 int launch_init_prompt_seq(int* seq, int* finished, int* out_len, int R, int L, const int* prompt, int prompt_rows, int P, int V,
                            int pad, hipStream_t s);
-// greedy selection: argmax (lowest index wins ties), pad after EOS, append at seq[row][t+1], track finished/len
+// greedy selection: argmax (lowest index wins ties), pad after EOS, append at seq[row][t+1], track finished/len.
+// The token is always inside [0, V), in all three forms (they share the selection).  A NaN logit is never selected: no comparison
+// with it is true, so it stands as -inf does; a row with nothing above -inf (all -inf, all NaN, or finite only at an EOS that
+// min_len still masks) selects index 0, which is what torch.argmax gives for an all -inf row.  (Only the token is defined for
+// such a row or a row holding a NaN: the scoring forms' log-prob of it is NaN in general.)
 int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos,
                          int pad, int* finished, int* out_len, int R, hipStream_t s, int min_len = 0, int force_eos = 0,
                          RowMap map = RowMap(),             // logits row c belongs to row map.live[c] (seq / finished / out_len)

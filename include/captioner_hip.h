@@ -537,6 +537,49 @@ int cap_op_select_vocab(const float* logits, int ld, int V, int R, int t, int ma
 int cap_op_vocab_group_threshold(const float* acc, int acc_ld, int V, int N, const int32_t* group_rows, int M,
                                  const int32_t* group_off, int G, float th, int K, int32_t* out_ids, float* out_prob,
                                  int32_t* out_count, void* stream);
+/* The helper kernels of csrc/elementwise.hip alone (tests/test_elementwise_kernels_gpu.py).  Every pointer is a device pointer
+ * unless said otherwise; dtype picks the type of the GEMM-operand output (CAP_F32 fp32, CAP_BF16 bf16, CAP_F32_SPLIT G8: rows of a
+ * multiple of 8 elements, refused by name otherwise).  The hooks check pointers and counts; widths and layouts are the launchers'.
+ *
+ * Decoder embeddings, one step: compact row c < R (c < *n_live when live / n_live are given, both or neither) takes the token
+ * seq[(live ? live[c] : c) * seq_ld + t] and gives y_out fp32 [R, D] = word[tok] + pos[t], out_f fp32 / out_t (dtype) [R, D] =
+ * LayerNorm(y).  out_t, out_f, y_out may each be NULL.  Tokens are NOT clamped: every token must be inside the word table. */
+int cap_op_embed(int dtype, const int32_t* seq, int seq_ld, int t, const float* word, const float* pos, const float* gamma,
+                 const float* beta, float eps, void* out_t, float* out_f, float* y_out, int R, int D, const int32_t* live,
+                 const int32_t* n_live, void* stream);
+/* The same for positions 0 .. npos - 1 of captions row0 .. row0 + n_caps - 1 at once: output row c * npos + p is position p of
+ * caption row0 + c, with the bits of cap_op_embed at t = p. */
+int cap_op_embed_prompt(int dtype, const int32_t* seq, int seq_ld, int npos, int row0, const float* word, const float* pos,
+                        const float* gamma, const float* beta, float eps, void* out_t, float* out_f, float* y_out, int n_caps, int D,
+                        void* stream);
+/* Sentence-encoder embeddings: row r of R takes ids[r] (clamped to [0, V)) at position r % L:
+ * LayerNorm((word[id] + type0) + pos[r % L]) -> out_t (dtype) and out_f fp32 [R, D], both required. */
+int cap_op_embed_tokens(int dtype, const int32_t* ids, int L, const float* word, const float* pos, const float* type0,
+                        const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int R, int D, int V, void* stream);
+/* The sequence rows of a prompted greedy call: seq int32 [R, L] = prompt int32 [prompt_rows, P] (prompt_rows 1 or R; ids clamped to
+ * [0, V)) in columns 0 .. P - 1 and pad after it; finished[r] = 0, lengths[r] = L. */
+int cap_op_init_prompt_seq(int32_t* seq, int32_t* finished, int32_t* lengths, int R, int L, const int32_t* prompt, int prompt_rows,
+                           int P, int V, int pad, void* stream);
+/* live int32 [R] = the rows with finished[r] == 0 in ascending order (entries from the count on are left alone), *n_live = count */
+int cap_op_compact_rows(const int32_t* finished, int R, int32_t* live, int32_t* n_live, void* stream);
+/* Split-K consumer without LayerNorm: out (dtype) [M, N] = act(((part[0] + part[1]) + ...) + bias), part fp32 [S][M][N], bias [N]
+ * or NULL, act 0 none / 2 ReLU.  N % 4 == 0. */
+int cap_op_reduce_bias_act(int dtype, const float* part, int S, const float* bias, void* out, int M, int N, int act, void* stream);
+/* Sentence pooling: out fp32 [B, D] = normalize(mean over the first clamp(lens[b], 1, L) rows of x fp32 [B, L, D]), F.normalize's
+ * eps 1e-12.  D % 4 == 0, D <= 1024. */
+int cap_op_mean_pool_normalize(const float* x, const int32_t* lens, int B, int L, int D, float* out, void* stream);
+/* Patch gather: pixels (fmt CAP_PIX_F32_NCHW fp32 [B, 3, img, img], or CAP_PIX_U8_NHWC uint8 [B, img, img, 3] normalised with
+ * (x / 255 - mean[c]) / std[c]) -> out (dtype) [B * (img / ps)^2, Kpad], column c * ps^2 + dy * ps + dx; columns from 3 ps^2 on are
+ * left alone.  mean / std: HOST pointers to 3 floats (NULL: 0 / 1). */
+int cap_op_patchify(int dtype, const void* pixels, int fmt, int B, int img, int ps, int Kpad, void* out, const float* mean,
+                    const float* std, void* stream);
+/* X fp32 [B, tokens, D]: X[b, 0, :] = cls + pos[0, :]; nothing else is written */
+int cap_op_cls_rows(const float* cls, const float* pos, float* X, int B, int tokens, int D, void* stream);
+/* fp32 src [rows, cols] -> dst (dtype), values times scale: dst[r * dst_ld + c] = src[r][c] (columns from cols on left alone), or
+ * with transposed != 0 the dense transpose dst[c * rows + r] (dst_ld == rows). */
+int cap_op_convert2d(int dtype, const float* src, void* dst, int rows, int cols, int dst_ld, float scale, int transposed, void* stream);
+/* *out_bits = max(*out_bits, bit pattern of max |src[i]|): the caller zeroes it.  A NaN gives a pattern above +inf's. */
+int cap_op_absmax(const float* src, size_t n, uint32_t* out_bits, void* stream);
 int cap_op_convert(int dtype, const float* src, void* dst, size_t n, void* stream);
 /* Weight upload as cap_load_weight does it: dst [rows, cols] in the GEMM-operand type of `dtype` (CAP_F32_SPLIT: G8 halves of
  * 4096 * w - the split GEMM's epilogue divides by 4096; a G8 buffer is 4 bytes per element, cols % 8 == 0). */
