@@ -71,6 +71,16 @@ class CapSmallCross(C.Structure):
     ]
 
 
+class CapGenerateArgs(C.Structure):
+    _fields_ = [
+        ("pixels", C.c_void_p), ("pixel_fmt", C.c_int32), ("B", C.c_int32), ("num_beams", C.c_int32), ("num_beam_groups", C.c_int32),
+        ("max_len", C.c_int32), ("length_penalty", C.c_float), ("out_ids", C.c_void_p), ("out_len", C.c_void_p),
+        ("out_scores", C.c_void_p), ("out_step_logits", C.c_void_p), ("out_logprobs", C.c_void_p), ("out_scored", C.c_void_p),
+        ("out_vocab", C.c_void_p), ("acc_ld", C.c_int32), ("prompt_ids", C.c_void_p), ("prompt_rows", C.c_int32),
+        ("prompt_len", C.c_int32),
+    ]
+
+
 _SIGNATURES = {
     "cap_last_error": (C.c_char_p, []),
     "cap_version": (C.c_int, []),
@@ -80,6 +90,7 @@ _SIGNATURES = {
     "cap_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p]),
     "cap_finalize_weights": (C.c_int, [C.c_void_p]),
     "cap_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cap_generate_request": (C.c_int, [C.c_void_p, C.POINTER(CapGenerateArgs), C.c_void_p]),
     "cap_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cap_generate_scored": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,

@@ -667,12 +667,48 @@ int poll_all_finished(Captioner* m, int step, int steps, const int* finished, in
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- a request's per-step outputs
+// Both decode loops (run_generate, run_generate_blip2) write a request's optional outputs through these.  R = rows of the loop,
+// cols = steps a caption can take (max_len - 1 for BLIP / CoCa, max_len for BLIP-2), step = index among them.
+__global__ void copy_logits_kernel(const float* src, int ld, float* dst, int R, int V) {
+    const size_t n = (size_t)R * V;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / V, c = i - r * V;
+        dst[i] = src[r * ld + c];
+    }
+}
+// out_logprobs [R, cols] / out_scored [R] / out_vocab [R, acc_ld] start from zero, on the caller's stream: the selection kernel
+// writes the open captions' entries only, indexed by the caption's row whatever the loop's compaction
+int zero_greedy_outputs(const CapGenerateArgs& a, int R, int cols, hipStream_t s) {
+    if (a.out_logprobs) {
+        TRY(launch_fill_f32(a.out_logprobs, 0.f, (size_t)R * cols, s));
+        TRY(launch_fill_i32(a.out_scored, 0, (size_t)R, s));
+    }
+    if (a.out_vocab) TRY(launch_fill_f32(a.out_vocab, 0.f, (size_t)R * a.acc_ld, s));
+    return 0;
+}
+int copy_step_logits(Captioner* m, const CapGenerateArgs& a, int R, int step, hipStream_t s) {
+    if (!a.out_step_logits) return 0;
+    hipLaunchKernelGGL(copy_logits_kernel, dim3(1024), dim3(256), 0, s, m->logits, m->ldl,
+                       a.out_step_logits + (size_t)step * R * m->c.vocab, R, m->c.vocab);
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+// The token of position t + 1 of every open caption (a row ends on EOS or at `end` tokens; CoCa: MinLength mask and forced EOS), with
+// the request's log-prob / vocabulary outputs taken by the same kernel.
+int select_greedy_step(Captioner* m, const CapGenerateArgs& a, int R, int step, int cols, int seq_ld, int t, int end, RowMap map,
+                       hipStream_t s) {
+    const CapConfig& c = m->c;
+    const bool coca = c.arch == CAP_ARCH_COCA;
+    return launch_greedy_select(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s,
+                                coca ? c.min_len : 0, coca ? 1 : 0, map, a.out_logprobs, cols, step, a.out_scored, a.out_vocab, a.acc_ld);
+}
+
 // ---------------------------------------------------------------------------------------------- BLIP-2 OPT
 int run_encoder(Captioner* m, const void* pixels, int fmt, int B, float* out_embeds, hipStream_t s);
 int gemm_partial(Captioner* m, hipStream_t s, const char* tag, const void* A, const void* W, float* part, int R, int N,
                  int K, int max_S, int* S_out, const int* m_live = nullptr);
 __global__ void init_seq_kernel(int* seq, int* fin, int* len, int R, int L, int bos, int pad);
-__global__ void copy_logits_kernel(const float* src, int ld, float* dst, int R, int V);
 __global__ void copy_new_tokens_kernel(const int* seq, int seq_ld, int P, const int* lens, int* out_ids, int* out_len, int B, int n) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * n; i += gridDim.x * blockDim.x) out_ids[i] = seq[(size_t)(i / n) * seq_ld + P + i % n];
     if (out_len)
@@ -1067,18 +1103,13 @@ int run_opt_prompt_plain(Captioner* m, int B, int L, hipStream_t s) {
 }
 
 // HF Blip2ForConditionalGeneration.generate, greedy: out_ids [B, max_len] = the new tokens (pad after EOS), out_len [B] =
-// their count incl. EOS, out_step_logits [max_len, B, vocab]; out_lp [B, max_len] / out_scored [B]: cap_generate_scored.
-int run_generate_blip2(Captioner* m, const void* pixels, int fmt, int B, int max_len, int32_t* out_ids, int32_t* out_len,
-                       float* out_step_logits, float* out_lp, int32_t* out_scored, hipStream_t s, float* out_vocab = nullptr,
-                       int acc_ld = 0) {
+// their count incl. EOS, out_step_logits [max_len, B, vocab]; the optional greedy outputs have max_len columns.
+int run_generate_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
     const CapConfig& c = m->c;
+    const int B = a.B, max_len = a.max_len;
     const int T = c.t_hidden, nq = c.num_query_tokens, P = nq + 1, Lmax = P + c.max_len;
-    if (out_lp) {
-        TRY(launch_fill_f32(out_lp, 0.f, (size_t)B * max_len, s));
-        TRY(launch_fill_i32(out_scored, 0, (size_t)B, s));
-    }
-    if (out_vocab) TRY(launch_fill_f32(out_vocab, 0.f, (size_t)B * acc_ld, s));
-    TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
+    TRY(zero_greedy_outputs(a, B, max_len, s));
+    TRY(run_encoder(m, a.pixels, a.pixel_fmt, B, nullptr, s));
     TRY(run_qformer(m, B, s));
     TRY(gemm(m, s, "b2_gemm_lproj", m->qx_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1));
     TRY(launch_opt_prefill_inputs(m->lm_proj, m->o_tok, m->o_pos, m->ox, B, nq, T, c.bos, s));
@@ -1092,14 +1123,9 @@ int run_generate_blip2(Captioner* m, const void* pixels, int fmt, int B, int max
     }
     for (int t = 0; t < max_len; ++t) {
         m->last_steps = t + 1;
-        if (out_step_logits) {
-            hipLaunchKernelGGL(copy_logits_kernel, dim3(1024), dim3(256), 0, s, m->logits, m->ldl,
-                               out_step_logits + (size_t)t * B * c.vocab, B, c.vocab);
-            CAP_HIP_CHECK(hipGetLastError());
-        }
         // token of position P + t; a row finishes on EOS or at P + max_len tokens (greedy_select's `t` is the last filled index)
-        TRY(launch_greedy_select(m->logits, m->ldl, c.vocab, m->seq, Lmax, P - 1 + t, P + max_len, c.eos, c.pad, m->finished, m->lens, B, s, 0, 0,
-                                 RowMap(), out_lp, max_len, t, out_scored, out_vocab, acc_ld));
+        TRY(copy_step_logits(m, a, B, t, s));
+        TRY(select_greedy_step(m, a, B, t, max_len, Lmax, P - 1 + t, P + max_len, RowMap(), s));
         if (t + 1 == max_len) break;
         {
             bool done;
@@ -1110,7 +1136,7 @@ int run_generate_blip2(Captioner* m, const void* pixels, int fmt, int B, int max
         TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B, T, s));
         TRY(run_opt(m, B, 1, P + t, s));
     }
-    hipLaunchKernelGGL(copy_new_tokens_kernel, dim3(64), dim3(256), 0, s, m->seq, Lmax, P, m->lens, out_ids, out_len, B, max_len);
+    hipLaunchKernelGGL(copy_new_tokens_kernel, dim3(64), dim3(256), 0, s, m->seq, Lmax, P, m->lens, a.out_ids, a.out_len, B, max_len);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1690,13 +1716,6 @@ __global__ void init_seq_kernel(int* seq, int* fin, int* len, int R, int L, int 
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < R * L; i += gridDim.x * blockDim.x) seq[i] = (i % L == 0) ? bos : pad;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < R; i += gridDim.x * blockDim.x) { fin[i] = 0; len[i] = L; }
 }
-__global__ void copy_logits_kernel(const float* src, int ld, float* dst, int R, int V) {
-    const size_t n = (size_t)R * V;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = i / V, c = i - r * V;
-        dst[i] = src[r * ld + c];
-    }
-}
 __global__ void copy_i32_kernel(const int* s, int* d, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) d[i] = s[i];
 }
@@ -1716,36 +1735,35 @@ static int run_image_side(Captioner* m, const void* pixels, int fmt, int B, hipS
     return 0;
 }
 
-int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm, float lp, int32_t* out_ids,
-                 int32_t* out_len, float* out_scores, float* out_step_logits, hipStream_t s, bool force_beam = false,
-                 float* out_lp = nullptr, int32_t* out_scored = nullptr, float* out_vocab = nullptr, int acc_ld = 0,
-                 const int32_t* prompt = nullptr, int prompt_rows = 0, int Pn = 0) {
-    // force_beam: K == 1 runs as a 1-beam BEAM search (the scorer's bookkeeping, no forced EOS) instead of the greedy loop -
-    // what a beam group of size one is (cap_generate_groups)
-    // out_lp [B, Lm - 1] / out_scored [B] (greedy only, cap_generate_scored): per-step log max softmax from the selection kernel,
-    // indexed by the caption's row whatever the loop's compaction; zero-filled here, on the caller's stream
-    // out_vocab [B, acc_ld] (cap_generate_vocab; with out_lp): per-caption maximum over its steps of the step's softmax, same rules
-    // prompt int32 [prompt_rows, Pn] (device; cap_generate_prompted, greedy BLIP): every caption starts with these Pn tokens; positions
-    // 0 .. Pn - 2 run as a prefill and the loop starts at t = Pn - 1, so step outputs (out_step_logits, out_lp) are indexed from there
+// Rows of one beam search of the request.  A group search (num_beam_groups given): the reference's loop runs its groups one after
+// the other on the SAME logits with only MinLength / RepetitionPenalty(1.0) as processors (coca_model.py:236-241: no
+// HammingDiversity processor), every group starts from the same scores (:380-384), and finalize picks the best hypothesis over all
+// groups of an image: the groups are identical searches of num_beams / num_beam_groups beams, and the result is that of ONE of
+// them.  That one is what runs.
+int beams_per_search(const CapGenerateArgs& a) { return a.num_beam_groups ? a.num_beams / a.num_beam_groups : a.num_beams; }
+
+// BLIP / CoCa.  num_beams == 1 is the greedy loop (HF `_sample` with do_sample=False; CoCa: the reference's top-k(1) loop, coca.py:29),
+// num_beams > 1 beam search (CoCa: its `_generate_beamsearch`, coca_model.py:335-482; length_penalty is the scorer's).  A group
+// search runs as a BEAM search (the scorer's bookkeeping, no forced EOS) even with one beam per group.
+// prompt_ids [prompt_rows, prompt_len] (greedy BLIP): every caption starts with these tokens; positions 0 .. prompt_len - 2 run as a
+// prefill and the loop starts at t = prompt_len - 1, so the step outputs (out_step_logits, out_logprobs) are indexed from there.
+int run_generate(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
     const CapConfig& c = m->c;
-    const int t0 = prompt ? Pn - 1 : 0;
+    const int B = a.B, K = beams_per_search(a), Lm = a.max_len;
+    const int t0 = a.prompt_ids ? a.prompt_len - 1 : 0;
     const int R = B * K;
     const bool coca = c.arch == CAP_ARCH_COCA;
-    const bool greedy = K == 1 && !force_beam;
-    if (out_lp) {
-        TRY(launch_fill_f32(out_lp, 0.f, (size_t)R * (Lm - 1), s));
-        TRY(launch_fill_i32(out_scored, 0, (size_t)R, s));
-    }
-    if (out_vocab) TRY(launch_fill_f32(out_vocab, 0.f, (size_t)R * acc_ld, s));
-    TRY(run_image_side(m, pixels, fmt, B, s));
+    const bool greedy = K == 1 && !a.num_beam_groups;
+    TRY(zero_greedy_outputs(a, R, Lm - 1, s));
+    TRY(run_image_side(m, a.pixels, a.pixel_fmt, B, s));
     Dec d = make_dec(m, B, K);
     // Row compaction (ops.h, RowMap): the greedy BLIP loop on the batch kernels, when nobody asked for per-step logits (their rows
     // are the batch's rows) and every position takes the fused self-attention (<= 32: the k / v append goes through map.live)
-    const bool compact = greedy && c.arch == CAP_ARCH_BLIP && m->compaction && m->live && !out_step_logits && Lm - 1 <= 32 &&
+    const bool compact = greedy && c.arch == CAP_ARCH_BLIP && m->compaction && m->live && !a.out_step_logits && Lm - 1 <= 32 &&
                          R > SMALL_MAX_ROWS && m->decode_path != 2;
     m->last_compacted = compact ? 1 : 0;
     if (greedy) {
-        if (prompt) TRY(launch_init_prompt_seq(d.seq, d.finished, d.lens, R, Lm, prompt, prompt_rows, Pn, c.vocab, c.pad, s));
+        if (a.prompt_ids) TRY(launch_init_prompt_seq(d.seq, d.finished, d.lens, R, Lm, a.prompt_ids, a.prompt_rows, a.prompt_len, c.vocab, c.pad, s));
         else hipLaunchKernelGGL(init_seq_kernel, dim3(64), dim3(256), 0, s, d.seq, d.finished, d.lens, R, Lm, c.bos, c.pad);
         if (compact) {
             d.map.live = m->live; d.map.n = m->n_live;
@@ -1756,11 +1774,6 @@ int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm
         hipLaunchKernelGGL(iota_rows_kernel, dim3(64), dim3(256), 0, s, d.anc, R, Lm);
     }
     CAP_HIP_CHECK(hipGetLastError());
-    if (m->decode_path == 2 && Lm - 1 > 32) {      // fail at entry, not after 32 steps have run
-        cap_set_error("cap_generate: the small-batch decode path was forced (cap_set_decode_path 2) but max_len %d needs %d positions: "
-                      "it takes at most 32 (automatic selection continues on the batch kernels from position 33)", Lm, Lm - 1);
-        return -1;
-    }
     m->last_prefill_passes = 0;
     if (t0 > 0) {
         // the whole batch in one pass where the workspace holds it (CapConfig.max_prompt), else as many captions at a time as it does
@@ -1775,42 +1788,29 @@ int run_generate(Captioner* m, const void* pixels, int fmt, int B, int K, int Lm
         m->last_steps = t + 1;
         const int* tokens = greedy ? d.seq : beam_running_tokens_p(d.beam, B, K, Lm, cur_len & 1);
         const int* anc = greedy ? nullptr : d.anc + (size_t)(cur_len & 1) * R * Lm;
-        {
-            const bool can = small_path_takes(m, d, t);
-            if (m->decode_path == 2 && !can) {
-                cap_set_error("cap_generate: the small-batch decode path was forced (cap_set_decode_path 2) but does not take this call "
-                              "(%d rows, step %d, compute type %d): at most %d rows, 32 positions, split or bf16 mode, BLIP / CoCa", R, t, m->gdt, SMALL_MAX_ROWS);
-                return -1;
-            }
-            const bool small = can && (m->decode_path == 0 || m->decode_path == 2);
-            m->last_path = small ? 2 : 1;
-            TRY((small ? run_step_small : run_step)(m, d, tokens, Lm, t, K, anc, Lm, s));
-        }
-        if (out_step_logits) {
-            hipLaunchKernelGGL(copy_logits_kernel, dim3(1024), dim3(256), 0, s, d.logits, m->ldl,
-                               out_step_logits + (size_t)(t - t0) * R * c.vocab, R, c.vocab);
-            CAP_HIP_CHECK(hipGetLastError());
-        }
+        // a forced small path (decode_path 2) takes every step of the call: validate_generate refused the request otherwise
+        const bool small = m->decode_path != 1 && small_path_takes(m, d, t);
+        m->last_path = small ? 2 : 1;
+        TRY((small ? run_step_small : run_step)(m, d, tokens, Lm, t, K, anc, Lm, s));
+        TRY(copy_step_logits(m, a, R, t - t0, s));
         ProfScope ps(m, s, greedy ? "greedy_select" : "beam_step", 0, (double)R * c.vocab * 4);
-        if (greedy)
-        {
-            TRY(launch_greedy_select(d.logits, m->ldl, c.vocab, d.seq, Lm, t, Lm, c.eos, c.pad, d.finished, d.lens, R, s,
-                                     coca ? c.min_len : 0, coca ? 1 : 0, d.map, out_lp, Lm - 1, t - t0, out_scored, out_vocab, acc_ld));
+        if (greedy) {
+            TRY(select_greedy_step(m, a, R, t - t0, Lm - 1, Lm, t, Lm, d.map, s));
             if (compact) TRY(launch_compact_rows(d.finished, R, m->live, m->n_live, s));
-        }
-        else
-            TRY(launch_beam_step(d.beam, d.logits, m->ldl, c.vocab, B, K, Lm, cur_len, c.eos, lp, d.anc, Lm, s,
+        } else {
+            TRY(launch_beam_step(d.beam, d.logits, m->ldl, c.vocab, B, K, Lm, cur_len, c.eos, a.length_penalty, d.anc, Lm, s,
                                  coca ? BEAM_LEGACY_RAW : BEAM_HF_V5, coca ? c.min_len : 0));
+        }
         bool done;
         TRY(poll_all_finished(m, t, Lm - 1, d.finished, R, greedy ? nullptr : beam_active_flag_p(d.beam, B, K, Lm), s, &done));
         if (done) break;
     }
     if (greedy) {
-        hipLaunchKernelGGL(copy_i32_kernel, dim3(64), dim3(256), 0, s, d.seq, out_ids, (size_t)R * Lm);
-        if (out_len) hipLaunchKernelGGL(copy_i32_kernel, dim3(4), dim3(256), 0, s, d.lens, out_len, (size_t)R);
+        hipLaunchKernelGGL(copy_i32_kernel, dim3(64), dim3(256), 0, s, d.seq, a.out_ids, (size_t)R * Lm);
+        if (a.out_len) hipLaunchKernelGGL(copy_i32_kernel, dim3(4), dim3(256), 0, s, d.lens, a.out_len, (size_t)R);
         CAP_HIP_CHECK(hipGetLastError());
     } else {
-        TRY(launch_beam_finalize(d.beam, B, K, Lm, out_ids, out_len, out_scores, s));
+        TRY(launch_beam_finalize(d.beam, B, K, Lm, a.out_ids, a.out_len, a.out_scores, s));
     }
     return 0;
 }
@@ -2120,18 +2120,18 @@ int cap_finalize_weights(CapHandle h) {
     return missing;
 }
 
-static int check_call(Captioner* m, int B, int K, int Lm, int fmt) {
-    if (!m) { cap_set_error("null handle"); return -1; }
+static int check_call(Captioner* m, int B, int K, int Lm, int fmt, const char* who) {
+    if (!m) { cap_set_error("%s: null handle", who); return -1; }
     if (cap_finalize_weights((CapHandle)m) != 0) return -1;
     if (B < 1 || B > m->c.max_batch || K < 1 || K > m->c.max_beams || Lm < (m->c.arch == CAP_ARCH_BLIP2 ? 1 : 2) || Lm > m->c.max_len) {
-        cap_set_error("request B=%d beams=%d max_len=%d exceeds the handle's capacity (%d, %d, %d)", B, K, Lm,
+        cap_set_error("%s: request B=%d beams=%d max_len=%d exceeds the handle's capacity (%d, %d, %d)", who, B, K, Lm,
                       m->c.max_batch, m->c.max_beams, m->c.max_len);
         return -1;
     }
-    if (fmt != CAP_PIX_F32_NCHW && fmt != CAP_PIX_U8_NHWC) { cap_set_error("unknown pixel format %d", fmt); return -1; }
-    if (m->c.arch == CAP_ARCH_MINILM) { cap_set_error("this handle is a sentence encoder: use cap_embed_text"); return -1; }
-    if (m->c.arch == CAP_ARCH_CLIP) { cap_set_error("this handle is a CLIP scorer: use cap_clip_embed_images / cap_clip_embed_text"); return -1; }
-    if (m->c.arch == CAP_ARCH_BLIP2_ITM) { cap_set_error("this handle is a BLIP-2 image-text scorer: use cap_blip2_itm_encode_images / cap_blip2_itc_* / cap_blip2_itm_logits"); return -1; }
+    if (fmt != CAP_PIX_F32_NCHW && fmt != CAP_PIX_U8_NHWC) { cap_set_error("%s: unknown pixel format %d", who, fmt); return -1; }
+    if (m->c.arch == CAP_ARCH_MINILM) { cap_set_error("%s: this handle is a sentence encoder: use cap_embed_text", who); return -1; }
+    if (m->c.arch == CAP_ARCH_CLIP) { cap_set_error("%s: this handle is a CLIP scorer: use cap_clip_embed_images / cap_clip_embed_text", who); return -1; }
+    if (m->c.arch == CAP_ARCH_BLIP2_ITM) { cap_set_error("%s: this handle is a BLIP-2 image-text scorer: use cap_blip2_itm_encode_images / cap_blip2_itc_* / cap_blip2_itm_logits", who); return -1; }
     return 0;
 }
 
@@ -2262,7 +2262,7 @@ int cap_embed_text(CapHandle h, const int32_t* ids, const int32_t* lens, int B, 
 
 int cap_encode(CapHandle h, const void* pixels, int pixel_fmt, int B, float* out_embeds, void* stream) {
     Captioner* m = (Captioner*)h;
-    TRY(check_call(m, B, 1, 2, pixel_fmt));
+    TRY(check_call(m, B, 1, 2, pixel_fmt, "cap_encode"));
     if (!pixels || !out_embeds) { cap_set_error("cap_encode: null buffer"); return -1; }
     if (m->c.arch == CAP_ARCH_COCA) {    // out_embeds: fp32 [B, pool_queries, embed_dim] (row 0 pooled token, rows 1.. image_embs)
         TRY(run_encoder(m, pixels, pixel_fmt, B, nullptr, (hipStream_t)stream));
@@ -2271,97 +2271,87 @@ int cap_encode(CapHandle h, const void* pixels, int pixel_fmt, int B, float* out
     return run_encoder(m, pixels, pixel_fmt, B, out_embeds, (hipStream_t)stream);
 }
 
+// Every rule of a generate request, each once, in the order of refusal: the handle and its capacity (check_call), buffers, what the
+// architecture takes, shapes - all before anything is launched.  who: the entry point the caller used; missing: what that entry
+// point requires beyond the request's own rules and did not get (null: nothing).
+static int validate_generate(Captioner* m, const CapGenerateArgs& a, const char* who, const char* missing) {
+#define REFUSE_IF(cond, ...) do { if (cond) { cap_set_error(__VA_ARGS__); return -1; } } while (0)
+    TRY(check_call(m, a.B, a.num_beams, a.max_len, a.pixel_fmt, who));
+    const CapConfig& c = m->c;
+    const int K = a.num_beams, G = a.num_beam_groups, P = a.prompt_len;
+    const bool greedy = K == 1 && !G;
+    REFUSE_IF(!a.pixels || !a.out_ids, "%s: null buffer", who);
+    REFUSE_IF(missing, "%s: %s", who, missing);
+    REFUSE_IF(a.prompt_ids && c.arch != CAP_ARCH_BLIP,
+              "%s: a text prompt is taken by CAP_ARCH_BLIP handles (this handle's arch is %d: CoCa's `text=` and BLIP-2's prompt are not built)",
+              who, c.arch);
+    REFUSE_IF(G && c.arch != CAP_ARCH_COCA,
+              "%s: beam groups are the CoCa loop's (coca_model.py:335-482); HF's group beam search for the other architectures needs a "
+              "diversity penalty, which this library does not implement", who);
+    REFUSE_IF(c.arch == CAP_ARCH_BLIP2 && K != 1, "%s: BLIP-2 supports greedy decoding (num_beams = 1)", who);
+    REFUSE_IF(G < 0 || G > K || (G && K % G != 0), "%s: num_beams (%d) must be a multiple of num_beam_groups (%d) (BeamSearchScorer's own check)",
+              who, K, G);
+    REFUSE_IF(G && a.out_step_logits, "%s: per-step logits are not recorded by the group beam search", who);
+    if (a.prompt_ids) {
+        REFUSE_IF(!greedy, "%s: a prompt is taken by the greedy loop (num_beams = 1, no beam groups), got num_beams = %d", who, K);
+        REFUSE_IF(a.prompt_rows != 1 && a.prompt_rows != a.B, "%s: prompt_rows %d is neither 1 (shared) nor the batch size %d", who, a.prompt_rows, a.B);
+        REFUSE_IF(P > CAP_MAX_PROMPT, "%s: prompt_len %d exceeds the limit of %d prompt tokens (BOS included)", who, P, CAP_MAX_PROMPT);
+        REFUSE_IF(P < 2 || P >= a.max_len,
+                  "%s: prompt_len %d must be in [2, max_len = %d): BOS plus at least one token, and room for one generated token", who, P, a.max_len);
+        REFUSE_IF((size_t)(P - 1) > m->ws_rows,
+                  "%s: prompt_len %d exceeds the limit of %zu tokens this handle's workspace (%zu rows) takes: create it with "
+                  "CapConfig.max_prompt >= %d", who, P, m->ws_rows + 1, m->ws_rows, P);
+    }
+    REFUSE_IF((a.out_logprobs != nullptr) != (a.out_scored != nullptr), "%s: out_logprobs and out_scored come together (both or neither)", who);
+    REFUSE_IF(a.out_logprobs && !greedy,
+              "%s: per-step log-probs are the greedy loop's (num_beams = 1), got num_beams = %d: beam search returns sequences_scores", who, K);
+    if (a.out_vocab) {
+        REFUSE_IF(!a.out_logprobs, "%s: out_vocab needs out_logprobs and out_scored", who);
+        REFUSE_IF(a.acc_ld < c.vocab, "%s: acc_ld (%d) is below the vocabulary size (%d)", who, a.acc_ld, c.vocab);
+        REFUSE_IF(a.acc_ld % 4 != 0, "%s: acc_ld (%d) must be a multiple of 4 (16-byte rows)", who, a.acc_ld);
+        REFUSE_IF(((uintptr_t)a.out_vocab & 15) != 0, "%s: out_vocab must be 16-byte aligned", who);
+    }
+    if (m->decode_path == 2 && c.arch != CAP_ARCH_BLIP2) {      // within a call small_path_takes varies only through the position
+        const int R = a.B * beams_per_search(a), t0 = a.prompt_ids ? P - 1 : 0;
+        REFUSE_IF(a.max_len - 1 > 32,
+                  "%s: the small-batch decode path was forced (cap_set_decode_path 2) but max_len %d needs %d positions: it takes at most 32 "
+                  "(automatic selection continues on the batch kernels from position 33)", who, a.max_len, a.max_len - 1);
+        REFUSE_IF(!small_path_takes(m, make_dec(m, a.B, beams_per_search(a)), t0),
+                  "%s: the small-batch decode path was forced (cap_set_decode_path 2) but does not take this call (%d rows, step %d, compute "
+                  "type %d): at most %d rows, 32 positions, split or bf16 mode, BLIP / CoCa", who, R, t0, m->gdt, SMALL_MAX_ROWS);
+    }
+#undef REFUSE_IF
+    return 0;
+}
+
+// The one way into the decode loops: validate, then the architecture's loop.
+static int generate(CapHandle h, const CapGenerateArgs& a, void* stream, const char* who, const char* missing) {
+    Captioner* m = (Captioner*)h;
+    TRY(validate_generate(m, a, who, missing));
+    return (m->c.arch == CAP_ARCH_BLIP2 ? run_generate_blip2 : run_generate)(m, a, (hipStream_t)stream);
+}
+
+int cap_generate_request(CapHandle h, const CapGenerateArgs* args, void* stream) {
+    if (!args) { cap_set_error("cap_generate_request: null request"); return -1; }
+    return generate(h, *args, stream, "cap_generate_request", nullptr);
+}
+
+// The five calls below fix parts of a request and leave the rest absent.
+static CapGenerateArgs request_of(const void* pixels, int pixel_fmt, int B, int num_beams, int max_len, float length_penalty,
+                                  int32_t* out_ids, int32_t* out_len) {
+    CapGenerateArgs a = {};
+    a.pixels = pixels; a.pixel_fmt = pixel_fmt; a.B = B; a.num_beams = num_beams; a.max_len = max_len; a.length_penalty = length_penalty;
+    a.out_ids = out_ids; a.out_len = out_len;
+    return a;
+}
+
 int cap_generate_scored(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int max_len, float length_penalty,
                         int32_t* out_ids, int32_t* out_len, float* out_scores, float* out_step_logits, float* out_logprobs,
                         int32_t* out_scored, void* stream) {
-    Captioner* m = (Captioner*)h;
-    TRY(check_call(m, B, num_beams, max_len, pixel_fmt));
-    if (!pixels || !out_ids) { cap_set_error("cap_generate: null buffer"); return -1; }
-    if ((out_logprobs != nullptr) != (out_scored != nullptr)) {
-        cap_set_error("cap_generate_scored: out_logprobs and out_scored come together (both or neither)");
-        return -1;
-    }
-    if (out_logprobs && num_beams != 1) {
-        cap_set_error("cap_generate_scored: per-step log-probs are the greedy loop's (num_beams = 1), got num_beams = %d: beam search "
-                      "returns sequences_scores", num_beams);
-        return -1;
-    }
-    if (m->c.arch == CAP_ARCH_BLIP2) {
-        if (num_beams != 1) { cap_set_error("cap_generate: BLIP-2 supports greedy decoding (num_beams = 1)"); return -1; }
-        return run_generate_blip2(m, pixels, pixel_fmt, B, max_len, out_ids, out_len, out_step_logits, out_logprobs, out_scored,
-                                  (hipStream_t)stream);
-    }
-    // CoCa: num_beams == 1 is the reference's top-k(1) loop (coca.py:29), num_beams > 1 its `_generate_beamsearch` with one
-    // beam group (coca_model.py:335-482; length_penalty is the scorer's: pass 1.0 for the reference's default)
-    return run_generate(m, pixels, pixel_fmt, B, num_beams, max_len, length_penalty, out_ids, out_len, out_scores,
-                        out_step_logits, (hipStream_t)stream, false, out_logprobs, out_scored);
+    CapGenerateArgs a = request_of(pixels, pixel_fmt, B, num_beams, max_len, length_penalty, out_ids, out_len);
+    a.out_scores = out_scores; a.out_step_logits = out_step_logits; a.out_logprobs = out_logprobs; a.out_scored = out_scored;
+    return generate(h, a, stream, out_logprobs || out_scored ? "cap_generate_scored" : "cap_generate", nullptr);
 }
-
-int cap_generate_vocab(CapHandle h, const void* pixels, int pixel_fmt, int B, int max_len, int32_t* out_ids, int32_t* out_len,
-                       float* out_step_logits, float* out_logprobs, int32_t* out_scored, float* out_vocab, int acc_ld, void* stream) {
-    Captioner* m = (Captioner*)h;
-    TRY(check_call(m, B, 1, max_len, pixel_fmt));
-    if (!pixels || !out_ids) { cap_set_error("cap_generate_vocab: null buffer"); return -1; }
-    if (!out_logprobs || !out_scored || !out_vocab) {
-        cap_set_error("cap_generate_vocab: out_logprobs, out_scored and out_vocab are all required");
-        return -1;
-    }
-    if (acc_ld < m->c.vocab) { cap_set_error("cap_generate_vocab: acc_ld (%d) is below the vocabulary size (%d)", acc_ld, m->c.vocab); return -1; }
-    if (acc_ld % 4 != 0) { cap_set_error("cap_generate_vocab: acc_ld (%d) must be a multiple of 4 (16-byte rows)", acc_ld); return -1; }
-    if (((uintptr_t)out_vocab & 15) != 0) { cap_set_error("cap_generate_vocab: out_vocab must be 16-byte aligned"); return -1; }
-    if (m->c.arch == CAP_ARCH_BLIP2)
-        return run_generate_blip2(m, pixels, pixel_fmt, B, max_len, out_ids, out_len, out_step_logits, out_logprobs, out_scored,
-                                  (hipStream_t)stream, out_vocab, acc_ld);
-    return run_generate(m, pixels, pixel_fmt, B, 1, max_len, 1.0f, out_ids, out_len, nullptr, out_step_logits, (hipStream_t)stream, false,
-                        out_logprobs, out_scored, out_vocab, acc_ld);
-}
-
-int cap_generate_prompted(CapHandle h, const void* pixels, int pixel_fmt, int B, int max_len, const int32_t* prompt_ids, int prompt_rows,
-                          int prompt_len, int32_t* out_ids, int32_t* out_len, float* out_step_logits, float* out_logprobs,
-                          int32_t* out_scored, float* out_vocab, int acc_ld, void* stream) {
-    Captioner* m = (Captioner*)h;
-    TRY(check_call(m, B, 1, max_len, pixel_fmt));
-    if (!pixels || !out_ids || !prompt_ids) { cap_set_error("cap_generate_prompted: null buffer"); return -1; }
-    if (m->c.arch != CAP_ARCH_BLIP) {
-        cap_set_error("cap_generate_prompted: a text prompt is taken by CAP_ARCH_BLIP handles (this handle's arch is %d: CoCa's `text=` and "
-                      "BLIP-2's prompt are not built)", m->c.arch);
-        return -1;
-    }
-    if (prompt_rows != 1 && prompt_rows != B) {
-        cap_set_error("cap_generate_prompted: prompt_rows %d is neither 1 (shared) nor the batch size %d", prompt_rows, B);
-        return -1;
-    }
-    if (prompt_len > CAP_MAX_PROMPT) {
-        cap_set_error("cap_generate_prompted: prompt_len %d exceeds the limit of %d prompt tokens (BOS included)", prompt_len, CAP_MAX_PROMPT);
-        return -1;
-    }
-    if (prompt_len < 2 || prompt_len >= max_len) {
-        cap_set_error("cap_generate_prompted: prompt_len %d must be in [2, max_len = %d): BOS plus at least one token, and room for one "
-                      "generated token", prompt_len, max_len);
-        return -1;
-    }
-    if ((size_t)(prompt_len - 1) > m->ws_rows) {
-        cap_set_error("cap_generate_prompted: prompt_len %d exceeds the limit of %zu tokens this handle's workspace (%zu rows) takes: "
-                      "create it with CapConfig.max_prompt >= %d", prompt_len, m->ws_rows + 1, m->ws_rows, prompt_len);
-        return -1;
-    }
-    if ((out_logprobs != nullptr) != (out_scored != nullptr)) {
-        cap_set_error("cap_generate_prompted: out_logprobs and out_scored come together (both or neither)");
-        return -1;
-    }
-    if (out_vocab) {
-        if (!out_logprobs) { cap_set_error("cap_generate_prompted: out_vocab needs out_logprobs and out_scored"); return -1; }
-        if (acc_ld < m->c.vocab || acc_ld % 4 != 0 || ((uintptr_t)out_vocab & 15) != 0) {
-            cap_set_error("cap_generate_prompted: out_vocab needs acc_ld >= vocab (%d), acc_ld %% 4 == 0 (got %d) and a 16-byte aligned pointer",
-                          m->c.vocab, acc_ld);
-            return -1;
-        }
-    }
-    return run_generate(m, pixels, pixel_fmt, B, 1, max_len, 1.0f, out_ids, out_len, nullptr, out_step_logits, (hipStream_t)stream, false,
-                        out_logprobs, out_scored, out_vocab, acc_ld, prompt_ids, prompt_rows, prompt_len);
-}
-
-int cap_last_prefill_passes(CapHandle h) { return h ? ((Captioner*)h)->last_prefill_passes : -1; }
 
 int cap_generate(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int max_len, float length_penalty,
                  int32_t* out_ids, int32_t* out_len, float* out_scores, float* out_step_logits, void* stream) {
@@ -2369,28 +2359,30 @@ int cap_generate(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_
                                out_step_logits, nullptr, nullptr, stream);
 }
 
+int cap_generate_vocab(CapHandle h, const void* pixels, int pixel_fmt, int B, int max_len, int32_t* out_ids, int32_t* out_len,
+                       float* out_step_logits, float* out_logprobs, int32_t* out_scored, float* out_vocab, int acc_ld, void* stream) {
+    CapGenerateArgs a = request_of(pixels, pixel_fmt, B, 1, max_len, 1.0f, out_ids, out_len);
+    a.out_step_logits = out_step_logits; a.out_logprobs = out_logprobs; a.out_scored = out_scored; a.out_vocab = out_vocab; a.acc_ld = acc_ld;
+    return generate(h, a, stream, "cap_generate_vocab",
+                    out_logprobs && out_scored && out_vocab ? nullptr : "out_logprobs, out_scored and out_vocab are all required");
+}
+
+int cap_generate_prompted(CapHandle h, const void* pixels, int pixel_fmt, int B, int max_len, const int32_t* prompt_ids, int prompt_rows,
+                          int prompt_len, int32_t* out_ids, int32_t* out_len, float* out_step_logits, float* out_logprobs,
+                          int32_t* out_scored, float* out_vocab, int acc_ld, void* stream) {
+    CapGenerateArgs a = request_of(pixels, pixel_fmt, B, 1, max_len, 1.0f, out_ids, out_len);
+    a.out_step_logits = out_step_logits; a.out_logprobs = out_logprobs; a.out_scored = out_scored; a.out_vocab = out_vocab; a.acc_ld = acc_ld;
+    a.prompt_ids = prompt_ids; a.prompt_rows = prompt_rows; a.prompt_len = prompt_len;
+    return generate(h, a, stream, "cap_generate_prompted", prompt_ids ? nullptr : "prompt_ids is required");
+}
+
+int cap_last_prefill_passes(CapHandle h) { return h ? ((Captioner*)h)->last_prefill_passes : -1; }
+
 int cap_generate_groups(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int num_beam_groups, int max_len,
                         float length_penalty, int32_t* out_ids, int32_t* out_len, float* out_scores, void* stream) {
-    Captioner* m = (Captioner*)h;
-    TRY(check_call(m, B, num_beams, max_len, pixel_fmt));
-    if (!pixels || !out_ids) { cap_set_error("cap_generate_groups: null buffer"); return -1; }
-    if (m->c.arch != CAP_ARCH_COCA) {
-        cap_set_error("cap_generate_groups: beam groups are the CoCa loop's (coca_model.py:335-482); HF's group beam search for the "
-                      "other architectures needs a diversity penalty, which this library does not implement");
-        return -1;
-    }
-    if (num_beam_groups < 1 || num_beam_groups > num_beams || num_beams % num_beam_groups != 0) {
-        cap_set_error("cap_generate_groups: num_beams (%d) must be a multiple of num_beam_groups (%d) (BeamSearchScorer's own check)",
-                      num_beams, num_beam_groups);
-        return -1;
-    }
-    // The reference's loop runs its groups one after the other on the SAME logits with only MinLength / RepetitionPenalty(1.0)
-    // as processors (coca_model.py:236-241: no HammingDiversity processor), every group starts from the same scores (:380-384),
-    // and finalize picks the best hypothesis over all groups of an image: the groups are identical searches of
-    // num_beams / num_beam_groups beams, and the result is that of ONE of them.  That one is what runs here.
-    const int sub = num_beams / num_beam_groups;
-    return run_generate(m, pixels, pixel_fmt, B, sub, max_len, length_penalty, out_ids, out_len, out_scores, nullptr,
-                        (hipStream_t)stream, /*force_beam=*/true);
+    CapGenerateArgs a = request_of(pixels, pixel_fmt, B, num_beams, max_len, length_penalty, out_ids, out_len);
+    a.num_beam_groups = num_beam_groups; a.out_scores = out_scores;
+    return generate(h, a, stream, "cap_generate_groups", num_beam_groups >= 1 ? nullptr : "num_beam_groups must be at least 1");
 }
 
 long long cap_g8_saturations(int reset) {

@@ -410,15 +410,13 @@ class CaptionerEngine:
         ids = torch.empty((B, L), dtype=torch.int32, device=self.device)
         lens = torch.empty((B,), dtype=torch.int32, device=self.device)
         scores = torch.zeros((B,), dtype=torch.float32, device=self.device)
-        logits = None
+        steps = L if getattr(self, "is_blip2", False) else L - 1
+        logits = lps = scored = vmax = prompt_d = None
         if output_logits:
-            steps = L if getattr(self, "is_blip2", False) else L - 1
-            if prompt is not None:
-                steps = L - int(prompt.shape[1])
             # zeros, not empty: with early exit the steps after the last executed one are never written (callers see 0, not
             # stale memory); `last_decode_steps` tells how many steps ran
-            logits = torch.zeros((steps, B * num_beams, self.arch.vocab), dtype=torch.float32, device=self.device)
-        lps = scored = vmax = None
+            logits = torch.zeros((steps if prompt is None else L - int(prompt.shape[1]), B * num_beams, self.arch.vocab),
+                                 dtype=torch.float32, device=self.device)
         if output_vocab_maxprob:
             output_logprobs = True
             acc_ld = (self.arch.vocab + 3) // 4 * 4
@@ -427,51 +425,27 @@ class CaptionerEngine:
             if num_beam_groups is not None:
                 raise N.CaptionerHipError("output_logprobs is the greedy loop's (num_beams = 1): the group beam search "
                                           f"(num_beams = {num_beams}, num_beam_groups = {num_beam_groups}) returns sequences_scores")
-            steps = L if getattr(self, "is_blip2", False) else L - 1
             # the library zero-fills both on this stream (entries after a caption's end and steps an early exit skipped stay 0)
             lps = torch.empty((B, steps), dtype=torch.float32, device=self.device)
             scored = torch.empty((B,), dtype=torch.int32, device=self.device)
-        if num_beam_groups is not None:
-            if output_logits:
-                raise ValueError("per-step logits are not recorded by the group beam search")
-            with torch.cuda.device(self.device):
-                N.check(self.lib.cap_generate_groups(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, num_beams, int(num_beam_groups), L,
-                                                     C.c_float(length_penalty), C.c_void_p(ids.data_ptr()), C.c_void_p(lens.data_ptr()),
-                                                     C.c_void_p(scores.data_ptr()), C.c_void_p(_stream_ptr(self.device))), "cap_generate_groups")
-            return {"sequences": ids, "lengths": lens, "sequences_scores": scores}
+        if num_beam_groups is not None and output_logits:
+            raise ValueError("per-step logits are not recorded by the group beam search")
+        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731 - an absent buffer is NULL
+        req = N.CapGenerateArgs(pixels=ptr(pixels), pixel_fmt=fmt, B=B, num_beams=num_beams, max_len=L, length_penalty=length_penalty,
+                                out_ids=ptr(ids), out_len=ptr(lens), out_scores=ptr(scores), out_step_logits=ptr(logits),
+                                out_logprobs=ptr(lps), out_scored=ptr(scored), out_vocab=ptr(vmax),
+                                acc_ld=0 if vmax is None else vmax.shape[1])
+        if num_beam_groups is not None:          # 0 is the library's "no groups": a count below 1 goes in as one it refuses
+            req.num_beam_groups = max(int(num_beam_groups), -1) or -1
         with torch.cuda.device(self.device):
             if prompt is not None:
                 prompt_d = prompt.to(self.device, non_blocking=False)
-                N.check(self.lib.cap_generate_prompted(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, L, C.c_void_p(prompt_d.data_ptr()),
-                                                       int(prompt.shape[0]), int(prompt.shape[1]), C.c_void_p(ids.data_ptr()),
-                                                       C.c_void_p(lens.data_ptr()),
-                                                       C.c_void_p(logits.data_ptr() if logits is not None else 0),
-                                                       C.c_void_p(lps.data_ptr() if lps is not None else 0),
-                                                       C.c_void_p(scored.data_ptr() if scored is not None else 0),
-                                                       C.c_void_p(vmax.data_ptr() if vmax is not None else 0),
-                                                       vmax.shape[1] if vmax is not None else 0,
-                                                       C.c_void_p(_stream_ptr(self.device))), "cap_generate_prompted")
+                req.prompt_ids, req.prompt_rows, req.prompt_len = prompt_d.data_ptr(), int(prompt.shape[0]), int(prompt.shape[1])
+            N.check(self.lib.cap_generate_request(self._h, C.byref(req), C.c_void_p(_stream_ptr(self.device))), "cap_generate_request")
+            if prompt_d is not None:
                 prompt_d.record_stream(torch.cuda.current_stream(self.device))
-            elif vmax is not None:
-                N.check(self.lib.cap_generate_vocab(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, L, C.c_void_p(ids.data_ptr()),
-                                                    C.c_void_p(lens.data_ptr()),
-                                                    C.c_void_p(logits.data_ptr() if logits is not None else 0),
-                                                    C.c_void_p(lps.data_ptr()), C.c_void_p(scored.data_ptr()),
-                                                    C.c_void_p(vmax.data_ptr()), vmax.shape[1],
-                                                    C.c_void_p(_stream_ptr(self.device))), "cap_generate_vocab")
-            elif lps is not None:
-                N.check(self.lib.cap_generate_scored(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, num_beams, L,
-                                                     C.c_float(length_penalty), C.c_void_p(ids.data_ptr()),
-                                                     C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
-                                                     C.c_void_p(logits.data_ptr() if logits is not None else 0),
-                                                     C.c_void_p(lps.data_ptr()), C.c_void_p(scored.data_ptr()),
-                                                     C.c_void_p(_stream_ptr(self.device))), "cap_generate_scored")
-            else:
-                N.check(self.lib.cap_generate(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, num_beams, L,
-                                              C.c_float(length_penalty), C.c_void_p(ids.data_ptr()),
-                                              C.c_void_p(lens.data_ptr()), C.c_void_p(scores.data_ptr()),
-                                              C.c_void_p(logits.data_ptr() if logits is not None else 0),
-                                              C.c_void_p(_stream_ptr(self.device))), "cap_generate")
+        if num_beam_groups is not None:
+            return {"sequences": ids, "lengths": lens, "sequences_scores": scores}
         out = {"sequences": ids, "lengths": lens}
         if lps is not None:
             out["token_logprobs"], out["scored_steps"] = lps, scored

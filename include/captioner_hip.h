@@ -11,8 +11,8 @@
  *                       utils/predictor_utils.py:182-185 (load_state_dict)
  *   image tower         coca_model.py:152-155 `_encode_image`;                       cap_encode
  *                       HF modeling_blip.py:901-906 `vision_model(pixel_values)`
- *   generate            blip2.py:26 `model.generate(..., output_logits=True)`;       cap_generate
- *                       coca.py:29 `model.generate(x, generation_type=...)`;
+ *   generate            blip2.py:26 `model.generate(..., output_logits=True)`;       cap_generate_request (CapGenerateArgs);
+ *                       coca.py:29 `model.generate(x, generation_type=...)`;         cap_generate and its siblings fill one
  *                       coca_model.py:205-333 (greedy/top-k loop), :335-482 (beam);
  *                       blip2.py:26 BLIP-2 OPT (CAP_ARCH_BLIP2): out_ids = the max_len NEW tokens (HF's sequences
  *                       minus the 32 image placeholders and BOS), logits as HF's `output_logits`
@@ -166,7 +166,7 @@ int cap_last_decode_steps(CapHandle h);
  * (csrc/decode_small.hip) instead of the batch path's 11.  Both paths form the same sums in the same order: tokens, logits and
  * scores have the same bits (tests/test_small_decode_gpu.py).
  *   path 0 (default): by row count;  1: always the batch kernels;  2: always the small-batch kernels - cap_generate then fails for
- *   calls they do not take (more than 16 rows, more than 32 positions [checked at entry], CAP_F32, other architectures). */
+ *   calls they do not take (more than 16 rows, more than 32 positions, CAP_F32, other architectures), before anything is launched. */
 int cap_set_decode_path(CapHandle h, int path);
 /* 1 = batch kernels, 2 = small-batch kernels: what the last decode step of the last cap_generate ran on (0 before any). */
 int cap_last_decode_path(CapHandle h);
@@ -212,80 +212,84 @@ int cap_crop_resize_u8_frames(const uint8_t* packed, const int64_t* frames, int 
 /* Image tower.  pixels: B frames in `pixel_fmt`; out_embeds: fp32 [B, tokens, v_hidden] (device). */
 int cap_encode(CapHandle h, const void* pixels, int pixel_fmt, int B, float* out_embeds, void* stream);
 
-/* Encoder + autoregressive decode.
- *   num_beams == 1: greedy (HF `_sample` with do_sample=False); num_beams > 1: HF v5 beam search.
- *   out_ids     int32 [B, max_len]   token ids incl. BOS; rows are padded after their end
- *   out_len     int32 [B]            tokens in each row incl. BOS and EOS (may be NULL)
- *   out_scores  fp32  [B]            beam `sequences_scores`; untouched for greedy (may be NULL)
- *   out_step_logits fp32 [max_len-1, B*num_beams, vocab]  raw per-step logits (may be NULL).  Greedy: a caption's rows
- *               are meaningful up to and including the step that produced its EOS; later steps of that row are
- *               unspecified (the attention kernels skip ended captions; HF feeds them pad and ignores the result)
- * max_len <= cfg.max_len, B <= cfg.max_batch, num_beams <= cfg.max_beams. */
+/* Encoder + autoregressive decode: ONE request, everything a generate call can ask for.  Zero / NULL = absent.  Every rule below is
+ * checked by cap_generate_request before anything is launched, in this order: handle and capacity (B <= max_batch, num_beams <=
+ * max_beams, max_len <= cfg.max_len), buffers, what the handle's architecture takes, shapes.  A refused request leaves the stream,
+ * the output buffers and the handle's cap_last_* values untouched.  Nothing is allocated or synchronised (cap_set_early_exit aside). */
+typedef struct CapGenerateArgs {
+    const void* pixels;        /* B frames in pixel_fmt (device); required */
+    int32_t pixel_fmt;         /* CAP_PIX_F32_NCHW | CAP_PIX_U8_NHWC */
+    int32_t B;
+    int32_t num_beams;         /* 1: greedy (HF `_sample` with do_sample=False; CoCa: the reference's top-k(1) loop, coca.py:29); > 1: HF v5 beam
+                                  search (CoCa: its `_generate_beamsearch`, coca_model.py:335-482).  CAP_ARCH_BLIP2: 1 only */
+    int32_t num_beam_groups;   /* 0: not a group search.  >= 1 (CAP_ARCH_COCA only): CoCa's `_generate_beamsearch` with beam GROUPS (`generate()`
+                                  defaults num_beams = 6, num_beam_groups = 3, coca_model.py:218-219): num_beams % num_beam_groups == 0, each group
+                                  a beam search of num_beams / num_beam_groups beams, the best hypothesis over an image's groups returned.  The
+                                  reference attaches no diversity processor (:236-241), so its groups are identical searches and the result equals
+                                  ONE search of num_beams / num_beam_groups beams - which is what runs (a group of one beam runs as a 1-beam BEAM
+                                  search, not as the greedy loop).  No per-step outputs in that mode */
+    int32_t max_len;           /* tokens per caption incl. BOS (and the prompt, as HF's max_length); CAP_ARCH_BLIP2: NEW tokens per caption */
+    float length_penalty;      /* beam search's scorer (pass 1.0 for the references' default); unused by greedy */
+    int32_t* out_ids;          /* int32 [B, max_len]  token ids incl. BOS, rows padded after their end (BLIP-2: the new tokens only); required */
+    int32_t* out_len;          /* int32 [B]  tokens in each row incl. BOS and EOS */
+    float* out_scores;         /* fp32 [B]  beam `sequences_scores`; untouched for greedy */
+    float* out_step_logits;    /* fp32 [steps, B * beams, vocab]  raw per-step logits, steps = max_len - 1 (BLIP-2: max_len; prompted: max_len -
+                                  prompt_len).  Greedy: a caption's rows are meaningful up to and including the step that produced its EOS; later
+                                  steps of that row are unspecified (the attention kernels skip ended captions; HF feeds them pad and ignores
+                                  the result).  With early exit, steps after the last executed one are left untouched */
+    float* out_logprobs;       /* fp32 [B, steps], steps = max_len - 1 (BLIP-2: max_len).  Greedy only, together with out_scored: the per-step term
+                                  of the reference's `compute_perplexity` (captioning_predictor.py:34-47), taken by the token selection kernel
+                                  from the logits row it reads anyway: log max softmax of the step's row as the selection saw it (CoCa: EOS at
+                                  -inf while the caption is shorter than min_len) for every step at which the caption was open; 0 after its end,
+                                  for steps an early exit never ran, and in the tail of a prompted row.  It is the log of the MAXIMAL probability,
+                                  not of the emitted token (they differ on CoCa's forced-EOS last step), as the reference defines it */
+    int32_t* out_scored;       /* int32 [B]  steps at which the caption was open = valid entries of its out_logprobs row;
+                                  perplexity = exp(-sum_{j < scored} logprobs[j] / scored) */
+    float* out_vocab;          /* fp32 [B, acc_ld]  needs the log-prob pair: out_vocab[b][i] = max over the steps at which caption b was open of
+                                  softmax(row as selected from)[i], i < vocab (CoCa: 0 for EOS while it is masked) - the vector the reference's
+                                  probability fusion builds from per-step logits (captioner/test_pseudo_caption_generation.py:28-63); columns
+                                  vocab .. acc_ld - 1 hold the zero fill.  The three greedy outputs are zero-filled by the call on `stream` */
+    int32_t acc_ld;            /* row stride of out_vocab: >= vocab, a multiple of 4, and out_vocab 16-byte aligned (the kernel moves 16 bytes) */
+    const int32_t* prompt_ids; /* int32 [prompt_rows, prompt_len] (device).  CAP_ARCH_BLIP, greedy: the tokens every caption starts with, column 0 =
+                                  BOS (HF `BlipForConditionalGeneration.generate(pixel_values, input_ids=...)`, modeling_blip.py:858-932: the
+                                  text decoder receives input_ids[:, :-1]).  Ids are the caller's to validate (engine.py does, on the host); the
+                                  library clamps them to [0, vocab) before any gather.  out_ids rows START WITH the prompt and out_len includes
+                                  it; the step outputs cover the GENERATED steps only (entry j is the j-th generated token, HF's `logits`
+                                  tuple).  Positions 0 .. prompt_len - 2 of all captions run through the decoder as one prefill pass
+                                  (caption-major rows, no vocabulary GEMM, no token selection; in chunks of captions when the workspace is
+                                  smaller than B x (prompt_len - 1) rows), which leaves the self-attention caches with the BITS the single
+                                  steps would have written; the loop then starts at position prompt_len - 1 with everything an unprompted
+                                  call has (small-batch path, row compaction, early exit).  A caption prompted with its own unprompted prefix
+                                  decodes to the bits of the unprompted call (tests/test_prompt_gpu.py) */
+    int32_t prompt_rows;       /* 1 (one prompt shared by the batch) or B (row b for caption b) */
+    int32_t prompt_len;        /* 2 <= prompt_len < max_len, <= CAP_MAX_PROMPT (32), and prompt_len - 1 <= the handle's workspace rows
+                                  (max(max_batch x max_beams, max_batch x (max_prompt - 1))) - refused with the limit named */
+} CapGenerateArgs;
+int cap_generate_request(CapHandle h, const CapGenerateArgs* args, void* stream);
+
+/* Conveniences over cap_generate_request: each fills a CapGenerateArgs from its arguments, leaves the rest absent, and goes the same
+ * way (messages name the call that was made).
+ *   cap_generate           no greedy outputs, no prompt, no groups
+ *   cap_generate_scored    + out_logprobs / out_scored (both NULL = cap_generate)
+ *   cap_generate_vocab     num_beams = 1, + out_vocab / acc_ld; out_logprobs, out_scored and out_vocab are all required
+ *   cap_generate_prompted  num_beams = 1, + prompt_ids (required) / prompt_rows / prompt_len and the greedy outputs
+ *   cap_generate_groups    + num_beam_groups (>= 1), no per-step outputs */
 int cap_generate(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int max_len,
                  float length_penalty, int32_t* out_ids, int32_t* out_len, float* out_scores,
                  float* out_step_logits, void* stream);
-
-/* cap_generate that also scores the captions of the greedy loop: the per-step term of the reference's `compute_perplexity`
- * (captioning_predictor.py:34-47), taken by the token selection kernel from the logits row it reads anyway - no per-step logits
- * buffer, any batch size, row compaction and the decode path chosen as for cap_generate.
- *   out_logprobs fp32 [B, steps]  log max softmax of the step's logits row as the selection saw it (CoCa: EOS at -inf while the
- *                caption is shorter than min_len), for every step at which the caption was open; 0 after its end and for steps
- *                an early exit never ran.  steps = max_len - 1 (BLIP, CoCa) or max_len (BLIP-2).  It is the log of the MAXIMAL
- *                probability, not of the emitted token (they differ on CoCa's forced-EOS last step), as the reference defines it.
- *   out_scored   int32 [B]        steps at which the caption was open = valid entries of its out_logprobs row
- *                perplexity = exp(-sum_{j < scored} logprobs[j] / scored)
- * Both buffers are zero-filled by the call on `stream`; both NULL = cap_generate.  num_beams must be 1 when they are given
- * (beam search returns out_scores).  Nothing is allocated or synchronised. */
 int cap_generate_scored(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int max_len,
                         float length_penalty, int32_t* out_ids, int32_t* out_len, float* out_scores,
                         float* out_step_logits, float* out_logprobs, int32_t* out_scored, void* stream);
-
-/* The greedy loop of cap_generate_scored that also keeps, per caption, every vocabulary entry's maximal probability over the
- * caption's steps - the vector the reference's probability fusion builds from per-step logits
- * (captioner/test_pseudo_caption_generation.py:28-63: softmax of each step's row, maximum over the steps) - again inside the token
- * selection kernel: no logits buffer, any batch size, early exit, the small-batch path and row compaction as for cap_generate.
- *   out_vocab fp32 [B, acc_ld]  out_vocab[b][i] = max over the steps at which caption b was open of softmax(row as selected from)[i],
- *             i < vocab (CoCa: 0 for EOS while it is masked); columns vocab .. acc_ld - 1 hold the zero fill.  acc_ld >= vocab,
- *             acc_ld % 4 == 0 and a 16-byte aligned pointer (the kernel moves 16 bytes at a time) - refused otherwise.
- *   out_logprobs / out_scored   as cap_generate_scored; required (the steps counted by out_scored are the steps maximised over).
- *   out_step_logits             as cap_generate, or NULL.
- * All three families, num_beams = 1.  The three output buffers are zero-filled by the call on `stream`. */
 int cap_generate_vocab(CapHandle h, const void* pixels, int pixel_fmt, int B, int max_len, int32_t* out_ids, int32_t* out_len,
                        float* out_step_logits, float* out_logprobs, int32_t* out_scored, float* out_vocab, int acc_ld,
                        void* stream);
-
-/* The greedy loop of cap_generate_scored / cap_generate_vocab started from a text PROMPT instead of the lone BOS (HF
- * `BlipForConditionalGeneration.generate(pixel_values, input_ids=...)`, modeling_blip.py:858-932: the text decoder receives
- * input_ids[:, :-1] with column 0 = BOS).  CAP_ARCH_BLIP, num_beams = 1; other architectures are refused by name.
- *   prompt_ids  int32 [prompt_rows, prompt_len] (device)  the tokens every caption starts with, column 0 = BOS; prompt_rows = 1 (one
- *               prompt shared by the batch) or B (row b for caption b).  Ids are the caller's to validate (engine.py does, on the
- *               host); the library clamps them to [0, vocab) before any gather.
- *   prompt_len  2 <= prompt_len < max_len, <= CAP_MAX_PROMPT (32), and prompt_len - 1 <= the handle's workspace rows
- *               (max(max_batch x max_beams, max_batch x (max_prompt - 1))) - refused at entry, before any launch, with the limit named
- *   max_len     counts the prompt, as HF's max_length does
- *   out_ids     int32 [B, max_len]  rows START WITH the prompt;  out_len [B] includes it
- *   out_step_logits fp32 [max_len - prompt_len, B, vocab], out_logprobs fp32 [B, max_len - 1], out_scored, out_vocab: the GENERATED steps
- *               only - entry j is the j-th generated token (HF's `logits` tuple); the tail of an out_logprobs row stays zero
- * Positions 0 .. prompt_len - 2 of all captions run through the decoder as one prefill pass (caption-major rows, no vocabulary GEMM,
- * no token selection; in chunks of captions when the workspace is smaller than B x (prompt_len - 1) rows), which leaves the
- * self-attention caches with the BITS the single steps would have written; the loop then starts at position prompt_len - 1 with
- * everything cap_generate has (small-batch path, row compaction, early exit).  A caption prompted with its own unprompted prefix
- * decodes to the bits of the unprompted call (tests/test_prompt_gpu.py).  out_logprobs / out_scored / out_vocab / out_step_logits /
- * out_len may be NULL (out_vocab needs the log-prob pair). */
 int cap_generate_prompted(CapHandle h, const void* pixels, int pixel_fmt, int B, int max_len, const int32_t* prompt_ids, int prompt_rows,
                           int prompt_len, int32_t* out_ids, int32_t* out_len, float* out_step_logits, float* out_logprobs,
                           int32_t* out_scored, float* out_vocab, int acc_ld, void* stream);
-/* Prefill passes the last cap_generate_prompted on this handle ran (1 = the whole batch at once; 0 after an unprompted call). */
-int cap_last_prefill_passes(CapHandle h);
-
-/* CoCa's `_generate_beamsearch` with beam GROUPS (reference coca_model.py:335-482; `generate()` defaults num_beams = 6,
- * num_beam_groups = 3, :218-219): num_beams % num_beam_groups == 0, each group a beam search of num_beams / num_beam_groups
- * beams, the best hypothesis over an image's groups returned.  The reference attaches no diversity processor (:236-241), so
- * its groups are identical searches and the result equals ONE search of num_beams / num_beam_groups beams - which is what this
- * entry point runs (a group of one beam runs as a 1-beam BEAM search, not as cap_generate's greedy loop).  Outputs as
- * cap_generate; B <= max_batch, num_beams <= max_beams.  CAP_ARCH_COCA only. */
 int cap_generate_groups(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int num_beam_groups, int max_len,
                         float length_penalty, int32_t* out_ids, int32_t* out_len, float* out_scores, void* stream);
+/* Prefill passes the last prompted generate on this handle ran (1 = the whole batch at once; 0 after an unprompted call). */
+int cap_last_prefill_passes(CapHandle h);
 
 /* Sentence encoder (CAP_ARCH_MINILM handle; weights by HF BertModel names as sentence-transformers stores them):
  * WordPiece ids int32 [B, L] incl. [CLS]/[SEP] (rows padded with any valid id), lens int32 [B] = valid tokens per row

@@ -165,6 +165,7 @@ def test_forcing_the_small_path_beyond_its_row_limit_fails_by_name():
     eng.load_state_dict(sd)
     with pytest.raises(CaptionerHipError, match="small-batch decode path was forced"):
         eng.generate(px.cuda(), num_beams=1, max_length=meta["max_length"])
+    assert eng.last_decode_steps == 0 and eng.last_decode_path == "none"      # refused at entry: nothing was launched on the fresh handle
     eng.set_decode_path("auto")
     eng.generate(px.cuda(), num_beams=1, max_length=meta["max_length"])
     assert eng.last_decode_path == "batch"

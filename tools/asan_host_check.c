@@ -67,6 +67,13 @@ int main(void) {
     EXPECT(cap_encode(NULL, w, 0, 1, w, NULL) != 0);
     EXPECT(cap_generate(NULL, w, 0, 1, 1, 8, 1.0f, NULL, NULL, NULL, NULL, NULL) != 0);
     EXPECT(cap_embed_text(NULL, NULL, NULL, 1, 1, NULL, NULL) != 0);
+    {   /* the request call: a null handle and a null request are both refused by message */
+        CapGenerateArgs args;
+        memset(&args, 0, sizeof(args));
+        args.pixels = w; args.B = 1; args.num_beams = 1; args.max_len = 8;
+        EXPECT(cap_generate_request(NULL, &args, NULL) != 0 && strlen(cap_last_error()) > 0);
+        EXPECT(cap_generate_request(NULL, NULL, NULL) != 0 && strstr(cap_last_error(), "cap_generate_request"));
+    }
     EXPECT(cap_profile_enable(NULL, 1) != 0);
     char buf[8];
     EXPECT(cap_profile_report(NULL, buf, sizeof(buf)) != 0);
