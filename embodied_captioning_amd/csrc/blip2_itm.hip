@@ -2,7 +2,7 @@
 // embeddings, its self-attention over [query rows | text rows] with a text length per pair, and the ITC / ITM heads.  Replaces, per
 // (crop, caption) pair, HF `Blip2ForImageTextRetrieval.forward` as the reference's `--method blip2_itm | blip2_itc` calls the LAVIS
 // model it was ported from (experimenting_env/captioner/pseudocaptioner.py:34-37, :193-308); GEMMs, LayerNorm, the query rows'
-// cross-attention and the ViT-g tower run on the shared kernels (captioner.hip, run_itm_qformer).
+// cross-attention and the ViT-g tower run on the shared kernels (captioner.hip, run_qformer).
 //
 // Every sum here is formed in an order fixed by the row's own width and the pair's own text length - never by the batch or by the
 // padded L - so a pair has the same bits alone, in a batch, at the end of a partial micro-batch and padded to a longer L

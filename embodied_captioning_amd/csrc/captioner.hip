@@ -81,15 +81,6 @@ struct VLayer {
     void *w_qkv, *w_proj, *w_fc1, *w_fc2;
     float *b_qkv, *b_proj, *b_fc1, *b_fc2, *ln1_g, *ln1_b, *ln2_g, *ln2_b;
 };
-struct QLayer {            // BLIP-2 Q-Former layer (queries only): self-attention, optional cross-attention, query FFN; post-LN
-    bool cross = false;
-    void *w_qkv = nullptr, *w_so = nullptr, *w_cq = nullptr, *w_ckv = nullptr, *w_co = nullptr, *w_f1 = nullptr, *w_f2 = nullptr;
-    float *b_qkv = nullptr, *b_so = nullptr, *so_g = nullptr, *so_b = nullptr, *b_cq = nullptr, *b_ckv = nullptr, *b_co = nullptr,
-          *co_g = nullptr, *co_b = nullptr, *b_f1 = nullptr, *b_f2 = nullptr, *f_g = nullptr, *f_b = nullptr;
-    // CAP_ARCH_BLIP2_ITM: the text rows' own FFN (intermediate / output beside intermediate_query / output_query)
-    void *w_t1 = nullptr, *w_t2 = nullptr;
-    float *b_t1 = nullptr, *b_t2 = nullptr, *t_g = nullptr, *t_b = nullptr;
-};
 // int8 weights: up to this many crops per call the prompt pass (crops x 33 rows) runs on the weight-streaming kernels like a decode
 // step; beyond, it is a GEMM proper and goes to the tiled kernels (run_opt).  Within each range a crop's bits do not depend on the
 // batch it is in; across the two the prompt's sums are formed in a different order (fp32-rounding-level differences before the bf16
@@ -101,13 +92,10 @@ struct OLayer {            // OPT decoder layer (pre-LN): fused q|k|v, out_proj,
     float *s_qkv = nullptr, *s_o = nullptr, *s_f1 = nullptr, *s_f2 = nullptr;   // CapConfig.weight_int8: row scales of the int8 weights
     float *b_qkv, *b_o, *b_f1, *b_f2, *ln1_g, *ln1_b, *ln2_g, *ln2_b;
 };
-struct TLayer {            // sentence-encoder (BERT) layer: fused q|k|v, output projection, FFN; post-LN
-    void *w_qkv, *w_so, *w_f1, *w_f2;
-    float *b_qkv, *b_so, *so_g, *so_b, *b_f1, *b_f2, *f_g, *f_b;
-};
 
-// The BLIP and CoCa text decoders as ONE list of sub-layers (run_step / run_step_small walk it; build_blip / build_coca fill it
-// once).  A sub-layer is two projections around its core, followed by a split-K consumer: bias + residual + ONE LayerNorm.
+// A sub-layer is two projections around its core, followed by bias + residual + ONE LayerNorm.  The BLIP and CoCa text decoders
+// are ONE list of sub-layers (run_step / run_step_small walk it; build_blip / build_coca fill it once; the tail is a split-K
+// consumer); a post-LN encoder layer (PostLayer below) is made of the same struct.
 //   DEC_SELF   q|k|v projection [3W, W] -> causal attention over the self cache -> output projection [W, W]
 //   DEC_CROSS  query projection [W, W]  -> attention over the image's K/V        -> output projection [W, W]
 //   DEC_FFN    fc [F, W] (GELU)                                                  -> projection back  [W, F]
@@ -115,13 +103,13 @@ struct TLayer {            // sentence-encoder (BERT) layer: fused q|k|v, output
 // residual row.  CoCa is pre-LN: [SELF, FFN] per unimodal / multimodal self block, [CROSS, FFN] per cross block, the LayerNorm is
 // the NEXT sub-layer's (ln_2 of the block, ln_1 of the next block, ln_final after the last), the residual row is the sum.
 enum { DEC_SELF = 0, DEC_CROSS = 1, DEC_FFN = 2 };
-struct DecSub {
+struct SubLayer {
     int kind = DEC_FFN;
     void *w_in = nullptr, *w_out = nullptr;
     float *b_in = nullptr, *b_out = nullptr;
     float *ln_g = nullptr, *ln_b = nullptr;   // the LayerNorm applied to the sub-layer's result (see above)
-    void* cache = nullptr;                    // DEC_SELF: [k|v][R][H][max_len][64] in the activation type (arena)
-    int slot = -1;                            // DEC_CROSS: layer index inside the cross K/V cache
+    void* cache = nullptr;                    // decoder DEC_SELF: [k|v][R][H][max_len][64] in the activation type (arena)
+    int slot = -1;                            // decoder DEC_CROSS: layer index inside the cross K/V cache
 };
 // Profile tags of the decoder's launches, indexed by sub-layer kind.  Batch kernels: input GEMM, attention, output GEMM; fused
 // small-batch kernels: the sub-layer's first and second launch.
@@ -138,7 +126,7 @@ const DecTags kCocaDecTags = {{"coca_gemm_qkv", "coca_gemm_cq", "coca_gemm_fc"},
                               {"coca_small_qkv", "coca_small_cross", "coca_small_fc"}, {"coca_small_o", "coca_small_o", "coca_small_pr"},
                               nullptr, "coca_small_vocab"};
 struct DecPlan {
-    std::vector<DecSub> subs;
+    std::vector<SubLayer> subs;
     bool pre_ln = false;          // CoCa (SmallLN::x_is_sum; the batch consumer's y_out instead of out_f)
     bool skip_finished = false;   // BLIP greedy: ended captions' rows are left alone.  CoCa computes them: their step logits are observable
     int W = 0;                    // width: t_hidden (BLIP), embed_dim (CoCa)
@@ -153,6 +141,32 @@ struct DecPlan {
     float *b_tr = nullptr, *tr_g = nullptr, *tr_b = nullptr, *b_vocab = nullptr;
     const DecTags* tags = nullptr;
 };
+
+// One layer of a post-LN (BERT-style) encoder - the BLIP-2 Q-Former, the sentence encoder - as sub-layers (reg_post_layers fills
+// them, run_qformer / run_text_encoder walk them): self (q|k|v in), on the Q-Former's cross layers cross (query in; the image's
+// k|v projection [2 W, D] is the layer's w_ckv / b_ckv), ffn, and with CAP_ARCH_BLIP2_ITM ffn_text: the text rows' own FFN.
+struct PostLayer {
+    bool has_cross = false;
+    SubLayer self, cross, ffn, ffn_text;
+    void* w_ckv = nullptr;
+    float* b_ckv = nullptr;
+};
+// The activations of a post-LN encoder over R rows of width W, FFN width F (alloc_post_rows)
+struct PostRows {
+    float *x = nullptr, *y = nullptr;          // fp32 [R, W]: the stream (LayerNorm output = next residual), the pre-LayerNorm sum
+    void *x_t = nullptr, *qkv = nullptr, *ctx = nullptr, *h = nullptr;   // [R, W] operand copy of x, [R, 3 W], [R, W], [R, F] in the compute type
+};
+struct PostDims { int W, F; float eps; };
+// Profile tags of one row set's launches (null: the pass has no such launch; ln null: the LayerNorms are not recorded)
+struct PostTags { const char *qkv, *self_attn, *so, *cq, *ckv, *cross_attn, *co, *f1, *f2, *ln; };
+const PostTags kQformerTags = {"qf_gemm_qkv", "qf_self_attn", "qf_gemm_so", "qf_gemm_cq", "qf_gemm_ckv", "qf_cross_attn", "qf_gemm_co",
+                               "qf_gemm_f1", "qf_gemm_f2", nullptr};
+const PostTags kItmQueryTags = {"itm_gemm_qkv_q", "itm_self_attn", "itm_gemm_so_q", "itm_gemm_cq", "itm_gemm_ckv", "itm_cross_attn",
+                                "itm_gemm_co", "itm_gemm_f1_q", "itm_gemm_f2_q", nullptr};
+const PostTags kItmTextTags = {"itm_gemm_qkv_t", "itm_self_attn", "itm_gemm_so_t", nullptr, nullptr, nullptr, nullptr, "itm_gemm_f1_t",
+                               "itm_gemm_f2_t", nullptr};
+const PostTags kMiniLMTags = {"te_gemm_qkv", "te_attention", "te_gemm_o", nullptr, nullptr, nullptr, nullptr, "te_gemm_f1", "te_gemm_f2",
+                              "te_layernorm"};
 
 // The ViT branch GEMMs (proj, fc2) of the MFMA-staged types add their output to the residual stream X IN PLACE (gemm_pp.hip's
 // residual epilogue: C = acc + bias + C) and the next LayerNorm reads X once.  The older scheme - branch output to `delta`, the
@@ -180,6 +194,8 @@ struct Captioner {
     int dt; size_t esz;          // storage type of activations / K-V caches that kernels other than the GEMMs read
     int gdt;                     // type of every GEMM operand (A and W): == dt, except CAP_F32_SPLIT: dt = fp32, gdt = G8
                                  // (split fp16, common.h) - there every kernel whose output feeds a GEMM writes G8
+    // out_f32 of a GEMM whose output an attention kernel reads (q, k, v): fp32 in the split mode, where only GEMM operands are G8
+    int attn_f32() const { return gdt == CAP_DT_G8 ? 1 : 0; }
     int NT, P, Kpatch, Kpad;
     bool kv16 = false;           // split mode: the cross-attention K/V cache is KV16 (int16 + one scale per head row, common.h) instead of fp32
     size_t kvrow = 0;            // bytes of one 64-wide head row of that cache (KV16: 132, amortised)
@@ -210,7 +226,7 @@ struct Captioner {
     // text weights
     float *word_f32, *tpos, *emb_g, *emb_b, *b_ckv;
     void* w_ckv;
-    std::vector<TLayer> tl;      // (sentence encoder)
+    std::vector<PostLayer> pl;   // post-LN encoder layers: the Q-Former's (BLIP-2, the image-text scorer) or the sentence encoder's
     DecPlan dec;                 // BLIP / CoCa text decoder
     // arena
     void *patches, *emb_t, *cross;
@@ -230,30 +246,30 @@ struct Captioner {
     void *w_pool_kv = nullptr, *w_pool_o = nullptr, *pool_kvbuf = nullptr, *pool_ctx = nullptr, *xhat = nullptr;
     int ldl;
     // ---- BLIP-2 (CAP_ARCH_BLIP2)
-    std::vector<QLayer> ql;
     std::vector<OLayer> ol;
     bool wq8 = false;            // CapConfig.weight_int8: the OPT decoder's Linear weights are row-quantised int8 (gemm_skinny.hip)
     void* w8_scratch = nullptr;  // one weight matrix as row-major bf16 integers: the prompt pass of more than kI8SkinnyPromptCrops crops
     float *q_x0 = nullptr, *b_lproj = nullptr, *o_tok = nullptr, *o_pos = nullptr, *o_lnf_g = nullptr, *o_lnf_b = nullptr;
     void *w_lproj = nullptr, *o_tok_t = nullptr;
-    float *qx = nullptr, *qy = nullptr, *lm_proj = nullptr, *ox = nullptr;      // activations
-    void *qx_t = nullptr, *qqkv = nullptr, *qctx = nullptr, *qh = nullptr, *qkvimg = nullptr, *oh_t = nullptr, *oqkv = nullptr,
-         *octx = nullptr, *off = nullptr;
-    // ---- sentence encoder (CAP_ARCH_MINILM): token-type row 0, activations [max_batch * max_len, .]
-    float *tok_type = nullptr, *te_x = nullptr, *te_y = nullptr;
-    void *te_xt = nullptr, *te_qkv = nullptr, *te_ctx = nullptr, *te_h = nullptr;
+    PostRows qr;                 // the Q-Former's query rows [max_batch * num_query_tokens, .] (the image-text scorer's too)
+    float *lm_proj = nullptr, *ox = nullptr;      // activations
+    void *qkvimg = nullptr, *oh_t = nullptr, *oqkv = nullptr, *octx = nullptr, *off = nullptr;
+    // ---- sentence encoder (CAP_ARCH_MINILM): layers in pl, token-type row 0, activations [max_batch * max_len, .]
+    float* tok_type = nullptr;
+    PostRows te;
     // ---- CLIP scorer (CAP_ARCH_CLIP): image tower on the encoder's (vl, vt), text tower on its own [max_batch * max_len, .]
     // rows; projections fp32 [embed_dim, width] for the pooled head kernel
     std::vector<VLayer> ctl;
     Tower ct;
     float *c_vproj = nullptr, *c_tproj = nullptr, *c_tok = nullptr, *c_lnf_g = nullptr, *c_lnf_b = nullptr, *c_logit = nullptr;
-    // ---- BLIP-2 image-text scorer (CAP_ARCH_BLIP2_ITM): image tower on (vl, vt), Q-Former layers in ql with both FFN sets; the
-    // text rows [max_batch * max_len, .] beside the query rows (qx ..); heads fp32 for the head kernels.  itm_ckv holds the cross
-    // K/V of every cross-attention layer for the itm_B images of the last cap_blip2_itm_encode_images: [layer][B * NT, 2 Q].
+    // ---- BLIP-2 image-text scorer (CAP_ARCH_BLIP2_ITM): image tower on (vl, vt), Q-Former layers in pl with both FFN sets; the
+    // text rows tr [max_batch * max_len, .] beside the query rows qr; heads fp32 for the head kernels.  itm_ckv holds the cross
+    // K/V of every cross-attention layer for the itm_B images of the last cap_blip2_itm_encode_images: [layer][B * NT, 2 Q]
+    // (itm_ckv_slot).
     float *i_word = nullptr, *i_pos = nullptr, *i_ln_g = nullptr, *i_ln_b = nullptr, *i_vproj = nullptr, *i_vproj_b = nullptr,
           *i_tproj = nullptr, *i_tproj_b = nullptr, *i_head = nullptr, *i_head_b = nullptr;
-    float *tx = nullptr, *ty = nullptr;
-    void *tx_t = nullptr, *tqkv = nullptr, *tctx = nullptr, *th = nullptr, *itm_ckv = nullptr;
+    PostRows tr;
+    void* itm_ckv = nullptr;
     int itm_B = 0;
     // profiling
     bool prof = false;
@@ -397,10 +413,54 @@ int reg_tower(Captioner* m, const TowerNames& n, std::vector<VLayer>& layers, in
 }
 
 // a BERT-style output block into a sub-layer: p + "dense." -> the output projection [N, K], p + "LayerNorm." -> its LayerNorm
-int reg_out_ln(Captioner* m, const std::string& p, DecSub& u, int N, int K) {
+int reg_out_ln(Captioner* m, const std::string& p, SubLayer& u, int N, int K) {
     TRY(reg_mat(m, p + "dense.weight", &u.w_out, N, K));
     TRY(reg_f32(m, p + "dense.bias", &u.b_out, N));
     return reg_ln(m, p + "LayerNorm.", &u.ln_g, &u.ln_b, N);
+}
+
+// Checkpoint names of a post-LN encoder's layers.  Layer i: layers + i + "."; below it attn holds query. / key. / value. (and
+// "cross" + attn the cross-attention's), fc the FFN's first Linear and out its output block.
+struct PostNames { const char *layers, *attn, *fc, *out; };
+const PostNames kQformerNames = {"qformer.encoder.layer.", "attention.attention.", "intermediate_query.dense.", "output_query."};
+const PostNames kBertNames = {"encoder.layer.", "attention.self.", "intermediate.dense.", "output."};
+
+int reg_post_ffn(Captioner* m, const std::string& p, const char* fc, const char* out, SubLayer& u, int W, int F) {
+    u.kind = DEC_FFN;
+    TRY(reg_fused(m, p, &fc, 1, &u.w_in, &u.b_in, F, W));
+    return reg_out_ln(m, p + out, u, W, F);
+}
+// `count` post-LN layers of width W, FFN width F.  cross_freq > 0: every cross_freq-th layer cross-attends rows of width D.
+// text_ffn: with the text rows' FFN (BERT's own names: `intermediate` / `output`) beside the one n names.
+int reg_post_layers(Captioner* m, const PostNames& n, int count, int W, int F, int cross_freq, int D, bool text_ffn) {
+    const char* nm[3] = {"query.", "key.", "value."};
+    m->pl.resize(count);
+    for (int i = 0; i < count; ++i) {
+        PostLayer& L = m->pl[i];
+        const std::string p = n.layers + std::to_string(i) + ".";
+        L.self.kind = DEC_SELF; L.cross.kind = DEC_CROSS;
+        TRY(reg_fused(m, p + n.attn, nm, 3, &L.self.w_in, &L.self.b_in, W, W));
+        TRY(reg_out_ln(m, p + "attention.output.", L.self, W, W));
+        L.has_cross = cross_freq > 0 && i % cross_freq == 0;
+        if (L.has_cross) {
+            const std::string cp = p + "cross" + n.attn;
+            TRY(reg_fused(m, cp, nm, 1, &L.cross.w_in, &L.cross.b_in, W, W));
+            TRY(reg_fused(m, cp, nm + 1, 2, &L.w_ckv, &L.b_ckv, W, D));
+            TRY(reg_out_ln(m, p + "crossattention.output.", L.cross, W, W));
+        }
+        TRY(reg_post_ffn(m, p, n.fc, n.out, L.ffn, W, F));
+        if (text_ffn) TRY(reg_post_ffn(m, p, kBertNames.fc, kBertNames.out, L.ffn_text, W, F));
+    }
+    return 0;
+}
+int alloc_post_rows(Captioner* m, PostRows& r, size_t R, size_t W, size_t F) {
+    const size_t e = m->esz;
+    TRY(dev_alloc(m, (void**)&r.x, R * W * 4));
+    TRY(dev_alloc(m, (void**)&r.y, R * W * 4));
+    TRY(dev_alloc(m, &r.x_t, R * W * e));
+    TRY(dev_alloc(m, &r.qkv, R * 3 * W * e));
+    TRY(dev_alloc(m, &r.ctx, R * W * e));
+    return dev_alloc(m, &r.h, R * F * e);
 }
 
 int build_blip(Captioner* m) {
@@ -430,7 +490,7 @@ int build_blip(Captioner* m) {
     P.subs.resize(3 * c.t_layers);
     const char* nm[3] = {"query.", "key.", "value."};
     for (int i = 0; i < c.t_layers; ++i) {
-        DecSub &sa = P.subs[3 * i], &ca = P.subs[3 * i + 1], &ff = P.subs[3 * i + 2];
+        SubLayer &sa = P.subs[3 * i], &ca = P.subs[3 * i + 1], &ff = P.subs[3 * i + 2];
         sa.kind = DEC_SELF; ca.kind = DEC_CROSS; ca.slot = i; ff.kind = DEC_FFN;
         const std::string p = tb + "encoder.layer." + std::to_string(i) + ".";
         TRY(reg_fused(m, p + "attention.self.", nm, 3, &sa.w_in, &sa.b_in, T, T));
@@ -453,7 +513,7 @@ int build_blip(Captioner* m) {
 // One CoCa text block = an attention sub-layer (causal self-attention, or cross-attention over cache slot `slot` >= 0) and an FFN
 // sub-layer.  Pre-LN: the block's ln_1 is the LayerNorm of whatever comes BEFORE it (ln1_g / ln1_b: the previous FFN sub-layer's,
 // the embedding's for the first block), its ln_2 the attention sub-layer's; the FFN sub-layer's is left to the next block.
-int reg_block(Captioner* m, const std::string& p, DecSub& at, DecSub& ff, float** ln1_g, float** ln1_b, int E, int F, int slot) {
+int reg_block(Captioner* m, const std::string& p, SubLayer& at, SubLayer& ff, float** ln1_g, float** ln1_b, int E, int F, int slot) {
     at.kind = slot < 0 ? DEC_SELF : DEC_CROSS; at.slot = slot; ff.kind = DEC_FFN;
     TRY(reg_ln(m, p + ".ln_1.", ln1_g, ln1_b, E));
     if (slot < 0) {
@@ -499,7 +559,7 @@ int build_coca(Captioner* m) {
     int n = 0;
     float **g = &P.emb_g, **b = &P.emb_b;          // where the next block's ln_1 goes
     auto block = [&](const std::string& p, int slot) {
-        DecSub &at = P.subs[n], &ff = P.subs[n + 1];
+        SubLayer &at = P.subs[n], &ff = P.subs[n + 1];
         n += 2;
         const int rc = reg_block(m, p, at, ff, g, b, E, F, slot);
         g = &ff.ln_g; b = &ff.ln_b;
@@ -572,7 +632,7 @@ int build_arena_coca(Captioner* m) {
     TRY(dev_alloc(m, &m->dh, R * c.t_ffn * e));
     m->ldl = (c.vocab + 3) & ~3;
     TRY(dev_alloc(m, (void**)&m->logits, R * (size_t)m->ldl * 4));
-    for (DecSub& u : m->dec.subs)
+    for (SubLayer& u : m->dec.subs)
         if (u.kind == DEC_SELF) TRY(dev_alloc(m, &u.cache, 2 * R * H * Lm * 64 * e));
     TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, (int)Lm)));      // (a 1-beam search exists: beam groups)
     return 0;
@@ -606,7 +666,7 @@ int build_arena(Captioner* m) {
     TRY(dev_alloc(m, &m->dh, Rw * c.t_ffn * e));
     m->ldl = (c.vocab + 3) & ~3;
     TRY(dev_alloc(m, (void**)&m->logits, R * (size_t)m->ldl * 4));
-    for (DecSub& u : m->dec.subs)
+    for (SubLayer& u : m->dec.subs)
         if (u.kind == DEC_SELF) TRY(dev_alloc(m, &u.cache, 2 * R * H * Lm * 64 * e));
     TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, (int)Lm)));
     return 0;
@@ -719,43 +779,8 @@ __global__ void copy_new_tokens_kernel(const int* seq, int seq_ld, int P, const 
 // image-text scorer; `use_qformer_text_input` checkpoints).
 int reg_qformer(Captioner* m, bool text_ffn) {
     const CapConfig& c = m->c;
-    const int D = c.v_hidden, Q = c.q_hidden, F = c.q_ffn, nq = c.num_query_tokens;
-    TRY(reg_f32(m, "derived.qformer_x0", &m->q_x0, (int64_t)nq * Q));
-    m->ql.resize(c.q_layers);
-    const char* nm[3] = {"query.", "key.", "value."};
-    for (int i = 0; i < c.q_layers; ++i) {
-        QLayer& L = m->ql[i];
-        L.cross = i % c.q_cross_freq == 0;
-        const std::string p = "qformer.encoder.layer." + std::to_string(i) + ".";
-        TRY(reg_fused(m, p + "attention.attention.", nm, 3, &L.w_qkv, &L.b_qkv, Q, Q));
-        TRY(reg_mat(m, p + "attention.output.dense.weight", &L.w_so, Q, Q));
-        TRY(reg_f32(m, p + "attention.output.dense.bias", &L.b_so, Q));
-        TRY(reg_f32(m, p + "attention.output.LayerNorm.weight", &L.so_g, Q));
-        TRY(reg_f32(m, p + "attention.output.LayerNorm.bias", &L.so_b, Q));
-        if (L.cross) {
-            TRY(reg_mat(m, p + "crossattention.attention.query.weight", &L.w_cq, Q, Q));
-            TRY(reg_f32(m, p + "crossattention.attention.query.bias", &L.b_cq, Q));
-            TRY(reg_fused(m, p + "crossattention.attention.", nm + 1, 2, &L.w_ckv, &L.b_ckv, Q, D));
-            TRY(reg_mat(m, p + "crossattention.output.dense.weight", &L.w_co, Q, Q));
-            TRY(reg_f32(m, p + "crossattention.output.dense.bias", &L.b_co, Q));
-            TRY(reg_f32(m, p + "crossattention.output.LayerNorm.weight", &L.co_g, Q));
-            TRY(reg_f32(m, p + "crossattention.output.LayerNorm.bias", &L.co_b, Q));
-        }
-        TRY(reg_mat(m, p + "intermediate_query.dense.weight", &L.w_f1, F, Q));
-        TRY(reg_f32(m, p + "intermediate_query.dense.bias", &L.b_f1, F));
-        TRY(reg_mat(m, p + "output_query.dense.weight", &L.w_f2, Q, F));
-        TRY(reg_f32(m, p + "output_query.dense.bias", &L.b_f2, Q));
-        TRY(reg_f32(m, p + "output_query.LayerNorm.weight", &L.f_g, Q));
-        TRY(reg_f32(m, p + "output_query.LayerNorm.bias", &L.f_b, Q));
-        if (!text_ffn) continue;
-        TRY(reg_mat(m, p + "intermediate.dense.weight", &L.w_t1, F, Q));
-        TRY(reg_f32(m, p + "intermediate.dense.bias", &L.b_t1, F));
-        TRY(reg_mat(m, p + "output.dense.weight", &L.w_t2, Q, F));
-        TRY(reg_f32(m, p + "output.dense.bias", &L.b_t2, Q));
-        TRY(reg_f32(m, p + "output.LayerNorm.weight", &L.t_g, Q));
-        TRY(reg_f32(m, p + "output.LayerNorm.bias", &L.t_b, Q));
-    }
-    return 0;
+    TRY(reg_f32(m, "derived.qformer_x0", &m->q_x0, (int64_t)c.num_query_tokens * c.q_hidden));
+    return reg_post_layers(m, kQformerNames, c.q_layers, c.q_hidden, c.q_ffn, c.q_cross_freq, c.v_hidden, text_ffn);
 }
 
 // HF `Blip2ForConditionalGeneration` state-dict names (transformers 5.x).
@@ -818,12 +843,7 @@ int build_blip2(Captioner* m) {
     TRY(alloc_image_tower(m));
     TRY(dev_alloc(m, (void**)&m->emb_f, M * D * 4));
     TRY(dev_alloc(m, &m->emb_t, M * D * e));
-    TRY(dev_alloc(m, (void**)&m->qx, Bm * nq * Q * 4));
-    TRY(dev_alloc(m, (void**)&m->qy, Bm * nq * Q * 4));
-    TRY(dev_alloc(m, &m->qx_t, Bm * nq * Q * e));
-    TRY(dev_alloc(m, &m->qqkv, Bm * nq * 3 * Q * e));
-    TRY(dev_alloc(m, &m->qctx, Bm * nq * Q * e));
-    TRY(dev_alloc(m, &m->qh, Bm * nq * F * e));
+    TRY(alloc_post_rows(m, m->qr, Bm * nq, Q, F));
     TRY(dev_alloc(m, &m->qkvimg, M * 2 * Q * e));
     TRY(dev_alloc(m, (void**)&m->lm_proj, Bm * nq * T * 4));
     TRY(dev_alloc(m, (void**)&m->ox, Bm * P * T * 4));
@@ -851,44 +871,84 @@ int build_blip2(Captioner* m) {
     return 0;
 }
 
-// One post-LN sub-block over R rows: y = A W^T + b + x; x, x_t = LayerNorm(y)
-int qf_out_ln(Captioner* m, hipStream_t s, const char* tag, const void* A, int K, const void* W, const float* b, const float* g,
-              const float* be, float* x, float* y, void* x_t, int R) {
-    const int Q = m->c.q_hidden;
-    TRY(gemm(m, s, tag, A, K, W, K, y, Q, b, x, R, Q, K, 0, 1));
-    return launch_layernorm(m->gdt, y, Q, g, be, m->c.q_eps, x_t, x, R, Q, s);
+// ---------------------------------------------------------------------------------------------- post-LN encoders
+// The pieces of a post-LN layer over the R rows of one row set r.  Every launch takes m->gdt as its type selector; the sentence
+// encoder's kernels are m->dt kernels, the same thing there: cap_create refuses CAP_F32_SPLIT for CAP_ARCH_MINILM.
+int post_qkv(Captioner* m, hipStream_t s, const PostTags& tg, const SubLayer& u, const PostRows& r, int R, const PostDims& d) {
+    return gemm(m, s, tg.qkv, r.x_t, d.W, u.w_in, d.W, r.qkv, 3 * d.W, u.b_in, nullptr, R, 3 * d.W, d.W, 0, m->attn_f32());
+}
+// the tail of a sub-layer: y = A W_out^T + b_out + x; x, x_t = LayerNorm(y)
+int post_out_ln(Captioner* m, hipStream_t s, const char* tag, const char* ln_tag, const void* A, int K, const SubLayer& u,
+                const PostRows& r, int R, const PostDims& d) {
+    TRY(gemm(m, s, tag, A, K, u.w_out, K, r.y, d.W, u.b_out, r.x, R, d.W, K, 0, 1));
+    if (!ln_tag) return launch_layernorm(m->gdt, r.y, d.W, u.ln_g, u.ln_b, d.eps, r.x_t, r.x, R, d.W, s);
+    ProfScope ps(m, s, ln_tag, 0, (double)R * d.W * (8 + m->esz));
+    return launch_layernorm(m->gdt, r.y, d.W, u.ln_g, u.ln_b, d.eps, r.x_t, r.x, R, d.W, s);
+}
+int post_ffn(Captioner* m, hipStream_t s, const PostTags& tg, const SubLayer& u, const PostRows& r, int R, const PostDims& d) {
+    TRY(gemm(m, s, tg.f1, r.x_t, d.W, u.w_in, d.W, r.h, d.F, u.b_in, nullptr, R, d.F, d.W, 1, 0));
+    return post_out_ln(m, s, tg.f2, tg.ln, r.h, d.F, u, r, R, d);
 }
 
-// Q-Former over the image tokens (emb_t [B * NT, D]) -> qx_t [B * nq, Q]
-int run_qformer(Captioner* m, int B, hipStream_t s) {
+// the image-text scorer's resident cross K/V of the slot-th cross layer: [max_batch * NT, 2 Q]
+char* itm_ckv_slot(const Captioner* m, size_t slot) {
+    return (char*)m->itm_ckv + slot * (size_t)m->c.max_batch * m->NT * 2 * m->c.q_hidden * m->esz;
+}
+
+// What differs between the Q-Former's two uses: the tags of the query rows' and the text rows' launches, the self-attention
+// (queries alone on the generic kernel, or [queries | the pair's text] with the text's key count), and where the image's cross
+// K/V come from (projected in the loop into qkvimg, or resident in itm_ckv since cap_blip2_itm_encode_images).
+struct QformerPass { const PostTags *qt, *tt; bool pair_attn, resident_kv; };
+const QformerPass kCaptionPass = {&kQformerTags, nullptr, false, false};
+const QformerPass kScorerPass = {&kItmQueryTags, &kItmTextTags, true, true};
+
+// The Q-Former over B images / pairs with nq query rows (0: none - the ITC text pass) and L text rows (0: none - captioning, the
+// ITC image pass) each: self-attention, cross-attention of the query rows to the image's K/V (emb_t [B * NT, D] projected, or
+// cached) on the cross layers, the query rows through intermediate_query / output_query and the text rows through intermediate /
+// output.  The two kinds of rows live in their own row sets (qr, tr), so every GEMM runs over contiguous rows.  Leaves the last
+// hidden states in qr.x / qr.x_t [B * nq, Q] and tr.x [B * L, Q].
+int run_qformer(Captioner* m, const QformerPass& ps, int B, int nq, int L, const int* ids, const int* lens, hipStream_t s) {
     const CapConfig& c = m->c;
-    const int D = c.v_hidden, Q = c.q_hidden, F = c.q_ffn, H = c.q_heads, nq = c.num_query_tokens, NT = m->NT, R = B * nq, hd = Q / H;
+    const int D = c.v_hidden, Q = c.q_hidden, H = c.q_heads, NT = m->NT, Rq = B * nq, Rt = B * L, hd = Q / H;
     const size_t e = m->esz;
-    const int af = m->gdt == CAP_DT_G8 ? 1 : 0;     // split mode: what the attention kernels read (q, k, v) is fp32, only GEMM operands are G8
-    TRY(launch_rows_broadcast(m->gdt, m->q_x0, m->qx, m->qx_t, B, nq, Q, s));
-    for (int i = 0; i < c.q_layers; ++i) {
-        const QLayer& L = m->ql[i];
-        TRY(gemm(m, s, "qf_gemm_qkv", m->qx_t, Q, L.w_qkv, Q, m->qqkv, 3 * Q, L.b_qkv, nullptr, R, 3 * Q, Q, 0, af));
+    const PostDims d = {Q, c.q_ffn, c.q_eps};
+    const PostRows &q = m->qr, &t = m->tr;
+    if (nq) TRY(launch_rows_broadcast(m->gdt, m->q_x0, q.x, q.x_t, B, nq, Q, s));
+    if (L) {
+        ProfScope p(m, s, "itm_embed_text", 0, (double)Rt * Q * (8 + 4 + e));
+        TRY(launch_itm_embed_text(m->gdt, ids, L, m->i_word, m->i_pos, m->i_ln_g, m->i_ln_b, c.q_eps, t.x, t.x_t, Rt, Q, c.vocab, s));
+    }
+    size_t slot = 0;
+    for (const PostLayer& Ly : m->pl) {
+        if (nq) TRY(post_qkv(m, s, *ps.qt, Ly.self, q, Rq, d));
+        if (L) TRY(post_qkv(m, s, *ps.tt, Ly.self, t, Rt, d));
         {
-            ProfScope ps(m, s, "qf_self_attn", 4.0 * B * H * (double)nq * nq * hd, (double)R * 4 * Q * e);
-            const char* base = (const char*)m->qqkv;
-            TRY(launch_generic_attention(m->dt, base, 3 * Q, (long)nq * 3 * Q, base + Q * e, 3 * Q, (long)nq * 3 * Q, base + 2 * Q * e, 3 * Q,
-                                         (long)nq * 3 * Q, m->qctx, Q, (long)nq * Q, B, nq, nq, H, hd, -1, s, m->gdt));
+            ProfScope p(m, s, ps.qt->self_attn, 4.0 * B * H * (double)(nq + L) * (nq + L) * hd, (double)(Rq + Rt) * 4 * Q * e);
+            const char* base = (const char*)q.qkv;
+            if (ps.pair_attn)
+                TRY(launch_itm_self_attention(m->dt, q.qkv, t.qkv, lens, q.ctx, t.ctx, B, nq, L, H, hd, s, m->gdt));
+            else
+                TRY(launch_generic_attention(m->dt, base, 3 * Q, (long)nq * 3 * Q, base + Q * e, 3 * Q, (long)nq * 3 * Q, base + 2 * Q * e,
+                                             3 * Q, (long)nq * 3 * Q, q.ctx, Q, (long)nq * Q, B, nq, nq, H, hd, -1, s, m->gdt));
         }
-        TRY(qf_out_ln(m, s, "qf_gemm_so", m->qctx, Q, L.w_so, L.b_so, L.so_g, L.so_b, m->qx, m->qy, m->qx_t, R));
-        if (L.cross) {
-            TRY(gemm(m, s, "qf_gemm_cq", m->qx_t, Q, L.w_cq, Q, m->qqkv, Q, L.b_cq, nullptr, R, Q, Q, 0, af));
-            TRY(gemm(m, s, "qf_gemm_ckv", m->emb_t, D, L.w_ckv, D, m->qkvimg, 2 * Q, L.b_ckv, nullptr, B * NT, 2 * Q, D, 0, af));
-            {
-                ProfScope ps(m, s, "qf_cross_attn", 4.0 * B * H * (double)nq * NT * hd, (double)B * NT * 2 * Q * e);
-                const char* kv = (const char*)m->qkvimg;
-                TRY(launch_generic_attention(m->dt, m->qqkv, Q, (long)nq * Q, kv, 2 * Q, (long)NT * 2 * Q, kv + Q * e, 2 * Q, (long)NT * 2 * Q,
-                                             m->qctx, Q, (long)nq * Q, B, nq, NT, H, hd, -1, s, m->gdt));
+        if (nq) TRY(post_out_ln(m, s, ps.qt->so, nullptr, q.ctx, Q, Ly.self, q, Rq, d));
+        if (L) TRY(post_out_ln(m, s, ps.tt->so, nullptr, t.ctx, Q, Ly.self, t, Rt, d));
+        if (Ly.has_cross) {
+            const char* kv = ps.resident_kv ? itm_ckv_slot(m, slot++) : (const char*)m->qkvimg;
+            if (nq) {
+                TRY(gemm(m, s, ps.qt->cq, q.x_t, Q, Ly.cross.w_in, Q, q.qkv, Q, Ly.cross.b_in, nullptr, Rq, Q, Q, 0, m->attn_f32()));
+                if (!ps.resident_kv)
+                    TRY(gemm(m, s, ps.qt->ckv, m->emb_t, D, Ly.w_ckv, D, m->qkvimg, 2 * Q, Ly.b_ckv, nullptr, B * NT, 2 * Q, D, 0, m->attn_f32()));
+                {
+                    ProfScope p(m, s, ps.qt->cross_attn, 4.0 * B * H * (double)nq * NT * hd, (double)B * NT * 2 * Q * e);
+                    TRY(launch_generic_attention(m->dt, q.qkv, Q, (long)nq * Q, kv, 2 * Q, (long)NT * 2 * Q, kv + Q * e, 2 * Q, (long)NT * 2 * Q,
+                                                 q.ctx, Q, (long)nq * Q, B, nq, NT, H, hd, -1, s, m->gdt));
+                }
+                TRY(post_out_ln(m, s, ps.qt->co, nullptr, q.ctx, Q, Ly.cross, q, Rq, d));
             }
-            TRY(qf_out_ln(m, s, "qf_gemm_co", m->qctx, Q, L.w_co, L.b_co, L.co_g, L.co_b, m->qx, m->qy, m->qx_t, R));
         }
-        TRY(gemm(m, s, "qf_gemm_f1", m->qx_t, Q, L.w_f1, Q, m->qh, F, L.b_f1, nullptr, R, F, Q, 1, 0));
-        TRY(qf_out_ln(m, s, "qf_gemm_f2", m->qh, F, L.w_f2, L.b_f2, L.f_g, L.f_b, m->qx, m->qy, m->qx_t, R));
+        if (nq) TRY(post_ffn(m, s, *ps.qt, Ly.ffn, q, Rq, d));
+        if (L) TRY(post_ffn(m, s, *ps.tt, Ly.ffn_text, t, Rt, d));
     }
     return 0;
 }
@@ -912,25 +972,15 @@ int build_blip2_itm(Captioner* m) {
     TRY(reg_f32(m, "itm_head.weight", &m->i_head, (int64_t)2 * Q));
     TRY(reg_f32(m, "itm_head.bias", &m->i_head_b, 2));
     // arena: image rows [max_batch * tokens, .], query rows [max_batch * nq, .], text rows [max_batch * max_len, .]
-    const size_t Bm = c.max_batch, M = Bm * m->NT, Rq = Bm * nq, Rt = Bm * c.max_len, e = m->esz;
+    const size_t Bm = c.max_batch, M = Bm * m->NT, e = m->esz;
     int ncross = 0;
-    for (const QLayer& L : m->ql) ncross += L.cross;
+    for (const PostLayer& L : m->pl) ncross += L.has_cross;
     TRY(alloc_image_tower(m));
     TRY(dev_alloc(m, (void**)&m->emb_f, M * D * 4));
     TRY(dev_alloc(m, &m->emb_t, M * D * e));
     TRY(dev_alloc(m, &m->itm_ckv, (size_t)ncross * M * 2 * Q * e));
-    TRY(dev_alloc(m, (void**)&m->qx, Rq * Q * 4));
-    TRY(dev_alloc(m, (void**)&m->qy, Rq * Q * 4));
-    TRY(dev_alloc(m, &m->qx_t, Rq * Q * e));
-    TRY(dev_alloc(m, &m->qqkv, Rq * 3 * Q * e));
-    TRY(dev_alloc(m, &m->qctx, Rq * Q * e));
-    TRY(dev_alloc(m, &m->qh, Rq * F * e));
-    TRY(dev_alloc(m, (void**)&m->tx, Rt * Q * 4));
-    TRY(dev_alloc(m, (void**)&m->ty, Rt * Q * 4));
-    TRY(dev_alloc(m, &m->tx_t, Rt * Q * e));
-    TRY(dev_alloc(m, &m->tqkv, Rt * 3 * Q * e));
-    TRY(dev_alloc(m, &m->tctx, Rt * Q * e));
-    return dev_alloc(m, &m->th, Rt * F * e);
+    TRY(alloc_post_rows(m, m->qr, Bm * nq, Q, F));
+    return alloc_post_rows(m, m->tr, Bm * c.max_len, Q, F);
 }
 
 // ViT-g over B images -> emb_t [B * NT, D] (post_layernorm on every token), then the cross-attention K/V of every cross layer of
@@ -938,65 +988,15 @@ int build_blip2_itm(Captioner* m) {
 int run_itm_images(Captioner* m, const void* pixels, int fmt, int B, hipStream_t s) {
     const CapConfig& c = m->c;
     const int D = c.v_hidden, Q = c.q_hidden, NT = m->NT;
-    const int af = m->gdt == CAP_DT_G8 ? 1 : 0;
     m->itm_B = 0;
     TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
     size_t slot = 0;
-    for (const QLayer& L : m->ql) {
-        if (!L.cross) continue;
-        void* kv = (char*)m->itm_ckv + slot++ * (size_t)c.max_batch * NT * 2 * Q * m->esz;
-        TRY(gemm(m, s, "itm_gemm_ckv", m->emb_t, D, L.w_ckv, D, kv, 2 * Q, L.b_ckv, nullptr, B * NT, 2 * Q, D, 0, af));
+    for (const PostLayer& L : m->pl) {
+        if (!L.has_cross) continue;
+        TRY(gemm(m, s, kItmQueryTags.ckv, m->emb_t, D, L.w_ckv, D, itm_ckv_slot(m, slot++), 2 * Q, L.b_ckv, nullptr, B * NT, 2 * Q, D, 0,
+                 m->attn_f32()));
     }
     m->itm_B = B;
-    return 0;
-}
-
-// The Q-Former over B pairs with nq query rows (0: none - the ITC text pass) and L text rows (0: none - the ITC image pass) each:
-// self-attention over [queries | the pair's text], cross-attention of the query rows to the cached image K/V on the cross layers,
-// the query rows through intermediate_query / output_query and the text rows through intermediate / output.  The two kinds of
-// rows live in their own buffers (qx .. / tx ..), so every GEMM runs over contiguous rows.  Leaves the last hidden states in qx
-// [B * nq, Q] and tx [B * L, Q] (fp32).
-int run_itm_qformer(Captioner* m, int B, int nq, int L, const int* ids, const int* lens, hipStream_t s) {
-    const CapConfig& c = m->c;
-    const int Q = c.q_hidden, F = c.q_ffn, H = c.q_heads, NT = m->NT, Rq = B * nq, Rt = B * L, hd = Q / H;
-    const size_t e = m->esz;
-    const int af = m->gdt == CAP_DT_G8 ? 1 : 0;     // split mode: what the attention kernels read (q, k, v) is fp32, only GEMM operands are G8
-    if (nq) TRY(launch_rows_broadcast(m->gdt, m->q_x0, m->qx, m->qx_t, B, nq, Q, s));
-    if (L) {
-        ProfScope ps(m, s, "itm_embed_text", 0, (double)Rt * Q * (8 + 4 + e));
-        TRY(launch_itm_embed_text(m->gdt, ids, L, m->i_word, m->i_pos, m->i_ln_g, m->i_ln_b, c.q_eps, m->tx, m->tx_t, Rt, Q, c.vocab, s));
-    }
-    size_t slot = 0;
-    for (const QLayer& Ly : m->ql) {
-        if (nq) TRY(gemm(m, s, "itm_gemm_qkv_q", m->qx_t, Q, Ly.w_qkv, Q, m->qqkv, 3 * Q, Ly.b_qkv, nullptr, Rq, 3 * Q, Q, 0, af));
-        if (L) TRY(gemm(m, s, "itm_gemm_qkv_t", m->tx_t, Q, Ly.w_qkv, Q, m->tqkv, 3 * Q, Ly.b_qkv, nullptr, Rt, 3 * Q, Q, 0, af));
-        {
-            ProfScope ps(m, s, "itm_self_attn", 4.0 * B * H * (double)(nq + L) * (nq + L) * hd, (double)(Rq + Rt) * 4 * Q * e);
-            TRY(launch_itm_self_attention(m->dt, m->qqkv, m->tqkv, lens, m->qctx, m->tctx, B, nq, L, H, hd, s, m->gdt));
-        }
-        if (nq) TRY(qf_out_ln(m, s, "itm_gemm_so_q", m->qctx, Q, Ly.w_so, Ly.b_so, Ly.so_g, Ly.so_b, m->qx, m->qy, m->qx_t, Rq));
-        if (L) TRY(qf_out_ln(m, s, "itm_gemm_so_t", m->tctx, Q, Ly.w_so, Ly.b_so, Ly.so_g, Ly.so_b, m->tx, m->ty, m->tx_t, Rt));
-        if (Ly.cross) {
-            const char* kv = (const char*)m->itm_ckv + slot++ * (size_t)c.max_batch * NT * 2 * Q * e;
-            if (nq) {
-                TRY(gemm(m, s, "itm_gemm_cq", m->qx_t, Q, Ly.w_cq, Q, m->qqkv, Q, Ly.b_cq, nullptr, Rq, Q, Q, 0, af));
-                {
-                    ProfScope ps(m, s, "itm_cross_attn", 4.0 * B * H * (double)nq * NT * hd, (double)B * NT * 2 * Q * e);
-                    TRY(launch_generic_attention(m->dt, m->qqkv, Q, (long)nq * Q, kv, 2 * Q, (long)NT * 2 * Q, kv + Q * e, 2 * Q, (long)NT * 2 * Q,
-                                                 m->qctx, Q, (long)nq * Q, B, nq, NT, H, hd, -1, s, m->gdt));
-                }
-                TRY(qf_out_ln(m, s, "itm_gemm_co", m->qctx, Q, Ly.w_co, Ly.b_co, Ly.co_g, Ly.co_b, m->qx, m->qy, m->qx_t, Rq));
-            }
-        }
-        if (nq) {
-            TRY(gemm(m, s, "itm_gemm_f1_q", m->qx_t, Q, Ly.w_f1, Q, m->qh, F, Ly.b_f1, nullptr, Rq, F, Q, 1, 0));
-            TRY(qf_out_ln(m, s, "itm_gemm_f2_q", m->qh, F, Ly.w_f2, Ly.b_f2, Ly.f_g, Ly.f_b, m->qx, m->qy, m->qx_t, Rq));
-        }
-        if (L) {
-            TRY(gemm(m, s, "itm_gemm_f1_t", m->tx_t, Q, Ly.w_t1, Q, m->th, F, Ly.b_t1, nullptr, Rt, F, Q, 1, 0));
-            TRY(qf_out_ln(m, s, "itm_gemm_f2_t", m->th, F, Ly.w_t2, Ly.b_t2, Ly.t_g, Ly.t_b, m->tx, m->ty, m->tx_t, Rt));
-        }
-    }
     return 0;
 }
 
@@ -1110,8 +1110,8 @@ int run_generate_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
     const int T = c.t_hidden, nq = c.num_query_tokens, P = nq + 1, Lmax = P + c.max_len;
     TRY(zero_greedy_outputs(a, B, max_len, s));
     TRY(run_encoder(m, a.pixels, a.pixel_fmt, B, nullptr, s));
-    TRY(run_qformer(m, B, s));
-    TRY(gemm(m, s, "b2_gemm_lproj", m->qx_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1));
+    TRY(run_qformer(m, kCaptionPass, B, nq, 0, nullptr, nullptr, s));
+    TRY(gemm(m, s, "b2_gemm_lproj", m->qr.x_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1));
     TRY(launch_opt_prefill_inputs(m->lm_proj, m->o_tok, m->o_pos, m->ox, B, nq, T, c.bos, s));
     hipLaunchKernelGGL(init_seq_kernel, dim3(64), dim3(256), 0, s, m->seq, m->finished, m->lens, B, Lmax, c.bos, c.pad);
     CAP_HIP_CHECK(hipGetLastError());
@@ -1154,73 +1154,34 @@ int build_minilm(Captioner* m) {
     add_slot(m, "embeddings.token_type_embeddings.weight", m->tok_type, CAP_DT_F32, 2, T);
     TRY(reg_f32(m, "embeddings.LayerNorm.weight", &m->emb_g, T));
     TRY(reg_f32(m, "embeddings.LayerNorm.bias", &m->emb_b, T));
-    m->tl.resize(c.t_layers);
-    for (int i = 0; i < c.t_layers; ++i) {
-        TLayer& L = m->tl[i];
-        const std::string p = "encoder.layer." + std::to_string(i) + ".";
-        TRY(walloc(m, &L.w_qkv, (size_t)3 * T * T * m->esz));
-        TRY(walloc(m, (void**)&L.b_qkv, (size_t)3 * T * 4));
-        const char* nm[3] = {"query", "key", "value"};
-        for (int j = 0; j < 3; ++j) {
-            add_slot(m, p + "attention.self." + nm[j] + ".weight", (char*)L.w_qkv + (size_t)j * T * T * m->esz, m->dt, T, T);
-            add_slot(m, p + "attention.self." + nm[j] + ".bias", L.b_qkv + (size_t)j * T, CAP_DT_F32, 1, T);
-        }
-        TRY(reg_mat(m, p + "attention.output.dense.weight", &L.w_so, T, T));
-        TRY(reg_f32(m, p + "attention.output.dense.bias", &L.b_so, T));
-        TRY(reg_f32(m, p + "attention.output.LayerNorm.weight", &L.so_g, T));
-        TRY(reg_f32(m, p + "attention.output.LayerNorm.bias", &L.so_b, T));
-        TRY(reg_mat(m, p + "intermediate.dense.weight", &L.w_f1, F, T));
-        TRY(reg_f32(m, p + "intermediate.dense.bias", &L.b_f1, F));
-        TRY(reg_mat(m, p + "output.dense.weight", &L.w_f2, T, F));
-        TRY(reg_f32(m, p + "output.dense.bias", &L.b_f2, T));
-        TRY(reg_f32(m, p + "output.LayerNorm.weight", &L.f_g, T));
-        TRY(reg_f32(m, p + "output.LayerNorm.bias", &L.f_b, T));
-    }
-    const size_t M = (size_t)c.max_batch * c.max_len, e = m->esz;
-    TRY(dev_alloc(m, (void**)&m->te_x, M * T * 4));
-    TRY(dev_alloc(m, (void**)&m->te_y, M * T * 4));
-    TRY(dev_alloc(m, &m->te_xt, M * T * e));
-    TRY(dev_alloc(m, &m->te_qkv, M * 3 * T * e));
-    TRY(dev_alloc(m, &m->te_ctx, M * T * e));
-    TRY(dev_alloc(m, &m->te_h, M * F * e));
-    return 0;
+    TRY(reg_post_layers(m, kBertNames, c.t_layers, T, F, 0, 0, false));
+    return alloc_post_rows(m, m->te, (size_t)c.max_batch * c.max_len, T, F);
 }
 
 // ids int32 [B, L] (padded rows: any valid id), lens int32 [B] (tokens incl. [CLS]/[SEP]) -> out fp32 [B, T]: mean of the
 // last hidden states over the valid tokens, L2-normalised.
 int run_text_encoder(Captioner* m, const int* ids, const int* lens, int B, int L, float* out, hipStream_t s) {
     const CapConfig& c = m->c;
-    const int T = c.t_hidden, F = c.t_ffn, H = c.t_heads, M = B * L;
+    const int T = c.t_hidden, H = c.t_heads, M = B * L;
+    const PostDims d = {T, c.t_ffn, c.t_eps};
+    const PostTags& tg = kMiniLMTags;
+    const PostRows& r = m->te;
     {
         ProfScope ps(m, s, "te_embed", 0, (double)M * T * (12 + m->esz));
-        TRY(launch_embed_tokens(m->dt, ids, L, m->word_f32, m->tpos, m->tok_type, m->emb_g, m->emb_b, c.t_eps, m->te_xt,
-                                m->te_x, M, T, s, c.vocab));
+        TRY(launch_embed_tokens(m->dt, ids, L, m->word_f32, m->tpos, m->tok_type, m->emb_g, m->emb_b, c.t_eps, r.x_t, r.x, M, T, s,
+                                c.vocab));
     }
-    for (int i = 0; i < c.t_layers; ++i) {
-        const TLayer& Ly = m->tl[i];
-        TRY(gemm(m, s, "te_gemm_qkv", m->te_xt, T, Ly.w_qkv, T, m->te_qkv, 3 * T, Ly.b_qkv, nullptr, M, 3 * T, T, 0, 0,
-                 EPI_STORE, 0, 0, 0, 0, nullptr, nullptr));
+    for (const PostLayer& Ly : m->pl) {
+        TRY(post_qkv(m, s, tg, Ly.self, r, M, d));
         {
-            ProfScope ps(m, s, "te_attention", 4.0 * B * H * (double)L * L * (T / H), (double)M * 4 * T * m->esz);
-            TRY(launch_text_attention(m->dt, m->te_qkv, lens, m->te_ctx, B, L, H, T / H, s));
+            ProfScope ps(m, s, tg.self_attn, 4.0 * B * H * (double)L * L * (T / H), (double)M * 4 * T * m->esz);
+            TRY(launch_text_attention(m->dt, r.qkv, lens, r.ctx, B, L, H, T / H, s));
         }
-        TRY(gemm(m, s, "te_gemm_o", m->te_ctx, T, Ly.w_so, T, m->te_y, T, Ly.b_so, m->te_x, M, T, T, 0, 1, EPI_STORE, 0, 0, 0,
-                 0, nullptr, nullptr));
-        {
-            ProfScope ps(m, s, "te_layernorm", 0, (double)M * T * (8 + m->esz));
-            TRY(launch_layernorm(m->dt, m->te_y, T, Ly.so_g, Ly.so_b, c.t_eps, m->te_xt, m->te_x, M, T, s));
-        }
-        TRY(gemm(m, s, "te_gemm_f1", m->te_xt, T, Ly.w_f1, T, m->te_h, F, Ly.b_f1, nullptr, M, F, T, 1, 0, EPI_STORE, 0, 0, 0,
-                 0, nullptr, nullptr));
-        TRY(gemm(m, s, "te_gemm_f2", m->te_h, F, Ly.w_f2, F, m->te_y, T, Ly.b_f2, m->te_x, M, T, F, 0, 1, EPI_STORE, 0, 0, 0,
-                 0, nullptr, nullptr));
-        {
-            ProfScope ps(m, s, "te_layernorm", 0, (double)M * T * (8 + m->esz));
-            TRY(launch_layernorm(m->dt, m->te_y, T, Ly.f_g, Ly.f_b, c.t_eps, m->te_xt, m->te_x, M, T, s));
-        }
+        TRY(post_out_ln(m, s, tg.so, tg.ln, r.ctx, T, Ly.self, r, M, d));
+        TRY(post_ffn(m, s, tg, Ly.ffn, r, M, d));
     }
     ProfScope ps(m, s, "te_pool", 0, (double)M * T * 4);
-    return launch_mean_pool_normalize(m->te_x, lens, B, L, T, out, s);
+    return launch_mean_pool_normalize(r.x, lens, B, L, T, out, s);
 }
 
 // ---------------------------------------------------------------------------------------------- pre-LN towers
@@ -1491,7 +1452,7 @@ int run_step(Captioner* m, const Dec& d, const int* tokens, int tok_ld, int t, i
     const int* skip = (P.skip_finished && K == 1 && !cm) ? d.finished : nullptr;
     TRY(launch_embed(m->gdt, tokens, tok_ld, t, P.word, P.pos, P.emb_g, P.emb_b, c.t_eps, d.dx_t, P.pre_ln ? nullptr : d.dx, R, W, s,
                      P.pre_ln ? d.dx : nullptr, d.map));
-    for (const DecSub& u : P.subs) {
+    for (const SubLayer& u : P.subs) {
         const void* A = d.dctx;      // the output projection's operand [R, Kout]
         int Kout = W, S = 1;
         if (u.kind == DEC_FFN) {
@@ -1590,7 +1551,7 @@ int run_step_small(Captioner* m, const Dec& d, const int* tokens, int tok_ld, in
         return launch_small_gemm(m->gdt, g, s);
     };
     bool first = true;                             // the first kernel reads the embedding's LayerNorm from d.dx_t
-    for (const DecSub& u : P.subs) {
+    for (const SubLayer& u : P.subs) {
         const char *t_in = tg.s_in[u.kind], *t_out = tg.s_out[u.kind];
         int S_out = S_ww;
         if (u.kind == DEC_SELF) {
@@ -1677,7 +1638,7 @@ int run_prefill(Captioner* m, const Dec& d, int c0, int nc, int npos, int Lm, hi
         ProfScope ps(m, s, "prefill_embed", 0, (double)Rp * W * (8 + e));
         TRY(launch_embed_prompt(m->gdt, d.seq, Lm, npos, c0, P.word, P.pos, P.emb_g, P.emb_b, c.t_eps, pd.dx_t, pd.dx, nc, W, s));
     }
-    for (const DecSub& u : P.subs) {
+    for (const SubLayer& u : P.subs) {
         const void* A = pd.dctx;
         int Kout = W, S = 1;
         if (u.kind == DEC_FFN) {
@@ -1852,6 +1813,7 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
         cap_set_error("cap_create: unknown dtype");
         return -1;
     }
+    // (the post-LN helpers the sentence encoder shares with the Q-Former rely on this: with dt == gdt their m->gdt is its m->dt)
     if (cfg->compute_dtype == CAP_F32_SPLIT && cfg->arch == CAP_ARCH_MINILM) {
         cap_set_error("cap_create: CAP_F32_SPLIT is built for the captioner architectures (the sentence encoder takes CAP_F32 or CAP_BF16)");
         return -1;
@@ -2210,9 +2172,9 @@ int cap_blip2_itc_image_features(CapHandle h, int B, float* out, void* stream) {
     TRY(check_itm_resident(m, "cap_blip2_itc_image_features", B));
     const CapConfig& c = m->c;
     hipStream_t s = (hipStream_t)stream;
-    TRY(run_itm_qformer(m, B, c.num_query_tokens, 0, nullptr, nullptr, s));
+    TRY(run_qformer(m, kScorerPass, B, c.num_query_tokens, 0, nullptr, nullptr, s));
     ProfScope ps(m, s, "itc_image_head", 2.0 * B * c.num_query_tokens * c.q_hidden * c.embed_dim, (double)B * c.num_query_tokens * (c.q_hidden + c.embed_dim) * 4);
-    return launch_itc_head(m->qx, 1, m->i_vproj, m->i_vproj_b, out, B * c.num_query_tokens, c.q_hidden, c.embed_dim, s);
+    return launch_itc_head(m->qr.x, 1, m->i_vproj, m->i_vproj_b, out, B * c.num_query_tokens, c.q_hidden, c.embed_dim, s);
 }
 
 int cap_blip2_itc_text_features(CapHandle h, const int32_t* ids, const int32_t* lens, int B, int L, float* out, void* stream) {
@@ -2222,9 +2184,9 @@ int cap_blip2_itc_text_features(CapHandle h, const int32_t* ids, const int32_t* 
     if (!out) { cap_set_error("cap_blip2_itc_text_features: null buffer"); return -1; }
     const CapConfig& c = m->c;
     hipStream_t s = (hipStream_t)stream;
-    TRY(run_itm_qformer(m, B, 0, L, ids, lens, s));
+    TRY(run_qformer(m, kScorerPass, B, 0, L, ids, lens, s));
     ProfScope ps(m, s, "itc_text_head", 2.0 * B * c.q_hidden * c.embed_dim, (double)B * (c.q_hidden + c.embed_dim) * 4);
-    return launch_itc_head(m->tx, L, m->i_tproj, m->i_tproj_b, out, B, c.q_hidden, c.embed_dim, s);
+    return launch_itc_head(m->tr.x, L, m->i_tproj, m->i_tproj_b, out, B, c.q_hidden, c.embed_dim, s);
 }
 
 int cap_blip2_itc_scores(const float* img, const float* txt, int Ni, int Nt, int paired, float* out, int num_queries, int embed_dim,
@@ -2242,9 +2204,9 @@ int cap_blip2_itm_logits(CapHandle h, const int32_t* ids, const int32_t* lens, i
     TRY(check_itm_resident(m, "cap_blip2_itm_logits", B));
     const CapConfig& c = m->c;
     hipStream_t s = (hipStream_t)stream;
-    TRY(run_itm_qformer(m, B, c.num_query_tokens, L, ids, lens, s));
+    TRY(run_qformer(m, kScorerPass, B, c.num_query_tokens, L, ids, lens, s));
     ProfScope ps(m, s, "itm_head", 4.0 * B * c.num_query_tokens * c.q_hidden, (double)B * c.num_query_tokens * c.q_hidden * 4);
-    return launch_itm_head(m->qx, m->i_head, m->i_head_b, out_logits, out_prob, B, c.num_query_tokens, c.q_hidden, s);
+    return launch_itm_head(m->qr.x, m->i_head, m->i_head_b, out_logits, out_prob, B, c.num_query_tokens, c.q_hidden, s);
 }
 
 int cap_embed_text(CapHandle h, const int32_t* ids, const int32_t* lens, int B, int L, float* out, void* stream) {
