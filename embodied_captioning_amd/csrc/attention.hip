@@ -1162,7 +1162,8 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(const T* __restri
 
 
 // ---- decode attention, short history (n_keys <= 8*NI): one wave per (row, head): decode_attn.h's wave unit.
-template <typename T, int NI, typename TO = T>
+// SHARE: the unit's form for passes of ~1 000 rows (fused q|k|v producer; see the unit) - same bits.
+template <typename T, int NI, typename TO = T, bool SHARE = false>
 __global__ __launch_bounds__(256, 3) void decode_attention_wave_kernel(const T* __restrict__ q, T* __restrict__ kbase,
                                                                     T* __restrict__ vbase,
                                                                     const int* __restrict__ anc, int anc_ld,
@@ -1175,8 +1176,8 @@ __global__ __launch_bounds__(256, 3) void decode_attention_wave_kernel(const T* 
     if (map.n && crow >= *map.n) return;
     const int row = map.live ? map.live[crow] : crow;
     if (skip && skip[row]) return;          // caption already ended: its logits are never looked at again
-    decode_attention_wave_unit<T, NI, TO>(q, kbase, vbase, anc, anc_ld, rows_per_kv, kv_ld, n_keys, out + (size_t)crow * H * 64, R, H,
-                                          qs, row, h, threadIdx.x & 63, true, nullptr, crow);
+    decode_attention_wave_unit<T, NI, TO, SHARE>(q, kbase, vbase, anc, anc_ld, rows_per_kv, kv_ld, n_keys, out + (size_t)crow * H * 64,
+                                                 R, H, qs, row, h, threadIdx.x & 63, true, nullptr, crow);
 }
 
 
@@ -1901,9 +1902,26 @@ int launch_decode_attention(int dtype, const DecodeAttn& a, hipStream_t s) {
         cap_set_error("decode_attention: a row map is taken by the greedy kernels only (impl 0, one row per K/V block, no ancestry)");
         return -1;
     }
-#define CAP_DA_WAVE_O(TT, NI, TOO)                                                                                     \
-    hipLaunchKernelGGL((decode_attention_wave_kernel<TT, NI, TOO>), dim3((R * H + 3) / 4), dim3(256), 0, s, (const TT*)q,  \
+    // The fused self-attention step of the greedy loop (q|k|v partial sums in, k / v appended, no ancestry): the unit's SHARE form,
+    // which finishes each partial-sum column once per unit instead of once per key sub-lane - 68 / 100 registers and no scratch at
+    // 16 / 32 key slots where the plain form takes 168 and spills (3 waves per SIMD).  Same bits
+    // (tests/test_pass_size_decode_kernels_gpu.py), so the row count may choose.  Launches replayed from a captured graph over
+    // rotating caches (tools/bench_self_attention.py; us per launch, plain / SHARE, 4 | 10 | 20 positions), split mode: 256 rows
+    // 7.9 / 6.6 | 11.3 / 7.7 | 22.0 / 10.3, 512 rows 13.3 / 9.6 | 20.5 / 11.5 | 46.9 / 22.1, 1 024 rows 27.0 / 14.8 | 44.0 / 24.3 | 87.4 /
+    // 38.7; bf16: 256 rows 7.1 / 6.1 | 8.1 / 7.0 | 11.0 / 8.3, 1 024 rows 21.5 / 13.1 | 29.6 / 16.6 | 43.0 / 26.6.  Ahead at every row count
+    // measured: the threshold is the smallest of them, 256 rows (below it: not measured, the plain form stays).
+    // a.form 1 / 2 = the plain / the SHARE form whatever the row count (tests, tools).
+    const bool share_ok = q_part && append_kv && impl == 0 && n_keys <= 32 && !anc;
+    if (a.form < 0 || a.form > 2 || (a.form == 2 && !share_ok) || (a.form == 1 && !(q_part && append_kv))) {
+        cap_set_error("decode_attention: form %d - 0 = by row count; 1 (every key sub-lane finishes its own partial sums) and 2 (each column "
+                      "finished once per unit: no ancestry, impl 0, up to 32 positions) name a form of the fused k/v-append step only", a.form);
+        return -1;
+    }
+    const bool share = share_ok && (a.form == 2 || (a.form == 0 && R >= DECODE_ATTN_SHARE_ROWS));
+#define CAP_DA_WAVE_S(TT, NI, TOO, SH)                                                                                 \
+    hipLaunchKernelGGL((decode_attention_wave_kernel<TT, NI, TOO, SH>), dim3((R * H + 3) / 4), dim3(256), 0, s, (const TT*)q,  \
                        (TT*)kbase, (TT*)vbase, anc, anc_ld, rows_per_kv, kv_ld, n_keys, (TOO*)out, R, H, qs, skip_rows, map)
+#define CAP_DA_WAVE_O(TT, NI, TOO) do { if (share) CAP_DA_WAVE_S(TT, NI, TOO, true); else CAP_DA_WAVE_S(TT, NI, TOO, false); } while (0)
 #define CAP_DA_WAVE(TT, NI) CAP_DA_WAVE_O(TT, NI, TT)
     // bf16: chunks of 40 keys, double-buffered (168 VGPRs -> 3 waves/SIMD, all of a 256-row launch resident at once;
     // 197 image tokens = 5 chunks).  fp32: chunks of 56 keys, single buffer (same register budget).
@@ -1978,6 +1996,7 @@ int launch_decode_attention(int dtype, const DecodeAttn& a, hipStream_t s) {
     }
 #undef CAP_DA_WAVE
 #undef CAP_DA_WAVE_O
+#undef CAP_DA_WAVE_S
 #undef CAP_DA_ONLINE
 #undef CAP_DA_ONLINE_NT
     // impl 1: the simple two-pass kernel (kept as an independent implementation for the tests)

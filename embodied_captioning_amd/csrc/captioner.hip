@@ -688,13 +688,15 @@ struct ProfScope {
 
 int gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, int lda, const void* W, int ldw, void* C, int ldc,
          const float* bias, const float* resid, int M, int N, int K, int gelu, int out_f32, int epi = EPI_STORE,
-         int p0 = 0, int p1 = 0, int p2 = 0, int p3 = 0, const float* aux = nullptr, void* C2 = nullptr) {
+         int p0 = 0, int p1 = 0, int p2 = 0, int p3 = 0, const float* aux = nullptr, void* C2 = nullptr,
+         const int* m_live = nullptr) {      // m_live: GemmParams::m_live (the head of the compacted greedy loop)
     GemmParams p;
     memset(&p, 0, sizeof(p));
     p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.C = C; p.ldc = ldc; p.bias = bias; p.resid = resid; p.ldr = ldc;
     p.M = M; p.N = N; p.K = K; p.gelu = gelu; p.out_f32 = out_f32; p.epi = epi;
     p.p0 = p0; p.p1 = p1; p.p2 = p2; p.p3 = p3; p.aux = aux; p.C2 = C2; p.splitk = 1;
     p.kv16 = epi == EPI_CROSSKV && m->kv16 ? 1 : 0;
+    p.m_live = m_live;
     const double osz = out_f32 ? 4.0 : (double)m->esz;
     ProfScope ps(m, s, tag, 2.0 * M * N * K, ((double)M * K + (double)N * K) * m->esz + (double)M * N * (osz + (resid ? 4.0 : 0.0)));
     return launch_gemm(m->gdt, p, 0, s);   // tile 0 = auto (stream kernel for encoder-sized problems without residual)
@@ -1490,12 +1492,15 @@ int run_step(Captioner* m, const Dec& d, const int* tokens, int tok_ld, int t, i
         TRY(gemm_splitk_reduce_ln(m, s, d, tg.out[u.kind], A, u.w_out, u.b_out, u.ln_g, u.ln_b, c.t_eps, W, Kout, d.dx_t,
                                   P.pre_ln ? nullptr : d.dx, P.pre_ln ? d.dx : nullptr));
     }
+    // the head: compacted, its row tiles and rows from the open count on return too (the split / bf16 kernels of these shapes take
+    // GemmParams::m_live; an fp32-mode vocabulary GEMM covers every row of the pass - the dead rows' logits are never read)
     if (P.w_tr) {
-        TRY(gemm(m, s, tg.tr, d.dx_t, W, P.w_tr, W, d.dy, W, P.b_tr, nullptr, R, W, W, 1, 1));
+        TRY(gemm(m, s, tg.tr, d.dx_t, W, P.w_tr, W, d.dy, W, P.b_tr, nullptr, R, W, W, 1, 1, EPI_STORE, 0, 0, 0, 0, nullptr, nullptr, d.map.n));
         ProfScope ps(m, s, tg.ln, 0, (double)R * W * (8 + e));
-        TRY(launch_layernorm(m->gdt, d.dy, W, P.tr_g, P.tr_b, c.t_eps, d.dx_t, d.dx, R, W, s));
+        TRY(launch_layernorm(m->gdt, d.dy, W, P.tr_g, P.tr_b, c.t_eps, d.dx_t, d.dx, R, W, s, d.map.n));
     }
-    return gemm(m, s, tg.vocab, d.dx_t, W, P.w_vocab, W, d.logits, m->ldl, P.b_vocab, nullptr, R, c.vocab, W, 0, 1);
+    return gemm(m, s, tg.vocab, d.dx_t, W, P.w_vocab, W, d.logits, m->ldl, P.b_vocab, nullptr, R, c.vocab, W, 0, 1, EPI_STORE, 0, 0, 0, 0,
+                nullptr, nullptr, d.map.n);
 }
 
 // ---------------------------------------------------------------------------------------------- small-batch decoder step
@@ -2516,6 +2521,31 @@ int cap_op_decode_attention_fused(int dtype, const float* q_part, int q_S, const
     a.kbase = kbase; a.vbase = vbase; a.anc = anc; a.anc_ld = anc_ld; a.rows_per_kv = rows_per_kv; a.kv_ld = kv_ld;
     a.n_keys = n_keys; a.out = out; a.R = R; a.H = H; a.impl = impl & 15; a.out_dtype = dt_of(dtype); a.kv16 = (impl >> 4) & 1;
     a.q_part = q_part; a.q_S = q_S; a.q_bias = q_bias; a.q_ld = q_ld; a.q_col0 = q_col0; a.append_kv = append_kv;
+    return launch_decode_attention(in_dt_of(dtype), a, (hipStream_t)stream);
+}
+/* the row-wise decode kernels with the compacted loop's live-row count (tests/test_pass_size_decode_kernels_gpu.py) */
+int cap_op_gemm_live(int dtype, const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int gelu, int out_f32,
+                     int tile, const int32_t* n_live, void* stream) {
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.C = C; p.ldc = N; p.bias = bias; p.ldr = N;
+    p.M = M; p.N = N; p.K = K; p.gelu = gelu; p.out_f32 = out_f32; p.epi = EPI_STORE; p.splitk = 1; p.m_live = n_live;
+    return launch_gemm(dt_of(dtype), p, tile, (hipStream_t)stream);
+}
+int cap_op_layernorm_live(int dtype, const float* in, const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int M,
+                          int D, const int32_t* n_live, void* stream) {
+    return launch_layernorm(dt_of(dtype), in, D, gamma, beta, eps, out_t, out_f, M, D, (hipStream_t)stream, n_live);
+}
+int cap_op_decode_attention_live(int dtype, const float* q_part, int q_S, const float* q_bias, int q_ld, int q_col0, int append_kv,
+                                 void* kbase, void* vbase, int kv_ld, int n_keys, void* out, int R, int H, const int32_t* live,
+                                 const int32_t* n_live, int form, void* stream) {
+    if (!q_part || !kbase || !vbase || !out) { cap_set_error("cap_op_decode_attention_live: null pointer"); return -1; }
+    DecodeAttn a;
+    memset(&a, 0, sizeof(a));
+    a.kbase = kbase; a.vbase = vbase; a.rows_per_kv = 1; a.kv_ld = kv_ld; a.n_keys = n_keys; a.out = out; a.R = R; a.H = H;
+    a.out_dtype = dt_of(dtype);
+    a.q_part = q_part; a.q_S = q_S; a.q_bias = q_bias; a.q_ld = q_ld; a.q_col0 = q_col0; a.append_kv = append_kv;
+    a.map.live = live; a.map.n = n_live; a.form = form;
     return launch_decode_attention(in_dt_of(dtype), a, (hipStream_t)stream);
 }
 /* the small-batch decode kernels alone (tests/test_small_kernels_gpu.py): the launchers' own structs, filled field for field */

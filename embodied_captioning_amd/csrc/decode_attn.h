@@ -66,6 +66,35 @@ struct Part8 {
     }
 };
 
+// Part8 for 4 consecutive columns: the same loads, weights and adds per column, so a column finishes to the same bits whichever
+// of the two a lane uses (decode_attention_wave_unit, SHARE).
+struct Part4 {
+    f32x4 a[4], ba;
+    const float* p;
+    size_t zs;
+    __device__ __forceinline__ void issue(const QSource& qs, int R, int row, int col) {
+        p = qs.part + (size_t)row * qs.part_ld + col;
+        zs = (size_t)R * qs.part_ld;
+#pragma unroll
+        for (int z = 0; z < 4; ++z) a[z] = z < qs.S ? *(const f32x4*)(p + (size_t)z * zs) : a[0];
+        ba = *(const f32x4*)(qs.bias + col);
+    }
+    template <typename T>
+    __device__ __forceinline__ void finish(const QSource& qs, float (&v)[4]) {
+#pragma clang fp contract(off)
+        f32x4 sa = a[0];
+#pragma unroll
+        for (int z = 1; z < 4; ++z) {
+            const float w = z < qs.S ? 1.f : 0.f;
+            sa += a[z] * w;
+        }
+        for (int z = 4; z < qs.S; ++z) sa += *(const f32x4*)(p + z * zs);
+        sa += ba;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = to_f32(from_f32<T>(sa[i]));
+    }
+};
+
 template <typename T> struct Raw8;
 template <> struct Raw8<bf16_t> {
     bf16x8 r;
@@ -119,7 +148,12 @@ template <> struct Raw8<float> {
 // the whole history is one memory round trip.  out_row: element 0 of this row's context (columns h * 64 .. are written by the
 // 8 lanes with ksub == 0).  write_kv: append the new position's k / v to the cache (the small-batch path computes a unit in
 // several workgroups; one of them writes).  q_ready: see decode_attention_online_unit.
-template <typename T, int NI, typename TO>
+// SHARE (the fused q|k|v producer only: qs.part with append_kv, no q_ready): the unit's 192 partial-sum columns are finished ONCE,
+// four columns per lane (lanes 0-15 q, 16-31 k, 32-47 v), and handed to the lanes that use them by cross-lane reads.  Without it
+// the 8 key sub-lanes of a dimension chunk each load and sum the same q, k and v columns: 30 16-byte load instructions per wave
+// (S = 4) for 3.8 KB of distinct bytes, beside the 4 NI that bring the history - at ~1 000 rows the CU's load path, not the
+// memory, paces the launch.  Same loads per column, same adds in the same order: the same bits.
+template <typename T, int NI, typename TO, bool SHARE = false>
 __device__ __forceinline__ void decode_attention_wave_unit(const T* __restrict__ q, T* __restrict__ kbase, T* __restrict__ vbase,
                                                            const int* __restrict__ anc, int anc_ld, int rows_per_kv, int kv_ld,
                                                            int n_keys, TO* out_row, int R, int H, const QSource& qs, int row, int h,
@@ -140,10 +174,16 @@ __device__ __forceinline__ void decode_attention_wave_unit(const T* __restrict__
         srcs[i] = (anc && key < n_keys) ? anc[(size_t)row * anc_ld + key] : row / rows_per_kv;
     }
     Part8 pq, pk, pv;
-    if (qs.part) pq.issue(qs, R, pr, qs.col0 + h * 64 + dch * 8);
-    if (fused_kv) {
-        pk.issue(qs, R, pr, qs.col0 + Dh + h * 64 + dch * 8);
-        pv.issue(qs, R, pr, qs.col0 + 2 * Dh + h * 64 + dch * 8);
+    Part4 ps;
+    const int seg = lane >> 4;              // SHARE: 0 = q, 1 = k, 2 = v columns (lane & 15) * 4 .. + 3 of the head; 3 = none
+    if constexpr (SHARE) {
+        if (seg < 3) ps.issue(qs, R, pr, qs.col0 + seg * Dh + h * 64 + (lane & 15) * 4);
+    } else {
+        if (qs.part) pq.issue(qs, R, pr, qs.col0 + h * 64 + dch * 8);
+        if (fused_kv) {
+            pk.issue(qs, R, pr, qs.col0 + Dh + h * 64 + dch * 8);
+            pv.issue(qs, R, pr, qs.col0 + 2 * Dh + h * 64 + dch * 8);
+        }
     }
     Raw8<T> kk[NI], vv[NI];
 #pragma unroll
@@ -157,8 +197,19 @@ __device__ __forceinline__ void decode_attention_wave_unit(const T* __restrict__
             kk[i].zero(); vv[i].zero();
         }
     }
-    float qv[8];
-    if (q_ready) {
+    float qv[8], kn[8], vn[8];
+    if constexpr (SHARE) {
+        // column dch * 8 + e of q / k / v was finished by lane (0 / 16 / 32) + dch * 2 + e / 4 as its element e % 4
+        float fin[4] = {0.f, 0.f, 0.f, 0.f};
+        if (seg < 3) ps.finish<T>(qs, fin);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int src = dch * 2 + (e >> 2);
+            qv[e] = __shfl(fin[e & 3], src, 64);
+            kn[e] = __shfl(fin[e & 3], 16 + src, 64);
+            vn[e] = __shfl(fin[e & 3], 32 + src, 64);
+        }
+    } else if (q_ready) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) qv[e] = q_ready[dch * 8 + e];
     } else if (qs.part) {
@@ -169,9 +220,10 @@ __device__ __forceinline__ void decode_attention_wave_unit(const T* __restrict__
     if (fused_kv) {
         // every lane finishes the newest position's k/v for its 8 columns (same addresses across the 8 key sub-lanes);
         // the 8 lanes that own that position append them to this row's cache and use them
-        float kn[8], vn[8];
-        pk.finish<T>(qs, kn);
-        pv.finish<T>(qs, vn);
+        if constexpr (!SHARE) {
+            pk.finish<T>(qs, kn);
+            pv.finish<T>(qs, vn);
+        }
         const int t = n_keys - 1;
 #pragma unroll
         for (int i = 0; i < NI; ++i) {

@@ -77,9 +77,10 @@ __global__ void cls_rows_kernel(const float* __restrict__ cls, const float* __re
 template <typename T, int MAXV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ in, int ld_in,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        float eps, T* out_t, float* out_f, int M, int D) {
+                                                        float eps, T* out_t, float* out_f, int M, int D,
+                                                        const int* __restrict__ n_rows) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= M) return;
+    if (row >= M || (n_rows && row >= *n_rows)) return;      // n_rows: RowMap::n, rows from the count on are left alone
     const int nv = (D + 255) / 256;
     float4 v[MAXV];
     const float* x = in + (size_t)row * ld_in;
@@ -757,14 +758,14 @@ int launch_cls_rows(const float* cls, const float* pos, float* X, int B, int tok
 }
 
 int launch_layernorm(int dtype, const float* in, int ld_in, const float* gamma, const float* beta, float eps,
-                     void* out_t, float* out_f, int M, int D, hipStream_t s) {
+                     void* out_t, float* out_f, int M, int D, hipStream_t s, const int* n_rows) {
     if (D % 4 != 0 || D > 256 * LN_MAXV || (ld_in % 4) != 0 || (dtype == CAP_DT_G8 && D % 8 != 0)) {
         cap_set_error("layernorm: unsupported width %d (ld %d)", D, ld_in);
         return -1;
     }
 #define CAP_LN(TT, MV)                                                                                                  \
     hipLaunchKernelGGL((layernorm_kernel<TT, MV>), dim3((M + 3) / 4), dim3(256), 0, s, in, ld_in, gamma, beta, eps,    \
-                       (TT*)out_t, out_f, M, D)
+                       (TT*)out_t, out_f, M, D, n_rows)
 #define CAP_LN_T(TT) do { if (D <= 1024) CAP_LN(TT, 4); else if (D <= 2048) CAP_LN(TT, 8); else CAP_LN(TT, LN_MAXV); } while (0)
     CAP_DISPATCH_T(dtype, CAP_LN_T);
 #undef CAP_LN_T

@@ -105,7 +105,20 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, WPE) void gemm_kernel(G
     // before, the four row tiles of a 256-row decode GEMM landed on four XCDs and W crossed the fabric four times: 3.6x the
     // algorithmic bytes by the counters, profiles/r02_bench_pmc.json.)  Placement is a speed heuristic only.
     const int S = EPI == EPI_PARTIAL ? p.splitk : 1;
-    const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN, nwg = ntm * ntn * S;
+    // compacted decode loop (GemmParams::m_live): the open captions are the first *m_live rows.  The grid is the host's; the
+    // workgroups are numbered over the live row tiles, the ones beyond them have the highest ids and return at once (see
+    // gemm_rows_kernel).  EPI_STORE (the head's transform GEMM): the launch is the one over that many rows - rows from the count on
+    // are neither read nor written.  EPI_PARTIAL (the fp32 mode's decode projections): whole live row tiles, as the rows kernel;
+    // M keeps its slab-stride meaning.
+    int m_rows = p.M;
+    if constexpr (EPI == EPI_STORE || EPI == EPI_PARTIAL) {
+        if (p.m_live) {
+            m_rows = min(p.M, *p.m_live);
+            if ((int)blockIdx.x >= ((m_rows + BM - 1) / BM) * ((p.N + BN - 1) / BN) * S) return;
+            if constexpr (EPI == EPI_STORE) p.M = m_rows;
+        }
+    }
+    const int ntm = (m_rows + BM - 1) / BM, ntn = (p.N + BN - 1) / BN, nwg = ntm * ntn * S;
     int bid = blockIdx.x;
     {
         int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
@@ -307,6 +320,10 @@ __global__ __launch_bounds__(512, 2) void gemm_big_kernel(GemmParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm0 = (wave >> 2) * WM, wn0 = (wave & 3) * WN;
     const int r32 = lane & 31, h = lane >> 5;
+    // compacted decode loop (GemmParams::m_live; the fp32 mode's vocabulary GEMM): the launch over the first *m_live rows
+    if constexpr (EPI == EPI_STORE) {
+        if (p.m_live) p.M = min(p.M, *p.m_live);
+    }
     const int ntm = (p.M + BM - 1) / BM, ntn = (p.N + BN - 1) / BN, ntiles = ntm * ntn;
     const int nk = p.K / SLAB;
 

@@ -363,7 +363,18 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p) {
     const int r16 = lane & 15, kg = lane >> 4;
     const int ntn = (p.N + BN - 1) / BN;
     const int tile0 = p.tile1 > 0 ? p.tile0 : 0;
-    const int nitems = ((p.tile1 > 0 ? p.tile1 : ((p.M + 255) / 256) * ntn) - tile0) * SUB;
+    int nitems = ((p.tile1 > 0 ? p.tile1 : ((p.M + 255) / 256) * ntn) - tile0) * SUB;
+    if constexpr (OUT_F32 && EPI == EPI_STORE && !RESID) {
+        // compacted decode loop (GemmParams::m_live; the vocabulary GEMM): the open captions are the first *m_live rows - the tiles are
+        // those of a launch over that many rows (numbered over the live row tiles: a tile range of the host's, tile0 / tile1, ends
+        // where they end), rows from the count on are neither read nor written.  Only this instantiation family looks at the
+        // pointer: the encoder's launches (operand-type or residual outputs) compile without it.
+        if (p.m_live) {
+            p.M = min(p.M, *p.m_live);
+            const int nt = ((p.M + 255) / 256) * ntn;
+            nitems = max((p.tile1 > 0 ? min(p.tile1, nt) : nt) - tile0, 0) * SUB;
+        }
+    }
     const int nk = p.K / (8 * EPC);
     // Tile t -> (row tile tm, column tile tn).  The 32 workgroups of an XCD work on 32 consecutive tiles at a time and share what
     // they fetch through that XCD's L2.  Row-major numbering makes those 32 tiles one strip of 32 / ntn rows x ntn columns - fine

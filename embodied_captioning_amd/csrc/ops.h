@@ -28,7 +28,8 @@ int launch_patchify(int dtype, const void* pixels, int fmt, int B, int img, int 
 int launch_cls_rows(const float* cls, const float* pos, float* X, int B, int tokens, int D, hipStream_t s);
 // row LayerNorm: in fp32 [M,D]; writes out_t (T, optional) and out_f (fp32, optional; may alias in)
 int launch_layernorm(int dtype, const float* in, int ld_in, const float* gamma, const float* beta, float eps,
-                     void* out_t, float* out_f, int M, int D, hipStream_t s);
+                     void* out_t, float* out_f, int M, int D, hipStream_t s,
+                     const int* n_rows = nullptr);   // device int32: rows from *n_rows on are left alone (RowMap::n)
 // split-K / residual consumer: y = sum_z part[z][M][D] + bias + resid (fixed order); y_out (optional, may alias resid)
 // receives y, then LayerNorm(y) goes to out_t / out_f as above (out_f may alias resid when y_out is null)
 int launch_reduce_layernorm(int dtype, const float* part, int S, const float* bias, const float* resid,
@@ -131,7 +132,10 @@ struct DecodeAttn {                    // zero-initialise (memset), then fill
     size_t kv_row0;                    // ancestry, > 32 keys); kv_row0 = index of the launch's first row in them
     RowMap map;                        // q_part / out rows are compact, caches and ancestry belong to map.live[c]
                                        // (wave / online kernels, impl 0)
+    int form;                          // the fused k/v-append step (q_part, append_kv): 0 = by row count, 1 = every key sub-lane finishes
+                                       // its own partial sums, 2 = each column finished once per unit (the pass-size form); same bits
 };
+constexpr int DECODE_ATTN_SHARE_ROWS = 256;    // form 0 takes form 2 from this many rows on (attention.hip, launch_decode_attention)
 int launch_decode_attention(int dtype, const DecodeAttn& a, hipStream_t s);
 // Self-attention of a prompt prefill: n_caps * npos rows, row r = position r % npos of caption row0 + r / npos, its fused q|k|v
 // projection as split-K partial sums part fp32 [S][n_caps * npos][part_ld] (+ bias [3 H 64]).  Two launches: every row's k / v are

@@ -443,6 +443,23 @@ int cap_op_decode_attention(int dtype, const void* q, const void* kbase, const v
 int cap_op_decode_attention_fused(int dtype, const float* q_part, int q_S, const float* q_bias, int q_ld, int q_col0, int append_kv,
                                   void* kbase, void* vbase, const int32_t* anc, int anc_ld, int rows_per_kv, int kv_ld, int n_keys,
                                   void* out, int R, int H, int impl, void* stream);
+/* The row-wise decode kernels as a merged pass of the compacted greedy loop launches them (tests/test_pass_size_decode_kernels_gpu.py).
+ * n_live (device int32, or NULL = every row): rows, row tiles and (row, head) units from *n_live on return at once and leave
+ * their outputs alone.
+ *   cap_op_gemm_live: cap_op_gemm without a residual, C rows from the count on untouched.  The 64 x 64 / 128 x 128 / 256 x 256
+ *     register-staged tiles (tile 2 / 1 / 4), the fp32-output 256 x 256 kernel of the split and bf16 modes (tile 3 / 20) and the
+ *     fp32 mode's 256 x 256 kernel (tile 3) take the count; the other kernels ignore it and cover every row.
+ *   cap_op_layernorm_live: cap_op_layernorm.
+ *   cap_op_decode_attention_live: cap_op_decode_attention_fused (no ancestry, one row per cache block) with the row map - q_part /
+ *     out rows are compact rows c, the caches belong to row live[c] (live NULL: c) - and the form of the fused k/v-append kernel:
+ *     0 by row count, 1 every key sub-lane finishes its own partial sums, 2 each column finished once per unit; same bits. */
+int cap_op_gemm_live(int dtype, const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int gelu, int out_f32,
+                     int tile, const int32_t* n_live, void* stream);
+int cap_op_layernorm_live(int dtype, const float* in, const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int M,
+                          int D, const int32_t* n_live, void* stream);
+int cap_op_decode_attention_live(int dtype, const float* q_part, int q_S, const float* q_bias, int q_ld, int q_col0, int append_kv,
+                                 void* kbase, void* vbase, int kv_ld, int n_keys, void* out, int R, int H, const int32_t* live,
+                                 const int32_t* n_live, int form, void* stream);
 /* The small-batch decode kernels alone (csrc/decode_small.hip; at most 16 rows): the launchers' argument structs field for field
  * (csrc/decode_small.h says what each one means).  dtype CAP_BF16: bf16 operands and caches; CAP_F32_SPLIT: G8 operands (weights
  * through cap_op_convert_weight), fp32 self-attention caches, fp32 or KV16 cross K/V.  The hooks check pointers only: every shape
