@@ -1,37 +1,31 @@
-// Attention kernels of the captioner path (head_dim = 64 everywhere on this path).
+// Attention kernels of the captioner path.
 //
-//  vit_attention_mfma  bf16, whole K / V^T of one (image, head) resident in LDS (N <= 288 tokens), QK^T and PV on
-//                      v_mfma_f32_32x32x16_bf16.  S^T = K.Q^T is computed so that a lane owns one query column:
-//                      the softmax row-reduction is in-lane (+ one cross-half shuffle), and the S^T accumulator
-//                      registers are fed straight back as the B operand of O^T = V^T.P^T (no LDS round trip).
-//  vit_attention_flash bf16, 289..608 tokens (CoCa at 336x336): same LDS-resident K/V, keys walked in chunks with an
-//                      online softmax because the score tile no longer fits in registers.
-//  vit_attention_scalar  any dtype / any N: one thread per query, K/V tiles broadcast from LDS, online softmax in
-//                      fp32.  Strict-fp32 mode uses it; tests use it to cross-check the MFMA kernel.
-//  decode_attention    one new query per (row, head) against cached keys (self-attention cache with per-position
-//                      ancestor indirection for beams, or the beam-shared cross-attention cache). HBM-bound:
-//                      8 lanes x 16 B cover one 128-byte key row, 8 keys per wave-instruction.
+//  ViT (fused q|k|v rows in, context out), seven kernels on the matrix pipe built from the steps in vit_attn_frag.h:
+//    vit_attention_mfma           bf16, head 64, 1 / 2 / 7 / 9 key blocks: whole K / V and the whole score tile resident
+//    vit_attention_flash          bf16, head 64, 19 key blocks (577 tokens): keys in chunks, online softmax
+//    vit_attention_flash_wide     bf16, heads of 65..128 (BLIP-2's ViT-g: 88; OPT prefill: 80, causal)
+//    vit_attention_f32_mfma       exact fp32 products, head 64, 1 / 7 / 9 key blocks, fp32 or G8 context
+//    vit_attention_f32_mfma_wide  exact fp32 products, heads up to 96, any token count
+//    vit_attention_split          G8 in and out (split fp16), any token count
+//    vit_attention_split_pw       its 193..224-token case as a persistent kernel
+//  and vit_attention_scalar: any dtype / any N, one thread per query, K/V tiles broadcast from LDS, online softmax in fp32
+//  (impl 1; tests use it to cross-check the MFMA kernels).
+//  Decode: decode_attention_kernel here and the fused units of decode_attn.h - one new query per (row, head) against cached
+//  keys (self-attention cache with per-position ancestor indirection for beams, or the beam-shared cross-attention cache).
+//  Then the prefill self-attention, the KV16 pack, the generic kernels (any head width, masks), OPT's decode / prefill
+//  helpers, the text-tower attention and the attention pooler.
 #include <algorithm>
 
 #include <type_traits>
 
 #include "ops.h"
 #include "decode_attn.h"
+#include "vit_attn_frag.h"
 
 namespace {
 
-__device__ __forceinline__ int swz_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-constexpr float LOG2E = 1.4426950408889634f;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-#define CAP_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define CAP_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
-
 // ------------------------------------------------------------------------------------------------
-// K and V of one (image, head) sit in LDS as [key][64] bf16 rows of 128 B with the same 16-byte-chunk XOR swizzle as the
-// GEMM tiles, filled by LDS-DMA (swizzle on the source address).  Q.K^T reads K rows with ds_read_b128; P.V needs V
-// "by column" (4 consecutive keys for one d per lane): ds_read_b64_tr_b16 delivers exactly that from the row-major
-// image, so V is never transposed in memory.
+// Whole K / V of one (image, head) resident in LDS (N <= 288 tokens), the whole 32 x N score tile of a query block in registers.
 template <int KB>
 __global__ __launch_bounds__(256, 2) void vit_attention_mfma(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
                                                              int N, int H) {
@@ -45,120 +39,43 @@ __global__ __launch_bounds__(256, 2) void vit_attention_mfma(const bf16_t* __res
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bf16_t* base = qkv + (size_t)b * N * ld + h * 64;
 
-    // 1 KiB pieces of 8 rows; piece p of K and of V go to wave p % 4
-    for (int p = wave; p < NP / 8; p += 4) {
-        const int row = p * 8 + (lane >> 3);
-        const int gch = (lane & 7) ^ ((row >> 1) & 7);
-        const bf16_t* src = base + (size_t)min(row, N - 1) * ld + gch * 8;
-        __builtin_amdgcn_global_load_lds(CAP_GPTR(src + D), CAP_LPTR(Ks + p * 1024), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds(CAP_GPTR(src + 2 * D), CAP_LPTR(Vs + p * 1024), 16, 0, 0);
-    }
+    bf16_stage_kv<1>(Ks, Vs, NP, base, ld, D, N, 64, wave, lane);
     // this wave's query tiles (qt = wave, wave+4, ...): take their Q fragments now, so the loads fly with the K/V DMA
     constexpr int QT = (KB + 3) / 4;
     bf16x8 qfa[QT][4];
 #pragma unroll
-    for (int t = 0; t < QT; ++t) {
-        const int qc = min((wave + 4 * t) * 32 + r32, N - 1);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qfa[t][ks] = *(const bf16x8*)(base + (size_t)qc * ld + ks * 16 + hh * 8);
-    }
+    for (int t = 0; t < QT; ++t) bf16_load_q<1>(qfa[t], base + (size_t)min((wave + 4 * t) * 32 + r32, N - 1) * ld, hh, 64);
     __syncthreads();   // vmcnt(0) + barrier: every piece has landed
 
-    // transposed-read addressing for the P.V A operand: 16-lane group g = lane>>4 handles d columns (g&1)*16 .. +15 and
-    // key sub-block 4*(g>>1); inside a group lane 4q+p supplies row (key) q, columns 4p..4p+3
-    const int tq = (lane >> 2) & 3, tp = lane & 3, tg = lane >> 4;
     const int nqt = (N + 31) / 32;
+    const float c1 = 0.125f * LOG2E;
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
         const int qt = wave + 4 * t;
         if (qt >= nqt) break;
         const int q = qt * 32 + r32;
-        const bf16x8 (&qf)[4] = qfa[t];
-
         f32x16 s[KB];
 #pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) s[kb][e] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                bf16x8 a = *(const bf16x8*)(Ks + swz_off(kb * 32 + r32, ks * 2 + hh));
-                s[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[ks], s[kb], 0, 0, 0);
-            }
-        }
-        // softmax over keys for query column r32: key(kb, e) = kb*32 + (e&3) + 8*(e>>2) + 4*hh
-        float m = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                if (kb == KB - 1) {      // only the last key block can hold padding keys
-                    const int key = kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                    if (key >= N) s[kb][e] = -INFINITY;
-                }
-                m = fmaxf(m, s[kb][e]);
-            }
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        for (int kb = 0; kb < KB; ++kb) bf16_scores<1>(s[kb], Ks, 0, kb * 32 + r32, hh, qfa[t]);
+        const float m = att_mask_max<ATT_MASK_LAST>(s, 0, KB - 1, N, hh);
         float l = 0.f;
-        const float c1 = 0.125f * LOG2E;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float p = __builtin_amdgcn_exp2f((s[kb][e] - m) * c1);   // raw v_exp_f32: inputs are <= 0
-                s[kb][e] = p;
-                l += p;
-            }
+        att_exp_sum(s, m, c1, l);
         l += __shfl_xor(l, 32, 64);
 
         f32x16 o[2];
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[db][e] = 0.f;
+        att_zero(o);
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                // B operand: element j of lane half hh is P^T[key = kb*32 + 16*s2 + 8*(j>>2) + 4*hh + (j&3)][q]
-                bf16x8 pb;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) pb[j] = (bf16_t)s[kb][8 * s2 + j];
-#pragma unroll
-                for (int db = 0; db < 2; ++db) {
-                    // A operand: lane (d = db*32 + r32, hh) needs V[key0 .. key0+3][d] and V[key0+8 .. +11][d],
-                    // key0 = kb*32 + 16*s2 + 4*hh.  In its 16-lane group this lane ADDRESSES row key0+tq,
-                    // columns dcol..dcol+3 and RECEIVES column (lane&15) of the 4 rows.
-                    const int dcol = db * 32 + (tg & 1) * 16 + tp * 4;
-                    const int key0 = kb * 32 + 16 * s2 + 4 * (tg >> 1) + tq;
-                    const char* a0 = Vs + swz_off(key0, dcol >> 3) + (dcol & 7) * 2;
-                    const char* a1 = Vs + swz_off(key0 + 8, dcol >> 3) + (dcol & 7) * 2;
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a1);
-                    const bf16x8 a = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pb, o[db], 0, 0, 0);
-                }
-            }
-        if (q < N) {
-            const float inv = 1.0f / l;
-            bf16_t* op = ctx + ((size_t)b * N + q) * D + h * 64;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    bf16x4 w;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) w[i] = (bf16_t)(o[db][4 * g + i] * inv);
-                    *(bf16x4*)(op + db * 32 + 8 * g + 4 * hh) = w;
-                }
-        }
+            for (int s2 = 0; s2 < 2; ++s2) bf16_pv(o, s[kb], s2, Vs, 0, kb, lane);
+        if (q < N) att_store(ctx + ((size_t)b * N + q) * D + h * 64, 0, o, l, hh);
     }
 }
 
 // Long-sequence variant (CoCa ViT-L/14 at 336x336: 577 tokens, KB = 19): K and V of the (image, head) still fit in LDS
 // (2 x 608 x 128 B = 152 KiB, one workgroup per CU), but the 32 x 608 score tile of a query block does not fit in
 // registers, so the keys are walked in chunks of KC blocks with an online softmax (running max m, running sum l,
-// O rescaled by exp2((m_old - m_new) c)) - same MFMA dataflow per chunk as vit_attention_mfma.
+// O rescaled by exp2((m_old - m_new) c)).
 template <int KB, int KC>
 __global__ __launch_bounds__(256, 1) void vit_attention_flash(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
                                                               int N, int H) {
@@ -172,34 +89,20 @@ __global__ __launch_bounds__(256, 1) void vit_attention_flash(const bf16_t* __re
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bf16_t* base = qkv + (size_t)b * N * ld + h * 64;
 
-    for (int p = wave; p < NP / 8; p += 4) {
-        const int row = p * 8 + (lane >> 3);
-        const int gch = (lane & 7) ^ ((row >> 1) & 7);
-        const bf16_t* src = base + (size_t)min(row, N - 1) * ld + gch * 8;
-        __builtin_amdgcn_global_load_lds(CAP_GPTR(src + D), CAP_LPTR(Ks + p * 1024), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds(CAP_GPTR(src + 2 * D), CAP_LPTR(Vs + p * 1024), 16, 0, 0);
-    }
+    bf16_stage_kv<1>(Ks, Vs, NP, base, ld, D, N, 64, wave, lane);
     const int nqt = (N + 31) / 32;
-    auto load_q = [&](int qt, bf16x8 (&qf)[4]) {
-        const int qc = min(qt * 32 + r32, N - 1);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8*)(base + (size_t)qc * ld + ks * 16 + hh * 8);
-    };
+    auto load_q = [&](int qt, bf16x8 (&qf)[4]) { bf16_load_q<1>(qf, base + (size_t)min(qt * 32 + r32, N - 1) * ld, hh, 64); };
     bf16x8 qf[4], qn[4];
     load_q(min(wave, nqt - 1), qf);
     __syncthreads();   // vmcnt(0) + barrier: every piece has landed
 
-    const int tq = (lane >> 2) & 3, tp = lane & 3, tg = lane >> 4;
     const float c1 = 0.125f * LOG2E;
     for (int qt = wave; qt < nqt; qt += 4) {
         load_q(min(qt + 4, nqt - 1), qn);                 // next tile's Q flies under this tile's MFMAs
         const int q = qt * 32 + r32;
         float m = -INFINITY, l = 0.f;
         f32x16 o[2];
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[db][e] = 0.f;
+        att_zero(o);
 #pragma unroll
         for (int c0 = 0; c0 < KB; c0 += KC) {
             f32x16 s[KC];
@@ -208,86 +111,32 @@ __global__ __launch_bounds__(256, 1) void vit_attention_flash(const bf16_t* __re
             for (int kc = 0; kc < KC; ++kc) {
                 const int kb = c0 + kc;
                 if (kb < KB) {
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) s[kc][e] = 0.f;
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) {
-                        bf16x8 a = *(const bf16x8*)(Ks + swz_off(kb * 32 + r32, ks * 2 + hh));
-                        s[kc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[ks], s[kc], 0, 0, 0);
-                    }
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        if (kb == KB - 1) {      // only the last key block can hold padding keys
-                            const int key = kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                            if (key >= N) s[kc][e] = -INFINITY;
-                        }
-                        cm = fmaxf(cm, s[kc][e]);
-                    }
+                    bf16_scores<1>(s[kc], Ks, 0, kb * 32 + r32, hh, qf);
+                    att_mask_max<ATT_MASK_LAST>(s[kc], kb, KB - 1, N, hh, cm);
                 }
             }
-            cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
-            const float mn = fmaxf(m, cm);
-            const float alpha = __builtin_amdgcn_exp2f((m - mn) * c1);     // first chunk: exp2(-inf) = 0, l and o are 0
-            l *= alpha;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) o[db][e] *= alpha;
-            m = mn;
+            const float mn = att_rescale(m, l, o, att_half_max(cm), c1);
 #pragma unroll
             for (int kc = 0; kc < KC; ++kc) {
                 const int kb = c0 + kc;
                 if (kb < KB) {
+                    att_exp_sum(s[kc], mn, c1, l);
 #pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const float pv = __builtin_amdgcn_exp2f((s[kc][e] - mn) * c1);
-                        s[kc][e] = pv;
-                        l += pv;
-                    }
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) {
-                        bf16x8 pb;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) pb[j] = (bf16_t)s[kc][8 * s2 + j];
-#pragma unroll
-                        for (int db = 0; db < 2; ++db) {
-                            const int dcol = db * 32 + (tg & 1) * 16 + tp * 4;
-                            const int key0 = kb * 32 + 16 * s2 + 4 * (tg >> 1) + tq;
-                            const char* a0 = Vs + swz_off(key0, dcol >> 3) + (dcol & 7) * 2;
-                            const char* a1 = Vs + swz_off(key0 + 8, dcol >> 3) + (dcol & 7) * 2;
-                            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
-                            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a1);
-                            const bf16x8 a = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-                            o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pb, o[db], 0, 0, 0);
-                        }
-                    }
+                    for (int s2 = 0; s2 < 2; ++s2) bf16_pv(o, s[kc], s2, Vs, 0, kb, lane);
                 }
             }
         }
         l += __shfl_xor(l, 32, 64);
-        if (q < N) {
-            const float inv = 1.0f / l;
-            bf16_t* op = ctx + ((size_t)b * N + q) * D + h * 64;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    bf16x4 w;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) w[i] = (bf16_t)(o[db][4 * g + i] * inv);
-                    *(bf16x4*)(op + db * 32 + 8 * g + 4 * hh) = w;
-                }
-        }
+        if (q < N) att_store(ctx + ((size_t)b * N + q) * D + h * 64, 0, o, l, hh);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = qn[ks];
     }
 }
 
 // Heads wider than 64 (BLIP-2's ViT-g/14: 88): the head is handled as TWO 64-wide halves, each with its own K and V
-// image in LDS (the swizzled 128-byte-row layout of the kernels above; columns beyond head_dim are zero - the images are
-// cleared first and the LDS-DMA lanes of missing columns are masked off).  S = Q_lo.K_lo^T + Q_hi.K_hi^T is one longer MFMA
-// chain, O has four 32-wide column blocks.  257 tokens: 4 x 288 x 128 B = 144 KiB, one workgroup per CU; keys in chunks of
-// KC blocks with the online softmax of vit_attention_flash.
+// image in LDS (columns beyond head_dim are zero - the images are cleared first and the LDS-DMA lanes of missing columns
+// are masked off).  S = Q_lo.K_lo^T + Q_hi.K_hi^T is one longer MFMA chain, O has four 32-wide column blocks.  257 tokens:
+// 4 x 288 x 128 B = 144 KiB, one workgroup per CU; keys in chunks of KC blocks with the online softmax of vit_attention_flash.
 template <int KB, int KC>
 __global__ __launch_bounds__(256, 1) void vit_attention_flash_wide(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ ctx,
                                                                    int N, int H, int hd, int causal) {
@@ -308,44 +157,19 @@ __global__ __launch_bounds__(256, 1) void vit_attention_flash_wide(const bf16_t*
         }
         __syncthreads();
     }
-    for (int p = wave; p < NP / 8; p += 4) {
-        const int row = p * 8 + (lane >> 3);
-        const int gch = (lane & 7) ^ ((row >> 1) & 7);
-        const bf16_t* src = base + (size_t)min(row, N - 1) * ld + gch * 8;
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-            if (hf * 64 + gch * 8 < hd) {              // whole 16-byte chunks: head_dim is a multiple of 8
-                __builtin_amdgcn_global_load_lds(CAP_GPTR(src + hf * 64 + D), CAP_LPTR(Ks + hf * IMG + p * 1024), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds(CAP_GPTR(src + hf * 64 + 2 * D), CAP_LPTR(Vs + hf * IMG + p * 1024), 16, 0, 0);
-            }
-        }
-    }
+    bf16_stage_kv<2>(Ks, Vs, NP, base, ld, D, N, hd, wave, lane);
     const int nqt = (N + 31) / 32;
-    auto load_q = [&](int qt, bf16x8 (&qf)[8]) {
-        const int qc = min(qt * 32 + r32, N - 1);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            const int col = ks * 16 + hh * 8;
-            if (col < hd) qf[ks] = *(const bf16x8*)(base + (size_t)qc * ld + col);
-            else
-#pragma unroll
-                for (int i = 0; i < 8; ++i) qf[ks][i] = (bf16_t)0.f;
-        }
-    };
     bf16x8 qf[8];
     __syncthreads();   // vmcnt(0) + barrier: every piece has landed
 
     const int tq = (lane >> 2) & 3, tp = lane & 3, tg = lane >> 4;
     const float c1 = LOG2E / sqrtf((float)hd);
     for (int qt = wave; qt < nqt; qt += 4) {
-        load_q(qt, qf);
+        bf16_load_q<2>(qf, base + (size_t)min(qt * 32 + r32, N - 1) * ld, hh, hd);
         const int q = qt * 32 + r32;
         float m = -INFINITY, l = 0.f;
         f32x16 o[4];
-#pragma unroll
-        for (int db = 0; db < 4; ++db)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[db][e] = 0.f;
+        att_zero(o);
 #pragma unroll
         for (int c0 = 0; c0 < KB; c0 += KC) {
             f32x16 s[KC];
@@ -354,42 +178,25 @@ __global__ __launch_bounds__(256, 1) void vit_attention_flash_wide(const bf16_t*
             for (int kc = 0; kc < KC; ++kc) {
                 const int kb = c0 + kc;
                 if (kb < KB) {
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) s[kc][e] = 0.f;
-#pragma unroll
-                    for (int ks = 0; ks < 8; ++ks) {
-                        bf16x8 a = *(const bf16x8*)(Ks + (ks >> 2) * IMG + swz_off(kb * 32 + r32, (ks & 3) * 2 + hh));
-                        s[kc] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[ks], s[kc], 0, 0, 0);
-                    }
+                    bf16_scores<2>(s[kc], Ks, IMG, kb * 32 + r32, hh, qf);
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         if (kb == KB - 1 || causal) {      // causal (decoder prefill): a query sees the keys up to itself
-                            const int key = kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+                            const int key = att_key(kb, e, hh);
                             if (key >= N || (causal && key > q)) s[kc][e] = -INFINITY;
                         }
                         cm = fmaxf(cm, s[kc][e]);
                     }
                 }
             }
-            cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
-            const float mn = fmaxf(m, cm);
-            const float alpha = __builtin_amdgcn_exp2f((m - mn) * c1);
-            l *= alpha;
-#pragma unroll
-            for (int db = 0; db < 4; ++db)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) o[db][e] *= alpha;
-            m = mn;
+            const float mn = att_rescale(m, l, o, att_half_max(cm), c1);
 #pragma unroll
             for (int kc = 0; kc < KC; ++kc) {
                 const int kb = c0 + kc;
                 if (kb < KB) {
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        const float pv = __builtin_amdgcn_exp2f((s[kc][e] - mn) * c1);
-                        s[kc][e] = pv;
-                        l += pv;
-                    }
+                    att_exp_sum(s[kc], mn, c1, l);
+                    // The mask above, bf16_pv and att_store are written out here: <9, 5> sits at the 512-register limit, and with any
+                    // of the three through vit_attn_frag.h it spills 164 to 228 bytes per lane instead of 148
 #pragma unroll
                     for (int s2 = 0; s2 < 2; ++s2) {
                         bf16x8 pb;
@@ -480,14 +287,8 @@ __global__ __launch_bounds__(256) void vit_attention_scalar(const T* __restrict_
 // ------------------------------------------------------------------------------------------------
 // fp32 ViT attention on the matrix pipe (strict-fp32 and split-fp16 modes: qkv arrives as fp32).  v_mfma_f32_32x32x2_f32
 // multiplies exact fp32 products (157 TFLOP/s peak, 1/16 of the bf16 rate - still ~10x the one-thread-per-query kernel
-// above, which it replaces for 1 / 7 / 9 key blocks).  Same dataflow as vit_attention_mfma: K and V of the (image, head)
-// sit in LDS, S^T = K.Q^T so a lane owns one query column and the S^T accumulators are the B operand of O^T = V^T.P^T.
-//   * LDS rows of 64 fp32 with a pitch of 68 floats: lane (r32, hh) reads the 16-byte chunk 2 ks + hh of key row r32
-//     (its 4 values feed 4 MFMAs as the k-pair (hh = 0, hh = 1); Q uses the same k permutation, so the sum is unchanged)
-//     - with pitch 68 the 16 lanes of a ds_read_b128 phase hit 16 distinct 4-bank groups;
-//   * P.V: MFMA #e of a key block takes keys {kappa_e, kappa_e + 4} = exactly what accumulator register e of the two lane
-//     halves holds, so P never leaves its registers; V^T[d][key] is a ds_read_b32 of 32 consecutive floats per half.
-// One workgroup per (image, head), one wave per SIMD (the MFMA chains are long: 32 dependent MFMAs per score tile).
+// above, which it replaces for 1 / 7 / 9 key blocks).  K and V of the (image, head) sit in LDS as rows of 64 fp32 with a pitch
+// of 68.  One workgroup per (image, head), one wave per SIMD (the MFMA chains are long: 32 dependent MFMAs per score tile).
 template <int KB, typename TO>
 __global__ __launch_bounds__(256, 1) void vit_attention_f32_mfma(const float* __restrict__ qkv, TO* __restrict__ ctx, int N, int H) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -513,74 +314,26 @@ __global__ __launch_bounds__(256, 1) void vit_attention_f32_mfma(const float* __
     for (int qt = wave; qt < nqt; qt += 4) {
         const int q = qt * 32 + r32, qc = min(q, N - 1);
         f32x4 qf[8];
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) qf[ks] = *(const f32x4*)(base + (size_t)qc * ld + (2 * ks + hh) * 4);
+        f32_load_q(qf, base + (size_t)qc * ld, hh);
 
         f32x16 s[KB];
 #pragma unroll
         for (int kb = 0; kb < KB; ++kb) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) s[kb][e] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const f32x4 a = *(const f32x4*)(Ks + (kb * 32 + r32) * PITCH + (2 * ks + hh) * 4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) s[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], qf[ks][j], s[kb], 0, 0, 0);
-            }
+            f32_scores(s[kb], Ks + (kb * 32 + r32) * PITCH, hh, qf);
             __builtin_amdgcn_sched_barrier(0);     // keep the next block's K reads from being hoisted over this chain (spills)
         }
-        // softmax over keys for query column r32: key(kb, e) = kb*32 + (e&3) + 8*(e>>2) + 4*hh
-        float m = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                if (kb == KB - 1) {
-                    const int key = kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                    if (key >= N) s[kb][e] = -INFINITY;
-                }
-                m = fmaxf(m, s[kb][e]);
-            }
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        const float m = att_mask_max<ATT_MASK_LAST>(s, 0, KB - 1, N, hh);
         float l = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float p = __builtin_amdgcn_exp2f((s[kb][e] - m) * c1);
-                s[kb][e] = p;
-                l += p;
-            }
+        att_exp_sum(s, m, c1, l);
         l += __shfl_xor(l, 32, 64);
 
         f32x16 o[2];
+        att_zero(o);
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[db][e] = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int key = kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-#pragma unroll
-                for (int db = 0; db < 2; ++db)
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[key * PITCH + db * 32 + r32], s[kb][e], o[db], 0, 0, 0);
-                if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-            }
-        if (q < N) {
-            const float inv = 1.0f / l;
-            TO* op = ctx + ((size_t)b * N + q) * D;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    store4(op, h * 64 + db * 32 + 8 * g + 4 * hh,
-                           make_float4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv));
-        }
+        for (int kb = 0; kb < KB; ++kb) f32_pv<PITCH>(o, s[kb], Vs + kb * 32 * PITCH, r32, hh);
+        if (q < N) att_store(ctx + ((size_t)b * N + q) * D, h * 64, o, l, hh);
     }
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // The same exact-product fp32 MFMA attention for heads of ANY width up to 96 (a multiple of 8: BLIP-2's ViT-g/14 has 88) and
@@ -610,16 +363,11 @@ __global__ __launch_bounds__(256, 2) void vit_attention_f32_mfma_wide(const floa
     const int qt = qg * 4 + wave;                         // this wave's query tile (past the end: it still helps to fill the chunk)
     const bool live = qt < nqt;
     const int q = qt * 32 + r32, qc = min(q, N - 1);
-    f32x4 qf[12];                                         // up to 96 dims: k-step ks covers dims 8 ks .. 8 ks + 7 (4 per lane half)
-#pragma unroll
-    for (int ks = 0; ks < 12; ++ks)
-        qf[ks] = ks < nks ? *(const f32x4*)(base + (size_t)qc * ld + (2 * ks + hh) * 4) : f32x4(0.f);
+    f32x4 qf[12];                                         // up to 96 dims
+    f32_load_q(qf, base + (size_t)qc * ld, hh, nks);
     float m = -INFINITY, l = 0.f;
     f32x16 o[NDB];
-#pragma unroll
-    for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[db][e] = 0.f;
+    att_zero(o);
 
     for (int c0 = 0; c0 < nkb; c0 += KC) {
         if (c0 > 0) __syncthreads();                      // every wave is done with the previous chunk
@@ -639,84 +387,25 @@ __global__ __launch_bounds__(256, 2) void vit_attention_f32_mfma_wide(const floa
         f32x16 s[KC];
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) s[kc][e] = 0.f;
-            if (c0 + kc < nkb) {
-#pragma unroll
-                for (int ks = 0; ks < 12; ++ks) {
-                    if (ks < nks) {
-                        const f32x4 a = *(const f32x4*)(Ks + (kc * 32 + r32) * PITCH + (2 * ks + hh) * 4);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) s[kc] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], qf[ks][j], s[kc], 0, 0, 0);
-                    }
-                }
-            }
+            f32_scores(s[kc], Ks + (kc * 32 + r32) * PITCH, hh, qf, c0 + kc < nkb, nks);
             __builtin_amdgcn_sched_barrier(0);
         }
-        // scores of this chunk for query column r32: key(kc, e) = (c0 + kc) * 32 + (e & 3) + 8 (e >> 2) + 4 hh
-        float cm = -INFINITY;
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int key = (c0 + kc) * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                if (key >= N) s[kc][e] = -INFINITY;       // padding keys and key blocks past the end
-                cm = fmaxf(cm, s[kc][e]);
-            }
-        cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
-        const float mn = fmaxf(m, cm);
-        const float alpha = __builtin_amdgcn_exp2f((m - mn) * c1);      // first chunk: exp2(-inf) = 0 and l, o are 0
-        l *= alpha;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[db][e] *= alpha;
-        m = mn;
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float pe = __builtin_amdgcn_exp2f((s[kc][e] - mn) * c1);
-                s[kc][e] = pe;
-                l += pe;
-            }
+        // every block is compared with N: padding keys and key blocks past the end
+        const float mn = att_rescale(m, l, o, att_mask_max<ATT_MASK_ALL>(s, c0, 0, N, hh), c1);
+        att_exp_sum(s, mn, c1, l);
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
             if (c0 + kc >= nkb) continue;                 // (its probabilities are all zero)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int key = kc * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-#pragma unroll
-                for (int db = 0; db < NDB; ++db)
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[key * PITCH + db * 32 + r32], s[kc][e], o[db], 0, 0, 0);
-                if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-            }
+            f32_pv<PITCH>(o, s[kc], Vs + kc * 32 * PITCH, r32, hh);
         }
     }
     l += __shfl_xor(l, 32, 64);
-    if (live && q < N) {
-        const float inv = 1.0f / l;
-        TO* op = ctx + ((size_t)b * N + q) * D;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d0 = db * 32 + 8 * g + 4 * hh;       // 4 consecutive dims; HD % 4 == 0: inside or outside together
-                if (d0 < HD)
-                    store4(op, h * HD + d0, make_float4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv));
-            }
-    }
+    if (live && q < N) att_store(ctx + ((size_t)b * N + q) * D, h * HD, o, l, hh, HD);   // HD % 4 == 0: 4 dims inside or outside together
 }
 
 // ------------------------------------------------------------------------------------------------
 // Split-fp16 ViT attention (CAP_F32_SPLIT): q|k|v arrive as G8 (the qkv GEMM writes its output that way), both matrix
-// products run on the fp16 MFMA pipe as hi.lo + lo.hi + hi.hi (common.h), softmax in fp32, context out as G8.  Dataflow of
-// vit_attention_mfma: S^T = K.Q^T (a lane owns a query column), O^T = V^T.P^T with P taken from the S^T accumulators.
-//   * a head's 64 dims of one token are 256 contiguous bytes of the G8 row = 16 chunks [H0 L0 H1 L1 .. H7 L7]; K and V sit in
-//     LDS as rows of 256 B filled by LDS-DMA, chunk c of row r stored at slot c ^ (r & 15) (swizzle applied on the DMA's
-//     source address) so the 16 lanes of a ds_read_b128 phase - 16 consecutive keys, same chunk - hit 16 different slots;
-//   * lane (r32, hh) of a 32x32x16 MFMA supplies 8 consecutive d = group 2 ks + hh: hi chunk 2 (2 ks + hh), lo chunk + 1;
-//   * P.V: V^T fragments through ds_read_b64_tr_b16 from the hi and the lo chunks; P (fp32, in (0, 1]) is split in registers.
+// products run on the fp16 MFMA pipe as hi.lo + lo.hi + hi.hi, softmax in fp32, context out as G8.
 // Any token count: a workgroup = one (image, head, group of 8 query tiles), EIGHT waves = one 32-query tile each (two per
 // SIMD, so one wave's softmax / P-split VALU work runs under the other's MFMAs); the keys are walked in chunks of KC key
 // blocks (KC = 7: 224 keys, 112 KiB of LDS) with an online softmax across chunks - 197 tokens are one chunk and one group
@@ -736,12 +425,6 @@ __global__ __launch_bounds__(512, 1) void vit_attention_split(const g8_t* __rest
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const char* base = (const char*)(qkv + (size_t)b * N * ld + h * 64);      // byte address of (token 0, q dims of head h)
     const size_t rowb = (size_t)ld * 4;
-    auto koff = [](int row, int chunk) { return row * 256 + ((chunk ^ (row & 15)) << 4); };
-    // V is read by ds_read_b64_tr_b16, served in two groups of 32 lanes: 4 consecutive keys x the 4 same-parity chunks of half a
-    // row x 8 bytes.  Key r & 15 folds those 16 pieces onto 8 slots (2-way conflict on every V read); keys {0, 1, 8, 9} by r & 3
-    // send the four rows' chunk sets to {0 2 4 6}, {1 3 5 7}, {8 ..}, {9 ..} (+ 8 for the other half): 16 slots, all 64 banks.
-    auto voff = [](int row, int chunk) { return row * 256 + ((chunk ^ ((row & 1) | ((row & 2) << 2))) << 4); };
-    const int tq = (lane >> 2) & 3, tp = lane & 3, tg = lane >> 4;
     const int nqt = (N + 31) / 32, nkb = nqt;
     const float c1 = 0.125f * LOG2E;
 
@@ -749,127 +432,72 @@ __global__ __launch_bounds__(512, 1) void vit_attention_split(const g8_t* __rest
     const bool live = qt < nqt;
     const int q = qt * 32 + r32, qc = min(q, N - 1);
     f16x8 qh[4], ql[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        const char* qp = base + (size_t)qc * rowb + (2 * ks + hh) * 32;
-        qh[ks] = *(const f16x8*)qp;
-        ql[ks] = *(const f16x8*)(qp + 16);
-    }
+    split_load_q(qh, ql, base + (size_t)qc * rowb, hh);
     float m = -INFINITY, l = 0.f;
     f32x16 o[2];
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o[db][e] = 0.f;
+    att_zero(o);
 
     for (int c0 = 0; c0 < (ONE ? 1 : nkb); c0 += KC) {
         if (c0 > 0) __syncthreads();                   // every wave is done with the previous chunk's K / V
-        // 1 KiB pieces of 4 rows; piece p of K and of V go to wave p % 8
-        for (int p = wave; p < NP / 4; p += 8) {
-            const int row = p * 4 + (lane >> 4);
-            const int c = (lane & 15) ^ (row & 15);
-            const int cv = (lane & 15) ^ ((row & 1) | ((row & 2) << 2));
-            const char* src = base + (size_t)min(c0 * 32 + row, N - 1) * rowb;
-            __builtin_amdgcn_global_load_lds(CAP_GPTR(src + (size_t)D * 4 + c * 16), CAP_LPTR(Ks + p * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds(CAP_GPTR(src + (size_t)2 * D * 4 + cv * 16), CAP_LPTR(Vs + p * 1024), 16, 0, 0);
-        }
+        split_stage<true, true>(Ks, Vs, NP, base, rowb, D, c0 * 32, N, wave, lane);
         __syncthreads();                               // vmcnt(0) + barrier: every piece has landed
         if (!live) continue;
         f32x16 s[KC];
-        float cm = -INFINITY;
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) s[kc][e] = 0.f;
+            att_zero(s[kc]);
             if (EXACT || c0 + kc < nkb) {
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const f16x8 kh = *(const f16x8*)(Ks + koff(kc * 32 + r32, 2 * (2 * ks + hh)));
-                    const f16x8 kl = *(const f16x8*)(Ks + koff(kc * 32 + r32, 2 * (2 * ks + hh) + 1));
-                    s[kc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], s[kc], 0, 0, 0);
-                    s[kc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], s[kc], 0, 0, 0);
-                    s[kc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], s[kc], 0, 0, 0);
-                }
+                for (int ks = 0; ks < 4; ++ks)
+                    split_qk(s[kc], Ks + split_koff(kc * 32 + r32, 2 * (2 * ks + hh)), Ks + split_koff(kc * 32 + r32, 2 * (2 * ks + hh) + 1),
+                             qh[ks], ql[ks]);
             }
             __builtin_amdgcn_sched_barrier(0);      // keep later K reads from piling up over this chain (spills at 256 VGPRs)
         }
-        // scores of this chunk for query column r32: key(kc, e) = (c0 + kc)*32 + (e&3) + 8*(e>>2) + 4*hh
+        // EXACT: only the last block has padding keys; otherwise also key blocks past the end
+        float cm = -INFINITY;
+        if constexpr (EXACT) {
+            cm = att_mask_max<ATT_MASK_LAST>(s, c0, KC - 1, N, hh);
+        } else {
+            // every block is compared with N, written out here on att_key: behind att_mask_max the compiler hoists the KC x 16
+            // comparisons of a single-chunk kernel to its top as live lane masks (<7, true>: 400 more instructions) and re-forms the
+            // lane parts of the key index per chunk in the chunked one (<4, false>: 4 % slower at 577 tokens) - docs/experiments.md
 #pragma unroll
-        for (int kc = 0; kc < KC; ++kc)
+            for (int kc = 0; kc < KC; ++kc)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                if (!EXACT || kc == KC - 1) {
-                    const int key = (c0 + kc) * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                    if (key >= N) s[kc][e] = -INFINITY;     // padding keys and key blocks past the end
+                for (int e = 0; e < 16; ++e) {
+                    if (att_key(c0 + kc, e, hh) >= N) s[kc][e] = -INFINITY;
+                    cm = fmaxf(cm, s[kc][e]);
                 }
-                cm = fmaxf(cm, s[kc][e]);
-            }
-        cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
-        float mn = cm;
-        if constexpr (!ONE) {
-            mn = fmaxf(m, cm);
-            const float alpha = __builtin_amdgcn_exp2f((m - mn) * c1);      // first chunk: exp2(-inf) = 0 and l, o are 0
-            l *= alpha;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) o[db][e] *= alpha;
-            m = mn;
+            cm = att_half_max(cm);
         }
-#pragma unroll
-        for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float p = __builtin_amdgcn_exp2f((s[kc][e] - mn) * c1);
-                s[kc][e] = p;
-                l += p;
-            }
+        float mn = cm;
+        if constexpr (!ONE) mn = att_rescale(m, l, o, cm, c1);
+        att_exp_sum(s, mn, c1, l);
 #pragma unroll
         for (int kc = 0; kc < KC; ++kc) {
             if (!EXACT && c0 + kc >= nkb) continue;     // (its probabilities are all zero)
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                // B operand: element j of lane half hh is P^T[key = kb*32 + 16*s2 + 8*(j>>2) + 4*hh + (j&3)][q]
                 f16x8 ph, pl;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float pv = s[kc][8 * s2 + j];
-                    const f16_t hv = (f16_t)pv;
-                    ph[j] = hv;
-                    pl[j] = (f16_t)(pv - (float)hv);
-                }
+                split_p(s[kc], s2, ph, pl);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    // A operand (see vit_attention_mfma): this lane ADDRESSES row key0 (+8), dims dcol..dcol+3 and RECEIVES
-                    // column (lane & 15) of the 4 rows of its 16-lane group; once from the hi chunk, once from the lo chunk
-                    const int dcol = db * 32 + (tg & 1) * 16 + tp * 4;
-                    const int key0 = kc * 32 + 16 * s2 + 4 * (tg >> 1) + tq;
+                    // A operand as in bf16_pv, once from the hi chunk, once from the lo chunk
+                    const int dcol = att_tr_dcol(lane, db), key0 = kc * 32 + 16 * s2 + att_tr_key(lane);
                     const int ch = 2 * (dcol >> 3), sub = (dcol & 7) * 2;
-                    const s16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + voff(key0, ch) + sub));
-                    const s16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + voff(key0 + 8, ch) + sub));
-                    const s16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + voff(key0, ch + 1) + sub));
-                    const s16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vs + voff(key0 + 8, ch + 1) + sub));
-                    const f16x8 vh = __builtin_bit_cast(f16x8, __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7));
-                    const f16x8 vl = __builtin_bit_cast(f16x8, __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7));
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl, o[db], 0, 0, 0);
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, o[db], 0, 0, 0);
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph, o[db], 0, 0, 0);
+                    const s16x4 h0 = att_read_tr(Vs + split_voff(key0, ch) + sub);
+                    const s16x4 h1 = att_read_tr(Vs + split_voff(key0 + 8, ch) + sub);
+                    const s16x4 l0 = att_read_tr(Vs + split_voff(key0, ch + 1) + sub);
+                    const s16x4 l1 = att_read_tr(Vs + split_voff(key0 + 8, ch + 1) + sub);
+                    split_pv(o[db], att_join<f16x8>(h0, h1), att_join<f16x8>(l0, l1), ph, pl);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
     }
     l += __shfl_xor(l, 32, 64);
-    if (live && q < N) {
-        const float inv = 1.0f / l;
-        g8_t* op = ctx + ((size_t)b * N + q) * D;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                store4(op, h * 64 + db * 32 + 8 * g + 4 * hh,
-                       make_float4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv));
-    }
+    if (live && q < N) att_store(ctx + ((size_t)b * N + q) * D, h * 64, o, l, hh);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -880,7 +508,7 @@ __global__ __launch_bounds__(512, 1) void vit_attention_split(const g8_t* __rest
 //   barrier A (K_u, q_u have landed; every wave is done with V_{u-1}):  issue the DMA of V_u          -> S^T = K.Q^T
 //   barrier B (V_u has landed; every wave is done with K_u):            issue the DMA of K_{u+1}, load q_{u+1} -> softmax, O^T = V^T.P^T, store
 // In vit_attention_split every workgroup starts with its 112 KiB of DMA and a barrier in front of the first MFMA (~3 us of an
-// ~18 us unit at one workgroup per CU).  The per-unit arithmetic is that kernel's, statement for statement: the context has the
+// ~18 us unit at one workgroup per CU).  The per-unit arithmetic is that kernel's, from the same functions: the context has the
 // same bits (tests/test_split_gpu.py::test_vit_attention_persistent_matches_per_unit_kernel).  Measured, interleaved in one process
 // (tools/bench_vit_attention.py, 256 x 12 units): 180 us per launch against 214 for the per-unit kernel; 1024 x 12: 711 / 799.
 // Tried on this structure and not kept: the probabilities of key half-block t + 1 (exp, denominator, hi / lo split) formed in the
@@ -919,31 +547,10 @@ __global__ __launch_bounds__(512, 1) void vit_attention_split_pw(const g8_t* __r
     const int q = wave * 32 + r32, qc = min(q, N - 1);
 
     auto unit_base = [&](int u) { return (const char*)(qkv + (size_t)(u / H) * N * ld + (u % H) * 64); };
-    auto issue_k = [&](const char* base) {
-        for (int p = wave; p < NP / 4; p += 8) {
-            const int row = p * 4 + (lane >> 4);
-            const int c = (lane & 15) ^ (row & 15);
-            const char* src = base + (size_t)min(row, N - 1) * rowb;
-            __builtin_amdgcn_global_load_lds(CAP_GPTR(src + (size_t)D * 4 + c * 16), CAP_LPTR(Ks + p * 1024), 16, 0, 0);
-        }
-    };
-    auto issue_v = [&](const char* base) {
-        for (int p = wave; p < NP / 4; p += 8) {
-            const int row = p * 4 + (lane >> 4);
-            const int cv = (lane & 15) ^ ((row & 1) | ((row & 2) << 2));
-            const char* src = base + (size_t)min(row, N - 1) * rowb;
-            __builtin_amdgcn_global_load_lds(CAP_GPTR(src + (size_t)2 * D * 4 + cv * 16), CAP_LPTR(Vs + p * 1024), 16, 0, 0);
-        }
-    };
+    auto issue_k = [&](const char* base) { split_stage<true, false>(Ks, Vs, NP, base, rowb, D, 0, N, wave, lane); };
+    auto issue_v = [&](const char* base) { split_stage<false, true>(Ks, Vs, NP, base, rowb, D, 0, N, wave, lane); };
     f16x8 qh[4], ql[4];
-    auto load_q = [&](const char* base) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const char* qp = base + (size_t)qc * rowb + (2 * ks + hh) * 32;
-            qh[ks] = *(const f16x8*)qp;
-            ql[ks] = *(const f16x8*)(qp + 16);
-        }
-    };
+    auto load_q = [&](const char* base) { split_load_q(qh, ql, base + (size_t)qc * rowb, hh); };
 
     // LDS fragment addresses as a lane base + a compile-time offset.  K: block kc, k-step ks, half hl is row kc * 32 + r32, chunk
     // 2 (2 ks + hh) + hl, swizzled by the row's low four bits = r32's: 8 bases, + kc * 8192.  V (ds_read_b64_tr_b16): row key0 = kc * 32 +
@@ -954,17 +561,14 @@ __global__ __launch_bounds__(512, 1) void vit_attention_split_pw(const g8_t* __r
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-        for (int hl = 0; hl < 2; ++hl) kb[ks][hl] = (unsigned)(r32 * 256 + (((2 * (2 * ks + hh) + hl) ^ (r32 & 15)) << 4));
-    {
-        const int keyv = (tq & 1) | ((tq & 2) << 2);
+        for (int hl = 0; hl < 2; ++hl) kb[ks][hl] = (unsigned)split_koff(r32, 2 * (2 * ks + hh) + hl);
 #pragma unroll
-        for (int db = 0; db < 2; ++db)
+    for (int db = 0; db < 2; ++db)
 #pragma unroll
-            for (int hl = 0; hl < 2; ++hl) {
-                const int dcol = db * 32 + (tg & 1) * 16 + tp * 4;
-                vb[db][hl] = (unsigned)((4 * (tg >> 1) + tq) * 256 + (((2 * (dcol >> 3) + hl) ^ keyv) << 4) + (dcol & 7) * 2);
-            }
-    }
+        for (int hl = 0; hl < 2; ++hl) {
+            const int dcol = db * 32 + (tg & 1) * 16 + tp * 4;
+            vb[db][hl] = (unsigned)(split_voff(4 * (tg >> 1) + tq, 2 * (dcol >> 3) + hl) + (dcol & 7) * 2);
+        }
 
     int u = blockIdx.x;
     if (u >= n_units) return;
@@ -975,20 +579,12 @@ __global__ __launch_bounds__(512, 1) void vit_attention_split_pw(const g8_t* __r
         __syncthreads();                               // A
         issue_v(base);
         f32x16 s[KC];
-        float cm = -INFINITY;
         if (live) {
 #pragma unroll
             for (int kc = 0; kc < KC; ++kc) {
+                att_zero(s[kc]);
 #pragma unroll
-                for (int e = 0; e < 16; ++e) s[kc][e] = 0.f;
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    const f16x8 kh = *(const f16x8*)(Ks + kb[ks][0] + kc * 8192);
-                    const f16x8 kl = *(const f16x8*)(Ks + kb[ks][1] + kc * 8192);
-                    s[kc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], s[kc], 0, 0, 0);
-                    s[kc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], s[kc], 0, 0, 0);
-                    s[kc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], s[kc], 0, 0, 0);
-                }
+                for (int ks = 0; ks < 4; ++ks) split_qk(s[kc], Ks + kb[ks][0] + kc * 8192, Ks + kb[ks][1] + kc * 8192, qh[ks], ql[ks]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -1001,33 +597,11 @@ __global__ __launch_bounds__(512, 1) void vit_attention_split_pw(const g8_t* __r
             load_q(nbase);
         }
         if (live) {
-            // scores for query column r32: key(kc, e) = kc*32 + (e&3) + 8*(e>>2) + 4*hh
-#pragma unroll
-            for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    if (kc == KC - 1) {
-                        const int key = kc * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
-                        if (key >= N) s[kc][e] = -INFINITY;     // padding keys of the last block
-                    }
-                    cm = fmaxf(cm, s[kc][e]);
-                }
-            cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
-            const float mn = cm;
+            const float mn = att_mask_max<ATT_MASK_LAST>(s, 0, KC - 1, N, hh);
             float l = 0.f;
             f32x16 o[2];
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) o[db][e] = 0.f;
-#pragma unroll
-            for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float pe = __builtin_amdgcn_exp2f((s[kc][e] - mn) * c1);
-                    s[kc][e] = pe;
-                    l += pe;
-                }
+            att_zero(o);
+            att_exp_sum(s, mn, c1, l);
             // The V fragment reads are asm statements: the compiler cannot tell an LDS read from Vs from the LDS-DMA into Ks that is
             // in flight (the next unit's K, issued at barrier B) and waits vmcnt(0) in front of the first ds_read_b64_tr_b16 - which
             // puts the whole prefetch, q rows included, in front of the context products instead of under them.  V itself was
@@ -1036,17 +610,9 @@ __global__ __launch_bounds__(512, 1) void vit_attention_split_pw(const g8_t* __r
                                           {(unsigned)(size_t)CAP_LPTR(Vs) + vb[1][0], (unsigned)(size_t)CAP_LPTR(Vs) + vb[1][1]}};
             att_static_for<0, 2 * KC>([&](auto tc) {
                 constexpr int t = decltype(tc)::value, kc = t >> 1, s2 = t & 1, ro = (kc * 32 + 16 * s2) * 256;
-                // B operand: element j of lane half hh is P^T[key = kc*32 + 16*s2 + 8*(j>>2) + 4*hh + (j&3)][q]
                 f16x8 ph, pl;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float pv = s[kc][8 * s2 + j];
-                    const f16_t hv = (f16_t)pv;
-                    ph[j] = hv;
-                    pl[j] = (f16_t)(pv - (float)hv);
-                }
-                // A operand (see vit_attention_mfma): this lane ADDRESSES row key0 (+8), dims dcol..dcol+3 and RECEIVES column
-                // (lane & 15) of the 4 rows of its 16-lane group; once from the hi chunk, once from the lo chunk
+                split_p(s[kc], s2, ph, pl);
+                // A operand: hi and lo chunk of rows key0 and key0 + 8
                 s16x4 h0[2], h1[2], l0[2], l1[2];
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
@@ -1057,34 +623,17 @@ __global__ __launch_bounds__(512, 1) void vit_attention_split_pw(const g8_t* __r
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(h0[0]), "+v"(h1[0]), "+v"(l0[0]), "+v"(l1[0]), "+v"(h0[1]), "+v"(h1[1]), "+v"(l0[1]), "+v"(l1[1]));
 #pragma unroll
-                for (int db = 0; db < 2; ++db) {
-                    const f16x8 vh = __builtin_bit_cast(f16x8, __builtin_shufflevector(h0[db], h1[db], 0, 1, 2, 3, 4, 5, 6, 7));
-                    const f16x8 vl = __builtin_bit_cast(f16x8, __builtin_shufflevector(l0[db], l1[db], 0, 1, 2, 3, 4, 5, 6, 7));
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl, o[db], 0, 0, 0);
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph, o[db], 0, 0, 0);
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph, o[db], 0, 0, 0);
-                }
+                for (int db = 0; db < 2; ++db) split_pv(o[db], att_join<f16x8>(h0[db], h1[db]), att_join<f16x8>(l0[db], l1[db]), ph, pl);
                 __builtin_amdgcn_sched_barrier(0);
             });
             l += __shfl_xor(l, 32, 64);
-            if (q < N) {
-                const float inv = 1.0f / l;
-                g8_t* op = ctx + ((size_t)(u / H) * N + q) * D;
-                const int h = u % H;
-#pragma unroll
-                for (int db = 0; db < 2; ++db)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        store4(op, h * 64 + db * 32 + 8 * g + 4 * hh,
-                               make_float4(o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv));
-            }
+            if (q < N) att_store(ctx + ((size_t)(u / H) * N + q) * D, (u % H) * 64, o, l, hh);
         }
         if (un >= n_units) break;
         u = un;
         base = nbase;
     }
 }
-
 // ------------------------------------------------------------------------------------------------
 
 template <typename T>

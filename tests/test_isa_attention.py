@@ -2,6 +2,8 @@
 and `o[HDP]` rows in registers by design (252 VGPRs for itm_self_attention_kernel); a toolchain bump that spills them turns
 every key's fma chain into scratch traffic without failing any numerical test.  So the generated code is read: no instantiation may
 have a private segment - except the ones named in SPILLS, asserted with their byte counts so that they cannot grow unnoticed.
+The same for the seven MFMA ViT attention kernels, which keep a query tile's scores and context in accumulators (several of them
+within a few registers of their limit) and are assembled from the shared steps of csrc/vit_attn_frag.h.
 No GPU needed (hipcc cross-compiles)."""
 import os
 import re
@@ -13,8 +15,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = ("itm_self_attention_kernel", "generic_attention_kp_kernel", "generic_attention_kernel", "text_attention_kernel",
            "pool_attention_kernel")
-# demangled-name fragment -> private_segment_fixed_size in bytes, for instantiations that are known to spill
-SPILLS = {}
+VIT_KERNELS = ("vit_attention_mfma", "vit_attention_flash", "vit_attention_flash_wide", "vit_attention_f32_mfma",
+               "vit_attention_f32_mfma_wide", "vit_attention_split", "vit_attention_split_pw")
+# mangled-name fragment -> private_segment_fixed_size in bytes, for instantiations that are known to spill
+SPILLS = {"24vit_attention_flash_wideILi9ELi5EE": 148}      # BLIP-2's ViT-g (88-wide heads, 257 tokens): 512 registers and 36 more
 
 
 @pytest.fixture(scope="module")
@@ -48,12 +52,12 @@ def _is(name, kernel):
     return re.search(r"\d+" + kernel + r"I", name) is not None       # Itanium mangling: <length><name>I<template args>
 
 
-def test_lane_per_query_attention_kernels_keep_their_rows_in_registers(attention_asm):
-    segs = _private_segments(attention_asm)
-    seen = {k: 0 for k in KERNELS}
-    unused = dict(SPILLS)
+def _count_and_check(segs, kernels, what):
+    """instantiations seen per kernel; every one without a private segment, or with exactly its recorded one"""
+    seen = {k: 0 for k in kernels}
+    unused = {frag: size for frag, size in SPILLS.items() if any(_is(frag, k) for k in kernels)}
     for name, size in sorted(segs.items()):
-        for k in KERNELS:
+        for k in kernels:
             if not _is(name, k):
                 continue
             seen[k] += 1
@@ -62,8 +66,21 @@ def test_lane_per_query_attention_kernels_keep_their_rows_in_registers(attention
                 assert size == SPILLS[hit[0]], (name, size, "the recorded spill changed")
                 unused.pop(hit[0], None)
             else:
-                assert size == 0, (name, size, "spills its query / output rows to scratch")
+                assert size == 0, (name, size, what)
+    assert not unused, ("recorded spills that no longer exist", unused)
+    return seen
+
+
+def test_lane_per_query_attention_kernels_keep_their_rows_in_registers(attention_asm):
+    seen = _count_and_check(_private_segments(attention_asm), KERNELS, "spills its query / output rows to scratch")
     # bf16, fp32 and G8-output forms: 3 of the scorer's kernel, 6 four-wave (HDP 32, 64), 12 lane = query (HDP 32..128), 4 text, 6 pooler
     assert seen == {"itm_self_attention_kernel": 3, "generic_attention_kp_kernel": 6, "generic_attention_kernel": 12,
                     "text_attention_kernel": 4, "pool_attention_kernel": 6}, seen
-    assert not unused, ("recorded spills that no longer exist", unused)
+
+
+def test_mfma_vit_attention_kernels_keep_their_tiles_in_registers(attention_asm):
+    seen = _count_and_check(_private_segments(attention_asm), VIT_KERNELS, "spills its score / context accumulators to scratch")
+    # mfma<1, 2, 7, 9>; flash<19, 5>; flash_wide<9, 5>, <2, 2>; f32_mfma<1, 7, 9> x {fp32, G8}; f32_mfma_wide<3, 1..3> x {fp32, G8};
+    # split<2, 1>, <7, 1>, <7, 1, 1>, <4, 0>; split_pw<7>
+    assert seen == {"vit_attention_mfma": 4, "vit_attention_flash": 1, "vit_attention_flash_wide": 2, "vit_attention_f32_mfma": 6,
+                    "vit_attention_f32_mfma_wide": 6, "vit_attention_split": 4, "vit_attention_split_pw": 1}, seen
