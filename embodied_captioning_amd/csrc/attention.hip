@@ -1235,11 +1235,12 @@ __global__ void opt_prefill_inputs_kernel(const float* __restrict__ proj, const 
     }
 }
 __global__ void opt_token_inputs_kernel(const int* __restrict__ seq, int seq_ld, int cur, const float* __restrict__ tok,
-                                        const float* __restrict__ pos, float* __restrict__ x, int B, int T) {
+                                        const float* __restrict__ pos, float* __restrict__ x, int B, int T, int V) {
     const size_t n = (size_t)B * T;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int d = i % T, b = i / T;
-        x[i] = tok[(size_t)seq[(size_t)b * seq_ld + cur] * T + d] + pos[(size_t)(cur + 2) * T + d];
+        const int id = min(max(seq[(size_t)b * seq_ld + cur], 0), V - 1);      // never index outside the table
+        x[i] = tok[(size_t)id * T + d] + pos[(size_t)(cur + 2) * T + d];
     }
 }
 // k|v columns of fused qkv rows [B * L, 3T] -> caches [B][Lmax][T] at positions pos0 .. pos0 + L - 1
@@ -1765,9 +1766,9 @@ int launch_opt_prefill_inputs(const float* proj, const float* tok, const float* 
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }
-int launch_opt_token_inputs(const int* seq, int seq_ld, int cur, const float* tok, const float* pos, float* x, int B, int T,
+int launch_opt_token_inputs(const int* seq, int seq_ld, int cur, const float* tok, const float* pos, float* x, int B, int T, int V,
                             hipStream_t s) {
-    hipLaunchKernelGGL(opt_token_inputs_kernel, dim3(64), dim3(256), 0, s, seq, seq_ld, cur, tok, pos, x, B, T);
+    hipLaunchKernelGGL(opt_token_inputs_kernel, dim3(64), dim3(256), 0, s, seq, seq_ld, cur, tok, pos, x, B, T, V);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }

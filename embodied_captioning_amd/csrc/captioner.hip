@@ -1134,7 +1134,7 @@ int run_generate_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
             TRY(poll_all_finished(m, t, max_len, m->finished, B, nullptr, s, &done));
             if (done) break;
         }
-        TRY(launch_opt_token_inputs(m->seq, Lmax, P + t, m->o_tok, m->o_pos, m->ox, B, T, s));
+        TRY(launch_opt_token_inputs(m->seq, Lmax, P + t, m->o_tok, m->o_pos, m->ox, B, T, c.vocab, s));
         TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B, T, s));
         TRY(run_opt(m, B, 1, P + t, s));
     }
@@ -2462,6 +2462,45 @@ int cap_op_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, 
 }
 int cap_op_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, void* stream) {
     return launch_kv_append(in_dt_of(dtype), qkv, kc, vc, B, L, T, Lmax, pos0, (hipStream_t)stream);
+}
+/* the kernels of a prompt pass alone (tests/test_prefill_kernels_gpu.py) */
+int cap_op_prefill_self_attention(int dtype, const float* part, int S, const float* bias, int part_ld, void* kbase, void* vbase, int kv_ld,
+                                  void* out, int n_caps, int npos, int row0, int H, void* stream) {
+    if (!part || !bias || !kbase || !vbase || !out) { cap_set_error("cap_op_prefill_self_attention: null pointer"); return -1; }
+    return launch_prefill_self_attention(in_dt_of(dtype), part, S, bias, part_ld, kbase, vbase, kv_ld, out, dt_of(dtype), n_caps, npos, row0,
+                                         H, (hipStream_t)stream);
+}
+int cap_op_opt_prefill_inputs(const float* proj, const float* tok, const float* pos, float* x, int B, int nq, int T, int bos, void* stream) {
+    if (!proj || !tok || !pos || !x) { cap_set_error("cap_op_opt_prefill_inputs: null pointer"); return -1; }
+    if (B < 1 || nq < 1 || T < 1 || bos < 0) { cap_set_error("cap_op_opt_prefill_inputs: B = %d, nq = %d, T = %d, bos = %d", B, nq, T, bos); return -1; }
+    return launch_opt_prefill_inputs(proj, tok, pos, x, B, nq, T, bos, (hipStream_t)stream);
+}
+int cap_op_opt_token_inputs(const int32_t* seq, int seq_ld, int cur, const float* tok, const float* pos, float* x, int B, int T, int V,
+                            void* stream) {
+    if (!seq || !tok || !pos || !x) { cap_set_error("cap_op_opt_token_inputs: null pointer"); return -1; }
+    if (B < 1 || T < 1 || V < 1 || cur < 0 || cur >= seq_ld) {
+        cap_set_error("cap_op_opt_token_inputs: B = %d, T = %d, V = %d, column %d of %d", B, T, V, cur, seq_ld);
+        return -1;
+    }
+    return launch_opt_token_inputs(seq, seq_ld, cur, tok, pos, x, B, T, V, (hipStream_t)stream);
+}
+int cap_op_rows_broadcast(int dtype, const float* src, float* dst_f, void* dst_t, int B, int n, int D, void* stream) {
+    if (!src || !dst_f || !dst_t) { cap_set_error("cap_op_rows_broadcast: null pointer"); return -1; }
+    if (B < 1 || n < 1 || D < 1 || (dtype == CAP_F32_SPLIT && D % 8 != 0)) {
+        cap_set_error("cap_op_rows_broadcast: B = %d, n = %d, D = %d (G8 rows need D %% 8 == 0)", B, n, D);
+        return -1;
+    }
+    return launch_rows_broadcast(dt_of(dtype), src, dst_f, dst_t, B, n, D, (hipStream_t)stream);
+}
+int cap_op_dequant_i8_rowmajor(const void* packed, void* dst_bf16, int rows, int cols, void* stream) {
+    if (!packed || !dst_bf16) { cap_set_error("cap_op_dequant_i8_rowmajor: null pointer"); return -1; }
+    if (rows < 1 || cols < 1) { cap_set_error("cap_op_dequant_i8_rowmajor: rows = %d, cols = %d", rows, cols); return -1; }
+    return launch_dequant_i8_rowmajor(packed, dst_bf16, rows, cols, (hipStream_t)stream);
+}
+int cap_op_scale_cols(float* part, const float* scale, int M, int N, void* stream) {
+    if (!part || !scale) { cap_set_error("cap_op_scale_cols: null pointer"); return -1; }
+    if (M < 1 || N < 1) { cap_set_error("cap_op_scale_cols: M = %d, N = %d", M, N); return -1; }
+    return launch_scale_cols(part, scale, M, N, (hipStream_t)stream);
 }
 int cap_op_pool_attention(int dtype, const float* qp, const void* kv, void* out, int B, int N, int Q, int E, int heads, void* stream) {
     return launch_pool_attention(in_dt_of(dtype), qp, kv, out, B, N, Q, E, heads, (hipStream_t)stream, dt_of(dtype));

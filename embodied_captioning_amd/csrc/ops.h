@@ -103,8 +103,8 @@ int launch_generic_attention(int dtype, const void* q, long ldq, long qbs, const
                              int causal_off, hipStream_t s, int out_dtype = -1);   // out_dtype: see launch_vit_attention
 int launch_opt_prefill_inputs(const float* proj, const float* tok, const float* pos, float* x, int B, int nq, int T, int bos,
                               hipStream_t s);
-int launch_opt_token_inputs(const int* seq, int seq_ld, int cur, const float* tok, const float* pos, float* x, int B, int T,
-                            hipStream_t s);
+int launch_opt_token_inputs(const int* seq, int seq_ld, int cur, const float* tok, const float* pos, float* x, int B, int T, int V,
+                            hipStream_t s);     // ids outside [0, V) are clamped
 // decode step of a pre-LN decoder: q|k|v row [B, 3T] -> appends k, v to caches [B][Lmax][T] at `past`, out [B, T]
 constexpr int OPT_DECODE_MAX_KEYS = 1024;      // cached positions (past + 1) launch_opt_decode_attention takes: its scores sit in LDS
 int launch_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int T, int H, int Lmax,

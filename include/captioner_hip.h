@@ -408,6 +408,26 @@ int cap_op_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, 
                                 void* stream);
 /* k | v columns of fused rows qkv [B * L, 3 T] -> caches kc / vc [B][Lmax][T] at positions pos0 .. pos0 + L - 1 (CAP_F32_SPLIT: fp32). */
 int cap_op_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, void* stream);
+/* The kernels that run once per prompt pass, alone (tests/test_prefill_kernels_gpu.py).  One kernel (or kernel pair) each.
+ *   cap_op_prefill_self_attention: the self-attention of a prompt prefill over n_caps * npos rows, row r = position r % npos of caption
+ *     row0 + r / npos.  part fp32 [S][n_caps * npos][part_ld] (S 1..4, part_ld % 4 == 0, >= 3 H 64) + bias [3 H 64] are the fused q|k|v
+ *     projection; every row's k / v go to positions 0 .. npos - 1 of its caption's cache row (kbase / vbase [.][H][kv_ld][64]:
+ *     CAP_BF16 bf16, otherwise fp32), then row (c, p) attends keys 0 .. p -> out [n_caps * npos, H 64] (CAP_F32_SPLIT: G8).
+ *     1 <= npos <= min(31, kv_ld).  The bits of npos calls of cap_op_decode_attention_fused with append_kv.
+ *   cap_op_opt_prefill_inputs: x fp32 [B, nq + 1, T]: row (b, j) = (j < nq ? proj [B * nq, T] row (b, j) : tok row bos) + pos row j + 2.
+ *   cap_op_opt_token_inputs: x fp32 [B, T]: row b = tok row seq[b * seq_ld + cur] (the id clamped to [0, V)) + pos row cur + 2.
+ *   cap_op_rows_broadcast: src fp32 [n, D] repeated for B batch items -> dst_f fp32 and dst_t (dtype; CAP_F32_SPLIT: G8, D % 8 == 0),
+ *     both [B * n, D].
+ *   cap_op_dequant_i8_rowmajor: the bytes of cap_op_quant_i8_pack -> dst_bf16 [rows, cols], the integers as bf16 (exact).
+ *   cap_op_scale_cols: part fp32 [M, N] (N % 4 == 0), part[m][n] *= scale[n]. */
+int cap_op_prefill_self_attention(int dtype, const float* part, int S, const float* bias, int part_ld, void* kbase, void* vbase, int kv_ld,
+                                  void* out, int n_caps, int npos, int row0, int H, void* stream);
+int cap_op_opt_prefill_inputs(const float* proj, const float* tok, const float* pos, float* x, int B, int nq, int T, int bos, void* stream);
+int cap_op_opt_token_inputs(const int32_t* seq, int seq_ld, int cur, const float* tok, const float* pos, float* x, int B, int T, int V,
+                            void* stream);
+int cap_op_rows_broadcast(int dtype, const float* src, float* dst_f, void* dst_t, int B, int n, int D, void* stream);
+int cap_op_dequant_i8_rowmajor(const void* packed, void* dst_bf16, int rows, int cols, void* stream);
+int cap_op_scale_cols(float* part, const float* scale, int M, int N, void* stream);
 /* The CoCa attentional pooler's attention: Q projected queries qp [Q, E] (fp32, shared by the batch) over kv [B * N, 2 E] (K then V)
  * -> out [B * Q, E]; head_dim = E / heads is 64 or 96. */
 int cap_op_pool_attention(int dtype, const float* qp, const void* kv, void* out, int B, int N, int Q, int E, int heads, void* stream);

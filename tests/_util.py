@@ -1,4 +1,5 @@
 """Shared helpers for the GPU parity tests (never imported by the product package)."""
+import ctypes as C
 import json
 import os
 
@@ -117,6 +118,81 @@ def g8_decode(c, scale=1.0):
     c = np.ascontiguousarray(np.asarray(c, dtype=np.float32))
     h = c.view(np.float16).reshape(*c.shape[:-1], -1, 2, 8).astype(np.float32)
     return ((h[..., 0, :] + h[..., 1, :]) / np.float32(scale)).reshape(c.shape)
+
+
+# ---- operands of the single-kernel entry points (cap_op_*): dt is "f32", "bf16" or "f32s" (split mode: fp32 values, G8 operands) ----
+NAN = float("nan")
+
+
+def ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def cur_stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def check_rc(lib, rc):
+    assert rc == 0, lib.cap_last_error().decode()
+
+
+def att_dtype(dt):
+    """element type of q / k / v and the caches of the attention kernels (split mode: fp32)"""
+    return torch.bfloat16 if dt == "bf16" else torch.float32
+
+
+def nan_buf(dt, *shape):
+    """NaN words of the operand's width (a G8 container is 4 bytes per element: a NaN word decodes to NaN)"""
+    return torch.full(shape, NAN, dtype=att_dtype(dt), device="cuda")
+
+
+def nan_f32(*shape):
+    return torch.full(shape, NAN, dtype=torch.float32, device="cuda")
+
+
+def same_bits(a, b):
+    """torch.equal on the bytes (a G8 container's words are not numbers)"""
+    it = {2: torch.int16, 4: torch.int32}[a.element_size()]
+    return a.shape == b.shape and torch.equal(a.contiguous().view(it), b.contiguous().view(it))
+
+
+def finish32(part, bias):
+    """Part8::finish / the cross kernel's q: the slices in order, then the bias, in fp32"""
+    s = part[0].clone()
+    for z in range(1, part.shape[0]):
+        s = s + part[z]
+    return s + bias
+
+
+def operand_values(dt, t, scale=1.0):
+    """device operand -> its float64 values (a NaN container decodes to NaN)"""
+    if dt != "f32s":
+        return t.cpu().double()
+    return torch.from_numpy(g8_decode(t.cpu().contiguous().numpy(), scale)).double()
+
+
+# ---- int8 weights (csrc/gemm_skinny.hip): row-quantised signed bytes in MFMA fragment order + fp32 row scales -------------------------
+def i8_pack(lib, N, w):
+    """fp32 device matrix -> (packed bytes, row scales) through cap_op_quant_i8_pack"""
+    rows, cols = w.shape
+    packed = torch.empty(rows * cols, dtype=torch.uint8, device="cuda")
+    scale = torch.empty(rows, dtype=torch.float32, device="cuda")
+    N.check(lib.cap_op_quant_i8_pack(C.c_void_p(w.data_ptr()), C.c_void_p(packed.data_ptr()), C.c_void_p(scale.data_ptr()), rows, cols, cur_stream()),
+            "cap_op_quant_i8_pack")
+    return packed, scale
+
+
+def i8_unpack(packed, rows, cols):
+    """fragment order -> [rows, cols] int8: block (t, s) of 1 KiB, lane r + 16 g owns 16 bytes = k-step 0 (8) then k-step 1 (8)"""
+    b = packed.view(torch.int8).cpu().view(rows // 16, cols // 64, 4, 16, 2, 8)           # t, s, g, r, ks, e
+    return b.permute(0, 3, 1, 4, 2, 5).reshape(rows, cols)                               # (t, r), (s, ks, g, e)
+
+
+def i8_pack_host(q):
+    """the inverse of i8_unpack on the host: int8 [rows, cols] -> the fragment-ordered bytes (uint8 [rows * cols])"""
+    rows, cols = q.shape
+    b = q.reshape(rows // 16, 16, cols // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5)          # (t, r), (s, ks, g, e) -> t, s, g, r, ks, e
+    return b.contiguous().view(torch.uint8).reshape(-1)
 
 
 # ---- KV16: the split mode's cross-attention K/V cache layout (embodied_captioning_amd/csrc/common.h) ------------------

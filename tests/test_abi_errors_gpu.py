@@ -118,6 +118,15 @@ def test_attention_entry_points_refuse_bad_head_dims_and_null_pointers():
     assert lib.cap_op_kv_append(0, None, p, p, 1, 2, 64, 8, 0, s) != 0 and "kv_append" in N.last_error()
     assert lib.cap_op_kv_append(0, p, p, p, 1, 2, 64, 8, 7, s) != 0 and "do not fit" in N.last_error()
     assert lib.cap_op_kv_append(0, p, p, p, 1, 2, 64, 8, -1, s) != 0 and "do not fit" in N.last_error()
+    # the prompt pass's kernels: q|k|v partial sums of 1 caption x 2 positions, one head, caches of 4 positions
+    pre = lambda part, bias, kc, vc, out, npos=2: lib.cap_op_prefill_self_attention(0, part, 1, bias, 192, kc, vc, 4, out, 1, npos, 0, 1, s)  # noqa: E731
+    for args in [(None, p, p, p, p), (p, None, p, p, p), (p, p, None, p, p), (p, p, p, None, p), (p, p, p, p, None)]:
+        assert pre(*args) != 0 and "cap_op_prefill_self_attention: null" in N.last_error()
+    assert pre(p, p, p, p, p, npos=5) != 0 and "prefill_self_attention: 5 positions" in N.last_error()      # more than the cache rows hold
+    assert lib.cap_op_opt_prefill_inputs(p, p, p, None, 1, 1, 8, 0, s) != 0 and "cap_op_opt_prefill_inputs: null" in N.last_error()
+    assert lib.cap_op_opt_token_inputs(None, 4, 0, p, p, p, 1, 8, 4, s) != 0 and "cap_op_opt_token_inputs: null" in N.last_error()
+    assert lib.cap_op_opt_token_inputs(C.c_void_p(lens.data_ptr()), 4, 4, p, p, p, 1, 8, 4, s) != 0 and "column 4 of 4" in N.last_error()
+    assert lib.cap_op_rows_broadcast(0, p, None, p, 1, 1, 8, s) != 0 and "cap_op_rows_broadcast: null" in N.last_error()
     pool = lambda kv, E, heads: lib.cap_op_pool_attention(0, p, kv, p, 1, 4, 4, E, heads, s)      # noqa: E731
     assert pool(p, 160, 2) != 0 and "head_dim 80" in N.last_error()
     assert pool(p, 128, 0) != 0 and "head_dim" in N.last_error()

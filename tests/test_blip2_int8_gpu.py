@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import token_parity
+from _util import cur_stream as _stream, i8_pack as _pack, i8_unpack as _unpack, token_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -16,25 +16,6 @@ pytestmark = pytest.mark.gpu
 def _lib():
     from embodied_captioning_amd import _native as N
     return N, N.load_library()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _pack(lib, N, w):
-    rows, cols = w.shape
-    packed = torch.empty(rows * cols, dtype=torch.uint8, device="cuda")
-    scale = torch.empty(rows, dtype=torch.float32, device="cuda")
-    N.check(lib.cap_op_quant_i8_pack(C.c_void_p(w.data_ptr()), C.c_void_p(packed.data_ptr()), C.c_void_p(scale.data_ptr()), rows, cols, _stream()),
-            "cap_op_quant_i8_pack")
-    return packed, scale
-
-
-def _unpack(packed, rows, cols):
-    """fragment order -> [rows, cols] int8: block (t, s) of 1 KiB, lane r + 16 g owns 16 bytes = k-step 0 (8) then k-step 1 (8)"""
-    b = packed.view(torch.int8).cpu().view(rows // 16, cols // 64, 4, 16, 2, 8)           # t, s, g, r, ks, e
-    return b.permute(0, 3, 1, 4, 2, 5).reshape(rows, cols)                               # (t, r), (s, ks, g, e)
 
 
 @pytest.mark.parametrize("rows,cols", [(32, 64), (96, 256), (2560, 2560), (256, 10240)])

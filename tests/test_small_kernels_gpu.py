@@ -41,7 +41,9 @@ import numpy as np
 import pytest
 import torch
 
-from _util import G8_WSCALE, g8_decode, g8_encode, kv16_unpack
+from _util import G8_WSCALE, NAN, g8_decode, g8_encode, kv16_unpack
+from _util import att_dtype as _att_dtype, check_rc as _check, cur_stream as _stream, finish32 as _finish32, nan_buf as _nan, nan_f32 as _nanf
+from _util import operand_values as _val, ptr as _p, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +51,6 @@ SPLIT = 2
 TAG = {"bf16": 1, "f32s": SPLIT}
 SLAB = {"bf16": 64, "f32s": 32}
 DTYPES = ["bf16", "f32s"]
-NAN = float("nan")
 EPS = 1e-5
 PRO_GLOBAL, PRO_LN, PRO_SA = 0, 1, 2
 EPI_PARTIAL, EPI_ACT_T, EPI_ACT_F32 = 0, 1, 2
@@ -74,18 +75,6 @@ def lib():
     return _native.load_library()
 
 
-def _p(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _check(lib, rc):
-    assert rc == 0, lib.cap_last_error().decode()
-
-
 def _report(kind, dt, batch_err, small_err):
     print(f"MEASURE {kind} {dt} batch {batch_err:.3e} small {small_err:.3e}")
 
@@ -107,44 +96,11 @@ def _wop(lib, dt, W):
     return d
 
 
-def _val(dt, t, scale=1.0):
-    """device operand -> its float64 values (a NaN container decodes to NaN)"""
-    if dt == "bf16":
-        return t.cpu().double()
-    return torch.from_numpy(g8_decode(t.cpu().contiguous().numpy(), scale)).double()
-
-
 def _round_op(dt, x64):
     """what a store in the operand type keeps of a value"""
     if dt == "bf16":
         return x64.float().to(torch.bfloat16).double()
     return torch.from_numpy(g8_decode(g8_encode(x64.float().contiguous().numpy()))).double()
-
-
-def _att_dtype(dt):
-    return torch.bfloat16 if dt == "bf16" else torch.float32
-
-
-def _nan(dt, *shape):
-    return torch.full(shape, NAN, dtype=torch.bfloat16 if dt == "bf16" else torch.float32, device="cuda")
-
-
-def _nanf(*shape):
-    return torch.full(shape, NAN, dtype=torch.float32, device="cuda")
-
-
-def _same_bits(a, b):
-    """torch.equal on the bytes (a G8 container's words are not numbers)"""
-    it = {2: torch.int16, 4: torch.int32}[a.element_size()]
-    return a.shape == b.shape and torch.equal(a.contiguous().view(it), b.contiguous().view(it))
-
-
-def _finish32(part, bias):
-    """Part8::finish / the cross kernel's q: the slices in order, then the bias, in fp32"""
-    s = part[0].clone()
-    for z in range(1, part.shape[0]):
-        s = s + part[z]
-    return s + bias
 
 
 def _act64(x, act):
