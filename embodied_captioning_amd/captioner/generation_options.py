@@ -5,7 +5,8 @@ stopping_criteria, text prompt, ...; logit processors at ``:236-241``, warpers a
 and HF ``GenerationMixin.generate`` behind ``blip2.py:26``.  What the library runs: greedy decoding (CoCa: ``generation_type=
 "top_k"`` with ``top_k=1`` - what the reference's wrapper calls, ``coca.py:29``; MinLength and forced EOS included) and beam search
 (HF v5 semantics for BLIP / BLIP-2, the reference's ``_generate_beamsearch`` incl. beam groups for CoCa).  Everything below is
-deterministic arg-max / beam arithmetic; sampling, temperature, nucleus / top-k filtering and repetition penalties are not built.
+deterministic arg-max / beam arithmetic (``captioner.num_beams`` and, for BLIP and BLIP-2, ``captioner.length_penalty`` are the config keys;
+BLIP-2 searches with 1 to 8 beams like the other families and computes the prompt once per image, not once per beam); sampling, temperature, nucleus / top-k filtering and repetition penalties are not built.
 """
 from __future__ import annotations
 

@@ -59,6 +59,7 @@ class BLIP(CaptioningPredictor):
         super().__init__(cfg)
         name = cfg.model_name or "Salesforce/blip-image-captioning-base"
         self.num_beams = int(getattr(cfg, "num_beams", 1) or 1)
+        self.length_penalty = self._length_penalty(cfg)
         self.max_length = int(getattr(cfg, "max_length", 20) or 20)
         self.batch_size = int(getattr(cfg, "batch_size", 8) or 8)
         # default arithmetic: split-fp16 GEMMs ("f32s") - token-identical to the reference's fp32 CPU path; "bf16" is ~2x
@@ -139,6 +140,12 @@ class BLIP(CaptioningPredictor):
             self.pool.set_early_exit(poll)
         elif cr:
             logger.warning("captioner.coalesce_rows is the engine pool's dynamic batching: it needs captioner.streams > 1 - ignored")
+
+    @staticmethod
+    def _length_penalty(cfg) -> float:
+        """captioner.length_penalty: the beam search's (HF `generate(length_penalty=)`; absent = 1.0, the greedy loop does not read it)."""
+        lp = getattr(cfg, "length_penalty", None)
+        return 1.0 if lp is None else float(lp)
 
     # nn.Module surface the callers use; weights live in the engine, so .to() only re-targets host-side tensors
     @property
@@ -224,6 +231,7 @@ class BLIP(CaptioningPredictor):
         kw = {"output_logprobs": True} if output_perplexity else {}
         if output_vocab_maxprob:
             kw["output_vocab_maxprob"] = True
+        kw["length_penalty"] = self.length_penalty
         seqs, lens, scores, logits = [], [], [], []
         pool = getattr(self, "pool", None)
         n_images = int(images.shape[0]) if isinstance(images, torch.Tensor) and images.dim() == 4 else \
@@ -296,7 +304,7 @@ class BLIP(CaptioningPredictor):
         # `decode(out[0], skip_special_tokens=True)`), the logits are the generated steps
         pr = None if self.prompt_ids is None else self._prompt_row(self.prompt_ids)
         out = self.engine.generate(px.to(self._device), num_beams=self.num_beams, max_length=self.max_length,
-                                   output_logits=True, prompt_ids=pr)
+                                   length_penalty=self.length_penalty, output_logits=True, prompt_ids=pr)
         n = int(out["lengths"][0])
         ids = out["sequences"][0, :n].tolist()
         self._range_tick()

@@ -115,7 +115,12 @@ class BLIP2(BLIP):
         td = getattr(cfg, "torch_dtype", None)
         if td is not None and str(td).replace("torch.", "") not in ("float16", "half", "bfloat16", "float32", "float"):
             raise ValueError(f"BLIP2(cfg): torch_dtype={td!r} is not a floating type a checkpoint is stored in")
-        self.num_beams = 1
+        # captioner.num_beams / captioner.length_penalty: HF `generate(..., num_beams=K, length_penalty=lp)` (beam search on the
+        # device; the 33 prompt positions are computed and cached once per image, not once per beam)
+        self.num_beams = int(getattr(cfg, "num_beams", 1) or 1)
+        if not 1 <= self.num_beams <= 8:
+            raise ValueError(f"BLIP2(cfg): num_beams = {self.num_beams} (the library searches with 1 to 8 beams)")
+        self.length_penalty = self._length_penalty(cfg)
         self.batch_size = int(getattr(cfg, "batch_size", 8) or 8)
         dtype = "bf16" if self.load_in_8bit else getattr(cfg, "dtype", None) or "f32s"   # parity-grade default: tokens identical to HF fp32 on the golden
         self._device = torch.device(getattr(cfg, "device", "cuda:0") or "cuda:0")
@@ -144,7 +149,7 @@ class BLIP2(BLIP):
         # the reference passes no length: HF then generates 20 new tokens; the optional config key `max_new_tokens` (HF's
         # name) overrides that.  The plugin's `max_length` key is BLIP's / CoCa's TOTAL length and is not read here.
         self.max_length = int(getattr(cfg, "max_new_tokens", 0) or self.arch.max_new_tokens)
-        self.engine = CaptionerEngine(self.arch, dtype=dtype, max_batch=self.batch_size, max_beams=1, max_len=self.max_length,
+        self.engine = CaptionerEngine(self.arch, dtype=dtype, max_batch=self.batch_size, max_beams=self.num_beams, max_len=self.max_length,
                                       device=self._device, cross_cache=getattr(cfg, "cross_cache", None) or "auto",
                                       weight_int8=self.load_in_8bit)
         # HF generate stops once every caption has its EOS; look every few steps (cfg early_exit_poll, 0 = never)
@@ -174,7 +179,7 @@ class BLIP2(BLIP):
                 self.coalesce_rows = 0
             from ....engine import EnginePool
             self.pool = EnginePool(self.arch, n=n_streams, device=self._device, dtype=dtype, max_batch=max(self.batch_size, self.coalesce_rows),
-                                   max_beams=1, max_len=self.max_length, weights_of=self.engine, cross_cache=self.engine.cross_cache,
+                                   max_beams=self.num_beams, max_len=self.max_length, weights_of=self.engine, cross_cache=self.engine.cross_cache,
                                    weight_int8=self.load_in_8bit)
             self.pool.set_early_exit(4 if poll is None else int(poll))
         elif cr:
@@ -194,9 +199,13 @@ class BLIP2(BLIP):
         if not hasattr(self.arch, "num_query_tokens"):
             return super().forward(inputs)
         px = self.preprocess(inputs)[:1]
-        out = self.engine.generate(px.to(self._device), max_length=self.max_length, output_logits=True)
+        out = self.engine.generate(px.to(self._device), num_beams=self.num_beams, max_length=self.max_length,
+                                   length_penalty=self.length_penalty, output_logits=True)
         n = int(out["lengths"][0])
         self._range_tick()
-        # HF's `logits` tuple has one entry per generated token; new objects every call (callers keep references)
+        # HF's `logits` tuple has one entry per generated token ([num_beams, vocab] each, the running beams' rows, under beam search);
+        # new objects every call (callers keep references)
         self.outputs = {"text": self.decode(out["sequences"][0, :n].tolist()), "logits": tuple(out["logits"][t] for t in range(n))}
+        if "sequences_scores" in out:
+            self.outputs["sequences_scores"] = float(out["sequences_scores"][0])
         return self.outputs

@@ -1,5 +1,6 @@
 """Plugin configuration objects - same fields as the reference's ``experimenting_env/captioner/utils/utils.py:2-12``
-plus optional keys (defaults keep existing yamls working): num_beams, max_length, dtype, batch_size, device,
+plus optional keys (defaults keep existing yamls working): num_beams, length_penalty (BLIP / BLIP-2 beam search: HF's
+`generate(length_penalty=)`; None = 1.0), max_length, dtype, batch_size, device,
 image_size (CoCa: open_clip's force_image_size), streams (BLIP: engines / HIP streams the micro-batches of one call rotate
 over, engine.EnginePool; 1 = one engine; the BLIP-2 / CoCa wrappers run one engine and warn when asked for more),
 coalesce_rows (BLIP with streams > 1: the pool merges consecutive micro-batches into passes of at most that many rows - same
@@ -26,13 +27,14 @@ class CaptionerField:
                  early_exit_poll=None, max_new_tokens=None, num_beam_groups=None, tokenizer_dir=None,
                  generation_type=None, top_k=None, top_p=None, temperature=None, repetition_penalty=None,
                  load_in_8bit=None, load_in_4bit=None, torch_dtype=None, cross_cache=None, strict_range=False,
-                 coalesce_rows=None, device_resize=None, prompt=None, prompt_ids=None, max_prompt=None):
+                 coalesce_rows=None, device_resize=None, prompt=None, prompt_ids=None, max_prompt=None, length_penalty=None):
         self.arch_name = arch_name
         self.model_name = model_name
         self.checkpoint_name = checkpoint_name
         self.height = height
         self.width = width
         self.num_beams = num_beams
+        self.length_penalty = length_penalty
         self.max_length = max_length
         self.dtype = dtype
         self.batch_size = batch_size

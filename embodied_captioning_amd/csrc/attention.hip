@@ -1140,16 +1140,32 @@ __global__ __launch_bounds__(64) void generic_decode_attention_kernel(const T* _
 // P.V with a 4-way sum through LDS.  head_dim a multiple of 8, <= 128; past + 1 <= 1024.
 // HD8 = head_dim / 8 when it is known at compile time (10: OPT-2.7b, 8, 16), 0 = any: with a constant trip count a lane's
 // 16-byte loads of a key row are all issued before the first FMA (a runtime loop serialises load -> fma, 10 round trips).
-template <typename T, int HD8, typename TO = T>
-__global__ __launch_bounds__(64) void opt_decode_attention_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
-                                                                  TO* __restrict__ out, int Tw, int H, int hd, int Lmax, int past,
-                                                                  float scale) {
+//
+// BEAM: the rows are r = image * K + beam of a beam search (beam.hip) and a row's history is spread over the caches of its image's
+// rows, nothing having been copied on a reorder.  Keys j < P (the prompt: query tokens + BOS) sit in the cache of the image's row
+// image * K, written once per image by the prompt pass; key P + g, g < past - P, sits at the same position of the cache of row
+// anc[r * anc_ld + g], the row that generated it (clamped into the image's own rows, so no table content reads outside them); the
+// step's own key is appended to row r's cache at `past`.  The physical row of every key is looked up once, in the score pass, and kept
+// in LDS for P.V.  What is summed, and in which order, does not depend on BEAM: a beam row and a greedy row with the same history give
+// the same bits.
+template <typename T, int HD8, typename TO, bool BEAM>
+__device__ __forceinline__ void opt_decode_attention_body(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
+                                                          TO* __restrict__ out, int Tw, int H, int hd, int Lmax, int past, float scale,
+                                                          const int* __restrict__ anc, int anc_ld, int K, int P) {
     __shared__ float qs[128], ps[OPT_DECODE_MAX_KEYS], os[4][128];
+    __shared__ int rs[BEAM ? OPT_DECODE_MAX_KEYS : 1];      // BEAM: physical row of key j
     const int b = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x;
     const T* row = qkv + (size_t)b * 3 * Tw + h * hd;
-    const T* kb = kc + (size_t)b * Lmax * Tw + h * hd;
-    const T* vb = vc + (size_t)b * Lmax * Tw + h * hd;
+    // not BEAM: row b's own cache.  BEAM: position 0 of cache row 0, a key's row chosen per key below
+    const T* kb = kc + (BEAM ? (size_t)0 : (size_t)b * Lmax * Tw) + h * hd;
+    const T* vb = vc + (BEAM ? (size_t)0 : (size_t)b * Lmax * Tw) + h * hd;
     const int Lk = past + 1;
+    [[maybe_unused]] const int r0 = BEAM ? b / K * K : 0;    // first row of this row's image: the prompt's
+    // offset of cached key j (< past) from kb / vb
+    auto key_at = [&](int j) -> size_t {
+        if constexpr (BEAM) return ((size_t)rs[j] * Lmax + j) * Tw;
+        else return (size_t)j * Tw;
+    };
     const int n8 = HD8 ? HD8 : hd >> 3;
     for (int d = lane; d < hd; d += 64) {
         qs[d] = to_f32(row[d]) * scale;
@@ -1159,7 +1175,8 @@ __global__ __launch_bounds__(64) void opt_decode_attention_kernel(const T* __res
     __syncthreads();
     float m = -INFINITY;
     for (int j = lane; j < Lk; j += 64) {
-        const T* kr = j == past ? row + Tw : kb + (size_t)j * Tw;
+        if constexpr (BEAM) rs[j] = j < P || j == past ? r0 : min(max(anc[(size_t)b * anc_ld + j - P], r0), r0 + K - 1);
+        const T* kr = j == past ? row + Tw : kb + key_at(j);
         float sc = 0.f;
         if constexpr (HD8 > 0) {
             float kk[HD8][8];
@@ -1198,7 +1215,7 @@ __global__ __launch_bounds__(64) void opt_decode_attention_kernel(const T* __res
         for (; j + 12 < Lk; j += 16) {            // four keys of this lane's group per trip, loads first
             float vv[4][8];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) load8<T>((j + 4 * u == past ? row + 2 * Tw : vb + (size_t)(j + 4 * u) * Tw) + dc, vv[u]);
+            for (int u = 0; u < 4; ++u) load8<T>((j + 4 * u == past ? row + 2 * Tw : vb + key_at(j + 4 * u)) + dc, vv[u]);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const float pj = ps[j + 4 * u];
@@ -1208,7 +1225,7 @@ __global__ __launch_bounds__(64) void opt_decode_attention_kernel(const T* __res
         }
         for (; j < Lk; j += 4) {
             float vv[8];
-            load8<T>((j == past ? row + 2 * Tw : vb + (size_t)j * Tw) + dc, vv);
+            load8<T>((j == past ? row + 2 * Tw : vb + key_at(j)) + dc, vv);
             const float pj = ps[j];
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = fmaf(pj, vv[e], o[e]);
@@ -1220,9 +1237,22 @@ __global__ __launch_bounds__(64) void opt_decode_attention_kernel(const T* __res
     const float inv = 1.0f / l;
     for (int d = lane; d < hd; d += 64) store1(out + (size_t)b * Tw, h * hd + d, (os[0][d] + os[1][d] + os[2][d] + os[3][d]) * inv);
 }
+template <typename T, int HD8, typename TO = T>
+__global__ __launch_bounds__(64) void opt_decode_attention_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
+                                                                  TO* __restrict__ out, int Tw, int H, int hd, int Lmax, int past,
+                                                                  float scale) {
+    opt_decode_attention_body<T, HD8, TO, false>(qkv, kc, vc, out, Tw, H, hd, Lmax, past, scale, nullptr, 0, 1, 0);
+}
+template <typename T, int HD8, typename TO = T>
+__global__ __launch_bounds__(64) void opt_beam_decode_attention_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
+                                                                       TO* __restrict__ out, int Tw, int H, int hd, int Lmax, int past,
+                                                                       float scale, const int* __restrict__ anc, int anc_ld, int K, int P) {
+    opt_decode_attention_body<T, HD8, TO, true>(qkv, kc, vc, out, Tw, H, hd, Lmax, past, scale, anc, anc_ld, K, P);
+}
 
 // OPT decoder inputs.  Prefill: row (b, j) of x[B, P, T] = (j < nq ? projected query (b, j) : token table[bos]) + position
-// table[j + 2] (HF OPTLearnedPositionalEmbedding offset).  Decode: x[b] = token table[seq[b][cur]] + position table[cur + 2].
+// table[j + 2] (HF OPTLearnedPositionalEmbedding offset).  Decode: x[b] = token table[seq[b][cur]] + position table[at + 2] (the greedy loop
+// keeps token `cur` at sequence position at = cur; a beam search's token columns start at BOS, behind the prompt's positions).
 __global__ void opt_prefill_inputs_kernel(const float* __restrict__ proj, const float* __restrict__ tok, const float* __restrict__ pos,
                                           float* __restrict__ x, int B, int nq, int T, int bos) {
     const size_t n = (size_t)B * (nq + 1) * T;
@@ -1234,25 +1264,26 @@ __global__ void opt_prefill_inputs_kernel(const float* __restrict__ proj, const 
         x[i] = e + pos[(size_t)(j + 2) * T + d];
     }
 }
-__global__ void opt_token_inputs_kernel(const int* __restrict__ seq, int seq_ld, int cur, const float* __restrict__ tok,
+__global__ void opt_token_inputs_kernel(const int* __restrict__ seq, int seq_ld, int cur, int at, const float* __restrict__ tok,
                                         const float* __restrict__ pos, float* __restrict__ x, int B, int T, int V) {
     const size_t n = (size_t)B * T;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int d = i % T, b = i / T;
         const int id = min(max(seq[(size_t)b * seq_ld + cur], 0), V - 1);      // never index outside the table
-        x[i] = tok[(size_t)id * T + d] + pos[(size_t)(cur + 2) * T + d];
+        x[i] = tok[(size_t)id * T + d] + pos[(size_t)(at + 2) * T + d];
     }
 }
-// k|v columns of fused qkv rows [B * L, 3T] -> caches [B][Lmax][T] at positions pos0 .. pos0 + L - 1
+// k|v columns of fused qkv rows [B * L, 3T] -> caches [B][row_ld][T] at positions pos0 .. pos0 + L - 1 (row_ld = positions from one
+// row's cache to the next: the cache length, or K times it where only the first of an image's K beam rows takes the prompt)
 template <typename T>
 __global__ void kv_append_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc, int B, int L, int Tw,
-                                 int Lmax, int pos0) {
+                                 size_t row_ld, int pos0) {
     const size_t n = (size_t)B * L * Tw;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int d = i % Tw;
         const size_t r = i / Tw;
         const int j = r % L, b = r / L;
-        const size_t dst = ((size_t)b * Lmax + pos0 + j) * Tw + d;
+        const size_t dst = (b * row_ld + pos0 + j) * Tw + d;
         kc[dst] = qkv[r * 3 * Tw + Tw + d];
         vc[dst] = qkv[r * 3 * Tw + 2 * Tw + d];
     }
@@ -1760,6 +1791,45 @@ int launch_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, 
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }
+// The beam form: R = B * K rows, r = image * K + beam; P prompt keys per image in the cache of row image * K; anc [R, anc_ld] = the
+// row that generated key P + g of row r's history, for g < past - P (null only where no table is needed: K == 1, every key its own).
+int launch_opt_beam_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int K, int T, int H, int Lmax,
+                                     int P, int past, const int* anc, int anc_ld, hipStream_t s, int out_dtype) {
+    if (out_dtype < 0) out_dtype = dtype;
+    if (out_dtype != dtype && !(dtype == CAP_DT_F32 && out_dtype == CAP_DT_G8 && T % 8 == 0)) {
+        cap_set_error("opt_beam_decode_attention: output type %d for input type %d is not supported here", out_dtype, dtype);
+        return -1;
+    }
+    const int hd = H > 0 ? T / H : 0;
+    if (B < 1 || H < 1 || T % H != 0 || hd % 8 != 0 || hd < 8 || hd > 128 || past < 0 || past + 1 > OPT_DECODE_MAX_KEYS || past >= Lmax) {
+        cap_set_error("opt_beam_decode_attention: unsupported shape T=%d H=%d past=%d Lmax=%d (head_dim a multiple of 8 up to 128, past < min(Lmax, %d))",
+                      T, H, past, Lmax, OPT_DECODE_MAX_KEYS);
+        return -1;
+    }
+    if (K < 1 || K > 8 || P < 0 || P > past || (anc && anc_ld < past - P)) {
+        cap_set_error("opt_beam_decode_attention: beams=%d (1..8), prompt keys=%d of past=%d, ancestry rows of %d entries (>= past - prompt)",
+                      K, P, past, anc_ld);
+        return -1;
+    }
+    if (!qkv || !kc || !vc || !out) { cap_set_error("opt_beam_decode_attention: null pointer"); return -1; }
+    if (!anc && K > 1) { cap_set_error("opt_beam_decode_attention: %d beams need an ancestry table (null)", K); return -1; }
+    const float scale = 1.0f / sqrtf((float)hd);
+    // without a table (K == 1) every key is the row's own: the greedy kernel, whose caches are the same [rows][Lmax][T]
+    if (!anc) return launch_opt_decode_attention(dtype, qkv, kc, vc, out, B, T, H, Lmax, past, s, out_dtype);
+#define CAP_OBA(TT, H8, TO)                                                                                             \
+    hipLaunchKernelGGL((opt_beam_decode_attention_kernel<TT, H8, TO>), dim3(B * K * H), dim3(64), 0, s, (const TT*)qkv, (TT*)kc, \
+                       (TT*)vc, (TO*)out, T, H, hd, Lmax, past, scale, anc, anc_ld, K, P)
+    if (dtype == CAP_DT_BF16) {
+        if (hd == 80) CAP_OBA(bf16_t, 10, bf16_t); else if (hd == 64) CAP_OBA(bf16_t, 8, bf16_t); else if (hd == 128) CAP_OBA(bf16_t, 16, bf16_t); else CAP_OBA(bf16_t, 0, bf16_t);
+    } else if (out_dtype == CAP_DT_G8) {
+        if (hd == 80) CAP_OBA(float, 10, g8_t); else if (hd == 64) CAP_OBA(float, 8, g8_t); else if (hd == 128) CAP_OBA(float, 16, g8_t); else CAP_OBA(float, 0, g8_t);
+    } else {
+        if (hd == 80) CAP_OBA(float, 10, float); else if (hd == 64) CAP_OBA(float, 8, float); else if (hd == 128) CAP_OBA(float, 16, float); else CAP_OBA(float, 0, float);
+    }
+#undef CAP_OBA
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 int launch_opt_prefill_inputs(const float* proj, const float* tok, const float* pos, float* x, int B, int nq, int T, int bos,
                               hipStream_t s) {
     hipLaunchKernelGGL(opt_prefill_inputs_kernel, dim3(256), dim3(256), 0, s, proj, tok, pos, x, B, nq, T, bos);
@@ -1767,20 +1837,21 @@ int launch_opt_prefill_inputs(const float* proj, const float* tok, const float* 
     return 0;
 }
 int launch_opt_token_inputs(const int* seq, int seq_ld, int cur, const float* tok, const float* pos, float* x, int B, int T, int V,
-                            hipStream_t s) {
-    hipLaunchKernelGGL(opt_token_inputs_kernel, dim3(64), dim3(256), 0, s, seq, seq_ld, cur, tok, pos, x, B, T, V);
+                            hipStream_t s, int at) {
+    hipLaunchKernelGGL(opt_token_inputs_kernel, dim3(64), dim3(256), 0, s, seq, seq_ld, cur, at < 0 ? cur : at, tok, pos, x, B, T, V);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }
-int launch_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, hipStream_t s) {
-    if (B < 1 || L < 1 || T < 1 || pos0 < 0 || pos0 + L > Lmax || !qkv || !kc || !vc) {
+int launch_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, hipStream_t s,
+                     int row_stride) {
+    if (B < 1 || L < 1 || T < 1 || pos0 < 0 || pos0 + L > Lmax || row_stride < 1 || !qkv || !kc || !vc) {
         cap_set_error("kv_append: rows %d..%d do not fit a cache of %d positions (B=%d T=%d), or a null pointer", pos0, pos0 + L - 1, Lmax, B, T);
         return -1;
     }
     if (dtype == CAP_DT_BF16)
-        hipLaunchKernelGGL(kv_append_kernel<bf16_t>, dim3(256), dim3(256), 0, s, (const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, B, L, T, Lmax, pos0);
+        hipLaunchKernelGGL(kv_append_kernel<bf16_t>, dim3(256), dim3(256), 0, s, (const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, B, L, T, (size_t)Lmax * row_stride, pos0);
     else
-        hipLaunchKernelGGL(kv_append_kernel<float>, dim3(256), dim3(256), 0, s, (const float*)qkv, (float*)kc, (float*)vc, B, L, T, Lmax, pos0);
+        hipLaunchKernelGGL(kv_append_kernel<float>, dim3(256), dim3(256), 0, s, (const float*)qkv, (float*)kc, (float*)vc, B, L, T, (size_t)Lmax * row_stride, pos0);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -803,7 +803,8 @@ int build_blip2(Captioner* m) {
     if (m->gdt == CAP_DT_F32) m->o_tok_t = m->o_tok;
     else { TRY(walloc(m, &m->o_tok_t, (size_t)V * T * m->esz)); add_slot(m, lm + "embed_tokens.weight", m->o_tok_t, m->gdt, V, T); }
     TRY(reg_f32(m, lm + "embed_positions.weight", &m->o_pos, (int64_t)(c.max_pos + 2) * T));
-    const size_t Bm = c.max_batch, Lmax = nq + 1 + c.max_len;
+    // Rm: the decode step's rows (image x beam); the prompt pass runs over the Bm images whatever the beam count
+    const size_t Bm = c.max_batch, Rm = Bm * c.max_beams, Lmax = nq + 1 + c.max_len;
     m->ol.resize(c.t_layers);
     const char* pn[3] = {"q_proj", "k_proj", "v_proj"};
     for (int i = 0; i < c.t_layers; ++i) {
@@ -834,27 +835,28 @@ int build_blip2(Captioner* m) {
         TRY(reg_f32(m, p + "fc2.bias", &L.b_f2, T));
         TRY(reg_f32(m, p + "final_layer_norm.weight", &L.ln2_g, T));
         TRY(reg_f32(m, p + "final_layer_norm.bias", &L.ln2_b, T));
-        TRY(dev_alloc(m, &L.kc, Bm * Lmax * T * m->esz));
-        TRY(dev_alloc(m, &L.vc, Bm * Lmax * T * m->esz));
+        TRY(dev_alloc(m, &L.kc, Rm * Lmax * T * m->esz));
+        TRY(dev_alloc(m, &L.vc, Rm * Lmax * T * m->esz));
     }
     TRY(reg_f32(m, lm + "final_layer_norm.weight", &m->o_lnf_g, T));
     TRY(reg_f32(m, lm + "final_layer_norm.bias", &m->o_lnf_b, T));
 
     // arena
     const size_t NT = m->NT, M = Bm * NT, e = m->esz, P = nq + 1;
+    const size_t Ro = std::max(Bm * P, Rm);             // rows of the buffers the prompt pass and the step share
     TRY(alloc_image_tower(m));
     TRY(dev_alloc(m, (void**)&m->emb_f, M * D * 4));
     TRY(dev_alloc(m, &m->emb_t, M * D * e));
     TRY(alloc_post_rows(m, m->qr, Bm * nq, Q, F));
     TRY(dev_alloc(m, &m->qkvimg, M * 2 * Q * e));
     TRY(dev_alloc(m, (void**)&m->lm_proj, Bm * nq * T * 4));
-    TRY(dev_alloc(m, (void**)&m->ox, Bm * P * T * 4));
-    TRY(dev_alloc(m, &m->oh_t, Bm * P * T * e));
-    TRY(dev_alloc(m, &m->oqkv, Bm * P * 3 * T * e));
-    TRY(dev_alloc(m, &m->octx, Bm * P * T * e));
-    TRY(dev_alloc(m, &m->off, Bm * P * G * e));
+    TRY(dev_alloc(m, (void**)&m->ox, Ro * T * 4));
+    TRY(dev_alloc(m, &m->oh_t, Ro * T * e));
+    TRY(dev_alloc(m, &m->oqkv, Ro * 3 * T * e));
+    TRY(dev_alloc(m, &m->octx, Ro * T * e));
+    TRY(dev_alloc(m, &m->off, Ro * G * e));
     {
-        size_t dpart_bytes = (size_t)8 * Bm * std::max(3 * T, G) * 4;                     // split-K slabs of the decode-step GEMMs
+        size_t dpart_bytes = (size_t)8 * Rm * std::max(3 * T, G) * 4;                     // split-K slabs of the decode-step GEMMs
         if (m->wq8) {                                   // int8 weights: the prompt pass runs the same chain over Bm * P rows
             const size_t Sm = (size_t)std::max(skinny_i8_plan(T, T, false), skinny_i8_plan(T, G, false));
             dpart_bytes = std::max(dpart_bytes, Sm * std::min<size_t>(Bm, kI8SkinnyPromptCrops) * P * T * 4);
@@ -869,7 +871,11 @@ int build_blip2(Captioner* m) {
     TRY(dev_alloc(m, (void**)&m->finished, Bm * 4));
     TRY(dev_alloc(m, (void**)&m->lens, Bm * 4));
     m->ldl = (V + 3) & ~3;
-    TRY(dev_alloc(m, (void**)&m->logits, Bm * (size_t)m->ldl * 4));
+    TRY(dev_alloc(m, (void**)&m->logits, Rm * (size_t)m->ldl * 4));
+    if (c.max_beams > 1) {      // beam search (beam.hip): BOS + max_len token columns per row
+        TRY(dev_alloc(m, (void**)&m->anc, 2 * Rm * (c.max_len + 1) * 4));
+        TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, c.max_len + 1)));
+    }
     return 0;
 }
 
@@ -1045,13 +1051,20 @@ int opt_gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, const 
 // Self-attention of one layer over the fused q|k|v rows in oqkv -> octx, the new K/V rows into the layer's caches.  The prompt
 // (L positions, nothing cached): causal attention over the rows themselves (MFMA kernel for bf16 heads wider than 64).  A step
 // (L == 1): the new position against the `past` cached ones.
-int opt_attention(Captioner* m, const OLayer& Ly, int B, int L, int past, hipStream_t s) {
+// A beam search (bm): the caches are those of B x K rows, row = image * K + beam.  Its prompt pass runs over the B images and leaves
+// image b's positions in the cache of row b * K, for the K rows of the image; its steps run over the B * K rows, each reading the
+// generated positions from the rows its ancestry table names (opt_beam_decode_attention).
+struct OptBeams { int K; const int* anc; int anc_ld; };      // anc [B * K, anc_ld]: the step's table, from the first generated position on
+int opt_attention(Captioner* m, const OLayer& Ly, int B, int L, int past, hipStream_t s, const OptBeams* bm) {
     const CapConfig& c = m->c;
-    const int T = c.t_hidden, H = c.t_heads, hd = T / H, Lmax = c.num_query_tokens + 1 + c.max_len;
+    const int T = c.t_hidden, H = c.t_heads, hd = T / H, P = c.num_query_tokens + 1, Lmax = P + c.max_len;
     if (L > 1 && past != 0) { cap_set_error("opt_attention: %d new positions behind a cached prefix (%d) are not built", L, past); return -1; }
-    if (L > 1) TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, L, T, Lmax, 0, s));
+    if (L > 1) TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, L, T, Lmax, 0, s, bm ? bm->K : 1));
     ProfScope ps(m, s, "opt_attn", 4.0 * B * H * (double)L * (past + L) * hd, 2.0 * B * (past + L) * T * m->esz);
     if (L > 1) return launch_vit_attention(m->dt, m->oqkv, m->octx, B, L, H, 0, s, hd, 1, m->gdt);
+    if (bm)     // (cap_create holds BLIP-2's head widths to what the kernel takes)
+        return launch_opt_beam_decode_attention(m->dt, m->oqkv, Ly.kc, Ly.vc, m->octx, B / bm->K, bm->K, T, H, Lmax, P, past, bm->anc,
+                                                bm->anc_ld, s, m->gdt);
     if (hd % 8 == 0 && hd <= 128) return launch_opt_decode_attention(m->dt, m->oqkv, Ly.kc, Ly.vc, m->octx, B, T, H, Lmax, past, s, m->gdt);
     TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, 1, T, Lmax, past, s));
     return launch_generic_attention(m->dt, m->oqkv, 3 * T, 3 * T, Ly.kc, T, (long)Lmax * T, Ly.vc, T, (long)Lmax * T, m->octx, T, T, B, 1, past + 1,
@@ -1064,7 +1077,8 @@ int opt_attention(Captioner* m, const OLayer& Ly, int B, int L, int past, hipStr
 // through the step's weight streams (a one-crop prompt is 33 rows: a weight stream too), beyond through the tiled GEMM.  The
 // consumers finish the projections' sums - bias (+ ReLU) -> T for q|k|v and fc1; bias + residual + the NEXT LayerNorm (the
 // final one on the last layer, over every row) for out_proj and fc2.
-int run_opt(Captioner* m, int B, int L, int past, hipStream_t s) {
+// bm: the rows are a beam search's (opt_attention); its prompt pass leaves image b's logits in row b * K of m->logits.
+int run_opt(Captioner* m, int B, int L, int past, hipStream_t s, const OptBeams* bm = nullptr) {
     const CapConfig& c = m->c;
     const int T = c.t_hidden, G = c.t_ffn, R = B * L;
     const bool tiled = L > 1 && B > kI8SkinnyPromptCrops;
@@ -1073,7 +1087,7 @@ int run_opt(Captioner* m, int B, int L, int past, hipStream_t s) {
         const OLayer& Ly = m->ol[i];
         const bool last = i + 1 == c.t_layers;
         TRY(opt_gemm(m, s, "opt_gemm_qkv", m->oh_t, Ly.w_qkv, Ly.b_qkv, 0, m->oqkv, R, 3 * T, T, false, &S, m->dt, Ly.s_qkv, tiled));
-        TRY(opt_attention(m, Ly, B, L, past, s));
+        TRY(opt_attention(m, Ly, B, L, past, s, bm));
         TRY(opt_gemm(m, s, "opt_gemm_o", m->octx, Ly.w_o, nullptr, 0, nullptr, R, T, T, true, &S, m->gdt, Ly.s_o, tiled));
         TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_o, m->ox, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
         TRY(opt_gemm(m, s, "opt_gemm_f1", m->oh_t, Ly.w_f1, Ly.b_f1, 2, m->off, R, G, T, false, &S, m->gdt, Ly.s_f1, tiled));
@@ -1081,31 +1095,86 @@ int run_opt(Captioner* m, int B, int L, int past, hipStream_t s) {
         TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_f2, m->ox, last ? m->o_lnf_g : m->ol[i + 1].ln1_g,
                                     last ? m->o_lnf_b : m->ol[i + 1].ln1_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
     }
-    return gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)(L - 1) * T * m->esz, L * T, m->o_tok_t, T, m->logits, m->ldl, nullptr,
-                nullptr, B, c.vocab, T, 0, 1);
+    return gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)(L - 1) * T * m->esz, L * T, m->o_tok_t, T, m->logits,
+                (bm && L > 1 ? bm->K : 1) * m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
 }
 
 // The prompt pass with plain weights (f32 / f32s / bf16): B * L rows are GEMMs proper, so bias and residual ride the tiled GEMM's
 // epilogue, every sub-block opens with its own LayerNorm, and the final one covers each row's last position only.
-int run_opt_prompt_plain(Captioner* m, int B, int L, hipStream_t s) {
+int run_opt_prompt_plain(Captioner* m, int B, int L, hipStream_t s, const OptBeams* bm = nullptr) {
     const CapConfig& c = m->c;
     const int T = c.t_hidden, G = c.t_ffn, R = B * L;
     const int af = m->gdt == CAP_DT_G8 ? 1 : 0;     // split mode: q | k | v for the attention kernels and the caches are fp32
     for (const OLayer& Ly : m->ol) {
         TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln1_g, Ly.ln1_b, c.t_eps, m->oh_t, nullptr, R, T, s));
         TRY(gemm(m, s, "opt_gemm_qkv", m->oh_t, T, Ly.w_qkv, T, m->oqkv, 3 * T, Ly.b_qkv, nullptr, R, 3 * T, T, 0, af));
-        TRY(opt_attention(m, Ly, B, L, 0, s));
+        TRY(opt_attention(m, Ly, B, L, 0, s, bm));
         TRY(gemm(m, s, "opt_gemm_o", m->octx, T, Ly.w_o, T, m->ox, T, Ly.b_o, m->ox, R, T, T, 0, 1));
         TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, R, T, s));
         TRY(gemm(m, s, "opt_gemm_f1", m->oh_t, T, Ly.w_f1, T, m->off, G, Ly.b_f1, nullptr, R, G, T, 2, 0));
         TRY(gemm(m, s, "opt_gemm_f2", m->off, G, Ly.w_f2, G, m->ox, T, Ly.b_f2, m->ox, R, T, G, 0, 1));
     }
     TRY(launch_layernorm(m->gdt, m->ox + (size_t)(L - 1) * T, L * T, m->o_lnf_g, m->o_lnf_b, c.t_eps, m->oh_t, nullptr, B, T, s));
-    return gemm(m, s, "opt_gemm_vocab", m->oh_t, T, m->o_tok_t, T, m->logits, m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
+    return gemm(m, s, "opt_gemm_vocab", m->oh_t, T, m->o_tok_t, T, m->logits, (bm ? bm->K : 1) * m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
+}
+
+// row b * K of logits [B * K, ld] -> the other K - 1 rows of image b
+__global__ void beam_rows_from_first_kernel(float* logits, int ld, int B, int K, int V) {
+    const size_t n = (size_t)B * (K - 1) * V;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / V, c = i - r * V, b = r / (K - 1), k = 1 + r % (K - 1);
+        logits[(b * K + k) * ld + c] = logits[b * K * ld + c];
+    }
+}
+__global__ void iota_rows_kernel(int* anc, int R, int L);
+
+// The beam search behind the prompt pass (HF `_beam_search` under Blip2ForConditionalGeneration.generate(num_beams = K)): the prompt
+// pass ran once per IMAGE and left its positions in the caches of rows b * K and its logits in rows b * K of m->logits; HF runs it on
+// K identical rows per image, so step 0 takes K copies of those logits (beam.hip starts beams 1 .. K - 1 at -1e9).
+// The bookkeeping is beam.hip's in HF-v5 mode over max_len + 1 token columns, column 0 = BOS.  HF subtracts decoder_prompt_len (the
+// query tokens + BOS) from every length it uses: its length penalty's cur_len + 1 - prompt and its early-stop heuristic's
+// max_length - prompt count new tokens, and so does beam.hip's cur_len + 1 - 1 with BOS as the only column ahead of them (pinned by
+// tests/golden/blip2_tiny_beam.npz).  Column c's token is sequence position P - 1 + c; the ancestry table's entry c names the row
+// that wrote that position, so the attention takes the table from column 1 (the first generated position, P) on.
+int run_beams_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int B = a.B, K = a.num_beams, R = B * K, max_len = a.max_len, Lb = max_len + 1;
+    const int T = c.t_hidden, P = c.num_query_tokens + 1;
+    TRY(launch_beam_init(m->beam, B, K, Lb, c.bos, c.pad, c.eos, s, BEAM_HF_V5));
+    hipLaunchKernelGGL(iota_rows_kernel, dim3(64), dim3(256), 0, s, m->anc, R, Lb);
+    hipLaunchKernelGGL(beam_rows_from_first_kernel, dim3(256), dim3(256), 0, s, m->logits, m->ldl, B, K, c.vocab);
+    CAP_HIP_CHECK(hipGetLastError());
+    for (int t = 0; t < max_len; ++t) {
+        const int cur_len = t + 1, nxt = (cur_len & 1) ^ 1;      // the step fills column cur_len and leaves its state in parity nxt
+        m->last_steps = t + 1;
+        TRY(copy_step_logits(m, a, R, t, s));
+        {
+            ProfScope ps(m, s, "beam_step", 0, (double)R * c.vocab * 4);
+            TRY(launch_beam_step(m->beam, m->logits, m->ldl, c.vocab, B, K, Lb, cur_len, c.eos, a.length_penalty, m->anc, Lb, s, BEAM_HF_V5, 0));
+        }
+        if (t + 1 == max_len) break;
+        {
+            bool done;
+            TRY(poll_all_finished(m, t, max_len, nullptr, R, beam_active_flag_p(m->beam, B, K, Lb), s, &done));
+            if (done) break;
+        }
+        const OptBeams step = {K, m->anc + (size_t)nxt * R * Lb + 1, Lb};
+        TRY(launch_opt_token_inputs(beam_running_tokens_p(m->beam, B, K, Lb, nxt), Lb, cur_len, m->o_tok, m->o_pos, m->ox, R, T, c.vocab, s,
+                                    P - 1 + cur_len));
+        TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, R, T, s));
+        TRY(run_opt(m, R, 1, P - 1 + cur_len, s, &step));
+    }
+    // the best hypothesis of every image with its BOS column, then the new tokens alone as the greedy loop returns them
+    TRY(launch_beam_finalize(m->beam, B, K, Lb, m->seq, m->lens, a.out_scores, s));
+    hipLaunchKernelGGL(copy_new_tokens_kernel, dim3(64), dim3(256), 0, s, m->seq, Lb, 1, m->lens, a.out_ids, a.out_len, B, max_len);
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 // HF Blip2ForConditionalGeneration.generate, greedy: out_ids [B, max_len] = the new tokens (pad after EOS), out_len [B] =
 // their count incl. EOS, out_step_logits [max_len, B, vocab]; the optional greedy outputs have max_len columns.
+// num_beams > 1: the same front half over the B images, then run_beams_blip2 (out_scores = sequences_scores, out_step_logits
+// [max_len, B * num_beams, vocab]).
 int run_generate_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
     const CapConfig& c = m->c;
     const int B = a.B, max_len = a.max_len;
@@ -1115,14 +1184,20 @@ int run_generate_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
     TRY(run_qformer(m, kCaptionPass, B, nq, 0, nullptr, nullptr, s));
     TRY(gemm(m, s, "b2_gemm_lproj", m->qr.x_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1));
     TRY(launch_opt_prefill_inputs(m->lm_proj, m->o_tok, m->o_pos, m->ox, B, nq, T, c.bos, s));
-    hipLaunchKernelGGL(init_seq_kernel, dim3(64), dim3(256), 0, s, m->seq, m->finished, m->lens, B, Lmax, c.bos, c.pad);
-    CAP_HIP_CHECK(hipGetLastError());
+    const int K = a.num_beams;
+    const OptBeams prompt_beams = {K, nullptr, 0};
+    const OptBeams* pb = K > 1 ? &prompt_beams : nullptr;
+    if (!pb) {
+        hipLaunchKernelGGL(init_seq_kernel, dim3(64), dim3(256), 0, s, m->seq, m->finished, m->lens, B, Lmax, c.bos, c.pad);
+        CAP_HIP_CHECK(hipGetLastError());
+    }
     if (m->wq8) {
         TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B * P, T, s));
-        TRY(run_opt(m, B, P, 0, s));
+        TRY(run_opt(m, B, P, 0, s, pb));
     } else {
-        TRY(run_opt_prompt_plain(m, B, P, s));
+        TRY(run_opt_prompt_plain(m, B, P, s, pb));
     }
+    if (pb) return run_beams_blip2(m, a, s);
     for (int t = 0; t < max_len; ++t) {
         m->last_steps = t + 1;
         // token of position P + t; a row finishes on EOS or at P + max_len tokens (greedy_select's `t` is the last filled index)
@@ -1871,10 +1946,10 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
         if (!hd_ok(cfg->v_hidden, cfg->v_heads) || !hd_ok(cfg->q_hidden, cfg->q_heads) || !hd_ok(cfg->t_hidden, cfg->t_heads) ||
             cfg->v_hidden % 64 || cfg->v_mlp % 64 || cfg->q_hidden % 64 || cfg->q_ffn % 64 || cfg->t_hidden % 64 || cfg->t_ffn % 64 ||
             cfg->t_hidden > 256 * 12 || cfg->image_size % cfg->patch_size || cfg->q_layers < 1 || cfg->q_cross_freq < 1 ||
-            cfg->num_query_tokens < 1 || cfg->max_batch < 1 || cfg->max_beams != 1 || cfg->max_len < 1 ||
+            cfg->num_query_tokens < 1 || cfg->max_batch < 1 || cfg->max_beams < 1 || cfg->max_beams > 8 || cfg->max_len < 1 ||
             cfg->num_query_tokens + 1 + cfg->max_len > cfg->max_pos) {
             cap_set_error("cap_create: BLIP-2 needs head dims that are multiples of 8 (<= 128), widths multiple of 64 (OPT hidden <= 3072), "
-                          "max_beams 1 and num_query_tokens + 1 + max_len <= max_pos");
+                          "1 <= max_beams <= 8 and num_query_tokens + 1 + max_len <= max_pos");
             return -1;
         }
         if (cfg->num_query_tokens + 1 + cfg->max_len > OPT_DECODE_MAX_KEYS) {      // launch_opt_decode_attention's limit: refused here, not mid-generation
@@ -2255,7 +2330,6 @@ static int validate_generate(Captioner* m, const CapGenerateArgs& a, const char*
     REFUSE_IF(G && c.arch != CAP_ARCH_COCA,
               "%s: beam groups are the CoCa loop's (coca_model.py:335-482); HF's group beam search for the other architectures needs a "
               "diversity penalty, which this library does not implement", who);
-    REFUSE_IF(c.arch == CAP_ARCH_BLIP2 && K != 1, "%s: BLIP-2 supports greedy decoding (num_beams = 1)", who);
     REFUSE_IF(G < 0 || G > K || (G && K % G != 0), "%s: num_beams (%d) must be a multiple of num_beam_groups (%d) (BeamSearchScorer's own check)",
               who, K, G);
     REFUSE_IF(G && a.out_step_logits, "%s: per-step logits are not recorded by the group beam search", who);
@@ -2459,6 +2533,11 @@ int cap_op_attention(int dtype, const void* q, int64_t ldq, int64_t qbs, const v
 int cap_op_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int T, int H, int Lmax, int past,
                                 void* stream) {
     return launch_opt_decode_attention(in_dt_of(dtype), qkv, kc, vc, out, B, T, H, Lmax, past, (hipStream_t)stream, dt_of(dtype));
+}
+int cap_op_opt_beam_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int K, int T, int H, int Lmax, int P,
+                                     int past, const int32_t* anc, int anc_ld, void* stream) {
+    return launch_opt_beam_decode_attention(in_dt_of(dtype), qkv, kc, vc, out, B, K, T, H, Lmax, P, past, anc, anc_ld, (hipStream_t)stream,
+                                            dt_of(dtype));
 }
 int cap_op_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, void* stream) {
     return launch_kv_append(in_dt_of(dtype), qkv, kc, vc, B, L, T, Lmax, pos0, (hipStream_t)stream);

@@ -378,7 +378,8 @@ class CaptionerEngine:
         Returns device tensors: sequences int32 [B, max_length] (incl. BOS), lengths int32 [B],
         sequences_scores fp32 [B] (beams only), logits fp32 [max_length-1, B*num_beams, vocab] (optional).
         BLIP-2: max_length counts NEW tokens (HF max_new_tokens); sequences are those new tokens only (no image
-        placeholders / BOS), logits [max_length, B, vocab].
+        placeholders / BOS), logits [max_length, B*num_beams, vocab]; num_beams > 1 as for BLIP (HF's search behind a prompt pass
+        that runs once per image: step 0's rows of an image are copies).
         output_logprobs (greedy): token_logprobs fp32 [B, steps] = log max softmax of every step's logits row as the selection saw
         it (steps as for logits), zero from the caption's end on, and scored_steps int32 [B] = valid entries per row - taken by the
         selection kernel itself (cap_generate_scored): any batch size, no logits buffer, same kernels otherwise;

@@ -221,7 +221,10 @@ typedef struct CapGenerateArgs {
     int32_t pixel_fmt;         /* CAP_PIX_F32_NCHW | CAP_PIX_U8_NHWC */
     int32_t B;
     int32_t num_beams;         /* 1: greedy (HF `_sample` with do_sample=False; CoCa: the reference's top-k(1) loop, coca.py:29); > 1: HF v5 beam
-                                  search (CoCa: its `_generate_beamsearch`, coca_model.py:335-482).  CAP_ARCH_BLIP2: 1 only */
+                                  search (CoCa: its `_generate_beamsearch`, coca_model.py:335-482).  CAP_ARCH_BLIP2: the same search behind the
+                                  prompt pass, which runs once per IMAGE - the K rows of an image share its cached prompt positions;
+                                  max_len counts new tokens, out_ids / out_len are the new tokens of the best hypothesis, out_step_logits
+                                  [max_len, B * num_beams, vocab] (step 0: K copies of the image's prompt logits) */
     int32_t num_beam_groups;   /* 0: not a group search.  >= 1 (CAP_ARCH_COCA only): CoCa's `_generate_beamsearch` with beam GROUPS (`generate()`
                                   defaults num_beams = 6, num_beam_groups = 3, coca_model.py:218-219): num_beams % num_beam_groups == 0, each group
                                   a beam search of num_beams / num_beam_groups beams, the best hypothesis over an image's groups returned.  The
@@ -406,6 +409,13 @@ int cap_op_attention(int dtype, const void* q, int64_t ldq, int64_t qbs, const v
  * of 8 up to 128, past < min(Lmax, 1024). */
 int cap_op_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int T, int H, int Lmax, int past,
                                 void* stream);
+/* The same step for the B * K rows of a beam search, row r = image * K + beam, over caches kc / vc [B * K][Lmax][T]: positions below P
+ * (the prompt) are read from the cache of row image * K, position P + g (g < past - P) from the cache of row anc[r * anc_ld + g]
+ * (clamped into the image's rows), and the row's own k | v are written to ITS cache at position past.  anc may be null for K = 1
+ * (every position the row's own).  1 <= K <= 8, 0 <= P <= past, anc_ld >= past - P.  Same sums in the same order as
+ * cap_op_opt_decode_attention: a row with the same history gives the same bits. */
+int cap_op_opt_beam_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int K, int T, int H, int Lmax, int P,
+                                     int past, const int32_t* anc, int anc_ld, void* stream);
 /* k | v columns of fused rows qkv [B * L, 3 T] -> caches kc / vc [B][Lmax][T] at positions pos0 .. pos0 + L - 1 (CAP_F32_SPLIT: fp32). */
 int cap_op_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, void* stream);
 /* The kernels that run once per prompt pass, alone (tests/test_prefill_kernels_gpu.py).  One kernel (or kernel pair) each.

@@ -3,6 +3,13 @@
 
     python tools/summarize_prof.py stats  <dir with *_kernel_stats.csv>  profiles/rNN_kernel_stats.md
     python tools/summarize_prof.py pmc    <dir of pmc passes>            profiles/rNN_pmc.json
+    python tools/summarize_prof.py steps  <dir with *_results.db>  profiles/x.md  <anchor kernel>  <anchor launches per call>
+
+`steps` reads the database a rocprofv3 kernel trace leaves (its `kernels` view: one row per dispatch, start / end in ns) and
+tabulates the decode steps of the LAST call of the traced program alone: the dispatches from the first of the call's anchor
+launches (a kernel that only the decode steps run, e.g. the step's attention: layers x steps launches per call) to the end of the
+trace.  Weight loading, the image side and the prompt pass lie before that window; so do the three launches of the first step that
+precede its first attention (token inputs, LayerNorm, layer 0's q|k|v projection).
 
 `pmc` aggregates per kernel name: launches, average duration and every counter's per-launch average; FETCH_SIZE is
 also reported corrected (x2: gfx950 tallies 128-byte requests at 64 B - MI355X_MICROARCH.md §HBM) in bytes."""
@@ -32,6 +39,27 @@ def stats(src, dst):
     print("wrote", dst)
 
 
+def steps(src, dst, anchor, per_call):
+    import sqlite3
+    f = sorted(glob.glob(os.path.join(src, "**", "*_results.db"), recursive=True))[0]
+    rows = list(sqlite3.connect(f).execute("select name, start, end from kernels order by start"))
+    at = [i for i, r in enumerate(rows) if anchor in r[0]]
+    assert len(at) >= int(per_call), f"{len(at)} launches of {anchor}, fewer than one call's {per_call}"
+    win = rows[at[-int(per_call)]:]
+    agg = collections.defaultdict(lambda: [0, 0])
+    for name, t0, t1 in win:
+        agg[short(name)][0] += 1
+        agg[short(name)][1] += t1 - t0
+    tot = sum(v[1] for v in agg.values())
+    with open(dst, "w") as o:
+        o.write(f"# the decode steps of one call: rocprofv3 --kernel-trace, dispatches from the call's first `{anchor}` launch on\n\n")
+        o.write(f"{len(win)} dispatches, kernel time {tot / 1e6:.3f} ms, wall {(win[-1][2] - win[0][1]) / 1e6:.3f} ms\n\n")
+        o.write("| kernel | calls | total ms | avg us | % |\n|---|---:|---:|---:|---:|\n")
+        for k, (n, t) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
+            o.write(f"| `{k}` | {n} | {t / 1e6:.3f} | {t / n / 1e3:.2f} | {100.0 * t / tot:.2f} |\n")
+    print("wrote", dst)
+
+
 def pmc(src, dst):
     agg = collections.defaultdict(lambda: collections.defaultdict(list))
     dur = collections.defaultdict(list)
@@ -58,4 +86,4 @@ def pmc(src, dst):
 
 
 if __name__ == "__main__":
-    {"stats": stats, "pmc": pmc}[sys.argv[1]](sys.argv[2], sys.argv[3])
+    {"stats": stats, "pmc": pmc, "steps": steps}[sys.argv[1]](*sys.argv[2:])
