@@ -7,6 +7,7 @@ and HF ``GenerationMixin.generate`` behind ``blip2.py:26``.  What the library ru
 (HF v5 semantics for BLIP / BLIP-2, the reference's ``_generate_beamsearch`` incl. beam groups for CoCa).  Everything below is
 deterministic arg-max / beam arithmetic (``captioner.num_beams`` and, for BLIP and BLIP-2, ``captioner.length_penalty`` are the config keys;
 BLIP-2 searches with 1 to 8 beams like the other families and computes the prompt once per image, not once per beam); sampling, temperature, nucleus / top-k filtering and repetition penalties are not built.
+Scoring a GIVEN caption (teacher forcing: ``CaptionerEngine.score`` / ``BLIP.score_captions`` / ``BLIP2.score_captions``) is a separate entry point, not a generation option or a prompt: plain logits, no EOS mask or MinLength.
 """
 from __future__ import annotations
 

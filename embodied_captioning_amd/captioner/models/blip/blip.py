@@ -108,7 +108,8 @@ class BLIP(CaptioningPredictor):
             logger.info("Captioner model checkpoint loaded successfully from %s", cfg.checkpoint_name)
         self.engine = CaptionerEngine(self.arch, dtype=dtype, max_batch=self.batch_size, max_beams=self.num_beams,
                                       max_len=self.max_length, device=self._device,
-                                      cross_cache=self._cross_cache_for(cfg, sd, dtype), max_prompt=self.max_prompt)
+                                      cross_cache=self._cross_cache_for(cfg, sd, dtype), max_prompt=self.max_prompt,
+                                      max_score_rows=int(getattr(cfg, "max_score_rows", None) or 0))
         # HF generate stops once every caption has its EOS; look every few steps (cfg early_exit_poll, 0 = never)
         poll = getattr(cfg, "early_exit_poll", None)
         poll = 4 if poll is None else int(poll)
@@ -295,6 +296,55 @@ class BLIP(CaptioningPredictor):
             if not output_perplexity:
                 res["token_logprobs"] = torch.cat([o["token_logprobs"] for o in outs]).cpu()
                 res["scored_steps"] = torch.cat([o["scored_steps"] for o in outs]).cpu()
+        return res
+
+    def caption_ids(self, caption) -> List[int]:
+        """One caption as the decoder's tokens for scoring: a string goes through the checkpoint's tokenizer (`[CLS] words [SEP]`)
+        with BOS in place of [CLS] and the closing [SEP] kept, so the end of the caption is scored; a list of token ids (models
+        without a tokenizer) is taken as it is, BOS put in front when it does not start with it."""
+        if isinstance(caption, str):
+            if self.tokenizer is None:
+                raise ValueError("score_captions: a caption string needs a tokenizer and this model has none (a procedural model, or a "
+                                 "checkpoint directory without tokenizer files): give lists of token ids")
+            ids = [int(i) for i in self.tokenizer(caption, add_special_tokens=True)["input_ids"]]
+            return [int(self.arch.bos)] + ids[1:]
+        ids = [int(i) for i in caption]
+        return ids if ids and ids[0] == self.arch.bos else [int(self.arch.bos)] + ids
+
+    @torch.no_grad()
+    def score_captions(self, images, captions) -> dict:
+        """Teacher-forced likelihood of GIVEN captions under this captioner (`CaptionerEngine.score`; HF `model(pixel_values,
+        input_ids=...)` reduced to log-probs).  captions: one per image (strings, or token-id lists for models without a tokenizer),
+        or a list of candidates per image (a list of lists; images may have different numbers of candidates).
+        -> host tensors, caption-major ([image 0's candidates, image 1's, ...], images with fewer candidates padded with absent
+        slots): "token_logprobs" fp32 [N, L - 1], "n_tokens" int64 [N] (scored tokens: the caption's without BOS; 0 = absent slot),
+        "logprob_sum" / "logprob_mean" / "perplexity" (exp(-mean) of the given tokens) / "top_perplexity" (the reference's max-softmax
+        form on the same rows) float64 [N] (nan for absent slots), "top_ids" int32 [N, L - 1], "captions_per_image" int.  Captions
+        longer than the engine takes (`engine.score_limit`) are refused; scoring longer than batch_size x num_beams tokens needs
+        captioner.max_score_rows."""
+        from ....engine import score_summary
+        captions = list(captions)
+        nested = bool(captions) and all(isinstance(c, (list, tuple)) and (len(c) == 0 or isinstance(c[0], (str, list, tuple))) for c in captions)
+        groups = [list(c) for c in captions] if nested else [[c] for c in captions]
+        px = self.preprocess(images)
+        if int(px.shape[0]) != len(groups):
+            raise ValueError(f"score_captions: {int(px.shape[0])} images but {len(groups)} captions / candidate lists")
+        Cn = max((len(g) for g in groups), default=0)
+        if Cn < 1:
+            raise ValueError("score_captions: no caption to score")
+        rows = [[self.caption_ids(c) for c in g] for g in groups]
+        L = max(2, max(len(r) for g in rows for r in g))
+        ids = np.full((len(groups) * Cn, L), self.arch.pad, dtype=np.int32)
+        lens = np.zeros(len(groups) * Cn, dtype=np.int32)
+        for b, g in enumerate(rows):
+            for c, r in enumerate(g):
+                ids[b * Cn + c, : len(r)] = r
+                lens[b * Cn + c] = len(r)
+        out = self.engine.score(px.to(self._device), ids, lens, captions_per_image=Cn)
+        self._range_tick()
+        res = {"token_logprobs": out["token_logprobs"].cpu(), "top_logprobs": out["top_logprobs"].cpu(), "top_ids": out["top_ids"].cpu(),
+               "captions_per_image": Cn}
+        res.update(score_summary(res["token_logprobs"], res["top_logprobs"], out["scored"]))
         return res
 
     @torch.no_grad()

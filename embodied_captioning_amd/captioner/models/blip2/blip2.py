@@ -194,6 +194,19 @@ class BLIP2(BLIP):
         a = self.arch
         return " ".join(str(i) for i in ids if i not in (a.bos, a.eos, a.pad))
 
+    def caption_ids(self, caption) -> List[int]:
+        """One caption as OPT's tokens for scoring (BLIP.score_captions): BOS + the tokenizer's tokens + the generation EOS, so the end of
+        the caption is scored as `generate` would have ended it; a list of token ids (models without a tokenizer) is taken as it is,
+        BOS put in front when it does not start with it."""
+        if isinstance(caption, str):
+            if self.tokenizer is None:
+                raise ValueError("score_captions: a caption string needs a tokenizer and this model has none (a procedural model, or a "
+                                 "checkpoint directory without tokenizer files): give lists of token ids")
+            ids = [int(i) for i in self.tokenizer(caption, add_special_tokens=False)["input_ids"]]
+            return [int(self.arch.bos)] + ids + [int(self.arch.eos)]
+        ids = [int(i) for i in caption]
+        return ids if ids and ids[0] == self.arch.bos else [int(self.arch.bos)] + ids
+
     @torch.no_grad()
     def forward(self, inputs):
         if not hasattr(self.arch, "num_query_tokens"):

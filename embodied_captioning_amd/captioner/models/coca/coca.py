@@ -242,6 +242,10 @@ class CoCa(CaptioningPredictor):
                 res["scored_steps"] = torch.cat([o["scored_steps"] for o in outs]).cpu()
         return res
 
+    def score_captions(self, images, captions) -> dict:
+        """Scoring given captions is built for BLIP; CoCa refuses by name."""
+        raise ValueError("score_captions: scoring given captions is not built for CoCa; it is BLIP's (arch_name 'blip')")
+
     @torch.no_grad()
     def forward(self, inputs):
         a = self.arch

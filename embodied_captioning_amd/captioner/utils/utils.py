@@ -27,7 +27,8 @@ class CaptionerField:
                  early_exit_poll=None, max_new_tokens=None, num_beam_groups=None, tokenizer_dir=None,
                  generation_type=None, top_k=None, top_p=None, temperature=None, repetition_penalty=None,
                  load_in_8bit=None, load_in_4bit=None, torch_dtype=None, cross_cache=None, strict_range=False,
-                 coalesce_rows=None, device_resize=None, prompt=None, prompt_ids=None, max_prompt=None, length_penalty=None):
+                 coalesce_rows=None, device_resize=None, prompt=None, prompt_ids=None, max_prompt=None, length_penalty=None,
+                 max_score_rows=None):
         self.arch_name = arch_name
         self.model_name = model_name
         self.checkpoint_name = checkpoint_name
@@ -73,3 +74,6 @@ class CaptionerField:
         self.prompt = prompt
         self.prompt_ids = prompt_ids
         self.max_prompt = max_prompt
+        # BLIP: scoring capacity of the arena in decoder rows (`score_captions`: captions x (tokens - 1) per pass); None / 0 = none
+        # reserved - captions of up to batch_size x num_beams + 1 tokens are scored in passes of what the decode rows hold
+        self.max_score_rows = max_score_rows

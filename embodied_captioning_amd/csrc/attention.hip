@@ -1250,6 +1250,111 @@ __global__ __launch_bounds__(64) void opt_beam_decode_attention_kernel(const T* 
     opt_decode_attention_body<T, HD8, TO, true>(qkv, kc, vc, out, Tw, H, hd, Lmax, past, scale, anc, anc_ld, K, P);
 }
 
+// Teacher-forced scoring (cap_score_captions, BLIP-2): self-attention of n NEW positions per caption behind an image's cached prompt.
+// Rows are caption-major, r = caption * n + t, fused q|k|v rows [rows, 3 Tw]; local caption cl = r / n is caption cap0 + cl of the
+// request and belongs to image (cap0 + cl) / C.  The keys of row (cl, t) come from two sources: j < P from the image's cache row
+// (kc / vc [image][Lmax][Tw], what the prompt pass wrote), then the caption's own positions 0 .. t straight from the pass's rows
+// cl * n + (j - P) - nothing is appended to the caches, so any number of captions score against one image's prompt.  n_pos (optional):
+// rows with t >= n_pos[cap0 + cl] are left untouched (behind the caption's end; an absent slot has 0).
+// One wave per (row, head), opt_decode_attention_body's walk: lanes over keys for the scores (HD8 16-byte loads of a key row issued
+// before the first FMA), softmax through LDS, then (key group of 4) x (8-dim chunk) for P.V with a 4-way sum - the same sums in the same
+// order as the decode step with past = P + t, so a caption scored here and decoded token by token see the same bits.
+template <typename T, int HD8, typename TO>
+__global__ __launch_bounds__(64) void opt_prefix_attention_kernel(const T* __restrict__ qkv, const T* __restrict__ kc, const T* __restrict__ vc,
+                                                                  TO* __restrict__ out, int Tw, int H, int hd, int Lmax, int P, int n,
+                                                                  int cap0, int C, const int* __restrict__ n_pos, float scale) {
+    __shared__ float qs[128], ps[OPT_DECODE_MAX_KEYS], os[4][128];
+    const int r = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x;
+    const int cl = r / n, t = r - cl * n, img = (cap0 + cl) / C;
+    if (n_pos && t >= n_pos[cap0 + cl]) return;            // uniform over the block: before any barrier
+    const T* row = qkv + (size_t)r * 3 * Tw + h * hd;
+    const T* own = qkv + (size_t)cl * n * 3 * Tw + h * hd;  // position 0 of this caption in the pass
+    const T* kb = kc + (size_t)img * Lmax * Tw + h * hd;
+    const T* vb = vc + (size_t)img * Lmax * Tw + h * hd;
+    const int Lk = P + t + 1;
+    auto k_at = [&](int j) -> const T* { return j < P ? kb + (size_t)j * Tw : own + (size_t)(j - P) * 3 * Tw + Tw; };
+    auto v_at = [&](int j) -> const T* { return j < P ? vb + (size_t)j * Tw : own + (size_t)(j - P) * 3 * Tw + 2 * Tw; };
+    const int n8 = HD8 ? HD8 : hd >> 3;
+    for (int d = lane; d < hd; d += 64) qs[d] = to_f32(row[d]) * scale;
+    __syncthreads();
+    float m = -INFINITY;
+    for (int j = lane; j < Lk; j += 64) {
+        const T* kr = k_at(j);
+        float sc = 0.f;
+        if constexpr (HD8 > 0) {
+            float kk[HD8][8];
+#pragma unroll
+            for (int c = 0; c < HD8; ++c) load8<T>(kr + c * 8, kk[c]);
+#pragma unroll
+            for (int c = 0; c < HD8; ++c)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sc = fmaf(qs[c * 8 + e], kk[c][e], sc);
+        } else {
+            for (int c = 0; c < n8; ++c) {
+                float kk[8];
+                load8<T>(kr + c * 8, kk);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sc = fmaf(qs[c * 8 + e], kk[e], sc);
+            }
+        }
+        ps[j] = sc;
+        m = fmaxf(m, sc);
+    }
+    m = wave_max(m);
+    float l = 0.f;
+    for (int j = lane; j < Lk; j += 64) {
+        const float pj = expf(ps[j] - m);
+        ps[j] = pj;
+        l += pj;
+    }
+    l = wave_sum(l);
+    __syncthreads();
+    const int jg = lane >> 4, dc = (lane & 15) * 8;
+    float o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = 0.f;
+    if (dc < hd) {
+        int j = jg;
+        for (; j + 12 < Lk; j += 16) {            // four keys of this lane's group per trip, loads first
+            float vv[4][8];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) load8<T>(v_at(j + 4 * u) + dc, vv[u]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float pj = ps[j + 4 * u];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = fmaf(pj, vv[u][e], o[e]);
+            }
+        }
+        for (; j < Lk; j += 4) {
+            float vv[8];
+            load8<T>(v_at(j) + dc, vv);
+            const float pj = ps[j];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = fmaf(pj, vv[e], o[e]);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) os[jg][dc + e] = o[e];
+    __syncthreads();
+    const float inv = 1.0f / l;
+    for (int d = lane; d < hd; d += 64) store1(out + (size_t)r * Tw, h * hd + d, (os[0][d] + os[1][d] + os[2][d] + os[3][d]) * inv);
+}
+
+// Caption-pass inputs of the same call: row r = caption * n + t of x [rows, T] = token table[ids[caption * ids_ld + t]] + position
+// table[P + t + 2] (the caption's t-th new position sits at sequence position P + t; ids clamped to [0, V))
+__global__ void opt_caption_inputs_kernel(const int* __restrict__ ids, int ids_ld, int n, int P, const float* __restrict__ tok,
+                                          const float* __restrict__ pos, float* __restrict__ x, int rows, int T, int V) {
+    const size_t tot = (size_t)rows * T;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (size_t)gridDim.x * blockDim.x) {
+        const int d = i % T;
+        const size_t r = i / T;
+        const int cl = r / n, t = r - (size_t)cl * n;
+        const int id = min(max(ids[(size_t)cl * ids_ld + t], 0), V - 1);
+        x[i] = tok[(size_t)id * T + d] + pos[(size_t)(P + t + 2) * T + d];
+    }
+}
+
 // OPT decoder inputs.  Prefill: row (b, j) of x[B, P, T] = (j < nq ? projected query (b, j) : token table[bos]) + position
 // table[j + 2] (HF OPTLearnedPositionalEmbedding offset).  Decode: x[b] = token table[seq[b][cur]] + position table[at + 2] (the greedy loop
 // keeps token `cur` at sequence position at = cur; a beam search's token columns start at BOS, behind the prompt's positions).
@@ -1788,6 +1893,47 @@ int launch_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, 
         if (hd == 80) CAP_ODA(float, 10, float); else if (hd == 64) CAP_ODA(float, 8, float); else if (hd == 128) CAP_ODA(float, 16, float); else CAP_ODA(float, 0, float);
     }
 #undef CAP_ODA
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_opt_prefix_attention(int dtype, const void* qkv, const void* kc, const void* vc, void* out, int n_caps, int n, int cap0, int C,
+                                const int* n_pos, int T, int H, int Lmax, int P, hipStream_t s, int out_dtype) {
+    if (out_dtype < 0) out_dtype = dtype;
+    if (out_dtype != dtype && !(dtype == CAP_DT_F32 && out_dtype == CAP_DT_G8 && T % 8 == 0)) {
+        cap_set_error("opt_prefix_attention: output type %d for input type %d is not supported here", out_dtype, dtype);
+        return -1;
+    }
+    const int hd = H > 0 ? T / H : 0;
+    if (n_caps < 1 || n < 1 || cap0 < 0 || C < 1 || H < 1 || T % H != 0 || hd % 8 != 0 || hd < 8 || hd > 128 || P < 1 || P > Lmax ||
+        P + n > OPT_DECODE_MAX_KEYS || (long long)n_caps * n * H > 0x7fffffffLL) {
+        cap_set_error("opt_prefix_attention: unsupported shape captions=%d positions=%d from caption %d (%d per image) T=%d H=%d prefix=%d Lmax=%d "
+                      "(head_dim a multiple of 8 up to 128, 1 <= prefix <= Lmax, prefix + positions <= %d)", n_caps, n, cap0, C, T, H, P, Lmax,
+                      OPT_DECODE_MAX_KEYS);
+        return -1;
+    }
+    if (!qkv || !kc || !vc || !out) { cap_set_error("opt_prefix_attention: null pointer"); return -1; }
+    const float scale = 1.0f / sqrtf((float)hd);
+#define CAP_OPA(TT, H8, TO)                                                                                                      \
+    hipLaunchKernelGGL((opt_prefix_attention_kernel<TT, H8, TO>), dim3(n_caps * n * H), dim3(64), 0, s, (const TT*)qkv, (const TT*)kc, \
+                       (const TT*)vc, (TO*)out, T, H, hd, Lmax, P, n, cap0, C, n_pos, scale)
+    if (dtype == CAP_DT_BF16) {
+        if (hd == 80) CAP_OPA(bf16_t, 10, bf16_t); else if (hd == 64) CAP_OPA(bf16_t, 8, bf16_t); else if (hd == 128) CAP_OPA(bf16_t, 16, bf16_t); else CAP_OPA(bf16_t, 0, bf16_t);
+    } else if (out_dtype == CAP_DT_G8) {
+        if (hd == 80) CAP_OPA(float, 10, g8_t); else if (hd == 64) CAP_OPA(float, 8, g8_t); else if (hd == 128) CAP_OPA(float, 16, g8_t); else CAP_OPA(float, 0, g8_t);
+    } else {
+        if (hd == 80) CAP_OPA(float, 10, float); else if (hd == 64) CAP_OPA(float, 8, float); else if (hd == 128) CAP_OPA(float, 16, float); else CAP_OPA(float, 0, float);
+    }
+#undef CAP_OPA
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_opt_caption_inputs(const int* ids, int ids_ld, int n_caps, int n, int P, const float* tok, const float* pos, float* x, int T, int V,
+                              hipStream_t s) {
+    if (!ids || !tok || !pos || !x || n_caps < 1 || n < 1 || ids_ld < n || P < 0 || T < 1 || V < 1) {
+        cap_set_error("opt_caption_inputs: %d captions x %d positions (ids rows of %d) behind %d positions", n_caps, n, ids_ld, P);
+        return -1;
+    }
+    hipLaunchKernelGGL(opt_caption_inputs_kernel, dim3(256), dim3(256), 0, s, ids, ids_ld, n, P, tok, pos, x, n_caps * n, T, V);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }

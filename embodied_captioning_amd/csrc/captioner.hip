@@ -217,6 +217,7 @@ struct Captioner {
     int compaction = 1;          // cap_set_row_compaction: 1 = the greedy batch path works on the open captions' rows only (RowMap)
     int last_prefill_passes = 0; // prefill passes of the last prompted generate (cap_last_prefill_passes): 1 when the workspace held the batch
     int last_compacted = 0;      // did the last cap_generate's decode loop run compacted (cap_last_row_compaction)
+    int last_score_passes = 0;   // decoder passes of the last cap_score_captions (cap_last_score_passes)
     int *live = nullptr, *n_live = nullptr;       // RowMap storage: int32 [max rows] + the count
     // vision weights (post_g / post_b: the image tower's final LayerNorm - CoCa: the pooler's ln_k)
     float *cls, *vpos, *b_patch = nullptr, *post_g, *post_b;
@@ -239,6 +240,7 @@ struct Captioner {
     void* beam = nullptr;
     size_t cache_layer_bytes = 0;
     size_t ws_rows = 0;          // rows the decoder's pass buffers (dx, dx_t, dctx, dh, dpart) hold: the decode rows, or a whole prompt prefill's
+    size_t head_rows = 0;        // rows the head's buffers (dy, logits) hold: the decode rows, or CapConfig.max_score_rows
     // ---- CoCa (CAP_ARCH_COCA)
     int Q = 0, E = 0;
     float *lnpost_g = nullptr, *lnpost_b = nullptr, *pool_q = nullptr, *b_pool_kv = nullptr, *b_pool_o = nullptr, *ones = nullptr,
@@ -654,10 +656,13 @@ int build_arena(Captioner* m) {
     TRY(dev_alloc(m, (void**)&m->anc, 2 * R * Lm * 4));
     // prompt prefill (run_prefill): max_prompt - 1 known positions of every caption go through the decoder as ONE pass of rows, so
     // the buffers a pass over rows touches hold that many (CapConfig.max_prompt = 0: exactly the decode rows, as ever)
-    const size_t Rw = std::max(R, Bm * (size_t)std::max(c.max_prompt - 1, 0));
+    // teacher-forced scoring (run_score): max_score_rows rows of a pass AND of its head (0: nothing beyond the above)
+    const size_t Rs = (size_t)std::max(c.max_score_rows, 0), Rh = std::max(R, Rs);
+    const size_t Rw = std::max(std::max(R, Bm * (size_t)std::max(c.max_prompt - 1, 0)), Rs);
     m->ws_rows = Rw;
+    m->head_rows = Rh;
     TRY(dev_alloc(m, (void**)&m->dx, Rw * T * 4));
-    TRY(dev_alloc(m, (void**)&m->dy, R * T * 4));
+    TRY(dev_alloc(m, (void**)&m->dy, Rh * T * 4));
     TRY(dev_alloc(m, (void**)&m->dx2, (size_t)(R > SMALL_MAX_ROWS ? R : SMALL_MAX_ROWS) * T * 4));
     TRY(dev_alloc(m, (void**)&m->dpart, 12 * Rw * T * 4));      // split-K slabs: 8 x [R,T] (ffn) or 4 x [R,3T] (qkv)
     TRY(dev_alloc(m, &m->dx_t, Rw * T * e));
@@ -665,7 +670,7 @@ int build_arena(Captioner* m) {
     TRY(dev_alloc(m, &m->dctx, Rw * T * e));
     TRY(dev_alloc(m, &m->dh, Rw * c.t_ffn * e));
     m->ldl = (c.vocab + 3) & ~3;
-    TRY(dev_alloc(m, (void**)&m->logits, R * (size_t)m->ldl * 4));
+    TRY(dev_alloc(m, (void**)&m->logits, Rh * (size_t)m->ldl * 4));
     for (SubLayer& u : m->dec.subs)
         if (u.kind == DEC_SELF) TRY(dev_alloc(m, &u.cache, 2 * R * H * Lm * 64 * e));
     TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, (int)Lm)));
@@ -1055,9 +1060,17 @@ int opt_gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, const 
 // image b's positions in the cache of row b * K, for the K rows of the image; its steps run over the B * K rows, each reading the
 // generated positions from the rows its ancestry table names (opt_beam_decode_attention).
 struct OptBeams { int K; const int* anc; int anc_ld; };      // anc [B * K, anc_ld]: the step's table, from the first generated position on
-int opt_attention(Captioner* m, const OLayer& Ly, int B, int L, int past, hipStream_t s, const OptBeams* bm) {
+// Teacher-forced scoring (sc, run_score_blip2): the B rows-of-L are captions cap0 .. cap0 + B - 1 of a request with C captions per
+// image, their L new positions behind the P positions the prompt pass left in the cache of row image = caption / C; the caches are
+// read only (opt_prefix_attention).
+struct OptScore { int C, cap0; };
+int opt_attention(Captioner* m, const OLayer& Ly, int B, int L, int past, hipStream_t s, const OptBeams* bm, const OptScore* sc = nullptr) {
     const CapConfig& c = m->c;
     const int T = c.t_hidden, H = c.t_heads, hd = T / H, P = c.num_query_tokens + 1, Lmax = P + c.max_len;
+    if (sc) {
+        ProfScope ps(m, s, "opt_prefix_attn", 4.0 * B * H * (double)L * (P + L) * hd, 2.0 * B * (P + L) * T * m->esz);
+        return launch_opt_prefix_attention(m->dt, m->oqkv, Ly.kc, Ly.vc, m->octx, B, L, sc->cap0, sc->C, nullptr, T, H, Lmax, P, s, m->gdt);
+    }
     if (L > 1 && past != 0) { cap_set_error("opt_attention: %d new positions behind a cached prefix (%d) are not built", L, past); return -1; }
     if (L > 1) TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, L, T, Lmax, 0, s, bm ? bm->K : 1));
     ProfScope ps(m, s, "opt_attn", 4.0 * B * H * (double)L * (past + L) * hd, 2.0 * B * (past + L) * T * m->esz);
@@ -1078,16 +1091,19 @@ int opt_attention(Captioner* m, const OLayer& Ly, int B, int L, int past, hipStr
 // consumers finish the projections' sums - bias (+ ReLU) -> T for q|k|v and fc1; bias + residual + the NEXT LayerNorm (the
 // final one on the last layer, over every row) for out_proj and fc2.
 // bm: the rows are a beam search's (opt_attention); its prompt pass leaves image b's logits in row b * K of m->logits.
-int run_opt(Captioner* m, int B, int L, int past, hipStream_t s, const OptBeams* bm = nullptr) {
+// sc (scoring): the rows are captions' new positions behind their images' cached prompts; no head here - the final LayerNorm of EVERY
+// row is left in oh_t for the caller's vocabulary GEMM over all of them.  Its rows take the weight streams up to the row count of
+// kI8SkinnyPromptCrops prompts, the tiled GEMM beyond, as the prompt pass does.
+int run_opt(Captioner* m, int B, int L, int past, hipStream_t s, const OptBeams* bm = nullptr, const OptScore* sc = nullptr) {
     const CapConfig& c = m->c;
     const int T = c.t_hidden, G = c.t_ffn, R = B * L;
-    const bool tiled = L > 1 && B > kI8SkinnyPromptCrops;
+    const bool tiled = sc ? R > kI8SkinnyPromptCrops * (c.num_query_tokens + 1) : L > 1 && B > kI8SkinnyPromptCrops;
     int S = 1;
     for (int i = 0; i < c.t_layers; ++i) {
         const OLayer& Ly = m->ol[i];
         const bool last = i + 1 == c.t_layers;
         TRY(opt_gemm(m, s, "opt_gemm_qkv", m->oh_t, Ly.w_qkv, Ly.b_qkv, 0, m->oqkv, R, 3 * T, T, false, &S, m->dt, Ly.s_qkv, tiled));
-        TRY(opt_attention(m, Ly, B, L, past, s, bm));
+        TRY(opt_attention(m, Ly, B, L, past, s, bm, sc));
         TRY(opt_gemm(m, s, "opt_gemm_o", m->octx, Ly.w_o, nullptr, 0, nullptr, R, T, T, true, &S, m->gdt, Ly.s_o, tiled));
         TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_o, m->ox, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
         TRY(opt_gemm(m, s, "opt_gemm_f1", m->oh_t, Ly.w_f1, Ly.b_f1, 2, m->off, R, G, T, false, &S, m->gdt, Ly.s_f1, tiled));
@@ -1095,25 +1111,29 @@ int run_opt(Captioner* m, int B, int L, int past, hipStream_t s, const OptBeams*
         TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_f2, m->ox, last ? m->o_lnf_g : m->ol[i + 1].ln1_g,
                                     last ? m->o_lnf_b : m->ol[i + 1].ln1_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
     }
+    if (sc) return 0;
     return gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)(L - 1) * T * m->esz, L * T, m->o_tok_t, T, m->logits,
                 (bm && L > 1 ? bm->K : 1) * m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
 }
 
 // The prompt pass with plain weights (f32 / f32s / bf16): B * L rows are GEMMs proper, so bias and residual ride the tiled GEMM's
 // epilogue, every sub-block opens with its own LayerNorm, and the final one covers each row's last position only.
-int run_opt_prompt_plain(Captioner* m, int B, int L, hipStream_t s, const OptBeams* bm = nullptr) {
+// sc (scoring): the same chain over captions' new positions behind the cached prompts; the final LayerNorm then covers EVERY row and
+// the head is the caller's (run_opt).
+int run_opt_prompt_plain(Captioner* m, int B, int L, hipStream_t s, const OptBeams* bm = nullptr, const OptScore* sc = nullptr) {
     const CapConfig& c = m->c;
     const int T = c.t_hidden, G = c.t_ffn, R = B * L;
     const int af = m->gdt == CAP_DT_G8 ? 1 : 0;     // split mode: q | k | v for the attention kernels and the caches are fp32
     for (const OLayer& Ly : m->ol) {
         TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln1_g, Ly.ln1_b, c.t_eps, m->oh_t, nullptr, R, T, s));
         TRY(gemm(m, s, "opt_gemm_qkv", m->oh_t, T, Ly.w_qkv, T, m->oqkv, 3 * T, Ly.b_qkv, nullptr, R, 3 * T, T, 0, af));
-        TRY(opt_attention(m, Ly, B, L, 0, s, bm));
+        TRY(opt_attention(m, Ly, B, L, sc ? c.num_query_tokens + 1 : 0, s, bm, sc));
         TRY(gemm(m, s, "opt_gemm_o", m->octx, T, Ly.w_o, T, m->ox, T, Ly.b_o, m->ox, R, T, T, 0, 1));
         TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, R, T, s));
         TRY(gemm(m, s, "opt_gemm_f1", m->oh_t, T, Ly.w_f1, T, m->off, G, Ly.b_f1, nullptr, R, G, T, 2, 0));
         TRY(gemm(m, s, "opt_gemm_f2", m->off, G, Ly.w_f2, G, m->ox, T, Ly.b_f2, m->ox, R, T, G, 0, 1));
     }
+    if (sc) return launch_layernorm(m->gdt, m->ox, T, m->o_lnf_g, m->o_lnf_b, c.t_eps, m->oh_t, nullptr, R, T, s);
     TRY(launch_layernorm(m->gdt, m->ox + (size_t)(L - 1) * T, L * T, m->o_lnf_g, m->o_lnf_b, c.t_eps, m->oh_t, nullptr, B, T, s));
     return gemm(m, s, "opt_gemm_vocab", m->oh_t, T, m->o_tok_t, T, m->logits, (bm ? bm->K : 1) * m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
 }
@@ -1215,6 +1235,69 @@ int run_generate_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
     }
     hipLaunchKernelGGL(copy_new_tokens_kernel, dim3(64), dim3(256), 0, s, m->seq, Lmax, P, m->lens, a.out_ids, a.out_len, B, max_len);
     CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// Teacher-forced scoring under BLIP-2 (cap_score_captions): the front half of run_generate_blip2 once per IMAGE - encoder, Q-Former,
+// projection, the P-position prompt pass, which leaves every image's prompt in its cache row and its BOS logits in m->logits - then
+//   entry 0 of every caption from its image's BOS logits (launch_target_logprob, one logits row shared by the image's C captions),
+//   the caption pass: the n = L - 2 tokens behind BOS of as many captions as the pass rows hold (max_batch x P: what the prompt
+//     pass is sized for), caption-major, behind the cached prompts (opt_prefix_attention; nothing is appended to the caches), the
+//     final LayerNorm over every row, and the tied head over those rows in slices of the logits buffer, each reduced at once.
+// Passes take whole images while one fits, else part of one image's captions.
+size_t score_pass_captions(const Captioner* m, int L);
+__global__ void score_counts_kernel(const int* __restrict__ lens, int* __restrict__ scored, int N, int L);
+int run_score_blip2(Captioner* m, const void* pixels, int fmt, int B, const int* ids, const int* lens, int C, int L, float* out_tlp, float* out_top,
+                    int* out_top_ids, int* out_scored, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden, nq = c.num_query_tokens, P = nq + 1, N = B * C, npos = L - 1, n = L - 2;
+    const size_t e = m->esz;
+    TRY(launch_fill_f32(out_tlp, 0.f, (size_t)N * npos, s));
+    TRY(launch_fill_f32(out_top, 0.f, (size_t)N * npos, s));
+    TRY(launch_fill_i32(out_top_ids, 0, (size_t)N * npos, s));
+    hipLaunchKernelGGL(score_counts_kernel, dim3((N + 255) / 256), dim3(256), 0, s, lens, out_scored, N, L);
+    CAP_HIP_CHECK(hipGetLastError());
+    TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
+    TRY(run_qformer(m, kCaptionPass, B, nq, 0, nullptr, nullptr, s));
+    TRY(gemm(m, s, "b2_gemm_lproj", m->qr.x_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1));
+    TRY(launch_opt_prefill_inputs(m->lm_proj, m->o_tok, m->o_pos, m->ox, B, nq, T, c.bos, s));
+    if (m->wq8) {
+        TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B * P, T, s));
+        TRY(run_opt(m, B, P, 0, s));
+    } else {
+        TRY(run_opt_prompt_plain(m, B, P, s));
+    }
+    {
+        ProfScope ps(m, s, "target_logprob", 0, 2.0 * N * c.vocab * 4);
+        TRY(launch_target_logprob(m->logits, m->ldl, c.vocab, N, 0, 1, ids + 1, L, out_scored, out_tlp, out_top, out_top_ids, npos, s, 0, C));
+    }
+    m->last_score_passes = 0;
+    if (n < 1) return 0;
+    const int per = (int)std::min<size_t>(score_pass_captions(m, L), (size_t)N);
+    const int step = per >= C ? per / C * C : per;
+    const int head_rows = c.max_batch * c.max_beams;
+    for (int n0 = 0; n0 < N;) {
+        const int nc = step >= C ? std::min(step, N - n0) : std::min(step, (n0 / C + 1) * C - n0);
+        const int Rp = nc * n;
+        const OptScore sc = {C, n0};
+        TRY(launch_opt_caption_inputs(ids + (size_t)n0 * L + 1, L, nc, n, P, m->o_tok, m->o_pos, m->ox, T, c.vocab, s));
+        if (m->wq8) {
+            TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, Rp, T, s));
+            TRY(run_opt(m, nc, n, P, s, nullptr, &sc));
+        } else {
+            TRY(run_opt_prompt_plain(m, nc, n, s, nullptr, &sc));
+        }
+        for (int r0 = 0; r0 < Rp; r0 += head_rows) {
+            const int hr = std::min(head_rows, Rp - r0);
+            TRY(gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)r0 * T * e, T, m->o_tok_t, T, m->logits, m->ldl, nullptr, nullptr, hr,
+                     c.vocab, T, 0, 1));
+            ProfScope ps(m, s, "target_logprob", 0, 2.0 * hr * c.vocab * 4);
+            TRY(launch_target_logprob(m->logits, m->ldl, c.vocab, hr, r0, n, ids + (size_t)n0 * L + 2, L, out_scored + n0,
+                                      out_tlp + (size_t)n0 * npos + 1, out_top + (size_t)n0 * npos + 1, out_top_ids + (size_t)n0 * npos + 1, npos, s, 1, 1));
+        }
+        ++m->last_score_passes;
+        n0 += nc;
+    }
     return 0;
 }
 
@@ -1700,7 +1783,9 @@ int run_step_small(Captioner* m, const Dec& d, const int* tokens, int tok_ld, in
 // (rows_per_kv); the embedding and the self-attention are the prefill's kernels (launch_embed_prompt,
 // launch_prefill_self_attention), built on the same row / unit functions.  So the caches hold the bits of the single steps.
 // d: the CALL's decode state (d.B, d.R = its captions: the caches and the cross K/V are laid out for them).
-int run_prefill(Captioner* m, const Dec& d, int c0, int nc, int npos, int Lm, hipStream_t s) {
+// kv_rows / img0 (teacher-forced scoring, run_score: several captions of one image in a pass): the rows from row 0 on share cross K/V
+// in runs of kv_rows, the first run image img0's; by default every caption is its own image (kv_rows = npos, img0 = c0).
+int run_prefill(Captioner* m, const Dec& d, int c0, int nc, int npos, int Lm, hipStream_t s, int kv_rows = 0, int img0 = -1) {
     const CapConfig& c = m->c;
     const DecPlan& P = m->dec;
     const int W = P.W, F = c.t_ffn, H = c.t_heads, Rp = nc * npos;
@@ -1733,12 +1818,12 @@ int run_prefill(Captioner* m, const Dec& d, int c0, int nc, int npos, int Lm, hi
             DecodeAttn a;
             memset(&a, 0, sizeof(a));
             a.out = pd.dctx; a.R = Rp; a.H = H; a.out_dtype = m->gdt;
-            // the image of row r is c0 + r / npos: the slot's blocks from image c0 on
+            // the image of row r is c0 + r / npos (img0 + r / kv_rows where given): the slot's blocks from that image on
             const CrossKV kv = cross_kv(m, u.slot, d.B, m->kv16);
-            const size_t img0 = (size_t)c0 * H * P.kv_tokens;       // head rows before image c0
-            a.kbase = m->kv16 ? kv.k : kv.k + img0 * m->kvrow; a.vbase = m->kv16 ? kv.v : kv.v + img0 * m->kvrow;
-            a.kv16 = m->kv16 ? 1 : 0; a.kv_row0 = m->kv16 ? kv.row0 + img0 : 0;
-            a.rows_per_kv = npos; a.kv_ld = P.kv_tokens; a.n_keys = P.kv_keys;
+            const size_t hr0 = (size_t)(img0 < 0 ? c0 : img0) * H * P.kv_tokens;       // head rows before the first image
+            a.kbase = m->kv16 ? kv.k : kv.k + hr0 * m->kvrow; a.vbase = m->kv16 ? kv.v : kv.v + hr0 * m->kvrow;
+            a.kv16 = m->kv16 ? 1 : 0; a.kv_row0 = m->kv16 ? kv.row0 + hr0 : 0;
+            a.rows_per_kv = kv_rows > 0 ? kv_rows : npos; a.kv_ld = P.kv_tokens; a.n_keys = P.kv_keys;
             TRY(gemm_partial(m, s, "prefill_gemm_cq", pd.dx_t, u.w_in, pd.dpart, Rp, W, W, 4, &S, nullptr));
             a.q_part = pd.dpart; a.q_S = S; a.q_bias = u.b_in; a.q_ld = W;
             ProfScope ps(m, s, "prefill_cross_attn", 4.0 * Rp * H * a.n_keys * 64, 2.0 * nc * H * a.n_keys * m->kvrow);
@@ -1852,6 +1937,75 @@ int run_generate(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
         CAP_HIP_CHECK(hipGetLastError());
     } else {
         TRY(launch_beam_finalize(d.beam, B, K, Lm, a.out_ids, a.out_len, a.out_scores, s));
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- teacher-forced scoring (BLIP)
+// scored[n] = positions of caption n that have a target: lens[n] - 1 inside [0, L - 1] (an absent slot, lens 0, has none)
+__global__ void score_counts_kernel(const int* __restrict__ lens, int* __restrict__ scored, int N, int L) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) scored[i] = min(max(lens[i] - 1, 0), L - 1);
+}
+
+struct ScoreArgs {
+    const void* pixels; int pixel_fmt, B;
+    const int *ids, *lens;      // int32 [B * C, L] / [B * C] (device)
+    int C, L;
+    float *out_tlp, *out_top; int *out_top_ids, *out_scored;   // [B * C, L - 1] x 3, [B * C]
+};
+
+// Captions a scoring pass of this handle takes at npos positions each: what its pass buffers and self-attention caches hold
+// (BLIP-2: the caption pass has L - 2 rows per caption - the first token comes from the prompt pass - in buffers of max_batch x P rows)
+size_t score_pass_captions(const Captioner* m, int L) {
+    if (m->c.arch == CAP_ARCH_BLIP2)
+        return L <= 2 ? (size_t)0x7fffffff : (size_t)m->c.max_batch * (m->c.num_query_tokens + 1) / (size_t)(L - 2);
+    return std::min<size_t>((size_t)m->c.max_batch * m->c.max_beams, m->ws_rows / (size_t)(L - 1));
+}
+
+// log p(ids[n][j + 1] | image n / C, ids[n][0..j]) for every caption and position, with the row's log max softmax and arg-max: the image
+// side once per image, then positions 0 .. L - 2 of the captions through the decoder as prefill passes (run_prefill: one read of every
+// weight per pass, the C captions of an image sharing its cross K/V as beams do), the head of run_step over the pass's rows - as many
+// at a time as the logits buffer holds - and launch_target_logprob on each slice.  Passes take whole images while one fits, else part
+// of one image's captions: a caption's rows are computed by row-wise kernels and attend their own caption's positions only, so the
+// chunking changes no bits.  Rows behind a caption's end are computed on whatever ids the caller left there (clamped) and come out
+// as zeros: attention is causal, so they reach no row that is reported.
+int run_score(Captioner* m, const ScoreArgs& a, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const DecPlan& P = m->dec;
+    const DecTags& tg = *P.tags;
+    const int N = a.B * a.C, L = a.L, npos = L - 1, W = P.W;
+    const size_t e = m->esz;
+    TRY(launch_fill_f32(a.out_tlp, 0.f, (size_t)N * npos, s));
+    TRY(launch_fill_f32(a.out_top, 0.f, (size_t)N * npos, s));
+    TRY(launch_fill_i32(a.out_top_ids, 0, (size_t)N * npos, s));
+    hipLaunchKernelGGL(score_counts_kernel, dim3((N + 255) / 256), dim3(256), 0, s, a.lens, a.out_scored, N, L);
+    CAP_HIP_CHECK(hipGetLastError());
+    TRY(run_image_side(m, a.pixels, a.pixel_fmt, a.B, s));
+    const int per = (int)std::min<size_t>(score_pass_captions(m, L), (size_t)N);
+    const int step = per >= a.C ? per / a.C * a.C : per;        // whole images, or part of one image's captions
+    m->last_score_passes = 0;
+    for (int n0 = 0; n0 < N;) {
+        const int nc = step >= a.C ? std::min(step, N - n0) : std::min(step, (n0 / a.C + 1) * a.C - n0);
+        Dec d = make_dec(m, a.B, 1);       // the cross K/V are packed for the call's images; the caches hold this pass's captions
+        d.R = nc;
+        TRY(launch_init_prompt_seq(d.seq, d.finished, d.lens, nc, L, a.ids + (size_t)n0 * L, nc, L, c.vocab, c.pad, s));
+        TRY(run_prefill(m, d, 0, nc, npos, L, s, (step >= a.C ? a.C : nc) * npos, n0 / a.C));
+        const int Rp = nc * npos;
+        for (int r0 = 0; r0 < Rp; r0 += (int)m->head_rows) {
+            const int hr = std::min((int)m->head_rows, Rp - r0);
+            const char* x_t = (const char*)d.dx_t + (size_t)r0 * W * e;
+            TRY(gemm(m, s, tg.tr, x_t, W, P.w_tr, W, d.dy, W, P.b_tr, nullptr, hr, W, W, 1, 1));
+            {
+                ProfScope ps(m, s, tg.ln, 0, (double)hr * W * (8 + e));
+                TRY(launch_layernorm(m->gdt, d.dy, W, P.tr_g, P.tr_b, c.t_eps, (void*)x_t, nullptr, hr, W, s));
+            }
+            TRY(gemm(m, s, tg.vocab, x_t, W, P.w_vocab, W, d.logits, m->ldl, P.b_vocab, nullptr, hr, c.vocab, W, 0, 1));
+            ProfScope ps(m, s, "target_logprob", 0, 2.0 * hr * c.vocab * 4);
+            TRY(launch_target_logprob(d.logits, m->ldl, c.vocab, hr, r0, npos, a.ids + (size_t)n0 * L + 1, L, a.out_scored + n0,
+                                      a.out_tlp + (size_t)n0 * npos, a.out_top + (size_t)n0 * npos, a.out_top_ids + (size_t)n0 * npos, npos, s));
+        }
+        ++m->last_score_passes;
+        n0 += nc;
     }
     return 0;
 }
@@ -1982,6 +2136,10 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
                       cfg->max_prompt, CAP_MAX_PROMPT);
         return -1;
     }
+    if (cfg->max_score_rows != 0 && (cfg->arch != CAP_ARCH_BLIP || cfg->max_score_rows < 0)) {
+        cap_set_error("cap_create: max_score_rows %d - scoring capacity is CAP_ARCH_BLIP's, 0 (none) or a row count", cfg->max_score_rows);
+        return -1;
+    }
     if (cfg->weight_int8) {
         const int T = cfg->t_hidden, G = cfg->t_ffn;
         if (cfg->weight_int8 != 1 || cfg->arch != CAP_ARCH_BLIP2 || cfg->compute_dtype != CAP_BF16) {
@@ -2000,6 +2158,7 @@ static int create_impl(const CapConfig* cfg, Captioner* share, CapHandle* out) {
         // same model, same arithmetic, same GPU; only the capacity of the arena may differ
         CapConfig a = *cfg, b = share->c;
         a.max_batch = b.max_batch = 0; a.max_beams = b.max_beams = 0; a.max_len = b.max_len = 0; a.max_prompt = b.max_prompt = 0;
+        a.max_score_rows = b.max_score_rows = 0;
         if (memcmp(&a, &b, sizeof(a)) != 0 || share->ws->device != dev) {
             cap_set_error("cap_create_shared: the new handle must describe the same model, compute dtype and GPU as the handle "
                           "whose weights it shares");
@@ -2419,6 +2578,55 @@ int cap_generate_prompted(CapHandle h, const void* pixels, int pixel_fmt, int B,
 
 int cap_last_prefill_passes(CapHandle h) { return h ? ((Captioner*)h)->last_prefill_passes : -1; }
 
+// Every rule of a scoring request, before anything is launched (validate_generate's style and order: handle, capacity, buffers, what
+// the architecture takes, shapes).  ids and lens are device data: the caller validates them (engine.validate_score_ids); the
+// library clamps ids to [0, vocab) and lens - 1 to [0, L - 1].
+static int validate_score(Captioner* m, const ScoreArgs& a, const char* who) {
+#define REFUSE_IF(cond, ...) do { if (cond) { cap_set_error(__VA_ARGS__); return -1; } } while (0)
+    REFUSE_IF(!m, "%s: null handle", who);
+    REFUSE_IF(m->c.arch == CAP_ARCH_COCA, "%s: scoring given captions is not built for CoCa handles (CAP_ARCH_COCA): BLIP and BLIP-2 only", who);
+    const bool b2 = m->c.arch == CAP_ARCH_BLIP2;
+    // capacity: BLIP's max_len counts the caption's tokens with BOS, BLIP-2's the tokens behind BOS
+    TRY(check_call(m, a.B, 1, b2 ? std::max(a.L - 1, 1) : std::max(a.L, 2), a.pixel_fmt, who));
+    REFUSE_IF(m->c.arch != CAP_ARCH_BLIP && !b2, "%s: the handle is not a BLIP / BLIP-2 captioner (arch %d)", who, m->c.arch);
+    REFUSE_IF(!a.pixels || !a.ids || !a.lens || !a.out_tlp || !a.out_top || !a.out_top_ids || !a.out_scored, "%s: null buffer", who);
+    REFUSE_IF(a.C < 1, "%s: captions_per_image %d must be at least 1", who, a.C);
+    REFUSE_IF(a.L < 2, "%s: L = %d - a caption has BOS and at least one scored token", who, a.L);
+    REFUSE_IF(!b2 && a.L - 1 > PREFILL_MAX_POS, "%s: L = %d exceeds the %d tokens a scoring pass takes (%d positions)", who, a.L, PREFILL_MAX_POS + 1,
+              PREFILL_MAX_POS);
+    REFUSE_IF(b2 && m->c.num_query_tokens + 1 + a.L - 1 > m->c.max_pos,
+              "%s: %d prompt positions + %d caption positions exceed the OPT decoder's %d positions (max_pos)", who, m->c.num_query_tokens + 1,
+              a.L - 1, m->c.max_pos);
+    REFUSE_IF((long long)a.B * a.C > 0x7fffffffLL / a.L, "%s: %d x %d captions of %d tokens overflow the row index", who, a.B, a.C, a.L);
+    REFUSE_IF(b2 && score_pass_captions(m, a.L) < 1,
+              "%s: one caption of L = %d tokens is %d decoder rows and this handle's pass buffers hold %d (max_batch x prompt positions): "
+              "create it with a larger max_batch", who, a.L, a.L - 2, m->c.max_batch * (m->c.num_query_tokens + 1));
+    REFUSE_IF(!b2 && score_pass_captions(m, a.L) < 1,
+              "%s: one caption of L = %d tokens is %d decoder rows and this handle's workspace holds %zu: create it with "
+              "CapConfig.max_score_rows >= %d", who, a.L, a.L - 1, m->ws_rows, a.L - 1);
+#undef REFUSE_IF
+    return 0;
+}
+
+int cap_score_captions(CapHandle h, const void* pixels, int pixel_fmt, int B, const int32_t* ids, const int32_t* lens, int captions_per_image,
+                       int L, float* out_token_logprobs, float* out_top_logprobs, int32_t* out_top_ids, int32_t* out_scored, void* stream) {
+    Captioner* m = (Captioner*)h;
+    const ScoreArgs a = {pixels, pixel_fmt, B, ids, lens, captions_per_image, L, out_token_logprobs, out_top_logprobs, out_top_ids, out_scored};
+    TRY(validate_score(m, a, "cap_score_captions"));
+    if (m->c.arch == CAP_ARCH_BLIP2)
+        return run_score_blip2(m, pixels, pixel_fmt, B, ids, lens, captions_per_image, L, out_token_logprobs, out_top_logprobs, out_top_ids,
+                               out_scored, (hipStream_t)stream);
+    return run_score(m, a, (hipStream_t)stream);
+}
+int cap_last_score_passes(CapHandle h) { return h ? ((Captioner*)h)->last_score_passes : -1; }
+int cap_score_pass_captions(CapHandle h, int L) {
+    Captioner* m = (Captioner*)h;
+    if (!m || L < 2) return -1;
+    if (m->c.arch == CAP_ARCH_BLIP2) { if (L - 1 > m->c.max_len) return -1; }
+    else if (m->c.arch != CAP_ARCH_BLIP || L - 1 > PREFILL_MAX_POS || L > m->c.max_len) return -1;
+    return (int)std::min<size_t>(score_pass_captions(m, L), 0x7fffffff);
+}
+
 int cap_generate_groups(CapHandle h, const void* pixels, int pixel_fmt, int B, int num_beams, int num_beam_groups, int max_len,
                         float length_penalty, int32_t* out_ids, int32_t* out_len, float* out_scores, void* stream) {
     CapGenerateArgs a = request_of(pixels, pixel_fmt, B, num_beams, max_len, length_penalty, out_ids, out_len);
@@ -2533,6 +2741,10 @@ int cap_op_attention(int dtype, const void* q, int64_t ldq, int64_t qbs, const v
 int cap_op_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int T, int H, int Lmax, int past,
                                 void* stream) {
     return launch_opt_decode_attention(in_dt_of(dtype), qkv, kc, vc, out, B, T, H, Lmax, past, (hipStream_t)stream, dt_of(dtype));
+}
+int cap_op_opt_prefix_attention(int dtype, const void* qkv, const void* kc, const void* vc, void* out, int n_caps, int n, int cap0, int C,
+                                const int32_t* n_pos, int T, int H, int Lmax, int P, void* stream) {
+    return launch_opt_prefix_attention(in_dt_of(dtype), qkv, kc, vc, out, n_caps, n, cap0, C, n_pos, T, H, Lmax, P, (hipStream_t)stream, dt_of(dtype));
 }
 int cap_op_opt_beam_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int K, int T, int H, int Lmax, int P,
                                      int past, const int32_t* anc, int anc_ld, void* stream) {
@@ -2777,6 +2989,12 @@ int cap_op_beam_peek(void* state, int B, int K, int max_len, int parity, int32_t
     CAP_HIP_CHECK(hipMemcpyAsync(active, beam_active_flag_p(state, B, K, max_len), 4, hipMemcpyDeviceToDevice, s));
     return 0;
 }
+int cap_op_target_logprob(const float* logits, int ld, int V, int rows, const int32_t* targets, const int32_t* live, float* out_target,
+                          float* out_top, int32_t* out_top_id, void* stream) {
+    // one position per "caption": row r's target is targets[r], it is live when live[r] > 0
+    return launch_target_logprob(logits, ld, V, rows, 0, 1, targets, 1, live, out_target, out_top, out_top_id, 1, (hipStream_t)stream);
+}
+
 int cap_op_select_logprob(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int min_len, int force_eos,
                           int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths,
                           float* logprobs, int lp_ld, int32_t* scored, void* stream) {

@@ -584,6 +584,71 @@ __global__ __launch_bounds__(256) void greedy_select_vocab_kernel(const float* _
 }
 
 // ------------------------------------------------------------------------------------------------
+// Teacher-forced scoring (cap_score_captions): the head consumer that reduces a logits row to the log-softmax at a GIVEN id, beside
+// the two things the scoring form above takes from it.  Logits row r0 + b (block b) is position j = r % npos of caption c = r / npos:
+//   live      = j < n_live[c]
+//   target    = targets[c * tgt_ld + j]                              (clamped to [0, V))
+//   out_tlp   [c * out_ld + j] = z_target - logsumexp(z) = (z_target - z_max) - log1p(sum_{i != argmax} exp(z_i - z_max))
+//   out_top   [c * out_ld + j] = -log1p(the same sum)                (log max softmax: the scoring form's bits, no EOS mask)
+//   out_top_id[c * out_ld + j] = argmax                              (greedy_row_argmax: lowest index wins ties, NaN never wins)
+// A dead row writes zeros and reads nothing.  The row is read the way the scoring form reads it - the selection, then the sums from
+// L2, both with 16-byte loads, thread assignment and LDS tree a function of V alone - so a row's values do not depend on where it
+// sits; when the target is the argmax, out_tlp == out_top bit for bit (z_target - z_max is an exact 0).
+__global__ __launch_bounds__(256) void target_logprob_kernel(const float* __restrict__ logits, int ld, int V, int r0, int npos,
+                                                             const int* __restrict__ targets, int tgt_ld,
+                                                             const int* __restrict__ n_live, float* __restrict__ out_tlp,
+                                                             float* __restrict__ out_top, int* __restrict__ out_top_id, int out_ld,
+                                                             int j0, int share) {
+    // j0: the pass's first position is the caption's j0-th (live = j0 + j < n_live; targets / outputs are passed moved by j0);
+    // share: that many consecutive rows read ONE logits row (BLIP-2: an image's prompt logits score the first token of all its captions)
+    const int tid = threadIdx.x, r = r0 + blockIdx.x, c = r / npos, j = r - c * npos;
+    const size_t o = (size_t)c * out_ld + j;
+    if (j0 + j >= n_live[c]) {                                // uniform over the block: before any barrier
+        if (tid == 0) { out_tlp[o] = 0.f; out_top[o] = 0.f; out_top_id[o] = 0; }
+        return;
+    }
+    const float* x = logits + (size_t)(blockIdx.x / share) * ld;
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    const int imax = greedy_row_argmax(x, V, -1, false, tid, sv, si);
+    const float zmax = sv[0];
+    __syncthreads();                                     // sv[] is reused for the sums
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int V4 = V >> 2;
+    for (int c0 = tid; c0 < V4; c0 += 1024) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int cc = c0 + u * 256;
+            v[u] = cc < V4 ? *(const float4*)(x + 4 * cc) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int i = 4 * (c0 + u * 256);
+            acc.x += i == imax ? 0.f : expf(v[u].x - zmax);
+            acc.y += i + 1 == imax ? 0.f : expf(v[u].y - zmax);
+            acc.z += i + 2 == imax ? 0.f : expf(v[u].z - zmax);
+            acc.w += i + 3 == imax ? 0.f : expf(v[u].w - zmax);
+        }
+    }
+    float tail = 0.f;
+    for (int i = (V4 << 2) + tid; i < V; i += 256) tail += i == imax ? 0.f : expf(x[i] - zmax);
+    sv[tid] = ((acc.x + acc.y) + (acc.z + acc.w)) + tail;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) sv[tid] += sv[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int tgt = min(max(targets[(size_t)c * tgt_ld + j], 0), V - 1);
+        const float top = -log1pf(sv[0]);
+        out_tlp[o] = (x[tgt] - zmax) + top;
+        out_top[o] = top;
+        out_top_id[o] = imax;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Probability fusion behind the vocab form: per group of caption rows (CSR: group_rows[group_off[g] .. group_off[g + 1])), the mean
 // of the rows' vocab_acc vectors, the tokens whose mean exceeds th in ascending id order, their means, and their full count.
 //   mean(i) = (((a_0 + a_1) + a_2) + ...) / (float)n   in fp32, members in listed order; kept if mean > th (strict)
@@ -922,6 +987,20 @@ int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_l
         hipLaunchKernelGGL(greedy_select_kernel, dim3(R), dim3(256), 0, s, logits, ld, V, seq, seq_ld, t, max_len, eos, pad,
                            finished, out_len, min_len, force_eos, map);
     }
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_target_logprob(const float* logits, int ld, int V, int rows, int r0, int npos, const int* targets, int tgt_ld,
+                          const int* n_live, float* out_tlp, float* out_top, int* out_top_id, int out_ld, hipStream_t s, int j0, int share) {
+    if (!logits || !targets || !n_live || !out_tlp || !out_top || !out_top_id) { cap_set_error("target_logprob: null buffer"); return -1; }
+    if (rows < 1 || r0 < 0 || npos < 1 || V < 1 || ld < V || ld % 4 != 0 || ((uintptr_t)logits & 15) != 0 || out_ld < npos || tgt_ld < 1 || j0 < 0 || share < 1) {
+        cap_set_error("target_logprob: %d rows from %d at %d positions per caption (outputs [., %d]) of [., %d] logits with ld %d: ld >= V, "
+                      "ld %% 4 == 0, a 16-byte aligned pointer and out_ld >= positions are needed", rows, r0, npos, out_ld, V, ld);
+        return -1;
+    }
+    hipLaunchKernelGGL(target_logprob_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, r0, npos, targets, tgt_ld, n_live, out_tlp,
+                       out_top, out_top_id, out_ld, j0, share);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }

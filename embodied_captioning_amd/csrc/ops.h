@@ -71,6 +71,13 @@ int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_l
                          // vocab form (launched only when vocab_acc is given; needs the scoring buffers): vocab_acc[row*acc_ld + i] =
                          // max(itself, softmax_i of the row as selected from), i < V, for the rows open at this step
                          float* vocab_acc = nullptr, int acc_ld = 0);
+// teacher-forced scoring: logits row b of `rows` (fp32 [rows, ld]) is pass row r = r0 + b = position r % npos of caption r / npos; for
+// positions below n_live[caption] the log-softmax at targets[caption * tgt_ld + position] (clamped to [0, V)), log max softmax and the
+// arg-max (launch_greedy_select's selection and tie rule, no EOS mask) go to out_*[caption * out_ld + position], zeros for the others
+int launch_target_logprob(const float* logits, int ld, int V, int rows, int r0, int npos, const int* targets, int tgt_ld,
+                          const int* n_live, float* out_tlp, float* out_top, int* out_top_id, int out_ld, hipStream_t s,
+                          int j0 = 0,        // the pass starts at the caption's j0-th position: live = j0 + position < n_live[caption]
+                          int share = 1);    // consecutive rows reading one logits row (row b reads logits row b / share)
 // per group g of rows group_rows[group_off[g] .. group_off[g+1]) of acc [., acc_ld]: the tokens i < V whose fp32 mean over the
 // members (summed in listed order) exceeds th, ascending: out_ids / out_prob [G, K] (at most K written), out_count [G] (all)
 int launch_vocab_group_threshold(const float* acc, int acc_ld, int V, const int* group_rows, const int* group_off, int G, float th,
@@ -114,6 +121,14 @@ int launch_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, 
 int launch_opt_beam_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int K, int T, int H, int Lmax,
                                      int P, int past, const int* anc, int anc_ld, hipStream_t s, int out_dtype = -1);
 // row_stride: row b's positions go to cache row b * row_stride (a beam search's prompt: the first of each image's K rows)
+// teacher-forced scoring behind a cached prompt (BLIP-2): n new positions of n_caps captions, caption-major fused q|k|v rows; caption
+// cap0 + c belongs to image (cap0 + c) / C, whose P prompt keys are read from cache row `image` of kc / vc [.][Lmax][T], the caption's
+// own keys from the rows themselves; n_pos (device, optional): rows with position >= n_pos[cap0 + c] are left untouched
+int launch_opt_prefix_attention(int dtype, const void* qkv, const void* kc, const void* vc, void* out, int n_caps, int n, int cap0, int C,
+                                const int* n_pos, int T, int H, int Lmax, int P, hipStream_t s, int out_dtype = -1);
+// x [n_caps * n, T] = token table[ids[c * ids_ld + t]] + position table[P + t + 2] (ids clamped to [0, V))
+int launch_opt_caption_inputs(const int* ids, int ids_ld, int n_caps, int n, int P, const float* tok, const float* pos, float* x, int T, int V,
+                              hipStream_t s);
 int launch_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, hipStream_t s,
                      int row_stride = 1);
 int launch_rows_broadcast(int dtype, const float* src, float* dst_f, void* dst_t, int B, int n, int D, hipStream_t s);

@@ -130,13 +130,86 @@ def validate_prompt_ids(prompt_ids, arch, batch: int, max_length: int, num_beams
     return t.to(torch.int32).contiguous()
 
 
+def score_summary(token_logprobs, top_logprobs, scored) -> Dict[str, torch.Tensor]:
+    """Per-caption numbers from `score`'s outputs, float64 on the host: n_tokens int64 [N] (= scored), logprob_sum, logprob_mean,
+    perplexity = exp(-mean) of the GIVEN tokens, and top_perplexity = the reference's `compute_perplexity` on the teacher-forced
+    rows (exp(-mean log max softmax), `perplexity_from_logprobs`).  A caption with no scored token (an absent slot) gives nan."""
+    lp = torch.as_tensor(token_logprobs).detach().cpu().to(torch.float64)
+    n = torch.as_tensor(scored).detach().cpu().to(torch.int64)
+    if lp.dim() != 2 or n.shape != (lp.shape[0],):
+        raise ValueError(f"token_logprobs must be [N, L - 1] and scored [N], got {tuple(lp.shape)} / {tuple(n.shape)}")
+    keep = torch.arange(lp.shape[1])[None, :] < n[:, None]
+    total = torch.where(keep, lp, torch.zeros_like(lp)).sum(dim=1)
+    mean = total / n.to(torch.float64)
+    return {"n_tokens": n, "logprob_sum": total, "logprob_mean": mean, "perplexity": torch.exp(-mean),
+            "top_perplexity": perplexity_from_logprobs(top_logprobs, n)}
+
+
+SCORE_MAX_TOKENS = 32     # tokens per caption (BOS included) cap_score_captions takes: one prefill pass covers 31 positions
+
+
+def validate_score_ids(ids, lens, arch, n_images: int, captions_per_image: int = 1, limit: int = SCORE_MAX_TOKENS):
+    """The host check of `score(pixels, ids, lens)`: -> (ids int32 [N, L], lens int32 [N]) host tensors, N = n_images *
+    captions_per_image.  Raises ValueError, naming the fault, BEFORE anything is uploaded or launched: an architecture that is not
+    scored (CoCa), captions_per_image < 1, ids not an integer [N, L] array or lens not an integer [N] array, L outside
+    [2, limit], lens[n] outside [2, L] (0 = an absent slot, only with captions_per_image > 1), an id outside [0, vocab), column 0 of
+    a present caption not BOS, pad or EOS INSIDE a caption (EOS as its last token is allowed).  Columns from lens[n] on are padding:
+    only the range of their ids is checked.  Needs no GPU."""
+    fam = _arch_family(arch)
+    if fam == "coca":
+        raise ValueError("score: scoring given captions is not built for CoCa; it is BLIP's and BLIP-2's")
+    C_ = int(captions_per_image)
+    if C_ < 1:
+        raise ValueError(f"score: captions_per_image = {captions_per_image} must be at least 1")
+    t, ln = torch.as_tensor(ids), torch.as_tensor(lens)
+    for name, x in (("ids", t), ("lens", ln)):
+        if x.is_floating_point() or x.dtype == torch.bool or x.is_complex():
+            raise ValueError(f"score: {name} must hold integers, got dtype {x.dtype}")
+    t, ln = t.detach().cpu().to(torch.int64), ln.detach().cpu().to(torch.int64)
+    n = int(n_images) * C_
+    if t.dim() != 2 or int(t.shape[0]) != n:
+        raise ValueError(f"score: ids must be [N, L] with N = {n_images} images x {C_} captions = {n}, got shape {tuple(t.shape)}")
+    if ln.dim() != 1 or int(ln.shape[0]) != n:
+        raise ValueError(f"score: lens must be [N] with N = {n}, got shape {tuple(ln.shape)}")
+    if n < 1:
+        raise ValueError(f"score: nothing to score ({n_images} images x {C_} captions)")
+    L = int(t.shape[1])
+    if L < 2:
+        raise ValueError(f"score: ids has {L} column(s): a caption is BOS plus at least one scored token (L >= 2)")
+    if L > int(limit):
+        raise ValueError(f"score: ids has {L} columns: too long, the limit is {limit} tokens (BOS included) for this engine")
+    absent = ln == 0
+    if bool(absent.any()) and C_ == 1:
+        raise ValueError(f"score: lens[{int(absent.nonzero()[0])}] = 0 marks an absent slot, which exists only with captions_per_image > 1")
+    bad = ~absent & ((ln < 2) | (ln > L))
+    if bool(bad.any()):
+        i = int(bad.nonzero()[0])
+        raise ValueError(f"score: lens[{i}] = {int(ln[i])} is outside [2, L = {L}] (BOS plus at least one token; 0 = absent slot)")
+    lo, hi = int(t.min()), int(t.max())
+    if lo < 0 or hi >= arch.vocab:
+        raise ValueError(f"score: ids holds token id {lo if lo < 0 else hi}, out of range [0, {arch.vocab}) of the vocabulary")
+    if bool((t[~absent, 0] != arch.bos).any()):
+        raise ValueError(f"score: ids column 0 must be BOS ({arch.bos}) in every caption, got {sorted(set(t[~absent, 0].tolist()))[:4]}")
+    col = torch.arange(L)[None, :]
+    inside = (col >= 1) & (col < (ln[:, None] - 1))          # tokens 1 .. lens - 2: behind BOS, before the last
+    last = (col == (ln[:, None] - 1)) & ~absent[:, None]
+    if bool((inside & (t == arch.pad)).any() or (last & (t == arch.pad) & (arch.pad != arch.eos)).any()):
+        raise ValueError(f"score: ids holds the pad token ({arch.pad}) inside a caption (padding starts at lens[n])")
+    if bool((inside & (t == arch.eos)).any()):
+        raise ValueError(f"score: ids holds the EOS token ({arch.eos}) inside a caption: EOS is allowed as the last token only")
+    return t.to(torch.int32).contiguous(), ln.to(torch.int32).contiguous()
+
+
 class CaptionerEngine:
     """One handle = one model replica on one GPU, bound to torch's current stream of `device` at each call."""
 
     def __init__(self, arch: BlipArch, dtype: str = "bf16", max_batch: int = 8, max_beams: int = 1,
                  max_len: int = 20, device: str | torch.device = "cuda:0", share_weights_with: "CaptionerEngine | None" = None,
-                 cross_cache: str = "auto", weight_int8: bool = False, max_prompt: int = 0):
-        """max_prompt (BLIP): prompt capacity - with max_prompt >= P the P - 1 prompt positions of a FULL batch run through the decoder
+                 cross_cache: str = "auto", weight_int8: bool = False, max_prompt: int = 0, max_score_rows: int = 0):
+        """max_score_rows (BLIP): scoring capacity in decoder rows (`score`): N captions of L tokens run as ONE pass with one vocabulary
+        GEMM when N * (L - 1) <= max_score_rows; 0 reserves nothing (the arena is what it always was) and `score` works in passes of
+        as many captions as the decode rows hold, the head over max_batch * max_beams rows at a time - same bits.
+        max_prompt (BLIP): prompt capacity - with max_prompt >= P the P - 1 prompt positions of a FULL batch run through the decoder
         as one prefill pass (`generate(prompt_ids=)`); 0 reserves nothing (the arena is what it always was) and a prompted batch
         is prefilled in chunks of as many captions as the decode rows hold (`prompt_limit` = the longest prompt taken).
         weight_int8 (BLIP-2, dtype "bf16" only): the reference's `load_in_8bit=True` (blip2.py:19-22) - the OPT decoder layers' Linear
@@ -163,6 +236,10 @@ class CaptionerEngine:
         cfg.struct_size = C.sizeof(N.CapConfig)
         cfg.compute_dtype = _DTYPES[dtype]
         cfg.max_prompt = self.max_prompt
+        self.max_score_rows = int(max_score_rows)
+        if self.max_score_rows and (_arch_family(arch) != "blip" or self.max_score_rows < 0):
+            raise ValueError(f"max_score_rows = {max_score_rows}: scoring capacity is BLIP's, 0 or a row count")
+        cfg.max_score_rows = self.max_score_rows
         cfg.image_size, cfg.patch_size = arch.image_size, arch.patch_size
         self.is_coca = isinstance(arch, CocaArch)
         self.is_blip2 = isinstance(arch, Blip2Arch)
@@ -456,6 +533,76 @@ class CaptionerEngine:
             out["sequences_scores"] = scores
         if logits is not None:
             out["logits"] = logits
+        return out
+
+    @property
+    def score_limit(self) -> int:
+        """Longest caption (tokens, BOS included) `score` takes on this engine: BLIP's max_len counts BOS and one prefill pass covers 31
+        positions; BLIP-2's max_len counts the tokens behind BOS, within the OPT decoder's positions."""
+        if getattr(self, "is_blip2", False):
+            return min(self.max_len, self.arch.max_pos - self.arch.num_query_tokens - 1) + 1
+        return min(self.max_len, SCORE_MAX_TOKENS)
+
+    @property
+    def last_score_passes(self) -> int:
+        """Decoder passes of the last cap_score_captions call (`score` makes one call per max_batch images)."""
+        return int(self.lib.cap_last_score_passes(self._h))
+
+    def score(self, pixels: torch.Tensor, ids, lens, captions_per_image: int = 1, sort_by_length: bool = True) -> Dict[str, torch.Tensor]:
+        """Teacher-forced log-probs of GIVEN captions under the captioner (BLIP, BLIP-2) - HF `model(pixel_values, input_ids=...)` reduced on
+        the device.  ids [N, L] (column 0 = BOS) and lens [N] (tokens incl. BOS, and EOS / [SEP] if the end is to be scored; 0 = an
+        absent slot when captions_per_image > 1) are host lists / tensors, N = B * captions_per_image, caption n belongs to image
+        n // captions_per_image; columns from lens[n] on are padding.  Validated on the host first (`validate_score_ids`).
+        Returns device tensors: token_logprobs fp32 [N, L - 1] (entry j = log_softmax(logits at position j)[ids[n, j + 1]] for j <
+        lens[n] - 1, 0 behind), top_logprobs fp32 / top_ids int32 [N, L - 1] (log max softmax and arg-max of the same rows), scored
+        int32 [N] = lens - 1.  Plain logits: no EOS mask, no MinLength, no label smoothing.
+        The image side runs once per image.  More than max_batch images go in calls of max_batch; each call is trimmed to its own
+        longest caption, and with captions_per_image == 1 and sort_by_length the pairs are sorted by length first (and un-sorted
+        on return) so that a call's rows are its own maximum.  None of this changes a caption's bits."""
+        Cn = int(captions_per_image)
+        B = int(pixels.shape[0])
+        ids_h, lens_h = validate_score_ids(ids, lens, self.arch, B, Cn, self.score_limit)
+        need = max(int(lens_h.max()), 2) - 1
+        if int(self.lib.cap_score_pass_captions(self._h, need + 1)) == 0:        # the handle's own capacity: nothing is uploaded
+            raise ValueError(f"score: a caption of {need + 1} tokens is {need} decoder rows, more than this engine's workspace holds: "
+                             f"no chunking fits it - create the engine with " +
+                             ("a larger max_batch" if getattr(self, "is_blip2", False) else f"max_score_rows >= {need}"))
+        pixels, fmt = self._pixels(pixels)
+        N_, L = int(ids_h.shape[0]), int(ids_h.shape[1])
+        dev = self.device
+        out = {"token_logprobs": torch.zeros((N_, L - 1), dtype=torch.float32, device=dev),
+               "top_logprobs": torch.zeros((N_, L - 1), dtype=torch.float32, device=dev),
+               "top_ids": torch.zeros((N_, L - 1), dtype=torch.int32, device=dev),
+               "scored": torch.zeros((N_,), dtype=torch.int32, device=dev)}
+        order = None
+        if Cn == 1 and sort_by_length and B > self.max_batch:
+            order = torch.argsort(lens_h, stable=True, descending=True)
+            ids_h, lens_h = ids_h[order], lens_h[order]
+            pixels = pixels[order.to(dev)]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            for b0 in range(0, B, self.max_batch):
+                nb = min(self.max_batch, B - b0)
+                rows = slice(b0 * Cn, (b0 + nb) * Cn)
+                Lc = max(int(lens_h[rows].max()), 2)
+                ids_d = ids_h[rows, :Lc].contiguous().to(dev)
+                lens_d = lens_h[rows].contiguous().to(dev)
+                px = pixels[b0:b0 + nb]
+                n = nb * Cn
+                tlp = torch.empty((n, Lc - 1), dtype=torch.float32, device=dev)        # zero-filled by the library
+                top = torch.empty((n, Lc - 1), dtype=torch.float32, device=dev)
+                tid = torch.empty((n, Lc - 1), dtype=torch.int32, device=dev)
+                sc = torch.empty((n,), dtype=torch.int32, device=dev)
+                N.check(self.lib.cap_score_captions(self._h, C.c_void_p(px.data_ptr()), fmt, nb, C.c_void_p(ids_d.data_ptr()),
+                                                    C.c_void_p(lens_d.data_ptr()), Cn, Lc, C.c_void_p(tlp.data_ptr()),
+                                                    C.c_void_p(top.data_ptr()), C.c_void_p(tid.data_ptr()), C.c_void_p(sc.data_ptr()),
+                                                    C.c_void_p(stream.cuda_stream)), "cap_score_captions")
+                for t in (ids_d, lens_d):
+                    t.record_stream(stream)
+                dst = rows if order is None else order[rows].to(dev)
+                for key, val in (("token_logprobs", tlp), ("top_logprobs", top), ("top_ids", tid)):
+                    out[key][dst, :Lc - 1] = val
+                out["scored"][dst] = sc
         return out
 
     def fuse_vocab_groups(self, vocab_maxprob: torch.Tensor, groups: Sequence[Sequence[int]], th: float,

@@ -6,6 +6,10 @@ batched device calls (captioner/clip_scorer.py, captioner/blip2_itm_scorer.py) i
     python -m embodied_captioning_amd.pseudocaptioner --file_path DIR --output_csv_path OUT.json --method clip
     python -m embodied_captioning_amd.pseudocaptioner --file_path DIR --output_csv_path OUT.json --method blip2_itm [--model DIR]
 
+    python -m embodied_captioning_amd.pseudocaptioner --file_path DIR --output_csv_path OUT.json --method blip_ll [--model DIR]
+
+`--method blip_ll` has no counterpart in the reference: the selector is the BLIP captioner's OWN likelihood of each caption given each
+crop of the object (captioner/likelihood_scorer.py), so no second model is needed; `--method blip2_ll` is the same under BLIP-2.
 The reference's other methods (`llm`, `mobileclip`, `openclip` ViT-bigG-14) are refused by name.
 """
 from __future__ import annotations
@@ -23,8 +27,10 @@ from .pseudolabeler import expand_box
 
 REFUSED_METHODS = ("llm", "mobileclip", "openclip")
 BLIP2_METHODS = {"blip2_itm": "itm", "blip2_itc": "itc"}          # --method -> the scorer's head
+LIKELIHOOD_METHODS = {"blip_ll": "blip", "blip2_ll": "blip2"}     # --method -> the captioner family whose likelihood selects
 DEFAULT_MODELS = {"clip": "openai/clip-vit-base-patch32", "blip2_itm": "Salesforce/blip2-itm-vit-g-coco",
-                  "blip2_itc": "Salesforce/blip2-itm-vit-g-coco"}
+                  "blip2_itc": "Salesforce/blip2-itm-vit-g-coco", "blip_ll": "Salesforce/blip-image-captioning-base",
+                  "blip2_ll": "Salesforce/blip2-opt-2.7b"}
 REFERENCE_FRAME = (1280, 1280)       # the reference's hard-coded image size for expand_box (:346)
 
 
@@ -127,6 +133,52 @@ def blip2_pseudo_scores(grouped: Dict, scorer, head: str = "itm", expand_factor:
     return out
 
 
+def likelihood_pseudo_captions(grouped: Dict, scorer, expand_factor: float = 0.1, image_size=REFERENCE_FRAME, crop=None) -> Dict[str, dict]:
+    """grouped as for `clip_pseudo_captions`; scorer: a `CaptionLikelihoodScorer` (anything with `score_matrix(images, captions) ->
+    [n_images, n_captions]`).  Per object, every DISTINCT caption of the group (first occurrence order) is scored against EVERY crop
+    of the group - one `score_matrix` call per group, each crop encoded once - and a caption's score is the mean over the crops of
+    its mean token log-prob.  -> `clip_pseudo_captions`' structure, one entry per distinct caption: {str(key): {'captions_list':
+    [[score, caption], ...] (by score, descending, stable), 'pseudocaption': [score, caption]}}."""
+    crop = crop or device_crops(scorer, center_crop=False)
+    keys = list(grouped)
+    frames, rects, owner = [], [], {}
+    frame_idx = {}
+    for k in keys:
+        owner[k] = []
+        for inst in grouped[k]:
+            img = inst["image"]
+            fi = frame_idx.setdefault(id(img), len(frames))
+            if fi == len(frames):
+                frames.append(np.ascontiguousarray(img))
+                rects.append([])
+            rects[fi].append(crop_rect(inst["pred_box"], img.shape, expand_factor, image_size))
+            owner[k].append((fi, len(rects[fi]) - 1))
+    if not any(owner.values()):
+        return {}
+    images = crop(frames, rects)
+    first = np.cumsum([0] + [len(r) for r in rects])
+    out: Dict[str, dict] = {}
+    for k in keys:
+        if not owner[k]:
+            continue
+        order = [int(first[fi]) + j for fi, j in owner[k]]
+        if hasattr(images, "index_select"):
+            import torch
+            imgs = images.index_select(0, torch.tensor(order, device=images.device))
+        else:
+            imgs = [images[i] for i in order]
+        caps: List = []
+        for inst in grouped[k]:
+            if inst["caption"] not in caps:
+                caps.append(inst["caption"])
+        m = scorer.score_matrix(imgs, caps)
+        m = np.asarray(m.double().cpu() if hasattr(m, "cpu") else m, dtype=np.float64).reshape(len(order), len(caps))
+        lst = [[float(s), c] for s, c in zip(m.mean(axis=0), caps)]
+        lst.sort(key=lambda x: x[0], reverse=True)       # list.sort is stable: equal scores keep first-occurrence order
+        out[str(k)] = {"captions_list": lst, "pseudocaption": list(lst[0])}
+    return out
+
+
 def _instances_fields(inst, idx):
     if isinstance(inst, dict):
         info, box, cap = inst["infos"][idx], inst["pred_boxes"][idx], inst["captions"][idx]
@@ -169,18 +221,25 @@ def main(argv=None) -> int:
     if args.method in REFUSED_METHODS:
         raise SystemExit(f"--method {args.method} is not supported here (it needs models this project does not run); "
                          f"use --method clip, blip2_itm or blip2_itc")
-    if args.method != "clip" and args.method not in BLIP2_METHODS:
+    if args.method != "clip" and args.method not in BLIP2_METHODS and args.method not in LIKELIHOOD_METHODS:
         raise SystemExit(f"unknown --method {args.method!r}; supported: clip, blip2_itm, blip2_itc")
     model = args.model or DEFAULT_MODELS[args.method]
     grouped = group_records(sorted(glob.glob(os.path.join(args.file_path, "*.npz"))))
-    if args.method == "clip":
+    if args.method in LIKELIHOOD_METHODS:
+        from .captioner.likelihood_scorer import CaptionLikelihoodScorer
+        scorer = CaptionLikelihoodScorer(model, device=args.device, dtype=args.dtype, batch_size=min(args.batch_size, 32),
+                                         family=LIKELIHOOD_METHODS[args.method])
+    elif args.method == "clip":
         from .captioner.clip_scorer import ClipScorer
         scorer = ClipScorer(model, device=args.device, dtype=args.dtype, batch_size=args.batch_size)
     else:
         from .captioner.blip2_itm_scorer import Blip2ItmScorer
         scorer = Blip2ItmScorer(model, device=args.device, dtype=args.dtype, batch_size=args.batch_size)
     try:
-        result = clip_pseudo_captions(grouped, scorer) if args.method == "clip" else blip2_pseudo_scores(grouped, scorer, BLIP2_METHODS[args.method])
+        if args.method in LIKELIHOOD_METHODS:
+            result = likelihood_pseudo_captions(grouped, scorer)
+        else:
+            result = clip_pseudo_captions(grouped, scorer) if args.method == "clip" else blip2_pseudo_scores(grouped, scorer, BLIP2_METHODS[args.method])
     finally:
         scorer.close()
     print("Scoring completed. Saving scores to", args.output_csv_path)

@@ -35,7 +35,8 @@ class Captioner(_Base):
         """Get the captioner model based on the configuration settings (reference :190-202)."""
         extra = {k: getattr(cfg, k) for k in ("num_beams", "max_length", "max_new_tokens", "dtype", "batch_size", "device",
                                               "streams", "early_exit_poll", "image_size", "num_beam_groups", "tokenizer_dir",
-                                              "coalesce_rows", "cross_cache", "strict_range", "prompt", "prompt_ids", "max_prompt")
+                                              "coalesce_rows", "cross_cache", "strict_range", "prompt", "prompt_ids", "max_prompt",
+                                              "max_score_rows")
                  if hasattr(cfg, k)}
         captioner_cfg = Configuration(arch_name=cfg.arch_name, model_name=cfg.model_name,
                                       checkpoint_name=getattr(cfg, "checkpoint_name", None), height=cfg.height,
@@ -57,6 +58,15 @@ class Captioner(_Base):
             out = self.model.generate_batch(images, output_perplexity=True, **kw)
             return out["texts"], out["perplexities"]
         return self.model.generate_batch(images, **kw)["texts"]
+
+    def score_batch(self, crops, captions) -> dict:
+        """Likelihood of GIVEN captions under the captioner (BLIP): crops as for `caption_batch`, captions one per crop or a list of
+        candidates per crop -> the model's `score_captions` dict (token_logprobs, n_tokens, logprob_sum, logprob_mean, perplexity,
+        top_perplexity).  Architectures without it (CoCa, BLIP-2) refuse by name."""
+        fn = getattr(self.model, "score_captions", None)
+        if fn is None:
+            raise ValueError(f"score_batch: {type(self.model).__name__} does not score given captions (built for BLIP)")
+        return fn(crops, captions)
 
     @property
     def direct_resize_size(self):

@@ -21,6 +21,9 @@
  *   text prompt         HF modeling_blip.py:858-932 `generate(pixel_values, input_ids=...)`    cap_generate_prompted (CAP_ARCH_BLIP, greedy:
  *                       ("a picture of ..."; the decoder gets input_ids[:, :-1], column 0 = BOS);   the prompt positions run as one prefill pass),
  *                       coca_model.py:207, 280-292 `generate(text=...)` is NOT built (refused)       CapConfig.max_prompt, cap_last_prefill_passes
+ *   teacher forcing     HF modeling_blip.py / modeling_blip_2.py `forward(pixel_values, input_ids=...)`   cap_score_captions (BLIP, BLIP-2: log-prob of
+ *                       (the reference scores only text it generated itself:                       a GIVEN caption's tokens, log max softmax and
+ *                       captioning_predictor.py:34-47 `compute_perplexity`)                        arg-max per position), CapConfig.max_score_rows
  *   one crop per call   coca.py:27-33, blip2.py:24-29, goal_exploration.py:95-105,     cap_generate (rows <= 16: fused
  *                       pseudolabeler.py:673-676 (the callers hand over ONE image)      launches), cap_set_decode_path
  *   greedy stopping     HF generation/utils.py:2894-2937 (a finished row keeps its slot and   cap_set_row_compaction (the open
@@ -121,6 +124,13 @@ typedef struct CapConfig {
      * (max_batch x max_beams rows) holds.  2 .. CAP_MAX_PROMPT: the buffers a decoder pass works in hold max_batch x (max_prompt - 1)
      * rows, so the prompt positions of a full batch are ONE pass (every decoder weight read once per prefill). */
     int32_t max_prompt;
+    /* CAP_ARCH_BLIP only: scoring capacity of the arena, in decoder rows (one row per caption position).  0 (default): none reserved -
+     * the handle allocates exactly what it did before the field existed; cap_score_captions then works in passes of as many captions
+     * as the decode workspace holds (max(max_batch x max_beams, max_batch x (max_prompt - 1)) rows) and runs the head over max_batch x
+     * max_beams rows at a time.  > 0: the pass buffers AND the head's (one fp32 logits row of `vocab` columns each) hold this many
+     * rows, so N captions of L tokens are one pass with one vocabulary GEMM when N x (L - 1) <= max_score_rows (and N <= max_batch x
+     * max_beams: the self-attention caches).  The chunking changes no bits. */
+    int32_t max_score_rows;
 } CapConfig;
 enum { CAP_MAX_PROMPT = 32 };   /* prompt tokens per caption, BOS included, cap_generate_prompted takes */
 
@@ -294,6 +304,43 @@ int cap_generate_groups(CapHandle h, const void* pixels, int pixel_fmt, int B, i
 /* Prefill passes the last prompted generate on this handle ran (1 = the whole batch at once; 0 after an unprompted call). */
 int cap_last_prefill_passes(CapHandle h);
 
+/* Teacher-forced scoring of GIVEN captions (CAP_ARCH_BLIP, CAP_ARCH_BLIP2): what HF `BlipForConditionalGeneration(pixel_values, input_ids=...)` returns
+ * as `logits`, reduced on the device to the numbers a caller wants from them.  Nothing vocabulary-wide leaves the library and no
+ * [N, L, vocab] buffer exists: the head runs over as many rows as the handle's logits buffer holds and each slice is reduced at once.
+ *   pixels   B frames in pixel_fmt (device), B <= max_batch; the image side runs once per image
+ *   ids      int32 [N, L] (device), N = B * captions_per_image; caption n belongs to image n / captions_per_image; column 0 = BOS
+ *   lens     int32 [N] (device): tokens of caption n incl. BOS (and EOS / [SEP] if the end is to be scored), 2 <= lens[n] <= L, or 0 for
+ *            an absent slot (captions_per_image > 1).  Columns from lens[n] on are padding: any id; they influence nothing returned
+ *   out_token_logprobs fp32 [N, L - 1]: entry j = log_softmax(logits at position j)[ids[n][j + 1]] for j < lens[n] - 1, 0 behind
+ *   out_top_logprobs   fp32 [N, L - 1], out_top_ids int32 [N, L - 1]: log max softmax and arg-max of the same rows (the selection and
+ *            tie rule of the greedy loop) - the reference's compute_perplexity on teacher-forced logits, and where the model would have
+ *            said something else.  Where the target IS the arg-max the two log-probs are equal bit for bit
+ *   out_scored int32 [N] = lens - 1 (0 for an absent slot)
+ * The rows are the model's plain logits: no EOS mask, no MinLength.  ids and lens are the caller's to validate (engine.py does, on the
+ * host); the library clamps ids to [0, vocab) and lens - 1 to [0, L - 1].  Refused before anything is launched: a CoCa handle
+ * (by name: not built), null buffers, captions_per_image < 1, L < 2, L beyond max_len or 32 (BLIP-2: L - 1 beyond max_len, which counts
+ * the tokens behind BOS there, or num_query_tokens + L beyond max_pos), B beyond max_batch, and a request no chunking fits (one caption's
+ * rows beyond the workspace: the message names the capacity that takes it - CapConfig.max_score_rows, BLIP-2: max_batch).
+ * CAP_ARCH_BLIP2 (`Blip2ForConditionalGeneration(pixel_values, input_ids=[image tokens, BOS, caption])`): ids / lens as above (BOS first,
+ * the generation EOS last when the end is to be scored).  The encoder, the Q-Former, the projection and the prompt pass (query tokens +
+ * BOS) run once per image as in cap_generate; entry 0 of every caption comes from its image's BOS logits; the L - 2 positions behind
+ * BOS run as caption-major passes behind the image's cached prompt (opt_prefix_attention: prompt keys from the image's cache row, the
+ * caption's own from the pass; nothing is appended to the caches), in the prompt pass's buffers (max_batch x (num_query_tokens + 1)
+ * rows per pass), the final LayerNorm and the tied head over every row in slices of max_batch x max_beams rows.  int8 weights: up to
+ * the row count of 4 prompts a pass runs on the weight streams, beyond on the tiled GEMM - as the prompt pass does, so bits are the
+ * same across chunkings only within one of the two.
+ * Passes take whole images while one fits, else part of one image's captions; the result does not depend on the chunking, on the
+ * batch a caption is scored in or on the slot it sits in (tests/test_score_captions_gpu.py).  No label smoothing, no loss, no
+ * gradients. */
+int cap_score_captions(CapHandle h, const void* pixels, int pixel_fmt, int B, const int32_t* ids, const int32_t* lens, int captions_per_image,
+                       int L, float* out_token_logprobs, float* out_top_logprobs, int32_t* out_top_ids, int32_t* out_scored, void* stream);
+/* Decoder passes the last cap_score_captions on this handle ran (1 = every caption at once). */
+int cap_last_score_passes(CapHandle h);
+/* Captions of L tokens one decoder pass of cap_score_captions takes on this handle: BLIP min(max_batch x max_beams, workspace rows /
+ * (L - 1)), BLIP-2 max_batch x (num_query_tokens + 1) / (L - 2); 0 = a caption of that length cannot be scored (no chunking fits);
+ * -1: not a BLIP / BLIP-2 handle, or L outside what cap_score_captions takes. */
+int cap_score_pass_captions(CapHandle h, int L);
+
 /* Sentence encoder (CAP_ARCH_MINILM handle; weights by HF BertModel names as sentence-transformers stores them):
  * WordPiece ids int32 [B, L] incl. [CLS]/[SEP] (rows padded with any valid id), lens int32 [B] = valid tokens per row
  * -> out fp32 [B, t_hidden]: mean of the last hidden states over the valid tokens, L2-normalised
@@ -414,6 +461,13 @@ int cap_op_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, 
  * (clamped into the image's rows), and the row's own k | v are written to ITS cache at position past.  anc may be null for K = 1
  * (every position the row's own).  1 <= K <= 8, 0 <= P <= past, anc_ld >= past - P.  Same sums in the same order as
  * cap_op_opt_decode_attention: a row with the same history gives the same bits. */
+/* Self-attention of cap_score_captions' caption pass on a BLIP-2 handle, alone: n new positions of n_caps captions behind a cached
+ * prefix.  qkv [n_caps * n, 3 T] fused rows, caption-major (row = caption * n + position); caption cap0 + c belongs to image
+ * (cap0 + c) / C, whose P prefix keys are read from row `image` of kc / vc [.][Lmax][T]; the caption's own keys 0 .. position come
+ * from the rows themselves (nothing is written to the caches).  n_pos int32 (device, may be NULL): rows with position >=
+ * n_pos[cap0 + c] are left untouched.  head_dim = T / H a multiple of 8 up to 128, P + n <= 1024.  out [n_caps * n, T]. */
+int cap_op_opt_prefix_attention(int dtype, const void* qkv, const void* kc, const void* vc, void* out, int n_caps, int n, int cap0, int C,
+                                const int32_t* n_pos, int T, int H, int Lmax, int P, void* stream);
 int cap_op_opt_beam_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int K, int T, int H, int Lmax, int P,
                                      int past, const int32_t* anc, int anc_ld, void* stream);
 /* k | v columns of fused rows qkv [B * L, 3 T] -> caches kc / vc [B][Lmax][T] at positions pos0 .. pos0 + L - 1 (CAP_F32_SPLIT: fp32). */
@@ -571,6 +625,11 @@ int cap_op_beam_peek(void* state, int B, int K, int max_len, int parity, int32_t
 int cap_op_select_logprob(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int min_len, int force_eos,
                           int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths,
                           float* logprobs, int lp_ld, int32_t* scored, void* stream);
+/* The head consumer of cap_score_captions alone: logits fp32 [rows][ld] (ld >= V, ld % 4 == 0, 16-byte aligned; columns V .. ld - 1 are
+ * never read); per row r with live[r] > 0: out_target[r] = log_softmax(row)[targets[r]] (target clamped to [0, V)), out_top[r] = log max
+ * softmax, out_top_id[r] = arg-max (lowest index among equal maxima); a dead row (live[r] <= 0) gets zeros and is not read. */
+int cap_op_target_logprob(const float* logits, int ld, int V, int rows, const int32_t* targets, const int32_t* live, float* out_target,
+                          float* out_top, int32_t* out_top_id, void* stream);
 /* cap_op_select_logprob with the vocabulary accumulator of cap_generate_vocab: vocab_acc fp32 [., acc_ld] (caption rows, updated
  * in place for the open captions: entry i < V becomes the larger of itself and the row's softmax at i; acc_ld >= V, acc_ld % 4 == 0,
  * 16-byte aligned).  logprobs / scored are required. */
