@@ -1141,42 +1141,70 @@ __global__ __launch_bounds__(64) void generic_decode_attention_kernel(const T* _
 // HD8 = head_dim / 8 when it is known at compile time (10: OPT-2.7b, 8, 16), 0 = any: with a constant trip count a lane's
 // 16-byte loads of a key row are all issued before the first FMA (a runtime loop serialises load -> fma, 10 round trips).
 //
-// BEAM: the rows are r = image * K + beam of a beam search (beam.hip) and a row's history is spread over the caches of its image's
+// The walk is one body, opt_decode_attention_body, over a row's Lk keys; where key / value j sits is asked of a source: k(j, rs) and
+// v(j, rs) point at the head's hd values, locate(j, rs) runs once per key in the score pass ahead of them (rs: an LDS table of
+// OPT_DECODE_MAX_KEYS entries for a source with TABLE, else unused), and append(d) rides the loop that stages q - the decode forms
+// store dimension d of the step's key and value in the row's caches there, their loads in flight with q's.  What is summed, and in which order, does not depend on the source:
+// rows with the same history give the same bits under all three.
+//
+// The greedy step: the row's own caches [Lmax][Tw], the step's own key and value straight from its q|k|v row.
+template <typename T>
+struct OptOwnKeys {
+    static constexpr bool TABLE = false;
+    const T *kb, *vb, *row;     // position 0 of the row's caches and its q|k|v row, at this head
+    T *kd, *vd;                 // position `past` of the row's caches: the step's key and value go there
+    int Tw, past;
+    __device__ void append(int d) const { kd[d] = row[Tw + d]; vd[d] = row[2 * Tw + d]; }
+    __device__ void locate(int, int*) const {}
+    __device__ const T* k(int j, const int*) const { return j == past ? row + Tw : kb + (size_t)j * Tw; }
+    __device__ const T* v(int j, const int*) const { return j == past ? row + 2 * Tw : vb + (size_t)j * Tw; }
+};
+// A beam search's step: the rows are r = image * K + beam (beam.hip) and a row's history is spread over the caches of its image's
 // rows, nothing having been copied on a reorder.  Keys j < P (the prompt: query tokens + BOS) sit in the cache of the image's row
-// image * K, written once per image by the prompt pass; key P + g, g < past - P, sits at the same position of the cache of row
-// anc[r * anc_ld + g], the row that generated it (clamped into the image's own rows, so no table content reads outside them); the
-// step's own key is appended to row r's cache at `past`.  The physical row of every key is looked up once, in the score pass, and kept
-// in LDS for P.V.  What is summed, and in which order, does not depend on BEAM: a beam row and a greedy row with the same history give
-// the same bits.
-template <typename T, int HD8, typename TO, bool BEAM>
-__device__ __forceinline__ void opt_decode_attention_body(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
-                                                          TO* __restrict__ out, int Tw, int H, int hd, int Lmax, int past, float scale,
-                                                          const int* __restrict__ anc, int anc_ld, int K, int P) {
+// r0 = image * K, written once per image by the prompt pass; key P + g, g < past - P, sits at the same position of the cache of row
+// anc[g] (the row's table entries), the row that generated it (clamped into the image's own rows, so no table content reads outside
+// them); the step's own key is appended to row r's cache at `past` and read from its q|k|v row.  The physical row of every key is looked
+// up once, in the score pass, and kept in LDS for P.V.
+template <typename T>
+struct OptBeamKeys {
+    static constexpr bool TABLE = true;
+    const T *kb, *vb, *row;     // position 0 of cache row 0 and the row's q|k|v row, at this head
+    T *kd, *vd;                 // position `past` of the row's own caches
+    const int* anc;
+    int Tw, Lmax, past, P, r0, K;
+    __device__ void append(int d) const { kd[d] = row[Tw + d]; vd[d] = row[2 * Tw + d]; }
+    __device__ void locate(int j, int* rs) const { rs[j] = j < P || j == past ? r0 : min(max(anc[j - P], r0), r0 + K - 1); }
+    __device__ const T* k(int j, const int* rs) const { return j == past ? row + Tw : kb + ((size_t)rs[j] * Lmax + j) * Tw; }
+    __device__ const T* v(int j, const int* rs) const { return j == past ? row + 2 * Tw : vb + ((size_t)rs[j] * Lmax + j) * Tw; }
+};
+// Teacher-forced scoring: keys j < P from the image's cache row, then the caption's own positions 0 .. t from the pass's q|k|v rows.
+template <typename T>
+struct OptPrefixKeys {
+    static constexpr bool TABLE = false;
+    const T *kb, *vb, *own;     // position 0 of the image's caches and of this caption in the pass, at this head
+    int Tw, P;
+    __device__ void append(int) const {}      // nothing is appended: the caches are read only
+    __device__ void locate(int, int*) const {}
+    __device__ const T* k(int j, const int*) const { return j < P ? kb + (size_t)j * Tw : own + (size_t)(j - P) * 3 * Tw + Tw; }
+    __device__ const T* v(int j, const int*) const { return j < P ? vb + (size_t)j * Tw : own + (size_t)(j - P) * 3 * Tw + 2 * Tw; }
+};
+
+// q: the query row at head h; orow: the output row (its head h is written)
+template <typename T, int HD8, typename TO, typename Src>
+__device__ __forceinline__ void opt_decode_attention_body(const T* q, TO* orow, int h, int hd, int Lk, float scale, const Src src) {
     __shared__ float qs[128], ps[OPT_DECODE_MAX_KEYS], os[4][128];
-    __shared__ int rs[BEAM ? OPT_DECODE_MAX_KEYS : 1];      // BEAM: physical row of key j
-    const int b = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x;
-    const T* row = qkv + (size_t)b * 3 * Tw + h * hd;
-    // not BEAM: row b's own cache.  BEAM: position 0 of cache row 0, a key's row chosen per key below
-    const T* kb = kc + (BEAM ? (size_t)0 : (size_t)b * Lmax * Tw) + h * hd;
-    const T* vb = vc + (BEAM ? (size_t)0 : (size_t)b * Lmax * Tw) + h * hd;
-    const int Lk = past + 1;
-    [[maybe_unused]] const int r0 = BEAM ? b / K * K : 0;    // first row of this row's image: the prompt's
-    // offset of cached key j (< past) from kb / vb
-    auto key_at = [&](int j) -> size_t {
-        if constexpr (BEAM) return ((size_t)rs[j] * Lmax + j) * Tw;
-        else return (size_t)j * Tw;
-    };
+    __shared__ int rs[Src::TABLE ? OPT_DECODE_MAX_KEYS : 1];
+    const int lane = threadIdx.x;
     const int n8 = HD8 ? HD8 : hd >> 3;
     for (int d = lane; d < hd; d += 64) {
-        qs[d] = to_f32(row[d]) * scale;
-        kc[((size_t)b * Lmax + past) * Tw + h * hd + d] = row[Tw + d];
-        vc[((size_t)b * Lmax + past) * Tw + h * hd + d] = row[2 * Tw + d];
+        qs[d] = to_f32(q[d]) * scale;
+        src.append(d);
     }
     __syncthreads();
     float m = -INFINITY;
     for (int j = lane; j < Lk; j += 64) {
-        if constexpr (BEAM) rs[j] = j < P || j == past ? r0 : min(max(anc[(size_t)b * anc_ld + j - P], r0), r0 + K - 1);
-        const T* kr = j == past ? row + Tw : kb + key_at(j);
+        src.locate(j, rs);
+        const T* kr = src.k(j, rs);
         float sc = 0.f;
         if constexpr (HD8 > 0) {
             float kk[HD8][8];
@@ -1215,7 +1243,7 @@ __device__ __forceinline__ void opt_decode_attention_body(const T* __restrict__ 
         for (; j + 12 < Lk; j += 16) {            // four keys of this lane's group per trip, loads first
             float vv[4][8];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) load8<T>((j + 4 * u == past ? row + 2 * Tw : vb + key_at(j + 4 * u)) + dc, vv[u]);
+            for (int u = 0; u < 4; ++u) load8<T>(src.v(j + 4 * u, rs) + dc, vv[u]);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const float pj = ps[j + 4 * u];
@@ -1225,7 +1253,7 @@ __device__ __forceinline__ void opt_decode_attention_body(const T* __restrict__ 
         }
         for (; j < Lk; j += 4) {
             float vv[8];
-            load8<T>((j == past ? row + 2 * Tw : vb + key_at(j)) + dc, vv);
+            load8<T>(src.v(j, rs) + dc, vv);
             const float pj = ps[j];
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = fmaf(pj, vv[e], o[e]);
@@ -1235,19 +1263,28 @@ __device__ __forceinline__ void opt_decode_attention_body(const T* __restrict__ 
     for (int e = 0; e < 8; ++e) os[jg][dc + e] = o[e];
     __syncthreads();
     const float inv = 1.0f / l;
-    for (int d = lane; d < hd; d += 64) store1(out + (size_t)b * Tw, h * hd + d, (os[0][d] + os[1][d] + os[2][d] + os[3][d]) * inv);
+    for (int d = lane; d < hd; d += 64) store1(orow, h * hd + d, (os[0][d] + os[1][d] + os[2][d] + os[3][d]) * inv);
 }
 template <typename T, int HD8, typename TO = T>
 __global__ __launch_bounds__(64) void opt_decode_attention_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
                                                                   TO* __restrict__ out, int Tw, int H, int hd, int Lmax, int past,
                                                                   float scale) {
-    opt_decode_attention_body<T, HD8, TO, false>(qkv, kc, vc, out, Tw, H, hd, Lmax, past, scale, nullptr, 0, 1, 0);
+    const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const T* row = qkv + (size_t)b * 3 * Tw + h * hd;
+    const size_t own = (size_t)b * Lmax * Tw + h * hd, at = own + (size_t)past * Tw;      // positions 0 and `past` of row b's caches
+    opt_decode_attention_body<T, HD8, TO>(row, out + (size_t)b * Tw, h, hd, past + 1, scale,
+                                          OptOwnKeys<T>{kc + own, vc + own, row, kc + at, vc + at, Tw, past});
 }
 template <typename T, int HD8, typename TO = T>
 __global__ __launch_bounds__(64) void opt_beam_decode_attention_kernel(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
                                                                        TO* __restrict__ out, int Tw, int H, int hd, int Lmax, int past,
                                                                        float scale, const int* __restrict__ anc, int anc_ld, int K, int P) {
-    opt_decode_attention_body<T, HD8, TO, true>(qkv, kc, vc, out, Tw, H, hd, Lmax, past, scale, anc, anc_ld, K, P);
+    const int b = blockIdx.x / H, h = blockIdx.x % H;
+    const T* row = qkv + (size_t)b * 3 * Tw + h * hd;
+    const size_t at = ((size_t)b * Lmax + past) * Tw + h * hd;      // position `past` of row b's own caches
+    opt_decode_attention_body<T, HD8, TO>(row, out + (size_t)b * Tw, h, hd, past + 1, scale,
+                                          OptBeamKeys<T>{kc + h * hd, vc + h * hd, row, kc + at, vc + at, anc + (size_t)b * anc_ld, Tw, Lmax, past, P,
+                                                         b / K * K, K});
 }
 
 // Teacher-forced scoring (cap_score_captions, BLIP-2): self-attention of n NEW positions per caption behind an image's cached prompt.
@@ -1256,89 +1293,19 @@ __global__ __launch_bounds__(64) void opt_beam_decode_attention_kernel(const T* 
 // (kc / vc [image][Lmax][Tw], what the prompt pass wrote), then the caption's own positions 0 .. t straight from the pass's rows
 // cl * n + (j - P) - nothing is appended to the caches, so any number of captions score against one image's prompt.  n_pos (optional):
 // rows with t >= n_pos[cap0 + cl] are left untouched (behind the caption's end; an absent slot has 0).
-// One wave per (row, head), opt_decode_attention_body's walk: lanes over keys for the scores (HD8 16-byte loads of a key row issued
-// before the first FMA), softmax through LDS, then (key group of 4) x (8-dim chunk) for P.V with a 4-way sum - the same sums in the same
-// order as the decode step with past = P + t, so a caption scored here and decoded token by token see the same bits.
+// One wave per (row, head) on opt_decode_attention_body: the decode step's walk with past = P + t, so a caption scored here and decoded
+// token by token see the same bits.
 template <typename T, int HD8, typename TO>
 __global__ __launch_bounds__(64) void opt_prefix_attention_kernel(const T* __restrict__ qkv, const T* __restrict__ kc, const T* __restrict__ vc,
                                                                   TO* __restrict__ out, int Tw, int H, int hd, int Lmax, int P, int n,
                                                                   int cap0, int C, const int* __restrict__ n_pos, float scale) {
-    __shared__ float qs[128], ps[OPT_DECODE_MAX_KEYS], os[4][128];
-    const int r = blockIdx.x / H, h = blockIdx.x % H, lane = threadIdx.x;
+    const int r = blockIdx.x / H, h = blockIdx.x % H;
     const int cl = r / n, t = r - cl * n, img = (cap0 + cl) / C;
     if (n_pos && t >= n_pos[cap0 + cl]) return;            // uniform over the block: before any barrier
-    const T* row = qkv + (size_t)r * 3 * Tw + h * hd;
     const T* own = qkv + (size_t)cl * n * 3 * Tw + h * hd;  // position 0 of this caption in the pass
-    const T* kb = kc + (size_t)img * Lmax * Tw + h * hd;
-    const T* vb = vc + (size_t)img * Lmax * Tw + h * hd;
-    const int Lk = P + t + 1;
-    auto k_at = [&](int j) -> const T* { return j < P ? kb + (size_t)j * Tw : own + (size_t)(j - P) * 3 * Tw + Tw; };
-    auto v_at = [&](int j) -> const T* { return j < P ? vb + (size_t)j * Tw : own + (size_t)(j - P) * 3 * Tw + 2 * Tw; };
-    const int n8 = HD8 ? HD8 : hd >> 3;
-    for (int d = lane; d < hd; d += 64) qs[d] = to_f32(row[d]) * scale;
-    __syncthreads();
-    float m = -INFINITY;
-    for (int j = lane; j < Lk; j += 64) {
-        const T* kr = k_at(j);
-        float sc = 0.f;
-        if constexpr (HD8 > 0) {
-            float kk[HD8][8];
-#pragma unroll
-            for (int c = 0; c < HD8; ++c) load8<T>(kr + c * 8, kk[c]);
-#pragma unroll
-            for (int c = 0; c < HD8; ++c)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) sc = fmaf(qs[c * 8 + e], kk[c][e], sc);
-        } else {
-            for (int c = 0; c < n8; ++c) {
-                float kk[8];
-                load8<T>(kr + c * 8, kk);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) sc = fmaf(qs[c * 8 + e], kk[e], sc);
-            }
-        }
-        ps[j] = sc;
-        m = fmaxf(m, sc);
-    }
-    m = wave_max(m);
-    float l = 0.f;
-    for (int j = lane; j < Lk; j += 64) {
-        const float pj = expf(ps[j] - m);
-        ps[j] = pj;
-        l += pj;
-    }
-    l = wave_sum(l);
-    __syncthreads();
-    const int jg = lane >> 4, dc = (lane & 15) * 8;
-    float o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = 0.f;
-    if (dc < hd) {
-        int j = jg;
-        for (; j + 12 < Lk; j += 16) {            // four keys of this lane's group per trip, loads first
-            float vv[4][8];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) load8<T>(v_at(j + 4 * u) + dc, vv[u]);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float pj = ps[j + 4 * u];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = fmaf(pj, vv[u][e], o[e]);
-            }
-        }
-        for (; j < Lk; j += 4) {
-            float vv[8];
-            load8<T>(v_at(j) + dc, vv);
-            const float pj = ps[j];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = fmaf(pj, vv[e], o[e]);
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) os[jg][dc + e] = o[e];
-    __syncthreads();
-    const float inv = 1.0f / l;
-    for (int d = lane; d < hd; d += 64) store1(out + (size_t)r * Tw, h * hd + d, (os[0][d] + os[1][d] + os[2][d] + os[3][d]) * inv);
+    const size_t cache = (size_t)img * Lmax * Tw + h * hd;
+    opt_decode_attention_body<T, HD8, TO>(qkv + (size_t)r * 3 * Tw + h * hd, out + (size_t)r * Tw, h, hd, P + t + 1, scale,
+                                          OptPrefixKeys<T>{kc + cache, vc + cache, own, Tw, P});
 }
 
 // Caption-pass inputs of the same call: row r = caption * n + t of x [rows, T] = token table[ids[caption * ids_ld + t]] + position
@@ -1867,65 +1834,74 @@ int launch_generic_attention(int dtype, const void* q, long ldq, long qbs, const
     return 0;
 }
 
-int launch_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int T, int H, int Lmax,
-                                int past, hipStream_t s, int out_dtype) {
+// One instantiation of the OPT wave walk's kernels (opt_decode_attention_body): element types in and out, HD8
+template <typename T_, int HD8_, typename TO_>
+struct OptWalk {
+    using T = T_;
+    using TO = TO_;
+    static constexpr int HD8 = HD8_;
+};
+// What the three launchers of the walk share, after the checks that are their own: the output-type rule, the head widths the walk
+// takes, `past` (the newest key of the longest row) inside the LDS score array, the pointers, the scale, and the one dispatch over
+// (bf16 | fp32 -> G8 | fp32) x head_dim (80 | 64 | 128 | any) - launch(OptWalk<...>(), head_dim, scale) starts the caller's kernel.
+template <typename Launch>
+static int opt_attention_launch(const char* name, int dtype, int out_dtype, const void* qkv, const void* kc, const void* vc, const void* out,
+                                int T, int H, int past, Launch&& launch) {
     if (out_dtype < 0) out_dtype = dtype;
     if (out_dtype != dtype && !(dtype == CAP_DT_F32 && out_dtype == CAP_DT_G8 && T % 8 == 0)) {
-        cap_set_error("opt_decode_attention: output type %d for input type %d is not supported here", out_dtype, dtype);
+        cap_set_error("%s: output type %d for input type %d is not supported here", name, out_dtype, dtype);
         return -1;
     }
     const int hd = H > 0 ? T / H : 0;
-    if (B < 1 || H < 1 || T % H != 0 || hd % 8 != 0 || hd < 8 || hd > 128 || past < 0 || past + 1 > OPT_DECODE_MAX_KEYS || past >= Lmax) {
-        cap_set_error("opt_decode_attention: unsupported shape T=%d H=%d past=%d Lmax=%d (head_dim a multiple of 8 up to 128, past < min(Lmax, %d))",
-                      T, H, past, Lmax, OPT_DECODE_MAX_KEYS);
+    if (H < 1 || T % H != 0 || hd % 8 != 0 || hd < 8 || hd > 128 || past < 0 || past + 1 > OPT_DECODE_MAX_KEYS) {
+        cap_set_error("%s: unsupported shape T=%d H=%d past=%d (head_dim a multiple of 8 up to 128, the newest key's position past < %d)", name,
+                      T, H, past, OPT_DECODE_MAX_KEYS);
         return -1;
     }
-    if (!qkv || !kc || !vc || !out) { cap_set_error("opt_decode_attention: null pointer"); return -1; }
+    if (!qkv || !kc || !vc || !out) { cap_set_error("%s: null pointer", name); return -1; }
     const float scale = 1.0f / sqrtf((float)hd);
-#define CAP_ODA(TT, H8, TO)                                                                                             \
-    hipLaunchKernelGGL((opt_decode_attention_kernel<TT, H8, TO>), dim3(B * H), dim3(64), 0, s, (const TT*)qkv, (TT*)kc, (TT*)vc,  \
-                       (TO*)out, T, H, hd, Lmax, past, scale)
-    if (dtype == CAP_DT_BF16) {
-        if (hd == 80) CAP_ODA(bf16_t, 10, bf16_t); else if (hd == 64) CAP_ODA(bf16_t, 8, bf16_t); else if (hd == 128) CAP_ODA(bf16_t, 16, bf16_t); else CAP_ODA(bf16_t, 0, bf16_t);
-    } else if (out_dtype == CAP_DT_G8) {
-        if (hd == 80) CAP_ODA(float, 10, g8_t); else if (hd == 64) CAP_ODA(float, 8, g8_t); else if (hd == 128) CAP_ODA(float, 16, g8_t); else CAP_ODA(float, 0, g8_t);
-    } else {
-        if (hd == 80) CAP_ODA(float, 10, float); else if (hd == 64) CAP_ODA(float, 8, float); else if (hd == 128) CAP_ODA(float, 16, float); else CAP_ODA(float, 0, float);
-    }
-#undef CAP_ODA
+    auto by_hd = [&](auto t, auto to) {
+        using TT = decltype(t);
+        using TO = decltype(to);
+        if (hd == 80) launch(OptWalk<TT, 10, TO>(), hd, scale);
+        else if (hd == 64) launch(OptWalk<TT, 8, TO>(), hd, scale);
+        else if (hd == 128) launch(OptWalk<TT, 16, TO>(), hd, scale);
+        else launch(OptWalk<TT, 0, TO>(), hd, scale);
+    };
+    if (dtype == CAP_DT_BF16) by_hd(bf16_t(), bf16_t());
+    else if (out_dtype == CAP_DT_G8) by_hd(float(), g8_t());
+    else by_hd(float(), float());
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }
-int launch_opt_prefix_attention(int dtype, const void* qkv, const void* kc, const void* vc, void* out, int n_caps, int n, int cap0, int C,
-                                const int* n_pos, int T, int H, int Lmax, int P, hipStream_t s, int out_dtype) {
-    if (out_dtype < 0) out_dtype = dtype;
-    if (out_dtype != dtype && !(dtype == CAP_DT_F32 && out_dtype == CAP_DT_G8 && T % 8 == 0)) {
-        cap_set_error("opt_prefix_attention: output type %d for input type %d is not supported here", out_dtype, dtype);
+int launch_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int T, int H, int Lmax,
+                                int past, hipStream_t s, int out_dtype) {
+    if (B < 1 || past >= Lmax) {
+        cap_set_error("opt_decode_attention: unsupported shape B=%d past=%d Lmax=%d (the step's key needs a cache position: past < Lmax)", B, past, Lmax);
         return -1;
     }
-    const int hd = H > 0 ? T / H : 0;
-    if (n_caps < 1 || n < 1 || cap0 < 0 || C < 1 || H < 1 || T % H != 0 || hd % 8 != 0 || hd < 8 || hd > 128 || P < 1 || P > Lmax ||
-        P + n > OPT_DECODE_MAX_KEYS || (long long)n_caps * n * H > 0x7fffffffLL) {
-        cap_set_error("opt_prefix_attention: unsupported shape captions=%d positions=%d from caption %d (%d per image) T=%d H=%d prefix=%d Lmax=%d "
-                      "(head_dim a multiple of 8 up to 128, 1 <= prefix <= Lmax, prefix + positions <= %d)", n_caps, n, cap0, C, T, H, P, Lmax,
+    return opt_attention_launch("opt_decode_attention", dtype, out_dtype, qkv, kc, vc, out, T, H, past, [&](auto w, int hd, float scale) {
+        using W = decltype(w);
+        using TT = typename W::T;
+        hipLaunchKernelGGL((opt_decode_attention_kernel<TT, W::HD8, typename W::TO>), dim3(B * H), dim3(64), 0, s, (const TT*)qkv, (TT*)kc,
+                           (TT*)vc, (typename W::TO*)out, T, H, hd, Lmax, past, scale);
+    });
+}
+int launch_opt_prefix_attention(int dtype, const void* qkv, const void* kc, const void* vc, void* out, int n_caps, int n, int cap0, int C,
+                                const int* n_pos, int T, int H, int Lmax, int P, hipStream_t s, int out_dtype) {
+    if (n_caps < 1 || n < 1 || cap0 < 0 || C < 1 || H < 1 || P < 1 || P > Lmax || (long long)P + n > OPT_DECODE_MAX_KEYS ||
+        (long long)n_caps * n * H > 0x7fffffffLL) {
+        cap_set_error("opt_prefix_attention: unsupported shape captions=%d positions=%d from caption %d (%d per image) H=%d prefix=%d Lmax=%d "
+                      "(1 <= prefix <= Lmax, prefix + positions <= %d, captions x positions x H inside int32)", n_caps, n, cap0, C, H, P, Lmax,
                       OPT_DECODE_MAX_KEYS);
         return -1;
     }
-    if (!qkv || !kc || !vc || !out) { cap_set_error("opt_prefix_attention: null pointer"); return -1; }
-    const float scale = 1.0f / sqrtf((float)hd);
-#define CAP_OPA(TT, H8, TO)                                                                                                      \
-    hipLaunchKernelGGL((opt_prefix_attention_kernel<TT, H8, TO>), dim3(n_caps * n * H), dim3(64), 0, s, (const TT*)qkv, (const TT*)kc, \
-                       (const TT*)vc, (TO*)out, T, H, hd, Lmax, P, n, cap0, C, n_pos, scale)
-    if (dtype == CAP_DT_BF16) {
-        if (hd == 80) CAP_OPA(bf16_t, 10, bf16_t); else if (hd == 64) CAP_OPA(bf16_t, 8, bf16_t); else if (hd == 128) CAP_OPA(bf16_t, 16, bf16_t); else CAP_OPA(bf16_t, 0, bf16_t);
-    } else if (out_dtype == CAP_DT_G8) {
-        if (hd == 80) CAP_OPA(float, 10, g8_t); else if (hd == 64) CAP_OPA(float, 8, g8_t); else if (hd == 128) CAP_OPA(float, 16, g8_t); else CAP_OPA(float, 0, g8_t);
-    } else {
-        if (hd == 80) CAP_OPA(float, 10, float); else if (hd == 64) CAP_OPA(float, 8, float); else if (hd == 128) CAP_OPA(float, 16, float); else CAP_OPA(float, 0, float);
-    }
-#undef CAP_OPA
-    CAP_HIP_CHECK(hipGetLastError());
-    return 0;
+    return opt_attention_launch("opt_prefix_attention", dtype, out_dtype, qkv, kc, vc, out, T, H, P + n - 1, [&](auto w, int hd, float scale) {
+        using W = decltype(w);
+        using TT = typename W::T;
+        hipLaunchKernelGGL((opt_prefix_attention_kernel<TT, W::HD8, typename W::TO>), dim3(n_caps * n * H), dim3(64), 0, s, (const TT*)qkv,
+                           (const TT*)kc, (const TT*)vc, (typename W::TO*)out, T, H, hd, Lmax, P, n, cap0, C, n_pos, scale);
+    });
 }
 int launch_opt_caption_inputs(const int* ids, int ids_ld, int n_caps, int n, int P, const float* tok, const float* pos, float* x, int T, int V,
                               hipStream_t s) {
@@ -1941,40 +1917,25 @@ int launch_opt_caption_inputs(const int* ids, int ids_ld, int n_caps, int n, int
 // row that generated key P + g of row r's history, for g < past - P (null only where no table is needed: K == 1, every key its own).
 int launch_opt_beam_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int K, int T, int H, int Lmax,
                                      int P, int past, const int* anc, int anc_ld, hipStream_t s, int out_dtype) {
-    if (out_dtype < 0) out_dtype = dtype;
-    if (out_dtype != dtype && !(dtype == CAP_DT_F32 && out_dtype == CAP_DT_G8 && T % 8 == 0)) {
-        cap_set_error("opt_beam_decode_attention: output type %d for input type %d is not supported here", out_dtype, dtype);
-        return -1;
-    }
-    const int hd = H > 0 ? T / H : 0;
-    if (B < 1 || H < 1 || T % H != 0 || hd % 8 != 0 || hd < 8 || hd > 128 || past < 0 || past + 1 > OPT_DECODE_MAX_KEYS || past >= Lmax) {
-        cap_set_error("opt_beam_decode_attention: unsupported shape T=%d H=%d past=%d Lmax=%d (head_dim a multiple of 8 up to 128, past < min(Lmax, %d))",
-                      T, H, past, Lmax, OPT_DECODE_MAX_KEYS);
-        return -1;
-    }
     if (K < 1 || K > 8 || P < 0 || P > past || (anc && anc_ld < past - P)) {
         cap_set_error("opt_beam_decode_attention: beams=%d (1..8), prompt keys=%d of past=%d, ancestry rows of %d entries (>= past - prompt)",
                       K, P, past, anc_ld);
         return -1;
     }
-    if (!qkv || !kc || !vc || !out) { cap_set_error("opt_beam_decode_attention: null pointer"); return -1; }
     if (!anc && K > 1) { cap_set_error("opt_beam_decode_attention: %d beams need an ancestry table (null)", K); return -1; }
-    const float scale = 1.0f / sqrtf((float)hd);
     // without a table (K == 1) every key is the row's own: the greedy kernel, whose caches are the same [rows][Lmax][T]
     if (!anc) return launch_opt_decode_attention(dtype, qkv, kc, vc, out, B, T, H, Lmax, past, s, out_dtype);
-#define CAP_OBA(TT, H8, TO)                                                                                             \
-    hipLaunchKernelGGL((opt_beam_decode_attention_kernel<TT, H8, TO>), dim3(B * K * H), dim3(64), 0, s, (const TT*)qkv, (TT*)kc, \
-                       (TT*)vc, (TO*)out, T, H, hd, Lmax, past, scale, anc, anc_ld, K, P)
-    if (dtype == CAP_DT_BF16) {
-        if (hd == 80) CAP_OBA(bf16_t, 10, bf16_t); else if (hd == 64) CAP_OBA(bf16_t, 8, bf16_t); else if (hd == 128) CAP_OBA(bf16_t, 16, bf16_t); else CAP_OBA(bf16_t, 0, bf16_t);
-    } else if (out_dtype == CAP_DT_G8) {
-        if (hd == 80) CAP_OBA(float, 10, g8_t); else if (hd == 64) CAP_OBA(float, 8, g8_t); else if (hd == 128) CAP_OBA(float, 16, g8_t); else CAP_OBA(float, 0, g8_t);
-    } else {
-        if (hd == 80) CAP_OBA(float, 10, float); else if (hd == 64) CAP_OBA(float, 8, float); else if (hd == 128) CAP_OBA(float, 16, float); else CAP_OBA(float, 0, float);
+    if (B < 1 || past >= Lmax) {
+        cap_set_error("opt_beam_decode_attention: unsupported shape B=%d past=%d Lmax=%d (the step's key needs a cache position: past < Lmax)", B, past,
+                      Lmax);
+        return -1;
     }
-#undef CAP_OBA
-    CAP_HIP_CHECK(hipGetLastError());
-    return 0;
+    return opt_attention_launch("opt_beam_decode_attention", dtype, out_dtype, qkv, kc, vc, out, T, H, past, [&](auto w, int hd, float scale) {
+        using W = decltype(w);
+        using TT = typename W::T;
+        hipLaunchKernelGGL((opt_beam_decode_attention_kernel<TT, W::HD8, typename W::TO>), dim3(B * K * H), dim3(64), 0, s, (const TT*)qkv,
+                           (TT*)kc, (TT*)vc, (typename W::TO*)out, T, H, hd, Lmax, past, scale, anc, anc_ld, K, P);
+    });
 }
 int launch_opt_prefill_inputs(const float* proj, const float* tok, const float* pos, float* x, int B, int nq, int T, int bos,
                               hipStream_t s) {

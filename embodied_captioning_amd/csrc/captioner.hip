@@ -772,10 +772,7 @@ int select_greedy_step(Captioner* m, const CapGenerateArgs& a, int R, int step, 
 }
 
 // ---------------------------------------------------------------------------------------------- BLIP-2 OPT
-int run_encoder(Captioner* m, const void* pixels, int fmt, int B, float* out_embeds, hipStream_t s);
-int gemm_partial(Captioner* m, hipStream_t s, const char* tag, const void* A, const void* W, float* part, int R, int N,
-                 int K, int max_S, int* S_out, const int* m_live = nullptr);
-__global__ void init_seq_kernel(int* seq, int* fin, int* len, int R, int L, int bos, int pad);
+// (the builder; the OPT decoder and the runs sit behind the decoder sections they call, ahead of the C ABI)
 __global__ void copy_new_tokens_kernel(const int* seq, int seq_ld, int P, const int* lens, int* out_ids, int* out_len, int B, int n) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * n; i += gridDim.x * blockDim.x) out_ids[i] = seq[(size_t)(i / n) * seq_ld + P + i % n];
     if (out_len)
@@ -996,311 +993,6 @@ int build_blip2_itm(Captioner* m) {
     return alloc_post_rows(m, m->tr, Bm * c.max_len, Q, F);
 }
 
-// ViT-g over B images -> emb_t [B * NT, D] (post_layernorm on every token), then the cross-attention K/V of every cross layer of
-// the Q-Former (they depend on the image alone) -> itm_ckv: what an ITC and an ITM call on this image batch both read.
-int run_itm_images(Captioner* m, const void* pixels, int fmt, int B, hipStream_t s) {
-    const CapConfig& c = m->c;
-    const int D = c.v_hidden, Q = c.q_hidden, NT = m->NT;
-    m->itm_B = 0;
-    TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
-    size_t slot = 0;
-    for (const PostLayer& L : m->pl) {
-        if (!L.has_cross) continue;
-        TRY(gemm(m, s, kItmQueryTags.ckv, m->emb_t, D, L.w_ckv, D, itm_ckv_slot(m, slot++), 2 * Q, L.b_ckv, nullptr, B * NT, 2 * Q, D, 0,
-                 m->attn_f32()));
-    }
-    m->itm_B = B;
-    return 0;
-}
-
-// ---- The OPT decoder (pre-LN blocks: what follows a residual add is always a LayerNorm).
-// One projection over `rows` rows, left for a consumer to finish: in place (ln == false: bias + act -> out_t, of type out_dt -
-// split mode: fp32 for q|k|v, G8 for a GEMM operand) or as *S_out slice sums in m->dpart for the reduce + LayerNorm consumer.
-//   int8 weights (W = fragment-ordered bytes, wscale = row scales), tiled: a batch's prompt pass, B x 33 rows, is a GEMM proper.
-//     The matrix is unpacked into a row-major bf16 scratch of its INTEGERS (exact), multiplied by the tiled kernel into fp32 and
-//     the row scales applied to that output (S = 1): (A . q^T) * scale + bias as in the weight-streaming kernel, the sums in the
-//     tiled kernel's order.  Measured at 32 crops (us per fc1 GEMM): 365 on the rows-walking weight-stream kernel, ~135 here.
-//   int8 weights otherwise: the weight-streaming kernel, which takes any row count (further row groups re-read a unit's bytes
-//     from the XCD's L2).
-//   bf16 at a shape the weight-streaming kernel takes: that kernel - at a few dozen rows every GEMM is a weight stream, so K is
-//     split over blocks (all slabs of a block in flight at once).  Otherwise the tiled split-K GEMM with a reduce kernel.
-// Apart from `tiled` the choice depends on dtype and (N, K) only - never on the row count.
-int opt_gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, const void* W, const float* bias, int act, void* out_t,
-             int rows, int N, int K, bool ln, int* S_out, int out_dt, const float* wscale, bool tiled) {
-    if (m->wq8 && !tiled) {
-        const int S8 = skinny_i8_plan(N, K, !ln);
-        ProfScope ps(m, s, tag, 2.0 * rows * N * K,
-                     (double)rows * K * 2 + (double)N * K + (ln ? (double)S8 * rows * N * 4 : (double)rows * N * 2));
-        *S_out = S8;
-        return launch_gemm_skinny_i8(A, K, W, wscale, bias, act, out_t, N, ln ? m->dpart : nullptr, rows, N, K, s) == S8 ? 0 : -1;
-    }
-    const int S = !m->wq8 && m->dt == CAP_DT_BF16 ? skinny_plan(N, K, !ln) : 0;
-    if (S >= 1) {
-        ProfScope ps(m, s, tag, 2.0 * rows * N * K,
-                     ((double)rows * K + (double)N * K) * 2 + (ln ? (double)S * rows * N * 4 : (double)rows * N * 2));
-        *S_out = S;
-        return launch_gemm_skinny(A, K, W, K, bias, act, out_t, N, ln ? m->dpart : nullptr, rows, N, K, s) == S ? 0 : -1;
-    }
-    if (m->wq8) {
-        TRY(launch_dequant_i8_rowmajor(W, m->w8_scratch, N, K, s));
-        TRY(gemm(m, s, tag, A, K, m->w8_scratch, K, m->dpart, N, nullptr, nullptr, rows, N, K, 0, 1));
-        TRY(launch_scale_cols(m->dpart, wscale, rows, N, s));
-        *S_out = 1;
-    } else {
-        TRY(gemm_partial(m, s, tag, A, W, m->dpart, rows, N, K, 8, S_out));
-    }
-    if (!ln) TRY(launch_reduce_bias_act(out_dt, m->dpart, *S_out, bias, out_t, rows, N, act, s));
-    return 0;
-}
-
-// Self-attention of one layer over the fused q|k|v rows in oqkv -> octx, the new K/V rows into the layer's caches.  The prompt
-// (L positions, nothing cached): causal attention over the rows themselves (MFMA kernel for bf16 heads wider than 64).  A step
-// (L == 1): the new position against the `past` cached ones.
-// A beam search (bm): the caches are those of B x K rows, row = image * K + beam.  Its prompt pass runs over the B images and leaves
-// image b's positions in the cache of row b * K, for the K rows of the image; its steps run over the B * K rows, each reading the
-// generated positions from the rows its ancestry table names (opt_beam_decode_attention).
-struct OptBeams { int K; const int* anc; int anc_ld; };      // anc [B * K, anc_ld]: the step's table, from the first generated position on
-// Teacher-forced scoring (sc, run_score_blip2): the B rows-of-L are captions cap0 .. cap0 + B - 1 of a request with C captions per
-// image, their L new positions behind the P positions the prompt pass left in the cache of row image = caption / C; the caches are
-// read only (opt_prefix_attention).
-struct OptScore { int C, cap0; };
-int opt_attention(Captioner* m, const OLayer& Ly, int B, int L, int past, hipStream_t s, const OptBeams* bm, const OptScore* sc = nullptr) {
-    const CapConfig& c = m->c;
-    const int T = c.t_hidden, H = c.t_heads, hd = T / H, P = c.num_query_tokens + 1, Lmax = P + c.max_len;
-    if (sc) {
-        ProfScope ps(m, s, "opt_prefix_attn", 4.0 * B * H * (double)L * (P + L) * hd, 2.0 * B * (P + L) * T * m->esz);
-        return launch_opt_prefix_attention(m->dt, m->oqkv, Ly.kc, Ly.vc, m->octx, B, L, sc->cap0, sc->C, nullptr, T, H, Lmax, P, s, m->gdt);
-    }
-    if (L > 1 && past != 0) { cap_set_error("opt_attention: %d new positions behind a cached prefix (%d) are not built", L, past); return -1; }
-    if (L > 1) TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, L, T, Lmax, 0, s, bm ? bm->K : 1));
-    ProfScope ps(m, s, "opt_attn", 4.0 * B * H * (double)L * (past + L) * hd, 2.0 * B * (past + L) * T * m->esz);
-    if (L > 1) return launch_vit_attention(m->dt, m->oqkv, m->octx, B, L, H, 0, s, hd, 1, m->gdt);
-    if (bm)     // (cap_create holds BLIP-2's head widths to what the kernel takes)
-        return launch_opt_beam_decode_attention(m->dt, m->oqkv, Ly.kc, Ly.vc, m->octx, B / bm->K, bm->K, T, H, Lmax, P, past, bm->anc,
-                                                bm->anc_ld, s, m->gdt);
-    if (hd % 8 == 0 && hd <= 128) return launch_opt_decode_attention(m->dt, m->oqkv, Ly.kc, Ly.vc, m->octx, B, T, H, Lmax, past, s, m->gdt);
-    TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, 1, T, Lmax, past, s));
-    return launch_generic_attention(m->dt, m->oqkv, 3 * T, 3 * T, Ly.kc, T, (long)Lmax * T, Ly.vc, T, (long)Lmax * T, m->octx, T, T, B, 1, past + 1,
-                                    H, hd, past, s, m->gdt);
-}
-
-// The decoder layers over L new positions per row behind `past` cached ones (x = ox [B * L, T] fp32 with the positions added,
-// oh_t = LayerNorm_1 of layer 0 already applied), then the tied LM head (bf16, no bias) on each row's last new position ->
-// m->logits.  Every decode step (L = 1), and the prompt pass with int8 weights: up to kI8SkinnyPromptCrops crops its rows go
-// through the step's weight streams (a one-crop prompt is 33 rows: a weight stream too), beyond through the tiled GEMM.  The
-// consumers finish the projections' sums - bias (+ ReLU) -> T for q|k|v and fc1; bias + residual + the NEXT LayerNorm (the
-// final one on the last layer, over every row) for out_proj and fc2.
-// bm: the rows are a beam search's (opt_attention); its prompt pass leaves image b's logits in row b * K of m->logits.
-// sc (scoring): the rows are captions' new positions behind their images' cached prompts; no head here - the final LayerNorm of EVERY
-// row is left in oh_t for the caller's vocabulary GEMM over all of them.  Its rows take the weight streams up to the row count of
-// kI8SkinnyPromptCrops prompts, the tiled GEMM beyond, as the prompt pass does.
-int run_opt(Captioner* m, int B, int L, int past, hipStream_t s, const OptBeams* bm = nullptr, const OptScore* sc = nullptr) {
-    const CapConfig& c = m->c;
-    const int T = c.t_hidden, G = c.t_ffn, R = B * L;
-    const bool tiled = sc ? R > kI8SkinnyPromptCrops * (c.num_query_tokens + 1) : L > 1 && B > kI8SkinnyPromptCrops;
-    int S = 1;
-    for (int i = 0; i < c.t_layers; ++i) {
-        const OLayer& Ly = m->ol[i];
-        const bool last = i + 1 == c.t_layers;
-        TRY(opt_gemm(m, s, "opt_gemm_qkv", m->oh_t, Ly.w_qkv, Ly.b_qkv, 0, m->oqkv, R, 3 * T, T, false, &S, m->dt, Ly.s_qkv, tiled));
-        TRY(opt_attention(m, Ly, B, L, past, s, bm, sc));
-        TRY(opt_gemm(m, s, "opt_gemm_o", m->octx, Ly.w_o, nullptr, 0, nullptr, R, T, T, true, &S, m->gdt, Ly.s_o, tiled));
-        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_o, m->ox, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
-        TRY(opt_gemm(m, s, "opt_gemm_f1", m->oh_t, Ly.w_f1, Ly.b_f1, 2, m->off, R, G, T, false, &S, m->gdt, Ly.s_f1, tiled));
-        TRY(opt_gemm(m, s, "opt_gemm_f2", m->off, Ly.w_f2, nullptr, 0, nullptr, R, T, G, true, &S, m->gdt, Ly.s_f2, tiled));
-        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_f2, m->ox, last ? m->o_lnf_g : m->ol[i + 1].ln1_g,
-                                    last ? m->o_lnf_b : m->ol[i + 1].ln1_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
-    }
-    if (sc) return 0;
-    return gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)(L - 1) * T * m->esz, L * T, m->o_tok_t, T, m->logits,
-                (bm && L > 1 ? bm->K : 1) * m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
-}
-
-// The prompt pass with plain weights (f32 / f32s / bf16): B * L rows are GEMMs proper, so bias and residual ride the tiled GEMM's
-// epilogue, every sub-block opens with its own LayerNorm, and the final one covers each row's last position only.
-// sc (scoring): the same chain over captions' new positions behind the cached prompts; the final LayerNorm then covers EVERY row and
-// the head is the caller's (run_opt).
-int run_opt_prompt_plain(Captioner* m, int B, int L, hipStream_t s, const OptBeams* bm = nullptr, const OptScore* sc = nullptr) {
-    const CapConfig& c = m->c;
-    const int T = c.t_hidden, G = c.t_ffn, R = B * L;
-    const int af = m->gdt == CAP_DT_G8 ? 1 : 0;     // split mode: q | k | v for the attention kernels and the caches are fp32
-    for (const OLayer& Ly : m->ol) {
-        TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln1_g, Ly.ln1_b, c.t_eps, m->oh_t, nullptr, R, T, s));
-        TRY(gemm(m, s, "opt_gemm_qkv", m->oh_t, T, Ly.w_qkv, T, m->oqkv, 3 * T, Ly.b_qkv, nullptr, R, 3 * T, T, 0, af));
-        TRY(opt_attention(m, Ly, B, L, sc ? c.num_query_tokens + 1 : 0, s, bm, sc));
-        TRY(gemm(m, s, "opt_gemm_o", m->octx, T, Ly.w_o, T, m->ox, T, Ly.b_o, m->ox, R, T, T, 0, 1));
-        TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, R, T, s));
-        TRY(gemm(m, s, "opt_gemm_f1", m->oh_t, T, Ly.w_f1, T, m->off, G, Ly.b_f1, nullptr, R, G, T, 2, 0));
-        TRY(gemm(m, s, "opt_gemm_f2", m->off, G, Ly.w_f2, G, m->ox, T, Ly.b_f2, m->ox, R, T, G, 0, 1));
-    }
-    if (sc) return launch_layernorm(m->gdt, m->ox, T, m->o_lnf_g, m->o_lnf_b, c.t_eps, m->oh_t, nullptr, R, T, s);
-    TRY(launch_layernorm(m->gdt, m->ox + (size_t)(L - 1) * T, L * T, m->o_lnf_g, m->o_lnf_b, c.t_eps, m->oh_t, nullptr, B, T, s));
-    return gemm(m, s, "opt_gemm_vocab", m->oh_t, T, m->o_tok_t, T, m->logits, (bm ? bm->K : 1) * m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
-}
-
-// row b * K of logits [B * K, ld] -> the other K - 1 rows of image b
-__global__ void beam_rows_from_first_kernel(float* logits, int ld, int B, int K, int V) {
-    const size_t n = (size_t)B * (K - 1) * V;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t r = i / V, c = i - r * V, b = r / (K - 1), k = 1 + r % (K - 1);
-        logits[(b * K + k) * ld + c] = logits[b * K * ld + c];
-    }
-}
-__global__ void iota_rows_kernel(int* anc, int R, int L);
-
-// The beam search behind the prompt pass (HF `_beam_search` under Blip2ForConditionalGeneration.generate(num_beams = K)): the prompt
-// pass ran once per IMAGE and left its positions in the caches of rows b * K and its logits in rows b * K of m->logits; HF runs it on
-// K identical rows per image, so step 0 takes K copies of those logits (beam.hip starts beams 1 .. K - 1 at -1e9).
-// The bookkeeping is beam.hip's in HF-v5 mode over max_len + 1 token columns, column 0 = BOS.  HF subtracts decoder_prompt_len (the
-// query tokens + BOS) from every length it uses: its length penalty's cur_len + 1 - prompt and its early-stop heuristic's
-// max_length - prompt count new tokens, and so does beam.hip's cur_len + 1 - 1 with BOS as the only column ahead of them (pinned by
-// tests/golden/blip2_tiny_beam.npz).  Column c's token is sequence position P - 1 + c; the ancestry table's entry c names the row
-// that wrote that position, so the attention takes the table from column 1 (the first generated position, P) on.
-int run_beams_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
-    const CapConfig& c = m->c;
-    const int B = a.B, K = a.num_beams, R = B * K, max_len = a.max_len, Lb = max_len + 1;
-    const int T = c.t_hidden, P = c.num_query_tokens + 1;
-    TRY(launch_beam_init(m->beam, B, K, Lb, c.bos, c.pad, c.eos, s, BEAM_HF_V5));
-    hipLaunchKernelGGL(iota_rows_kernel, dim3(64), dim3(256), 0, s, m->anc, R, Lb);
-    hipLaunchKernelGGL(beam_rows_from_first_kernel, dim3(256), dim3(256), 0, s, m->logits, m->ldl, B, K, c.vocab);
-    CAP_HIP_CHECK(hipGetLastError());
-    for (int t = 0; t < max_len; ++t) {
-        const int cur_len = t + 1, nxt = (cur_len & 1) ^ 1;      // the step fills column cur_len and leaves its state in parity nxt
-        m->last_steps = t + 1;
-        TRY(copy_step_logits(m, a, R, t, s));
-        {
-            ProfScope ps(m, s, "beam_step", 0, (double)R * c.vocab * 4);
-            TRY(launch_beam_step(m->beam, m->logits, m->ldl, c.vocab, B, K, Lb, cur_len, c.eos, a.length_penalty, m->anc, Lb, s, BEAM_HF_V5, 0));
-        }
-        if (t + 1 == max_len) break;
-        {
-            bool done;
-            TRY(poll_all_finished(m, t, max_len, nullptr, R, beam_active_flag_p(m->beam, B, K, Lb), s, &done));
-            if (done) break;
-        }
-        const OptBeams step = {K, m->anc + (size_t)nxt * R * Lb + 1, Lb};
-        TRY(launch_opt_token_inputs(beam_running_tokens_p(m->beam, B, K, Lb, nxt), Lb, cur_len, m->o_tok, m->o_pos, m->ox, R, T, c.vocab, s,
-                                    P - 1 + cur_len));
-        TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, R, T, s));
-        TRY(run_opt(m, R, 1, P - 1 + cur_len, s, &step));
-    }
-    // the best hypothesis of every image with its BOS column, then the new tokens alone as the greedy loop returns them
-    TRY(launch_beam_finalize(m->beam, B, K, Lb, m->seq, m->lens, a.out_scores, s));
-    hipLaunchKernelGGL(copy_new_tokens_kernel, dim3(64), dim3(256), 0, s, m->seq, Lb, 1, m->lens, a.out_ids, a.out_len, B, max_len);
-    CAP_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// HF Blip2ForConditionalGeneration.generate, greedy: out_ids [B, max_len] = the new tokens (pad after EOS), out_len [B] =
-// their count incl. EOS, out_step_logits [max_len, B, vocab]; the optional greedy outputs have max_len columns.
-// num_beams > 1: the same front half over the B images, then run_beams_blip2 (out_scores = sequences_scores, out_step_logits
-// [max_len, B * num_beams, vocab]).
-int run_generate_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
-    const CapConfig& c = m->c;
-    const int B = a.B, max_len = a.max_len;
-    const int T = c.t_hidden, nq = c.num_query_tokens, P = nq + 1, Lmax = P + c.max_len;
-    TRY(zero_greedy_outputs(a, B, max_len, s));
-    TRY(run_encoder(m, a.pixels, a.pixel_fmt, B, nullptr, s));
-    TRY(run_qformer(m, kCaptionPass, B, nq, 0, nullptr, nullptr, s));
-    TRY(gemm(m, s, "b2_gemm_lproj", m->qr.x_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1));
-    TRY(launch_opt_prefill_inputs(m->lm_proj, m->o_tok, m->o_pos, m->ox, B, nq, T, c.bos, s));
-    const int K = a.num_beams;
-    const OptBeams prompt_beams = {K, nullptr, 0};
-    const OptBeams* pb = K > 1 ? &prompt_beams : nullptr;
-    if (!pb) {
-        hipLaunchKernelGGL(init_seq_kernel, dim3(64), dim3(256), 0, s, m->seq, m->finished, m->lens, B, Lmax, c.bos, c.pad);
-        CAP_HIP_CHECK(hipGetLastError());
-    }
-    if (m->wq8) {
-        TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B * P, T, s));
-        TRY(run_opt(m, B, P, 0, s, pb));
-    } else {
-        TRY(run_opt_prompt_plain(m, B, P, s, pb));
-    }
-    if (pb) return run_beams_blip2(m, a, s);
-    for (int t = 0; t < max_len; ++t) {
-        m->last_steps = t + 1;
-        // token of position P + t; a row finishes on EOS or at P + max_len tokens (greedy_select's `t` is the last filled index)
-        TRY(copy_step_logits(m, a, B, t, s));
-        TRY(select_greedy_step(m, a, B, t, max_len, Lmax, P - 1 + t, P + max_len, RowMap(), s));
-        if (t + 1 == max_len) break;
-        {
-            bool done;
-            TRY(poll_all_finished(m, t, max_len, m->finished, B, nullptr, s, &done));
-            if (done) break;
-        }
-        TRY(launch_opt_token_inputs(m->seq, Lmax, P + t, m->o_tok, m->o_pos, m->ox, B, T, c.vocab, s));
-        TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B, T, s));
-        TRY(run_opt(m, B, 1, P + t, s));
-    }
-    hipLaunchKernelGGL(copy_new_tokens_kernel, dim3(64), dim3(256), 0, s, m->seq, Lmax, P, m->lens, a.out_ids, a.out_len, B, max_len);
-    CAP_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// Teacher-forced scoring under BLIP-2 (cap_score_captions): the front half of run_generate_blip2 once per IMAGE - encoder, Q-Former,
-// projection, the P-position prompt pass, which leaves every image's prompt in its cache row and its BOS logits in m->logits - then
-//   entry 0 of every caption from its image's BOS logits (launch_target_logprob, one logits row shared by the image's C captions),
-//   the caption pass: the n = L - 2 tokens behind BOS of as many captions as the pass rows hold (max_batch x P: what the prompt
-//     pass is sized for), caption-major, behind the cached prompts (opt_prefix_attention; nothing is appended to the caches), the
-//     final LayerNorm over every row, and the tied head over those rows in slices of the logits buffer, each reduced at once.
-// Passes take whole images while one fits, else part of one image's captions.
-size_t score_pass_captions(const Captioner* m, int L);
-__global__ void score_counts_kernel(const int* __restrict__ lens, int* __restrict__ scored, int N, int L);
-int run_score_blip2(Captioner* m, const void* pixels, int fmt, int B, const int* ids, const int* lens, int C, int L, float* out_tlp, float* out_top,
-                    int* out_top_ids, int* out_scored, hipStream_t s) {
-    const CapConfig& c = m->c;
-    const int T = c.t_hidden, nq = c.num_query_tokens, P = nq + 1, N = B * C, npos = L - 1, n = L - 2;
-    const size_t e = m->esz;
-    TRY(launch_fill_f32(out_tlp, 0.f, (size_t)N * npos, s));
-    TRY(launch_fill_f32(out_top, 0.f, (size_t)N * npos, s));
-    TRY(launch_fill_i32(out_top_ids, 0, (size_t)N * npos, s));
-    hipLaunchKernelGGL(score_counts_kernel, dim3((N + 255) / 256), dim3(256), 0, s, lens, out_scored, N, L);
-    CAP_HIP_CHECK(hipGetLastError());
-    TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
-    TRY(run_qformer(m, kCaptionPass, B, nq, 0, nullptr, nullptr, s));
-    TRY(gemm(m, s, "b2_gemm_lproj", m->qr.x_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1));
-    TRY(launch_opt_prefill_inputs(m->lm_proj, m->o_tok, m->o_pos, m->ox, B, nq, T, c.bos, s));
-    if (m->wq8) {
-        TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B * P, T, s));
-        TRY(run_opt(m, B, P, 0, s));
-    } else {
-        TRY(run_opt_prompt_plain(m, B, P, s));
-    }
-    {
-        ProfScope ps(m, s, "target_logprob", 0, 2.0 * N * c.vocab * 4);
-        TRY(launch_target_logprob(m->logits, m->ldl, c.vocab, N, 0, 1, ids + 1, L, out_scored, out_tlp, out_top, out_top_ids, npos, s, 0, C));
-    }
-    m->last_score_passes = 0;
-    if (n < 1) return 0;
-    const int per = (int)std::min<size_t>(score_pass_captions(m, L), (size_t)N);
-    const int step = per >= C ? per / C * C : per;
-    const int head_rows = c.max_batch * c.max_beams;
-    for (int n0 = 0; n0 < N;) {
-        const int nc = step >= C ? std::min(step, N - n0) : std::min(step, (n0 / C + 1) * C - n0);
-        const int Rp = nc * n;
-        const OptScore sc = {C, n0};
-        TRY(launch_opt_caption_inputs(ids + (size_t)n0 * L + 1, L, nc, n, P, m->o_tok, m->o_pos, m->ox, T, c.vocab, s));
-        if (m->wq8) {
-            TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, Rp, T, s));
-            TRY(run_opt(m, nc, n, P, s, nullptr, &sc));
-        } else {
-            TRY(run_opt_prompt_plain(m, nc, n, s, nullptr, &sc));
-        }
-        for (int r0 = 0; r0 < Rp; r0 += head_rows) {
-            const int hr = std::min(head_rows, Rp - r0);
-            TRY(gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)r0 * T * e, T, m->o_tok_t, T, m->logits, m->ldl, nullptr, nullptr, hr,
-                     c.vocab, T, 0, 1));
-            ProfScope ps(m, s, "target_logprob", 0, 2.0 * hr * c.vocab * 4);
-            TRY(launch_target_logprob(m->logits, m->ldl, c.vocab, hr, r0, n, ids + (size_t)n0 * L + 2, L, out_scored + n0,
-                                      out_tlp + (size_t)n0 * npos + 1, out_top + (size_t)n0 * npos + 1, out_top_ids + (size_t)n0 * npos + 1, npos, s, 1, 1));
-        }
-        ++m->last_score_passes;
-        n0 += nc;
-    }
-    return 0;
-}
-
 // ---------------------------------------------------------------------------------------------- sentence encoder
 // HF BertModel state-dict names, as sentence-transformers stores all-MiniLM-L6-v2 (6 layers, 384 wide, 12 heads of 32,
 // FFN 1536, post-LN, eps 1e-12).  Replaces `SentenceTransformer("all-MiniLM-L6-v2").encode(caption)` - reference
@@ -1410,6 +1102,23 @@ int run_encoder(Captioner* m, const void* pixels, int fmt, int B, float* out_emb
     TRY(run_stem(m, pixels, fmt, B, kEncoderTags, s));
     return run_tower(m, s, m->vl, m->vt, B, m->NT, c.v_hidden, c.v_heads, c.v_mlp, c.v_eps, 1, false, kEncoderTags, m->post_g,
                      m->post_b, m->emb_t, emb_f);
+}
+
+// ViT-g over B images -> emb_t [B * NT, D] (post_layernorm on every token), then the cross-attention K/V of every cross layer of
+// the Q-Former (they depend on the image alone) -> itm_ckv: what an ITC and an ITM call on this image batch both read.
+int run_itm_images(Captioner* m, const void* pixels, int fmt, int B, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int D = c.v_hidden, Q = c.q_hidden, NT = m->NT;
+    m->itm_B = 0;
+    TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
+    size_t slot = 0;
+    for (const PostLayer& L : m->pl) {
+        if (!L.has_cross) continue;
+        TRY(gemm(m, s, kItmQueryTags.ckv, m->emb_t, D, L.w_ckv, D, itm_ckv_slot(m, slot++), 2 * Q, L.b_ckv, nullptr, B * NT, 2 * Q, D, 0,
+                 m->attn_f32()));
+    }
+    m->itm_B = B;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------- CLIP scorer
@@ -1524,7 +1233,7 @@ int decode_splitk(const Captioner* m, int N, int K, int max_S) {
 inline int decode_tile(const Captioner* m) { return m->gdt == CAP_DT_F32 ? 2 : 6; }
 
 int gemm_partial(Captioner* m, hipStream_t s, const char* tag, const void* A, const void* W, float* part, int R, int N,
-                 int K, int max_S, int* S_out, const int* m_live) {
+                 int K, int max_S, int* S_out, const int* m_live = nullptr) {
     const int S = decode_splitk(m, N, K, max_S);
     GemmParams p;
     memset(&p, 0, sizeof(p));
@@ -1961,6 +1670,23 @@ size_t score_pass_captions(const Captioner* m, int L) {
         return L <= 2 ? (size_t)0x7fffffff : (size_t)m->c.max_batch * (m->c.num_query_tokens + 1) / (size_t)(L - 2);
     return std::min<size_t>((size_t)m->c.max_batch * m->c.max_beams, m->ws_rows / (size_t)(L - 1));
 }
+// Captions of the pass that starts at caption n0 of N, where a pass holds `fit`: whole images while one fits, else part of one image's
+// captions (the result is a multiple of C, or below C).
+int score_pass_size(size_t fit, int C, int N, int n0) {
+    const int per = (int)std::min<size_t>(fit, (size_t)N);
+    return per >= C ? std::min(per / C * C, N - n0) : std::min(per, (n0 / C + 1) * C - n0);
+}
+// A scoring call's outputs before its passes: zeros, and every caption's count of scored positions
+int init_score_outputs(const ScoreArgs& a, hipStream_t s) {
+    const int N = a.B * a.C;
+    const size_t n = (size_t)N * (a.L - 1);
+    TRY(launch_fill_f32(a.out_tlp, 0.f, n, s));
+    TRY(launch_fill_f32(a.out_top, 0.f, n, s));
+    TRY(launch_fill_i32(a.out_top_ids, 0, n, s));
+    hipLaunchKernelGGL(score_counts_kernel, dim3((N + 255) / 256), dim3(256), 0, s, a.lens, a.out_scored, N, a.L);
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 
 // log p(ids[n][j + 1] | image n / C, ids[n][0..j]) for every caption and position, with the row's log max softmax and arg-max: the image
 // side once per image, then positions 0 .. L - 2 of the captions through the decoder as prefill passes (run_prefill: one read of every
@@ -1975,21 +1701,15 @@ int run_score(Captioner* m, const ScoreArgs& a, hipStream_t s) {
     const DecTags& tg = *P.tags;
     const int N = a.B * a.C, L = a.L, npos = L - 1, W = P.W;
     const size_t e = m->esz;
-    TRY(launch_fill_f32(a.out_tlp, 0.f, (size_t)N * npos, s));
-    TRY(launch_fill_f32(a.out_top, 0.f, (size_t)N * npos, s));
-    TRY(launch_fill_i32(a.out_top_ids, 0, (size_t)N * npos, s));
-    hipLaunchKernelGGL(score_counts_kernel, dim3((N + 255) / 256), dim3(256), 0, s, a.lens, a.out_scored, N, L);
-    CAP_HIP_CHECK(hipGetLastError());
+    TRY(init_score_outputs(a, s));
     TRY(run_image_side(m, a.pixels, a.pixel_fmt, a.B, s));
-    const int per = (int)std::min<size_t>(score_pass_captions(m, L), (size_t)N);
-    const int step = per >= a.C ? per / a.C * a.C : per;        // whole images, or part of one image's captions
     m->last_score_passes = 0;
     for (int n0 = 0; n0 < N;) {
-        const int nc = step >= a.C ? std::min(step, N - n0) : std::min(step, (n0 / a.C + 1) * a.C - n0);
+        const int nc = score_pass_size(score_pass_captions(m, L), a.C, N, n0);
         Dec d = make_dec(m, a.B, 1);       // the cross K/V are packed for the call's images; the caches hold this pass's captions
         d.R = nc;
         TRY(launch_init_prompt_seq(d.seq, d.finished, d.lens, nc, L, a.ids + (size_t)n0 * L, nc, L, c.vocab, c.pad, s));
-        TRY(run_prefill(m, d, 0, nc, npos, L, s, (step >= a.C ? a.C : nc) * npos, n0 / a.C));
+        TRY(run_prefill(m, d, 0, nc, npos, L, s, std::min(nc, a.C) * npos, n0 / a.C));
         const int Rp = nc * npos;
         for (int r0 = 0; r0 < Rp; r0 += (int)m->head_rows) {
             const int hr = std::min((int)m->head_rows, Rp - r0);
@@ -2003,6 +1723,289 @@ int run_score(Captioner* m, const ScoreArgs& a, hipStream_t s) {
             ProfScope ps(m, s, "target_logprob", 0, 2.0 * hr * c.vocab * 4);
             TRY(launch_target_logprob(d.logits, m->ldl, c.vocab, hr, r0, npos, a.ids + (size_t)n0 * L + 1, L, a.out_scored + n0,
                                       a.out_tlp + (size_t)n0 * npos, a.out_top + (size_t)n0 * npos, a.out_top_ids + (size_t)n0 * npos, npos, s));
+        }
+        ++m->last_score_passes;
+        n0 += nc;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- BLIP-2: the OPT decoder and the runs
+// ---- The OPT decoder (pre-LN blocks: what follows a residual add is always a LayerNorm).
+// One projection over `rows` rows, left for a consumer to finish: in place (ln == false: bias + act -> out_t, of type out_dt -
+// split mode: fp32 for q|k|v, G8 for a GEMM operand) or as *S_out slice sums in m->dpart for the reduce + LayerNorm consumer.
+//   int8 weights (W = fragment-ordered bytes, wscale = row scales), tiled: a batch's prompt pass, B x 33 rows, is a GEMM proper.
+//     The matrix is unpacked into a row-major bf16 scratch of its INTEGERS (exact), multiplied by the tiled kernel into fp32 and
+//     the row scales applied to that output (S = 1): (A . q^T) * scale + bias as in the weight-streaming kernel, the sums in the
+//     tiled kernel's order.  Measured at 32 crops (us per fc1 GEMM): 365 on the rows-walking weight-stream kernel, ~135 here.
+//   int8 weights otherwise: the weight-streaming kernel, which takes any row count (further row groups re-read a unit's bytes
+//     from the XCD's L2).
+//   bf16 at a shape the weight-streaming kernel takes: that kernel - at a few dozen rows every GEMM is a weight stream, so K is
+//     split over blocks (all slabs of a block in flight at once).  Otherwise the tiled split-K GEMM with a reduce kernel.
+// Apart from `tiled` the choice depends on dtype and (N, K) only - never on the row count.
+int opt_gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, const void* W, const float* bias, int act, void* out_t,
+             int rows, int N, int K, bool ln, int* S_out, int out_dt, const float* wscale, bool tiled) {
+    if (m->wq8 && !tiled) {
+        const int S8 = skinny_i8_plan(N, K, !ln);
+        ProfScope ps(m, s, tag, 2.0 * rows * N * K,
+                     (double)rows * K * 2 + (double)N * K + (ln ? (double)S8 * rows * N * 4 : (double)rows * N * 2));
+        *S_out = S8;
+        return launch_gemm_skinny_i8(A, K, W, wscale, bias, act, out_t, N, ln ? m->dpart : nullptr, rows, N, K, s) == S8 ? 0 : -1;
+    }
+    const int S = !m->wq8 && m->dt == CAP_DT_BF16 ? skinny_plan(N, K, !ln) : 0;
+    if (S >= 1) {
+        ProfScope ps(m, s, tag, 2.0 * rows * N * K,
+                     ((double)rows * K + (double)N * K) * 2 + (ln ? (double)S * rows * N * 4 : (double)rows * N * 2));
+        *S_out = S;
+        return launch_gemm_skinny(A, K, W, K, bias, act, out_t, N, ln ? m->dpart : nullptr, rows, N, K, s) == S ? 0 : -1;
+    }
+    if (m->wq8) {
+        TRY(launch_dequant_i8_rowmajor(W, m->w8_scratch, N, K, s));
+        TRY(gemm(m, s, tag, A, K, m->w8_scratch, K, m->dpart, N, nullptr, nullptr, rows, N, K, 0, 1));
+        TRY(launch_scale_cols(m->dpart, wscale, rows, N, s));
+        *S_out = 1;
+    } else {
+        TRY(gemm_partial(m, s, tag, A, W, m->dpart, rows, N, K, 8, S_out));
+    }
+    if (!ln) TRY(launch_reduce_bias_act(out_dt, m->dpart, *S_out, bias, out_t, rows, N, act, s));
+    return 0;
+}
+
+// Self-attention of one layer over the fused q|k|v rows in oqkv -> octx, the new K/V rows into the layer's caches.  The prompt
+// (L positions, nothing cached): causal attention over the rows themselves (MFMA kernel for bf16 heads wider than 64).  A step
+// (L == 1): the new position against the `past` cached ones.
+// What the B rows-of-L are says OptRows, the three key sources of attention.hip's OPT wave walk:
+//   OWN: every row has its own cache row (the greedy call).
+//   BEAMS: the caches are those of B x K rows, row = image * K + beam.  The prompt pass runs over the B images and leaves image b's
+//     positions in the cache of row b * K, for the K rows of the image (no table yet); the steps run over the B * K rows, each reading
+//     the generated positions from the rows its ancestry table names (opt_beam_decode_attention).
+//   CAPTIONS (teacher-forced scoring, run_score_blip2): the rows are captions cap0 .. cap0 + B - 1 of a request with C captions per
+//     image, their L new positions behind the P positions the prompt pass left in the cache of row image = caption / C; the caches
+//     are read only (opt_prefix_attention).
+struct OptRows {
+    enum Kind { OWN, BEAMS, CAPTIONS } kind = OWN;
+    int K = 1; const int* anc = nullptr; int anc_ld = 0;    // BEAMS: anc [B * K, anc_ld], the step's table from the first generated position on
+    int C = 0, cap0 = 0;                                    // CAPTIONS
+    static OptRows beams(int K, const int* anc = nullptr, int anc_ld = 0) { return {BEAMS, K, anc, anc_ld}; }
+    static OptRows captions(int C, int cap0) { return {CAPTIONS, 1, nullptr, 0, C, cap0}; }
+};
+int opt_attention(Captioner* m, const OLayer& Ly, int B, int L, int past, hipStream_t s, const OptRows& rw) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden, H = c.t_heads, hd = T / H, P = c.num_query_tokens + 1, Lmax = P + c.max_len;
+    if (rw.kind == OptRows::CAPTIONS) {
+        ProfScope ps(m, s, "opt_prefix_attn", 4.0 * B * H * (double)L * (P + L) * hd, 2.0 * B * (P + L) * T * m->esz);
+        return launch_opt_prefix_attention(m->dt, m->oqkv, Ly.kc, Ly.vc, m->octx, B, L, rw.cap0, rw.C, nullptr, T, H, Lmax, P, s, m->gdt);
+    }
+    if (L > 1 && past != 0) { cap_set_error("opt_attention: %d new positions behind a cached prefix (%d) are not built", L, past); return -1; }
+    if (L > 1) TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, L, T, Lmax, 0, s, rw.K));
+    ProfScope ps(m, s, "opt_attn", 4.0 * B * H * (double)L * (past + L) * hd, 2.0 * B * (past + L) * T * m->esz);
+    if (L > 1) return launch_vit_attention(m->dt, m->oqkv, m->octx, B, L, H, 0, s, hd, 1, m->gdt);
+    if (rw.kind == OptRows::BEAMS)     // (cap_create holds BLIP-2's head widths to what the kernel takes)
+        return launch_opt_beam_decode_attention(m->dt, m->oqkv, Ly.kc, Ly.vc, m->octx, B / rw.K, rw.K, T, H, Lmax, P, past, rw.anc,
+                                                rw.anc_ld, s, m->gdt);
+    if (hd % 8 == 0 && hd <= 128) return launch_opt_decode_attention(m->dt, m->oqkv, Ly.kc, Ly.vc, m->octx, B, T, H, Lmax, past, s, m->gdt);
+    TRY(launch_kv_append(m->dt, m->oqkv, Ly.kc, Ly.vc, B, 1, T, Lmax, past, s));
+    return launch_generic_attention(m->dt, m->oqkv, 3 * T, 3 * T, Ly.kc, T, (long)Lmax * T, Ly.vc, T, (long)Lmax * T, m->octx, T, T, B, 1, past + 1,
+                                    H, hd, past, s, m->gdt);
+}
+
+// The decoder layers over L new positions per row behind `past` cached ones (x = ox [B * L, T] fp32 with the positions added,
+// oh_t = LayerNorm_1 of layer 0 already applied), then the tied LM head (bf16, no bias) on each row's last new position ->
+// m->logits.  Every decode step (L = 1), and the prompt pass with int8 weights: up to kI8SkinnyPromptCrops crops its rows go
+// through the step's weight streams (a one-crop prompt is 33 rows: a weight stream too), beyond through the tiled GEMM.  The
+// consumers finish the projections' sums - bias (+ ReLU) -> T for q|k|v and fc1; bias + residual + the NEXT LayerNorm (the
+// final one on the last layer, over every row) for out_proj and fc2.
+// rw (opt_attention) - BEAMS: the prompt pass leaves image b's logits in row b * K of m->logits.
+// CAPTIONS: the rows are captions' new positions behind their images' cached prompts; no head here - the final LayerNorm of EVERY
+// row is left in oh_t for the caller's vocabulary GEMM over all of them.  Its rows take the weight streams up to the row count of
+// kI8SkinnyPromptCrops prompts, the tiled GEMM beyond, as the prompt pass does.
+int run_opt(Captioner* m, int B, int L, int past, hipStream_t s, const OptRows& rw) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden, G = c.t_ffn, R = B * L;
+    const bool sc = rw.kind == OptRows::CAPTIONS;
+    const bool tiled = sc ? R > kI8SkinnyPromptCrops * (c.num_query_tokens + 1) : L > 1 && B > kI8SkinnyPromptCrops;
+    int S = 1;
+    for (int i = 0; i < c.t_layers; ++i) {
+        const OLayer& Ly = m->ol[i];
+        const bool last = i + 1 == c.t_layers;
+        TRY(opt_gemm(m, s, "opt_gemm_qkv", m->oh_t, Ly.w_qkv, Ly.b_qkv, 0, m->oqkv, R, 3 * T, T, false, &S, m->dt, Ly.s_qkv, tiled));
+        TRY(opt_attention(m, Ly, B, L, past, s, rw));
+        TRY(opt_gemm(m, s, "opt_gemm_o", m->octx, Ly.w_o, nullptr, 0, nullptr, R, T, T, true, &S, m->gdt, Ly.s_o, tiled));
+        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_o, m->ox, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
+        TRY(opt_gemm(m, s, "opt_gemm_f1", m->oh_t, Ly.w_f1, Ly.b_f1, 2, m->off, R, G, T, false, &S, m->gdt, Ly.s_f1, tiled));
+        TRY(opt_gemm(m, s, "opt_gemm_f2", m->off, Ly.w_f2, nullptr, 0, nullptr, R, T, G, true, &S, m->gdt, Ly.s_f2, tiled));
+        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_f2, m->ox, last ? m->o_lnf_g : m->ol[i + 1].ln1_g,
+                                    last ? m->o_lnf_b : m->ol[i + 1].ln1_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
+    }
+    if (sc) return 0;
+    return gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)(L - 1) * T * m->esz, L * T, m->o_tok_t, T, m->logits,
+                (L > 1 ? rw.K : 1) * m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
+}
+
+// A pass (L > 1) with plain weights (f32 / f32s / bf16): B * L rows are GEMMs proper, so bias and residual ride the tiled GEMM's
+// epilogue, every sub-block opens with its own LayerNorm, and the final one covers each row's last position only.
+// CAPTIONS: the same chain over captions' new positions behind the cached prompts; the final LayerNorm then covers EVERY row and
+// the head is the caller's (run_opt).
+int run_opt_prompt_plain(Captioner* m, int B, int L, int past, hipStream_t s, const OptRows& rw) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden, G = c.t_ffn, R = B * L;
+    const int af = m->gdt == CAP_DT_G8 ? 1 : 0;     // split mode: q | k | v for the attention kernels and the caches are fp32
+    for (const OLayer& Ly : m->ol) {
+        TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln1_g, Ly.ln1_b, c.t_eps, m->oh_t, nullptr, R, T, s));
+        TRY(gemm(m, s, "opt_gemm_qkv", m->oh_t, T, Ly.w_qkv, T, m->oqkv, 3 * T, Ly.b_qkv, nullptr, R, 3 * T, T, 0, af));
+        TRY(opt_attention(m, Ly, B, L, past, s, rw));
+        TRY(gemm(m, s, "opt_gemm_o", m->octx, T, Ly.w_o, T, m->ox, T, Ly.b_o, m->ox, R, T, T, 0, 1));
+        TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, R, T, s));
+        TRY(gemm(m, s, "opt_gemm_f1", m->oh_t, T, Ly.w_f1, T, m->off, G, Ly.b_f1, nullptr, R, G, T, 2, 0));
+        TRY(gemm(m, s, "opt_gemm_f2", m->off, G, Ly.w_f2, G, m->ox, T, Ly.b_f2, m->ox, R, T, G, 0, 1));
+    }
+    if (rw.kind == OptRows::CAPTIONS) return launch_layernorm(m->gdt, m->ox, T, m->o_lnf_g, m->o_lnf_b, c.t_eps, m->oh_t, nullptr, R, T, s);
+    TRY(launch_layernorm(m->gdt, m->ox + (size_t)(L - 1) * T, L * T, m->o_lnf_g, m->o_lnf_b, c.t_eps, m->oh_t, nullptr, B, T, s));
+    return gemm(m, s, "opt_gemm_vocab", m->oh_t, T, m->o_tok_t, T, m->logits, rw.K * m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
+}
+
+// The layers over a pass of B x L rows whose inputs are in ox: the prompt (nothing cached), or captions' new positions behind it.
+// int8 weights walk as the steps do (run_opt, behind layer 0's first LayerNorm), plain ones as GEMMs proper.
+int run_opt_pass(Captioner* m, int B, int L, hipStream_t s, const OptRows& rw) {
+    const CapConfig& c = m->c;
+    const int past = rw.kind == OptRows::CAPTIONS ? c.num_query_tokens + 1 : 0;
+    if (!m->wq8) return run_opt_prompt_plain(m, B, L, past, s, rw);
+    TRY(launch_layernorm(m->gdt, m->ox, c.t_hidden, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B * L, c.t_hidden, s));
+    return run_opt(m, B, L, past, s, rw);
+}
+
+// One decode step over B rows: column `col` of tokens [B, ld] is the token at sequence position `at`, the `at` positions before it cached
+int run_opt_step(Captioner* m, const int* tokens, int ld, int col, int at, int B, hipStream_t s, const OptRows& rw) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden;
+    TRY(launch_opt_token_inputs(tokens, ld, col, m->o_tok, m->o_pos, m->ox, B, T, c.vocab, s, at));
+    TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B, T, s));
+    return run_opt(m, B, 1, at, s, rw);
+}
+
+// row b * K of logits [B * K, ld] -> the other K - 1 rows of image b
+__global__ void beam_rows_from_first_kernel(float* logits, int ld, int B, int K, int V) {
+    const size_t n = (size_t)B * (K - 1) * V;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / V, c = i - r * V, b = r / (K - 1), k = 1 + r % (K - 1);
+        logits[(b * K + k) * ld + c] = logits[b * K * ld + c];
+    }
+}
+
+// The beam search behind the prompt pass (HF `_beam_search` under Blip2ForConditionalGeneration.generate(num_beams = K)): the prompt
+// pass ran once per IMAGE and left its positions in the caches of rows b * K and its logits in rows b * K of m->logits; HF runs it on
+// K identical rows per image, so step 0 takes K copies of those logits (beam.hip starts beams 1 .. K - 1 at -1e9).
+// The bookkeeping is beam.hip's in HF-v5 mode over max_len + 1 token columns, column 0 = BOS.  HF subtracts decoder_prompt_len (the
+// query tokens + BOS) from every length it uses: its length penalty's cur_len + 1 - prompt and its early-stop heuristic's
+// max_length - prompt count new tokens, and so does beam.hip's cur_len + 1 - 1 with BOS as the only column ahead of them (pinned by
+// tests/golden/blip2_tiny_beam.npz).  Column c's token is sequence position P - 1 + c; the ancestry table's entry c names the row
+// that wrote that position, so the attention takes the table from column 1 (the first generated position, P) on.
+int run_beams_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int B = a.B, K = a.num_beams, R = B * K, max_len = a.max_len, Lb = max_len + 1, P = c.num_query_tokens + 1;
+    TRY(launch_beam_init(m->beam, B, K, Lb, c.bos, c.pad, c.eos, s, BEAM_HF_V5));
+    hipLaunchKernelGGL(iota_rows_kernel, dim3(64), dim3(256), 0, s, m->anc, R, Lb);
+    hipLaunchKernelGGL(beam_rows_from_first_kernel, dim3(256), dim3(256), 0, s, m->logits, m->ldl, B, K, c.vocab);
+    CAP_HIP_CHECK(hipGetLastError());
+    for (int t = 0; t < max_len; ++t) {
+        const int cur_len = t + 1, nxt = (cur_len & 1) ^ 1;      // the step fills column cur_len and leaves its state in parity nxt
+        m->last_steps = t + 1;
+        TRY(copy_step_logits(m, a, R, t, s));
+        {
+            ProfScope ps(m, s, "beam_step", 0, (double)R * c.vocab * 4);
+            TRY(launch_beam_step(m->beam, m->logits, m->ldl, c.vocab, B, K, Lb, cur_len, c.eos, a.length_penalty, m->anc, Lb, s, BEAM_HF_V5, 0));
+        }
+        if (t + 1 == max_len) break;
+        {
+            bool done;
+            TRY(poll_all_finished(m, t, max_len, nullptr, R, beam_active_flag_p(m->beam, B, K, Lb), s, &done));
+            if (done) break;
+        }
+        const OptRows rows = OptRows::beams(K, m->anc + (size_t)nxt * R * Lb + 1, Lb);
+        TRY(run_opt_step(m, beam_running_tokens_p(m->beam, B, K, Lb, nxt), Lb, cur_len, P - 1 + cur_len, R, s, rows));
+    }
+    // the best hypothesis of every image with its BOS column, then the new tokens alone as the greedy loop returns them
+    TRY(launch_beam_finalize(m->beam, B, K, Lb, m->seq, m->lens, a.out_scores, s));
+    hipLaunchKernelGGL(copy_new_tokens_kernel, dim3(64), dim3(256), 0, s, m->seq, Lb, 1, m->lens, a.out_ids, a.out_len, B, max_len);
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// BLIP-2's front half over the B images of a call: encoder, the Q-Former's caption pass, the language projection, and the prompt pass
+// over the P = query tokens + BOS positions, which leaves image b's prompt in cache row b * K and its BOS logits in row b * K of
+// m->logits (K > 1: for the K rows of a beam search).
+int run_blip2_prompt(Captioner* m, const void* pixels, int fmt, int B, int K, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden, nq = c.num_query_tokens;
+    TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
+    TRY(run_qformer(m, kCaptionPass, B, nq, 0, nullptr, nullptr, s));
+    TRY(gemm(m, s, "b2_gemm_lproj", m->qr.x_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1));
+    TRY(launch_opt_prefill_inputs(m->lm_proj, m->o_tok, m->o_pos, m->ox, B, nq, T, c.bos, s));
+    return run_opt_pass(m, B, nq + 1, s, K > 1 ? OptRows::beams(K) : OptRows());
+}
+
+// HF Blip2ForConditionalGeneration.generate, greedy: out_ids [B, max_len] = the new tokens (pad after EOS), out_len [B] =
+// their count incl. EOS, out_step_logits [max_len, B, vocab]; the optional greedy outputs have max_len columns.
+// num_beams > 1: the same front half over the B images, then run_beams_blip2 (out_scores = sequences_scores, out_step_logits
+// [max_len, B * num_beams, vocab]).
+int run_generate_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int B = a.B, max_len = a.max_len, P = c.num_query_tokens + 1, Lmax = P + c.max_len;
+    TRY(zero_greedy_outputs(a, B, max_len, s));
+    TRY(run_blip2_prompt(m, a.pixels, a.pixel_fmt, B, a.num_beams, s));
+    if (a.num_beams > 1) return run_beams_blip2(m, a, s);
+    hipLaunchKernelGGL(init_seq_kernel, dim3(64), dim3(256), 0, s, m->seq, m->finished, m->lens, B, Lmax, c.bos, c.pad);
+    CAP_HIP_CHECK(hipGetLastError());
+    for (int t = 0; t < max_len; ++t) {
+        m->last_steps = t + 1;
+        // token of position P + t; a row finishes on EOS or at P + max_len tokens (greedy_select's `t` is the last filled index)
+        TRY(copy_step_logits(m, a, B, t, s));
+        TRY(select_greedy_step(m, a, B, t, max_len, Lmax, P - 1 + t, P + max_len, RowMap(), s));
+        if (t + 1 == max_len) break;
+        {
+            bool done;
+            TRY(poll_all_finished(m, t, max_len, m->finished, B, nullptr, s, &done));
+            if (done) break;
+        }
+        TRY(run_opt_step(m, m->seq, Lmax, P + t, P + t, B, s, OptRows()));
+    }
+    hipLaunchKernelGGL(copy_new_tokens_kernel, dim3(64), dim3(256), 0, s, m->seq, Lmax, P, m->lens, a.out_ids, a.out_len, B, max_len);
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// Teacher-forced scoring under BLIP-2 (cap_score_captions): the front half once per IMAGE (run_blip2_prompt), then
+//   entry 0 of every caption from its image's BOS logits (launch_target_logprob, one logits row shared by the image's C captions),
+//   the caption pass: the n = L - 2 tokens behind BOS of as many captions as the pass rows hold (max_batch x P: what the prompt
+//     pass is sized for), caption-major, behind the cached prompts (opt_prefix_attention; nothing is appended to the caches), the
+//     final LayerNorm over every row, and the tied head over those rows in slices of the logits buffer, each reduced at once.
+// Passes take whole images while one fits, else part of one image's captions.
+int run_score_blip2(Captioner* m, const ScoreArgs& a, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden, P = c.num_query_tokens + 1, C = a.C, L = a.L, N = a.B * C, npos = L - 1, n = L - 2;
+    const size_t e = m->esz;
+    TRY(init_score_outputs(a, s));
+    TRY(run_blip2_prompt(m, a.pixels, a.pixel_fmt, a.B, 1, s));
+    {
+        ProfScope ps(m, s, "target_logprob", 0, 2.0 * N * c.vocab * 4);
+        TRY(launch_target_logprob(m->logits, m->ldl, c.vocab, N, 0, 1, a.ids + 1, L, a.out_scored, a.out_tlp, a.out_top, a.out_top_ids, npos, s, 0, C));
+    }
+    m->last_score_passes = 0;
+    if (n < 1) return 0;
+    const int head_rows = c.max_batch * c.max_beams;
+    for (int n0 = 0; n0 < N;) {
+        const int nc = score_pass_size(score_pass_captions(m, L), C, N, n0);
+        const int Rp = nc * n;
+        TRY(launch_opt_caption_inputs(a.ids + (size_t)n0 * L + 1, L, nc, n, P, m->o_tok, m->o_pos, m->ox, T, c.vocab, s));
+        TRY(run_opt_pass(m, nc, n, s, OptRows::captions(C, n0)));
+        for (int r0 = 0; r0 < Rp; r0 += head_rows) {
+            const int hr = std::min(head_rows, Rp - r0);
+            TRY(gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)r0 * T * e, T, m->o_tok_t, T, m->logits, m->ldl, nullptr, nullptr, hr,
+                     c.vocab, T, 0, 1));
+            ProfScope ps(m, s, "target_logprob", 0, 2.0 * hr * c.vocab * 4);
+            TRY(launch_target_logprob(m->logits, m->ldl, c.vocab, hr, r0, n, a.ids + (size_t)n0 * L + 2, L, a.out_scored + n0,
+                                      a.out_tlp + (size_t)n0 * npos + 1, a.out_top + (size_t)n0 * npos + 1, a.out_top_ids + (size_t)n0 * npos + 1, npos,
+                                      s, 1, 1));
         }
         ++m->last_score_passes;
         n0 += nc;
@@ -2613,10 +2616,7 @@ int cap_score_captions(CapHandle h, const void* pixels, int pixel_fmt, int B, co
     Captioner* m = (Captioner*)h;
     const ScoreArgs a = {pixels, pixel_fmt, B, ids, lens, captions_per_image, L, out_token_logprobs, out_top_logprobs, out_top_ids, out_scored};
     TRY(validate_score(m, a, "cap_score_captions"));
-    if (m->c.arch == CAP_ARCH_BLIP2)
-        return run_score_blip2(m, pixels, pixel_fmt, B, ids, lens, captions_per_image, L, out_token_logprobs, out_top_logprobs, out_top_ids,
-                               out_scored, (hipStream_t)stream);
-    return run_score(m, a, (hipStream_t)stream);
+    return (m->c.arch == CAP_ARCH_BLIP2 ? run_score_blip2 : run_score)(m, a, (hipStream_t)stream);
 }
 int cap_last_score_passes(CapHandle h) { return h ? ((Captioner*)h)->last_score_passes : -1; }
 int cap_score_pass_captions(CapHandle h, int L) {

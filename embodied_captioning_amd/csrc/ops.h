@@ -113,14 +113,13 @@ int launch_opt_prefill_inputs(const float* proj, const float* tok, const float* 
 int launch_opt_token_inputs(const int* seq, int seq_ld, int cur, const float* tok, const float* pos, float* x, int B, int T, int V,
                             hipStream_t s, int at = -1);     // ids outside [0, V) are clamped; at: the sequence position (default: cur)
 // decode step of a pre-LN decoder: q|k|v row [B, 3T] -> appends k, v to caches [B][Lmax][T] at `past`, out [B, T]
-constexpr int OPT_DECODE_MAX_KEYS = 1024;      // cached positions (past + 1) launch_opt_decode_attention takes: its scores sit in LDS
+constexpr int OPT_DECODE_MAX_KEYS = 1024;      // keys of a row (past + 1; scoring: P + n) the three launchers below take: the scores sit in LDS
 int launch_opt_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int T, int H, int Lmax,
                                 int past, hipStream_t s, int out_dtype = -1);
 // the same for the rows r = image * K + beam of a beam search (beam.hip): keys below P from the cache of row image * K, key P + g
 // from the cache of row anc[r * anc_ld + g], the new one appended to row r's own
 int launch_opt_beam_decode_attention(int dtype, const void* qkv, void* kc, void* vc, void* out, int B, int K, int T, int H, int Lmax,
                                      int P, int past, const int* anc, int anc_ld, hipStream_t s, int out_dtype = -1);
-// row_stride: row b's positions go to cache row b * row_stride (a beam search's prompt: the first of each image's K rows)
 // teacher-forced scoring behind a cached prompt (BLIP-2): n new positions of n_caps captions, caption-major fused q|k|v rows; caption
 // cap0 + c belongs to image (cap0 + c) / C, whose P prompt keys are read from cache row `image` of kc / vc [.][Lmax][T], the caption's
 // own keys from the rows themselves; n_pos (device, optional): rows with position >= n_pos[cap0 + c] are left untouched
@@ -129,6 +128,7 @@ int launch_opt_prefix_attention(int dtype, const void* qkv, const void* kc, cons
 // x [n_caps * n, T] = token table[ids[c * ids_ld + t]] + position table[P + t + 2] (ids clamped to [0, V))
 int launch_opt_caption_inputs(const int* ids, int ids_ld, int n_caps, int n, int P, const float* tok, const float* pos, float* x, int T, int V,
                               hipStream_t s);
+// row_stride: row b's positions go to cache row b * row_stride (a beam search's prompt: the first of each image's K rows)
 int launch_kv_append(int dtype, const void* qkv, void* kc, void* vc, int B, int L, int T, int Lmax, int pos0, hipStream_t s,
                      int row_stride = 1);
 int launch_rows_broadcast(int dtype, const float* src, float* dst_f, void* dst_t, int B, int n, int D, hipStream_t s);

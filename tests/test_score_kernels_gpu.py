@@ -247,6 +247,57 @@ def test_opt_prefix_attention_against_float64(dtype, hd, P, n):
     print(f"opt_prefix_attention {dtype} hd={hd:3d} P={P:2d} n={n:2d}: worst judged / bar {worst:.3f}")
 
 
+def _same_bits(a, b):
+    it = torch.int16 if a.dtype == torch.bfloat16 else torch.int32
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(it), b.contiguous().view(it))
+
+
+# The two kernels share one walk (opt_decode_attention_body) and differ in where key j is read from, so row (caption, t) of a prefix pass
+# must have the BITS of decode step past = P + t of a row whose cache holds the image's prompt and the caption's earlier keys: two
+# images x two captions each (caption index != image index), the runtime head width (16) and the unrolled one (80: HD8 = 10), and
+# (P, n) with 1 key, a few, and 61 .. 68 keys - across the lanes' 64-key trip of the score loop and several 16-key trips of P.V, with
+# the boundary between the two key sources beside it.  dtype codes: 0 fp32, 1 bf16, 2 split (fp32 in, G8 out: an fp32-sized container).
+@pytest.mark.parametrize("P,n", ((1, 1), (9, 5), (60, 8)))
+@pytest.mark.parametrize("hd", (16, 80))
+@pytest.mark.parametrize("dtype", (0, 1, 2), ids=("f32", "bf16", "f32s"))
+def test_opt_prefix_attention_rows_have_the_bits_of_the_decode_steps(dtype, hd, P, n):
+    from embodied_captioning_amd import _native
+    lib = _native.load_library()
+    Cn, N, T, Lmax = 2, PA_B * 2, PA_H * hd, P + n + 2
+    it = torch.bfloat16 if dtype == 1 else torch.float32
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    g = torch.Generator().manual_seed(9000 + 97 * hd + 7 * P + n)
+    qkv = (torch.randn((N, n, 3 * T), generator=g) * 1.5).to(it).cuda()          # caption-major rows of the pass
+    pk, pv = ((torch.randn((PA_B, P, T), generator=g) * 1.5).to(it).cuda() for _ in range(2))
+    img = torch.arange(N, device="cuda") // Cn
+
+    def caches(rows, prompt):      # [rows, Lmax, T]: the prompt, and NaN wherever nothing is stored
+        c = torch.full((rows, Lmax, T), float("nan"), dtype=it, device="cuda")
+        c[:, :P] = prompt
+        return c
+
+    kci, vci = caches(PA_B, pk), caches(PA_B, pv)                                # per image, read only
+    out_p = torch.full((N, n, T), float("nan"), dtype=it if dtype == 1 else torch.float32, device="cuda")
+    rc = lib.cap_op_opt_prefix_attention(dtype, _p(qkv), _p(kci), _p(vci), _p(out_p), N, n, 0, Cn, None, T, PA_H, Lmax, P, stream)
+    assert rc == 0, _native.last_error()
+    kc, vc = caches(N, pk[img]), caches(N, pv[img])                              # per caption, appended to by the steps
+    for t in range(n):
+        row = qkv[:, t].contiguous()
+        out_t = torch.full((N, T), float("nan"), dtype=out_p.dtype, device="cuda")
+        rc = lib.cap_op_opt_decode_attention(dtype, _p(row), _p(kc), _p(vc), _p(out_t), N, T, PA_H, Lmax, P + t, stream)
+        assert rc == 0, _native.last_error()
+        torch.cuda.synchronize()
+        assert _same_bits(out_t, out_p[:, t]), (dtype, hd, P, n, t)
+    if dtype == 2:
+        from _util import g8_decode
+        assert np.isfinite(g8_decode(out_p.cpu().numpy())).all()
+    else:
+        assert torch.isfinite(out_p.float()).all()                               # every row was written, and from keys that exist
+    assert _same_bits(kc[:, P:P + n], qkv[:, :, T:2 * T]) and _same_bits(vc[:, P:P + n], qkv[:, :, 2 * T:])
+    assert _same_bits(kc[:, :P], pk[img]) and _same_bits(vc[:, :P], pv[img])
+    assert torch.isnan(kc[:, P + n:]).all() and torch.isnan(kci[:, P:]).all() and torch.isnan(vci[:, P:]).all()
+
+
 def test_opt_prefix_attention_refusals():
     from embodied_captioning_amd import _native
     lib = _native.load_library()
