@@ -121,6 +121,8 @@ _SIGNATURES = {
     "cap_last_row_compaction": (C.c_int, [C.c_void_p]),
     "cap_cross_cache_kind": (C.c_int, [C.c_void_p]),
     "cap_device_bytes": (C.c_size_t, [C.c_void_p]),
+    "cap_debug_fill_arena": (C.c_longlong, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cap_debug_arena_kinds": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "cap_g8_saturations": (C.c_longlong, [C.c_int]),
     "cap_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "cap_profile_report": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),

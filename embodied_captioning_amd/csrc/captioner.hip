@@ -65,6 +65,13 @@ struct Slot {            // where one checkpoint tensor (or a row range of a fus
 
 struct ProfTag { std::string tag; double flops, bytes; hipEvent_t e0, e1; };
 
+// What an arena allocation holds between ABI calls (DESIGN.md "Arena state"; cap_debug_fill_arena / cap_debug_arena_kinds):
+//   ARENA_SCRATCH  fp32 / compute-type / KV16 data a call writes before it reads: no result may depend on what it held before
+//   ARENA_INDEX    int32 tables (token rows, row maps, beam ancestry and the beam state block): a value here becomes an address
+//   ARENA_KEPT     initialised at create, or carrying state from one ABI call to a later one by documented contract
+enum { ARENA_SCRATCH = 0, ARENA_INDEX = 1, ARENA_KEPT = 2, ARENA_KINDS = 3 };
+struct ArenaAlloc { void* p; size_t bytes; int kind; const char* name; };   // bytes: as allocated (rounded up to 256)
+
 // The weights of one model on one GPU: device buffers in allocation order + the name -> buffer registry.  Read-only once
 // loaded, so every handle of an EnginePool points at the same store (cap_create_shared): a pool of n engines costs one copy
 // of the weights plus n arenas.  Freed when the last handle that references it is destroyed.
@@ -202,7 +209,7 @@ struct Captioner {
     // bytes of one (layer, k | v) block of the cross cache holding `rows` head rows
     size_t cross_block(size_t rows) const { return kv16 ? kv16_block_bytes(rows) : rows * kvrow; }
     size_t dev_bytes = 0;        // arena (+ the weights when this handle created the store)
-    std::vector<void*> allocs;   // arena: owned by this handle
+    std::vector<ArenaAlloc> allocs;   // arena: owned by this handle
     WeightStore* ws = nullptr;   // weights: shared
     bool replay = false;         // building a handle on an existing store: walloc hands out the store's buffers in order
     size_t wcur = 0;
@@ -278,11 +285,12 @@ struct Captioner {
     std::vector<ProfTag> prof_recs;
 };
 
-int dev_alloc(Captioner* m, void** p, size_t bytes) {
+// name: required for every kind but ARENA_SCRATCH (cap_debug_arena_kinds reports it)
+int dev_alloc(Captioner* m, void** p, size_t bytes, int kind = ARENA_SCRATCH, const char* name = nullptr) {
     bytes = (bytes + 255) & ~(size_t)255;
     if (bytes == 0) bytes = 256;
     CAP_HIP_CHECK(hipMalloc(p, bytes));
-    m->allocs.push_back(*p);
+    m->allocs.push_back({*p, bytes, kind, name});
     m->dev_bytes += bytes;
     return 0;
 }
@@ -599,7 +607,7 @@ int alloc_tower(Captioner* m, Tower& t, size_t M, size_t D, size_t F) {
 // the image tower's: patch rows (zero padding columns up to Kpad) and its activations over max_batch images
 int alloc_image_tower(Captioner* m) {
     const size_t Bm = m->c.max_batch, bytes = Bm * m->P * m->Kpad * m->esz;
-    TRY(dev_alloc(m, &m->patches, bytes));
+    TRY(dev_alloc(m, &m->patches, bytes, ARENA_KEPT, "patches"));
     CAP_HIP_CHECK(hipMemset(m->patches, 0, bytes));
     return alloc_tower(m, m->vt, Bm * m->NT, m->c.v_hidden, m->c.v_mlp);
 }
@@ -620,10 +628,10 @@ int build_arena_coca(Captioner* m) {
     TRY(dev_alloc(m, (void**)&m->img_tokens, Bm * Q * E * 4));
     TRY(dev_alloc(m, &m->xhat, Bm * Q * E * e));
     TRY(dev_alloc(m, &m->cross, (size_t)c.mm_layers * cross_slot_bytes(m, Bm)));
-    TRY(dev_alloc(m, (void**)&m->seq, R * Lm * 4));
-    TRY(dev_alloc(m, (void**)&m->finished, R * 4));
-    TRY(dev_alloc(m, (void**)&m->lens, R * 4));
-    TRY(dev_alloc(m, (void**)&m->anc, 2 * R * Lm * 4 + 256));    // beam ancestry of the self-attention caches (beam.hip)
+    TRY(dev_alloc(m, (void**)&m->seq, R * Lm * 4, ARENA_INDEX, "seq"));
+    TRY(dev_alloc(m, (void**)&m->finished, R * 4, ARENA_INDEX, "finished"));
+    TRY(dev_alloc(m, (void**)&m->lens, R * 4, ARENA_INDEX, "lens"));
+    TRY(dev_alloc(m, (void**)&m->anc, 2 * R * Lm * 4 + 256, ARENA_INDEX, "anc"));    // beam ancestry of the self-attention caches (beam.hip)
     TRY(dev_alloc(m, (void**)&m->dx, R * E * 4));
     TRY(dev_alloc(m, (void**)&m->dy, R * E * 4));
     TRY(dev_alloc(m, (void**)&m->dx2, (size_t)(R > SMALL_MAX_ROWS ? R : SMALL_MAX_ROWS) * E * 4));
@@ -636,7 +644,7 @@ int build_arena_coca(Captioner* m) {
     TRY(dev_alloc(m, (void**)&m->logits, R * (size_t)m->ldl * 4));
     for (SubLayer& u : m->dec.subs)
         if (u.kind == DEC_SELF) TRY(dev_alloc(m, &u.cache, 2 * R * H * Lm * 64 * e));
-    TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, (int)Lm)));      // (a 1-beam search exists: beam groups)
+    TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, (int)Lm), ARENA_INDEX, "beam"));      // (a 1-beam search exists: beam groups)
     return 0;
 }
 
@@ -648,12 +656,12 @@ int build_arena(Captioner* m) {
     TRY(dev_alloc(m, (void**)&m->emb_f, M * D * 4));
     TRY(dev_alloc(m, &m->emb_t, M * D * e));
     TRY(dev_alloc(m, &m->cross, (size_t)c.t_layers * cross_slot_bytes(m, Bm)));
-    TRY(dev_alloc(m, (void**)&m->seq, R * Lm * 4));
-    TRY(dev_alloc(m, (void**)&m->finished, R * 4));
-    TRY(dev_alloc(m, (void**)&m->lens, R * 4));
-    TRY(dev_alloc(m, (void**)&m->live, R * 4));
-    TRY(dev_alloc(m, (void**)&m->n_live, 256));
-    TRY(dev_alloc(m, (void**)&m->anc, 2 * R * Lm * 4));
+    TRY(dev_alloc(m, (void**)&m->seq, R * Lm * 4, ARENA_INDEX, "seq"));
+    TRY(dev_alloc(m, (void**)&m->finished, R * 4, ARENA_INDEX, "finished"));
+    TRY(dev_alloc(m, (void**)&m->lens, R * 4, ARENA_INDEX, "lens"));
+    TRY(dev_alloc(m, (void**)&m->live, R * 4, ARENA_INDEX, "live"));
+    TRY(dev_alloc(m, (void**)&m->n_live, 256, ARENA_INDEX, "n_live"));
+    TRY(dev_alloc(m, (void**)&m->anc, 2 * R * Lm * 4, ARENA_INDEX, "anc"));
     // prompt prefill (run_prefill): max_prompt - 1 known positions of every caption go through the decoder as ONE pass of rows, so
     // the buffers a pass over rows touches hold that many (CapConfig.max_prompt = 0: exactly the decode rows, as ever)
     // teacher-forced scoring (run_score): max_score_rows rows of a pass AND of its head (0: nothing beyond the above)
@@ -673,7 +681,7 @@ int build_arena(Captioner* m) {
     TRY(dev_alloc(m, (void**)&m->logits, Rh * (size_t)m->ldl * 4));
     for (SubLayer& u : m->dec.subs)
         if (u.kind == DEC_SELF) TRY(dev_alloc(m, &u.cache, 2 * R * H * Lm * 64 * e));
-    TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, (int)Lm)));
+    TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, (int)Lm), ARENA_INDEX, "beam"));
     return 0;
 }
 
@@ -869,14 +877,14 @@ int build_blip2(Captioner* m) {
         }
         TRY(dev_alloc(m, (void**)&m->dpart, dpart_bytes));
     }
-    TRY(dev_alloc(m, (void**)&m->seq, Bm * Lmax * 4));
-    TRY(dev_alloc(m, (void**)&m->finished, Bm * 4));
-    TRY(dev_alloc(m, (void**)&m->lens, Bm * 4));
+    TRY(dev_alloc(m, (void**)&m->seq, Bm * Lmax * 4, ARENA_INDEX, "seq"));
+    TRY(dev_alloc(m, (void**)&m->finished, Bm * 4, ARENA_INDEX, "finished"));
+    TRY(dev_alloc(m, (void**)&m->lens, Bm * 4, ARENA_INDEX, "lens"));
     m->ldl = (V + 3) & ~3;
     TRY(dev_alloc(m, (void**)&m->logits, Rm * (size_t)m->ldl * 4));
     if (c.max_beams > 1) {      // beam search (beam.hip): BOS + max_len token columns per row
-        TRY(dev_alloc(m, (void**)&m->anc, 2 * Rm * (c.max_len + 1) * 4));
-        TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, c.max_len + 1)));
+        TRY(dev_alloc(m, (void**)&m->anc, 2 * Rm * (c.max_len + 1) * 4, ARENA_INDEX, "anc"));
+        TRY(dev_alloc(m, &m->beam, beam_state_bytes((int)Bm, c.max_beams, c.max_len + 1), ARENA_INDEX, "beam"));
     }
     return 0;
 }
@@ -988,7 +996,7 @@ int build_blip2_itm(Captioner* m) {
     TRY(alloc_image_tower(m));
     TRY(dev_alloc(m, (void**)&m->emb_f, M * D * 4));
     TRY(dev_alloc(m, &m->emb_t, M * D * e));
-    TRY(dev_alloc(m, &m->itm_ckv, (size_t)ncross * M * 2 * Q * e));
+    TRY(dev_alloc(m, &m->itm_ckv, (size_t)ncross * M * 2 * Q * e, ARENA_KEPT, "itm_ckv"));
     TRY(alloc_post_rows(m, m->qr, Bm * nq, Q, F));
     return alloc_post_rows(m, m->tr, Bm * c.max_len, Q, F);
 }
@@ -2018,7 +2026,7 @@ int run_score_blip2(Captioner* m, const ScoreArgs& a, hipStream_t s) {
 // Everything a handle owns - also the exit of every failed cap_create (streams and events included).
 static void release_captioner(Captioner* m) {
     for (auto& r : m->prof_recs) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
-    for (void* p : m->allocs) (void)hipFree(p);
+    for (const ArenaAlloc& a : m->allocs) (void)hipFree(a.p);
     if (m->ws && m->ws->refs.fetch_sub(1) == 1) {        // last handle on these weights
         for (void* p : m->ws->ptrs) (void)hipFree(p);
         delete m->ws;
@@ -2255,6 +2263,42 @@ int cap_cross_cache_kind(CapHandle h) {
 }
 
 size_t cap_device_bytes(CapHandle h) { return h ? ((Captioner*)h)->dev_bytes : 0; }
+
+long long cap_debug_fill_arena(CapHandle h, uint32_t pattern, void* stream) {
+    Captioner* m = (Captioner*)h;
+    if (!m) { cap_set_error("cap_debug_fill_arena: null handle"); return -1; }
+    long long filled = 0;
+    for (const ArenaAlloc& a : m->allocs) {
+        if (a.kind != ARENA_SCRATCH) continue;
+        if (launch_fill_i32((int*)a.p, (int)pattern, a.bytes / 4, (hipStream_t)stream) != 0) return -1;    // bytes: a multiple of 256
+        filled += (long long)a.bytes;
+    }
+    return filled;
+}
+
+int cap_debug_arena_kinds(CapHandle h, char* buf, size_t buf_bytes) {
+    Captioner* m = (Captioner*)h;
+    if (!m || !buf) { cap_set_error("cap_debug_arena_kinds: null argument"); return -1; }
+    size_t total[ARENA_KINDS] = {0, 0, 0};
+    std::string names[ARENA_KINDS];
+    for (const ArenaAlloc& a : m->allocs) {
+        if (a.kind < 0 || a.kind >= ARENA_KINDS || (a.kind != ARENA_SCRATCH && !a.name)) {
+            cap_set_error("cap_debug_arena_kinds: an allocation of kind %d has no name", a.kind);
+            return -1;
+        }
+        total[a.kind] += a.bytes;
+        if (a.kind != ARENA_SCRATCH) names[a.kind] += std::string(names[a.kind].empty() ? "\"" : ", \"") + a.name + "\"";
+    }
+    // the handle's arena as cap_device_bytes counts it: everything it allocated less the weights it created
+    const size_t arena = m->dev_bytes - (m->replay || !m->ws ? 0 : m->ws->bytes);
+    char head[256];
+    snprintf(head, sizeof(head), "{\"arena_bytes\": %zu, \"scratch_bytes\": %zu, \"index_bytes\": %zu, \"kept_bytes\": %zu, ", arena,
+             total[ARENA_SCRATCH], total[ARENA_INDEX], total[ARENA_KEPT]);
+    const std::string out = std::string(head) + "\"index\": [" + names[ARENA_INDEX] + "], \"kept\": [" + names[ARENA_KEPT] + "]}";
+    if (out.size() + 1 > buf_bytes) { cap_set_error("cap_debug_arena_kinds: buffer too small (%zu needed)", out.size() + 1); return -1; }
+    memcpy(buf, out.c_str(), out.size() + 1);
+    return 0;
+}
 
 int cap_load_weight(CapHandle h, const char* name, const float* data, int on_device, int ndim, const int64_t* shape,
                     void* stream) {

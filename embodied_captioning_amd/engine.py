@@ -656,6 +656,22 @@ class CaptionerEngine:
         N.check(self.lib.cap_profile_report(self._h, buf, len(buf)), "cap_profile_report")
         return json.loads(buf.value.decode())
 
+    # ------------------------------------------------------------------------------------------ arena state (tests only)
+    def _fill_arena(self, pattern: int) -> int:
+        """Write the 32-bit pattern over every scratch buffer of this handle's arena on the current stream (index and kept buffers
+        and the weights are left alone); returns the bytes filled.  For tests/test_arena_state_gpu.py: no product code calls it."""
+        with torch.cuda.device(self.device):
+            n = int(self.lib.cap_debug_fill_arena(self._h, C.c_uint32(pattern & 0xFFFFFFFF), C.c_void_p(_stream_ptr(self.device))))
+        if n < 0:
+            raise N.CaptionerHipError(f"cap_debug_fill_arena: {N.last_error()}")
+        return n
+
+    def _arena_kinds(self) -> dict:
+        """{"arena_bytes", "scratch_bytes", "index_bytes", "kept_bytes", "index": [names], "kept": [names]} of this handle's arena."""
+        buf = C.create_string_buffer(1 << 12)
+        N.check(self.lib.cap_debug_arena_kinds(self._h, buf, len(buf)), "cap_debug_arena_kinds")
+        return json.loads(buf.value.decode())
+
 
 class EnginePool:
     """Several CaptionerEngines on their own streams: consecutive batches overlap.  Every engine has its own arena (activations,
@@ -946,6 +962,8 @@ class TextEncoderEngine:
     device_bytes = CaptionerEngine.device_bytes
     profile = CaptionerEngine.profile
     profile_report = CaptionerEngine.profile_report
+    _fill_arena = CaptionerEngine._fill_arena
+    _arena_kinds = CaptionerEngine._arena_kinds
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> None:
         """HF BertModel names; a leading `0.auto_model.` / `bert.` prefix (sentence-transformers / BertFor* saves) is dropped."""
@@ -1021,6 +1039,8 @@ class ClipEngine:
     saturations = CaptionerEngine.saturations
     profile = CaptionerEngine.profile
     profile_report = CaptionerEngine.profile_report
+    _fill_arena = CaptionerEngine._fill_arena
+    _arena_kinds = CaptionerEngine._arena_kinds
     _pixels = CaptionerEngine._pixels
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> Dict[str, object]:
@@ -1137,6 +1157,8 @@ class Blip2ItmEngine:
     saturations = CaptionerEngine.saturations
     profile = CaptionerEngine.profile
     profile_report = CaptionerEngine.profile_report
+    _fill_arena = CaptionerEngine._fill_arena
+    _arena_kinds = CaptionerEngine._arena_kinds
     _pixels = CaptionerEngine._pixels
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> Dict[str, object]:

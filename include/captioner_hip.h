@@ -411,6 +411,25 @@ long long cap_g8_saturations(int reset);
  * (cap_create); a cap_create_shared handle reports its arena only. */
 size_t cap_device_bytes(CapHandle h);
 
+/* ---- arena state (tests only: no product code calls these) ----
+ * Every buffer of a handle's arena has a kind (DESIGN.md "Arena state"):
+ *   scratch  fp32 / compute-type / KV16 data that a call writes before it reads - no result may depend on what it held before;
+ *   index    int32 tables (token rows, finished / length flags, row maps, beam ancestry, the beam state block);
+ *   kept     initialised at create, or carrying state from one ABI call to a later one by documented contract.
+ * cap_debug_fill_arena writes the 32-bit pattern over every scratch allocation of THIS handle's arena, rounded tail included,
+ * stream-ordered on `stream`, and returns the bytes filled (-1 on error).  Kept and index buffers are not touched, and neither
+ * is the weight store (of a cap_create_shared handle or any other).  0xFFFFFFFF is a NaN as fp32, as bf16 and as both fp16
+ * halves of a split-fp16 word (and -1 with a NaN scale in a KV16 block); 0x42F742F7 is finite in all of them.
+ * Index buffers are not poisoned on purpose: the only way a stale index shows is as an address, and an arbitrary one may lie
+ * outside every allocation.  What reaches them is running a different call first (tests/test_arena_state_gpu.py, case d),
+ * which leaves in-range but wrong indices behind.
+ * cap_debug_arena_kinds writes a JSON object {"arena_bytes": n, "scratch_bytes": n, "index_bytes": n, "kept_bytes": n,
+ * "index": ["name", ...], "kept": ["name", ...]} into buf: arena_bytes is cap_device_bytes less the weights this handle
+ * created, so the three totals add up to it exactly when every arena allocation is classified; the names are those of the
+ * index and kept allocations in allocation order. */
+long long cap_debug_fill_arena(CapHandle h, uint32_t pattern, void* stream);
+int cap_debug_arena_kinds(CapHandle h, char* buf, size_t buf_bytes);
+
 /* Per-kernel timing with HIP events on the launch stream (bench.py's roofline leg).  While enabled every launch of the
  * tagged kernels is bracketed by an event pair; cap_profile_report synchronises the stream and writes a JSON object
  * {"tag": {"launches": n, "ms": total, "flops": f, "bytes": b}, ...} into buf. */

@@ -69,6 +69,18 @@ def test_product_package_never_imports_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M), os.path.join(dp, fn)
 
 
+def test_arena_debug_calls_are_bound_by_the_engine_module_alone():
+    """cap_debug_fill_arena / cap_debug_arena_kinds are for tests/test_arena_state_gpu.py: bound in _native.py, wrapped once in
+    engine.py (`_fill_arena`, `_arena_kinds`), named by no other module of the product package."""
+    pkg = os.path.join(ROOT, "embodied_captioning_amd")
+    users = set()
+    for dp, _, fns in os.walk(pkg):
+        for fn in fns:
+            if fn.endswith(".py") and re.search(r"cap_debug_|_fill_arena|_arena_kinds", open(os.path.join(dp, fn)).read()):
+                users.add(os.path.relpath(os.path.join(dp, fn), pkg))
+    assert users == {"_native.py", "engine.py"}
+
+
 @pytest.mark.skipif(os.environ.get("CAP_RUN_ASAN") != "1", reason="rebuilds every .hip file with -fsanitize=address (~2 min): "
                     "set CAP_RUN_ASAN=1; the committed run is profiles/r02_asan_host.txt")
 def test_host_side_asan_run_of_the_abi_argument_handling(tmp_path):
