@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libcaptioner_hip.so")
 
 CAP_F32, CAP_BF16, CAP_F32_SPLIT = 0, 1, 2
 CAP_PIX_F32_NCHW, CAP_PIX_U8_NHWC = 0, 1
+CAP_PIX_IMAGE_STATE = 2  # `pixels` = B image-state records (cap_encode_image_state): the decoding calls only
 CAP_ARCH_CLIP = 4
 CAP_ARCH_BLIP2_ITM = 5
 CAP_ACT_QUICK_GELU, CAP_ACT_GELU = 0, 1
@@ -90,6 +91,8 @@ _SIGNATURES = {
     "cap_load_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p]),
     "cap_finalize_weights": (C.c_int, [C.c_void_p]),
     "cap_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "cap_image_state_bytes": (C.c_size_t, [C.c_void_p]),
+    "cap_encode_image_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cap_generate_request": (C.c_int, [C.c_void_p, C.POINTER(CapGenerateArgs), C.c_void_p]),
     "cap_generate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -129,6 +132,8 @@ _SIGNATURES = {
     "cap_op_gemm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cap_op_pack_kv16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cap_op_image_state_pack": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cap_op_image_state_unpack": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cap_op_gemm_crosskv": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cap_op_gemm_partial": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "cap_op_layernorm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,

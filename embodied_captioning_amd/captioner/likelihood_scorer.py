@@ -65,7 +65,8 @@ class CaptionLikelihoodScorer:
         """Every caption against every image -> float64 [n_images, n_captions] of mean token log-probs.  Each image is encoded
         once; a caption that occurs several times is scored once per image and its column copied.  A caption longer than the
         engine scores (`engine.score_limit` tokens, BOS and [SEP] included) is not scored: its column is -inf, so it ranks last, and
-        a warning names it - one long caption does not end a whole selection run."""
+        a warning names it - one long caption does not end a whole selection run.  `images` may be the model's image state
+        (`model.image_state(crops)`, a uint8 [n, image_state_bytes] tensor): the image side then does not run at all."""
         captions = list(captions)
         key = [c if isinstance(c, str) else tuple(int(i) for i in c) for c in captions]
         limit = int(self.model.engine.score_limit)

@@ -23,7 +23,7 @@ import torch
 
 from ...captioning_predictor import CaptioningPredictor
 from ....config import BlipArch
-from ....engine import CaptionerEngine
+from ....engine import CaptionerEngine, images_or_state
 from ....weights import (load_hf_blip_checkpoint, load_state_dict_file, procedural_blip_state_dict, resolve_hf_dir,
                          BLIP_TIED)
 
@@ -170,6 +170,8 @@ class BLIP(CaptioningPredictor):
         S = self.arch.image_size
         if isinstance(images, torch.Tensor):
             t = images
+            if t.dtype == torch.uint8 and t.dim() == 2:        # an image state (`image_state`): the engine takes it as it is
+                return t
             if t.dtype == torch.uint8:
                 if t.dim() == 3:
                     t = t[None]
@@ -217,9 +219,18 @@ class BLIP(CaptioningPredictor):
 
     # ------------------------------------------------------------------------------------------ forward
     @torch.no_grad()
-    def generate_batch(self, images, output_logits: bool = False, output_perplexity: bool = False,
-                       output_vocab_maxprob: bool = False, prompt=None, prompt_ids=None) -> dict:
-        """prompt (string) / prompt_ids (token ids [P], or [N, P] one row per image): the text every caption starts with, for this
+    def image_state(self, images) -> torch.Tensor:
+        """The image side alone, once: images as `generate_batch` takes them (the same preprocessing) -> uint8 [N, image_state_bytes]
+        on the device (`CaptionerEngine.image_state`).  `generate_batch(image_state=...)` and `score_captions(image_state=...)`
+        decode from it - or from any selection of its rows - without running the image side again, to the bits of the calls on the
+        images.  It belongs to this model's weights and configuration."""
+        return self.engine.image_state(self.preprocess(images).to(self._device))
+
+    @torch.no_grad()
+    def generate_batch(self, images=None, output_logits: bool = False, output_perplexity: bool = False,
+                       output_vocab_maxprob: bool = False, prompt=None, prompt_ids=None, image_state=None) -> dict:
+        """image_state: the tensor `image_state(images)` returned (or rows of it), in place of images: the image side does not run.
+        prompt (string) / prompt_ids (token ids [P], or [N, P] one row per image): the text every caption starts with, for this
         call; without them the configured captioner.prompt / captioner.prompt_ids (if any).  Texts and sequences include the prompt,
         per-step outputs cover the generated steps.
         Batched extension: any number of frames -> {"texts": [str], "sequences": int32 [N, L], "lengths", "scores"}.
@@ -235,7 +246,8 @@ class BLIP(CaptioningPredictor):
         kw["length_penalty"] = self.length_penalty
         seqs, lens, scores, logits = [], [], [], []
         pool = getattr(self, "pool", None)
-        n_images = int(images.shape[0]) if isinstance(images, torch.Tensor) and images.dim() == 4 else \
+        images = images_or_state(images, image_state, "generate_batch")
+        n_images = int(images.shape[0]) if isinstance(images, torch.Tensor) and (images.dim() == 4 or image_state is not None) else \
             len(images) if isinstance(images, (list, tuple)) else 1
         pk = self._call_prompt(prompt, prompt_ids, n_images)
         bs = self.batch_size
@@ -312,8 +324,9 @@ class BLIP(CaptioningPredictor):
         return ids if ids and ids[0] == self.arch.bos else [int(self.arch.bos)] + ids
 
     @torch.no_grad()
-    def score_captions(self, images, captions) -> dict:
-        """Teacher-forced likelihood of GIVEN captions under this captioner (`CaptionerEngine.score`; HF `model(pixel_values,
+    def score_captions(self, images=None, captions=None, image_state=None) -> dict:
+        """image_state: the tensor `image_state(images)` returned (or rows of it), in place of images.
+        Teacher-forced likelihood of GIVEN captions under this captioner (`CaptionerEngine.score`; HF `model(pixel_values,
         input_ids=...)` reduced to log-probs).  captions: one per image (strings, or token-id lists for models without a tokenizer),
         or a list of candidates per image (a list of lists; images may have different numbers of candidates).
         -> host tensors, caption-major ([image 0's candidates, image 1's, ...], images with fewer candidates padded with absent
@@ -323,6 +336,9 @@ class BLIP(CaptioningPredictor):
         longer than the engine takes (`engine.score_limit`) are refused; scoring longer than batch_size x num_beams tokens needs
         captioner.max_score_rows."""
         from ....engine import score_summary
+        images = images_or_state(images, image_state, "score_captions")
+        if captions is None:
+            raise ValueError("score_captions: no caption to score")
         captions = list(captions)
         nested = bool(captions) and all(isinstance(c, (list, tuple)) and (len(c) == 0 or isinstance(c[0], (str, list, tuple))) for c in captions)
         groups = [list(c) for c in captions] if nested else [[c] for c in captions]

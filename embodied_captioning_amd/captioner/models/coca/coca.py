@@ -21,7 +21,7 @@ import torch
 
 from ...captioning_predictor import CaptioningPredictor
 from ....config import CocaArch
-from ....engine import CaptionerEngine
+from ....engine import CaptionerEngine, images_or_state
 from ....weights import load_state_dict_file, procedural_coca_state_dict
 
 logger = logging.getLogger(__name__)
@@ -133,6 +133,8 @@ class CoCa(CaptioningPredictor):
         from PIL import Image
         S = self.arch.image_size
         if isinstance(images, torch.Tensor):
+            if images.dtype == torch.uint8 and images.dim() == 2:      # an image state (`image_state`): the engine takes it as it is
+                return images
             return images if images.dim() == 4 else images[None]
         if isinstance(images, Image.Image):
             images = [images]
@@ -194,11 +196,20 @@ class CoCa(CaptioningPredictor):
         return out["sequences"]
 
     @torch.no_grad()
-    def generate_batch(self, images, output_perplexity: bool = False, output_vocab_maxprob: bool = False) -> dict:
-        """output_perplexity (the greedy top-k(1) loop): adds "perplexities" float64 [N] - `forward` + `compute_perplexity()` one crop
+    def image_state(self, images) -> torch.Tensor:
+        """The image side alone, once (ViT, pooler, cross K/V): images as `generate_batch` takes them -> uint8 [N, image_state_bytes] on
+        the device (`CaptionerEngine.image_state`); `generate_batch(image_state=...)` decodes from it, or from rows of it, to the
+        bits of the call on the images.  It belongs to this model's weights and configuration."""
+        return self.engine.image_state(self.preprocess(images).to(self._device))
+
+    @torch.no_grad()
+    def generate_batch(self, images=None, output_perplexity: bool = False, output_vocab_maxprob: bool = False, image_state=None) -> dict:
+        """image_state: the tensor `image_state(images)` returned (or rows of it), in place of images: the image side does not run.
+        output_perplexity (the greedy top-k(1) loop): adds "perplexities" float64 [N] - `forward` + `compute_perplexity()` one crop
         at a time - with the "token_logprobs" / "scored_steps" behind them (engine.generate, output_logprobs).
         output_vocab_maxprob (the same loop): adds "vocab_maxprob" fp32 [N, vocab] ON THE DEVICE (engine.generate,
         output_vocab_maxprob - the input of `engine.fuse_vocab_groups`) with "token_logprobs" / "scored_steps" on the host."""
+        images = images_or_state(images, image_state, "generate_batch")
         kw = dict(num_beams=self.num_beams, max_length=self.arch.seq_len, num_beam_groups=self.num_beam_groups)
         if output_perplexity:
             kw["output_logprobs"] = True

@@ -1563,9 +1563,33 @@ __global__ void copy_i32_kernel(const int* s, int* d, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) d[i] = s[i];
 }
 
+// Image state (captioner_hip.h): what the decode side reads from the image side and where it lives in the arena - BLIP / CoCa the
+// cross K/V cache, BLIP-2 the language projection's fp32 rows as 16-byte pieces.
+bool takes_image_state(const Captioner* m) {
+    return m->c.arch == CAP_ARCH_BLIP || m->c.arch == CAP_ARCH_COCA || m->c.arch == CAP_ARCH_BLIP2;
+}
+ImageStateLayout image_state_layout(const Captioner* m) {
+    const CapConfig& c = m->c;
+    if (c.arch == CAP_ARCH_BLIP2) return {1, c.num_query_tokens * c.t_hidden / 4, 16, 0};
+    return {2 * (c.arch == CAP_ARCH_COCA ? c.mm_layers : c.t_layers), c.t_heads * m->dec.kv_tokens, m->kv16 ? 128 : (int)(64 * m->esz),
+            m->kv16 ? 1 : 0};
+}
+void* image_state_buffer(const Captioner* m) { return m->c.arch == CAP_ARCH_BLIP2 ? (void*)m->lm_proj : m->cross; }
+int export_image_state(Captioner* m, int B, void* state, hipStream_t s) {
+    const ImageStateLayout L = image_state_layout(m);
+    ProfScope ps(m, s, "state_export", 0, 2.0 * B * L.record_bytes());
+    return launch_image_state_pack(L, B, image_state_buffer(m), state, s);
+}
+int import_image_state(Captioner* m, const void* state, int B, hipStream_t s) {
+    const ImageStateLayout L = image_state_layout(m);
+    ProfScope ps(m, s, "state_import", 0, 2.0 * B * L.record_bytes());
+    return launch_image_state_unpack(L, B, image_state_buffer(m), state, s);
+}
+
 static int run_image_side(Captioner* m, const void* pixels, int fmt, int B, hipStream_t s) {
     const CapConfig& c = m->c;
     const int NT = m->NT, D = c.v_hidden, T = c.t_hidden, H = c.t_heads;
+    if (fmt == CAP_PIX_IMAGE_STATE) return import_image_state(m, pixels, B, s);
     TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
     if (c.arch == CAP_ARCH_COCA) {
         TRY(run_coca_pool(m, B, nullptr, s));
@@ -1939,15 +1963,23 @@ int run_beams_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
     return 0;
 }
 
-// BLIP-2's front half over the B images of a call: encoder, the Q-Former's caption pass, the language projection, and the prompt pass
+// BLIP-2's image side: encoder, the Q-Former's caption pass, the language projection -> m->lm_proj fp32 [B * num_query_tokens, T]
+int run_blip2_image_side(Captioner* m, const void* pixels, int fmt, int B, hipStream_t s) {
+    const CapConfig& c = m->c;
+    const int T = c.t_hidden, nq = c.num_query_tokens;
+    TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
+    TRY(run_qformer(m, kCaptionPass, B, nq, 0, nullptr, nullptr, s));
+    return gemm(m, s, "b2_gemm_lproj", m->qr.x_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1);
+}
+
+// BLIP-2's front half over the B images of a call: the image side (or the import of its state), and the prompt pass
 // over the P = query tokens + BOS positions, which leaves image b's prompt in cache row b * K and its BOS logits in row b * K of
 // m->logits (K > 1: for the K rows of a beam search).
 int run_blip2_prompt(Captioner* m, const void* pixels, int fmt, int B, int K, hipStream_t s) {
     const CapConfig& c = m->c;
     const int T = c.t_hidden, nq = c.num_query_tokens;
-    TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
-    TRY(run_qformer(m, kCaptionPass, B, nq, 0, nullptr, nullptr, s));
-    TRY(gemm(m, s, "b2_gemm_lproj", m->qr.x_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1));
+    if (fmt == CAP_PIX_IMAGE_STATE) TRY(import_image_state(m, pixels, B, s));
+    else TRY(run_blip2_image_side(m, pixels, fmt, B, s));
     TRY(launch_opt_prefill_inputs(m->lm_proj, m->o_tok, m->o_pos, m->ox, B, nq, T, c.bos, s));
     return run_opt_pass(m, B, nq + 1, s, K > 1 ? OptRows::beams(K) : OptRows());
 }
@@ -2368,7 +2400,12 @@ int cap_finalize_weights(CapHandle h) {
     return missing;
 }
 
-static int check_call(Captioner* m, int B, int K, int Lm, int fmt, const char* who) {
+// what an entry point that needs pixels says to CAP_PIX_IMAGE_STATE
+#define REFUSE_IMAGE_STATE(who) cap_set_error("%s: CAP_PIX_IMAGE_STATE is taken by cap_generate_request, the cap_generate* calls and " \
+                                              "cap_score_captions; this call needs pixels (CAP_PIX_F32_NCHW or CAP_PIX_U8_NHWC)", who)
+
+// state_ok: the call decodes, so `pixels` may be image-state records (validate_generate / validate_score look at the pointer)
+static int check_call(Captioner* m, int B, int K, int Lm, int fmt, const char* who, bool state_ok = false) {
     if (!m) { cap_set_error("%s: null handle", who); return -1; }
     if (cap_finalize_weights((CapHandle)m) != 0) return -1;
     if (B < 1 || B > m->c.max_batch || K < 1 || K > m->c.max_beams || Lm < (m->c.arch == CAP_ARCH_BLIP2 ? 1 : 2) || Lm > m->c.max_len) {
@@ -2376,7 +2413,8 @@ static int check_call(Captioner* m, int B, int K, int Lm, int fmt, const char* w
                       m->c.max_batch, m->c.max_beams, m->c.max_len);
         return -1;
     }
-    if (fmt != CAP_PIX_F32_NCHW && fmt != CAP_PIX_U8_NHWC) { cap_set_error("%s: unknown pixel format %d", who, fmt); return -1; }
+    if (fmt == CAP_PIX_IMAGE_STATE && !state_ok) { REFUSE_IMAGE_STATE(who); return -1; }
+    if (fmt != CAP_PIX_F32_NCHW && fmt != CAP_PIX_U8_NHWC && fmt != CAP_PIX_IMAGE_STATE) { cap_set_error("%s: unknown pixel format %d", who, fmt); return -1; }
     if (m->c.arch == CAP_ARCH_MINILM) { cap_set_error("%s: this handle is a sentence encoder: use cap_embed_text", who); return -1; }
     if (m->c.arch == CAP_ARCH_CLIP) { cap_set_error("%s: this handle is a CLIP scorer: use cap_clip_embed_images / cap_clip_embed_text", who); return -1; }
     if (m->c.arch == CAP_ARCH_BLIP2_ITM) { cap_set_error("%s: this handle is a BLIP-2 image-text scorer: use cap_blip2_itm_encode_images / cap_blip2_itc_* / cap_blip2_itm_logits", who); return -1; }
@@ -2394,6 +2432,7 @@ int cap_clip_embed_images(CapHandle h, const void* pixels, int pixel_fmt, int B,
     TRY(check_clip(m, "cap_clip_embed_images"));
     if (!pixels || !out) { cap_set_error("cap_clip_embed_images: null buffer"); return -1; }
     if (B < 1 || B > m->c.max_batch) { cap_set_error("cap_clip_embed_images: B=%d exceeds the handle's capacity (%d)", B, m->c.max_batch); return -1; }
+    if (pixel_fmt == CAP_PIX_IMAGE_STATE) { REFUSE_IMAGE_STATE("cap_clip_embed_images"); return -1; }
     if (pixel_fmt != CAP_PIX_F32_NCHW && pixel_fmt != CAP_PIX_U8_NHWC) { cap_set_error("unknown pixel format %d", pixel_fmt); return -1; }
     return run_clip_images(m, pixels, pixel_fmt, B, out, (hipStream_t)stream);
 }
@@ -2447,6 +2486,7 @@ int cap_blip2_itm_encode_images(CapHandle h, const void* pixels, int pixel_fmt, 
     TRY(check_itm(m, "cap_blip2_itm_encode_images"));
     if (!pixels) { cap_set_error("cap_blip2_itm_encode_images: null buffer"); return -1; }
     if (B < 1 || B > m->c.max_batch) { cap_set_error("cap_blip2_itm_encode_images: B=%d exceeds the handle's capacity (max_batch %d)", B, m->c.max_batch); return -1; }
+    if (pixel_fmt == CAP_PIX_IMAGE_STATE) { REFUSE_IMAGE_STATE("cap_blip2_itm_encode_images"); return -1; }
     if (pixel_fmt != CAP_PIX_F32_NCHW && pixel_fmt != CAP_PIX_U8_NHWC) { cap_set_error("unknown pixel format %d", pixel_fmt); return -1; }
     return run_itm_images(m, pixels, pixel_fmt, B, (hipStream_t)stream);
 }
@@ -2519,16 +2559,39 @@ int cap_encode(CapHandle h, const void* pixels, int pixel_fmt, int B, float* out
     return run_encoder(m, pixels, pixel_fmt, B, out_embeds, (hipStream_t)stream);
 }
 
+size_t cap_image_state_bytes(CapHandle h) {
+    const Captioner* m = (const Captioner*)h;
+    if (!m) { cap_set_error("cap_image_state_bytes: null handle"); return 0; }
+    if (!takes_image_state(m)) {
+        cap_set_error("cap_image_state_bytes: an image state is what a BLIP, CoCa or BLIP-2 captioner decodes from; this handle's arch is %d", m->c.arch);
+        return 0;
+    }
+    return image_state_layout(m).record_bytes();
+}
+
+int cap_encode_image_state(CapHandle h, const void* pixels, int pixel_fmt, int B, void* out_state, void* stream) {
+    Captioner* m = (Captioner*)h;
+    const char* who = "cap_encode_image_state";
+    if (!m) { cap_set_error("%s: null handle", who); return -1; }
+    TRY(check_call(m, B, 1, m->c.arch == CAP_ARCH_BLIP2 ? 1 : 2, pixel_fmt, who));
+    if (!pixels || !out_state) { cap_set_error("%s: null buffer", who); return -1; }
+    if (((uintptr_t)out_state & 15) != 0) { cap_set_error("%s: out_state must be 16-byte aligned", who); return -1; }
+    if (m->c.arch == CAP_ARCH_BLIP2) TRY(run_blip2_image_side(m, pixels, pixel_fmt, B, (hipStream_t)stream));
+    else TRY(run_image_side(m, pixels, pixel_fmt, B, (hipStream_t)stream));
+    return export_image_state(m, B, out_state, (hipStream_t)stream);
+}
+
 // Every rule of a generate request, each once, in the order of refusal: the handle and its capacity (check_call), buffers, what the
 // architecture takes, shapes - all before anything is launched.  who: the entry point the caller used; missing: what that entry
 // point requires beyond the request's own rules and did not get (null: nothing).
 static int validate_generate(Captioner* m, const CapGenerateArgs& a, const char* who, const char* missing) {
 #define REFUSE_IF(cond, ...) do { if (cond) { cap_set_error(__VA_ARGS__); return -1; } } while (0)
-    TRY(check_call(m, a.B, a.num_beams, a.max_len, a.pixel_fmt, who));
+    TRY(check_call(m, a.B, a.num_beams, a.max_len, a.pixel_fmt, who, true));
     const CapConfig& c = m->c;
     const int K = a.num_beams, G = a.num_beam_groups, P = a.prompt_len;
     const bool greedy = K == 1 && !G;
     REFUSE_IF(!a.pixels || !a.out_ids, "%s: null buffer", who);
+    REFUSE_IF(a.pixel_fmt == CAP_PIX_IMAGE_STATE && ((uintptr_t)a.pixels & 15) != 0, "%s: the image state must be 16-byte aligned", who);
     REFUSE_IF(missing, "%s: %s", who, missing);
     REFUSE_IF(a.prompt_ids && c.arch != CAP_ARCH_BLIP,
               "%s: a text prompt is taken by CAP_ARCH_BLIP handles (this handle's arch is %d: CoCa's `text=` and BLIP-2's prompt are not built)",
@@ -2634,9 +2697,10 @@ static int validate_score(Captioner* m, const ScoreArgs& a, const char* who) {
     REFUSE_IF(m->c.arch == CAP_ARCH_COCA, "%s: scoring given captions is not built for CoCa handles (CAP_ARCH_COCA): BLIP and BLIP-2 only", who);
     const bool b2 = m->c.arch == CAP_ARCH_BLIP2;
     // capacity: BLIP's max_len counts the caption's tokens with BOS, BLIP-2's the tokens behind BOS
-    TRY(check_call(m, a.B, 1, b2 ? std::max(a.L - 1, 1) : std::max(a.L, 2), a.pixel_fmt, who));
+    TRY(check_call(m, a.B, 1, b2 ? std::max(a.L - 1, 1) : std::max(a.L, 2), a.pixel_fmt, who, true));
     REFUSE_IF(m->c.arch != CAP_ARCH_BLIP && !b2, "%s: the handle is not a BLIP / BLIP-2 captioner (arch %d)", who, m->c.arch);
     REFUSE_IF(!a.pixels || !a.ids || !a.lens || !a.out_tlp || !a.out_top || !a.out_top_ids || !a.out_scored, "%s: null buffer", who);
+    REFUSE_IF(a.pixel_fmt == CAP_PIX_IMAGE_STATE && ((uintptr_t)a.pixels & 15) != 0, "%s: the image state must be 16-byte aligned", who);
     REFUSE_IF(a.C < 1, "%s: captions_per_image %d must be at least 1", who, a.C);
     REFUSE_IF(a.L < 2, "%s: L = %d - a caption has BOS and at least one scored token", who, a.L);
     REFUSE_IF(!b2 && a.L - 1 > PREFILL_MAX_POS, "%s: L = %d exceeds the %d tokens a scoring pass takes (%d positions)", who, a.L, PREFILL_MAX_POS + 1,
@@ -2970,6 +3034,24 @@ int cap_op_gemm_crosskv(int dtype, const void* A, const void* W, const float* bi
 }
 int cap_op_pack_kv16(const float* src, void* dst, size_t n_rows, void* stream) {
     return launch_pack_kv16(src, dst, n_rows, (hipStream_t)stream);
+}
+static int op_image_state_layout(const char* who, int kind, int slots, int heads, int tokens, ImageStateLayout& L) {
+    if (kind < 0 || kind > 2 || slots < 1 || heads < 1 || tokens < 1 || (long long)heads * tokens > 0x3fffffff || slots > 0x3fffffff) {
+        cap_set_error("%s: kind %d (0 fp32, 1 bf16, 2 KV16), %d slots, %d heads, %d tokens", who, kind, slots, heads, tokens);
+        return -1;
+    }
+    L = {2 * slots, heads * tokens, kind == 0 ? 256 : 128, kind == 2 ? 1 : 0};
+    return 0;
+}
+int cap_op_image_state_pack(int kind, int slots, int heads, int tokens, int B, const void* cache, void* state, void* stream) {
+    ImageStateLayout L;
+    TRY(op_image_state_layout("cap_op_image_state_pack", kind, slots, heads, tokens, L));
+    return launch_image_state_pack(L, B, cache, state, (hipStream_t)stream);
+}
+int cap_op_image_state_unpack(int kind, int slots, int heads, int tokens, int B, void* cache, const void* state, void* stream) {
+    ImageStateLayout L;
+    TRY(op_image_state_layout("cap_op_image_state_unpack", kind, slots, heads, tokens, L));
+    return launch_image_state_unpack(L, B, cache, state, (hipStream_t)stream);
 }
 int cap_op_beam_candidates(const float* logits, int ld, int V, int B, int K, int legacy_raw, int masked_id, float* out_val,
                            int32_t* out_idx, void* stream) {

@@ -1078,4 +1078,103 @@ int launch_copy_f32(const float* src, float* dst, size_t n, hipStream_t s) {
     return 0;
 }
 
+// ---- image state: records <-> the call-packed buffer (ops.h, ImageStateLayout) ----------------------------------------------
+// Two copies.  Payload: one row = cpr 16-byte chunks, a lane per chunk, so a wave moves whole rows that are contiguous on both sides
+// except where a record or a KV16 group ends; rows are numbered [image][section][row] (the record's order), a workgroup takes
+// IMAGE_STATE_ROWS_PER_LANE sets of 256 / cpr rows and issues all its loads before its stores.  The KV16 scales are a 4-byte stream of
+// their own in the workgroups behind the payload's, a lane per scale; the same workgroups write a record's zero padding (pack only).
+// unpack writes the rows (and scales) of the B images and nothing else of the buffer.
+constexpr int IMAGE_STATE_ROWS_PER_LANE = 4;
+struct ImageStateGeom {
+    int sections, rows, cpr, kv16, B;
+    int scale_dwords;                    // per section: the rows' scales and their padding to 16 bytes (0 without scales)
+    int tail_dwords;                     // zeros that close a record
+    unsigned payload_blocks;
+    size_t rec_bytes, sec_bytes, block_bytes;
+};
+template <bool PACK>
+__device__ __forceinline__ void image_state_move(const ImageStateGeom& g, char* __restrict__ buf, char* __restrict__ state) {
+    if (blockIdx.x < g.payload_blocks) {
+        const int rpb = 256 / g.cpr, lr = (int)threadIdx.x / g.cpr, ch = (int)threadIdx.x - lr * g.cpr;
+        const size_t per_img = (size_t)g.sections * g.rows, total = per_img * g.B, row_bytes = (size_t)g.cpr * 16;
+        uint4 v[IMAGE_STATE_ROWS_PER_LANE];
+        uint4* dst[IMAGE_STATE_ROWS_PER_LANE];
+#pragma unroll
+        for (int u = 0; u < IMAGE_STATE_ROWS_PER_LANE; ++u) {
+            const size_t row = ((size_t)blockIdx.x * IMAGE_STATE_ROWS_PER_LANE + u) * rpb + lr;
+            dst[u] = nullptr;
+            if (row >= total) continue;
+            const size_t img = row / per_img, rem = row - img * per_img, sec = rem / g.rows, r = rem - sec * g.rows;
+            const size_t ri = img * g.rows + r;                  // the row inside the section's block of the buffer
+            char* b = buf + sec * g.block_bytes + (g.kv16 ? kv16_row_off(ri) : ri * row_bytes) + ch * 16;
+            char* st = state + img * g.rec_bytes + sec * g.sec_bytes + r * row_bytes + ch * 16;
+            v[u] = *reinterpret_cast<const uint4*>(PACK ? b : st);
+            dst[u] = reinterpret_cast<uint4*>(PACK ? st : b);
+        }
+#pragma unroll
+        for (int u = 0; u < IMAGE_STATE_ROWS_PER_LANE; ++u)
+            if (dst[u]) *dst[u] = v[u];
+        return;
+    }
+    const size_t n_scale = (size_t)g.sections * g.scale_dwords, aux = n_scale + (PACK ? g.tail_dwords : 0);
+    const size_t t = (size_t)(blockIdx.x - g.payload_blocks) * 256 + threadIdx.x;
+    if (t >= aux * g.B) return;
+    const size_t img = t / aux, a = t - img * aux;
+    char* rec = state + img * g.rec_bytes;
+    if (a < n_scale) {
+        const size_t sec = a / g.scale_dwords, r = a - sec * g.scale_dwords;
+        unsigned int* sp = reinterpret_cast<unsigned int*>(rec + sec * g.sec_bytes + (size_t)g.rows * g.cpr * 16) + r;
+        if (r < (size_t)g.rows) {
+            unsigned int* bp = reinterpret_cast<unsigned int*>(buf + sec * g.block_bytes + kv16_scale_off(img * g.rows + r));
+            if (PACK) *sp = *bp; else *bp = *sp;
+        } else if (PACK) {
+            *sp = 0u;
+        }
+    } else if (PACK) {
+        reinterpret_cast<unsigned int*>(rec + (size_t)g.sections * g.sec_bytes)[a - n_scale] = 0u;
+    }
+}
+__global__ __launch_bounds__(256) void image_state_pack_kernel(ImageStateGeom g, const char* __restrict__ buf, char* __restrict__ state) {
+    image_state_move<true>(g, const_cast<char*>(buf), state);
+}
+__global__ __launch_bounds__(256) void image_state_unpack_kernel(ImageStateGeom g, char* __restrict__ buf, const char* __restrict__ state) {
+    image_state_move<false>(g, buf, const_cast<char*>(state));
+}
+static int image_state_geom(const ImageStateLayout& L, int B, const void* buf, const void* state, const char* who, ImageStateGeom& g,
+                            bool pack, unsigned& blocks) {
+    if (!buf || !state) { cap_set_error("%s: null buffer", who); return -1; }
+    if ((((uintptr_t)buf | (uintptr_t)state) & 15) != 0) { cap_set_error("%s: the cache and the state must be 16-byte aligned", who); return -1; }
+    if (L.sections < 1 || L.rows < 1 || B < 1 || (L.row_bytes != 16 && L.row_bytes != 128 && L.row_bytes != 256) || (L.kv16 && L.row_bytes != 128)) {
+        cap_set_error("%s: %d sections of %d rows of %d bytes (KV16 %d) for %d images", who, L.sections, L.rows, L.row_bytes, L.kv16, B);
+        return -1;
+    }
+    g.sections = L.sections; g.rows = L.rows; g.cpr = L.row_bytes / 16; g.kv16 = L.kv16 ? 1 : 0; g.B = B;
+    g.scale_dwords = L.kv16 ? (L.rows + 3) / 4 * 4 : 0;
+    g.rec_bytes = L.record_bytes(); g.sec_bytes = L.section_bytes(); g.block_bytes = L.block_bytes((size_t)B);
+    g.tail_dwords = (int)((g.rec_bytes - (size_t)L.sections * g.sec_bytes) / 4);
+    const size_t rows = (size_t)B * L.sections * L.rows, per_block = (size_t)(256 / g.cpr) * IMAGE_STATE_ROWS_PER_LANE;
+    const size_t pb = (rows + per_block - 1) / per_block;
+    const size_t aux = ((size_t)L.sections * g.scale_dwords + (pack ? g.tail_dwords : 0)) * B, ab = (aux + 255) / 256;
+    if (pb + ab > 0x7fffffffu) { cap_set_error("%s: %zu rows of %d images exceed one launch", who, rows, B); return -1; }
+    g.payload_blocks = (unsigned)pb;
+    blocks = (unsigned)(pb + ab);
+    return 0;
+}
+int launch_image_state_pack(const ImageStateLayout& L, int B, const void* buffer, void* state, hipStream_t s) {
+    ImageStateGeom g;
+    unsigned blocks;
+    if (image_state_geom(L, B, buffer, state, "image_state_pack", g, true, blocks) != 0) return -1;
+    hipLaunchKernelGGL(image_state_pack_kernel, dim3(blocks), dim3(256), 0, s, g, (const char*)buffer, (char*)state);
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_image_state_unpack(const ImageStateLayout& L, int B, void* buffer, const void* state, hipStream_t s) {
+    ImageStateGeom g;
+    unsigned blocks;
+    if (image_state_geom(L, B, buffer, state, "image_state_unpack", g, false, blocks) != 0) return -1;
+    hipLaunchKernelGGL(image_state_unpack_kernel, dim3(blocks), dim3(256), 0, s, g, (char*)buffer, (const char*)state);
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 CAP_DEFINE_G8_CLAMP_READER(cap_g8_clamped_elementwise)

@@ -87,6 +87,21 @@ int launch_compact_rows(const int* finished, int R, int* live, int* n_live, hipS
 int launch_fill_i32(int* p, int v, size_t n, hipStream_t s);
 int launch_fill_f32(float* p, float v, size_t n, hipStream_t s);
 int launch_copy_f32(const float* src, float* dst, size_t n, hipStream_t s);
+// Image state (include/captioner_hip.h, "image state"): per-image records <-> the arena's buffer packed for a call's B images.
+// The buffer is `sections` blocks, each holding the rows of the B images one after the other (row index = image * rows + row): the
+// cross K/V cache ([slot][k|v] = 2 * slots sections of heads * kv_tokens head rows; KV16: blocks of kv16_block_bytes) or BLIP-2's
+// language projection (one section of 16-byte rows).  A record is the image's sections one after the other, each its row
+// payloads then (KV16) the rows' fp32 scales padded to 16 bytes, closed with zeros to a multiple of 256 bytes.
+struct ImageStateLayout {
+    int sections, rows, row_bytes, kv16;      // row_bytes: 256 / 128 (fp32 / bf16 and KV16 head rows), 16 (projection rows)
+    size_t section_bytes() const { return (size_t)rows * row_bytes + (kv16 ? ((size_t)rows * 4 + 15) / 16 * 16 : 0); }
+    size_t record_bytes() const { return ((size_t)sections * section_bytes() + 255) / 256 * 256; }
+    size_t block_bytes(size_t B) const { return kv16 ? kv16_block_bytes(B * rows) : B * rows * (size_t)row_bytes; }
+};
+// pack: buffer -> B records at `state` (padding written as zeros); unpack: B records -> the rows of the B images in the buffer,
+// nothing else of it.  Both pointers 16-byte aligned.
+int launch_image_state_pack(const ImageStateLayout& L, int B, const void* buffer, void* state, hipStream_t s);
+int launch_image_state_unpack(const ImageStateLayout& L, int B, void* buffer, const void* state, hipStream_t s);
 
 // max |src[i]| as the bit pattern of a non-negative float, atomically max-ed into *out_bits (caller zeroes it)
 int launch_absmax_f32(const float* src, size_t n, unsigned int* out_bits, hipStream_t s);

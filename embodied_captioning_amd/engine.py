@@ -200,6 +200,36 @@ def validate_score_ids(ids, lens, arch, n_images: int, captions_per_image: int =
     return t.to(torch.int32).contiguous(), ln.to(torch.int32).contiguous()
 
 
+def is_image_state(x) -> bool:
+    """What `generate` / `score` read as an image state (`CaptionerEngine.image_state`): a uint8 tensor of two dimensions.  uint8
+    frames have four."""
+    return isinstance(x, torch.Tensor) and x.dtype == torch.uint8 and x.dim() == 2
+
+
+def validate_image_state(state: torch.Tensor, image_state_bytes: int) -> None:
+    """The host check of a state handed to `generate` / `score`: its row size must be the engine's `image_state_bytes`.  Needs no
+    GPU.  A size is all that can be checked: see `CaptionerEngine.image_state`."""
+    if not is_image_state(state):
+        raise ValueError(f"an image state is a uint8 [B, image_state_bytes] tensor, got {tuple(state.shape)} {state.dtype}")
+    if int(state.shape[1]) != int(image_state_bytes):
+        raise ValueError(f"image state rows of {int(state.shape[1])} bytes do not fit this engine, whose image_state_bytes is "
+                         f"{int(image_state_bytes)}: a state belongs to engines of the same architecture, compute type and "
+                         f"cross-cache kind as the one that made it")
+    if int(state.shape[0]) < 1:
+        raise ValueError("an image state needs at least one row")
+
+
+def images_or_state(images, image_state, who: str):
+    """The wrappers' `images` / `image_state=` pair -> the one that was given (exactly one must be)."""
+    if (images is None) == (image_state is None):
+        raise ValueError(f"{who}: give images or image_state=, one of the two")
+    if image_state is None:
+        return images
+    if not is_image_state(image_state):
+        raise ValueError(f"{who}: image_state is the uint8 [N, image_state_bytes] tensor `image_state(images)` returns")
+    return image_state
+
+
 class CaptionerEngine:
     """One handle = one model replica on one GPU, bound to torch's current stream of `device` at each call."""
 
@@ -418,10 +448,45 @@ class CaptionerEngine:
         return {"matched": matched, "unknown": unknown}
 
     # ------------------------------------------------------------------------------------------ forward
+    @property
+    def image_state_bytes(self) -> int:
+        """Bytes of one image's state on this engine (cap_image_state_bytes)."""
+        n = int(self.lib.cap_image_state_bytes(self._h))
+        if n <= 0:
+            raise N.CaptionerHipError(f"cap_image_state_bytes: {N.last_error()}")
+        return n
+
+    def image_state(self, pixels: torch.Tensor) -> torch.Tensor:
+        """The image side alone: frames as `generate` takes them -> a plain uint8 [B, image_state_bytes] device tensor, one row per
+        image, holding what the decode side reads from the image side (BLIP / CoCa: the image's cross-attention K/V rows in this
+        engine's cache kind; BLIP-2: its language-projection rows).  `generate` and `score` take such a tensor where they take
+        pixels and then skip the image side; the results are the bits of the calls from the pixels.  It is a tensor and nothing
+        more: subsets, reorderings and repeats of images are indexing (`state[[4, 0, 0, 2]]`), batches are `torch.cat`, and a state
+        made on one engine decodes on any engine of the same architecture, compute type and cross-cache kind that has the same
+        weights (a pool's engines do).  Only the row size is checked on the way back in: a state made with OTHER WEIGHTS, or by
+        an engine of another image size whose records happen to have this size, is the caller's to keep apart - it decodes without
+        an error to captions of that other model's image.  More than max_batch frames go in calls of max_batch."""
+        pixels, fmt = self._pixels(pixels)
+        if fmt == N.CAP_PIX_IMAGE_STATE:
+            raise ValueError("image_state takes frames, got an image state")
+        B, nbytes = int(pixels.shape[0]), self.image_state_bytes
+        out = torch.empty((B, nbytes), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            for b0 in range(0, B, self.max_batch):
+                nb = min(self.max_batch, B - b0)
+                N.check(self.lib.cap_encode_image_state(self._h, C.c_void_p(pixels[b0:b0 + nb].data_ptr()), fmt, nb,
+                                                        C.c_void_p(out[b0:b0 + nb].data_ptr()), C.c_void_p(_stream_ptr(self.device))),
+                        "cap_encode_image_state")
+        return out
+
     def _pixels(self, pixels: torch.Tensor):
         if pixels.device != self.device:
             pixels = pixels.to(self.device, non_blocking=True)
         a = self.arch
+        # two dimensions: a state, not uint8 [B, S, S, 3] frames (the scorer engines that borrow this method take frames only)
+        if is_image_state(pixels) and isinstance(self, CaptionerEngine):
+            validate_image_state(pixels, self.image_state_bytes)
+            return pixels.contiguous(), N.CAP_PIX_IMAGE_STATE
         if pixels.dtype == torch.uint8:
             if pixels.dim() != 4 or pixels.shape[1:] != (a.image_size, a.image_size, 3):
                 raise ValueError(f"uint8 frames must be [B,{a.image_size},{a.image_size},3], got {tuple(pixels.shape)}")

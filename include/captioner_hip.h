@@ -78,7 +78,8 @@ enum { CAP_ACT_QUICK_GELU = 0, CAP_ACT_GELU = 1 };
  *                  on every golden fixture; the default of the plugin and of bench.py.  Every captioner architecture (BLIP, BLIP-2, CoCa); not the sentence encoder.  The mode has a
  *                  finite range - see cap_g8_saturations. */
 enum { CAP_F32 = 0, CAP_BF16 = 1, CAP_F32_SPLIT = 2 };
-enum { CAP_PIX_F32_NCHW = 0, CAP_PIX_U8_NHWC = 1 }; /* normalised fp32 [B,3,H,W] | raw RGB uint8 [B,H,W,3] */
+/* normalised fp32 [B,3,H,W] | raw RGB uint8 [B,H,W,3] | B image-state records (cap_encode_image_state; the decoding calls only) */
+enum { CAP_PIX_F32_NCHW = 0, CAP_PIX_U8_NHWC = 1, CAP_PIX_IMAGE_STATE = 2 };
 
 typedef struct CapConfig {
     int32_t struct_size;          /* sizeof(CapConfig), for ABI checking */
@@ -222,13 +223,46 @@ int cap_crop_resize_u8_frames(const uint8_t* packed, const int64_t* frames, int 
 /* Image tower.  pixels: B frames in `pixel_fmt`; out_embeds: fp32 [B, tokens, v_hidden] (device). */
 int cap_encode(CapHandle h, const void* pixels, int pixel_fmt, int B, float* out_embeds, void* stream);
 
+/* ---- image state: encode once, then generate, prompt and score from it ----
+ * Everything the decode side of a handle reads from the image side, as one opaque record per image in CALLER-owned device memory:
+ * nothing stays resident in the handle, and no result depends on what the arena held before a call.  cap_encode_image_state runs
+ * the image side and packs the records; cap_generate_request, every cap_generate* convenience and cap_score_captions take them as
+ * pixel_fmt = CAP_PIX_IMAGE_STATE (`pixels` = B contiguous records) and unpack them into the arena for the call's B INSTEAD of
+ * running the image side.  Both are re-layouts of bytes the decoder reads anyway: a call from a state gives the bits of the call
+ * from the pixels (tests/test_image_state_gpu.py), whatever the batch, order or repetition the records are given in.
+ * A record belongs to handles of the same architecture and geometry, compute type and cross-cache kind (cap_image_state_bytes
+ * differs for most other pairs, and the decoding calls cannot tell more than the caller's pointer); a record made with other
+ * weights decodes to that other model's image.
+ *
+ * Record layout.  CAP_ARCH_BLIP / CAP_ARCH_COCA: the image's rows of the cross-attention K/V cache [slot][k|v][image][head][kv_tokens]
+ * [64] (slots = t_layers, CoCa: mm_layers; kv_tokens = image tokens, CoCa: pool_queries - the pooled-token row travels with the rest
+ * and is not attended, as ever), in the handle's cache kind (cap_cross_cache_kind):
+ *     for slot in 0 .. slots - 1:  for part in (k, v):                                        -- one SECTION each
+ *         rows = t_heads * kv_tokens row payloads in [head][token] order, row_bytes each:
+ *             kind 0: 64 fp32 = 256 bytes,  kind 1: 64 bf16 = 128 bytes,  kind 2 (KV16): 64 int16 = 128 bytes
+ *         kind 2 only: the same rows' fp32 scales, rows * 4 bytes, zero-padded to a multiple of 16 bytes
+ *     zero padding to a multiple of 256 bytes
+ *   section_bytes = rows * row_bytes + (kind 2 ? round_up(rows * 4, 16) : 0);  record_bytes = round_up(2 * slots * section_bytes, 256).
+ *   (A KV16 block of the cache groups 32 head rows ACROSS images and the cache is packed for the call's B, so the same record lands
+ *   in different places for different B: that is the unpacking's work.)
+ * CAP_ARCH_BLIP2: the image's num_query_tokens rows of the language projection's output, fp32 [num_query_tokens][t_hidden], zero-padded
+ * to a multiple of 256 bytes.  The prompt pass stays on the decoding side (it depends on the beam count).
+ *
+ * cap_image_state_bytes: bytes of one record on this handle; 0 (and an error) for a null handle or one that is not BLIP, CoCa or BLIP-2.
+ * cap_encode_image_state: pixels = B frames in pixel_fmt (CAP_PIX_F32_NCHW | CAP_PIX_U8_NHWC), B <= max_batch; out_state = B records
+ * ([B, cap_image_state_bytes] bytes, device, 16-byte aligned), padding included in what is written.  Refused before anything is
+ * launched: another kind of handle, B beyond max_batch, a null or misaligned out_state, CAP_PIX_IMAGE_STATE as the input.  The decoding
+ * calls refuse a null or misaligned state the same way; cap_encode and the scorer handles' image calls refuse CAP_PIX_IMAGE_STATE by name. */
+size_t cap_image_state_bytes(CapHandle h);
+int cap_encode_image_state(CapHandle h, const void* pixels, int pixel_fmt, int B, void* out_state, void* stream);
+
 /* Encoder + autoregressive decode: ONE request, everything a generate call can ask for.  Zero / NULL = absent.  Every rule below is
  * checked by cap_generate_request before anything is launched, in this order: handle and capacity (B <= max_batch, num_beams <=
  * max_beams, max_len <= cfg.max_len), buffers, what the handle's architecture takes, shapes.  A refused request leaves the stream,
  * the output buffers and the handle's cap_last_* values untouched.  Nothing is allocated or synchronised (cap_set_early_exit aside). */
 typedef struct CapGenerateArgs {
-    const void* pixels;        /* B frames in pixel_fmt (device); required */
-    int32_t pixel_fmt;         /* CAP_PIX_F32_NCHW | CAP_PIX_U8_NHWC */
+    const void* pixels;        /* B frames in pixel_fmt (device), or B image-state records (16-byte aligned); required */
+    int32_t pixel_fmt;         /* CAP_PIX_F32_NCHW | CAP_PIX_U8_NHWC | CAP_PIX_IMAGE_STATE (the image side does not run: "image state" above) */
     int32_t B;
     int32_t num_beams;         /* 1: greedy (HF `_sample` with do_sample=False; CoCa: the reference's top-k(1) loop, coca.py:29); > 1: HF v5 beam
                                   search (CoCa: its `_generate_beamsearch`, coca_model.py:335-482).  CAP_ARCH_BLIP2: the same search behind the
@@ -307,7 +341,8 @@ int cap_last_prefill_passes(CapHandle h);
 /* Teacher-forced scoring of GIVEN captions (CAP_ARCH_BLIP, CAP_ARCH_BLIP2): what HF `BlipForConditionalGeneration(pixel_values, input_ids=...)` returns
  * as `logits`, reduced on the device to the numbers a caller wants from them.  Nothing vocabulary-wide leaves the library and no
  * [N, L, vocab] buffer exists: the head runs over as many rows as the handle's logits buffer holds and each slice is reduced at once.
- *   pixels   B frames in pixel_fmt (device), B <= max_batch; the image side runs once per image
+ *   pixels   B frames in pixel_fmt (device), B <= max_batch; the image side runs once per image - or B image-state records
+ *            (CAP_PIX_IMAGE_STATE): it does not run at all
  *   ids      int32 [N, L] (device), N = B * captions_per_image; caption n belongs to image n / captions_per_image; column 0 = BOS
  *   lens     int32 [N] (device): tokens of caption n incl. BOS (and EOS / [SEP] if the end is to be scored), 2 <= lens[n] <= L, or 0 for
  *            an absent slot (captions_per_image > 1).  Columns from lens[n] on are padding: any id; they influence nothing returned
@@ -607,6 +642,13 @@ int cap_op_small_cross(int dtype, const CapSmallCross* args, void* stream);
    (x ~ q * scale, scale = max|x| / 32767 over the row), rows in groups of 32 = [32 x 128 bytes][32 scales] = 4224 bytes; dst holds
    (n_rows + 31) / 32 groups.  The cross-K/V GEMM's epilogue writes this layout; the op exists for the kernel tests. */
 int cap_op_pack_kv16(const float* src, void* dst, size_t n_rows, void* stream);
+/* The two copies behind the image state alone ("image state" above), between a cross K/V cache packed for B images - kind 0 fp32 /
+   1 bf16 / 2 KV16, [slot][k | v][image][head][token][64], every (slot, k | v) block as cap_op_gemm_crosskv lays it out - and B records
+   at `state` (both device, 16-byte aligned).  pack writes the records whole, zero padding included; unpack writes the head rows (and
+   KV16 scales) of the B images and nothing else of the cache: the ragged tail of the last KV16 group and whatever lies behind the
+   call's B stay as they were. */
+int cap_op_image_state_pack(int kind, int slots, int heads, int tokens, int B, const void* cache, void* state, void* stream);
+int cap_op_image_state_unpack(int kind, int slots, int heads, int tokens, int B, void* cache, const void* state, void* stream);
 /* The cross-K/V GEMM as the image side runs it (replaces the per-layer key / value Linear calls of HF:modeling_blip_text.py:161-175):
    A [n_img * tokens, K] x W [layers * 2 * heads * 64, K]^T + bias -> cache [layer][k | v][image][head][token][64]; kv16 = 1 (CAP_F32_SPLIT
    only): every (layer, k | v) block is a KV16 block of (n_img * heads * tokens + 31) / 32 groups, else fp32 / bf16 rows. */
