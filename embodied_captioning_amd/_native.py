@@ -118,6 +118,13 @@ _SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "cap_set_early_exit": (C.c_int, [C.c_void_p, C.c_int]),
     "cap_last_decode_steps": (C.c_int, [C.c_void_p]),
+    "cap_set_bad_words": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "cap_bad_words": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cap_op_ban_words": (C.c_int, [C.c_int]),
+    "cap_op_select_banned": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "cap_op_beam_step_banned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "cap_set_decode_path": (C.c_int, [C.c_void_p, C.c_int]),
     "cap_last_decode_path": (C.c_int, [C.c_void_p]),
     "cap_set_row_compaction": (C.c_int, [C.c_void_p, C.c_int]),

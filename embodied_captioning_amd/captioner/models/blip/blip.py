@@ -99,6 +99,10 @@ class BLIP(CaptioningPredictor):
             from ....engine import prompt_token_limit, validate_prompt_ids
             validate_prompt_ids(self._prompt_row(self.prompt_ids), self.arch, 1, self.max_length, self.num_beams, None,
                                 prompt_token_limit(self.batch_size, self.num_beams, self.max_prompt))
+        # captioner.bad_words_ids / captioner.bad_words: HF generate(bad_words_ids=) for every caption (engine.set_bad_words);
+        # validated here, before an engine exists
+        from ...bad_words import resolve_bad_words
+        self.bad_words_ids = resolve_bad_words(cfg, self.tokenizer, self.arch)
         if getattr(cfg, "checkpoint_name", None):
             over = load_state_dict_file(cfg.checkpoint_name)
             for dst, src in BLIP_TIED.items():
@@ -141,6 +145,10 @@ class BLIP(CaptioningPredictor):
             self.pool.set_early_exit(poll)
         elif cr:
             logger.warning("captioner.coalesce_rows is the engine pool's dynamic batching: it needs captioner.streams > 1 - ignored")
+        if self.bad_words_ids:
+            self.engine.set_bad_words(self.bad_words_ids)
+            if self.pool is not None:
+                self.pool.set_bad_words(self.bad_words_ids)
 
     @staticmethod
     def _length_penalty(cfg) -> float:

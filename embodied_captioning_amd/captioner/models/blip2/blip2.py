@@ -137,6 +137,9 @@ class BLIP2(BLIP):
                 self.tokenizer = AutoTokenizer.from_pretrained(model_dir)
             except Exception as e:  # noqa: BLE001
                 logger.warning("no tokenizer under %s (%s): captions are returned as space-separated token ids", model_dir, e)
+        # captioner.bad_words_ids / captioner.bad_words (as for BLIP): validated before an engine exists
+        from ...bad_words import resolve_bad_words
+        self.bad_words_ids = resolve_bad_words(cfg, self.tokenizer, self.arch)
         ck = getattr(cfg, "checkpoint_name", None)
         self.adapter_report = None
         if ck:
@@ -184,6 +187,10 @@ class BLIP2(BLIP):
             self.pool.set_early_exit(4 if poll is None else int(poll))
         elif cr:
             logger.warning("captioner.coalesce_rows is the engine pool's dynamic batching: it needs captioner.streams > 1 - ignored")
+        if self.bad_words_ids:
+            self.engine.set_bad_words(self.bad_words_ids)
+            if self.pool is not None:
+                self.pool.set_bad_words(self.bad_words_ids)
 
     def decode(self, ids: Sequence[int]) -> str:
         if not hasattr(self.arch, "num_query_tokens"):

@@ -12,7 +12,8 @@ BLIP-2).  dtype: "f32s" (default for BLIP: fp32-grade split-fp16 GEMMs, token-id
 group), tokenizer_dir (directory holding the CLIP BPE vocabulary - vocab.json / merges.txt / bpe_simple_vocab_16e6.txt.gz -
 when it is not next to the checkpoint and open_clip is not installed); generation_type / top_k / top_p / temperature /
 repetition_penalty (the reference model's other `generate` options, coca_model.py:205-224): accepted at their neutral values
-("top_k" with top_k=1 = greedy, "beam_search"), rejected by name otherwise - sampling is not implemented."""
+("top_k" with top_k=1 = greedy, "beam_search"), rejected by name otherwise - sampling is not implemented.  bad_words_ids / bad_words / bad_words_mode (BLIP, BLIP-2): banned token
+sequences / words of the decode loops, HF's `generate(bad_words_ids=)`."""
 
 
 class Configuration:
@@ -28,7 +29,7 @@ class CaptionerField:
                  generation_type=None, top_k=None, top_p=None, temperature=None, repetition_penalty=None,
                  load_in_8bit=None, load_in_4bit=None, torch_dtype=None, cross_cache=None, strict_range=False,
                  coalesce_rows=None, device_resize=None, prompt=None, prompt_ids=None, max_prompt=None, length_penalty=None,
-                 max_score_rows=None):
+                 max_score_rows=None, bad_words_ids=None, bad_words=None, bad_words_mode=None):
         self.arch_name = arch_name
         self.model_name = model_name
         self.checkpoint_name = checkpoint_name
@@ -77,3 +78,9 @@ class CaptionerField:
         # BLIP: scoring capacity of the arena in decoder rows (`score_captions`: captions x (tokens - 1) per pass); None / 0 = none
         # reserved - captions of up to batch_size x num_beams + 1 tokens are scored in passes of what the decode rows hold
         self.max_score_rows = max_score_rows
+        # BLIP / BLIP-2: HF `generate(bad_words_ids=)` on the device (captioner/bad_words.py): bad_words_ids = a list of token-id
+        # lists; bad_words = a list of words, or "reference" (= distributed.BANNED_WORDS), tokenised with the checkpoint's tokenizer
+        # (bad_words_mode: "word", the default, or "substring").  CoCa refuses the keys by name.
+        self.bad_words_ids = bad_words_ids
+        self.bad_words = bad_words
+        self.bad_words_mode = bad_words_mode

@@ -14,6 +14,7 @@
 //   beam_merge_kernel  one 64-thread block per item: merge K*2K candidates, update running beams / finished pool /
 //                      ancestry (ranking sorts in LDS); the global "loop still running" flag is an atomic OR.
 #include "ops.h"
+#include "ban.h"
 
 namespace {
 
@@ -73,11 +74,16 @@ __global__ void beam_init_kernel(char* st, BeamLayout lo, int B, int K, int L, i
 __device__ __forceinline__ bool after(float v, int i, float pv, int pi) { return v < pv || (v == pv && i > pi); }
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
-__global__ __launch_bounds__(256) void beam_rows_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
-                                                        int ld, int V, int K, int par, int raw, int eos_mask) {
+// BAN (the *_banned kernels below; ops.h, BanSet): the block first builds the row's ban bitmap `bm` (LDS, ban_words(V) words) from the
+// row's LOGICAL history run_seq[par][row][0 .. cur_len) - the beam's tokens after every re-ordering, not what the physical row wrote -
+// and a banned candidate's value is -inf.  The statistics passes never look at it: HF takes the log-softmax of the raw row, then bans.
+template <bool BAN>
+__device__ __forceinline__ void beam_rows_body(char* st, BeamLayout lo, const float* __restrict__ logits, int ld, int V, int K, int par,
+                                               int raw, int eos_mask, unsigned* bm, BanSet ban, int L, int cur_len) {
     if (*(const int*)(st + lo.active) == 0) return;
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* x = logits + (size_t)row * ld;
+    if (BAN) ban_bitmap_fill(bm, V, ban, (const int*)(st + lo.run_seq[par]) + (size_t)row * L, cur_len, tid);
     __shared__ float redf[8];
     __shared__ int redi[8];
     __shared__ float bc[2];
@@ -105,6 +111,7 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(char* st, BeamLayout lo,
         for (int i = tid; i < V; i += 256) {
             float v = raw ? x[i] + run : ((x[i] - m) - lsum) + run;
             if (i == eos_mask) v = -INFINITY;
+            if (BAN && ban_bit(bm, i)) v = -INFINITY;
             if (after(v, i, pv, pi) && better(v, i, bv, bi)) { bv = v; bi = i; }
         }
 #pragma unroll
@@ -125,6 +132,17 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(char* st, BeamLayout lo,
     }
 }
 
+__global__ __launch_bounds__(256) void beam_rows_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
+                                                        int ld, int V, int K, int par, int raw, int eos_mask) {
+    beam_rows_body<false>(st, lo, logits, ld, V, K, par, raw, eos_mask, nullptr, BanSet(), 0, 0);
+}
+__global__ __launch_bounds__(256) void beam_rows_banned_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
+                                                               int ld, int V, int K, int par, int raw, int eos_mask, BanSet ban,
+                                                               int L, int cur_len) {
+    extern __shared__ unsigned ban_bm[];
+    beam_rows_body<true>(st, lo, logits, ld, V, K, par, raw, eos_mask, ban_bm, ban, L, cur_len);
+}
+
 // Single-pass variant of beam_rows_kernel: the row is read from global memory once (16-byte loads) into LDS; max, sum-exp
 // and the candidate scan run over the LDS copy; each thread keeps the CT best of ITS elements in a register list
 // (unrolled insertion, static indices), and the block then merges the 256 sorted lists by 2K rounds of block arg-max.
@@ -133,19 +151,22 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(char* st, BeamLayout lo,
 // STAGE = false: vocabularies whose row does not fit in LDS next to the candidate lists (CoCa: 49408 x 4 B = 193 KiB): the
 // same single-scan candidate selection reading the row from global memory (twice more for the log-softmax statistics; not at
 // all for raw-logit scores) - the 2K-pass fallback kernel took 874 us per step at 128 x 5 rows there.
-template <int CT, bool STAGE = true>
-__global__ __launch_bounds__(256) void beam_rows_lds_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
-                                                            int ld, int V, int K, int par, int raw, int eos_mask) {
+// BAN: as beam_rows_body - the bitmap sits behind the candidate lists in the dynamic LDS.
+template <int CT, bool STAGE, bool BAN>
+__device__ __forceinline__ void beam_rows_lds_body(char* st, BeamLayout lo, const float* __restrict__ logits, int ld, int V, int K,
+                                                   int par, int raw, int eos_mask, BanSet ban, int L, int cur_len) {
     if (*(const int*)(st + lo.active) == 0) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int V4 = (V + 3) >> 2, C = 2 * K;
     float* xs = (float*)smem;                                  // STAGE: [V4 * 4], tail padded with -inf
     float* lv = xs + (STAGE ? (size_t)V4 * 4 : 0);             // [C][256] candidate values, c-major
     int* li = (int*)(lv + (size_t)C * 256);                    // [C][256] candidate indices
+    const unsigned* bm = (const unsigned*)(li + (size_t)C * 256);   // BAN: [ban_words(V)]
     __shared__ float redf[4];
     __shared__ int redi[4];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* x = logits + (size_t)row * ld;
+    if (BAN) ban_bitmap_fill((unsigned*)bm, V, ban, (const int*)(st + lo.run_seq[par]) + (size_t)row * L, cur_len, tid);
     auto ldg = [&](int j) {                                     // 4 logits of the row, -inf beyond V
         float4 v;
         if (4 * j + 3 < V) v = *(const float4*)(x + 4 * j);
@@ -188,6 +209,7 @@ __global__ __launch_bounds__(256) void beam_rows_lds_kernel(char* st, BeamLayout
     int* ci = (int*)(st + lo.cand_idx) + (size_t)row * C;
     auto score = [&](float e, int i) {
         const float v = raw ? e + run : ((e - m) - lsum) + run;
+        if (BAN && i < V && ban_bit(bm, i)) return -INFINITY;
         return i == eos_mask ? -INFINITY : v;
     };
     // streaming from global memory (vocabulary larger than the LDS): 8 loads of 16 bytes per thread are in flight at a time
@@ -288,6 +310,7 @@ __global__ __launch_bounds__(256) void beam_rows_lds_kernel(char* st, BeamLayout
                 const int i = 4 * j + u;
                 float v = raw ? e[u] + run : ((e[u] - m) - lsum) + run;
                 if (i == eos_mask) v = -INFINITY;
+                if (BAN && i < V && ban_bit(bm, i)) v = -INFINITY;
                 if (i < V && better(v, i, tv[CT - 1], ti[CT - 1])) {
                     tv[CT - 1] = v; ti[CT - 1] = i;
 #pragma unroll
@@ -322,6 +345,18 @@ __global__ __launch_bounds__(256) void beam_rows_lds_kernel(char* st, BeamLayout
         if (tid == 0) { cv[c] = fv; ci[c] = fi; }
         __syncthreads();
     }
+}
+
+template <int CT, bool STAGE = true>
+__global__ __launch_bounds__(256) void beam_rows_lds_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
+                                                            int ld, int V, int K, int par, int raw, int eos_mask) {
+    beam_rows_lds_body<CT, STAGE, false>(st, lo, logits, ld, V, K, par, raw, eos_mask, BanSet(), 0, 0);
+}
+template <int CT, bool STAGE>
+__global__ __launch_bounds__(256) void beam_rows_lds_banned_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
+                                                                   int ld, int V, int K, int par, int raw, int eos_mask, BanSet ban,
+                                                                   int L, int cur_len) {
+    beam_rows_lds_body<CT, STAGE, true>(st, lo, logits, ld, V, K, par, raw, eos_mask, ban, L, cur_len);
 }
 
 // One 64-thread block per item.  The three selections of a step (top-2K continuations over the K candidate lists,
@@ -507,6 +542,51 @@ static int launch_beam_rows(void* state, const BeamLayout& lo, const float* logi
     return 0;
 }
 
+// launch_beam_rows under a ban: the same three branches, the bitmap's ban_words(V) words behind each one's dynamic LDS - a row that
+// no longer fits beside it takes the candidate-lists form.
+template <int CT, bool STAGE>
+static int launch_beam_rows_lds_banned(size_t lds, void* state, const BeamLayout& lo, const float* logits, int ld, int V, int B, int K,
+                                       int par, int raw, int eos_mask, const BanSet& ban, int L, int cur_len, hipStream_t s) {
+    if (cap_kernel_setup((const void*)beam_rows_lds_banned_kernel<CT, STAGE>, 148 * 1024, nullptr) != 0) return -1;
+    hipLaunchKernelGGL((beam_rows_lds_banned_kernel<CT, STAGE>), dim3(B * K), dim3(256), lds, s, (char*)state, lo, logits, ld, V, K, par,
+                       raw, eos_mask, ban, L, cur_len);
+    return 0;
+}
+static int launch_beam_rows_banned(void* state, const BeamLayout& lo, const float* logits, int ld, int V, int B, int K, int par, int raw,
+                                   int eos_mask, const BanSet& ban, int L, int cur_len, hipStream_t s) {
+    const size_t bmb = (size_t)ban_words(V) * 4, lists = (size_t)2 * K * 256 * 8;
+    const size_t lds = (size_t)((V + 3) / 4) * 16 + lists + bmb;
+    const bool fast = (ld & 3) == 0 && V > 2 * K;
+#define BANNED_ROWS(STAGE, bytes)                                                                                                       \
+    (2 * K <= 4   ? launch_beam_rows_lds_banned<4, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, raw, eos_mask, ban, L, cur_len, s)  \
+     : 2 * K <= 8 ? launch_beam_rows_lds_banned<8, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, raw, eos_mask, ban, L, cur_len, s)  \
+                  : launch_beam_rows_lds_banned<16, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, raw, eos_mask, ban, L, cur_len, s))
+    if (fast && lds <= 148 * 1024) { if (BANNED_ROWS(true, lds) != 0) return -1; }
+    else if (fast) { if (BANNED_ROWS(false, lists + bmb) != 0) return -1; }
+    else
+        hipLaunchKernelGGL(beam_rows_banned_kernel, dim3(B * K), dim3(256), bmb, s, (char*)state, lo, logits, ld, V, K, par, raw, eos_mask,
+                           ban, L, cur_len);
+#undef BANNED_ROWS
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static int launch_beam_merge(void* state, const BeamLayout& lo, int V, int B, int K, int max_len, int cur_len, int eos,
+                             float length_penalty, int* anc, int anc_ld, int raw, hipStream_t s);
+
+int launch_beam_step_banned(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
+                            float length_penalty, int* anc, int anc_ld, hipStream_t s, int mode, int min_len, BanSet ban) {
+    if (!ban.bits || (ban.n_multi && !ban.multi) || ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI) {
+        cap_set_error("beam_step (banned): no bitmap, or %d multi-token sequences (at most %d)", ban.n_multi, BAN_MAX_MULTI);
+        return -1;
+    }
+    const BeamLayout lo = beam_layout(B, K, max_len);
+    const int raw = mode == BEAM_LEGACY_RAW ? 1 : 0;
+    const int eos_mask = (raw && cur_len < min_len) ? eos : -1;
+    if (launch_beam_rows_banned(state, lo, logits, ld, V, B, K, cur_len & 1, raw, eos_mask, ban, max_len, cur_len, s) != 0) return -1;
+    return launch_beam_merge(state, lo, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, raw, s);
+}
+
 int launch_beam_step(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len,
                      int eos, float length_penalty, int* anc, int anc_ld, hipStream_t s, int mode, int min_len) {
     const BeamLayout lo = beam_layout(B, K, max_len);
@@ -514,6 +594,13 @@ int launch_beam_step(void* state, const float* logits, int ld, int V, int B, int
     const int raw = mode == BEAM_LEGACY_RAW ? 1 : 0;
     const int eos_mask = (raw && cur_len < min_len) ? eos : -1;       // MinLengthLogitsProcessor(min_len, eos)
     if (launch_beam_rows(state, lo, logits, ld, V, B, K, par, raw, eos_mask, s) != 0) return -1;
+    return launch_beam_merge(state, lo, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, raw, s);
+}
+
+// The step's second half: merge the rows' candidate lists into the next running beams / finished pool / ancestry.
+static int launch_beam_merge(void* state, const BeamLayout& lo, int V, int B, int K, int max_len, int cur_len, int eos,
+                             float length_penalty, int* anc, int anc_ld, int raw, hipStream_t s) {
+    const int par = cur_len & 1;
     // v5: prompt length is 1 ([BOS]); python computes the float power in double, torch divides in fp32.  Legacy scorer: the
     // prompt is not subtracted (generated_len = cur_len + 1 with decoder_prompt_len = 0)
     const int glen = raw ? cur_len + 1 : cur_len + 1 - 1;

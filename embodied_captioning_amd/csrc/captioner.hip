@@ -217,6 +217,13 @@ struct Captioner {
     unsigned int* absmax_dev = nullptr;   // cap_load_weight: max |w| of a tensor bound for a G8 slot (range check)
     // early exit of the decode loop (cap_set_early_exit): poll every `poll` steps through a host-mapped word
     int poll = 0; int* host_flag = nullptr; int* host_flag_dev = nullptr;
+    // banned tokens / sequences (cap_set_bad_words; ops.h, BanSet): device storage of its own, allocated at the first non-empty set
+    // (never part of the arena) and freed with the handle; the host copies are what the uploads read
+    unsigned* ban_bits = nullptr; int* ban_multi = nullptr;
+    int ban_n_single = 0, ban_n_multi = 0;
+    std::vector<unsigned> ban_bits_host; std::vector<int> ban_multi_host;
+    bool banned() const { return ban_n_single > 0 || ban_n_multi > 0; }
+    BanSet ban_set() const { BanSet b; b.bits = ban_bits; b.multi = ban_multi; b.n_multi = ban_n_multi; return b; }
     int last_steps = 0;          // decode steps the last cap_generate ran (cap_last_decode_steps)
     int decode_path = 0;         // cap_set_decode_path: 0 = by row count (<= SMALL_MAX_ROWS rows: the fused small-batch kernels),
                                  // 1 = always the batch kernels, 2 = always the small-batch kernels (an error beyond their row limit)
@@ -775,6 +782,13 @@ int select_greedy_step(Captioner* m, const CapGenerateArgs& a, int R, int step, 
                        hipStream_t s) {
     const CapConfig& c = m->c;
     const bool coca = c.arch == CAP_ARCH_COCA;
+    // a ban in force (cap_set_bad_words): the banned form, over the context HF's processor sees - BLIP's row from its BOS column on;
+    // BLIP-2's BOS and generated tokens: the generated columns and the one before them, which stands for BOS (it holds pad, and
+    // neither id is in any sequence).  validate_generate refused the log-prob / vocabulary outputs and CoCa; with nothing set this is
+    // the launch it has always been.
+    if (m->banned())
+        return launch_greedy_select_banned(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s, 0, 0,
+                                           map, m->ban_set(), c.arch == CAP_ARCH_BLIP2 ? c.num_query_tokens : 0);
     return launch_greedy_select(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s,
                                 coca ? c.min_len : 0, coca ? 1 : 0, map, a.out_logprobs, cols, step, a.out_scored, a.out_vocab, a.acc_ld);
 }
@@ -1665,8 +1679,12 @@ int run_generate(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
             TRY(select_greedy_step(m, a, R, t - t0, Lm - 1, Lm, t, Lm, d.map, s));
             if (compact) TRY(launch_compact_rows(d.finished, R, m->live, m->n_live, s));
         } else {
-            TRY(launch_beam_step(d.beam, d.logits, m->ldl, c.vocab, B, K, Lm, cur_len, c.eos, a.length_penalty, d.anc, Lm, s,
-                                 coca ? BEAM_LEGACY_RAW : BEAM_HF_V5, coca ? c.min_len : 0));
+            if (m->banned())      // (never CoCa: validate_generate)
+                TRY(launch_beam_step_banned(d.beam, d.logits, m->ldl, c.vocab, B, K, Lm, cur_len, c.eos, a.length_penalty, d.anc, Lm, s,
+                                            BEAM_HF_V5, 0, m->ban_set()));
+            else
+                TRY(launch_beam_step(d.beam, d.logits, m->ldl, c.vocab, B, K, Lm, cur_len, c.eos, a.length_penalty, d.anc, Lm, s,
+                                     coca ? BEAM_LEGACY_RAW : BEAM_HF_V5, coca ? c.min_len : 0));
         }
         bool done;
         TRY(poll_all_finished(m, t, Lm - 1, d.finished, R, greedy ? nullptr : beam_active_flag_p(d.beam, B, K, Lm), s, &done));
@@ -1945,7 +1963,11 @@ int run_beams_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
         TRY(copy_step_logits(m, a, R, t, s));
         {
             ProfScope ps(m, s, "beam_step", 0, (double)R * c.vocab * 4);
-            TRY(launch_beam_step(m->beam, m->logits, m->ldl, c.vocab, B, K, Lb, cur_len, c.eos, a.length_penalty, m->anc, Lb, s, BEAM_HF_V5, 0));
+            if (m->banned())
+                TRY(launch_beam_step_banned(m->beam, m->logits, m->ldl, c.vocab, B, K, Lb, cur_len, c.eos, a.length_penalty, m->anc, Lb, s,
+                                            BEAM_HF_V5, 0, m->ban_set()));
+            else
+                TRY(launch_beam_step(m->beam, m->logits, m->ldl, c.vocab, B, K, Lb, cur_len, c.eos, a.length_penalty, m->anc, Lb, s, BEAM_HF_V5, 0));
         }
         if (t + 1 == max_len) break;
         {
@@ -2066,6 +2088,8 @@ static void release_captioner(Captioner* m) {
     if (m->stage) (void)hipFree(m->stage);
     if (m->absmax_dev) (void)hipFree(m->absmax_dev);
     if (m->host_flag) (void)hipHostFree(m->host_flag);
+    if (m->ban_bits) (void)hipFree(m->ban_bits);
+    if (m->ban_multi) (void)hipFree(m->ban_multi);
     delete m;
 }
 
@@ -2267,6 +2291,79 @@ int cap_set_early_exit(CapHandle h, int poll_steps) {
         *m->host_flag = 1;
     }
     m->poll = poll_steps;
+    return 0;
+}
+
+int cap_set_bad_words(CapHandle h, const int32_t* ids, const int32_t* offsets, int n_sequences, void* stream) {
+    Captioner* m = (Captioner*)h;
+    const char* who = "cap_set_bad_words";
+    if (!m) { cap_set_error("%s: null handle", who); return -1; }
+    if (n_sequences < 0 || (n_sequences > 0 && (!ids || !offsets))) {
+        cap_set_error("%s: %d sequences with ids %s and offsets %s (CSR: offsets [n_sequences + 1], ids [offsets[n_sequences]])", who, n_sequences,
+                      ids ? "given" : "null", offsets ? "given" : "null");
+        return -1;
+    }
+    const CapConfig& c = m->c;
+    const int V = c.vocab;
+    std::vector<unsigned> bits((size_t)ban_words(V), 0u);
+    std::vector<int> multi;
+    int n_multi = 0, n_single = 0;
+    if (n_sequences > 0 && offsets[0] != 0) { cap_set_error("%s: offsets[0] = %d (CSR offsets start at 0)", who, offsets[0]); return -1; }
+    for (int q = 0; q < n_sequences; ++q) {
+        const int b = offsets[q], n = offsets[q + 1] - b;
+        if (n < 1) { cap_set_error("%s: sequence %d is empty (offsets %d .. %d)", who, q, b, offsets[q + 1]); return -1; }
+        for (int k = 0; k < n; ++k) {
+            const int id = ids[b + k];
+            if (id < 0 || id >= V) { cap_set_error("%s: sequence %d holds id %d, outside the vocabulary [0, %d)", who, q, id, V); return -1; }
+            if (id == c.bos || id == c.pad) {
+                cap_set_error("%s: sequence %d holds the %s id %d, which is never generated and only ever context", who, q, id == c.bos ? "BOS" : "pad", id);
+                return -1;
+            }
+        }
+        if (n == 1) {
+            if (ids[b] == c.eos) continue;                     // HF drops [eos] silently
+            unsigned& w = bits[(size_t)ids[b] >> 5];
+            const unsigned bit = 1u << (ids[b] & 31);
+            if (!(w & bit)) ++n_single;
+            w |= bit;
+            continue;
+        }
+        if (n > BAN_MAX_LEN) { cap_set_error("%s: sequence %d has %d tokens; a banned sequence has at most %d", who, q, n, BAN_MAX_LEN); return -1; }
+        if (n_multi == BAN_MAX_MULTI) {
+            cap_set_error("%s: more than %d multi-token sequences (single tokens are unbounded)", who, BAN_MAX_MULTI);
+            return -1;
+        }
+        multi.resize((size_t)(n_multi + 1) * BAN_REC, 0);
+        int* rec = multi.data() + (size_t)n_multi * BAN_REC;
+        rec[0] = n;
+        for (int k = 0; k < n; ++k) rec[1 + k] = ids[b + k];
+        ++n_multi;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (n_single == 0 && n_multi == 0) {                       // cleared: the launches are the unbanned ones again
+        m->ban_n_single = 0; m->ban_n_multi = 0;
+        return 0;
+    }
+    if (!m->ban_bits || !m->ban_multi) {                       // each pointer on its own: a failed allocation leaves nothing half-published
+        if (!m->ban_bits) CAP_HIP_CHECK(hipMalloc((void**)&m->ban_bits, (size_t)ban_words(V) * 4));
+        if (!m->ban_multi) CAP_HIP_CHECK(hipMalloc((void**)&m->ban_multi, (size_t)BAN_MAX_MULTI * BAN_REC * 4));
+    } else {
+        CAP_HIP_CHECK(hipStreamSynchronize(s));                // the host copies a previous upload may still be reading are replaced below
+    }
+    m->ban_bits_host.swap(bits);
+    m->ban_multi_host.swap(multi);
+    CAP_HIP_CHECK(hipMemcpyAsync(m->ban_bits, m->ban_bits_host.data(), m->ban_bits_host.size() * 4, hipMemcpyHostToDevice, s));
+    if (n_multi)
+        CAP_HIP_CHECK(hipMemcpyAsync(m->ban_multi, m->ban_multi_host.data(), m->ban_multi_host.size() * 4, hipMemcpyHostToDevice, s));
+    m->ban_n_single = n_single; m->ban_n_multi = n_multi;
+    return 0;
+}
+
+int cap_bad_words(CapHandle h, int* n_single, int* n_multi) {
+    const Captioner* m = (const Captioner*)h;
+    if (!m) { cap_set_error("cap_bad_words: null handle"); return -1; }
+    if (n_single) *n_single = m->ban_n_single;
+    if (n_multi) *n_multi = m->ban_n_multi;
     return 0;
 }
 
@@ -2596,9 +2693,19 @@ static int validate_generate(Captioner* m, const CapGenerateArgs& a, const char*
     REFUSE_IF(a.prompt_ids && c.arch != CAP_ARCH_BLIP,
               "%s: a text prompt is taken by CAP_ARCH_BLIP handles (this handle's arch is %d: CoCa's `text=` and BLIP-2's prompt are not built)",
               who, c.arch);
+    REFUSE_IF(m->banned() && G && c.arch != CAP_ARCH_COCA,
+              "%s: bad words are set on this handle (cap_set_bad_words) and beam groups do not take them", who);
     REFUSE_IF(G && c.arch != CAP_ARCH_COCA,
               "%s: beam groups are the CoCa loop's (coca_model.py:335-482); HF's group beam search for the other architectures needs a "
               "diversity penalty, which this library does not implement", who);
+    if (m->banned()) {          // cap_set_bad_words: BLIP and BLIP-2, greedy and beams, tokens only
+        REFUSE_IF(c.arch == CAP_ARCH_COCA,
+                  "%s: bad words are set on this handle (cap_set_bad_words) and it is a CoCa captioner: the reference's CoCa.generate has no "
+                  "such option (BLIP and BLIP-2 only); clear the set with n_sequences = 0", who);
+        REFUSE_IF(a.out_logprobs || a.out_scored || a.out_vocab,
+                  "%s: bad words are set on this handle (cap_set_bad_words) and out_logprobs / out_vocab describe the raw logits, which no "
+                  "longer describe the selection: clear the set, or leave these outputs out", who);
+    }
     REFUSE_IF(G < 0 || G > K || (G && K % G != 0), "%s: num_beams (%d) must be a multiple of num_beam_groups (%d) (BeamSearchScorer's own check)",
               who, K, G);
     REFUSE_IF(G && a.out_step_logits, "%s: per-step logits are not recorded by the group beam search", who);
@@ -3147,6 +3254,50 @@ int cap_op_select_vocab(const float* logits, int ld, int V, int R, int t, int ma
     map.live = live; map.n = n_live;
     return launch_greedy_select(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, min_len,
                                 force_eos, map, logprobs, lp_ld, t, scored, vocab_acc, acc_ld);
+}
+// The banned forms alone (tests/test_bad_words_kernels_gpu.py): the set comes as the device arrays the kernels read (ops.h, BanSet).
+int cap_op_ban_words(int V) { return V < 1 ? -1 : ban_words(V); }
+int cap_op_select_banned(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int32_t* finished,
+                         const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths, const uint32_t* ban_bits,
+                         const int32_t* ban_multi, int n_multi, int hist0, void* stream) {
+    if (!logits || !finished || !seq || !lengths || R < 1 || V < 1 || ld < V || ld % 4 != 0 || t < 0 || t + 1 >= max_len ||
+        (live != nullptr) != (n_live != nullptr)) {
+        cap_set_error("cap_op_select_banned: bad arguments");
+        return -1;
+    }
+    if (!ban_bits || n_multi < 0 || n_multi > BAN_MAX_MULTI || (n_multi > 0 && !ban_multi) || hist0 < 0 || hist0 > t + 1) {
+        cap_set_error("cap_op_select_banned: ban_bits is required, n_multi = %d must be in [0, %d] (with ban_multi), hist0 = %d in [0, t + 1 = %d]",
+                      n_multi, BAN_MAX_MULTI, hist0, t + 1);
+        return -1;
+    }
+    RowMap map;
+    map.live = live; map.n = n_live;
+    BanSet ban;
+    ban.bits = ban_bits; ban.multi = ban_multi; ban.n_multi = n_multi;
+    return launch_greedy_select_banned(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, 0, 0, map,
+                                       ban, hist0);
+}
+int cap_op_beam_step_banned(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
+                            float length_penalty, int32_t* anc, int anc_ld, int mode, int min_len, const uint32_t* ban_bits,
+                            const int32_t* ban_multi, int n_multi, void* stream) {
+    const char* f = "cap_op_beam_step_banned";
+    TRY(beam_op_args(f, state, B, K, max_len));
+    if (!logits) { cap_set_error("%s: logits is null", f); return -1; }
+    if (V < 1 || ld < V) { cap_set_error("%s: ld = %d, V = %d (ld >= V >= 1)", f, ld, V); return -1; }
+    if (cur_len - 1 < 0 || cur_len - 1 >= max_len - 1) {
+        cap_set_error("%s: cur_len = %d (step cur_len - 1 must satisfy 0 <= step < max_len - 1 = %d)", f, cur_len, max_len - 1);
+        return -1;
+    }
+    if (anc && anc_ld < 1) { cap_set_error("%s: anc_ld = %d with an ancestry table (anc_ld >= 1)", f, anc_ld); return -1; }
+    if (mode != BEAM_HF_V5 && mode != BEAM_LEGACY_RAW) { cap_set_error("%s: mode = %d (0: HF v5, 1: legacy raw)", f, mode); return -1; }
+    if (!ban_bits || n_multi < 0 || n_multi > BAN_MAX_MULTI || (n_multi > 0 && !ban_multi)) {
+        cap_set_error("%s: ban_bits is required and n_multi = %d must be in [0, %d] (with ban_multi)", f, n_multi, BAN_MAX_MULTI);
+        return -1;
+    }
+    BanSet ban;
+    ban.bits = ban_bits; ban.multi = ban_multi; ban.n_multi = n_multi;
+    return launch_beam_step_banned(state, logits, ld, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, (hipStream_t)stream, mode,
+                                   min_len, ban);
 }
 int cap_op_vocab_group_threshold(const float* acc, int acc_ld, int V, int N, const int32_t* group_rows, int M, const int32_t* group_off,
                                  int G, float th, int K, int32_t* out_ids, float* out_prob, int32_t* out_count, void* stream) {

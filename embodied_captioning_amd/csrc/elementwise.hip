@@ -2,6 +2,7 @@
 // greedy token selection.  One wave (64 lanes) per row for the row-wise ops; 16-byte accesses where the layout allows.
 #include <algorithm>
 #include "ops.h"
+#include "ban.h"
 
 namespace {
 
@@ -380,8 +381,10 @@ __global__ __launch_bounds__(256) void mean_pool_normalize_kernel(const float* _
 // mask_eos): the row's maximum in sv[0] for every thread after the last barrier, its index returned to every thread.
 // A row with no entry above -inf (all -inf, or finite only at a masked EOS) selects index 0, as torch.argmax does; a NaN never
 // compares greater, so it is never selected (ops.h, launch_greedy_select).
+// BAN (the banned form, greedy_select_banned_kernel): bm = the row's ban bitmap in LDS (ban.h), a set bit stands as -inf does.
+template <bool BAN = false>
 __device__ __forceinline__ int greedy_row_argmax(const float* __restrict__ x, int V, int eos, bool mask_eos, int tid,
-                                                  float* sv, int* si) {
+                                                  float* sv, int* si, const unsigned* bm = nullptr) {
     float best = -INFINITY;
     int bi = 0x7fffffff;
     // 16-byte loads, 4 independent chunks in flight per thread; ascending index order inside a thread keeps "first
@@ -403,6 +406,13 @@ __device__ __forceinline__ int greedy_row_argmax(const float* __restrict__ x, in
                 if (eos == i + 2) v[u].z = -INFINITY;
                 if (eos == i + 3) v[u].w = -INFINITY;
             }
+            if (BAN) {               // the chunk's four bits come from one LDS word
+                const unsigned nib = c0 + u * 256 < V4 ? ban_nibble(bm, i) : 0u;
+                if (nib & 1u) v[u].x = -INFINITY;
+                if (nib & 2u) v[u].y = -INFINITY;
+                if (nib & 4u) v[u].z = -INFINITY;
+                if (nib & 8u) v[u].w = -INFINITY;
+            }
             if (v[u].x > best) { best = v[u].x; bi = i; }
             if (v[u].y > best) { best = v[u].y; bi = i + 1; }
             if (v[u].z > best) { best = v[u].z; bi = i + 2; }
@@ -410,7 +420,7 @@ __device__ __forceinline__ int greedy_row_argmax(const float* __restrict__ x, in
         }
     }
     for (int i = (V4 << 2) + tid; i < V; i += 256) {
-        const float v = (mask_eos && i == eos) ? -INFINITY : x[i];
+        const float v = ((mask_eos && i == eos) || (BAN && ban_bit(bm, i))) ? -INFINITY : x[i];
         if (v > best) { best = v; bi = i; }
     }
     sv[tid] = best; si[tid] = bi;
@@ -457,6 +467,26 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const float* __restr
     __shared__ float sv[256];
     __shared__ int si[256];
     const int imax = greedy_row_argmax(logits + (size_t)crow * ld, V, eos, mask_eos, tid, sv, si);
+    if (tid == 0) greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
+}
+
+// Banned form (HF NoBadWordsLogitsProcessor ahead of the arg-max; ops.h, BanSet): the block builds the row's ban bitmap in LDS - the
+// static bitmap, then the multi-token sequences matched against the caption's history seq[row][hist0 .. t] - and the selection above
+// runs with it.  Finished rows, the tie rule, RowMap and force_eos are greedy_select_kernel's, from the same two functions.
+__global__ __launch_bounds__(256) void greedy_select_banned_kernel(const float* __restrict__ logits, int ld, int V,
+                                                                   int* __restrict__ seq, int seq_ld, int t, int max_len,
+                                                                   int eos, int pad, int* __restrict__ finished,
+                                                                   int* __restrict__ out_len, int min_len, int force_eos, RowMap map,
+                                                                   BanSet ban, int hist0) {
+    const int crow = blockIdx.x, tid = threadIdx.x;
+    if (map.n && crow >= *map.n) return;
+    const int row = map.live ? map.live[crow] : crow;
+    const bool mask_eos = min_len > 0 && t + 1 < min_len;
+    extern __shared__ unsigned ban_bm[];                 // ban_words(V) words
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    ban_bitmap_fill(ban_bm, V, ban, seq + (size_t)row * seq_ld + hist0, max(t + 1 - hist0, 0), tid);
+    const int imax = greedy_row_argmax<true>(logits + (size_t)crow * ld, V, eos, mask_eos, tid, sv, si, ban_bm);
     if (tid == 0) greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
 }
 
@@ -987,6 +1017,20 @@ int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_l
         hipLaunchKernelGGL(greedy_select_kernel, dim3(R), dim3(256), 0, s, logits, ld, V, seq, seq_ld, t, max_len, eos, pad,
                            finished, out_len, min_len, force_eos, map);
     }
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_greedy_select_banned(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
+                                int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
+                                BanSet ban, int hist0) {
+    if (!ban.bits || (ban.n_multi && !ban.multi) || ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI || hist0 < 0 || hist0 > t + 1) {
+        cap_set_error("greedy_select (banned): no bitmap, %d multi-token sequences (at most %d) or a history from column %d at step %d",
+                      ban.n_multi, BAN_MAX_MULTI, hist0, t);
+        return -1;
+    }
+    hipLaunchKernelGGL(greedy_select_banned_kernel, dim3(R), dim3(256), (size_t)ban_words(V) * 4, s, logits, ld, V, seq, seq_ld, t,
+                       max_len, eos, pad, finished, out_len, min_len, force_eos, map, ban, hist0);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -71,6 +71,23 @@ int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_l
                          // vocab form (launched only when vocab_acc is given; needs the scoring buffers): vocab_acc[row*acc_ld + i] =
                          // max(itself, softmax_i of the row as selected from), i < V, for the rows open at this step
                          float* vocab_acc = nullptr, int acc_ld = 0);
+// Banned tokens and sequences (HF NoBadWordsLogitsProcessor; captioner_hip.h, cap_set_bad_words), as the selection kernels read them:
+//   bits   uint32 [ban_words(V)]: bit i set = token i is banned at every step (the length-1 sequences); bits from V on are 0
+//   multi  int32 [n_multi][BAN_REC]: {n, tok[0 .. n - 1]}, 2 <= n <= BAN_MAX_LEN: tok[n - 1] is banned at a step exactly when the row's
+//          last n - 1 context tokens equal tok[0 .. n - 2]; a sequence longer than the context (n > its length) never matches
+// A block builds the row's bitmap in LDS from both (ban.h) and masks with it; banned = -inf.
+constexpr int BAN_MAX_MULTI = 1024, BAN_MAX_LEN = 8, BAN_REC = BAN_MAX_LEN + 1;
+struct BanSet {
+    const unsigned* bits = nullptr;
+    const int* multi = nullptr;
+    int n_multi = 0;
+};
+__host__ __device__ inline int ban_words(int V) { return ((V + 31) / 32 + 3) / 4 * 4; }       // whole 16-byte pieces
+// launch_greedy_select's plain form under a ban: the arg-max is taken over the row with its banned entries at -inf (a row with
+// nothing left selects index 0).  The context of caption `row` is seq[row][hist0 .. t]; everything else as launch_greedy_select.
+int launch_greedy_select_banned(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
+                                int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
+                                BanSet ban, int hist0);
 // teacher-forced scoring: logits row b of `rows` (fp32 [rows, ld]) is pass row r = r0 + b = position r % npos of caption r / npos; for
 // positions below n_live[caption] the log-softmax at targets[caption * tgt_ld + position] (clamped to [0, V)), log max softmax and the
 // arg-max (launch_greedy_select's selection and tie rule, no EOS mask) go to out_*[caption * out_ld + position], zeros for the others
@@ -259,6 +276,10 @@ enum { BEAM_HF_V5 = 0, BEAM_LEGACY_RAW = 1 };
 int launch_beam_init(void* state, int B, int K, int max_len, int bos, int pad, int eos, hipStream_t s, int mode = BEAM_HF_V5);
 int launch_beam_step(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len,
                      int eos, float length_penalty, int* anc, int anc_ld, hipStream_t s, int mode = BEAM_HF_V5, int min_len = 0);
+// launch_beam_step under a ban (BanSet above): the log-softmax statistics see the raw row, a banned candidate's value is -inf.  The
+// history of a row is its LOGICAL one, run_seq[cur_len & 1][row][0 .. cur_len).
+int launch_beam_step_banned(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
+                            float length_penalty, int* anc, int anc_ld, hipStream_t s, int mode, int min_len, BanSet ban);
 int launch_beam_finalize(void* state, int B, int K, int max_len, int* out_ids, int* out_len, float* out_scores,
                          hipStream_t s);
 // device pointer: int32, 1 while the beam loop of this state is still running (HF `is_done.all()` not yet true)

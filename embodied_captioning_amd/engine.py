@@ -16,6 +16,7 @@ import torch
 
 from . import _native as N
 from .config import Blip2Arch, Blip2ItmArch, BlipArch, ClipArch, CocaArch, MiniLMArch
+from .captioner.bad_words import validate_bad_words_ids  # noqa: F401 - the host check of set_bad_words, public here
 
 logger = logging.getLogger(__name__)
 
@@ -350,6 +351,37 @@ class CaptionerEngine:
         `poll_steps` steps (one stream synchronisation each).  0 = never (default): no host sync inside generate."""
         N.check(self.lib.cap_set_early_exit(self._h, int(poll_steps)), "cap_set_early_exit")
 
+    def set_bad_words(self, seqs) -> None:
+        """HF `generate(bad_words_ids=seqs)` for every generating call that follows (BLIP and BLIP-2, greedy and beams, every
+        decode path; `score` ignores it): a list of token-id lists - one token = banned at every step, n > 1 tokens = the last is
+        banned whenever the caption's last n - 1 context tokens are the first n - 1.  None or [] clears the set.  Validated on the
+        host (`validate_bad_words_ids`) before anything is uploaded; the upload is complete when this returns.  With a set in
+        force `generate` refuses output_logprobs / output_vocab_maxprob and beam groups (the library's rules, by name)."""
+        seqs = validate_bad_words_ids(seqs, self.arch)
+        flat = [t for q in seqs for t in q]
+        offs = [0]
+        for q in seqs:
+            offs.append(offs[-1] + len(q))
+        ids_a = (C.c_int32 * max(len(flat), 1))(*flat)
+        offs_a = (C.c_int32 * len(offs))(*offs)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            N.check(self.lib.cap_set_bad_words(self._h, ids_a, offs_a, len(seqs), C.c_void_p(stream.cuda_stream)), "cap_set_bad_words")
+            stream.synchronize()             # the engine may next be used on another stream (EnginePool)
+        self._bad_words = seqs
+
+    @property
+    def bad_words(self) -> List[List[int]]:
+        """The set in force as `set_bad_words` took it (validated; `[eos]` alone dropped); [] = none."""
+        return [list(q) for q in getattr(self, "_bad_words", [])]
+
+    @property
+    def bad_words_counts(self) -> tuple:
+        """(distinct single tokens, multi-token sequences) as the library holds them (cap_bad_words)."""
+        a, b = C.c_int(0), C.c_int(0)
+        N.check(self.lib.cap_bad_words(self._h, C.byref(a), C.byref(b)), "cap_bad_words")
+        return int(a.value), int(b.value)
+
     @property
     def last_decode_steps(self) -> int:
         return int(self.lib.cap_last_decode_steps(self._h))
@@ -510,7 +542,7 @@ class CaptionerEngine:
 
     def generate(self, pixels: torch.Tensor, num_beams: int = 1, max_length: Optional[int] = None,
                  length_penalty: float = 1.0, output_logits: bool = False, num_beam_groups: Optional[int] = None,
-                 output_logprobs: bool = False, output_vocab_maxprob: bool = False, prompt_ids=None,
+                 output_logprobs: bool = False, output_vocab_maxprob: bool = False, prompt_ids=None, bad_words_ids=None,
                  **sampling_options) -> Dict[str, torch.Tensor]:
         """prompt_ids (BLIP, greedy): a host list / tensor [P], [1, P] (one prompt for every caption) or [B, P] (one per caption), column
         0 = BOS - HF `BlipForConditionalGeneration.generate(pixel_values, input_ids=...)`, whose decoder receives input_ids[:, :-1].
@@ -532,11 +564,16 @@ class CaptionerEngine:
         the [B, acc_ld] buffer behind it; token_logprobs / scored_steps come with it; `fuse_vocab_groups` is its consumer.
         num_beam_groups (CoCa): the reference's `_generate_beamsearch` with that many beam groups (coca_model.py:335-482;
         its `generate()` defaults are 6 beams in 3 groups) - cap_generate_groups; no per-step logits in that mode.
+        bad_words_ids: accepted when it equals the set in force (`set_bad_words`, `.bad_words`; None = not given), refused by name
+        otherwise - the set is engine state, not a per-call option.
         sampling_options: anything else a caller of the reference's / HF's `generate` may pass (top_p, top_k, temperature,
         repetition_penalty, do_sample, ...): accepted at their neutral values, rejected BY NAME otherwise - never ignored."""
         if output_vocab_maxprob and (num_beam_groups is not None or num_beams != 1):      # before anything is allocated or run
             raise N.CaptionerHipError("output_vocab_maxprob is the greedy loop's (num_beams = 1): beam search "
                                       f"(num_beams = {num_beams}, num_beam_groups = {num_beam_groups}) keeps no per-step distribution")
+        if bad_words_ids is not None and validate_bad_words_ids(bad_words_ids, self.arch) != self.bad_words:
+            raise ValueError(f"generate: bad_words_ids differs from the set in force on this engine ({len(self.bad_words)} sequences): "
+                             "the banned set is engine state - call set_bad_words(bad_words_ids) first")
         if sampling_options:
             from .captioner.generation_options import reject_unsupported_generation_options, _NEUTRAL
             known = set(_NEUTRAL) | {"generation_type", "top_k", "top_p"}
@@ -780,6 +817,14 @@ class EnginePool:
     def set_decode_path(self, path: str) -> None:
         for e in self.engines:
             e.set_decode_path(path)
+
+    def set_bad_words(self, seqs) -> None:
+        for e in self.engines:
+            e.set_bad_words(seqs)
+
+    @property
+    def bad_words(self):
+        return self.engines[0].bad_words
 
     def set_row_compaction(self, on: bool) -> None:
         for e in self.engines:

@@ -57,7 +57,10 @@ class BatchedBoxCaptioner:
     `encoder` (optional): an object with `encode(list[str], convert_to_tensor=True)` (SentenceEncoder, or the reference's
     SentenceTransformer) - called once for the whole batch - or a plain callable caption -> vector.
     with_perplexity: every frame's result also carries "perplexities" (float64 [n], box order; the reference's per-caption
-    `compute_perplexity()`), from `captioner.caption_batch(crops, return_perplexity=True)`."""
+    `compute_perplexity()`), from `captioner.caption_batch(crops, return_perplexity=True)`.
+    `last_filter_failures`: captions of the last `predict_captions` call that fail `distributed.filter_caption` (None before one)."""
+
+    last_filter_failures = None
 
     def __init__(self, captioner, encoder: Optional[Callable[[str], torch.Tensor]] = None, expand_factor: float = 0.2,
                  device_resize: Optional[bool] = None, with_perplexity: bool = False):
@@ -115,6 +118,10 @@ class BatchedBoxCaptioner:
                 crops.extend(crop_boxes(img, boxes, self.expand_factor))
                 owner += [fi] * len(boxes)
         captions, ppl = self._caption(crops)
+        # how many captions of this call the reference's banned-word filter (distributed.filter_caption) would still throw away -
+        # with captioner.bad_words set this is what the constrained decoding could not prevent (captioner/bad_words.py)
+        from .distributed import filter_caption
+        self.last_filter_failures = sum(0 if filter_caption(c) else 1 for c in captions)
         out = [{"captions": [], "embeddings": torch.tensor([])} for _ in frames_bgr]
         for fi, cap in zip(owner, captions):
             out[fi]["captions"].append(cap)

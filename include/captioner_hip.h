@@ -28,6 +28,9 @@
  *                       pseudolabeler.py:673-676 (the callers hand over ONE image)      launches), cap_set_decode_path
  *   greedy stopping     HF generation/utils.py:2894-2937 (a finished row keeps its slot and   cap_set_row_compaction (the open
  *                       is fed pad tokens; `unfinished_sequences.max() == 0` ends the loop)  rows only), cap_set_early_exit
+ *   banned words        HF `generate(bad_words_ids=...)` (NoBadWordsLogitsProcessor) - what would   cap_set_bad_words, cap_bad_words
+ *                       keep the captions experimenting_env/captioner/pseudocaptioner.py:96-123    (BLIP, BLIP-2; inside the token
+ *                       throws away for a banned word                                             selection kernels)
  *   batches of crops    detector/pseudolabeler.py:664-711, scripts/run_pseudolabeler.py:77-107  cap_create_shared (n engines on one
  *                       (one generate per crop; here: micro-batches merged into passes)          weight store: engine.EnginePool)
  *   load options        blip2.py:19-22 `load_in_8bit=True, torch_dtype=float16`;       CapConfig.weight_int8 (int8 Linear weights as
@@ -170,6 +173,30 @@ int cap_finalize_weights(CapHandle h);
 int cap_set_early_exit(CapHandle h, int poll_steps);
 /* Decode steps the last cap_generate on this handle ran (max_len - 1 without early exit; diagnostics and tests). */
 int cap_last_decode_steps(CapHandle h);
+
+/* Banned tokens and token sequences of the decode loops: HF `generate(bad_words_ids=...)` (NoBadWordsLogitsProcessor), applied
+ * on the device inside the token selection.  Handle state, like cap_set_early_exit: it holds for every generating call that follows
+ * until it is replaced or cleared.  ids / offsets are HOST arrays in CSR form (sequence q = ids[offsets[q] .. offsets[q + 1]),
+ * offsets[0] = 0); n_sequences = 0 clears the set.
+ *   a sequence of one token      banned at every step ([eos] alone is dropped silently, as HF drops it); any number of them
+ *   a sequence of n > 1 tokens   its last token is banned at a step exactly when the caption's last n - 1 context tokens are its first
+ *                                n - 1; a sequence longer than the context (n > its length) never matches.  At most 1024 of them, at most 8 tokens each.
+ * Banned = -inf.  Greedy: the arg-max is taken over the banned row (first maximal index; a row with nothing left selects 0).  Beam
+ * search: log-softmax of the RAW row, then the ban, then the running score (HF `_beam_search`).  The context is what HF's processor
+ * sees: BLIP's BOS, prompt tokens and generated tokens (a sequence may match across the prompt boundary); BLIP-2's BOS and
+ * generated tokens.  out_step_logits stays the raw logits.
+ * Honoured by cap_generate_request and its siblings on CAP_ARCH_BLIP and CAP_ARCH_BLIP2 handles, num_beams 1 .. 8, on every path
+ * (batch, small-batch, compacted, prompted, from an image state).  With a non-empty set they refuse, by name: a CAP_ARCH_COCA handle,
+ * beam groups, out_logprobs / out_vocab.  cap_score_captions ignores the set by definition (teacher forcing reads plain logits).
+ * Refused by name: an empty sequence, an id outside [0, vocab), the BOS or pad id (context only, never generated), the limits above.
+ * The set's storage is allocated at the first non-empty set and freed by cap_destroy; it is not part of the arena.  The upload is
+ * in stream order; replacing a set synchronises the GIVEN stream first.  The caller's obligation: no generating call of this handle
+ * may be in flight on ANOTHER stream while the set is replaced or cleared (it reads the set's device arrays), and a call on another
+ * stream must be ordered behind the upload (CaptionerEngine.set_bad_words synchronises after it).  With nothing set every launch is
+ * the unbanned one. */
+int cap_set_bad_words(CapHandle h, const int32_t* ids, const int32_t* offsets, int n_sequences, void* stream);
+/* The set in force: distinct single tokens and multi-token sequences (either pointer may be NULL). */
+int cap_bad_words(CapHandle h, int* n_single, int* n_multi);
 
 /* Which kernels the decode steps of cap_generate run on (CAP_ARCH_BLIP, split and bf16 modes).  The reference calls its captioner
  * with ONE crop per call (captioner/models/coca/coca.py:27-33, blip2/blip2.py:24-29, agents/goal_exploration/goal_exploration.py:
@@ -697,6 +724,19 @@ int cap_op_target_logprob(const float* logits, int ld, int V, int rows, const in
 int cap_op_select_vocab(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int min_len, int force_eos,
                         int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths,
                         float* logprobs, int lp_ld, int32_t* scored, float* vocab_acc, int acc_ld, void* stream);
+/* The banned forms of the two selections alone (cap_set_bad_words), the set given as the device arrays the kernels read:
+ * ban_bits uint32 [cap_op_ban_words(V)] (bit i = token i banned at every step; bits from V on 0), ban_multi int32 [n_multi][9]
+ * ({n, tok[0 .. n - 1], zeros}, 2 <= n <= 8; n_multi <= 1024, ban_multi may be NULL when it is 0).
+ * cap_op_select_banned: cap_op_select_logprob's plain form (no min_len, no force_eos, no log-probs) over the row with its banned
+ * entries at -inf; a caption's context is seq[caption][hist0 .. t] (a sequence of n tokens is looked at when n <= its length).  cap_op_beam_step_banned: cap_op_beam_step with the ban applied
+ * to the candidates after the log-softmax of the raw row; a row's history is its running sequence, columns 0 .. cur_len - 1. */
+int cap_op_ban_words(int V);
+int cap_op_select_banned(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int32_t* finished,
+                         const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths, const uint32_t* ban_bits,
+                         const int32_t* ban_multi, int n_multi, int hist0, void* stream);
+int cap_op_beam_step_banned(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
+                            float length_penalty, int32_t* anc, int anc_ld, int mode, int min_len, const uint32_t* ban_bits,
+                            const int32_t* ban_multi, int n_multi, void* stream);
 /* The group step of the probability fusion.  acc fp32 [N, acc_ld] (device); G groups in CSR form, both arrays on the device:
  * group_rows int32 [M] (row indices into acc, in the caller's order, need not be contiguous, each row in one group at most) and
  * group_off int32 [G + 1] (0 = off[0] <= ... <= off[G] = M; an empty group is legal).  Per group, in fp32,
