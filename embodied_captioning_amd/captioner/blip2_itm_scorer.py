@@ -14,10 +14,10 @@ from __future__ import annotations
 
 from typing import List, Sequence, Union
 
-import numpy as np
 import torch
 
 from ..config import Blip2ItmArch
+from ..preprocess import pad_rows, pixel_batches
 
 PROCEDURAL = "procedural-blip2-itm"
 HEADS = ("itm", "itc")
@@ -48,15 +48,6 @@ def tokenize_captions(tokenizer, captions: Sequence[Union[str, Sequence[int]]], 
             raise ValueError("empty caption id row")
         rows.append(r)
     return rows
-
-
-def pad_rows(rows: Sequence[Sequence[int]], pad: int = 0):
-    """Id rows -> (ids int32 [n, L], lens int32 [n]) padded to the longest row of THIS batch."""
-    L = max(len(r) for r in rows)
-    ids = torch.full((len(rows), L), pad, dtype=torch.int32)
-    for b, r in enumerate(rows):
-        ids[b, :len(r)] = torch.tensor(r, dtype=torch.int32)
-    return ids, torch.tensor([len(r) for r in rows], dtype=torch.int32)
 
 
 class Blip2ItmScorer:
@@ -108,21 +99,7 @@ class Blip2ItmScorer:
 
     # ------------------------------------------------------------------------------------------ images
     def _pixel_batches(self, images):
-        S = self.arch.image_size
-        if isinstance(images, torch.Tensor) and (images.dtype != torch.uint8 or (images.dim() == 4 and tuple(images.shape[1:]) == (S, S, 3))):
-            x = images if images.dim() == 4 else images[None]      # normalised tensors, or uint8 frames already at the tower's size
-            for i in range(0, x.shape[0], self.batch_size):
-                yield x[i:i + self.batch_size]
-            return
-        from ..preprocess import resize_u8_list
-        arrs = []
-        for im in images:
-            a = np.asarray(im.convert("RGB")) if hasattr(im, "convert") else np.asarray(im.cpu() if isinstance(im, torch.Tensor) else im)
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-                raise ValueError(f"images must be PIL, uint8 [H, W, 3] RGB or normalised [n, 3, {S}, {S}] tensors, got {a.dtype} {a.shape}")
-            arrs.append(np.ascontiguousarray(a))
-        for i in range(0, len(arrs), self.batch_size):
-            yield resize_u8_list(arrs[i:i + self.batch_size], S, device=self.device, center_crop=False)
+        return pixel_batches(images, self.arch.image_size, self.batch_size, self.device, center_crop=False)
 
     def get_image_features(self, images) -> torch.Tensor:
         """-> fp32 [n, num_query_tokens, projection_dim] on the device, rows L2-normalised (HF's ITC `image_embeds`)."""

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from ..config import ClipArch
+from ..preprocess import pad_rows, pixel_batches
 
 PROCEDURAL = "procedural-clip"
 
@@ -94,42 +95,18 @@ class ClipScorer:
         pos = pooled_positions(rows, self.arch.eos_token_id)
         outs = []
         for i in range(0, len(rows), self.batch_size):
-            chunk, p = rows[i:i + self.batch_size], pos[i:i + self.batch_size]
-            L = max(len(r) for r in chunk)
-            ids = torch.full((len(chunk), L), self.arch.pad_token_id, dtype=torch.int32)
-            for b, r in enumerate(chunk):
-                ids[b, :len(r)] = torch.tensor(r, dtype=torch.int32)
-            lens = torch.tensor([q + 1 for q in p], dtype=torch.int32)
+            ids, _ = pad_rows(rows[i:i + self.batch_size], self.arch.pad_token_id)
+            lens = torch.tensor([q + 1 for q in pos[i:i + self.batch_size]], dtype=torch.int32)      # up to the pooled row, not the row's end
             outs.append(self.engine.embed_text(ids, lens))
         if not outs:
             return torch.empty((0, self.arch.projection_dim), device=self.device)
         return outs[0] if len(outs) == 1 else torch.cat(outs)
 
     # ------------------------------------------------------------------------------------------ images
-    def _pixel_batches(self, images):
-        S = self.arch.image_size
-        if isinstance(images, torch.Tensor) and images.dtype != torch.uint8:
-            x = images if images.dim() == 4 else images[None]
-            for i in range(0, x.shape[0], self.batch_size):
-                yield x[i:i + self.batch_size]
-            return
-        if isinstance(images, torch.Tensor) and images.dim() == 4 and tuple(images.shape[1:]) == (S, S, 3):
-            for i in range(0, images.shape[0], self.batch_size):    # already the tower's size (e.g. device crops): as they are
-                yield images[i:i + self.batch_size]
-            return
-        from ..preprocess import resize_u8_list
-        arrs = []
-        for im in images:
-            a = np.asarray(im.convert("RGB")) if hasattr(im, "convert") else np.asarray(im.cpu() if isinstance(im, torch.Tensor) else im)
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-                raise ValueError(f"images must be PIL, uint8 [H, W, 3] RGB or normalised [n, 3, {S}, {S}] tensors, got {a.dtype} {a.shape}")
-            arrs.append(np.ascontiguousarray(a))
-        for i in range(0, len(arrs), self.batch_size):
-            yield resize_u8_list(arrs[i:i + self.batch_size], S, device=self.device, center_crop=True, geometry="hf")
-
     def get_image_features(self, images) -> torch.Tensor:
         """-> fp32 [n, projection_dim] on the device, L2-normalised (HF's `image_embeds`)."""
-        outs = [self.engine.embed_images(px) for px in self._pixel_batches(images)]
+        batches = pixel_batches(images, self.arch.image_size, self.batch_size, self.device, center_crop=True, geometry="hf")
+        outs = [self.engine.embed_images(px) for px in batches]
         if not outs:
             return torch.empty((0, self.arch.projection_dim), device=self.device)
         return outs[0] if len(outs) == 1 else torch.cat(outs)

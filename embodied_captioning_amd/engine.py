@@ -5,6 +5,7 @@ libcaptioner_hip.so.  Mirrors what the reference's wrappers call on their torch 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import json
 import logging
@@ -231,86 +232,88 @@ def images_or_state(images, image_state, who: str):
     return image_state
 
 
-class CaptionerEngine:
-    """One handle = one model replica on one GPU, bound to torch's current stream of `device` at each call."""
+def _launch(lib, device, entry: str, *args) -> None:
+    """One native call on `device` and its current stream: tensors go in as their data pointers (None = NULL), everything else as it
+    is; the stream is the entry point's last argument; a non-zero status raises under the entry point's name."""
+    with torch.cuda.device(device):
+        argv = [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
+        N.check(getattr(lib, entry)(*argv, C.c_void_p(_stream_ptr(device))), entry)
 
-    def __init__(self, arch: BlipArch, dtype: str = "bf16", max_batch: int = 8, max_beams: int = 1,
-                 max_len: int = 20, device: str | torch.device = "cuda:0", share_weights_with: "CaptionerEngine | None" = None,
-                 cross_cache: str = "auto", weight_int8: bool = False, max_prompt: int = 0, max_score_rows: int = 0):
-        """max_score_rows (BLIP): scoring capacity in decoder rows (`score`): N captions of L tokens run as ONE pass with one vocabulary
-        GEMM when N * (L - 1) <= max_score_rows; 0 reserves nothing (the arena is what it always was) and `score` works in passes of
-        as many captions as the decode rows hold, the head over max_batch * max_beams rows at a time - same bits.
-        max_prompt (BLIP): prompt capacity - with max_prompt >= P the P - 1 prompt positions of a FULL batch run through the decoder
-        as one prefill pass (`generate(prompt_ids=)`); 0 reserves nothing (the arena is what it always was) and a prompted batch
-        is prefilled in chunks of as many captions as the decode rows hold (`prompt_limit` = the longest prompt taken).
-        weight_int8 (BLIP-2, dtype "bf16" only): the reference's `load_in_8bit=True` (blip2.py:19-22) - the OPT decoder layers' Linear
-        weights are kept as row-quantised int8 + fp32 row scales (bitsandbytes' storage) and streamed as bytes by the decode GEMMs,
-        the vision tower's Linears and language_projection pass through the same quantiser at load; activations stay bf16.
-        cross_cache: "auto" = the mode's own cross-attention K/V cache ("f32s": KV16 - int16 + one scale per 64-wide head row,
-        the decode side's HBM stream at half the bytes; "bf16": bf16 rows; "f32": fp32 rows); "fp32" = fp32 rows in "f32s" too
-        (`cross_cache_kind` tells what the handle uses).
-        share_weights_with: an engine of the same model / dtype / GPU whose (read-only) weights this one uses instead of
-        holding a copy - it gets its own arena only (cap_create_shared); load_state_dict through either is seen by both."""
+
+def _ids_shape(ids: torch.Tensor, lens: torch.Tensor):
+    if ids.dim() != 2 or lens.shape != (ids.shape[0],):
+        raise ValueError(f"ids must be [B, L] and lens [B], got {tuple(ids.shape)} / {tuple(lens.shape)}")
+    return ids.shape
+
+
+@contextlib.contextmanager
+def _deriving_tensors():
+    """Around the preparations of a `load_state_dict` that compute tensors from the checkpoint's own: a key they need and do not find
+    is named as the library's error."""
+    try:
+        yield
+    except KeyError as e:
+        raise N.CaptionerHipError(f"state dict lacks {e}: this architecture derives tensors from the checkpoint at load "
+                                  f"and needs the complete dict (keys with a 'model.' / 'module.' prefix? see "
+                                  f"weights.strip_wrapper_prefixes)") from e
+
+
+def _with_qformer_x0(sd: Dict[str, torch.Tensor], q_eps: float) -> Dict[str, torch.Tensor]:
+    """The Q-Former's input = LayerNorm(query_tokens) is a constant of the checkpoint: computed once here (`derived.qformer_x0`)."""
+    if "derived.qformer_x0" in sd:
+        return sd
+    sd = dict(sd)
+    q = sd["query_tokens"].float()[0]
+    sd["derived.qformer_x0"] = torch.nn.functional.layer_norm(
+        q, (q.shape[-1],), sd["qformer.layernorm.weight"].float(), sd["qformer.layernorm.bias"].float(), q_eps)
+    return sd
+
+
+class _Engine:
+    """One native handle on one GPU, bound to torch's current stream of `device` at each call: what the captioner and the three
+    scorer engines share - creation, lifetime and diagnostics, the weight stream, the checks of frames and of ids / lens, and the
+    form of a native call.  A subclass fills its own fields of the CapConfig and adds its forward calls."""
+
+    _NO_GPU = "needs a GPU"
+
+    def __init__(self, arch, dtype: str, max_batch: int, max_len: int, device: str | torch.device):
         if not torch.cuda.is_available():
-            raise N.CaptionerHipError("CaptionerEngine needs a GPU (torch.cuda.is_available() is False); "
-                                      "there is no CPU fallback in the product path")
+            raise N.CaptionerHipError(f"{type(self).__name__} {self._NO_GPU}; there is no CPU fallback in the product path")
         self.lib = N.load_library()
-        self.arch = arch
-        self.dtype = dtype
-        self.device = torch.device(device)
-        self.max_batch, self.max_beams, self.max_len = max_batch, max_beams, max_len
-        self.max_prompt = int(max_prompt)
-        if self.max_prompt and (_arch_family(arch) != "blip" or not 2 <= self.max_prompt <= N.CAP_MAX_PROMPT):
-            raise ValueError(f"max_prompt = {max_prompt}: prompt capacity is BLIP's, 0 or 2..{N.CAP_MAX_PROMPT} tokens (BOS included)")
-        self.prompt_limit = prompt_token_limit(max_batch, max_beams, self.max_prompt)
+        self.arch, self.dtype, self.device = arch, dtype, torch.device(device)
+        self.max_batch, self.max_len = max_batch, max_len
+
+    # ------------------------------------------------------------------------------------------ creation
+    def _config(self, arch_kind: int, max_beams: int = 1) -> N.CapConfig:
         cfg = N.CapConfig()
         cfg.struct_size = C.sizeof(N.CapConfig)
-        cfg.compute_dtype = _DTYPES[dtype]
-        cfg.max_prompt = self.max_prompt
-        self.max_score_rows = int(max_score_rows)
-        if self.max_score_rows and (_arch_family(arch) != "blip" or self.max_score_rows < 0):
-            raise ValueError(f"max_score_rows = {max_score_rows}: scoring capacity is BLIP's, 0 or a row count")
-        cfg.max_score_rows = self.max_score_rows
-        cfg.image_size, cfg.patch_size = arch.image_size, arch.patch_size
-        self.is_coca = isinstance(arch, CocaArch)
-        self.is_blip2 = isinstance(arch, Blip2Arch)
-        if self.is_blip2:
-            cfg.arch = 3
-            cfg.v_hidden, cfg.v_layers, cfg.v_heads, cfg.v_mlp, cfg.v_eps = (arch.v_hidden, arch.v_layers, arch.v_heads,
-                                                                             arch.v_mlp, arch.v_eps)
-            cfg.q_hidden, cfg.q_layers, cfg.q_heads, cfg.q_ffn = arch.q_hidden, arch.q_layers, arch.q_heads, arch.q_ffn
-            cfg.q_cross_freq, cfg.num_query_tokens, cfg.q_eps = arch.q_cross_freq, arch.num_query_tokens, arch.q_eps
-            cfg.t_hidden, cfg.t_layers, cfg.t_heads, cfg.t_ffn = arch.t_hidden, arch.t_layers, arch.t_heads, arch.t_ffn
-            cfg.vocab, cfg.max_pos, cfg.t_eps = arch.vocab, arch.max_pos, arch.t_eps
-            cfg.bos, cfg.eos, cfg.pad = arch.bos, arch.eos, arch.pad
-        elif self.is_coca:
-            cfg.arch = 1
-            cfg.v_hidden, cfg.v_layers, cfg.v_heads, cfg.v_mlp, cfg.v_eps = (arch.v_hidden, arch.v_layers, arch.v_heads,
-                                                                             arch.v_mlp, arch.eps)
-            cfg.t_hidden, cfg.t_layers, cfg.t_heads, cfg.t_ffn = arch.t_hidden, arch.t_layers, arch.t_heads, arch.t_ffn
-            cfg.vocab, cfg.max_pos, cfg.t_eps = arch.vocab, arch.context_length + 1, arch.eps
-            cfg.bos, cfg.eos, cfg.pad = arch.sot, arch.eos, arch.pad
-            cfg.embed_dim, cfg.pool_queries, cfg.pool_heads = arch.embed_dim, arch.pool_queries, arch.pool_heads
-            cfg.mm_layers, cfg.min_len = arch.mm_layers, arch.min_seq_len
-        else:
-            cfg.arch = 0
-            cfg.v_hidden, cfg.v_layers, cfg.v_heads, cfg.v_mlp, cfg.v_eps = (arch.v_hidden, arch.v_layers, arch.v_heads,
-                                                                             arch.v_mlp, arch.v_eps)
-            cfg.t_hidden, cfg.t_layers, cfg.t_heads, cfg.t_ffn = arch.t_hidden, arch.t_layers, arch.t_heads, arch.t_ffn
-            cfg.vocab, cfg.max_pos, cfg.t_eps = arch.vocab, arch.max_pos, arch.t_eps
-            cfg.bos, cfg.eos, cfg.pad = arch.bos, arch.eos, arch.pad
-        cfg.max_batch, cfg.max_beams, cfg.max_len = max_batch, max_beams, max_len
-        if cross_cache not in ("auto", "fp32"):
-            raise ValueError(f"cross_cache must be 'auto' or 'fp32', got {cross_cache!r}")
-        cfg.cross_kv_fp32 = int(cross_cache == "fp32")
-        self.cross_cache = cross_cache
-        self.weight_int8 = bool(weight_int8)
-        if self.weight_int8 and not (self.is_blip2 and dtype == "bf16"):
-            raise ValueError("weight_int8 (load_in_8bit) is built for BLIP-2 with dtype 'bf16'")
-        cfg.weight_int8 = int(self.weight_int8)
+        cfg.arch = arch_kind
+        cfg.compute_dtype = _DTYPES[self.dtype]
+        cfg.max_batch, cfg.max_beams, cfg.max_len = self.max_batch, max_beams, self.max_len
+        return cfg
+
+    def _vision_tower(self, cfg: N.CapConfig, eps: float) -> None:
+        a = self.arch
+        cfg.image_size, cfg.patch_size = a.image_size, a.patch_size
+        cfg.v_hidden, cfg.v_layers, cfg.v_heads, cfg.v_mlp, cfg.v_eps = a.v_hidden, a.v_layers, a.v_heads, a.v_mlp, eps
         for i in range(3):
             cfg.pix_mean[i] = OPENAI_CLIP_MEAN[i]
             cfg.pix_std[i] = OPENAI_CLIP_STD[i]
+
+    def _text_tower(self, cfg: N.CapConfig, max_pos: int, eps: float, tokens=None) -> None:
+        """tokens: (bos, eos, pad) of a tower that has special tokens."""
+        a = self.arch
+        cfg.t_hidden, cfg.t_layers, cfg.t_heads, cfg.t_ffn = a.t_hidden, a.t_layers, a.t_heads, a.t_ffn
+        cfg.vocab, cfg.max_pos, cfg.t_eps = a.vocab, max_pos, eps
+        if tokens is not None:
+            cfg.bos, cfg.eos, cfg.pad = tokens
+
+    def _qformer(self, cfg: N.CapConfig) -> None:
+        a = self.arch
+        cfg.q_hidden, cfg.q_layers, cfg.q_heads, cfg.q_ffn = a.q_hidden, a.q_layers, a.q_heads, a.q_ffn
+        cfg.q_cross_freq, cfg.num_query_tokens, cfg.q_eps = a.q_cross_freq, a.num_query_tokens, a.q_eps
+
+    def _create(self, cfg: N.CapConfig, share_weights_with: "_Engine | None") -> None:
         self._h = C.c_void_p()
         self.shares_weights = share_weights_with is not None
         with torch.cuda.device(self.device):
@@ -318,6 +321,10 @@ class CaptionerEngine:
                 N.check(self.lib.cap_create_shared(C.byref(cfg), share_weights_with._h, C.byref(self._h)), "cap_create_shared")
             else:
                 N.check(self.lib.cap_create(C.byref(cfg), C.byref(self._h)), "cap_create")
+
+    def _call(self, entry: str, *args) -> None:
+        """`_launch` of an entry point that takes this handle first."""
+        _launch(self.lib, self.device, entry, self._h, *args)
 
     # ------------------------------------------------------------------------------------------ lifetime
     def close(self) -> None:
@@ -345,6 +352,144 @@ class CaptionerEngine:
         if n < 0:
             raise N.CaptionerHipError(f"cap_g8_saturations: {N.last_error()}")
         return n
+
+    # ------------------------------------------------------------------------------------------ weights
+    def _stream_weights(self, sd: Dict[str, torch.Tensor], strict: bool) -> Dict[str, object]:
+        """What every `load_state_dict` ends in, once its dict is prepared: each tensor through cap_load_weight, then
+        cap_finalize_weights; the rules and the report are those of `CaptionerEngine.load_state_dict`."""
+        matched, unknown = 0, []
+        with torch.cuda.device(self.device):
+            s = _stream_ptr(self.device)
+            for name, t in sd.items():
+                t = t.detach()
+                if t.dtype != torch.float32:
+                    t = t.float()
+                t = t.contiguous()
+                shape = (C.c_int64 * max(t.dim(), 1))(*(t.shape if t.dim() else (1,)))
+                rc = self.lib.cap_load_weight(self._h, name.encode(), C.c_void_p(t.data_ptr()), int(t.is_cuda),
+                                              max(t.dim(), 1), shape, C.c_void_p(s))
+                if rc < 0:
+                    raise N.CaptionerHipError(f"cap_load_weight({name}): {N.last_error()}")
+                if rc == 0:
+                    matched += 1
+                else:
+                    unknown.append(name)
+            if len(sd) and not matched:
+                raise N.CaptionerHipError(f"none of the {len(sd)} tensors is one this architecture stores "
+                                          f"(first keys: {list(sd)[:3]}): wrong checkpoint or key prefix")
+            missing = self.lib.cap_finalize_weights(self._h)
+            if missing and strict:
+                raise N.CaptionerHipError(f"checkpoint incomplete: {N.last_error()}")
+        return {"matched": matched, "unknown": unknown}
+
+    # ------------------------------------------------------------------------------------------ input checks
+    def _pixels(self, pixels: torch.Tensor):
+        """Frames, uint8 [B, S, S, 3] or float [B, 3, S, S] -> (contiguous on this device, the library's pixel format)."""
+        if pixels.device != self.device:
+            pixels = pixels.to(self.device, non_blocking=True)
+        a = self.arch
+        if pixels.dtype == torch.uint8:
+            if pixels.dim() != 4 or pixels.shape[1:] != (a.image_size, a.image_size, 3):
+                raise ValueError(f"uint8 frames must be [B,{a.image_size},{a.image_size},3], got {tuple(pixels.shape)}")
+            fmt = N.CAP_PIX_U8_NHWC
+        else:
+            if pixels.dim() != 4 or pixels.shape[1:] != (3, a.image_size, a.image_size):
+                raise ValueError(f"float frames must be [B,3,{a.image_size},{a.image_size}], got {tuple(pixels.shape)}")
+            pixels = pixels.float()
+            fmt = N.CAP_PIX_F32_NCHW
+        return pixels.contiguous(), fmt
+
+    def _ids_lens(self, ids: torch.Tensor, lens: torch.Tensor):
+        """ids int [B, L], lens int [B] -> (ids, lens as int32 on this device, B, L).  Host tensors are validated here for free; device
+        tensors are clamped by the kernels (no host synchronisation per call)."""
+        B, L = _ids_shape(ids, lens)
+        if not ids.is_cuda and not lens.is_cuda and B and L:
+            if int(lens.max()) > L or int(lens.min()) < 1:
+                raise ValueError("lens must be within 1..L")
+            if int(ids.max()) >= self.arch.vocab or int(ids.min()) < 0:
+                raise ValueError("token id outside the vocabulary")
+        return ids.to(self.device, torch.int32).contiguous(), lens.to(self.device, torch.int32).contiguous(), B, L
+
+    # ------------------------------------------------------------------------------------------ profiling
+    def profile(self, on: bool) -> None:
+        N.check(self.lib.cap_profile_enable(self._h, int(on)), "cap_profile_enable")
+
+    def profile_report(self) -> dict:
+        buf = C.create_string_buffer(1 << 16)
+        N.check(self.lib.cap_profile_report(self._h, buf, len(buf)), "cap_profile_report")
+        return json.loads(buf.value.decode())
+
+    # ------------------------------------------------------------------------------------------ arena state (tests only)
+    def _fill_arena(self, pattern: int) -> int:
+        """Write the 32-bit pattern over every scratch buffer of this handle's arena on the current stream (index and kept buffers
+        and the weights are left alone); returns the bytes filled.  For tests/test_arena_state_gpu.py: no product code calls it."""
+        with torch.cuda.device(self.device):
+            n = int(self.lib.cap_debug_fill_arena(self._h, C.c_uint32(pattern & 0xFFFFFFFF), C.c_void_p(_stream_ptr(self.device))))
+        if n < 0:
+            raise N.CaptionerHipError(f"cap_debug_fill_arena: {N.last_error()}")
+        return n
+
+    def _arena_kinds(self) -> dict:
+        """{"arena_bytes", "scratch_bytes", "index_bytes", "kept_bytes", "index": [names], "kept": [names]} of this handle's arena."""
+        buf = C.create_string_buffer(1 << 12)
+        N.check(self.lib.cap_debug_arena_kinds(self._h, buf, len(buf)), "cap_debug_arena_kinds")
+        return json.loads(buf.value.decode())
+
+
+class CaptionerEngine(_Engine):
+    """One handle = one model replica on one GPU, bound to torch's current stream of `device` at each call."""
+
+    _NO_GPU = "needs a GPU (torch.cuda.is_available() is False)"
+    _skip_kv16_guard = False     # tests/probe_kv16_outliers.py sets it on an instance to load a checkpoint the guard refuses
+
+    def __init__(self, arch: BlipArch, dtype: str = "bf16", max_batch: int = 8, max_beams: int = 1,
+                 max_len: int = 20, device: str | torch.device = "cuda:0", share_weights_with: "CaptionerEngine | None" = None,
+                 cross_cache: str = "auto", weight_int8: bool = False, max_prompt: int = 0, max_score_rows: int = 0):
+        """max_score_rows (BLIP): scoring capacity in decoder rows (`score`): N captions of L tokens run as ONE pass with one vocabulary
+        GEMM when N * (L - 1) <= max_score_rows; 0 reserves nothing (the arena is what it always was) and `score` works in passes of
+        as many captions as the decode rows hold, the head over max_batch * max_beams rows at a time - same bits.
+        max_prompt (BLIP): prompt capacity - with max_prompt >= P the P - 1 prompt positions of a FULL batch run through the decoder
+        as one prefill pass (`generate(prompt_ids=)`); 0 reserves nothing (the arena is what it always was) and a prompted batch
+        is prefilled in chunks of as many captions as the decode rows hold (`prompt_limit` = the longest prompt taken).
+        weight_int8 (BLIP-2, dtype "bf16" only): the reference's `load_in_8bit=True` (blip2.py:19-22) - the OPT decoder layers' Linear
+        weights are kept as row-quantised int8 + fp32 row scales (bitsandbytes' storage) and streamed as bytes by the decode GEMMs,
+        the vision tower's Linears and language_projection pass through the same quantiser at load; activations stay bf16.
+        cross_cache: "auto" = the mode's own cross-attention K/V cache ("f32s": KV16 - int16 + one scale per 64-wide head row,
+        the decode side's HBM stream at half the bytes; "bf16": bf16 rows; "f32": fp32 rows); "fp32" = fp32 rows in "f32s" too
+        (`cross_cache_kind` tells what the handle uses).
+        share_weights_with: an engine of the same model / dtype / GPU whose (read-only) weights this one uses instead of
+        holding a copy - it gets its own arena only (cap_create_shared); load_state_dict through either is seen by both."""
+        super().__init__(arch, dtype, max_batch, max_len, device)
+        self.max_beams = max_beams
+        self.max_prompt = int(max_prompt)
+        if self.max_prompt and (_arch_family(arch) != "blip" or not 2 <= self.max_prompt <= N.CAP_MAX_PROMPT):
+            raise ValueError(f"max_prompt = {max_prompt}: prompt capacity is BLIP's, 0 or 2..{N.CAP_MAX_PROMPT} tokens (BOS included)")
+        self.prompt_limit = prompt_token_limit(max_batch, max_beams, self.max_prompt)
+        self.max_score_rows = int(max_score_rows)
+        if self.max_score_rows and (_arch_family(arch) != "blip" or self.max_score_rows < 0):
+            raise ValueError(f"max_score_rows = {max_score_rows}: scoring capacity is BLIP's, 0 or a row count")
+        self.is_coca = isinstance(arch, CocaArch)
+        self.is_blip2 = isinstance(arch, Blip2Arch)
+        if cross_cache not in ("auto", "fp32"):
+            raise ValueError(f"cross_cache must be 'auto' or 'fp32', got {cross_cache!r}")
+        self.cross_cache = cross_cache
+        self.weight_int8 = bool(weight_int8)
+        if self.weight_int8 and not (self.is_blip2 and dtype == "bf16"):
+            raise ValueError("weight_int8 (load_in_8bit) is built for BLIP-2 with dtype 'bf16'")
+        cfg = self._config(3 if self.is_blip2 else 1 if self.is_coca else 0, max_beams)
+        if self.is_coca:
+            self._vision_tower(cfg, arch.eps)
+            self._text_tower(cfg, arch.context_length + 1, arch.eps, (arch.sot, arch.eos, arch.pad))
+            cfg.embed_dim, cfg.pool_queries, cfg.pool_heads = arch.embed_dim, arch.pool_queries, arch.pool_heads
+            cfg.mm_layers, cfg.min_len = arch.mm_layers, arch.min_seq_len
+        else:
+            self._vision_tower(cfg, arch.v_eps)
+            self._text_tower(cfg, arch.max_pos, arch.t_eps, (arch.bos, arch.eos, arch.pad))
+        if self.is_blip2:
+            self._qformer(cfg)
+        cfg.max_prompt, cfg.max_score_rows = self.max_prompt, self.max_score_rows
+        cfg.cross_kv_fp32, cfg.weight_int8 = int(cross_cache == "fp32"), int(self.weight_int8)
+        self._create(cfg, share_weights_with)
 
     def set_early_exit(self, poll_steps: int) -> None:
         """Leave the decode loop once every caption is finished, as HF generate does; the device state is looked at every
@@ -423,29 +568,20 @@ class CaptionerEngine:
         Tensors the architecture does not store (tied heads, buffers) are skipped and reported; with strict=True missing
         ones raise.  A dict in which NOTHING matches always raises - it is a wrong checkpoint or wrong key prefixes, never a
         successful load.  Returns {"matched": n, "unknown": [names]}."""
-        try:
+        with _deriving_tensors():
             if self.is_coca and "derived.pool_q" not in sd:
                 from .coca_weights import coca_library_state_dict
                 sd = coca_library_state_dict(sd, self.arch)
-            if getattr(self, "is_blip2", False) and "derived.qformer_x0" not in sd:
-                # the Q-Former's input = LayerNorm(query_tokens) is a constant of the checkpoint: computed once here
-                sd = dict(sd)
-                q = sd["query_tokens"].float()[0]
-                sd["derived.qformer_x0"] = torch.nn.functional.layer_norm(
-                    q, (q.shape[-1],), sd["qformer.layernorm.weight"].float(), sd["qformer.layernorm.bias"].float(), self.arch.q_eps)
-            if getattr(self, "weight_int8", False):
+            if self.is_blip2:
+                sd = _with_qformer_x0(sd, self.arch.q_eps)
+            if self.weight_int8:
                 from .weights import blip2_int8_host_names, int8_roundtrip
                 sd = dict(sd)
                 for k in blip2_int8_host_names(sd):
                     sd[k] = int8_roundtrip(sd[k])
-        except KeyError as e:
-            raise N.CaptionerHipError(f"state dict lacks {e}: this architecture derives tensors from the checkpoint at load "
-                                      f"and needs the complete dict (keys with a 'model.' / 'module.' prefix? see "
-                                      f"weights.strip_wrapper_prefixes)") from e
         # the KV16 cross-attention cache has ONE scale per 64-wide head row: a checkpoint whose key / value heads carry outlier
         # dimensions is refused here (measured bound: weights.KV16_MAX_HEAD_SPREAD), never served with coarser logits
-        if not getattr(self, "_skip_kv16_guard", False) and hasattr(self.lib, "cap_cross_cache_kind") \
-                and not isinstance(self, TextEncoderEngine) and self.cross_cache_kind == "kv16":
+        if not self._skip_kv16_guard and self.cross_cache_kind == "kv16":
             from .weights import KV16_MAX_HEAD_SPREAD, cross_kv_head_spread
             spread = cross_kv_head_spread(sd)
             if spread > KV16_MAX_HEAD_SPREAD:
@@ -454,30 +590,7 @@ class CaptionerEngine:
                     f"magnitude; the split mode's KV16 cache (one scale per 64-wide head row) holds the 1e-3 logit bar up to "
                     f"{KV16_MAX_HEAD_SPREAD:.0f}x - create the engine with cross_cache='fp32' (captioner.cross_cache: fp32; the "
                     f"wrappers choose it themselves), or use dtype 'f32' / 'bf16'")
-        matched, unknown = 0, []
-        with torch.cuda.device(self.device):
-            s = _stream_ptr(self.device)
-            for name, t in sd.items():
-                t = t.detach()
-                if t.dtype != torch.float32:
-                    t = t.float()
-                t = t.contiguous()
-                shape = (C.c_int64 * max(t.dim(), 1))(*(t.shape if t.dim() else (1,)))
-                rc = self.lib.cap_load_weight(self._h, name.encode(), C.c_void_p(t.data_ptr()), int(t.is_cuda),
-                                              max(t.dim(), 1), shape, C.c_void_p(s))
-                if rc < 0:
-                    raise N.CaptionerHipError(f"cap_load_weight({name}): {N.last_error()}")
-                if rc == 0:
-                    matched += 1
-                else:
-                    unknown.append(name)
-            if len(sd) and not matched:
-                raise N.CaptionerHipError(f"none of the {len(sd)} tensors is one this architecture stores "
-                                          f"(first keys: {list(sd)[:3]}): wrong checkpoint or key prefix")
-            missing = self.lib.cap_finalize_weights(self._h)
-            if missing and strict:
-                raise N.CaptionerHipError(f"checkpoint incomplete: {N.last_error()}")
-        return {"matched": matched, "unknown": unknown}
+        return self._stream_weights(sd, strict)
 
     # ------------------------------------------------------------------------------------------ forward
     @property
@@ -503,42 +616,29 @@ class CaptionerEngine:
             raise ValueError("image_state takes frames, got an image state")
         B, nbytes = int(pixels.shape[0]), self.image_state_bytes
         out = torch.empty((B, nbytes), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            for b0 in range(0, B, self.max_batch):
-                nb = min(self.max_batch, B - b0)
-                N.check(self.lib.cap_encode_image_state(self._h, C.c_void_p(pixels[b0:b0 + nb].data_ptr()), fmt, nb,
-                                                        C.c_void_p(out[b0:b0 + nb].data_ptr()), C.c_void_p(_stream_ptr(self.device))),
-                        "cap_encode_image_state")
+        for b0 in range(0, B, self.max_batch):
+            nb = min(self.max_batch, B - b0)
+            self._call("cap_encode_image_state", pixels[b0:b0 + nb], fmt, nb, out[b0:b0 + nb])
         return out
 
     def _pixels(self, pixels: torch.Tensor):
-        if pixels.device != self.device:
-            pixels = pixels.to(self.device, non_blocking=True)
-        a = self.arch
-        # two dimensions: a state, not uint8 [B, S, S, 3] frames (the scorer engines that borrow this method take frames only)
-        if is_image_state(pixels) and isinstance(self, CaptionerEngine):
-            validate_image_state(pixels, self.image_state_bytes)
-            return pixels.contiguous(), N.CAP_PIX_IMAGE_STATE
-        if pixels.dtype == torch.uint8:
-            if pixels.dim() != 4 or pixels.shape[1:] != (a.image_size, a.image_size, 3):
-                raise ValueError(f"uint8 frames must be [B,{a.image_size},{a.image_size},3], got {tuple(pixels.shape)}")
-            fmt = N.CAP_PIX_U8_NHWC
-        else:
-            if pixels.dim() != 4 or pixels.shape[1:] != (3, a.image_size, a.image_size):
-                raise ValueError(f"float frames must be [B,3,{a.image_size},{a.image_size}], got {tuple(pixels.shape)}")
-            pixels = pixels.float()
-            fmt = N.CAP_PIX_F32_NCHW
-        return pixels.contiguous(), fmt
+        """Frames as every engine takes them, or an image state: two dimensions, not uint8 [B, S, S, 3] frames."""
+        if not is_image_state(pixels):
+            return super()._pixels(pixels)
+        validate_image_state(pixels, self.image_state_bytes)
+        return pixels.to(self.device, non_blocking=True).contiguous(), N.CAP_PIX_IMAGE_STATE
 
     def encode(self, pixels: torch.Tensor) -> torch.Tensor:
         pixels, fmt = self._pixels(pixels)
         B = pixels.shape[0]
         shape = (B, self.arch.pool_queries, self.arch.embed_dim) if self.is_coca else (B, self.arch.n_tokens, self.arch.v_hidden)   # BLIP / BLIP-2: ViT image_embeds
         out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(self.lib.cap_encode(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, C.c_void_p(out.data_ptr()),
-                                        C.c_void_p(_stream_ptr(self.device))), "cap_encode")
+        self._call("cap_encode", pixels, fmt, B, out)
         return out
+
+    def _decode_steps(self, max_length: int) -> int:
+        """Steps the decode loop runs for a max_length: BLIP-2's counts new tokens, BLIP's and CoCa's count BOS too."""
+        return max_length if self.is_blip2 else max_length - 1
 
     def generate(self, pixels: torch.Tensor, num_beams: int = 1, max_length: Optional[int] = None,
                  length_penalty: float = 1.0, output_logits: bool = False, num_beam_groups: Optional[int] = None,
@@ -590,7 +690,7 @@ class CaptionerEngine:
         ids = torch.empty((B, L), dtype=torch.int32, device=self.device)
         lens = torch.empty((B,), dtype=torch.int32, device=self.device)
         scores = torch.zeros((B,), dtype=torch.float32, device=self.device)
-        steps = L if getattr(self, "is_blip2", False) else L - 1
+        steps = self._decode_steps(L)
         logits = lps = scored = vmax = prompt_d = None
         if output_logits:
             # zeros, not empty: with early exit the steps after the last executed one are never written (callers see 0, not
@@ -641,7 +741,7 @@ class CaptionerEngine:
     def score_limit(self) -> int:
         """Longest caption (tokens, BOS included) `score` takes on this engine: BLIP's max_len counts BOS and one prefill pass covers 31
         positions; BLIP-2's max_len counts the tokens behind BOS, within the OPT decoder's positions."""
-        if getattr(self, "is_blip2", False):
+        if self.is_blip2:
             return min(self.max_len, self.arch.max_pos - self.arch.num_query_tokens - 1) + 1
         return min(self.max_len, SCORE_MAX_TOKENS)
 
@@ -668,7 +768,7 @@ class CaptionerEngine:
         if int(self.lib.cap_score_pass_captions(self._h, need + 1)) == 0:        # the handle's own capacity: nothing is uploaded
             raise ValueError(f"score: a caption of {need + 1} tokens is {need} decoder rows, more than this engine's workspace holds: "
                              f"no chunking fits it - create the engine with " +
-                             ("a larger max_batch" if getattr(self, "is_blip2", False) else f"max_score_rows >= {need}"))
+                             ("a larger max_batch" if self.is_blip2 else f"max_score_rows >= {need}"))
         pixels, fmt = self._pixels(pixels)
         N_, L = int(ids_h.shape[0]), int(ids_h.shape[1])
         dev = self.device
@@ -695,10 +795,7 @@ class CaptionerEngine:
                 top = torch.empty((n, Lc - 1), dtype=torch.float32, device=dev)
                 tid = torch.empty((n, Lc - 1), dtype=torch.int32, device=dev)
                 sc = torch.empty((n,), dtype=torch.int32, device=dev)
-                N.check(self.lib.cap_score_captions(self._h, C.c_void_p(px.data_ptr()), fmt, nb, C.c_void_p(ids_d.data_ptr()),
-                                                    C.c_void_p(lens_d.data_ptr()), Cn, Lc, C.c_void_p(tlp.data_ptr()),
-                                                    C.c_void_p(top.data_ptr()), C.c_void_p(tid.data_ptr()), C.c_void_p(sc.data_ptr()),
-                                                    C.c_void_p(stream.cuda_stream)), "cap_score_captions")
+                self._call("cap_score_captions", px, fmt, nb, ids_d, lens_d, Cn, Lc, tlp, top, tid, sc)
                 for t in (ids_d, lens_d):
                     t.record_stream(stream)
                 dst = rows if order is None else order[rows].to(dev)
@@ -724,8 +821,7 @@ class CaptionerEngine:
             raise ValueError(f"th must be finite, got {th}")
         Nr, V = int(v.shape[0]), int(v.shape[1])
         G = len(groups)
-        steps = self.max_len if getattr(self, "is_blip2", False) else self.max_len - 1
-        K = fusion_max_tokens(steps, th, V) if max_tokens is None else int(max_tokens)
+        K = fusion_max_tokens(self._decode_steps(self.max_len), th, V) if max_tokens is None else int(max_tokens)
         if K < 1:
             raise ValueError(f"max_tokens must be at least 1, got {K}")
         ids = torch.full((G, K), -1, dtype=torch.int32, device=v.device)
@@ -736,43 +832,14 @@ class CaptionerEngine:
         rows, off = vocab_group_csr(groups, Nr)
         rows_d, off_d = rows.to(v.device), off.to(v.device)
         acc_ld = int(v.stride(0)) if Nr > 1 else max(int(v.stride(0)), V)
-        with torch.cuda.device(v.device):
-            N.check(self.lib.cap_op_vocab_group_threshold(C.c_void_p(v.data_ptr()), acc_ld, V, Nr, C.c_void_p(rows_d.data_ptr()),
-                                                          int(rows.numel()), C.c_void_p(off_d.data_ptr()), G, C.c_float(th), K,
-                                                          C.c_void_p(ids.data_ptr()), C.c_void_p(probs.data_ptr()),
-                                                          C.c_void_p(counts.data_ptr()), C.c_void_p(_stream_ptr(v.device))),
-                    "cap_op_vocab_group_threshold")
+        _launch(self.lib, v.device, "cap_op_vocab_group_threshold", v, acc_ld, V, Nr, rows_d, int(rows.numel()), off_d, G,
+                C.c_float(th), K, ids, probs, counts)
         if max_tokens is not None:
             over = (counts > K).nonzero().flatten().tolist()
             if over:
                 raise N.CaptionerHipError(f"fuse_vocab_groups: group(s) {over[:8]} keep {counts[over[0]].item()} tokens above th = {th}, "
                                           f"more than max_tokens = {K}")
         return ids, probs, counts
-
-    # ------------------------------------------------------------------------------------------ profiling
-    def profile(self, on: bool) -> None:
-        N.check(self.lib.cap_profile_enable(self._h, int(on)), "cap_profile_enable")
-
-    def profile_report(self) -> dict:
-        buf = C.create_string_buffer(1 << 16)
-        N.check(self.lib.cap_profile_report(self._h, buf, len(buf)), "cap_profile_report")
-        return json.loads(buf.value.decode())
-
-    # ------------------------------------------------------------------------------------------ arena state (tests only)
-    def _fill_arena(self, pattern: int) -> int:
-        """Write the 32-bit pattern over every scratch buffer of this handle's arena on the current stream (index and kept buffers
-        and the weights are left alone); returns the bytes filled.  For tests/test_arena_state_gpu.py: no product code calls it."""
-        with torch.cuda.device(self.device):
-            n = int(self.lib.cap_debug_fill_arena(self._h, C.c_uint32(pattern & 0xFFFFFFFF), C.c_void_p(_stream_ptr(self.device))))
-        if n < 0:
-            raise N.CaptionerHipError(f"cap_debug_fill_arena: {N.last_error()}")
-        return n
-
-    def _arena_kinds(self) -> dict:
-        """{"arena_bytes", "scratch_bytes", "index_bytes", "kept_bytes", "index": [names], "kept": [names]} of this handle's arena."""
-        buf = C.create_string_buffer(1 << 12)
-        N.check(self.lib.cap_debug_arena_kinds(self._h, buf, len(buf)), "cap_debug_arena_kinds")
-        return json.loads(buf.value.decode())
 
 
 class EnginePool:
@@ -1040,42 +1107,21 @@ class EnginePool:
         return outs
 
 
-class TextEncoderEngine:
+class TextEncoderEngine(_Engine):
     """Sentence encoder replica (CAP_ARCH_MINILM handle): WordPiece ids + lengths -> L2-normalised mean-pooled embeddings.
     Replaces `SentenceTransformer("all-MiniLM-L6-v2").encode(...)` (reference goal_exploration.py:57,102;
     pseudolabeler.py:568,677); tokenisation stays on the host (captioner/sentence_encoder.py)."""
 
     def __init__(self, arch: MiniLMArch, dtype: str = "bf16", max_batch: int = 64, max_len: int = 32,
                  device: str | torch.device = "cuda:0", share_weights_with: "TextEncoderEngine | None" = None):
-        if not torch.cuda.is_available():
-            raise N.CaptionerHipError("TextEncoderEngine needs a GPU; there is no CPU fallback in the product path")
-        self.lib = N.load_library()
-        self.arch, self.dtype, self.device = arch, dtype, torch.device(device)
-        self.max_batch, self.max_len = max_batch, max_len
-        cfg = N.CapConfig()
-        cfg.struct_size = C.sizeof(N.CapConfig)
-        cfg.arch = 2
-        cfg.compute_dtype = _DTYPES[dtype]
+        super().__init__(arch, dtype, max_batch, max_len, device)
+        cfg = self._config(2)
+        # a lone encoder: its arch names the dimensions without the t_ of `_text_tower`
         cfg.t_hidden, cfg.t_layers, cfg.t_heads, cfg.t_ffn = arch.hidden, arch.layers, arch.heads, arch.ffn
         cfg.vocab, cfg.max_pos, cfg.t_eps = arch.vocab, arch.max_pos, arch.eps
-        cfg.max_batch, cfg.max_beams, cfg.max_len = max_batch, 1, max_len
-        self._h = C.c_void_p()
-        self.shares_weights = share_weights_with is not None
-        with torch.cuda.device(self.device):
-            if share_weights_with is not None:
-                N.check(self.lib.cap_create_shared(C.byref(cfg), share_weights_with._h, C.byref(self._h)), "cap_create_shared")
-            else:
-                N.check(self.lib.cap_create(C.byref(cfg), C.byref(self._h)), "cap_create")
+        self._create(cfg, share_weights_with)
 
-    close = CaptionerEngine.close
-    __del__ = CaptionerEngine.__del__
-    device_bytes = CaptionerEngine.device_bytes
-    profile = CaptionerEngine.profile
-    profile_report = CaptionerEngine.profile_report
-    _fill_arena = CaptionerEngine._fill_arena
-    _arena_kinds = CaptionerEngine._arena_kinds
-
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> None:
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> Dict[str, object]:
         """HF BertModel names; a leading `0.auto_model.` / `bert.` prefix (sentence-transformers / BertFor* saves) is dropped."""
         clean = {}
         for k, v in sd.items():
@@ -1083,83 +1129,38 @@ class TextEncoderEngine:
                 if k.startswith(pre):
                     k = k[len(pre):]
             clean[k] = v
-        self.is_coca = False
-        CaptionerEngine.load_state_dict(self, clean, strict)
+        return self._stream_weights(clean, strict)
 
     def embed(self, ids: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
         """ids int [B, L] (pad anywhere after `lens[b]` tokens), lens int [B] -> fp32 [B, hidden] on the device."""
-        if ids.dim() != 2 or lens.shape != (ids.shape[0],):
-            raise ValueError(f"ids must be [B, L] and lens [B], got {tuple(ids.shape)} / {tuple(lens.shape)}")
-        B, L = ids.shape
-        if not ids.is_cuda and not lens.is_cuda:      # host tensors: validate here for free; device tensors are clamped by the
-            if int(lens.max()) > L or int(lens.min()) < 1:                      # kernels (no host synchronisation per call)
-                raise ValueError("lens must be within 1..L")
-            if int(ids.max()) >= self.arch.vocab or int(ids.min()) < 0:
-                raise ValueError("token id outside the vocabulary")
-        ids = ids.to(self.device, torch.int32).contiguous()
-        lens = lens.to(self.device, torch.int32).contiguous()
+        ids, lens, B, L = self._ids_lens(ids, lens)
         out = torch.empty((B, self.arch.hidden), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(self.lib.cap_embed_text(self._h, C.c_void_p(ids.data_ptr()), C.c_void_p(lens.data_ptr()), B, L,
-                                            C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(self.device))), "cap_embed_text")
+        self._call("cap_embed_text", ids, lens, B, L, out)
         return out
 
 
-class ClipEngine:
+class ClipEngine(_Engine):
     """CLIP scorer replica (CAP_ARCH_CLIP handle): both towers and the image-caption logits of HF `CLIPModel`, as the
     reference's `--method clip` uses it (experimenting_env/captioner/pseudocaptioner.py:39-46, :352-357).  Embeddings come
     back L2-normalised, fp32 [B, projection_dim]; tokenisation stays on the host (captioner/clip_scorer.py)."""
 
-    _skip_kv16_guard = True      # no cross-attention cache
-
     def __init__(self, arch: ClipArch, dtype: str = "f32s", max_batch: int = 256, max_len: Optional[int] = None,
                  device: str | torch.device = "cuda:0", share_weights_with: "ClipEngine | None" = None):
-        if not torch.cuda.is_available():
-            raise N.CaptionerHipError("ClipEngine needs a GPU; there is no CPU fallback in the product path")
-        self.lib = N.load_library()
-        self.arch, self.dtype, self.device = arch, dtype, torch.device(device)
-        self.max_batch, self.max_len = max_batch, max_len or arch.max_pos
-        cfg = N.CapConfig()
-        cfg.struct_size = C.sizeof(N.CapConfig)
-        cfg.arch = N.CAP_ARCH_CLIP
-        cfg.compute_dtype = _DTYPES[dtype]
-        cfg.image_size, cfg.patch_size = arch.image_size, arch.patch_size
-        cfg.v_hidden, cfg.v_layers, cfg.v_heads, cfg.v_mlp, cfg.v_eps = arch.v_hidden, arch.v_layers, arch.v_heads, arch.v_mlp, arch.eps
-        cfg.t_hidden, cfg.t_layers, cfg.t_heads, cfg.t_ffn = arch.t_hidden, arch.t_layers, arch.t_heads, arch.t_ffn
-        cfg.vocab, cfg.max_pos, cfg.t_eps = arch.vocab, arch.max_pos, arch.eps
-        cfg.bos, cfg.eos, cfg.pad = arch.bos_token_id, arch.eos_token_id, arch.pad_token_id
+        super().__init__(arch, dtype, max_batch, max_len or arch.max_pos, device)
+        cfg = self._config(N.CAP_ARCH_CLIP)
+        self._vision_tower(cfg, arch.eps)
+        self._text_tower(cfg, arch.max_pos, arch.eps, (arch.bos_token_id, arch.eos_token_id, arch.pad_token_id))
         cfg.embed_dim = arch.projection_dim
         cfg.hidden_act = N.CAP_ACT_GELU if arch.hidden_act == "gelu" else N.CAP_ACT_QUICK_GELU
-        cfg.max_batch, cfg.max_beams, cfg.max_len = max_batch, 1, self.max_len
-        for i in range(3):
-            cfg.pix_mean[i] = OPENAI_CLIP_MEAN[i]
-            cfg.pix_std[i] = OPENAI_CLIP_STD[i]
-        self._h = C.c_void_p()
-        self.shares_weights = share_weights_with is not None
         self.logit_scale = share_weights_with.logit_scale if share_weights_with is not None else None
-        with torch.cuda.device(self.device):
-            if share_weights_with is not None:
-                N.check(self.lib.cap_create_shared(C.byref(cfg), share_weights_with._h, C.byref(self._h)), "cap_create_shared")
-            else:
-                N.check(self.lib.cap_create(C.byref(cfg), C.byref(self._h)), "cap_create")
-
-    close = CaptionerEngine.close
-    __del__ = CaptionerEngine.__del__
-    device_bytes = CaptionerEngine.device_bytes
-    saturations = CaptionerEngine.saturations
-    profile = CaptionerEngine.profile
-    profile_report = CaptionerEngine.profile_report
-    _fill_arena = CaptionerEngine._fill_arena
-    _arena_kinds = CaptionerEngine._arena_kinds
-    _pixels = CaptionerEngine._pixels
+        self._create(cfg, share_weights_with)
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> Dict[str, object]:
         """HF `CLIPModel` names (wrapper prefixes dropped, `*.position_ids` buffers and the absent patch bias ignored)."""
         from .weights import strip_wrapper_prefixes
         sd = {k: v for k, v in strip_wrapper_prefixes(sd).items()
               if not k.endswith("position_ids") and k != "vision_model.embeddings.patch_embedding.bias"}
-        self.is_coca = False
-        rep = CaptionerEngine.load_state_dict(self, sd, strict)
+        rep = self._stream_weights(sd, strict)
         v = C.c_float()
         with torch.cuda.device(self.device):
             if self.lib.cap_clip_logit_scale(self._h, C.byref(v)) == 0:
@@ -1173,32 +1174,20 @@ class ClipEngine:
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"batch of {B} images outside 1..{self.max_batch} (the engine's max_batch)")
         out = torch.empty((B, self.arch.projection_dim), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(self.lib.cap_clip_embed_images(self._h, C.c_void_p(pixels.data_ptr()), fmt, B, C.c_void_p(out.data_ptr()),
-                                                   C.c_void_p(_stream_ptr(self.device))), "cap_clip_embed_images")
+        self._call("cap_clip_embed_images", pixels, fmt, B, out)
         return out
 
     def embed_text(self, ids: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
         """ids int [B, L] (right padded; anything after the caption), lens int [B] = tokens up to and including the pooled EOT
         -> fp32 [B, projection_dim] (device), L2-normalised."""
-        if ids.dim() != 2 or lens.shape != (ids.shape[0],):
-            raise ValueError(f"ids must be [B, L] and lens [B], got {tuple(ids.shape)} / {tuple(lens.shape)}")
-        B, L = ids.shape
+        B, L = _ids_shape(ids, lens)
         if not 1 <= L <= self.max_len:
             raise ValueError(f"{L} tokens per caption outside 1..{self.max_len} (the engine's max_len)")
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"batch of {B} captions outside 1..{self.max_batch} (the engine's max_batch)")
-        if not ids.is_cuda and not lens.is_cuda:      # host tensors: validated here; device tensors are clamped by the kernels
-            if int(lens.max()) > L or int(lens.min()) < 1:
-                raise ValueError("lens must be within 1..L")
-            if int(ids.max()) >= self.arch.vocab or int(ids.min()) < 0:
-                raise ValueError("token id outside the vocabulary")
-        ids = ids.to(self.device, torch.int32).contiguous()
-        lens = lens.to(self.device, torch.int32).contiguous()
+        ids, lens, B, L = self._ids_lens(ids, lens)
         out = torch.empty((B, self.arch.projection_dim), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(self.lib.cap_clip_embed_text(self._h, C.c_void_p(ids.data_ptr()), C.c_void_p(lens.data_ptr()), B, L,
-                                                 C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(self.device))), "cap_clip_embed_text")
+        self._call("cap_clip_embed_text", ids, lens, B, L, out)
         return out
 
     def logits(self, img: torch.Tensor, txt: torch.Tensor, paired: bool = True) -> torch.Tensor:
@@ -1215,80 +1204,36 @@ class ClipEngine:
         txt = txt.to(self.device, torch.float32).contiguous()
         Ni, Nt = img.shape[0], txt.shape[0]
         out = torch.empty((Ni,) if paired else (Ni, Nt), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(self.lib.cap_clip_logits(C.c_void_p(img.data_ptr()), C.c_void_p(txt.data_ptr()), Ni, Nt, int(bool(paired)),
-                                             C.c_float(self.logit_scale), C.c_void_p(out.data_ptr()), P,
-                                             C.c_void_p(_stream_ptr(self.device))), "cap_clip_logits")
+        _launch(self.lib, self.device, "cap_clip_logits", img, txt, Ni, Nt, int(bool(paired)), C.c_float(self.logit_scale), out, P)
         return out
 
 
-class Blip2ItmEngine:
+class Blip2ItmEngine(_Engine):
     """BLIP-2 image-text scorer replica (CAP_ARCH_BLIP2_ITM handle): HF `Blip2ForImageTextRetrieval`'s two scores for batches of
     (image, caption) pairs, as the reference's `--method blip2_itm | blip2_itc` computes them one pair per call
     (experimenting_env/captioner/pseudocaptioner.py:193-308).  `encode_images` leaves an image batch's tokens and cross-attention
     K/V resident in the handle; `itc_image_features` and `itm` then read them without running the ViT-g again.  Tokenisation stays
     on the host (captioner/blip2_itm_scorer.py)."""
 
-    _skip_kv16_guard = True      # the Q-Former's cross K/V are kept in the compute type, never as KV16
-
     def __init__(self, arch: Blip2ItmArch, dtype: str = "f32s", max_batch: int = 256, max_len: Optional[int] = None,
                  device: str | torch.device = "cuda:0", share_weights_with: "Blip2ItmEngine | None" = None):
-        if not torch.cuda.is_available():
-            raise N.CaptionerHipError("Blip2ItmEngine needs a GPU; there is no CPU fallback in the product path")
-        self.lib = N.load_library()
-        self.arch, self.dtype, self.device = arch, dtype, torch.device(device)
-        self.max_batch, self.max_len = max_batch, max_len or arch.max_text_len
-        cfg = N.CapConfig()
-        cfg.struct_size = C.sizeof(N.CapConfig)
-        cfg.arch = N.CAP_ARCH_BLIP2_ITM
-        cfg.compute_dtype = _DTYPES[dtype]
-        cfg.image_size, cfg.patch_size = arch.image_size, arch.patch_size
-        cfg.v_hidden, cfg.v_layers, cfg.v_heads, cfg.v_mlp, cfg.v_eps = arch.v_hidden, arch.v_layers, arch.v_heads, arch.v_mlp, arch.v_eps
-        cfg.q_hidden, cfg.q_layers, cfg.q_heads, cfg.q_ffn = arch.q_hidden, arch.q_layers, arch.q_heads, arch.q_ffn
-        cfg.q_cross_freq, cfg.num_query_tokens, cfg.q_eps = arch.q_cross_freq, arch.num_query_tokens, arch.q_eps
-        cfg.vocab, cfg.max_pos, cfg.pad = arch.vocab, arch.max_pos, arch.pad
+        super().__init__(arch, dtype, max_batch, max_len or arch.max_text_len, device)
+        cfg = self._config(N.CAP_ARCH_BLIP2_ITM)
+        self._vision_tower(cfg, arch.v_eps)
+        self._qformer(cfg)
+        cfg.vocab, cfg.max_pos, cfg.pad = arch.vocab, arch.max_pos, arch.pad         # the text side is the Q-Former's: no tower of its own
         cfg.embed_dim = arch.projection_dim
-        cfg.max_batch, cfg.max_beams, cfg.max_len = max_batch, 1, self.max_len
-        for i in range(3):
-            cfg.pix_mean[i] = OPENAI_CLIP_MEAN[i]
-            cfg.pix_std[i] = OPENAI_CLIP_STD[i]
-        self._h = C.c_void_p()
-        self.shares_weights = share_weights_with is not None
         self.resident = 0            # images of the last encode_images
-        with torch.cuda.device(self.device):
-            if share_weights_with is not None:
-                N.check(self.lib.cap_create_shared(C.byref(cfg), share_weights_with._h, C.byref(self._h)), "cap_create_shared")
-            else:
-                N.check(self.lib.cap_create(C.byref(cfg), C.byref(self._h)), "cap_create")
-
-    close = CaptionerEngine.close
-    __del__ = CaptionerEngine.__del__
-    device_bytes = CaptionerEngine.device_bytes
-    saturations = CaptionerEngine.saturations
-    profile = CaptionerEngine.profile
-    profile_report = CaptionerEngine.profile_report
-    _fill_arena = CaptionerEngine._fill_arena
-    _arena_kinds = CaptionerEngine._arena_kinds
-    _pixels = CaptionerEngine._pixels
+        self._create(cfg, share_weights_with)
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> Dict[str, object]:
         """HF `Blip2ForImageTextRetrieval` names (wrapper prefixes dropped, `*.position_ids` buffers ignored);
         `derived.qformer_x0` = qformer.layernorm(query_tokens) is computed here."""
         from .weights import strip_wrapper_prefixes
         sd = {k: v for k, v in strip_wrapper_prefixes(sd).items() if not k.endswith("position_ids")}
-        self.is_coca, self.is_blip2 = False, True
-        return CaptionerEngine.load_state_dict(self, sd, strict)
-
-    def _text(self, ids: torch.Tensor, lens: torch.Tensor):
-        if ids.dim() != 2 or lens.shape != (ids.shape[0],):
-            raise ValueError(f"ids must be [B, L] and lens [B], got {tuple(ids.shape)} / {tuple(lens.shape)}")
-        B, L = ids.shape
-        if not ids.is_cuda and not lens.is_cuda and B and L:      # host tensors: validated here; device tensors are clamped by the kernels
-            if int(lens.max()) > L or int(lens.min()) < 1:
-                raise ValueError("lens must be within 1..L")
-            if int(ids.max()) >= self.arch.vocab or int(ids.min()) < 0:
-                raise ValueError("token id outside the vocabulary")
-        return ids.to(self.device, torch.int32).contiguous(), lens.to(self.device, torch.int32).contiguous(), B, L
+        with _deriving_tensors():
+            sd = _with_qformer_x0(sd, self.arch.q_eps)
+        return self._stream_weights(sd, strict)
 
     def encode_images(self, pixels: torch.Tensor) -> int:
         """uint8 [B, S, S, 3] RGB or normalised fp32 [B, 3, S, S]: runs the ViT-g and the cross K/V projections; the batch stays
@@ -1296,9 +1241,7 @@ class Blip2ItmEngine:
         pixels, fmt = self._pixels(pixels)
         B = pixels.shape[0]
         self.resident = 0
-        with torch.cuda.device(self.device):
-            N.check(self.lib.cap_blip2_itm_encode_images(self._h, C.c_void_p(pixels.data_ptr()), fmt, B,
-                                                         C.c_void_p(_stream_ptr(self.device))), "cap_blip2_itm_encode_images")
+        self._call("cap_blip2_itm_encode_images", pixels, fmt, B)
         self.resident = B
         return B
 
@@ -1306,19 +1249,14 @@ class Blip2ItmEngine:
         """The resident images -> fp32 [B, num_query_tokens, projection_dim] (device), each query row L2-normalised."""
         B = self.resident
         out = torch.empty((B, self.arch.num_query_tokens, self.arch.projection_dim), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(self.lib.cap_blip2_itc_image_features(self._h, B, C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(self.device))),
-                    "cap_blip2_itc_image_features")
+        self._call("cap_blip2_itc_image_features", B, out)
         return out
 
     def itc_text_features(self, ids: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
         """ids int [B, L] (right padded; anything after the caption), lens int [B] -> fp32 [B, projection_dim] (device), L2-normalised."""
-        ids, lens, B, L = self._text(ids, lens)
+        ids, lens, B, L = self._ids_lens(ids, lens)
         out = torch.empty((B, self.arch.projection_dim), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(self.lib.cap_blip2_itc_text_features(self._h, C.c_void_p(ids.data_ptr()), C.c_void_p(lens.data_ptr()), B, L,
-                                                         C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(self.device))),
-                    "cap_blip2_itc_text_features")
+        self._call("cap_blip2_itc_text_features", ids, lens, B, L, out)
         return out
 
     def itc_scores(self, img: torch.Tensor, txt: torch.Tensor, paired: bool = True) -> torch.Tensor:
@@ -1332,19 +1270,13 @@ class Blip2ItmEngine:
         txt = txt.to(self.device, torch.float32).contiguous()
         Ni, Nt = img.shape[0], txt.shape[0]
         out = torch.empty((Ni,) if paired else (Ni, Nt), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(self.lib.cap_blip2_itc_scores(C.c_void_p(img.data_ptr()), C.c_void_p(txt.data_ptr()), Ni, Nt, int(bool(paired)),
-                                                  C.c_void_p(out.data_ptr()), nq, P, C.c_void_p(_stream_ptr(self.device))),
-                    "cap_blip2_itc_scores")
+        _launch(self.lib, self.device, "cap_blip2_itc_scores", img, txt, Ni, Nt, int(bool(paired)), out, nq, P)
         return out
 
     def itm(self, ids: torch.Tensor, lens: torch.Tensor):
         """Resident image b against caption b -> (logits fp32 [B, 2], probability of a match fp32 [B]) on the device."""
-        ids, lens, B, L = self._text(ids, lens)
+        ids, lens, B, L = self._ids_lens(ids, lens)
         logits = torch.empty((B, 2), dtype=torch.float32, device=self.device)
         prob = torch.empty((B,), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            N.check(self.lib.cap_blip2_itm_logits(self._h, C.c_void_p(ids.data_ptr()), C.c_void_p(lens.data_ptr()), B, L,
-                                                  C.c_void_p(logits.data_ptr()), C.c_void_p(prob.data_ptr()),
-                                                  C.c_void_p(_stream_ptr(self.device))), "cap_blip2_itm_logits")
+        self._call("cap_blip2_itm_logits", ids, lens, B, L, logits, prob)
         return logits, prob

@@ -260,3 +260,32 @@ def resize_u8_list(images: Sequence[np.ndarray], size: int, device: str | torch.
             raise ValueError(f"image {i} must be uint8 [H, W, 3], got {a.dtype} {a.shape}")
     return crop_resize_u8_frames(images, [[(0, 0, a.shape[1], a.shape[0])] for a in images], size, device=device, center_crop=center_crop,
                                  geometry=geometry)
+
+
+def pixel_batches(images, size: int, batch_size: int, device: str | torch.device = "cuda:0", **resize):
+    """What the scorer wrappers (captioner/clip_scorer.py, blip2_itm_scorer.py) take as images -> batches of at most `batch_size`
+    frames for their engine.  Normalised tensors [n, 3, size, size] (or one [3, size, size]) and uint8 [n, size, size, 3] tensors
+    already at the tower's size go through as they are, in slices; PIL images and uint8 [H, W, 3] RGB arrays go through
+    `resize_u8_list(..., size, device, **resize)`, one call per batch."""
+    if isinstance(images, torch.Tensor) and (images.dtype != torch.uint8 or (images.dim() == 4 and tuple(images.shape[1:]) == (size, size, 3))):
+        x = images if images.dim() == 4 else images[None]
+        for i in range(0, x.shape[0], batch_size):
+            yield x[i:i + batch_size]
+        return
+    arrs = []
+    for im in images:
+        a = np.asarray(im.convert("RGB")) if hasattr(im, "convert") else np.asarray(im.cpu() if isinstance(im, torch.Tensor) else im)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"images must be PIL, uint8 [H, W, 3] RGB or normalised [n, 3, {size}, {size}] tensors, got {a.dtype} {a.shape}")
+        arrs.append(np.ascontiguousarray(a))
+    for i in range(0, len(arrs), batch_size):
+        yield resize_u8_list(arrs[i:i + batch_size], size, device=device, **resize)
+
+
+def pad_rows(rows: Sequence[Sequence[int]], pad: int = 0):
+    """Id rows -> (ids int32 [n, L], lens int32 [n]) padded to the longest row of THIS batch."""
+    L = max(len(r) for r in rows)
+    ids = torch.full((len(rows), L), pad, dtype=torch.int32)
+    for b, r in enumerate(rows):
+        ids[b, :len(r)] = torch.tensor(r, dtype=torch.int32)
+    return ids, torch.tensor([len(r) for r in rows], dtype=torch.int32)

@@ -144,6 +144,26 @@ def test_tokenisation_truncates_at_32_and_pads_per_batch(tmp_path):
         tokenize_captions(None, [[]], 32)
 
 
+def test_pixel_batches_slice_tensors_that_need_no_resize_and_refuse_other_arrays():
+    """The shared `pixel_batches` on inputs that need no device: normalised float tensors and uint8 frames already at the tower's
+    size go through as slices of at most batch_size, in order; a lone [3, S, S] image is a batch of one; anything that is not uint8
+    [H, W, 3] is refused by name before any resize."""
+    from embodied_captioning_amd.preprocess import pixel_batches
+    S = 8
+    for x in (torch.randn(7, 3, S, S), torch.randint(0, 256, (7, S, S, 3), dtype=torch.uint8)):
+        got = list(pixel_batches(x, S, 3, "cpu", center_crop=False))
+        assert [b.shape[0] for b in got] == [3, 3, 1] and torch.equal(torch.cat(got), x)
+        assert all(b.data_ptr() == x[i * 3:].data_ptr() for i, b in enumerate(got))       # views, not copies
+        assert len(list(pixel_batches(x, S, 7, "cpu", center_crop=True, geometry="hf"))) == 1
+    one = torch.randn(3, S, S)
+    got = list(pixel_batches(one, S, 4, "cpu"))
+    assert len(got) == 1 and got[0].shape == (1, 3, S, S) and torch.equal(got[0][0], one)
+    assert list(pixel_batches(torch.zeros(0, 3, S, S), S, 4, "cpu")) == [] and list(pixel_batches([], S, 4, "cpu")) == []
+    for bad in ([np.zeros((5, 6, 3), np.float32)], [np.zeros((5, 6), np.uint8)], [np.zeros((5, 6, 4), np.uint8)]):
+        with pytest.raises(ValueError, match="images must be PIL, uint8"):
+            list(pixel_batches(bad, S, 4, "cpu"))
+
+
 class _StubScorer:
     """Score = the image's mean red value / 100 (the crop's BGR -> RGB swap shows)."""
 

@@ -105,6 +105,35 @@ def test_tokenisation_and_pooled_rule_match_hf(tmp_path, legacy):
     assert torch.equal(out.pooler_output, out.last_hidden_state[torch.arange(len(caps)), torch.tensor(pos)])
 
 
+def test_text_batches_are_padded_per_chunk_and_lens_end_at_the_pooled_row():
+    """`get_text_features` through a stub engine: rows go in chunks of batch_size, each padded (shared `pad_rows`) to ITS longest row
+    with the pad id, and lens are pooled position + 1 - not the row length, which a row with ids behind its <eot> shows."""
+    from embodied_captioning_amd.captioner.clip_scorer import ClipScorer
+    from embodied_captioning_amd.config import ClipArch
+
+    class Engine:
+        calls = []
+
+        def embed_text(self, ids, lens):
+            self.calls.append((ids.clone(), lens.clone()))
+            return torch.zeros((ids.shape[0], 4))
+
+    arch = ClipArch.tiny()
+    sot, eot, pad = arch.bos_token_id, arch.eos_token_id, arch.pad_token_id
+    assert eot != 2                                    # not the legacy argmax rule: the FIRST <eot> pools
+    rows = [[sot, 5, 6, eot], [sot, 7, eot, 9, 9, 9], [sot, eot], [sot, 5, 6, 7, 8, eot], [sot, 5, eot]]
+    sc = object.__new__(ClipScorer)
+    sc.arch, sc.tokenizer, sc.batch_size, sc.device, sc.engine = arch, None, 2, torch.device("cpu"), Engine()
+    assert sc.get_text_features(rows).shape == (5, 4)
+    assert [tuple(i.shape) for i, _ in Engine.calls] == [(2, 6), (2, 6), (1, 3)]
+    assert [ln.tolist() for _, ln in Engine.calls] == [[4, 3], [2, 6], [3]]
+    for (ids, lens), chunk in zip(Engine.calls, (rows[0:2], rows[2:4], rows[4:5])):
+        assert ids.dtype == lens.dtype == torch.int32
+        for b, r in enumerate(chunk):
+            assert ids[b].tolist() == r + [pad] * (ids.shape[1] - len(r))
+    assert sc.get_text_features([]).shape == (0, arch.projection_dim)
+
+
 def test_hf_shortest_edge_geometry_matches_clip_image_processor():
     transformers = pytest.importorskip("transformers")
     from PIL import Image
