@@ -125,6 +125,15 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "cap_op_beam_step_banned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "cap_set_repeat_controls": (C.c_int, [C.c_void_p, C.c_float, C.c_int]),
+    "cap_repeat_controls": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "cap_set_image_token": (C.c_int, [C.c_void_p, C.c_int]),
+    "cap_op_select_processed": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int,
+                                          C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "cap_op_beam_step_processed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                             C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_void_p]),
     "cap_set_decode_path": (C.c_int, [C.c_void_p, C.c_int]),
     "cap_last_decode_path": (C.c_int, [C.c_void_p]),
     "cap_set_row_compaction": (C.c_int, [C.c_void_p, C.c_int]),

@@ -6,11 +6,16 @@ and HF ``GenerationMixin.generate`` behind ``blip2.py:26``.  What the library ru
 "top_k"`` with ``top_k=1`` - what the reference's wrapper calls, ``coca.py:29``; MinLength and forced EOS included) and beam search
 (HF v5 semantics for BLIP / BLIP-2, the reference's ``_generate_beamsearch`` incl. beam groups for CoCa).  Everything below is
 deterministic arg-max / beam arithmetic (``captioner.num_beams`` and, for BLIP and BLIP-2, ``captioner.length_penalty`` are the config keys;
-BLIP-2 searches with 1 to 8 beams like the other families and computes the prompt once per image, not once per beam); sampling, temperature, nucleus / top-k filtering and repetition penalties are not built.
+BLIP-2 searches with 1 to 8 beams like the other families and computes the prompt once per image, not once per beam); sampling, temperature and nucleus / top-k filtering are not built.
 ``bad_words_ids`` (HF ``NoBadWordsLogitsProcessor``) IS built, for BLIP and BLIP-2: it is engine state (``CaptionerEngine.set_bad_words``, the
 ``captioner.bad_words_ids`` / ``captioner.bad_words`` config keys) applied inside the token selection kernels, and ``generate(bad_words_ids=X)``
 is accepted when X equals the set in force; it is therefore no longer judged here.  CoCa refuses it by name (``CoCa.generate`` has no such
 option); ``sequence_bias`` with finite biases, ``force_words_ids`` and constraints stay unbuilt.
+``repetition_penalty`` and ``no_repeat_ngram_size`` (HF ``RepetitionPenaltyLogitsProcessor`` / ``NoRepeatNGramLogitsProcessor``) ARE built for
+BLIP and BLIP-2, as engine state too (``CaptionerEngine.set_repeat_controls``, the ``captioner.repetition_penalty`` /
+``captioner.no_repeat_ngram_size`` config keys): ``CaptionerEngine.generate`` takes the two keys out before this module sees them and accepts
+them when they equal the values in force.  This module's own judgement is unchanged - whoever still hands it the keys (CoCa) gets them
+accepted at their neutral values only.
 Scoring a GIVEN caption (teacher forcing: ``CaptionerEngine.score`` / ``BLIP.score_captions`` / ``BLIP2.score_captions``) is a separate entry point, not a generation option or a prompt: plain logits, no EOS mask or MinLength.
 """
 from __future__ import annotations

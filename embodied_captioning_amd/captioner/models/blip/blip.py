@@ -103,6 +103,10 @@ class BLIP(CaptioningPredictor):
         # validated here, before an engine exists
         from ...bad_words import resolve_bad_words
         self.bad_words_ids = resolve_bad_words(cfg, self.tokenizer, self.arch)
+        # captioner.repetition_penalty / captioner.no_repeat_ngram_size: HF generate's two repetition controls for every caption
+        # (engine.set_repeat_controls); validated here, before an engine exists
+        from ...repeat_controls import resolve_repeat_controls
+        self.repetition_penalty, self.no_repeat_ngram_size = resolve_repeat_controls(cfg, self.arch, self.max_length)
         if getattr(cfg, "checkpoint_name", None):
             over = load_state_dict_file(cfg.checkpoint_name)
             for dst, src in BLIP_TIED.items():
@@ -149,6 +153,10 @@ class BLIP(CaptioningPredictor):
             self.engine.set_bad_words(self.bad_words_ids)
             if self.pool is not None:
                 self.pool.set_bad_words(self.bad_words_ids)
+        if self.repetition_penalty != 1.0 or self.no_repeat_ngram_size:
+            self.engine.set_repeat_controls(self.repetition_penalty, self.no_repeat_ngram_size)
+            if self.pool is not None:
+                self.pool.set_repeat_controls(self.repetition_penalty, self.no_repeat_ngram_size)
 
     @staticmethod
     def _length_penalty(cfg) -> float:

@@ -152,6 +152,9 @@ class BLIP2(BLIP):
         # the reference passes no length: HF then generates 20 new tokens; the optional config key `max_new_tokens` (HF's
         # name) overrides that.  The plugin's `max_length` key is BLIP's / CoCa's TOTAL length and is not read here.
         self.max_length = int(getattr(cfg, "max_new_tokens", 0) or self.arch.max_new_tokens)
+        # captioner.repetition_penalty / captioner.no_repeat_ngram_size (as for BLIP): validated before an engine exists
+        from ...repeat_controls import resolve_repeat_controls
+        self.repetition_penalty, self.no_repeat_ngram_size = resolve_repeat_controls(cfg, self.arch, self.max_length)
         self.engine = CaptionerEngine(self.arch, dtype=dtype, max_batch=self.batch_size, max_beams=self.num_beams, max_len=self.max_length,
                                       device=self._device, cross_cache=getattr(cfg, "cross_cache", None) or "auto",
                                       weight_int8=self.load_in_8bit)
@@ -191,6 +194,10 @@ class BLIP2(BLIP):
             self.engine.set_bad_words(self.bad_words_ids)
             if self.pool is not None:
                 self.pool.set_bad_words(self.bad_words_ids)
+        if self.repetition_penalty != 1.0 or self.no_repeat_ngram_size:
+            self.engine.set_repeat_controls(self.repetition_penalty, self.no_repeat_ngram_size)
+            if self.pool is not None:
+                self.pool.set_repeat_controls(self.repetition_penalty, self.no_repeat_ngram_size)
 
     def decode(self, ids: Sequence[int]) -> str:
         if not hasattr(self.arch, "num_query_tokens"):

@@ -13,7 +13,9 @@ group), tokenizer_dir (directory holding the CLIP BPE vocabulary - vocab.json / 
 when it is not next to the checkpoint and open_clip is not installed); generation_type / top_k / top_p / temperature /
 repetition_penalty (the reference model's other `generate` options, coca_model.py:205-224): accepted at their neutral values
 ("top_k" with top_k=1 = greedy, "beam_search"), rejected by name otherwise - sampling is not implemented.  bad_words_ids / bad_words / bad_words_mode (BLIP, BLIP-2): banned token
-sequences / words of the decode loops, HF's `generate(bad_words_ids=)`."""
+sequences / words of the decode loops, HF's `generate(bad_words_ids=)`.  repetition_penalty / no_repeat_ngram_size (BLIP, BLIP-2): HF's two
+repetition controls, applied inside the token selection kernels (CaptionerEngine.set_repeat_controls); CoCa takes repetition_penalty at 1.0
+only and refuses no_repeat_ngram_size by name."""
 
 
 class Configuration:
@@ -29,7 +31,7 @@ class CaptionerField:
                  generation_type=None, top_k=None, top_p=None, temperature=None, repetition_penalty=None,
                  load_in_8bit=None, load_in_4bit=None, torch_dtype=None, cross_cache=None, strict_range=False,
                  coalesce_rows=None, device_resize=None, prompt=None, prompt_ids=None, max_prompt=None, length_penalty=None,
-                 max_score_rows=None, bad_words_ids=None, bad_words=None, bad_words_mode=None):
+                 max_score_rows=None, bad_words_ids=None, bad_words=None, bad_words_mode=None, no_repeat_ngram_size=None):
         self.arch_name = arch_name
         self.model_name = model_name
         self.checkpoint_name = checkpoint_name
@@ -84,3 +86,6 @@ class CaptionerField:
         self.bad_words_ids = bad_words_ids
         self.bad_words = bad_words
         self.bad_words_mode = bad_words_mode
+        # BLIP / BLIP-2: HF `generate(no_repeat_ngram_size=)` on the device, with `repetition_penalty` above (captioner/
+        # repeat_controls.py); None / 0 = off.  CoCa refuses the key by name (and any repetition_penalty but 1.0, as it always did).
+        self.no_repeat_ngram_size = no_repeat_ngram_size

@@ -13,6 +13,7 @@
 //   beam_rows_kernel   one block per (item, beam) row: log-softmax statistics + the row's top-2K candidates
 //   beam_merge_kernel  one 64-thread block per item: merge K*2K candidates, update running beams / finished pool /
 //                      ancestry (ranking sorts in LDS); the global "loop still running" flag is an atomic OR.
+#include <cmath>
 #include "ops.h"
 #include "ban.h"
 
@@ -77,13 +78,40 @@ __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { retur
 // BAN (the *_banned kernels below; ops.h, BanSet): the block first builds the row's ban bitmap `bm` (LDS, ban_words(V) words) from the
 // row's LOGICAL history run_seq[par][row][0 .. cur_len) - the beam's tokens after every re-ordering, not what the physical row wrote -
 // and a banned candidate's value is -inf.  The statistics passes never look at it: HF takes the log-softmax of the raw row, then bans.
-template <bool BAN>
+// MODE: ROWS_PLAIN, ROWS_BANNED, or ROWS_PROCESSED (ops.h, RepeatCtl): the bitmap also takes the n-gram bans of HF's context of the row
+// (RowContext: the logical history behind its virtual prefix), and with a penalty a second bitmap `seen` sits behind it: the
+// log-prob of a context token is multiplied by the penalty (log-probs are <= 0) before the bans and the running score.
+enum { ROWS_PLAIN = 0, ROWS_BANNED = 1, ROWS_PROCESSED = 2 };
+template <int MODE>
+__device__ __forceinline__ void beam_rows_fill(unsigned* bm, const unsigned*& seen, int V, const BanSet& ban, const RepeatCtl& ctl,
+                                               const int* hist, int cur_len, int tid) {
+    seen = nullptr;
+    if (MODE == ROWS_BANNED) ban_bitmap_fill(bm, V, ban, hist, cur_len, tid);
+    if (MODE == ROWS_PROCESSED) {
+        if (ctl.penalty != 1.f) seen = bm + ban_words(V);
+        const RowContext cx{hist, cur_len, ctl.vn, ctl.vtok, ctl.vbos};
+        processed_bitmaps_fill(bm, (unsigned*)seen, V, ban, ctl.ngram, cx, tid);
+    }
+}
+// a candidate's value ahead of the bans: the running score plus the (penalised) log-prob, or plus the raw logit
+template <int MODE>
+__device__ __forceinline__ float beam_value(float e, int i, int V, int raw, float m, float lsum, float run, const unsigned* seen, float pen) {
+    if (MODE != ROWS_PROCESSED) return raw ? e + run : ((e - m) - lsum) + run;
+    float lp = (e - m) - lsum;
+    if (seen && i < V && ban_bit(seen, i)) lp = __fmul_rn(lp, pen);
+    return __fadd_rn(lp, run);
+}
+
+template <int MODE>
 __device__ __forceinline__ void beam_rows_body(char* st, BeamLayout lo, const float* __restrict__ logits, int ld, int V, int K, int par,
-                                               int raw, int eos_mask, unsigned* bm, BanSet ban, int L, int cur_len) {
+                                               int raw, int eos_mask, unsigned* bm, BanSet ban, int L, int cur_len,
+                                               RepeatCtl ctl = RepeatCtl()) {
+    constexpr bool BAN = MODE != ROWS_PLAIN;
+    const unsigned* seen = nullptr;
     if (*(const int*)(st + lo.active) == 0) return;
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* x = logits + (size_t)row * ld;
-    if (BAN) ban_bitmap_fill(bm, V, ban, (const int*)(st + lo.run_seq[par]) + (size_t)row * L, cur_len, tid);
+    if (BAN) beam_rows_fill<MODE>(bm, seen, V, ban, ctl, (const int*)(st + lo.run_seq[par]) + (size_t)row * L, cur_len, tid);
     __shared__ float redf[8];
     __shared__ int redi[8];
     __shared__ float bc[2];
@@ -109,7 +137,7 @@ __device__ __forceinline__ void beam_rows_body(char* st, BeamLayout lo, const fl
     for (int c = 0; c < 2 * K; ++c) {
         float bv = -INFINITY; int bi = 0x7fffffff;
         for (int i = tid; i < V; i += 256) {
-            float v = raw ? x[i] + run : ((x[i] - m) - lsum) + run;
+            float v = beam_value<MODE>(x[i], i, V, raw, m, lsum, run, seen, ctl.penalty);
             if (i == eos_mask) v = -INFINITY;
             if (BAN && ban_bit(bm, i)) v = -INFINITY;
             if (after(v, i, pv, pi) && better(v, i, bv, bi)) { bv = v; bi = i; }
@@ -134,13 +162,19 @@ __device__ __forceinline__ void beam_rows_body(char* st, BeamLayout lo, const fl
 
 __global__ __launch_bounds__(256) void beam_rows_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
                                                         int ld, int V, int K, int par, int raw, int eos_mask) {
-    beam_rows_body<false>(st, lo, logits, ld, V, K, par, raw, eos_mask, nullptr, BanSet(), 0, 0);
+    beam_rows_body<ROWS_PLAIN>(st, lo, logits, ld, V, K, par, raw, eos_mask, nullptr, BanSet(), 0, 0);
 }
 __global__ __launch_bounds__(256) void beam_rows_banned_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
                                                                int ld, int V, int K, int par, int raw, int eos_mask, BanSet ban,
                                                                int L, int cur_len) {
     extern __shared__ unsigned ban_bm[];
-    beam_rows_body<true>(st, lo, logits, ld, V, K, par, raw, eos_mask, ban_bm, ban, L, cur_len);
+    beam_rows_body<ROWS_BANNED>(st, lo, logits, ld, V, K, par, raw, eos_mask, ban_bm, ban, L, cur_len);
+}
+__global__ __launch_bounds__(256) void beam_rows_processed_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
+                                                                  int ld, int V, int K, int par, BanSet ban, int L, int cur_len,
+                                                                  RepeatCtl ctl) {
+    extern __shared__ unsigned ban_bm[];                 // ban_words(V) words, twice with a penalty
+    beam_rows_body<ROWS_PROCESSED>(st, lo, logits, ld, V, K, par, 0, -1, ban_bm, ban, L, cur_len, ctl);
 }
 
 // Single-pass variant of beam_rows_kernel: the row is read from global memory once (16-byte loads) into LDS; max, sum-exp
@@ -151,22 +185,25 @@ __global__ __launch_bounds__(256) void beam_rows_banned_kernel(char* st, BeamLay
 // STAGE = false: vocabularies whose row does not fit in LDS next to the candidate lists (CoCa: 49408 x 4 B = 193 KiB): the
 // same single-scan candidate selection reading the row from global memory (twice more for the log-softmax statistics; not at
 // all for raw-logit scores) - the 2K-pass fallback kernel took 874 us per step at 128 x 5 rows there.
-// BAN: as beam_rows_body - the bitmap sits behind the candidate lists in the dynamic LDS.
-template <int CT, bool STAGE, bool BAN>
+// MODE: as beam_rows_body - the bitmap(s) sit behind the candidate lists in the dynamic LDS.
+template <int CT, bool STAGE, int MODE>
 __device__ __forceinline__ void beam_rows_lds_body(char* st, BeamLayout lo, const float* __restrict__ logits, int ld, int V, int K,
-                                                   int par, int raw, int eos_mask, BanSet ban, int L, int cur_len) {
+                                                   int par, int raw, int eos_mask, BanSet ban, int L, int cur_len,
+                                                   RepeatCtl ctl = RepeatCtl()) {
+    constexpr bool BAN = MODE != ROWS_PLAIN;
+    const unsigned* seen = nullptr;
     if (*(const int*)(st + lo.active) == 0) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int V4 = (V + 3) >> 2, C = 2 * K;
     float* xs = (float*)smem;                                  // STAGE: [V4 * 4], tail padded with -inf
     float* lv = xs + (STAGE ? (size_t)V4 * 4 : 0);             // [C][256] candidate values, c-major
     int* li = (int*)(lv + (size_t)C * 256);                    // [C][256] candidate indices
-    const unsigned* bm = (const unsigned*)(li + (size_t)C * 256);   // BAN: [ban_words(V)]
+    const unsigned* bm = (const unsigned*)(li + (size_t)C * 256);   // BAN: [ban_words(V)], twice with a penalty
     __shared__ float redf[4];
     __shared__ int redi[4];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* x = logits + (size_t)row * ld;
-    if (BAN) ban_bitmap_fill((unsigned*)bm, V, ban, (const int*)(st + lo.run_seq[par]) + (size_t)row * L, cur_len, tid);
+    if (BAN) beam_rows_fill<MODE>((unsigned*)bm, seen, V, ban, ctl, (const int*)(st + lo.run_seq[par]) + (size_t)row * L, cur_len, tid);
     auto ldg = [&](int j) {                                     // 4 logits of the row, -inf beyond V
         float4 v;
         if (4 * j + 3 < V) v = *(const float4*)(x + 4 * j);
@@ -208,7 +245,7 @@ __device__ __forceinline__ void beam_rows_lds_body(char* st, BeamLayout lo, cons
     float* cv = (float*)(st + lo.cand_val) + (size_t)row * C;
     int* ci = (int*)(st + lo.cand_idx) + (size_t)row * C;
     auto score = [&](float e, int i) {
-        const float v = raw ? e + run : ((e - m) - lsum) + run;
+        const float v = beam_value<MODE>(e, i, V, raw, m, lsum, run, seen, ctl.penalty);
         if (BAN && i < V && ban_bit(bm, i)) return -INFINITY;
         return i == eos_mask ? -INFINITY : v;
     };
@@ -308,7 +345,7 @@ __device__ __forceinline__ void beam_rows_lds_body(char* st, BeamLayout lo, cons
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int i = 4 * j + u;
-                float v = raw ? e[u] + run : ((e[u] - m) - lsum) + run;
+                float v = beam_value<MODE>(e[u], i, V, raw, m, lsum, run, seen, ctl.penalty);
                 if (i == eos_mask) v = -INFINITY;
                 if (BAN && i < V && ban_bit(bm, i)) v = -INFINITY;
                 if (i < V && better(v, i, tv[CT - 1], ti[CT - 1])) {
@@ -350,13 +387,19 @@ __device__ __forceinline__ void beam_rows_lds_body(char* st, BeamLayout lo, cons
 template <int CT, bool STAGE = true>
 __global__ __launch_bounds__(256) void beam_rows_lds_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
                                                             int ld, int V, int K, int par, int raw, int eos_mask) {
-    beam_rows_lds_body<CT, STAGE, false>(st, lo, logits, ld, V, K, par, raw, eos_mask, BanSet(), 0, 0);
+    beam_rows_lds_body<CT, STAGE, ROWS_PLAIN>(st, lo, logits, ld, V, K, par, raw, eos_mask, BanSet(), 0, 0);
 }
 template <int CT, bool STAGE>
 __global__ __launch_bounds__(256) void beam_rows_lds_banned_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
                                                                    int ld, int V, int K, int par, int raw, int eos_mask, BanSet ban,
                                                                    int L, int cur_len) {
-    beam_rows_lds_body<CT, STAGE, true>(st, lo, logits, ld, V, K, par, raw, eos_mask, ban, L, cur_len);
+    beam_rows_lds_body<CT, STAGE, ROWS_BANNED>(st, lo, logits, ld, V, K, par, raw, eos_mask, ban, L, cur_len);
+}
+template <int CT, bool STAGE>
+__global__ __launch_bounds__(256) void beam_rows_lds_processed_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
+                                                                      int ld, int V, int K, int par, BanSet ban, int L, int cur_len,
+                                                                      RepeatCtl ctl) {
+    beam_rows_lds_body<CT, STAGE, ROWS_PROCESSED>(st, lo, logits, ld, V, K, par, 0, -1, ban, L, cur_len, ctl);
 }
 
 // One 64-thread block per item.  The three selections of a step (top-2K continuations over the K candidate lists,
@@ -573,6 +616,45 @@ static int launch_beam_rows_banned(void* state, const BeamLayout& lo, const floa
 
 static int launch_beam_merge(void* state, const BeamLayout& lo, int V, int B, int K, int max_len, int cur_len, int eos,
                              float length_penalty, int* anc, int anc_ld, int raw, hipStream_t s);
+
+// launch_beam_rows_banned with the repetition controls: the same three branches; a penalty's second bitmap counts in the LDS budget
+template <int CT, bool STAGE>
+static int launch_beam_rows_lds_processed(size_t lds, void* state, const BeamLayout& lo, const float* logits, int ld, int V, int B, int K,
+                                          int par, const BanSet& ban, int L, int cur_len, const RepeatCtl& ctl, hipStream_t s) {
+    if (cap_kernel_setup((const void*)beam_rows_lds_processed_kernel<CT, STAGE>, 148 * 1024, nullptr) != 0) return -1;
+    hipLaunchKernelGGL((beam_rows_lds_processed_kernel<CT, STAGE>), dim3(B * K), dim3(256), lds, s, (char*)state, lo, logits, ld, V, K, par,
+                       ban, L, cur_len, ctl);
+    return 0;
+}
+int launch_beam_step_processed(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
+                               float length_penalty, int* anc, int anc_ld, hipStream_t s, BanSet ban, RepeatCtl ctl) {
+    if ((ban.n_multi && (!ban.multi || !ban.bits)) || ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI) {
+        cap_set_error("beam_step (processed): %d multi-token sequences (at most %d, with a bitmap)", ban.n_multi, BAN_MAX_MULTI);
+        return -1;
+    }
+    if (!(ctl.penalty > 0.f) || !std::isfinite(ctl.penalty) || ctl.ngram < 0 || ctl.vn < 0) {
+        cap_set_error("beam_step (processed): penalty %g (finite, > 0), n-gram size %d (>= 0), %d virtual context tokens (>= 0)",
+                      (double)ctl.penalty, ctl.ngram, ctl.vn);
+        return -1;
+    }
+    const BeamLayout lo = beam_layout(B, K, max_len);
+    const int par = cur_len & 1, L = max_len;
+    const size_t bmb = (size_t)ban_words(V) * 4 * (ctl.penalty != 1.f ? 2 : 1), lists = (size_t)2 * K * 256 * 8;
+    const size_t lds = (size_t)((V + 3) / 4) * 16 + lists + bmb;
+    const bool fast = (ld & 3) == 0 && V > 2 * K;
+#define PROCESSED_ROWS(STAGE, bytes)                                                                                                   \
+    (2 * K <= 4   ? launch_beam_rows_lds_processed<4, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, ban, L, cur_len, ctl, s)       \
+     : 2 * K <= 8 ? launch_beam_rows_lds_processed<8, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, ban, L, cur_len, ctl, s)       \
+                  : launch_beam_rows_lds_processed<16, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, ban, L, cur_len, ctl, s))
+    if (fast && lds <= 148 * 1024) { if (PROCESSED_ROWS(true, lds) != 0) return -1; }
+    else if (fast) { if (PROCESSED_ROWS(false, lists + bmb) != 0) return -1; }
+    else
+        hipLaunchKernelGGL(beam_rows_processed_kernel, dim3(B * K), dim3(256), bmb, s, (char*)state, lo, logits, ld, V, K, par, ban, L,
+                           cur_len, ctl);
+#undef PROCESSED_ROWS
+    CAP_HIP_CHECK(hipGetLastError());
+    return launch_beam_merge(state, lo, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, 0, s);
+}
 
 int launch_beam_step_banned(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
                             float length_penalty, int* anc, int anc_ld, hipStream_t s, int mode, int min_len, BanSet ban) {

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 #include <map>
 #include <string>
@@ -224,6 +225,15 @@ struct Captioner {
     std::vector<unsigned> ban_bits_host; std::vector<int> ban_multi_host;
     bool banned() const { return ban_n_single > 0 || ban_n_multi > 0; }
     BanSet ban_set() const { BanSet b; b.bits = ban_bits; b.multi = ban_multi; b.n_multi = ban_n_multi; return b; }
+    // repetition controls (cap_set_repeat_controls; ops.h, RepeatCtl): two numbers, no storage; image_token = the id of BLIP-2's image
+    // placeholders as HF's processors see them in front of BOS (cap_set_image_token; -1 = not given)
+    float rep_penalty = 1.f; int rep_ngram = 0; int image_token = -1;
+    bool repeat_active() const { return rep_penalty != 1.f || rep_ngram > 0; }
+    RepeatCtl repeat_ctl() const {
+        RepeatCtl r; r.penalty = rep_penalty; r.ngram = rep_ngram;
+        if (c.arch == CAP_ARCH_BLIP2) { r.vn = c.num_query_tokens; r.vtok = image_token; r.vbos = c.bos; }
+        return r;
+    }
     int last_steps = 0;          // decode steps the last cap_generate ran (cap_last_decode_steps)
     int decode_path = 0;         // cap_set_decode_path: 0 = by row count (<= SMALL_MAX_ROWS rows: the fused small-batch kernels),
                                  // 1 = always the batch kernels, 2 = always the small-batch kernels (an error beyond their row limit)
@@ -786,9 +796,15 @@ int select_greedy_step(Captioner* m, const CapGenerateArgs& a, int R, int step, 
     // BLIP-2's BOS and generated tokens: the generated columns and the one before them, which stands for BOS (it holds pad, and
     // neither id is in any sequence).  validate_generate refused the log-prob / vocabulary outputs and CoCa; with nothing set this is
     // the launch it has always been.
+    // Repetition controls (cap_set_repeat_controls): the processed form, which also takes the ban set if there is one; its context puts
+    // BLIP-2's image placeholders and BOS in front of the same columns (ops.h, RepeatCtl).
+    const int hist0 = c.arch == CAP_ARCH_BLIP2 ? c.num_query_tokens : 0;
+    if (m->repeat_active())
+        return launch_greedy_select_processed(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s, 0,
+                                              0, map, m->banned() ? m->ban_set() : BanSet(), hist0, m->repeat_ctl());
     if (m->banned())
         return launch_greedy_select_banned(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s, 0, 0,
-                                           map, m->ban_set(), c.arch == CAP_ARCH_BLIP2 ? c.num_query_tokens : 0);
+                                           map, m->ban_set(), hist0);
     return launch_greedy_select(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s,
                                 coca ? c.min_len : 0, coca ? 1 : 0, map, a.out_logprobs, cols, step, a.out_scored, a.out_vocab, a.acc_ld);
 }
@@ -1679,7 +1695,10 @@ int run_generate(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
             TRY(select_greedy_step(m, a, R, t - t0, Lm - 1, Lm, t, Lm, d.map, s));
             if (compact) TRY(launch_compact_rows(d.finished, R, m->live, m->n_live, s));
         } else {
-            if (m->banned())      // (never CoCa: validate_generate)
+            if (m->repeat_active())      // (never CoCa: validate_generate)
+                TRY(launch_beam_step_processed(d.beam, d.logits, m->ldl, c.vocab, B, K, Lm, cur_len, c.eos, a.length_penalty, d.anc, Lm, s,
+                                               m->banned() ? m->ban_set() : BanSet(), m->repeat_ctl()));
+            else if (m->banned())
                 TRY(launch_beam_step_banned(d.beam, d.logits, m->ldl, c.vocab, B, K, Lm, cur_len, c.eos, a.length_penalty, d.anc, Lm, s,
                                             BEAM_HF_V5, 0, m->ban_set()));
             else
@@ -1963,7 +1982,10 @@ int run_beams_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
         TRY(copy_step_logits(m, a, R, t, s));
         {
             ProfScope ps(m, s, "beam_step", 0, (double)R * c.vocab * 4);
-            if (m->banned())
+            if (m->repeat_active())
+                TRY(launch_beam_step_processed(m->beam, m->logits, m->ldl, c.vocab, B, K, Lb, cur_len, c.eos, a.length_penalty, m->anc, Lb, s,
+                                               m->banned() ? m->ban_set() : BanSet(), m->repeat_ctl()));
+            else if (m->banned())
                 TRY(launch_beam_step_banned(m->beam, m->logits, m->ldl, c.vocab, B, K, Lb, cur_len, c.eos, a.length_penalty, m->anc, Lb, s,
                                             BEAM_HF_V5, 0, m->ban_set()));
             else
@@ -2367,6 +2389,54 @@ int cap_bad_words(CapHandle h, int* n_single, int* n_multi) {
     return 0;
 }
 
+int cap_set_repeat_controls(CapHandle h, float repetition_penalty, int no_repeat_ngram_size) {
+    Captioner* m = (Captioner*)h;
+    const char* who = "cap_set_repeat_controls";
+    if (!m) { cap_set_error("%s: null handle", who); return -1; }
+    const CapConfig& c = m->c;
+    if (!std::isfinite(repetition_penalty) || !(repetition_penalty > 0.f)) {
+        cap_set_error("%s: repetition_penalty = %g (a finite number above 0; 1 = off)", who, (double)repetition_penalty);
+        return -1;
+    }
+    if (no_repeat_ngram_size < 0) { cap_set_error("%s: no_repeat_ngram_size = %d (0 = off, or an n-gram size >= 1)", who, no_repeat_ngram_size); return -1; }
+    // the longest context a processor ever sees: BLIP max_len tokens with BOS; BLIP-2 the placeholders, BOS and max_len new tokens
+    const int prefix = c.arch == CAP_ARCH_BLIP2 ? c.num_query_tokens + 1 : 0;
+    if (no_repeat_ngram_size > c.max_len + prefix) {
+        cap_set_error("%s: no_repeat_ngram_size = %d is beyond the %d tokens a caption of this handle can hold (max_len %d + a prefix of %d)", who,
+                      no_repeat_ngram_size, c.max_len + prefix, c.max_len, prefix);
+        return -1;
+    }
+    const bool on = repetition_penalty != 1.f || no_repeat_ngram_size > 0;
+    if (on && c.arch != CAP_ARCH_BLIP && c.arch != CAP_ARCH_BLIP2 && c.arch != CAP_ARCH_COCA) {
+        cap_set_error("%s: this handle's arch (%d) has no decode loop", who, c.arch);
+        return -1;
+    }
+    if (on && c.arch == CAP_ARCH_BLIP2 && m->image_token < 0) {
+        cap_set_error("%s: a BLIP-2 handle needs the id of its image placeholders first (cap_set_image_token): HF's processors see them "
+                      "in front of BOS", who);
+        return -1;
+    }
+    m->rep_penalty = repetition_penalty; m->rep_ngram = no_repeat_ngram_size;
+    return 0;
+}
+
+int cap_repeat_controls(CapHandle h, float* repetition_penalty, int* no_repeat_ngram_size) {
+    const Captioner* m = (const Captioner*)h;
+    if (!m) { cap_set_error("cap_repeat_controls: null handle"); return -1; }
+    if (repetition_penalty) *repetition_penalty = m->rep_penalty;
+    if (no_repeat_ngram_size) *no_repeat_ngram_size = m->rep_ngram;
+    return 0;
+}
+
+int cap_set_image_token(CapHandle h, int image_token) {
+    Captioner* m = (Captioner*)h;
+    if (!m) { cap_set_error("cap_set_image_token: null handle"); return -1; }
+    if (m->c.arch != CAP_ARCH_BLIP2) { cap_set_error("cap_set_image_token: image placeholders are CAP_ARCH_BLIP2's (this handle's arch is %d)", m->c.arch); return -1; }
+    if (image_token < 0) { cap_set_error("cap_set_image_token: id %d (>= 0; an id beyond the vocabulary is context no processor acts on)", image_token); return -1; }
+    m->image_token = image_token;
+    return 0;
+}
+
 int cap_last_decode_steps(CapHandle h) { return h ? ((Captioner*)h)->last_steps : -1; }
 
 int cap_set_decode_path(CapHandle h, int path) {
@@ -2695,6 +2765,8 @@ static int validate_generate(Captioner* m, const CapGenerateArgs& a, const char*
               who, c.arch);
     REFUSE_IF(m->banned() && G && c.arch != CAP_ARCH_COCA,
               "%s: bad words are set on this handle (cap_set_bad_words) and beam groups do not take them", who);
+    REFUSE_IF(m->repeat_active() && G && c.arch != CAP_ARCH_COCA,
+              "%s: repetition controls are set on this handle (cap_set_repeat_controls) and beam groups do not take them", who);
     REFUSE_IF(G && c.arch != CAP_ARCH_COCA,
               "%s: beam groups are the CoCa loop's (coca_model.py:335-482); HF's group beam search for the other architectures needs a "
               "diversity penalty, which this library does not implement", who);
@@ -2705,6 +2777,15 @@ static int validate_generate(Captioner* m, const CapGenerateArgs& a, const char*
         REFUSE_IF(a.out_logprobs || a.out_scored || a.out_vocab,
                   "%s: bad words are set on this handle (cap_set_bad_words) and out_logprobs / out_vocab describe the raw logits, which no "
                   "longer describe the selection: clear the set, or leave these outputs out", who);
+    }
+    if (m->repeat_active()) {   // cap_set_repeat_controls: BLIP and BLIP-2, greedy and beams, tokens only
+        REFUSE_IF(c.arch == CAP_ARCH_COCA,
+                  "%s: repetition controls are set on this handle (cap_set_repeat_controls: penalty %g, n-gram size %d) and it is a CoCa "
+                  "captioner: its decode loop does not apply them (BLIP and BLIP-2 only); reset them with (1, 0)", who,
+                  (double)m->rep_penalty, m->rep_ngram);
+        REFUSE_IF(a.out_logprobs || a.out_scored || a.out_vocab,
+                  "%s: repetition controls are set on this handle (cap_set_repeat_controls) and out_logprobs / out_vocab describe the raw "
+                  "logits, which no longer describe the selection: reset the controls with (1, 0), or leave these outputs out", who);
     }
     REFUSE_IF(G < 0 || G > K || (G && K % G != 0), "%s: num_beams (%d) must be a multiple of num_beam_groups (%d) (BeamSearchScorer's own check)",
               who, K, G);
@@ -3298,6 +3379,56 @@ int cap_op_beam_step_banned(void* state, const float* logits, int ld, int V, int
     ban.bits = ban_bits; ban.multi = ban_multi; ban.n_multi = n_multi;
     return launch_beam_step_banned(state, logits, ld, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, (hipStream_t)stream, mode,
                                    min_len, ban);
+}
+// The processed forms alone (tests/test_repeat_controls_kernels_gpu.py): cap_op_select_banned / cap_op_beam_step_banned with the
+// repetition controls; ban_bits may be NULL (no static bitmap; n_multi must then be 0).
+static int repeat_op_ctl(const char* f, float penalty, int ngram, int vn, int vtok, int vbos, const uint32_t* ban_bits, const int32_t* ban_multi,
+                         int n_multi, RepeatCtl* ctl, BanSet* ban) {
+    if (!std::isfinite(penalty) || !(penalty > 0.f) || ngram < 0 || vn < 0 || vn > 4096) {
+        cap_set_error("%s: penalty = %g (finite, > 0), n-gram size = %d (>= 0), %d virtual context tokens (0 .. 4096)", f, (double)penalty, ngram, vn);
+        return -1;
+    }
+    if (n_multi < 0 || n_multi > BAN_MAX_MULTI || (n_multi > 0 && (!ban_multi || !ban_bits))) {
+        cap_set_error("%s: n_multi = %d must be in [0, %d] (with ban_multi and ban_bits)", f, n_multi, BAN_MAX_MULTI);
+        return -1;
+    }
+    ctl->penalty = penalty; ctl->ngram = ngram; ctl->vn = vn; ctl->vtok = vtok; ctl->vbos = vbos;
+    ban->bits = ban_bits; ban->multi = ban_multi; ban->n_multi = n_multi;
+    return 0;
+}
+int cap_op_select_processed(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int32_t* finished,
+                            const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths, const uint32_t* ban_bits,
+                            const int32_t* ban_multi, int n_multi, int hist0, float penalty, int ngram, int vn, int vtok, int vbos,
+                            void* stream) {
+    const char* f = "cap_op_select_processed";
+    if (!logits || !finished || !seq || !lengths || R < 1 || V < 1 || ld < V || t < 0 || t + 1 >= max_len ||
+        (live != nullptr) != (n_live != nullptr) || hist0 < 0 || hist0 > t + 1) {
+        cap_set_error("%s: bad arguments (ld = %d >= V = %d >= 1; hist0 = %d in [0, t + 1 = %d])", f, ld, V, hist0, t + 1);
+        return -1;
+    }
+    RepeatCtl ctl; BanSet ban;
+    TRY(repeat_op_ctl(f, penalty, ngram, vn, vtok, vbos, ban_bits, ban_multi, n_multi, &ctl, &ban));
+    RowMap map;
+    map.live = live; map.n = n_live;
+    return launch_greedy_select_processed(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, 0, 0,
+                                          map, ban, hist0, ctl);
+}
+int cap_op_beam_step_processed(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
+                               float length_penalty, int32_t* anc, int anc_ld, const uint32_t* ban_bits, const int32_t* ban_multi,
+                               int n_multi, float penalty, int ngram, int vn, int vtok, int vbos, void* stream) {
+    const char* f = "cap_op_beam_step_processed";
+    TRY(beam_op_args(f, state, B, K, max_len));
+    if (!logits) { cap_set_error("%s: logits is null", f); return -1; }
+    if (V < 1 || ld < V) { cap_set_error("%s: ld = %d, V = %d (ld >= V >= 1)", f, ld, V); return -1; }
+    if (cur_len - 1 < 0 || cur_len - 1 >= max_len - 1) {
+        cap_set_error("%s: cur_len = %d (step cur_len - 1 must satisfy 0 <= step < max_len - 1 = %d)", f, cur_len, max_len - 1);
+        return -1;
+    }
+    if (anc && anc_ld < 1) { cap_set_error("%s: anc_ld = %d with an ancestry table (anc_ld >= 1)", f, anc_ld); return -1; }
+    RepeatCtl ctl; BanSet ban;
+    TRY(repeat_op_ctl(f, penalty, ngram, vn, vtok, vbos, ban_bits, ban_multi, n_multi, &ctl, &ban));
+    return launch_beam_step_processed(state, logits, ld, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, (hipStream_t)stream,
+                                      ban, ctl);
 }
 int cap_op_vocab_group_threshold(const float* acc, int acc_ld, int V, int N, const int32_t* group_rows, int M, const int32_t* group_off,
                                  int G, float th, int K, int32_t* out_ids, float* out_prob, int32_t* out_count, void* stream) {

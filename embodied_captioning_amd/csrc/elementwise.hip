@@ -1,6 +1,7 @@
 // HBM-bound helper kernels of the captioner path: dtype casts, patch gather, LayerNorm, decoder embeddings,
 // greedy token selection.  One wave (64 lanes) per row for the row-wise ops; 16-byte accesses where the layout allows.
 #include <algorithm>
+#include <cmath>
 #include "ops.h"
 #include "ban.h"
 
@@ -382,14 +383,17 @@ __global__ __launch_bounds__(256) void mean_pool_normalize_kernel(const float* _
 // A row with no entry above -inf (all -inf, or finite only at a masked EOS) selects index 0, as torch.argmax does; a NaN never
 // compares greater, so it is never selected (ops.h, launch_greedy_select).
 // BAN (the banned form, greedy_select_banned_kernel): bm = the row's ban bitmap in LDS (ban.h), a set bit stands as -inf does.
-template <bool BAN = false>
+// PEN (the processed form with a repetition penalty): seen = the bitmap of the row's context tokens, whose scores are penalised
+// (ban.h, repeat_penalise) before the bans, as HF orders its processors.
+template <bool BAN = false, bool PEN = false>
 __device__ __forceinline__ int greedy_row_argmax(const float* __restrict__ x, int V, int eos, bool mask_eos, int tid,
-                                                  float* sv, int* si, const unsigned* bm = nullptr) {
+                                                  float* sv, int* si, const unsigned* bm = nullptr, const unsigned* seen = nullptr,
+                                                  float pen = 1.f, bool vec = true) {
     float best = -INFINITY;
     int bi = 0x7fffffff;
     // 16-byte loads, 4 independent chunks in flight per thread; ascending index order inside a thread keeps "first
     // maximal index" with a strict > compare
-    const int V4 = V >> 2;
+    const int V4 = vec ? V >> 2 : 0;                     // vec = false (a row that is not 16-byte aligned): every element by the tail loop
     for (int c0 = tid; c0 < V4; c0 += 1024) {
         float4 v[4];
 #pragma unroll
@@ -406,6 +410,13 @@ __device__ __forceinline__ int greedy_row_argmax(const float* __restrict__ x, in
                 if (eos == i + 2) v[u].z = -INFINITY;
                 if (eos == i + 3) v[u].w = -INFINITY;
             }
+            if (PEN) {
+                const unsigned nib = c0 + u * 256 < V4 ? ban_nibble(seen, i) : 0u;
+                if (nib & 1u) v[u].x = repeat_penalise(v[u].x, pen);
+                if (nib & 2u) v[u].y = repeat_penalise(v[u].y, pen);
+                if (nib & 4u) v[u].z = repeat_penalise(v[u].z, pen);
+                if (nib & 8u) v[u].w = repeat_penalise(v[u].w, pen);
+            }
             if (BAN) {               // the chunk's four bits come from one LDS word
                 const unsigned nib = c0 + u * 256 < V4 ? ban_nibble(bm, i) : 0u;
                 if (nib & 1u) v[u].x = -INFINITY;
@@ -420,7 +431,9 @@ __device__ __forceinline__ int greedy_row_argmax(const float* __restrict__ x, in
         }
     }
     for (int i = (V4 << 2) + tid; i < V; i += 256) {
-        const float v = ((mask_eos && i == eos) || (BAN && ban_bit(bm, i))) ? -INFINITY : x[i];
+        float v = x[i];
+        if (PEN && ban_bit(seen, i)) v = repeat_penalise(v, pen);
+        if ((mask_eos && i == eos) || (BAN && ban_bit(bm, i))) v = -INFINITY;
         if (v > best) { best = v; bi = i; }
     }
     sv[tid] = best; si[tid] = bi;
@@ -487,6 +500,29 @@ __global__ __launch_bounds__(256) void greedy_select_banned_kernel(const float* 
     __shared__ int si[256];
     ban_bitmap_fill(ban_bm, V, ban, seq + (size_t)row * seq_ld + hist0, max(t + 1 - hist0, 0), tid);
     const int imax = greedy_row_argmax<true>(logits + (size_t)crow * ld, V, eos, mask_eos, tid, sv, si, ban_bm);
+    if (tid == 0) greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
+}
+
+// Processed form (ops.h, RepeatCtl): the banned form with HF's repetition controls ahead of the ban - the n-gram bans go into the same
+// bitmap, the penalty reads a second one ("seen", behind it in the dynamic LDS when PEN).  The row's context is RowContext's.
+template <bool PEN>
+__global__ __launch_bounds__(256) void greedy_select_processed_kernel(const float* __restrict__ logits, int ld, int V,
+                                                                      int* __restrict__ seq, int seq_ld, int t, int max_len,
+                                                                      int eos, int pad, int* __restrict__ finished,
+                                                                      int* __restrict__ out_len, int min_len, int force_eos, RowMap map,
+                                                                      BanSet ban, int hist0, RepeatCtl ctl) {
+    const int crow = blockIdx.x, tid = threadIdx.x;
+    if (map.n && crow >= *map.n) return;
+    const int row = map.live ? map.live[crow] : crow;
+    const bool mask_eos = min_len > 0 && t + 1 < min_len;
+    extern __shared__ unsigned ban_bm[];                 // ban_words(V) words, twice with PEN
+    __shared__ float sv[256];
+    __shared__ int si[256];
+    unsigned* seen = PEN ? ban_bm + ban_words(V) : nullptr;
+    const RowContext cx{seq + (size_t)row * seq_ld + hist0, max(t + 1 - hist0, 0), ctl.vn, ctl.vtok, ctl.vbos};
+    processed_bitmaps_fill(ban_bm, seen, V, ban, ctl.ngram, cx, tid);
+    const int imax = greedy_row_argmax<true, PEN>(logits + (size_t)crow * ld, V, eos, mask_eos, tid, sv, si, ban_bm, seen, ctl.penalty,
+                                                  (ld & 3) == 0);
     if (tid == 0) greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
 }
 
@@ -1031,6 +1067,30 @@ int launch_greedy_select_banned(const float* logits, int ld, int V, int* seq, in
     }
     hipLaunchKernelGGL(greedy_select_banned_kernel, dim3(R), dim3(256), (size_t)ban_words(V) * 4, s, logits, ld, V, seq, seq_ld, t,
                        max_len, eos, pad, finished, out_len, min_len, force_eos, map, ban, hist0);
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_greedy_select_processed(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
+                                   int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
+                                   BanSet ban, int hist0, RepeatCtl ctl) {
+    if ((ban.n_multi && (!ban.multi || !ban.bits)) || ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI || hist0 < 0 || hist0 > t + 1) {
+        cap_set_error("greedy_select (processed): %d multi-token sequences (at most %d, with a bitmap) or a history from column %d at step %d",
+                      ban.n_multi, BAN_MAX_MULTI, hist0, t);
+        return -1;
+    }
+    if (!(ctl.penalty > 0.f) || !std::isfinite(ctl.penalty) || ctl.ngram < 0 || ctl.vn < 0) {
+        cap_set_error("greedy_select (processed): penalty %g (finite, > 0), n-gram size %d (>= 0), %d virtual context tokens (>= 0)",
+                      (double)ctl.penalty, ctl.ngram, ctl.vn);
+        return -1;
+    }
+    const size_t bmb = (size_t)ban_words(V) * 4;
+    if (ctl.penalty != 1.f)
+        hipLaunchKernelGGL(greedy_select_processed_kernel<true>, dim3(R), dim3(256), 2 * bmb, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
+                           pad, finished, out_len, min_len, force_eos, map, ban, hist0, ctl);
+    else
+        hipLaunchKernelGGL(greedy_select_processed_kernel<false>, dim3(R), dim3(256), bmb, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
+                           pad, finished, out_len, min_len, force_eos, map, ban, hist0, ctl);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -88,6 +88,24 @@ __host__ __device__ inline int ban_words(int V) { return ((V + 31) / 32 + 3) / 4
 int launch_greedy_select_banned(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
                                 int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
                                 BanSet ban, int hist0);
+// Repetition controls (HF RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor; captioner_hip.h, cap_set_repeat_controls), as
+// the processed forms of the selection kernels read them.  The context of a row is what HF's processor sees: `vn` copies of `vtok`
+// (BLIP-2's image placeholders; 0 = none), then the row's stored history, whose FIRST token reads as `vbos` when vbos >= 0 (BLIP-2
+// keeps pad in the column that stands for BOS).
+//   penalty  every distinct context token in [0, V): x < 0 ? x * penalty : x / penalty (fp32, a true division); 1 = off
+//   ngram    n >= 1: a token that followed an earlier occurrence of the context's last n - 1 tokens is banned; 0 = off
+// Order: penalty, n-grams, bad words (the last two are -inf).
+struct RepeatCtl {
+    float penalty = 1.f;
+    int ngram = 0;
+    int vn = 0, vtok = 0, vbos = -1;
+    bool active() const { return penalty != 1.f || ngram > 0; }
+};
+// launch_greedy_select_banned with the repetition controls: any combination of a ban set (ban.bits may be null: no static bitmap),
+// a penalty and an n-gram size.  The stored history of caption `row` is seq[row][hist0 .. t].
+int launch_greedy_select_processed(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
+                                   int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
+                                   BanSet ban, int hist0, RepeatCtl ctl);
 // teacher-forced scoring: logits row b of `rows` (fp32 [rows, ld]) is pass row r = r0 + b = position r % npos of caption r / npos; for
 // positions below n_live[caption] the log-softmax at targets[caption * tgt_ld + position] (clamped to [0, V)), log max softmax and the
 // arg-max (launch_greedy_select's selection and tie rule, no EOS mask) go to out_*[caption * out_ld + position], zeros for the others
@@ -280,6 +298,10 @@ int launch_beam_step(void* state, const float* logits, int ld, int V, int B, int
 // history of a row is its LOGICAL one, run_seq[cur_len & 1][row][0 .. cur_len).
 int launch_beam_step_banned(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
                             float length_penalty, int* anc, int anc_ld, hipStream_t s, int mode, int min_len, BanSet ban);
+// launch_beam_step_banned with the repetition controls (RepeatCtl above; ban.bits may be null): log-softmax of the raw row, the penalty
+// on the log-probs (all <= 0: lp * penalty), the bans, then the running score.  HF v5 scores only.
+int launch_beam_step_processed(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
+                               float length_penalty, int* anc, int anc_ld, hipStream_t s, BanSet ban, RepeatCtl ctl);
 int launch_beam_finalize(void* state, int B, int K, int max_len, int* out_ids, int* out_len, float* out_scores,
                          hipStream_t s);
 // device pointer: int32, 1 while the beam loop of this state is still running (HF `is_done.all()` not yet true)

@@ -18,6 +18,7 @@ import torch
 from . import _native as N
 from .config import Blip2Arch, Blip2ItmArch, BlipArch, ClipArch, CocaArch, MiniLMArch
 from .captioner.bad_words import validate_bad_words_ids  # noqa: F401 - the host check of set_bad_words, public here
+from .captioner.repeat_controls import validate_repeat_controls  # noqa: F401 - the host check of set_repeat_controls, public here
 
 logger = logging.getLogger(__name__)
 
@@ -527,6 +528,37 @@ class CaptionerEngine(_Engine):
         N.check(self.lib.cap_bad_words(self._h, C.byref(a), C.byref(b)), "cap_bad_words")
         return int(a.value), int(b.value)
 
+    def set_repeat_controls(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0) -> None:
+        """HF `generate(repetition_penalty=, no_repeat_ngram_size=)` for every generating call that follows (BLIP and BLIP-2, greedy
+        and beams, every decode path; `score` ignores them): the penalty divides the positive and multiplies the negative scores of
+        every token of the caption's context, once per distinct token; the n-gram size bans every token that would repeat an n-gram
+        of the context.  HF's order (penalty, n-grams, bad words) and HF's context: BLIP's BOS, prompt and generated tokens; BLIP-2's
+        image placeholders, BOS and generated tokens.  The defaults (1.0, 0) switch both off.  Validated on the host
+        (`validate_repeat_controls`) first.  With a control on, `generate` refuses output_logprobs / output_vocab_maxprob, beam
+        groups and a CoCa engine (the library's rules, by name)."""
+        p, n = validate_repeat_controls(repetition_penalty, no_repeat_ngram_size, self.arch, self.max_len)
+        if self.is_blip2 and (p != 1.0 or n > 0):      # the placeholders HF's processors see in front of BOS
+            N.check(self.lib.cap_set_image_token(self._h, int(self.arch.image_token)), "cap_set_image_token")
+        N.check(self.lib.cap_set_repeat_controls(self._h, C.c_float(p), int(n)), "cap_set_repeat_controls")
+        self._repeat_controls = (float(C.c_float(p).value), n)
+
+    @property
+    def repetition_penalty(self) -> float:
+        """The penalty in force (`set_repeat_controls`), as the fp32 number the kernels use; 1.0 = off."""
+        return getattr(self, "_repeat_controls", (1.0, 0))[0]
+
+    @property
+    def no_repeat_ngram_size(self) -> int:
+        """The n-gram size in force (`set_repeat_controls`); 0 = off."""
+        return getattr(self, "_repeat_controls", (1.0, 0))[1]
+
+    @property
+    def repeat_controls(self) -> tuple:
+        """(penalty, n-gram size) as the library holds them (cap_repeat_controls)."""
+        a, b = C.c_float(0), C.c_int(0)
+        N.check(self.lib.cap_repeat_controls(self._h, C.byref(a), C.byref(b)), "cap_repeat_controls")
+        return float(a.value), int(b.value)
+
     @property
     def last_decode_steps(self) -> int:
         return int(self.lib.cap_last_decode_steps(self._h))
@@ -643,7 +675,7 @@ class CaptionerEngine(_Engine):
     def generate(self, pixels: torch.Tensor, num_beams: int = 1, max_length: Optional[int] = None,
                  length_penalty: float = 1.0, output_logits: bool = False, num_beam_groups: Optional[int] = None,
                  output_logprobs: bool = False, output_vocab_maxprob: bool = False, prompt_ids=None, bad_words_ids=None,
-                 **sampling_options) -> Dict[str, torch.Tensor]:
+                 repetition_penalty=None, no_repeat_ngram_size=None, **sampling_options) -> Dict[str, torch.Tensor]:
         """prompt_ids (BLIP, greedy): a host list / tensor [P], [1, P] (one prompt for every caption) or [B, P] (one per caption), column
         0 = BOS - HF `BlipForConditionalGeneration.generate(pixel_values, input_ids=...)`, whose decoder receives input_ids[:, :-1].
         Validated on the host (`validate_prompt_ids`).  max_length counts the prompt; `sequences` start with it and `lengths`
@@ -666,6 +698,8 @@ class CaptionerEngine(_Engine):
         its `generate()` defaults are 6 beams in 3 groups) - cap_generate_groups; no per-step logits in that mode.
         bad_words_ids: accepted when it equals the set in force (`set_bad_words`, `.bad_words`; None = not given), refused by name
         otherwise - the set is engine state, not a per-call option.
+        repetition_penalty / no_repeat_ngram_size: likewise accepted when they equal the values in force (`set_repeat_controls`; None =
+        not given), refused by name otherwise; they never reach `reject_unsupported_generation_options`.
         sampling_options: anything else a caller of the reference's / HF's `generate` may pass (top_p, top_k, temperature,
         repetition_penalty, do_sample, ...): accepted at their neutral values, rejected BY NAME otherwise - never ignored."""
         if output_vocab_maxprob and (num_beam_groups is not None or num_beams != 1):      # before anything is allocated or run
@@ -674,6 +708,16 @@ class CaptionerEngine(_Engine):
         if bad_words_ids is not None and validate_bad_words_ids(bad_words_ids, self.arch) != self.bad_words:
             raise ValueError(f"generate: bad_words_ids differs from the set in force on this engine ({len(self.bad_words)} sequences): "
                              "the banned set is engine state - call set_bad_words(bad_words_ids) first")
+        for name, given, held in (("repetition_penalty", repetition_penalty, self.repetition_penalty),
+                                  ("no_repeat_ngram_size", no_repeat_ngram_size, self.no_repeat_ngram_size)):
+            if given is None:
+                continue
+            p, n = validate_repeat_controls(given if name == "repetition_penalty" else None,
+                                            given if name == "no_repeat_ngram_size" else None, self.arch, self.max_len)
+            want = float(C.c_float(p).value) if name == "repetition_penalty" else n
+            if want != held:
+                raise ValueError(f"generate: {name} = {given!r} differs from the value in force on this engine ({held!r}): the repetition "
+                                 f"controls are engine state - call set_repeat_controls first")
         if sampling_options:
             from .captioner.generation_options import reject_unsupported_generation_options, _NEUTRAL
             known = set(_NEUTRAL) | {"generation_type", "top_k", "top_p"}
@@ -892,6 +936,18 @@ class EnginePool:
     @property
     def bad_words(self):
         return self.engines[0].bad_words
+
+    def set_repeat_controls(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0) -> None:
+        for e in self.engines:
+            e.set_repeat_controls(repetition_penalty, no_repeat_ngram_size)
+
+    @property
+    def repetition_penalty(self) -> float:
+        return self.engines[0].repetition_penalty
+
+    @property
+    def no_repeat_ngram_size(self) -> int:
+        return self.engines[0].no_repeat_ngram_size
 
     def set_row_compaction(self, on: bool) -> None:
         for e in self.engines:

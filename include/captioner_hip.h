@@ -31,6 +31,8 @@
  *   banned words        HF `generate(bad_words_ids=...)` (NoBadWordsLogitsProcessor) - what would   cap_set_bad_words, cap_bad_words
  *                       keep the captions experimenting_env/captioner/pseudocaptioner.py:96-123    (BLIP, BLIP-2; inside the token
  *                       throws away for a banned word                                             selection kernels)
+ *   repetition          HF `generate(repetition_penalty=, no_repeat_ngram_size=)`; coca_model.py:222,238       cap_set_repeat_controls (BLIP,
+ *                       has the penalty in CoCa.generate's signature                                            BLIP-2; same kernels)
  *   batches of crops    detector/pseudolabeler.py:664-711, scripts/run_pseudolabeler.py:77-107  cap_create_shared (n engines on one
  *                       (one generate per crop; here: micro-batches merged into passes)          weight store: engine.EnginePool)
  *   load options        blip2.py:19-22 `load_in_8bit=True, torch_dtype=float16`;       CapConfig.weight_int8 (int8 Linear weights as
@@ -197,6 +199,28 @@ int cap_last_decode_steps(CapHandle h);
 int cap_set_bad_words(CapHandle h, const int32_t* ids, const int32_t* offsets, int n_sequences, void* stream);
 /* The set in force: distinct single tokens and multi-token sequences (either pointer may be NULL). */
 int cap_bad_words(CapHandle h, int* n_single, int* n_multi);
+
+/* Repetition controls of the decode loops: HF `generate(repetition_penalty=p, no_repeat_ngram_size=n)` (RepetitionPenaltyLogitsProcessor,
+ * NoRepeatNGramLogitsProcessor), applied on the device inside the token selection.  Handle state, like cap_set_bad_words: two numbers
+ * that hold for every generating call that follows; (1, 0) switches both off, and every launch is then what it was without them.
+ *   penalty p (finite, > 0)   every distinct token id of the caption's context that lies in [0, vocab) has its score x replaced by x * p
+ *                             if x < 0, else x / p - once, however often it occurs; fp32, a true division
+ *   n-gram size n (>= 1)      every token that followed an earlier occurrence of the context's last n - 1 tokens is banned (-inf); n = 1
+ *                             bans every context token; nothing is banned while the context is shorter than n - 1
+ * Order: penalty, n-grams, bad words.  Greedy: on the raw fp32 row, then the arg-max (first maximal index; a row with nothing left
+ * selects 0).  Beam search: log-softmax of the RAW row, the penalty on the log-probs (lp * p), the bans, then the running score.
+ * The context is what HF's processors see: BLIP's BOS, prompt and generated tokens; BLIP-2's num_query_tokens image placeholders
+ * (cap_set_image_token gives their id; required before a control is switched on), BOS and generated tokens - so BLIP-2's BOS and
+ * placeholder scores are penalised from the first step on, and where BOS and EOS are one id (OPT's 2) so is EOS.  The ban set's own
+ * context is unchanged.  out_step_logits stays the raw logits; cap_score_captions ignores the controls.
+ * Refused by name here: a non-finite or non-positive penalty, a negative size, a size above max_len plus the prefix (BLIP-2:
+ * num_query_tokens + 1).  With a control on, the generating calls refuse by name: a CAP_ARCH_COCA handle (its loop does not apply
+ * them), beam groups, out_logprobs / out_vocab. */
+int cap_set_repeat_controls(CapHandle h, float repetition_penalty, int no_repeat_ngram_size);
+int cap_repeat_controls(CapHandle h, float* repetition_penalty, int* no_repeat_ngram_size);   /* either pointer may be NULL */
+/* CAP_ARCH_BLIP2: the id HF puts num_query_tokens times in front of BOS (Blip2Config.image_token_index); context for the repetition
+ * controls only.  An id at or beyond the vocabulary is legal (no processor acts on it). */
+int cap_set_image_token(CapHandle h, int image_token);
 
 /* Which kernels the decode steps of cap_generate run on (CAP_ARCH_BLIP, split and bf16 modes).  The reference calls its captioner
  * with ONE crop per call (captioner/models/coca/coca.py:27-33, blip2/blip2.py:24-29, agents/goal_exploration/goal_exploration.py:
@@ -737,6 +761,18 @@ int cap_op_select_banned(const float* logits, int ld, int V, int R, int t, int m
 int cap_op_beam_step_banned(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
                             float length_penalty, int32_t* anc, int anc_ld, int mode, int min_len, const uint32_t* ban_bits,
                             const int32_t* ban_multi, int n_multi, void* stream);
+/* The processed forms alone (cap_set_repeat_controls): the banned forms with a penalty (1 = off) and an n-gram size (0 = off); ban_bits
+ * may be NULL (no static bitmap; n_multi is then 0).  A row's context is `vn` copies of `vtok`, then its stored history
+ * (cap_op_select_processed: seq[caption][hist0 .. t]; cap_op_beam_step_processed: its running sequence, columns 0 .. cur_len - 1),
+ * whose first token reads as vbos when vbos >= 0.  The ban sequences match the stored history alone.  HF v5 beam scores only.
+ * cap_op_select_processed takes any ld >= V (rows that are not 16-byte aligned are read element by element). */
+int cap_op_select_processed(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int32_t* finished,
+                            const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths, const uint32_t* ban_bits,
+                            const int32_t* ban_multi, int n_multi, int hist0, float penalty, int ngram, int vn, int vtok, int vbos,
+                            void* stream);
+int cap_op_beam_step_processed(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
+                               float length_penalty, int32_t* anc, int anc_ld, const uint32_t* ban_bits, const int32_t* ban_multi,
+                               int n_multi, float penalty, int ngram, int vn, int vtok, int vbos, void* stream);
 /* The group step of the probability fusion.  acc fp32 [N, acc_ld] (device); G groups in CSR form, both arrays on the device:
  * group_rows int32 [M] (row indices into acc, in the caller's order, need not be contiguous, each row in one group at most) and
  * group_off int32 [G + 1] (0 = off[0] <= ... <= off[G] = M; an empty group is legal).  Per group, in fp32,
