@@ -134,6 +134,14 @@ _SIGNATURES = {
     "cap_op_beam_step_processed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                              C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
                                              C.c_int, C.c_void_p]),
+    "cap_generate_sampled": (C.c_int, [C.c_void_p, C.POINTER(CapGenerateArgs), C.c_void_p, C.c_void_p]),
+    "cap_set_sampling": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64]),
+    "cap_sampling": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_float),
+                               C.POINTER(C.c_uint64)]),
+    "cap_op_select_sampled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int,
+                                        C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p]),
     "cap_set_decode_path": (C.c_int, [C.c_void_p, C.c_int]),
     "cap_last_decode_path": (C.c_int, [C.c_void_p]),
     "cap_set_row_compaction": (C.c_int, [C.c_void_p, C.c_int]),

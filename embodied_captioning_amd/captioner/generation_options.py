@@ -6,7 +6,12 @@ and HF ``GenerationMixin.generate`` behind ``blip2.py:26``.  What the library ru
 "top_k"`` with ``top_k=1`` - what the reference's wrapper calls, ``coca.py:29``; MinLength and forced EOS included) and beam search
 (HF v5 semantics for BLIP / BLIP-2, the reference's ``_generate_beamsearch`` incl. beam groups for CoCa).  Everything below is
 deterministic arg-max / beam arithmetic (``captioner.num_beams`` and, for BLIP and BLIP-2, ``captioner.length_penalty`` are the config keys;
-BLIP-2 searches with 1 to 8 beams like the other families and computes the prompt once per image, not once per beam); sampling, temperature and nucleus / top-k filtering are not built.
+BLIP-2 searches with 1 to 8 beams like the other families and computes the prompt once per image, not once per beam).
+Sampling (``do_sample``, ``temperature``, ``top_k > 1``, ``top_p``) IS built for BLIP and BLIP-2's greedy loop, as engine state
+(``CaptionerEngine.set_sampling``, the ``captioner.do_sample`` / ``temperature`` / ``top_k`` / ``top_p`` / ``sample_seed`` config keys; captioner/sampling.py):
+with it in force ``CaptionerEngine.generate`` takes the four keys out before this module sees them and accepts them when they equal the
+values in force.  This module's own judgement is unchanged - whoever still hands it the keys (CoCa, an engine that does not sample) gets
+them accepted at their neutral values only; beam sampling, CoCa's own sampling loop and the ``min_p`` / typical / eta / epsilon warpers are not built.
 ``bad_words_ids`` (HF ``NoBadWordsLogitsProcessor``) IS built, for BLIP and BLIP-2: it is engine state (``CaptionerEngine.set_bad_words``, the
 ``captioner.bad_words_ids`` / ``captioner.bad_words`` config keys) applied inside the token selection kernels, and ``generate(bad_words_ids=X)``
 is accepted when X equals the set in force; it is therefore no longer judged here.  CoCa refuses it by name (``CoCa.generate`` has no such

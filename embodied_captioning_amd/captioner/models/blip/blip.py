@@ -107,6 +107,11 @@ class BLIP(CaptioningPredictor):
         # (engine.set_repeat_controls); validated here, before an engine exists
         from ...repeat_controls import resolve_repeat_controls
         self.repetition_penalty, self.no_repeat_ngram_size = resolve_repeat_controls(cfg, self.arch, self.max_length)
+        # captioner.do_sample / temperature / top_k / top_p / sample_seed / num_return_sequences: HF generate(do_sample=True, ...) for
+        # every caption (engine.set_sampling); validated here, before an engine exists
+        from ...sampling import resolve_sampling
+        (self.do_sample, self.temperature, self.top_k, self.top_p, self.sample_seed,
+         self.num_return_sequences) = resolve_sampling(cfg, self.arch, self.batch_size, self.num_beams, "BLIP(cfg)")
         if getattr(cfg, "checkpoint_name", None):
             over = load_state_dict_file(cfg.checkpoint_name)
             for dst, src in BLIP_TIED.items():
@@ -157,6 +162,10 @@ class BLIP(CaptioningPredictor):
             self.engine.set_repeat_controls(self.repetition_penalty, self.no_repeat_ngram_size)
             if self.pool is not None:
                 self.pool.set_repeat_controls(self.repetition_penalty, self.no_repeat_ngram_size)
+        if self.do_sample:
+            self.engine.set_sampling(True, self.temperature, self.top_k, self.top_p, self.sample_seed)
+            if self.pool is not None:
+                self.pool.set_sampling(True, self.temperature, self.top_k, self.top_p, self.sample_seed)
 
     @staticmethod
     def _length_penalty(cfg) -> float:
@@ -244,8 +253,12 @@ class BLIP(CaptioningPredictor):
 
     @torch.no_grad()
     def generate_batch(self, images=None, output_logits: bool = False, output_perplexity: bool = False,
-                       output_vocab_maxprob: bool = False, prompt=None, prompt_ids=None, image_state=None) -> dict:
-        """image_state: the tensor `image_state(images)` returned (or rows of it), in place of images: the image side does not run.
+                       output_vocab_maxprob: bool = False, prompt=None, prompt_ids=None, image_state=None,
+                       num_return_sequences=None) -> dict:
+        """num_return_sequences = n (with captioner.do_sample; default = captioner.num_return_sequences): n sampled captions per image
+        from ONE image pass - texts / sequences hold N * n entries, image-major (HF's order); the images go in chunks of
+        batch_size // n so that every call's rows fit the engine.
+        image_state: the tensor `image_state(images)` returned (or rows of it), in place of images: the image side does not run.
         prompt (string) / prompt_ids (token ids [P], or [N, P] one row per image): the text every caption starts with, for this
         call; without them the configured captioner.prompt / captioner.prompt_ids (if any).  Texts and sequences include the prompt,
         per-step outputs cover the generated steps.
@@ -267,6 +280,15 @@ class BLIP(CaptioningPredictor):
             len(images) if isinstance(images, (list, tuple)) else 1
         pk = self._call_prompt(prompt, prompt_ids, n_images)
         bs = self.batch_size
+        nret = int(num_return_sequences if num_return_sequences is not None else getattr(self, "num_return_sequences", 1) or 1)
+        if nret < 1 or (nret > 1 and not getattr(self, "do_sample", False)):
+            raise ValueError(f"generate_batch: num_return_sequences = {nret} needs captioner.do_sample (and a count >= 1): the arg-max "
+                             f"loop returns one caption per image")
+        if nret > bs:
+            raise ValueError(f"generate_batch: num_return_sequences = {nret} exceeds batch_size = {bs}: one image's captions are rows of one call")
+        if nret > 1:
+            pool, bs = None, bs // nret          # images per call; the engine expands every image's state to nret decode rows
+            kw["num_return_sequences"] = nret
 
         def pkw(row0, n_rows):      # prompt_ids of the micro-batches that cover rows row0 .. row0 + n_rows - 1 (generate_many's list form)
             return {} if pk is None else {"prompt_ids": [pk(i, min(bs, row0 + n_rows - i)) for i in range(row0, row0 + n_rows, bs)]}
@@ -290,7 +312,7 @@ class BLIP(CaptioningPredictor):
                                                     max_length=self.max_length, **kw, **pkw(g * rnd, int(px.shape[0])))
         else:
             px = self.preprocess(images)
-            chunks = [px[i:i + self.batch_size].to(self._device) for i in range(0, px.shape[0], self.batch_size)]
+            chunks = [px[i:i + bs].to(self._device) for i in range(0, px.shape[0], bs)]
             if pool is not None and len(chunks) > 1 and not output_logits:
                 outs = self.pool.generate_many(chunks, threads=True, coalesce_rows=self.coalesce_rows, num_beams=self.num_beams,
                                                max_length=self.max_length, **kw, **pkw(0, int(px.shape[0])))

@@ -155,6 +155,10 @@ class BLIP2(BLIP):
         # captioner.repetition_penalty / captioner.no_repeat_ngram_size (as for BLIP): validated before an engine exists
         from ...repeat_controls import resolve_repeat_controls
         self.repetition_penalty, self.no_repeat_ngram_size = resolve_repeat_controls(cfg, self.arch, self.max_length)
+        # captioner.do_sample / temperature / top_k / top_p / sample_seed / num_return_sequences (as for BLIP)
+        from ...sampling import resolve_sampling
+        (self.do_sample, self.temperature, self.top_k, self.top_p, self.sample_seed,
+         self.num_return_sequences) = resolve_sampling(cfg, self.arch, self.batch_size, self.num_beams, "BLIP2(cfg)")
         self.engine = CaptionerEngine(self.arch, dtype=dtype, max_batch=self.batch_size, max_beams=self.num_beams, max_len=self.max_length,
                                       device=self._device, cross_cache=getattr(cfg, "cross_cache", None) or "auto",
                                       weight_int8=self.load_in_8bit)
@@ -198,6 +202,10 @@ class BLIP2(BLIP):
             self.engine.set_repeat_controls(self.repetition_penalty, self.no_repeat_ngram_size)
             if self.pool is not None:
                 self.pool.set_repeat_controls(self.repetition_penalty, self.no_repeat_ngram_size)
+        if self.do_sample:
+            self.engine.set_sampling(True, self.temperature, self.top_k, self.top_p, self.sample_seed)
+            if self.pool is not None:
+                self.pool.set_sampling(True, self.temperature, self.top_k, self.top_p, self.sample_seed)
 
     def decode(self, ids: Sequence[int]) -> str:
         if not hasattr(self.arch, "num_query_tokens"):

@@ -51,6 +51,8 @@ class CoCa(CaptioningPredictor):
         reject_bad_words_keys(cfg, "CoCa(cfg)")
         from ...repeat_controls import reject_ngram_key
         reject_ngram_key(cfg, "CoCa(cfg)")
+        from ...sampling import reject_sampling_keys
+        reject_sampling_keys(cfg, "CoCa(cfg)")
         if self.generation_options.get("generation_type") == "beam_search" and self.num_beams < 2:
             raise ValueError("CoCa(cfg): generation_type='beam_search' needs num_beams >= 2 (the reference's default is 6 in 3 groups)")
         dtype = getattr(cfg, "dtype", None) or "f32s"      # fp32-grade default (token-identical to the fp32 restatement); "bf16" is ~2x faster

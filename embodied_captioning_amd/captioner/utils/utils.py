@@ -15,7 +15,10 @@ repetition_penalty (the reference model's other `generate` options, coca_model.p
 ("top_k" with top_k=1 = greedy, "beam_search"), rejected by name otherwise - sampling is not implemented.  bad_words_ids / bad_words / bad_words_mode (BLIP, BLIP-2): banned token
 sequences / words of the decode loops, HF's `generate(bad_words_ids=)`.  repetition_penalty / no_repeat_ngram_size (BLIP, BLIP-2): HF's two
 repetition controls, applied inside the token selection kernels (CaptionerEngine.set_repeat_controls); CoCa takes repetition_penalty at 1.0
-only and refuses no_repeat_ngram_size by name."""
+only and refuses no_repeat_ngram_size by name.  do_sample / temperature / top_k / top_p / sample_seed / num_return_sequences (BLIP,
+BLIP-2): HF's `generate(do_sample=True, ...)` in the greedy loop, drawn inside the token selection kernel (CaptionerEngine.set_sampling;
+captioner/sampling.py); without do_sample the three warper keys are accepted at their neutral values only, and CoCa refuses all of them
+by name."""
 
 
 class Configuration:
@@ -31,7 +34,8 @@ class CaptionerField:
                  generation_type=None, top_k=None, top_p=None, temperature=None, repetition_penalty=None,
                  load_in_8bit=None, load_in_4bit=None, torch_dtype=None, cross_cache=None, strict_range=False,
                  coalesce_rows=None, device_resize=None, prompt=None, prompt_ids=None, max_prompt=None, length_penalty=None,
-                 max_score_rows=None, bad_words_ids=None, bad_words=None, bad_words_mode=None, no_repeat_ngram_size=None):
+                 max_score_rows=None, bad_words_ids=None, bad_words=None, bad_words_mode=None, no_repeat_ngram_size=None,
+                 do_sample=None, sample_seed=None, num_return_sequences=None):
         self.arch_name = arch_name
         self.model_name = model_name
         self.checkpoint_name = checkpoint_name
@@ -89,3 +93,9 @@ class CaptionerField:
         # BLIP / BLIP-2: HF `generate(no_repeat_ngram_size=)` on the device, with `repetition_penalty` above (captioner/
         # repeat_controls.py); None / 0 = off.  CoCa refuses the key by name (and any repetition_penalty but 1.0, as it always did).
         self.no_repeat_ngram_size = no_repeat_ngram_size
+        # BLIP / BLIP-2: HF `generate(do_sample=True, temperature=, top_k=, top_p=)` on the device, with `temperature` / `top_k` /
+        # `top_p` above (captioner/sampling.py); sample_seed = the Philox key (None = 0), num_return_sequences = captions per image of
+        # `generate_batch` (None = 1).  CoCa refuses the keys by name.
+        self.do_sample = do_sample
+        self.sample_seed = sample_seed
+        self.num_return_sequences = num_return_sequences

@@ -234,6 +234,9 @@ struct Captioner {
         if (c.arch == CAP_ARCH_BLIP2) { r.vn = c.num_query_tokens; r.vtok = image_token; r.vbos = c.bos; }
         return r;
     }
+    // sampling (cap_set_sampling; ops.h, SampleCtl): the greedy loop draws its tokens instead of taking the arg-max
+    bool sampling = false; SampleCtl sample_ctl;
+    const uint64_t* call_keys = nullptr;   // the keys of the call in flight (cap_generate_sampled; null: the row index)
     int last_steps = 0;          // decode steps the last cap_generate ran (cap_last_decode_steps)
     int decode_path = 0;         // cap_set_decode_path: 0 = by row count (<= SMALL_MAX_ROWS rows: the fused small-batch kernels),
                                  // 1 = always the batch kernels, 2 = always the small-batch kernels (an error beyond their row limit)
@@ -798,7 +801,13 @@ int select_greedy_step(Captioner* m, const CapGenerateArgs& a, int R, int step, 
     // the launch it has always been.
     // Repetition controls (cap_set_repeat_controls): the processed form, which also takes the ban set if there is one; its context puts
     // BLIP-2's image placeholders and BOS in front of the same columns (ops.h, RepeatCtl).
+    // Sampling (cap_set_sampling): the sampled form, which takes whatever else is in force; `step` is the draw's counter word and
+    // the call's sample keys (cap_generate_sampled; null: the row index) name the captions.  With sampling off every launch is the one it was.
     const int hist0 = c.arch == CAP_ARCH_BLIP2 ? c.num_query_tokens : 0;
+    if (m->sampling)
+        return launch_greedy_select_sampled(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s, 0,
+                                            0, map, m->banned() ? m->ban_set() : BanSet(), hist0, m->repeat_ctl(), m->sample_ctl,
+                                            m->call_keys, step);
     if (m->repeat_active())
         return launch_greedy_select_processed(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s, 0,
                                               0, map, m->banned() ? m->ban_set() : BanSet(), hist0, m->repeat_ctl());
@@ -2437,6 +2446,41 @@ int cap_set_image_token(CapHandle h, int image_token) {
     return 0;
 }
 
+int cap_set_sampling(CapHandle h, int on, float temperature, int top_k, float top_p, uint64_t seed) {
+    Captioner* m = (Captioner*)h;
+    const char* who = "cap_set_sampling";
+    if (!m) { cap_set_error("%s: null handle", who); return -1; }
+    const CapConfig& c = m->c;
+    if (!std::isfinite(temperature) || !(temperature > 0.f)) {
+        cap_set_error("%s: temperature = %g (a finite number above 0; 1 = neutral)", who, (double)temperature);
+        return -1;
+    }
+    if (top_k < 0) { cap_set_error("%s: top_k = %d (0 = off, or a count >= 1)", who, top_k); return -1; }
+    if (!(top_p > 0.f) || !(top_p <= 1.f)) { cap_set_error("%s: top_p = %g (in (0, 1]; 1 = off)", who, (double)top_p); return -1; }
+    if (on && c.arch != CAP_ARCH_BLIP && c.arch != CAP_ARCH_BLIP2 && c.arch != CAP_ARCH_COCA) {
+        cap_set_error("%s: this handle's arch (%d) has no decode loop", who, c.arch);
+        return -1;
+    }
+    if (on && c.arch == CAP_ARCH_BLIP2 && m->image_token < 0 && m->repeat_active()) {
+        cap_set_error("%s: a BLIP-2 handle with repetition controls needs cap_set_image_token first", who);
+        return -1;
+    }
+    m->sampling = on != 0;
+    m->sample_ctl.temperature = temperature; m->sample_ctl.top_k = top_k; m->sample_ctl.top_p = top_p; m->sample_ctl.seed = seed;
+    return 0;
+}
+
+int cap_sampling(CapHandle h, int* on, float* temperature, int* top_k, float* top_p, uint64_t* seed) {
+    const Captioner* m = (const Captioner*)h;
+    if (!m) { cap_set_error("cap_sampling: null handle"); return -1; }
+    if (on) *on = m->sampling ? 1 : 0;
+    if (temperature) *temperature = m->sample_ctl.temperature;
+    if (top_k) *top_k = m->sample_ctl.top_k;
+    if (top_p) *top_p = m->sample_ctl.top_p;
+    if (seed) *seed = m->sample_ctl.seed;
+    return 0;
+}
+
 int cap_last_decode_steps(CapHandle h) { return h ? ((Captioner*)h)->last_steps : -1; }
 
 int cap_set_decode_path(CapHandle h, int path) {
@@ -2767,6 +2811,8 @@ static int validate_generate(Captioner* m, const CapGenerateArgs& a, const char*
               "%s: bad words are set on this handle (cap_set_bad_words) and beam groups do not take them", who);
     REFUSE_IF(m->repeat_active() && G && c.arch != CAP_ARCH_COCA,
               "%s: repetition controls are set on this handle (cap_set_repeat_controls) and beam groups do not take them", who);
+    REFUSE_IF(m->sampling && G && c.arch != CAP_ARCH_COCA,
+              "%s: sampling is set on this handle (cap_set_sampling) and beam groups do not take it: beam sampling is not built", who);
     REFUSE_IF(G && c.arch != CAP_ARCH_COCA,
               "%s: beam groups are the CoCa loop's (coca_model.py:335-482); HF's group beam search for the other architectures needs a "
               "diversity penalty, which this library does not implement", who);
@@ -2786,6 +2832,17 @@ static int validate_generate(Captioner* m, const CapGenerateArgs& a, const char*
         REFUSE_IF(a.out_logprobs || a.out_scored || a.out_vocab,
                   "%s: repetition controls are set on this handle (cap_set_repeat_controls) and out_logprobs / out_vocab describe the raw "
                   "logits, which no longer describe the selection: reset the controls with (1, 0), or leave these outputs out", who);
+    }
+    if (m->sampling) {          // cap_set_sampling: BLIP and BLIP-2, the greedy loop, tokens only
+        REFUSE_IF(c.arch == CAP_ARCH_COCA,
+                  "%s: sampling is set on this handle (cap_set_sampling) and it is a CoCa captioner: CoCa's sampling loop is not built (BLIP "
+                  "and BLIP-2 only); switch it off with on = 0", who);
+        REFUSE_IF(G, "%s: sampling is set on this handle (cap_set_sampling) and beam groups do not take it: beam sampling is not built", who);
+        REFUSE_IF(K > 1, "%s: sampling is set on this handle (cap_set_sampling) and num_beams = %d: beam sampling is not built (num_beams = "
+                  "1 only)", who, K);
+        REFUSE_IF(a.out_logprobs || a.out_scored || a.out_vocab,
+                  "%s: sampling is set on this handle (cap_set_sampling) and out_logprobs / out_vocab describe the arg-max of the raw logits, "
+                  "which is not the selection: switch sampling off, or leave these outputs out", who);
     }
     REFUSE_IF(G < 0 || G > K || (G && K % G != 0), "%s: num_beams (%d) must be a multiple of num_beam_groups (%d) (BeamSearchScorer's own check)",
               who, K, G);
@@ -2832,6 +2889,16 @@ static int generate(CapHandle h, const CapGenerateArgs& a, void* stream, const c
 int cap_generate_request(CapHandle h, const CapGenerateArgs* args, void* stream) {
     if (!args) { cap_set_error("cap_generate_request: null request"); return -1; }
     return generate(h, *args, stream, "cap_generate_request", nullptr);
+}
+
+// The request with one key per caption for a handle that samples (cap_set_sampling): the keys hold for this call alone.
+int cap_generate_sampled(CapHandle h, const CapGenerateArgs* args, const uint64_t* sample_keys, void* stream) {
+    if (!args) { cap_set_error("cap_generate_sampled: null request"); return -1; }
+    Captioner* m = (Captioner*)h;
+    if (m) m->call_keys = sample_keys;
+    const int rc = generate(h, *args, stream, "cap_generate_sampled", nullptr);
+    if (m) m->call_keys = nullptr;
+    return rc;
 }
 
 // The five calls below fix parts of a request and leave the rest absent.
@@ -3412,6 +3479,31 @@ int cap_op_select_processed(const float* logits, int ld, int V, int R, int t, in
     map.live = live; map.n = n_live;
     return launch_greedy_select_processed(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, 0, 0,
                                           map, ban, hist0, ctl);
+}
+// The sampled form alone (tests/test_sampling_kernels_gpu.py): cap_op_select_processed with the draw in place of the arg-max.
+int cap_op_select_sampled(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int32_t* finished,
+                          const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths, const uint32_t* ban_bits,
+                          const int32_t* ban_multi, int n_multi, int hist0, float penalty, int ngram, int vn, int vtok, int vbos,
+                          float temperature, int top_k, float top_p, uint64_t seed, const uint64_t* keys, int draw, int32_t* out_kept,
+                          void* stream) {
+    const char* f = "cap_op_select_sampled";
+    if (!logits || !finished || !seq || !lengths) { cap_set_error("%s: null buffer (logits, finished, seq and lengths are required)", f); return -1; }
+    if (R < 1 || V < 1 || ld < V || t < 0 || t + 1 >= max_len || (live != nullptr) != (n_live != nullptr) || hist0 < 0 || hist0 > t + 1) {
+        cap_set_error("%s: bad arguments (ld = %d >= V = %d >= 1; hist0 = %d in [0, t + 1 = %d])", f, ld, V, hist0, t + 1);
+        return -1;
+    }
+    if (!std::isfinite(temperature) || !(temperature > 0.f)) { cap_set_error("%s: temperature = %g (a finite number above 0)", f, (double)temperature); return -1; }
+    if (top_k < 0) { cap_set_error("%s: top_k = %d (0 = off, or a count >= 1)", f, top_k); return -1; }
+    if (!(top_p > 0.f) || !(top_p <= 1.f)) { cap_set_error("%s: top_p = %g (in (0, 1]; 1 = off)", f, (double)top_p); return -1; }
+    if (draw < 0) { cap_set_error("%s: draw = %d (>= 0)", f, draw); return -1; }
+    RepeatCtl ctl; BanSet ban;
+    TRY(repeat_op_ctl(f, penalty, ngram, vn, vtok, vbos, ban_bits, ban_multi, n_multi, &ctl, &ban));
+    RowMap map;
+    map.live = live; map.n = n_live;
+    SampleCtl sc;
+    sc.temperature = temperature; sc.top_k = top_k; sc.top_p = top_p; sc.seed = seed;
+    return launch_greedy_select_sampled(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, 0, 0,
+                                        map, ban, hist0, ctl, sc, keys, draw, out_kept);
 }
 int cap_op_beam_step_processed(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
                                float length_penalty, int32_t* anc, int anc_ld, const uint32_t* ban_bits, const int32_t* ban_multi,

@@ -4,6 +4,7 @@
 #include <cmath>
 #include "ops.h"
 #include "ban.h"
+#include "sample.h"
 
 namespace {
 
@@ -524,6 +525,102 @@ __global__ __launch_bounds__(256) void greedy_select_processed_kernel(const floa
     const int imax = greedy_row_argmax<true, PEN>(logits + (size_t)crow * ld, V, eos, mask_eos, tid, sv, si, ban_bm, seen, ctl.penalty,
                                                   (ld & 3) == 0);
     if (tid == 0) greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
+}
+
+// Sampled form (ops.h, SampleCtl): the processed form with a draw from the row's distribution in place of the arg-max.  On the
+// processed scores s (penalty, bans; banned and NaN = -inf), in this order:
+//   z = s / T (fp32, a true division)                       top-k: keep z >= the k-th largest value, ties included (0 or >= V: off)
+//   w = (uint64)(expf(z - max z) * 2^40) on what is kept    top-p: W = sum w, R = floor((1 - (double)top_p) * (double)W); a value v stays
+//                                                           iff sum_{z_j <= v} w_j > R; the maximum always stays (1: off)
+//   draw: U = Philox4x32-10 (sample.h) of (seed, the caption's key, draw); r = mulhi64(U, sum of the remaining w); the token is the
+//   smallest id i with sum_{j <= i} w_j > r.  A row with nothing left selects 0, as the arg-max forms do.
+// From the weights on all arithmetic is integer (LDS integer atomics, an integer scan), so the token depends on the row, the
+// parameters, seed, key and draw alone - not on the grid, the row's position or the RowMap.  A token whose weight is below 2^-40 of
+// the maximal one has w = 0 and is never drawn.
+// Reads of the row (from L2 after the first; a row is at most 200 KB): 1 for the maximum, 4 per cut that is on (one per radix byte,
+// sample.h), 1 for the draw's per-thread sums (thread t owns the ids [t * S, (t + 1) * S), S = ceil(V / 256)) and one thread's walk
+// over its S entries: 2 + 1/256 with both cuts off, 10 + 1/256 with both on.  No float atomics; no early return after the bitmaps.
+template <bool PEN>
+__global__ __launch_bounds__(256) void greedy_select_sampled_kernel(const float* __restrict__ logits, int ld, int V,
+                                                                    int* __restrict__ seq, int seq_ld, int t, int max_len,
+                                                                    int eos, int pad, int* __restrict__ finished,
+                                                                    int* __restrict__ out_len, int min_len, int force_eos, RowMap map,
+                                                                    BanSet ban, int hist0, RepeatCtl ctl, SampleCtl sc,
+                                                                    const unsigned long long* __restrict__ keys, int draw,
+                                                                    int* __restrict__ out_kept) {
+    const int crow = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (map.n && crow >= *map.n) return;
+    const int row = map.live ? map.live[crow] : crow;
+    const int mask = (min_len > 0 && t + 1 < min_len) ? eos : -1;
+    extern __shared__ unsigned ban_bm[];                 // ban_words(V) words, twice with PEN
+    __shared__ SampleShared sh;
+    unsigned* seen = PEN ? ban_bm + ban_words(V) : nullptr;
+    const RowContext cx{seq + (size_t)row * seq_ld + hist0, max(t + 1 - hist0, 0), ctl.vn, ctl.vtok, ctl.vbos};
+    processed_bitmaps_fill(ban_bm, seen, V, ban, ctl.ngram, cx, tid);
+    const float* __restrict__ x = logits + (size_t)crow * ld;
+    const float T = sc.temperature, pen = ctl.penalty;
+
+    // the maximum (it is always kept)
+    unsigned mk = 0u;
+    for (int i0 = tid; i0 < V; i0 += 256 * SAMPLE_LOADS) {
+        float xv[SAMPLE_LOADS];
+#pragma unroll
+        for (int u = 0; u < SAMPLE_LOADS; ++u) xv[u] = i0 + u * 256 < V ? x[i0 + u * 256] : 0.f;
+#pragma unroll
+        for (int u = 0; u < SAMPLE_LOADS; ++u)
+            if (i0 + u * 256 < V) mk = max(mk, sample_zkey<PEN>(xv[u], i0 + u * 256, ban_bm, seen, pen, T, mask));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mk = max(mk, (unsigned)__shfl_xor((int)mk, o));
+    if (lane == 0) sh.mkey[wave] = mk;
+    if (tid == 0) { sh.token = 0; sh.kept = 0; }
+    __syncthreads();
+    const unsigned mkey = max(max(sh.mkey[0], sh.mkey[1]), max(sh.mkey[2], sh.mkey[3]));
+    const float m = sample_unkey(mkey);
+
+    unsigned keep_min = 0u;
+    if (sc.top_k > 0 && sc.top_k < V)                    // (uniform: kernel arguments)
+        keep_min = ~sample_radix_select<PEN, true>(x, V, ban_bm, seen, pen, T, mask, tid, (sample_u64)(sc.top_k - 1), 0.0, 0u, mkey, m, sh);
+    if (sc.top_p < 1.f)
+        keep_min = max(keep_min, sample_radix_select<PEN, false>(x, V, ban_bm, seen, pen, T, mask, tid, 0ull, 1.0 - (double)sc.top_p,
+                                                                 keep_min, mkey, m, sh));
+
+    // the draw: per-thread sums over contiguous ids, an integer scan, and the owner of r walks its segment
+    const int S = (V + 255) >> 8, lo = min(tid * S, V), hi = min(lo + S, V);
+    sample_u64 sum = 0ull;
+    int cnt = 0;
+    for (int i0 = lo; i0 < hi; i0 += SAMPLE_LOADS) {
+        float xv[SAMPLE_LOADS];
+#pragma unroll
+        for (int u = 0; u < SAMPLE_LOADS; ++u) xv[u] = i0 + u < hi ? x[i0 + u] : 0.f;
+#pragma unroll
+        for (int u = 0; u < SAMPLE_LOADS; ++u) {
+            if (i0 + u >= hi) continue;
+            const unsigned key = sample_zkey<PEN>(xv[u], i0 + u, ban_bm, seen, pen, T, mask);
+            const sample_u64 w = key >= keep_min ? sample_weight(key, mkey, m) : 0ull;
+            sum += w; cnt += w != 0ull;
+        }
+    }
+    sample_u64 total;
+    const sample_u64 incl = sample_block_scan(sum, tid, sh.ws, &total);
+    const sample_u64 U = sample_uniform(sc.seed, keys ? keys[row] : (sample_u64)row, (unsigned)draw);
+    const sample_u64 r = __umul64hi(U, total);
+    if (out_kept && cnt) atomicAdd(&sh.kept, cnt);
+    if (incl > r && incl - sum <= r) {                   // one thread at most; none when total = 0
+        sample_u64 acc = incl - sum;
+        int tok = hi - 1;
+        for (int i = lo; i < hi; ++i) {
+            const unsigned key = sample_zkey<PEN>(x[i], i, ban_bm, seen, pen, T, mask);
+            acc += key >= keep_min ? sample_weight(key, mkey, m) : 0ull;
+            if (acc > r) { tok = i; break; }
+        }
+        sh.token = tok;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        greedy_row_emit(row, sh.token, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
+        if (out_kept) out_kept[row] = sh.kept;
+    }
 }
 
 // Scoring form: the same selection, plus log max softmax of the row as the selection sees it (EOS masked while mask_eos) -
@@ -1091,6 +1188,41 @@ int launch_greedy_select_processed(const float* logits, int ld, int V, int* seq,
     else
         hipLaunchKernelGGL(greedy_select_processed_kernel<false>, dim3(R), dim3(256), bmb, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
                            pad, finished, out_len, min_len, force_eos, map, ban, hist0, ctl);
+    CAP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_greedy_select_sampled(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
+                                 int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
+                                 BanSet ban, int hist0, RepeatCtl ctl, SampleCtl sc, const uint64_t* keys, int draw, int* out_kept) {
+    if ((ban.n_multi && (!ban.multi || !ban.bits)) || ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI || hist0 < 0 || hist0 > t + 1) {
+        cap_set_error("greedy_select (sampled): %d multi-token sequences (at most %d, with a bitmap) or a history from column %d at step %d",
+                      ban.n_multi, BAN_MAX_MULTI, hist0, t);
+        return -1;
+    }
+    if (!(ctl.penalty > 0.f) || !std::isfinite(ctl.penalty) || ctl.ngram < 0 || ctl.vn < 0) {
+        cap_set_error("greedy_select (sampled): penalty %g (finite, > 0), n-gram size %d (>= 0), %d virtual context tokens (>= 0)",
+                      (double)ctl.penalty, ctl.ngram, ctl.vn);
+        return -1;
+    }
+    if (!(sc.temperature > 0.f) || !std::isfinite(sc.temperature)) {
+        cap_set_error("greedy_select (sampled): temperature = %g (a finite number above 0)", (double)sc.temperature);
+        return -1;
+    }
+    if (sc.top_k < 0) { cap_set_error("greedy_select (sampled): top_k = %d (0 = off, or >= 1)", sc.top_k); return -1; }
+    if (!(sc.top_p > 0.f) || !(sc.top_p <= 1.f)) {
+        cap_set_error("greedy_select (sampled): top_p = %g (in (0, 1]; 1 = off)", (double)sc.top_p);
+        return -1;
+    }
+    if (draw < 0) { cap_set_error("greedy_select (sampled): draw = %d (>= 0)", draw); return -1; }
+    const size_t bmb = (size_t)ban_words(V) * 4;
+    const unsigned long long* k = (const unsigned long long*)keys;
+    if (ctl.penalty != 1.f)
+        hipLaunchKernelGGL(greedy_select_sampled_kernel<true>, dim3(R), dim3(256), 2 * bmb, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
+                           pad, finished, out_len, min_len, force_eos, map, ban, hist0, ctl, sc, k, draw, out_kept);
+    else
+        hipLaunchKernelGGL(greedy_select_sampled_kernel<false>, dim3(R), dim3(256), bmb, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
+                           pad, finished, out_len, min_len, force_eos, map, ban, hist0, ctl, sc, k, draw, out_kept);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }

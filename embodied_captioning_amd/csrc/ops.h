@@ -106,6 +106,22 @@ struct RepeatCtl {
 int launch_greedy_select_processed(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
                                    int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
                                    BanSet ban, int hist0, RepeatCtl ctl);
+// Sampling (HF `generate(do_sample=True, temperature=, top_k=, top_p=)`; captioner_hip.h, cap_set_sampling), as the sampled form of
+// the greedy selection reads it: temperature (finite, > 0; 1 leaves the bits), top_k (0 or >= V: off), top_p in (0, 1] (1: off),
+// seed = the Philox key.  The distribution is stated step by step at greedy_select_sampled_kernel (elementwise.hip).
+struct SampleCtl {
+    float temperature = 1.f;
+    int top_k = 0;
+    float top_p = 1.f;
+    uint64_t seed = 0;
+};
+// launch_greedy_select_processed with a draw in place of the arg-max (ban.bits may be null, ctl may be neutral).  keys = uint64
+// [captions] (device), the per-CAPTION Philox counter words (null: the caption's row index), draw = the index of the generated token
+// (the other counter word); out_kept (null, or int32 [captions]): entries left with a weight above 0 after both cuts.
+int launch_greedy_select_sampled(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
+                                 int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
+                                 BanSet ban, int hist0, RepeatCtl ctl, SampleCtl sc, const uint64_t* keys, int draw,
+                                 int* out_kept = nullptr);
 // teacher-forced scoring: logits row b of `rows` (fp32 [rows, ld]) is pass row r = r0 + b = position r % npos of caption r / npos; for
 // positions below n_live[caption] the log-softmax at targets[caption * tgt_ld + position] (clamped to [0, V)), log max softmax and the
 // arg-max (launch_greedy_select's selection and tie rule, no EOS mask) go to out_*[caption * out_ld + position], zeros for the others

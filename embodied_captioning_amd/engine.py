@@ -13,12 +13,14 @@ import math
 import numbers
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _native as N
 from .config import Blip2Arch, Blip2ItmArch, BlipArch, ClipArch, CocaArch, MiniLMArch
 from .captioner.bad_words import validate_bad_words_ids  # noqa: F401 - the host check of set_bad_words, public here
 from .captioner.repeat_controls import validate_repeat_controls  # noqa: F401 - the host check of set_repeat_controls, public here
+from .captioner.sampling import default_sample_keys, keys_tensor, return_sequence_keys, validate_sampling  # noqa: F401 - public here
 
 logger = logging.getLogger(__name__)
 
@@ -559,6 +561,60 @@ class CaptionerEngine(_Engine):
         N.check(self.lib.cap_repeat_controls(self._h, C.byref(a), C.byref(b)), "cap_repeat_controls")
         return float(a.value), int(b.value)
 
+    def set_sampling(self, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> None:
+        """HF `generate(do_sample=True, temperature=, top_k=, top_p=)` for every greedy generating call that follows (BLIP and
+        BLIP-2, num_beams = 1, every decode path; `score` ignores it): the token of a step is drawn inside the selection kernel from
+        the processed row (repetition controls and bad words in force) divided by the temperature, cut to the top_k best values
+        (0 = off; ties stay) and to the nucleus of mass top_p (1.0 = off), by an inverse CDF over 40-bit fixed-point weights with a
+        Philox4x32-10 uniform of (seed, the caption's key, the step) - INTEGRATION.md section 6g.  A caption's tokens depend on its
+        logits, these numbers, its key and the step alone.  The defaults switch sampling off.  Validated on the host
+        (`validate_sampling`) first.  Setting resets the engine's call counter, which numbers the default keys.  With sampling on,
+        `generate` refuses beams, beam groups, output_logprobs / output_vocab_maxprob and a CoCa engine (by name)."""
+        on, t, k, p, sd = validate_sampling(do_sample, temperature, top_k, top_p, seed, self.arch)
+        N.check(self.lib.cap_set_sampling(self._h, int(on), C.c_float(t), int(k), C.c_float(p), C.c_uint64(sd)), "cap_set_sampling")
+        self._sampling = (on, t, k, p, sd)
+        self._sample_call_no = 0
+
+    _NO_SAMPLING = (False, 1.0, 0, 1.0, 0)
+
+    @property
+    def do_sample(self) -> bool:
+        """Whether the greedy loop draws its tokens (`set_sampling`)."""
+        return getattr(self, "_sampling", self._NO_SAMPLING)[0]
+
+    @property
+    def temperature(self) -> float:
+        """The temperature in force (`set_sampling`), as the fp32 number the kernel divides by."""
+        return getattr(self, "_sampling", self._NO_SAMPLING)[1]
+
+    @property
+    def top_k(self) -> int:
+        """The top-k count in force (`set_sampling`); 0 = off."""
+        return getattr(self, "_sampling", self._NO_SAMPLING)[2]
+
+    @property
+    def top_p(self) -> float:
+        """The nucleus mass in force (`set_sampling`), as the fp32 number the kernel reads; 1.0 = off."""
+        return getattr(self, "_sampling", self._NO_SAMPLING)[3]
+
+    @property
+    def sample_seed(self) -> int:
+        """The Philox key in force (`set_sampling`)."""
+        return getattr(self, "_sampling", self._NO_SAMPLING)[4]
+
+    @property
+    def sampling(self) -> tuple:
+        """(on, temperature, top_k, top_p, seed) as the library holds them (cap_sampling)."""
+        on, t, k, p, sd = C.c_int(0), C.c_float(0), C.c_int(0), C.c_float(0), C.c_uint64(0)
+        N.check(self.lib.cap_sampling(self._h, C.byref(on), C.byref(t), C.byref(k), C.byref(p), C.byref(sd)), "cap_sampling")
+        return bool(on.value), float(t.value), int(k.value), float(p.value), int(sd.value)
+
+    def next_sample_call(self) -> int:
+        """The number of the next call that takes default sample keys, and advance the counter (`set_sampling` resets it)."""
+        n = getattr(self, "_sample_call_no", 0)
+        self._sample_call_no = n + 1
+        return n
+
     @property
     def last_decode_steps(self) -> int:
         return int(self.lib.cap_last_decode_steps(self._h))
@@ -675,7 +731,8 @@ class CaptionerEngine(_Engine):
     def generate(self, pixels: torch.Tensor, num_beams: int = 1, max_length: Optional[int] = None,
                  length_penalty: float = 1.0, output_logits: bool = False, num_beam_groups: Optional[int] = None,
                  output_logprobs: bool = False, output_vocab_maxprob: bool = False, prompt_ids=None, bad_words_ids=None,
-                 repetition_penalty=None, no_repeat_ngram_size=None, **sampling_options) -> Dict[str, torch.Tensor]:
+                 repetition_penalty=None, no_repeat_ngram_size=None, sample_keys=None, num_return_sequences=None,
+                 **sampling_options) -> Dict[str, torch.Tensor]:
         """prompt_ids (BLIP, greedy): a host list / tensor [P], [1, P] (one prompt for every caption) or [B, P] (one per caption), column
         0 = BOS - HF `BlipForConditionalGeneration.generate(pixel_values, input_ids=...)`, whose decoder receives input_ids[:, :-1].
         Validated on the host (`validate_prompt_ids`).  max_length counts the prompt; `sequences` start with it and `lengths`
@@ -700,6 +757,14 @@ class CaptionerEngine(_Engine):
         otherwise - the set is engine state, not a per-call option.
         repetition_penalty / no_repeat_ngram_size: likewise accepted when they equal the values in force (`set_repeat_controls`; None =
         not given), refused by name otherwise; they never reach `reject_unsupported_generation_options`.
+        do_sample / temperature / top_k / top_p: with sampling in force (`set_sampling`) they are taken out of sampling_options and
+        accepted when they equal the values in force, refused by name otherwise - the sampling state is engine state too.  Without
+        it they go the way of every other sampling option below, as they always did.
+        sample_keys (sampling only): an int64 tensor [B], caption b's 64-bit key; the default is (call_no << 32) | b, call_no = the
+        number of default-keyed calls since `set_sampling` - repeated calls differ and are reproducible.  A call with given keys
+        does not advance the counter.
+        num_return_sequences = n (sampling only): `image_state` once, every record n times, keys (call_no << 32) | (b * n + r);
+        sequences [B * n, L], image-major (HF's order).  Refused by name when B * n exceeds max_batch.
         sampling_options: anything else a caller of the reference's / HF's `generate` may pass (top_p, top_k, temperature,
         repetition_penalty, do_sample, ...): accepted at their neutral values, rejected BY NAME otherwise - never ignored."""
         if output_vocab_maxprob and (num_beam_groups is not None or num_beams != 1):      # before anything is allocated or run
@@ -718,6 +783,44 @@ class CaptionerEngine(_Engine):
             if want != held:
                 raise ValueError(f"generate: {name} = {given!r} differs from the value in force on this engine ({held!r}): the repetition "
                                  f"controls are engine state - call set_repeat_controls first")
+        if self.do_sample:          # the four keys are engine state: taken out before the judgement of the unbuilt options
+            held = {"do_sample": True, "temperature": self.temperature, "top_k": self.top_k, "top_p": self.top_p}
+            for name in list(held):
+                if name not in sampling_options:
+                    continue
+                given = sampling_options.pop(name)
+                if given is None:
+                    continue
+                _, t_, k_, p_, _ = validate_sampling(True, given if name == "temperature" else None, given if name == "top_k" else None,
+                                                     given if name == "top_p" else None, None, self.arch)
+                want = {"do_sample": bool(given), "temperature": t_, "top_k": k_, "top_p": p_}[name]
+                if want != held[name]:
+                    raise ValueError(f"generate: {name} = {given!r} differs from the value in force on this engine ({held[name]!r}): the "
+                                     f"sampling state is engine state - call set_sampling first")
+        elif sample_keys is not None or num_return_sequences not in (None, 1):
+            raise ValueError("generate: " + ("sample_keys" if sample_keys is not None else f"num_return_sequences = {num_return_sequences!r}") +
+                             " needs sampling in force on this engine (set_sampling(do_sample=True, ...)): the arg-max loop takes no keys "
+                             "and returns one caption per image")
+        if num_return_sequences not in (None, 1):
+            n = num_return_sequences
+            if isinstance(n, bool) or not hasattr(n, "__index__") or int(n) < 1:
+                raise ValueError(f"generate: num_return_sequences must be an integer >= 1, got {n!r}")
+            n, B0 = int(n), int(pixels.shape[0])
+            if B0 * n > self.max_batch:
+                raise ValueError(f"generate: num_return_sequences = {n} for {B0} images is {B0 * n} decode rows, more than this engine's "
+                                 f"max_batch = {self.max_batch}")
+            if prompt_ids is not None:
+                prompt_ids = validate_prompt_ids(prompt_ids, self.arch, B0, max_length or self.max_len, num_beams, num_beam_groups,
+                                                 self.prompt_limit)
+                if prompt_ids.shape[0] == B0 and B0 > 1:
+                    prompt_ids = prompt_ids.repeat_interleave(n, dim=0)
+            state = pixels if is_image_state(pixels) else self.image_state(pixels)
+            if sample_keys is None:
+                sample_keys = torch.from_numpy(return_sequence_keys(self.next_sample_call(), B0, n).view(np.int64))
+            return self.generate(state.repeat_interleave(n, dim=0), num_beams=num_beams, max_length=max_length, length_penalty=length_penalty,
+                                 output_logits=output_logits, num_beam_groups=num_beam_groups, output_logprobs=output_logprobs,
+                                 output_vocab_maxprob=output_vocab_maxprob, prompt_ids=prompt_ids, sample_keys=sample_keys,
+                                 **sampling_options)
         if sampling_options:
             from .captioner.generation_options import reject_unsupported_generation_options, _NEUTRAL
             known = set(_NEUTRAL) | {"generation_type", "top_k", "top_p"}
@@ -735,7 +838,10 @@ class CaptionerEngine(_Engine):
         lens = torch.empty((B,), dtype=torch.int32, device=self.device)
         scores = torch.zeros((B,), dtype=torch.float32, device=self.device)
         steps = self._decode_steps(L)
-        logits = lps = scored = vmax = prompt_d = None
+        logits = lps = scored = vmax = prompt_d = keys_d = None
+        if self.do_sample:           # one key per caption: given, or numbered by the engine's call counter
+            keys_h = (keys_tensor(sample_keys, B) if sample_keys is not None else
+                      torch.from_numpy(default_sample_keys(self.next_sample_call(), B).view(np.int64)))
         if output_logits:
             # zeros, not empty: with early exit the steps after the last executed one are never written (callers see 0, not
             # stale memory); `last_decode_steps` tells how many steps ran
@@ -765,9 +871,15 @@ class CaptionerEngine(_Engine):
             if prompt is not None:
                 prompt_d = prompt.to(self.device, non_blocking=False)
                 req.prompt_ids, req.prompt_rows, req.prompt_len = prompt_d.data_ptr(), int(prompt.shape[0]), int(prompt.shape[1])
-            N.check(self.lib.cap_generate_request(self._h, C.byref(req), C.c_void_p(_stream_ptr(self.device))), "cap_generate_request")
-            if prompt_d is not None:
-                prompt_d.record_stream(torch.cuda.current_stream(self.device))
+            if self.do_sample:
+                keys_d = keys_h.to(self.device, non_blocking=False)
+                N.check(self.lib.cap_generate_sampled(self._h, C.byref(req), C.c_void_p(keys_d.data_ptr()),
+                                                      C.c_void_p(_stream_ptr(self.device))), "cap_generate_sampled")
+            else:
+                N.check(self.lib.cap_generate_request(self._h, C.byref(req), C.c_void_p(_stream_ptr(self.device))), "cap_generate_request")
+            for t_ in (prompt_d, keys_d):
+                if t_ is not None:
+                    t_.record_stream(torch.cuda.current_stream(self.device))
         if num_beam_groups is not None:
             return {"sequences": ids, "lengths": lens, "sequences_scores": scores}
         out = {"sequences": ids, "lengths": lens}
@@ -949,6 +1061,24 @@ class EnginePool:
     def no_repeat_ngram_size(self) -> int:
         return self.engines[0].no_repeat_ngram_size
 
+    def set_sampling(self, do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> None:
+        """`CaptionerEngine.set_sampling` on every engine; resets the POOL's call counter, which numbers the batches of
+        `generate_many` (batch j of a call takes call number counter + j, whichever engine or merged pass runs it)."""
+        for e in self.engines:
+            e.set_sampling(do_sample, temperature, top_k, top_p, seed)
+        self._sample_call_no = 0
+
+    @property
+    def do_sample(self) -> bool:
+        return self.engines[0].do_sample
+
+    def batch_sample_keys(self, rows: Sequence[int]) -> List[torch.Tensor]:
+        """The default keys of consecutive batches with these row counts, numbered from the pool's counter (which advances by their
+        number): batch j's caption r has key ((counter + j) << 32) | r - what `engine.generate` gives a lone call of that number."""
+        c0 = getattr(self, "_sample_call_no", 0)
+        self._sample_call_no = c0 + len(rows)
+        return [torch.from_numpy(default_sample_keys(c0 + j, int(r)).view(np.int64)) for j, r in enumerate(rows)]
+
     def set_row_compaction(self, on: bool) -> None:
         for e in self.engines:
             e.set_row_compaction(on)
@@ -1108,6 +1238,18 @@ class EnginePool:
                        for p, b in zip(given, batches)]
         else:
             generate_kw.pop("prompt_ids", None)
+        # sampling: every batch's keys are fixed HERE, before any plan - from the pool's own counter, or the caller's list with one
+        # tensor per batch - and travel with the batch, so the pooled and the merged results are a lone call's bits
+        keys = None
+        nret = int(generate_kw.get("num_return_sequences") or 1)
+        if getattr(self.engines[0], "do_sample", False):
+            given = generate_kw.pop("sample_keys", None)
+            if given is None:
+                keys = self.batch_sample_keys([int(b.shape[0]) * nret for b in batches])
+            else:
+                if not isinstance(given, (list, tuple)) or len(given) != len(batches):
+                    raise ValueError(f"sample_keys must be a list with one key tensor per batch ({len(batches)} batches)")
+                keys = [keys_tensor(k, int(b.shape[0]) * nret) for k, b in zip(given, batches)]
         if coalesce_rows and len(batches) > 1:
             same = all(b.shape[1:] == batches[0].shape[1:] and b.dtype == batches[0].dtype and b.device == batches[0].device for b in batches)
             cap_rows = min(coalesce_rows, min(e.max_batch for e in self.engines))
@@ -1117,18 +1259,25 @@ class EnginePool:
                 self.last_coalesce = "not applied: the batches differ in frame shape, dtype or device"
             else:
                 rows = [int(b.shape[0]) for b in batches]
+                if nret > 1:
+                    raise ValueError("generate_many: coalesce_rows with num_return_sequences > 1 is not built (an image's captions are "
+                                     "rows of its own batch); expand the image state and pass sample_keys instead")
                 plan = (self.coalesce_plan(rows, len(self.engines), cap_rows) if prompts is None else
                         self.coalesce_plan_prompted(rows, len(self.engines), cap_rows, [int(p.shape[1]) for p in prompts]))
                 if any(len(g) > 1 for g in plan):
                     merged = [batches[g[0]] if len(g) == 1 else torch.cat([batches[j] for j in g], dim=0) for g in plan]
                     if prompts is not None:
                         generate_kw = dict(generate_kw, prompt_ids=self.merge_prompts(plan, rows, prompts))
+                    if keys is not None:     # concatenated in plan order, as the frames are
+                        generate_kw = dict(generate_kw, sample_keys=[torch.cat([keys[j] for j in g]) for g in plan])
                     outs_m = self.generate_many(merged, threads=threads, **generate_kw)
                     self.last_coalesce = plan            # (the inner call cleared it)
                     return self.split_merged_outputs(plan, [int(b.shape[0]) for b in batches], outs_m)
                 self.last_coalesce = f"not applied: {len(batches)} batches on {len(self.engines)} engines leave nothing to merge within {cap_rows} rows"
             logger.debug("generate_many(coalesce_rows=%d) %s", coalesce_rows, self.last_coalesce)
-        kw_of = (lambda j: generate_kw) if prompts is None else (lambda j: dict(generate_kw, prompt_ids=prompts[j]))
+        def kw_of(j):
+            kw = generate_kw if prompts is None else dict(generate_kw, prompt_ids=prompts[j])
+            return kw if keys is None else dict(kw, sample_keys=keys[j])
         if not threads or len(self.engines) == 1 or len(batches) <= 1:
             outs = [self.submit(b, **kw_of(j)) for j, b in enumerate(batches)]
             self.join()

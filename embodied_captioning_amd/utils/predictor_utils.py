@@ -37,7 +37,8 @@ class Captioner(_Base):
                                               "streams", "early_exit_poll", "image_size", "num_beam_groups", "tokenizer_dir",
                                               "coalesce_rows", "cross_cache", "strict_range", "prompt", "prompt_ids", "max_prompt",
                                               "max_score_rows", "bad_words_ids", "bad_words", "bad_words_mode",
-                                              "repetition_penalty", "no_repeat_ngram_size")
+                                              "repetition_penalty", "no_repeat_ngram_size", "do_sample", "temperature", "top_k",
+                                              "top_p", "sample_seed", "num_return_sequences")
                  if hasattr(cfg, k)}
         captioner_cfg = Configuration(arch_name=cfg.arch_name, model_name=cfg.model_name,
                                       checkpoint_name=getattr(cfg, "checkpoint_name", None), height=cfg.height,

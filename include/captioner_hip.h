@@ -222,6 +222,32 @@ int cap_repeat_controls(CapHandle h, float* repetition_penalty, int* no_repeat_n
  * controls only.  An id at or beyond the vocabulary is legal (no processor acts on it). */
 int cap_set_image_token(CapHandle h, int image_token);
 
+/* Sampling in the greedy loop: HF `generate(do_sample=True, temperature=T, top_k=k, top_p=p)` (the reference's CoCa has a loop of its
+ * own, coca_model.py:266-275, 304-320; HF's sits behind its BLIP / BLIP-2 wrappers), on the device inside the token selection.  Handle
+ * state, like cap_set_repeat_controls: it holds for every generating call that follows; on = 0 switches it off (the numbers are kept
+ * and read back, nothing else), and every launch is then what it was without it.
+ * For an open caption at the step that produces its j-th generated token (j = HF's index into its `logits` tuple; prompt positions
+ * are not counted), on the raw fp32 logits row x:
+ *   1. s = processors(x): repetition penalty, n-gram bans, bad words as in force, HF's order; banned = -inf, a NaN stands as -inf
+ *   2. z_i = s_i / T, fp32, a true division (T = 1 leaves the bits)
+ *   3. top-k (0 or >= vocab: off): i stays iff z_i >= the k-th largest value - every entry tied with it stays
+ *   4. m = max z; w_i = (uint64)(expf(z_i - m) * 2^40) for what stays, 0 otherwise (accurate expf); integer arithmetic from here on
+ *   5. top-p (1: off), after top-k as HF orders its warpers: W = sum w, R = (uint64)floor((1.0 - (double)top_p) * (double)W); a value v
+ *      stays iff sum_{kept j, z_j <= v} w_j > R; the maximal value always stays (HF min_tokens_to_keep = 1).  On a tie-free row this
+ *      is HF TopPLogitsWarper's set; tied values stay or go together
+ *   6. W' = the remaining sum; U = a 64-bit uniform; r = the high 64 bits of U * W'; the token is the smallest id i with
+ *      sum_{j <= i} w_j > r (an inverse CDF in ascending id order).  A row with nothing left selects 0, as the arg-max forms do
+ * A token whose weight relative to the row's maximum is below 2^-40 has w = 0 and is never drawn.
+ * RNG: Philox4x32-10, counter (j, 0, key_lo, key_hi), key (seed_lo, seed_hi), U = (out0 << 32) | out1.  `key` is a per-CAPTION 64-bit
+ * value (cap_generate_sampled's sample_keys; NULL = the row index), never a row position: a caption's tokens depend on its logits, the
+ * parameters, seed, key and j alone - not on the batch, the grid, the row it sits in, the compacted loop or a pool's merged passes.
+ * Finished rows, pad after EOS, lengths, early exit: the greedy loop's, unchanged.  out_step_logits stays the raw logits;
+ * cap_score_captions ignores the state.
+ * Refused by name here: a non-finite or non-positive temperature, top_k < 0, top_p outside (0, 1].  With sampling on the generating
+ * calls refuse by name: num_beams > 1 or beam groups (beam sampling is not built), a CAP_ARCH_COCA handle, out_logprobs / out_vocab. */
+int cap_set_sampling(CapHandle h, int on, float temperature, int top_k, float top_p, uint64_t seed);
+int cap_sampling(CapHandle h, int* on, float* temperature, int* top_k, float* top_p, uint64_t* seed);   /* any pointer may be NULL */
+
 /* Which kernels the decode steps of cap_generate run on (CAP_ARCH_BLIP, split and bf16 modes).  The reference calls its captioner
  * with ONE crop per call (captioner/models/coca/coca.py:27-33, blip2/blip2.py:24-29, agents/goal_exploration/goal_exploration.py:
  * 95-105; BASELINE config 1: 8 crops): for images x beams <= 16 rows a decoder layer-step runs as 6 fused launches
@@ -364,6 +390,10 @@ typedef struct CapGenerateArgs {
                                   (max(max_batch x max_beams, max_batch x (max_prompt - 1))) - refused with the limit named */
 } CapGenerateArgs;
 int cap_generate_request(CapHandle h, const CapGenerateArgs* args, void* stream);
+/* cap_generate_request with one key per caption for a handle that samples (cap_set_sampling): sample_keys = uint64 [B] (device), caption
+ * b's key - two counter words of its Philox draws; NULL = the row index b, which is what every other generating call uses.  The
+ * keys hold for this call alone and are ignored with sampling off.  (CapGenerateArgs itself is unchanged.) */
+int cap_generate_sampled(CapHandle h, const CapGenerateArgs* args, const uint64_t* sample_keys, void* stream);
 
 /* Conveniences over cap_generate_request: each fills a CapGenerateArgs from its arguments, leaves the rest absent, and goes the same
  * way (messages name the call that was made).
@@ -773,6 +803,14 @@ int cap_op_select_processed(const float* logits, int ld, int V, int R, int t, in
 int cap_op_beam_step_processed(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
                                float length_penalty, int32_t* anc, int anc_ld, const uint32_t* ban_bits, const int32_t* ban_multi,
                                int n_multi, float penalty, int ngram, int vn, int vtok, int vbos, void* stream);
+/* The sampled form alone (cap_set_sampling): cap_op_select_processed's arguments, then the sampling parameters, seed, keys (uint64
+ * [captions], device; NULL = the caption's index) and draw (the counter word j), and out_kept (NULL, or int32 [captions]: the entries
+ * left with w > 0 after both cuts, written for every caption a logits row maps to). */
+int cap_op_select_sampled(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int32_t* finished,
+                          const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths, const uint32_t* ban_bits,
+                          const int32_t* ban_multi, int n_multi, int hist0, float penalty, int ngram, int vn, int vtok, int vbos,
+                          float temperature, int top_k, float top_p, uint64_t seed, const uint64_t* keys, int draw, int32_t* out_kept,
+                          void* stream);
 /* The group step of the probability fusion.  acc fp32 [N, acc_ld] (device); G groups in CSR form, both arrays on the device:
  * group_rows int32 [M] (row indices into acc, in the caller's order, need not be contiguous, each row in one group at most) and
  * group_off int32 [G + 1] (0 = off[0] <= ... <= off[G] = M; an empty group is legal).  Per group, in fp32,
