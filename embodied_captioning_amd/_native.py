@@ -72,6 +72,16 @@ class CapSmallCross(C.Structure):
     ]
 
 
+class CapGemmEpi(C.Structure):
+    _fields_ = [
+        ("A", C.c_void_p), ("lda", C.c_int32), ("W", C.c_void_p), ("ldw", C.c_int32), ("bias", C.c_void_p), ("C", C.c_void_p),
+        ("ldc", C.c_int32), ("C2", C.c_void_p), ("aux", C.c_void_p),
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("gelu", C.c_int32), ("out_f32", C.c_int32), ("epi", C.c_int32),
+        ("splitk", C.c_int32), ("p0", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("p3", C.c_int32), ("kv16", C.c_int32),
+        ("m_live", C.c_void_p), ("tile", C.c_int32),
+    ]
+
+
 class CapGenerateArgs(C.Structure):
     _fields_ = [
         ("pixels", C.c_void_p), ("pixel_fmt", C.c_int32), ("B", C.c_int32), ("num_beams", C.c_int32), ("num_beam_groups", C.c_int32),
@@ -188,6 +198,7 @@ _SIGNATURES = {
                                                C.c_int, C.c_void_p]),
     "cap_op_small_gemm": (C.c_int, [C.c_int, C.POINTER(CapSmallGemm), C.c_void_p]),
     "cap_op_small_cross": (C.c_int, [C.c_int, C.POINTER(CapSmallCross), C.c_void_p]),
+    "cap_op_gemm_epi": (C.c_int, [C.c_int, C.POINTER(CapGemmEpi), C.c_void_p]),
     "cap_op_beam_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
     "cap_op_beam_state_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

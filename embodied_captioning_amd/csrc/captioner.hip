@@ -3287,6 +3287,51 @@ int cap_op_gemm_crosskv(int dtype, const void* A, const void* W, const float* bi
     p.p0 = tokens; p.p1 = heads; p.p2 = n_img; p.kv16 = kv16;
     return launch_gemm(dt_of(dtype), p, 0, (hipStream_t)stream);
 }
+/* launch_gemm with the whole of GemmParams (tests/test_gemm_epilogues_gpu.py).  launch_gemm checks shapes and alignment, not what an
+   epilogue computes its addresses from: that is refused here, before anything is launched */
+int cap_op_gemm_epi(int dtype, const CapGemmEpi* a, void* stream) {
+    if (!a || !a->A || !a->W || !a->C) { cap_set_error("cap_op_gemm_epi: null pointer (A / W / C)"); return -1; }
+    const long long M = a->M, N = a->N;
+    switch (a->epi) {
+        case EPI_STORE:
+            if (a->ldc < a->N) { cap_set_error("cap_op_gemm_epi: store: ldc=%d < N=%d", a->ldc, a->N); return -1; }
+            break;
+        case EPI_PATCH:
+            if (!a->aux) { cap_set_error("cap_op_gemm_epi: patch: null aux (the position table)"); return -1; }
+            if (a->p0 < 1 || M % a->p0 != 0) { cap_set_error("cap_op_gemm_epi: patch: M=%d is not whole images of p0=%d patches", a->M, a->p0); return -1; }
+            if (a->ldc < a->N) { cap_set_error("cap_op_gemm_epi: patch: ldc=%d < N=%d", a->ldc, a->N); return -1; }
+            break;
+        case EPI_CROSSKV:
+            if (a->p0 < 1 || a->p1 < 1 || a->p2 < 1) {
+                cap_set_error("cap_op_gemm_epi: cross K/V: p0=%d tokens, p1=%d heads, p2=%d images must be positive", a->p0, a->p1, a->p2);
+                return -1;
+            }
+            if (M != (long long)a->p0 * a->p2) { cap_set_error("cap_op_gemm_epi: cross K/V: M=%d is not p0 * p2 = %d * %d", a->M, a->p0, a->p2); return -1; }
+            if (N % (2LL * a->p1 * 64) != 0) { cap_set_error("cap_op_gemm_epi: cross K/V: N=%d is not whole layers of 2 * p1=%d * 64 columns", a->N, a->p1); return -1; }
+            break;
+        case EPI_QKVCACHE:
+            if (!a->C2) { cap_set_error("cap_op_gemm_epi: q|k|v: null C2 (the cache)"); return -1; }
+            if (a->p1 < 1 || N != 3LL * a->p1 * 64) { cap_set_error("cap_op_gemm_epi: q|k|v: N=%d is not 3 * p1=%d * 64", a->N, a->p1); return -1; }
+            if (a->p0 < a->M) { cap_set_error("cap_op_gemm_epi: q|k|v: the cache holds p0=%d rows, M=%d", a->p0, a->M); return -1; }
+            if (a->p3 < 0 || a->p3 >= a->p2) { cap_set_error("cap_op_gemm_epi: q|k|v: position p3=%d outside [0, p2=%d)", a->p3, a->p2); return -1; }
+            break;
+        case EPI_PARTIAL:
+            if (a->splitk < 1) { cap_set_error("cap_op_gemm_epi: split-K: splitk=%d < 1", a->splitk); return -1; }
+            // (the slice index travels in p3 and the kernels with a slice loop set it themselves: the one without reads the host's)
+            if (a->p3 != 0) { cap_set_error("cap_op_gemm_epi: split-K: p3=%d must be 0 (the kernels number the slices)", a->p3); return -1; }
+            if (a->ldc < a->N) { cap_set_error("cap_op_gemm_epi: split-K: ldc=%d < N=%d", a->ldc, a->N); return -1; }
+            break;
+        default:
+            cap_set_error("cap_op_gemm_epi: unknown epi %d (0 store, 1 patch, 2 cross K/V, 3 q|k|v, 4 split-K)", a->epi);
+            return -1;
+    }
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.A = a->A; p.lda = a->lda; p.W = a->W; p.ldw = a->ldw; p.bias = a->bias; p.C = a->C; p.ldc = a->ldc; p.C2 = a->C2; p.aux = a->aux;
+    p.M = a->M; p.N = a->N; p.K = a->K; p.gelu = a->gelu; p.out_f32 = a->out_f32; p.epi = a->epi; p.splitk = a->splitk;
+    p.p0 = a->p0; p.p1 = a->p1; p.p2 = a->p2; p.p3 = a->p3; p.kv16 = a->kv16; p.m_live = a->m_live;
+    return launch_gemm(dt_of(dtype), p, a->tile, (hipStream_t)stream);
+}
 int cap_op_pack_kv16(const float* src, void* dst, size_t n_rows, void* stream) {
     return launch_pack_kv16(src, dst, n_rows, (hipStream_t)stream);
 }

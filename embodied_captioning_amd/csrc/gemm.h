@@ -21,7 +21,8 @@ struct GemmParams {
     int gelu;                      // activation after bias: 0 none, 1 exact-erf GELU, 2 ReLU, 3 quick GELU x * sigmoid(1.702 x) (CLIP)
     int out_f32;                   // 1: C is fp32, 0: C is T
     int epi;
-    int splitk;                    // EPI_PARTIAL only: number of K slices (K % (slab*splitk) == 0)
+    int splitk;                    // EPI_PARTIAL only: number of K slices (K % (slab*splitk) == 0).  The register-staged tiles and the
+                                   // rows kernel loop over slices; gemm_big_kernel does not: more than one slice there is refused
     // EPI_PATCH: p0 = patches per image, aux = position table [(P+1), N] fp32
     // EPI_CROSSKV: p0 = tokens per image, p1 = heads, p2 = images   (N = layers*2*heads*64)
     // EPI_QKVCACHE: p0 = row capacity of the cache, p1 = heads, p2 = max positions, p3 = position t; C2 = cache base

@@ -1050,6 +1050,16 @@ int launch_big2(const GemmParams& p, hipStream_t stream) {
 template <typename T, bool OUT_F32, int EPI, int VAR = 0>
 int launch_big(const GemmParams& p, hipStream_t stream) {
     constexpr int LDS = 2 * 512 * 128 + 2 * 1024;       // two stages + bias ping-pong
+    if constexpr (EPI == EPI_PARTIAL) {
+        // gemm_big_kernel walks the whole K (nk = K / SLAB) and never reads splitk: it would write the full sum to slice 0 and leave
+        // the other slices as they were.  One slice is the plain product and stays; more are refused here, where every route to
+        // this kernel ends (tiles 3 / 5, tile 0's choice of them, bf16 once gemm_pp.hip has declined the epilogue)
+        if (p.splitk > 1) {
+            cap_set_error("launch_gemm: split-K %d (EPI_PARTIAL) on the 256x256 LDS-DMA kernel, which has no K-slice loop "
+                          "(M=%d N=%d K=%d): tiles 1, 2, 4 and 6 take slices", p.splitk, p.M, p.N, p.K);
+            return -1;
+        }
+    }
     auto kern = gemm_big_kernel<T, OUT_F32, EPI, VAR>;
     int n_cu = 0;
     if (cap_kernel_setup((const void*)kern, LDS, &n_cu) != 0) return -1;

@@ -735,6 +735,35 @@ int cap_op_image_state_unpack(int kind, int slots, int heads, int tokens, int B,
    only): every (layer, k | v) block is a KV16 block of (n_img * heads * tokens + 31) / 32 groups, else fp32 / bf16 rows. */
 int cap_op_gemm_crosskv(int dtype, const void* A, const void* W, const float* bias, void* cache, int n_img, int tokens, int heads,
                         int layers, int K, int kv16, void* stream);
+/* launch_gemm with the whole of its parameter struct (csrc/gemm.h, GemmParams; no residual operand), field for field: every epilogue
+   on every tile, alone (tests/test_gemm_epilogues_gpu.py).  A [M, lda] x W [N, ldw]^T + bias [N] (may be NULL); tile as cap_op_gemm.
+     epi 0 store:     C [M, ldc] (out_f32: fp32, else the operand type), gelu = the activation.
+     epi 1 patch:     row (b, p) -> row b * (p0 + 1) + 1 + p of C fp32 [M / p0 * (p0 + 1), ldc], + aux[(1 + p) * N + col]; aux fp32
+                      [p0 + 1, N] is the position table, p0 the patches per image; row 0 of every image (the class token) is not written.
+     epi 2 cross K/V: C [N / (2 p1 64)][k | v][p2][p1][p0][64], p0 tokens, p1 heads, p2 images (M = p0 p2); element type: the operand
+                      type, fp32 for CAP_F32_SPLIT (kv16 = 1: KV16 blocks, as cap_op_gemm_crosskv).
+     epi 3 q|k|v:     columns [0, p1 64) -> C [M, p1 64] whatever ldc says; k | v columns -> C2 [k | v][p0][p1][p2][64] at position p3:
+                      p0 the row capacity of the cache (>= M), p1 heads, p2 positions; element type as epi 2.
+     epi 4 split-K:   C fp32 [splitk][M][ldc], slice z = the product over the z-th K range, no bias; m_live (device int32, or NULL):
+                      row tiles that start at or beyond *m_live are not written (epi 0 and 4; which kernels take it: cap_op_gemm_live).
+   launch_gemm checks shapes and alignment; the hook refuses, before anything is launched and under its own name, what would make an
+   epilogue compute an address outside its buffer: NULL A / W / C, ldc < N (epi 0, 1, 4), epi 1 NULL aux / p0 < 1 / M % p0, epi 2
+   p0, p1, p2 < 1 / M != p0 p2 / N % (2 p1 64), epi 3 NULL C2 / N != 3 p1 64 / p0 < M / p3 outside [0, p2), epi 4 splitk < 1, and
+   an epi outside 0..4. */
+typedef struct CapGemmEpi {
+    const void* A; int32_t lda;
+    const void* W; int32_t ldw;
+    const float* bias;
+    void* C; int32_t ldc;
+    void* C2;
+    const float* aux;
+    int32_t M, N, K, gelu, out_f32, epi, splitk;
+    int32_t p0, p1, p2, p3;
+    int32_t kv16;
+    const int32_t* m_live;
+    int32_t tile;
+} CapGemmEpi;
+int cap_op_gemm_epi(int dtype, const CapGemmEpi* args, void* stream);
 /* The candidate selection of a beam step alone (first step: running score 0 for beam 0 of an item, -1e9 for the others):
  * logits fp32 [B*K][ld] -> the 2K best (score, token) per row, best first, ties to the lower token id; legacy_raw: scores are
  * raw logits + running score (CoCa), else log-softmax + running score (HF v5); masked_id >= 0: that token scores -inf (legacy

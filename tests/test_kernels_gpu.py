@@ -413,8 +413,11 @@ def test_gemm_partial_row_tile_writes_nothing_outside_c(lib, dtype, tile):
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("geom", [(3, 197, 12, 2, 768), (2, 50, 2, 3, 128), (1, 197, 12, 1, 768)])
 def test_cross_kv_gemm_scatters_into_the_cache_layout(lib, dtype, geom):
-    """The cross-K/V GEMM (EPI_CROSSKV; bf16: gemm_pp.hip for >= 128 tiles, the register-staged tiles below) writes
-    [layer][k | v][image][head][token][64]: against the per-layer Linear calls it replaces (HF:modeling_blip_text.py:161-175)."""
+    """The cross-K/V GEMM (EPI_CROSSKV) writes [layer][k | v][image][head][token][64]: against the per-layer Linear calls it
+    replaces (HF:modeling_blip_text.py:161-175).  cap_op_gemm_crosskv launches with tile 0, and at these three geometries (M <= 591,
+    N <= 3072: at most 36 tiles of 256 x 256, 120 of 128 x 128) launch_gemm picks the register-staged 64 x 64 tile every time: this
+    test reaches neither the 128 x 128 / 256 x 256 tiles nor gemm_pp.hip.  The scatter on those kernels, tile by tile and with the
+    half-tile tail launch, is tests/test_gemm_epilogues_gpu.py::test_crosskv_epilogue*."""
     n_img, tokens, heads, layers, K = geom
     tag, tdt = DT[dtype]
     M, N = n_img * tokens, layers * 2 * heads * 64
