@@ -239,6 +239,22 @@ __global__ __launch_bounds__(256, 1) void vit_attention_flash_wide(const bf16_t*
 }
 
 // ------------------------------------------------------------------------------------------------
+// The denominator of a lane's online softmax, l = l * c + p, summed with compensation (Kahan): `comp` carries the rounding error of the
+// running sum.  In a row with one dominant key l sits at 1 while every other key adds 1e-9 .. 1e-7 - below half an ulp of l such a
+// term is lost, just above it it counts as a whole ulp, and because every term is positive the loss grows with the key count: 6e-5 of
+// the context at 577 / 1 025 keys (tests/test_attention_kernels_gpu.py, peaked class; 5e-6 with the compensation), 4e-5 at 300 keys in
+// vit_attention_scalar (tests/test_vit_attention_classes_gpu.py).  The context sum o has terms of both signs and stays within the
+// reference's own error without it.
+__device__ __forceinline__ void softmax_denominator_add(float& l, float& comp, float c, float p) {
+#pragma clang fp contract(off)
+    const float ls = l * c;
+    comp *= c;
+    const float y = p - comp;
+    const float t = ls + y;
+    comp = (t - ls) - y;
+    l = t;
+}
+
 constexpr int SC_KT = 128;   // keys per LDS tile
 template <typename T, typename TO = T>
 __global__ __launch_bounds__(256) void vit_attention_scalar(const T* __restrict__ qkv, TO* __restrict__ ctx, int N, int H) {
@@ -253,7 +269,7 @@ __global__ __launch_bounds__(256) void vit_attention_scalar(const T* __restrict_
     const int qc = min(q, N - 1);
 #pragma unroll
     for (int d = 0; d < 64; ++d) { qv[d] = to_f32(base[(size_t)qc * ld + d]) * 0.125f; o[d] = 0.f; }
-    float m = -INFINITY, l = 0.f;
+    float m = -INFINITY, l = 0.f, lc = 0.f;
     for (int k0 = 0; k0 < N; k0 += SC_KT) {
         const int nk = min(SC_KT, N - k0);
         __syncthreads();
@@ -269,14 +285,14 @@ __global__ __launch_bounds__(256) void vit_attention_scalar(const T* __restrict_
             for (int d = 0; d < 64; ++d) sc = fmaf(qv[d], Ks[j][d], sc);
             const float mn = fmaxf(m, sc);
             const float c = expf(m - mn), p = expf(sc - mn);
-            l = l * c + p;
+            softmax_denominator_add(l, lc, c, p);
 #pragma unroll
             for (int d = 0; d < 64; ++d) o[d] = fmaf(p, Vs[j][d], o[d] * c);
             m = mn;
         }
     }
     if (q < N) {
-        const float inv = 1.0f / l;
+        const float inv = 1.0f / (l - lc);
         TO* op = ctx + ((size_t)b * N + q) * D;
 #pragma unroll
         for (int d = 0; d < 64; d += 4)
@@ -855,21 +871,6 @@ __global__ __launch_bounds__(256, 2) void decode_attention_shared_kernel(const T
             store4(op, h * 64 + dch * 8 + 4, make_float4(o[b][4] * inv, o[b][5] * inv, o[b][6] * inv, o[b][7] * inv));
         }
     }
-}
-
-// The denominator of a lane's online softmax, l = l * c + p, summed with compensation (Kahan): `comp` carries the rounding error of the
-// running sum.  In a row with one dominant key l sits at 1 while every other key adds 1e-9 .. 1e-7 - below half an ulp of l such a
-// term is lost, just above it it counts as a whole ulp, and because every term is positive the loss grows with the key count: 6e-5 of
-// the context at 577 / 1 025 keys (tests/test_attention_kernels_gpu.py, peaked class; 5e-6 with the compensation).  The context sum o
-// has terms of both signs and stays within the reference's own error without it.
-__device__ __forceinline__ void softmax_denominator_add(float& l, float& comp, float c, float p) {
-#pragma clang fp contract(off)
-    const float ls = l * c;
-    comp *= c;
-    const float y = p - comp;
-    const float t = ls + y;
-    comp = (t - ls) - y;
-    l = t;
 }
 
 // ---- attentional pooler: Q learned queries (already layer-normed and projected on the host, identical for every

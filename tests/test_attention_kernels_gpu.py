@@ -19,25 +19,24 @@ Bars (derived, never taken from the kernel's output):
   G8 out     the fp32 bar + the container's own error for the case, max |g8_decode(g8_encode(ref32)) - ref32|.
 The peaked class at 257 .. 1 025 keys is what found the lane = query kernels' denominator losing 2^-24 of the row per key (up to 6.4e-5;
 softmax_denominator_add in csrc/attention.hip is the fix): every case is held to the bars above, none is raised.
+The reference, the classes and the bars live in tests/_attention_ref.py, shared with tests/test_vit_attention_classes_gpu.py.
 Run with -s for the table of maxima and bars (profiles/attention_kernels_gpu_tolerances.txt is that output)."""
 import ctypes as C
 import math
 
-import numpy as np
 import pytest
 import torch
 
-from _util import g8_decode, g8_encode
+from _attention_ref import BF16, F32, FAMILIES, SPLIT, _judge, _problem, _rounded, _rows, _sides, _slots
+from _util import g8_decode
 
 pytestmark = pytest.mark.gpu
 
-F32, BF16, SPLIT = 0, 1, 2
 DTYPES = [F32, BF16, SPLIT]
 DT_NAME = {F32: "f32", BF16: "bf16", SPLIT: "f32s"}
 CLASSES = ("randn", "rising", "peaked")
 NAN = float("nan")
 GUARD, CANARY = 256, 77.0            # canary bands of GUARD elements either side of every buffer a kernel writes
-MARGIN = 8.0
 
 @pytest.fixture(scope="module")
 def lib():
@@ -71,11 +70,6 @@ def _out_t(dtype):
     return torch.bfloat16 if dtype == BF16 else torch.float32      # a G8 container is float32-typed, one element per value
 
 
-def _rounded(x, dtype):
-    """fp32 values as the kernel's input type holds them."""
-    return x.to(torch.bfloat16).float() if dtype == BF16 else x.float()
-
-
 def _banded(values, tdtype):
     """values (CPU, any shape) -> (full, body): a device buffer with canary bands either side, body viewed in values' shape."""
     n = values.numel()
@@ -98,107 +92,6 @@ def _read(body, dtype):
     if dtype == SPLIT:
         return torch.from_numpy(g8_decode(body.cpu().numpy()))
     return body.float().cpu()
-
-
-def _rows(x):
-    """[B, H, L, hd] -> [B, L, H * hd], the row layout of every buffer here."""
-    B, H, L, hd = x.shape
-    return x.permute(0, 2, 1, 3).reshape(B, L, H * hd)
-
-
-# ---------------------------------------------------------------------------------------------- the reference and the bars
-def _attn(q, k, v, mask, scale, dt):
-    """softmax(scale q k^T + mask) v per (batch, head) in dtype dt.  q [B, H, Lq, hd], k / v [B, H, Lk, hd], mask bool, broadcastable to
-    [B, H, Lq, Lk], True = the query sees the key."""
-    q, k, v = q.to(dt), k.to(dt), v.to(dt)
-    s = (q @ k.transpose(-1, -2)) * torch.tensor(scale, dtype=dt)
-    s = s.masked_fill(~mask, float("-inf"))
-    return torch.softmax(s, -1) @ v
-
-
-def _reference(prob):
-    """(float64 reference [B, Lq, H * hd], ref_err_fp32)."""
-    ref = _attn(prob["q"], prob["k"], prob["v"], prob["mask"], prob["scale"], torch.float64)
-    r32 = _attn(prob["q"], prob["k"], prob["v"], prob["mask"], prob["scale"], torch.float32)
-    return _rows(ref), (r32.double() - ref).abs().max().item()
-
-
-def _problem(cls, B, H, Lq, Lk, hd, seed, peaks=(), mask=None, scale=None, dtype=F32):
-    """q, k, v of one input class, rounded to the input type of `dtype`.  peaked: slot s = b * H + h leads at key peaks[s % len]."""
-    g = torch.Generator().manual_seed(seed)
-    scale = 1.0 / math.sqrt(hd) if scale is None else scale
-    rn = lambda *s: torch.randn(*s, generator=g)      # noqa: E731
-    if cls == "randn":
-        q, k, v = rn(B, H, Lq, hd) * 1.5, rn(B, H, Lk, hd) * 1.5, rn(B, H, Lk, hd) * 1.5
-    else:
-        u = rn(B, H, 1, hd)
-        u = u / u.norm(dim=-1, keepdim=True) * math.sqrt(hd)          # u . u = hd: key beta u scores scale * beta * hd against query u
-        v = rn(B, H, Lk, hd) * 1.5
-        if cls == "rising":
-            q, k = u + 0.1 * rn(B, H, Lq, hd), 0.02 * rn(B, H, Lk, hd)
-            step = min(3.0, 96.0 / Lk)
-            k = k + (step * torch.arange(Lk, dtype=torch.float32) / (scale * hd)).view(1, 1, Lk, 1) * u
-        else:
-            q, k = u + 0.5 * rn(B, H, Lq, hd), 0.5 * rn(B, H, Lk, hd)
-            for s in range(B * H):
-                b, h = divmod(s, H)
-                k[b, h, peaks[s % len(peaks)]] += 20.0 / (scale * hd) * u[b, h, 0]
-    if mask is None:
-        mask = torch.ones(1, 1, 1, Lk, dtype=torch.bool)
-    return {"q": _rounded(q, dtype), "k": _rounded(k, dtype), "v": _rounded(v, dtype), "mask": mask, "scale": scale}
-
-
-def _sides(bounds, n):
-    """first key, last key and both sides of every boundary inside (0, n)."""
-    pos = {0, n - 1}
-    for b in bounds:
-        if 0 < b < n:
-            pos.update((b - 1, b))
-    return sorted(pos)
-
-
-def _slots(cls, peaks, H):
-    """batch size: peaked cases carry one (batch, head) slot per peak position, the others two batch rows."""
-    return max(2, -(-len(peaks) // H)) if cls == "peaked" else 2
-
-
-_FLOOR = {}
-
-
-def _floor(family):
-    """smallest non-zero ref_err_fp32 over the family's randn cases (both input roundings): the bar's base where a case's own is 0."""
-    if family not in _FLOOR:
-        errs = []
-        for case in FAMILIES[family]["cases"]:
-            for dt in (F32, BF16):
-                e = _reference(FAMILIES[family]["problem"](case, "randn", dt))[1]
-                if e > 0:
-                    errs.append(e)
-        _FLOOR[family] = min(errs)
-    return _FLOOR[family]
-
-
-def _judge(tag, family, case, cls, dtype, out, prob, keep=None):
-    """out [B, Lq, H * hd] fp32 CPU against the float64 reference; keep: bool [B, Lq] of the rows the contract defines.
-    Prints `max / bar`, asserts."""
-    ref, err32 = _reference(prob)
-    base = err32 if err32 > 0 else _floor(family)
-    bar = MARGIN * base
-    if keep is not None:
-        out, ref = out[keep], ref[keep]
-    assert torch.isfinite(out).all(), (tag, cls, "non-finite output")
-    diff = (out.double() - ref).abs()
-    if dtype == BF16:
-        worst = (diff - 2.0 ** -8 * ref.abs()).max().item()           # what is left after the final rounding's half ulp
-    elif dtype == SPLIT:
-        r32 = ref.float().numpy()
-        r32 = r32.reshape(-1, r32.shape[-1])
-        bar += float(np.abs(g8_decode(g8_encode(r32)) - r32).max())
-        worst = diff.max().item()
-    else:
-        worst = diff.max().item()
-    print(f"{tag:<58s} {cls:<6s} max {diff.max().item():.3e}  judged {worst: .3e}  bar {bar:.3e}  ref_err_fp32 {err32:.3e}")
-    assert worst <= bar, (tag, cls, worst, bar)
 
 
 # ---------------------------------------------------------------------------------------------- OPT decode step
@@ -766,7 +659,7 @@ def test_pool_attention_refuses_bad_widths(lib):
     _refused(lib, lib.cap_op_pool_attention(F32, _p(x), _p(x), _p(x), 1, 0, 2, 128, 2, _stream()), "pool_attention")
 
 
-FAMILIES = {
+FAMILIES.update({
     "opt": {"cases": [(hd, p) for hd in OPT_HD for p in OPT_PAST], "problem": _opt_problem},
     "kp": {"cases": [(hd, n, n) for hd in KP_HD for n in KP_SELF_N] + [(hd, lq, lk) for hd in KP_HD for lq, lk in KP_CROSS], "problem": _kp_problem},
     "lq_wide": {"cases": sorted({(hd, n) for _, hd, n in LQ_WIDE}), "problem": _lq_wide_problem},
@@ -774,4 +667,4 @@ FAMILIES = {
     "itm": {"cases": ITM_SHAPES, "problem": _itm_problem},
     "text": {"cases": TEXT_CASES, "problem": _text_problem},
     "pool": {"cases": POOL_CASES, "problem": _pool_problem},
-}
+})
