@@ -3674,5 +3674,30 @@ int cap_op_convert(int dtype, const float* src, void* dst, size_t n, void* strea
 int cap_op_convert_weight(int dtype, const float* src, void* dst, int rows, int cols, void* stream) {
     return launch_convert2d(dt_of(dtype), src, dst, rows, cols, cols, (hipStream_t)stream, dtype == CAP_F32_SPLIT ? G8_WSCALE : 1.0f);
 }
+/* the embedding and head kernels of the CLIP and BLIP-2 scorers alone (tests/test_scorer_kernels_gpu.py); the two score kernels are
+ * cap_clip_logits and cap_blip2_itc_scores */
+int cap_op_clip_embed_text(const int32_t* ids, int L, const float* tok, const float* pos, float* x, int M, int D, int V, void* stream) {
+    if (!ids || !tok || !pos || !x) { cap_set_error("cap_op_clip_embed_text: null pointer"); return -1; }
+    return launch_clip_embed_text(ids, L, tok, pos, x, M, D, V, (hipStream_t)stream);
+}
+int cap_op_clip_head(const float* x, int rows_per, const int32_t* lens, const float* gamma, const float* beta, float eps, const float* W,
+                     float* out, int B, int D, int P, void* stream) {
+    if (!x || !gamma || !beta || !W || !out) { cap_set_error("cap_op_clip_head: null pointer"); return -1; }
+    return launch_clip_head(x, rows_per, lens, gamma, beta, eps, W, out, B, D, P, (hipStream_t)stream);
+}
+int cap_op_itm_embed_text(int dtype, const int32_t* ids, int L, const float* word, const float* pos, const float* gamma,
+                          const float* beta, float eps, float* x_f, void* x_t, int M, int D, int V, void* stream) {
+    // the kernel writes both outputs unconditionally
+    if (!ids || !word || !pos || !gamma || !beta || !x_f || !x_t) { cap_set_error("cap_op_itm_embed_text: null pointer"); return -1; }
+    return launch_itm_embed_text(dt_of(dtype), ids, L, word, pos, gamma, beta, eps, x_f, x_t, M, D, V, (hipStream_t)stream);
+}
+int cap_op_itc_head(const float* x, int rows_per, const float* W, const float* bias, float* out, int n, int D, int P, void* stream) {
+    if (!x || !W || !bias || !out) { cap_set_error("cap_op_itc_head: null pointer"); return -1; }
+    return launch_itc_head(x, rows_per, W, bias, out, n, D, P, (hipStream_t)stream);
+}
+int cap_op_itm_head(const float* x, const float* W, const float* bias, float* logits, float* prob, int B, int nq, int D, void* stream) {
+    if (!x || !W || !bias || !logits) { cap_set_error("cap_op_itm_head: null pointer"); return -1; }
+    return launch_itm_head(x, W, bias, logits, prob, B, nq, D, (hipStream_t)stream);
+}
 
 }  // extern "C"

@@ -898,6 +898,27 @@ int cap_op_convert(int dtype, const float* src, void* dst, size_t n, void* strea
 /* Weight upload as cap_load_weight does it: dst [rows, cols] in the GEMM-operand type of `dtype` (CAP_F32_SPLIT: G8 halves of
  * 4096 * w - the split GEMM's epilogue divides by 4096; a G8 buffer is 4 bytes per element, cols % 8 == 0). */
 int cap_op_convert_weight(int dtype, const float* src, void* dst, int rows, int cols, void* stream);
+/* The embedding and head kernels of the CLIP and BLIP-2 scorers alone (tests/test_scorer_kernels_gpu.py); their score kernels are
+ * cap_clip_logits and cap_blip2_itc_scores above.  Device pointers, fp32 unless said otherwise; the hooks check pointers, every
+ * shape limit is the launcher's and is refused by the launcher's name.
+ *
+ * CLIP text embeddings: x [M, D] = tok[clamp(ids[r], 0, V - 1)] + pos[r % L], tok [V, D], pos [>= L, D]. */
+int cap_op_clip_embed_text(const int32_t* ids, int L, const float* tok, const float* pos, float* x, int M, int D, int V, void* stream);
+/* CLIP pooled head: row b * rows_per + (lens ? clamp(lens[b], 1, rows_per) - 1 : 0) of x [B * rows_per, D] -> LayerNorm (gamma,
+ * beta, eps) -> . W^T (W [P, D], no bias) -> divided by its L2 norm (no eps: a zero projection gives NaN, as HF does) -> out [B, P].
+ * lens may be NULL.  D, P <= 1024. */
+int cap_op_clip_head(const float* x, int rows_per, const int32_t* lens, const float* gamma, const float* beta, float eps, const float* W,
+                     float* out, int B, int D, int P, void* stream);
+/* BLIP-2 Q-Former text embeddings: LayerNorm(word[clamp(ids[r], 0, V - 1)] + pos[r % L]) -> x_f fp32 and x_t (dtype: CAP_F32 fp32,
+ * CAP_BF16 bf16, CAP_F32_SPLIT G8) [M, D], both required.  D % 8 == 0, D <= 1024. */
+int cap_op_itm_embed_text(int dtype, const int32_t* ids, int L, const float* word, const float* pos, const float* gamma,
+                          const float* beta, float eps, float* x_f, void* x_t, int M, int D, int V, void* stream);
+/* BLIP-2 ITC head: row r * rows_per of x -> . W^T + bias (W [P, D], bias [P]) -> F.normalize (eps 1e-12) -> out [n, P].
+ * D, P <= 1024. */
+int cap_op_itc_head(const float* x, int rows_per, const float* W, const float* bias, float* out, int n, int D, int P, void* stream);
+/* BLIP-2 ITM head: logits [B, 2] = mean over the nq rows of pair b of x [B * nq, D] . W^T + bias (W [2, D], bias [2]);
+ * prob [B] = softmax(logits)[1], may be NULL. */
+int cap_op_itm_head(const float* x, const float* W, const float* bias, float* logits, float* prob, int B, int nq, int D, void* stream);
 
 #ifdef __cplusplus
 }
