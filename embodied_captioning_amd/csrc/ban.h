@@ -1,6 +1,7 @@
 // The ban bitmap of one logits row (ops.h, BanSet), built by the row's 256-thread block in LDS: the static bitmap (tokens banned at
 // every step), then every multi-token sequence whose first n - 1 tokens are the tail of the row's history sets its last token's bit.
-// Shared by the banned forms of the greedy selection (elementwise.hip) and of the beam candidate kernels (beam.hip).
+// Shared by the processed and sampled forms of the greedy selection (elementwise.hip) and the banned and processed modes of the beam
+// candidate kernels (beam.hip).
 #pragma once
 #include "ops.h"
 

@@ -75,7 +75,7 @@ __global__ void beam_init_kernel(char* st, BeamLayout lo, int B, int K, int L, i
 __device__ __forceinline__ bool after(float v, int i, float pv, int pi) { return v < pv || (v == pv && i > pi); }
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
-// BAN (the *_banned kernels below; ops.h, BanSet): the block first builds the row's ban bitmap `bm` (LDS, ban_words(V) words) from the
+// BAN (every MODE but ROWS_PLAIN; ops.h, BanSet): the block first builds the row's ban bitmap `bm` (LDS, ban_words(V) words) from the
 // row's LOGICAL history run_seq[par][row][0 .. cur_len) - the beam's tokens after every re-ordering, not what the physical row wrote -
 // and a banned candidate's value is -inf.  The statistics passes never look at it: HF takes the log-softmax of the raw row, then bans.
 // MODE: ROWS_PLAIN, ROWS_BANNED, or ROWS_PROCESSED (ops.h, RepeatCtl): the bitmap also takes the n-gram bans of HF's context of the row
@@ -103,7 +103,7 @@ __device__ __forceinline__ float beam_value(float e, int i, int V, int raw, floa
 }
 
 template <int MODE>
-__device__ __forceinline__ void beam_rows_body(char* st, BeamLayout lo, const float* __restrict__ logits, int ld, int V, int K, int par,
+__device__ __forceinline__ void beam_rows_body(char* st, const BeamLayout& lo, const float* __restrict__ logits, int ld, int V, int K, int par,
                                                int raw, int eos_mask, unsigned* bm, BanSet ban, int L, int cur_len,
                                                RepeatCtl ctl = RepeatCtl()) {
     constexpr bool BAN = MODE != ROWS_PLAIN;
@@ -160,21 +160,19 @@ __device__ __forceinline__ void beam_rows_body(char* st, BeamLayout lo, const fl
     }
 }
 
-__global__ __launch_bounds__(256) void beam_rows_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
-                                                        int ld, int V, int K, int par, int raw, int eos_mask) {
-    beam_rows_body<ROWS_PLAIN>(st, lo, logits, ld, V, K, par, raw, eos_mask, nullptr, BanSet(), 0, 0);
-}
-__global__ __launch_bounds__(256) void beam_rows_banned_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
-                                                               int ld, int V, int K, int par, int raw, int eos_mask, BanSet ban,
-                                                               int L, int cur_len) {
+// What the rows kernels of every MODE take: the state block, the logits, the step, and what the MODE reads of ban / ctl.
+struct BeamRows {
+    char* st; BeamLayout lo;
+    const float* logits; int ld, V, K, par, raw, eos_mask;
+    BanSet ban; int L, cur_len;
+    RepeatCtl ctl;
+};
+// dynamic LDS (MODE != ROWS_PLAIN): ban_words(V) words, twice with a penalty.  ROWS_PROCESSED is HF v5 only: log-softmax scores, no EOS mask.
+template <int MODE>
+__global__ __launch_bounds__(256) void beam_rows_kernel(BeamRows a) {
     extern __shared__ unsigned ban_bm[];
-    beam_rows_body<ROWS_BANNED>(st, lo, logits, ld, V, K, par, raw, eos_mask, ban_bm, ban, L, cur_len);
-}
-__global__ __launch_bounds__(256) void beam_rows_processed_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
-                                                                  int ld, int V, int K, int par, BanSet ban, int L, int cur_len,
-                                                                  RepeatCtl ctl) {
-    extern __shared__ unsigned ban_bm[];                 // ban_words(V) words, twice with a penalty
-    beam_rows_body<ROWS_PROCESSED>(st, lo, logits, ld, V, K, par, 0, -1, ban_bm, ban, L, cur_len, ctl);
+    constexpr bool P = MODE == ROWS_PROCESSED;
+    beam_rows_body<MODE>(a.st, a.lo, a.logits, a.ld, a.V, a.K, a.par, P ? 0 : a.raw, P ? -1 : a.eos_mask, ban_bm, a.ban, a.L, a.cur_len, a.ctl);
 }
 
 // Single-pass variant of beam_rows_kernel: the row is read from global memory once (16-byte loads) into LDS; max, sum-exp
@@ -187,7 +185,7 @@ __global__ __launch_bounds__(256) void beam_rows_processed_kernel(char* st, Beam
 // all for raw-logit scores) - the 2K-pass fallback kernel took 874 us per step at 128 x 5 rows there.
 // MODE: as beam_rows_body - the bitmap(s) sit behind the candidate lists in the dynamic LDS.
 template <int CT, bool STAGE, int MODE>
-__device__ __forceinline__ void beam_rows_lds_body(char* st, BeamLayout lo, const float* __restrict__ logits, int ld, int V, int K,
+__device__ __forceinline__ void beam_rows_lds_body(char* st, const BeamLayout& lo, const float* __restrict__ logits, int ld, int V, int K,
                                                    int par, int raw, int eos_mask, BanSet ban, int L, int cur_len,
                                                    RepeatCtl ctl = RepeatCtl()) {
     constexpr bool BAN = MODE != ROWS_PLAIN;
@@ -384,22 +382,11 @@ __device__ __forceinline__ void beam_rows_lds_body(char* st, BeamLayout lo, cons
     }
 }
 
-template <int CT, bool STAGE = true>
-__global__ __launch_bounds__(256) void beam_rows_lds_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
-                                                            int ld, int V, int K, int par, int raw, int eos_mask) {
-    beam_rows_lds_body<CT, STAGE, ROWS_PLAIN>(st, lo, logits, ld, V, K, par, raw, eos_mask, BanSet(), 0, 0);
-}
-template <int CT, bool STAGE>
-__global__ __launch_bounds__(256) void beam_rows_lds_banned_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
-                                                                   int ld, int V, int K, int par, int raw, int eos_mask, BanSet ban,
-                                                                   int L, int cur_len) {
-    beam_rows_lds_body<CT, STAGE, ROWS_BANNED>(st, lo, logits, ld, V, K, par, raw, eos_mask, ban, L, cur_len);
-}
-template <int CT, bool STAGE>
-__global__ __launch_bounds__(256) void beam_rows_lds_processed_kernel(char* st, BeamLayout lo, const float* __restrict__ logits,
-                                                                      int ld, int V, int K, int par, BanSet ban, int L, int cur_len,
-                                                                      RepeatCtl ctl) {
-    beam_rows_lds_body<CT, STAGE, ROWS_PROCESSED>(st, lo, logits, ld, V, K, par, 0, -1, ban, L, cur_len, ctl);
+template <int CT, bool STAGE, int MODE>
+__global__ __launch_bounds__(256) void beam_rows_lds_kernel(BeamRows a) {
+    constexpr bool P = MODE == ROWS_PROCESSED;
+    beam_rows_lds_body<CT, STAGE, MODE>(a.st, a.lo, a.logits, a.ld, a.V, a.K, a.par, P ? 0 : a.raw, P ? -1 : a.eos_mask, a.ban, a.L, a.cur_len,
+                                        a.ctl);
 }
 
 // One 64-thread block per item.  The three selections of a step (top-2K continuations over the K candidate lists,
@@ -555,61 +542,29 @@ int launch_beam_init(void* state, int B, int K, int max_len, int bos, int pad, i
     return 0;
 }
 
-// The 2K best continuations of every running beam -> cand_val / cand_idx of the state block.
-static int launch_beam_rows(void* state, const BeamLayout& lo, const float* logits, int ld, int V, int B, int K, int par, int raw,
-                            int eos_mask, hipStream_t s) {
-    const size_t lds = (size_t)((V + 3) / 4) * 16 + (size_t)2 * K * 256 * 8;
-    if (lds <= 148 * 1024 && (ld & 3) == 0 && V > 2 * K) {
-        if (cap_kernel_setup((const void*)beam_rows_lds_kernel<4>, 148 * 1024, nullptr) != 0 ||
-            cap_kernel_setup((const void*)beam_rows_lds_kernel<8>, 148 * 1024, nullptr) != 0 ||
-            cap_kernel_setup((const void*)beam_rows_lds_kernel<16>, 148 * 1024, nullptr) != 0)
-            return -1;
-        if (2 * K <= 4)
-            hipLaunchKernelGGL(beam_rows_lds_kernel<4>, dim3(B * K), dim3(256), lds, s, (char*)state, lo, logits, ld, V, K, par, raw, eos_mask);
-        else if (2 * K <= 8)
-            hipLaunchKernelGGL(beam_rows_lds_kernel<8>, dim3(B * K), dim3(256), lds, s, (char*)state, lo, logits, ld, V, K, par, raw, eos_mask);
-        else
-            hipLaunchKernelGGL(beam_rows_lds_kernel<16>, dim3(B * K), dim3(256), lds, s, (char*)state, lo, logits, ld, V, K, par, raw, eos_mask);
-    } else if ((ld & 3) == 0 && V > 2 * K) {
-        const size_t lds2 = (size_t)2 * K * 256 * 8;                 // candidate lists only
-        if (2 * K <= 4)
-            hipLaunchKernelGGL((beam_rows_lds_kernel<4, false>), dim3(B * K), dim3(256), lds2, s, (char*)state, lo, logits, ld, V, K, par, raw, eos_mask);
-        else if (2 * K <= 8)
-            hipLaunchKernelGGL((beam_rows_lds_kernel<8, false>), dim3(B * K), dim3(256), lds2, s, (char*)state, lo, logits, ld, V, K, par, raw, eos_mask);
-        else
-            hipLaunchKernelGGL((beam_rows_lds_kernel<16, false>), dim3(B * K), dim3(256), lds2, s, (char*)state, lo, logits, ld, V, K, par, raw, eos_mask);
-    } else {
-        hipLaunchKernelGGL(beam_rows_kernel, dim3(B * K), dim3(256), 0, s, (char*)state, lo, logits, ld, V, K, par, raw, eos_mask);
-    }
-    CAP_HIP_CHECK(hipGetLastError());
+// The 2K best continuations of every running beam -> cand_val / cand_idx of the state block.  Three kernels: the row staged in LDS
+// beside the candidate lists and the MODE's bitmap(s) while they fit 148 KiB together, the candidate lists alone (the row read from
+// global memory) when they do not, and the plain 2K-pass kernel for rows without 16-byte loads (ld % 4 != 0) or V <= 2K.
+template <int CT, bool STAGE, int MODE>
+static int launch_beam_rows_lds(size_t lds, const BeamRows& a, int B, hipStream_t s) {
+    if (cap_kernel_setup((const void*)beam_rows_lds_kernel<CT, STAGE, MODE>, 148 * 1024, nullptr) != 0) return -1;
+    hipLaunchKernelGGL((beam_rows_lds_kernel<CT, STAGE, MODE>), dim3(B * a.K), dim3(256), lds, s, a);
     return 0;
 }
-
-// launch_beam_rows under a ban: the same three branches, the bitmap's ban_words(V) words behind each one's dynamic LDS - a row that
-// no longer fits beside it takes the candidate-lists form.
-template <int CT, bool STAGE>
-static int launch_beam_rows_lds_banned(size_t lds, void* state, const BeamLayout& lo, const float* logits, int ld, int V, int B, int K,
-                                       int par, int raw, int eos_mask, const BanSet& ban, int L, int cur_len, hipStream_t s) {
-    if (cap_kernel_setup((const void*)beam_rows_lds_banned_kernel<CT, STAGE>, 148 * 1024, nullptr) != 0) return -1;
-    hipLaunchKernelGGL((beam_rows_lds_banned_kernel<CT, STAGE>), dim3(B * K), dim3(256), lds, s, (char*)state, lo, logits, ld, V, K, par,
-                       raw, eos_mask, ban, L, cur_len);
-    return 0;
+template <bool STAGE, int MODE>
+static int launch_beam_rows_ct(size_t lds, const BeamRows& a, int B, hipStream_t s) {
+    return 2 * a.K <= 4   ? launch_beam_rows_lds<4, STAGE, MODE>(lds, a, B, s)
+           : 2 * a.K <= 8 ? launch_beam_rows_lds<8, STAGE, MODE>(lds, a, B, s)
+                          : launch_beam_rows_lds<16, STAGE, MODE>(lds, a, B, s);
 }
-static int launch_beam_rows_banned(void* state, const BeamLayout& lo, const float* logits, int ld, int V, int B, int K, int par, int raw,
-                                   int eos_mask, const BanSet& ban, int L, int cur_len, hipStream_t s) {
-    const size_t bmb = (size_t)ban_words(V) * 4, lists = (size_t)2 * K * 256 * 8;
-    const size_t lds = (size_t)((V + 3) / 4) * 16 + lists + bmb;
-    const bool fast = (ld & 3) == 0 && V > 2 * K;
-#define BANNED_ROWS(STAGE, bytes)                                                                                                       \
-    (2 * K <= 4   ? launch_beam_rows_lds_banned<4, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, raw, eos_mask, ban, L, cur_len, s)  \
-     : 2 * K <= 8 ? launch_beam_rows_lds_banned<8, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, raw, eos_mask, ban, L, cur_len, s)  \
-                  : launch_beam_rows_lds_banned<16, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, raw, eos_mask, ban, L, cur_len, s))
-    if (fast && lds <= 148 * 1024) { if (BANNED_ROWS(true, lds) != 0) return -1; }
-    else if (fast) { if (BANNED_ROWS(false, lists + bmb) != 0) return -1; }
-    else
-        hipLaunchKernelGGL(beam_rows_banned_kernel, dim3(B * K), dim3(256), bmb, s, (char*)state, lo, logits, ld, V, K, par, raw, eos_mask,
-                           ban, L, cur_len);
-#undef BANNED_ROWS
+template <int MODE>
+static int launch_beam_rows(const BeamRows& a, int B, hipStream_t s) {
+    const size_t bmb = MODE == ROWS_PLAIN ? 0 : (size_t)ban_words(a.V) * 4 * (MODE == ROWS_PROCESSED && a.ctl.penalty != 1.f ? 2 : 1);
+    const size_t lists = (size_t)2 * a.K * 256 * 8, lds = (size_t)((a.V + 3) / 4) * 16 + lists + bmb;
+    const bool fast = (a.ld & 3) == 0 && a.V > 2 * a.K;
+    if (fast && lds <= 148 * 1024) { if (launch_beam_rows_ct<true, MODE>(lds, a, B, s) != 0) return -1; }
+    else if (fast) { if (launch_beam_rows_ct<false, MODE>(lists + bmb, a, B, s) != 0) return -1; }
+    else hipLaunchKernelGGL(beam_rows_kernel<MODE>, dim3(B * a.K), dim3(256), bmb, s, a);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -617,66 +572,28 @@ static int launch_beam_rows_banned(void* state, const BeamLayout& lo, const floa
 static int launch_beam_merge(void* state, const BeamLayout& lo, int V, int B, int K, int max_len, int cur_len, int eos,
                              float length_penalty, int* anc, int anc_ld, int raw, hipStream_t s);
 
-// launch_beam_rows_banned with the repetition controls: the same three branches; a penalty's second bitmap counts in the LDS budget
-template <int CT, bool STAGE>
-static int launch_beam_rows_lds_processed(size_t lds, void* state, const BeamLayout& lo, const float* logits, int ld, int V, int B, int K,
-                                          int par, const BanSet& ban, int L, int cur_len, const RepeatCtl& ctl, hipStream_t s) {
-    if (cap_kernel_setup((const void*)beam_rows_lds_processed_kernel<CT, STAGE>, 148 * 1024, nullptr) != 0) return -1;
-    hipLaunchKernelGGL((beam_rows_lds_processed_kernel<CT, STAGE>), dim3(B * K), dim3(256), lds, s, (char*)state, lo, logits, ld, V, K, par,
-                       ban, L, cur_len, ctl);
-    return 0;
-}
-int launch_beam_step_processed(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
-                               float length_penalty, int* anc, int anc_ld, hipStream_t s, BanSet ban, RepeatCtl ctl) {
-    if ((ban.n_multi && (!ban.multi || !ban.bits)) || ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI) {
-        cap_set_error("beam_step (processed): %d multi-token sequences (at most %d, with a bitmap)", ban.n_multi, BAN_MAX_MULTI);
+int launch_beam_step(const BeamStep& st, hipStream_t s) {
+    const BanSet& ban = st.ban;
+    const RepeatCtl& ctl = st.ctl;
+    if (ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI || (ban.n_multi && (!ban.multi || !ban.bits))) {
+        cap_set_error("beam_step: n_multi = %d must be in [0, %d], with ban_multi and ban_bits", ban.n_multi, BAN_MAX_MULTI);
         return -1;
     }
     if (!(ctl.penalty > 0.f) || !std::isfinite(ctl.penalty) || ctl.ngram < 0 || ctl.vn < 0) {
-        cap_set_error("beam_step (processed): penalty %g (finite, > 0), n-gram size %d (>= 0), %d virtual context tokens (>= 0)",
-                      (double)ctl.penalty, ctl.ngram, ctl.vn);
+        cap_set_error("beam_step: penalty %g (finite, > 0), n-gram size %d (>= 0), %d virtual context tokens (>= 0)", (double)ctl.penalty,
+                      ctl.ngram, ctl.vn);
         return -1;
     }
-    const BeamLayout lo = beam_layout(B, K, max_len);
-    const int par = cur_len & 1, L = max_len;
-    const size_t bmb = (size_t)ban_words(V) * 4 * (ctl.penalty != 1.f ? 2 : 1), lists = (size_t)2 * K * 256 * 8;
-    const size_t lds = (size_t)((V + 3) / 4) * 16 + lists + bmb;
-    const bool fast = (ld & 3) == 0 && V > 2 * K;
-#define PROCESSED_ROWS(STAGE, bytes)                                                                                                   \
-    (2 * K <= 4   ? launch_beam_rows_lds_processed<4, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, ban, L, cur_len, ctl, s)       \
-     : 2 * K <= 8 ? launch_beam_rows_lds_processed<8, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, ban, L, cur_len, ctl, s)       \
-                  : launch_beam_rows_lds_processed<16, STAGE>(bytes, state, lo, logits, ld, V, B, K, par, ban, L, cur_len, ctl, s))
-    if (fast && lds <= 148 * 1024) { if (PROCESSED_ROWS(true, lds) != 0) return -1; }
-    else if (fast) { if (PROCESSED_ROWS(false, lists + bmb) != 0) return -1; }
-    else
-        hipLaunchKernelGGL(beam_rows_processed_kernel, dim3(B * K), dim3(256), bmb, s, (char*)state, lo, logits, ld, V, K, par, ban, L,
-                           cur_len, ctl);
-#undef PROCESSED_ROWS
-    CAP_HIP_CHECK(hipGetLastError());
-    return launch_beam_merge(state, lo, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, 0, s);
-}
-
-int launch_beam_step_banned(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
-                            float length_penalty, int* anc, int anc_ld, hipStream_t s, int mode, int min_len, BanSet ban) {
-    if (!ban.bits || (ban.n_multi && !ban.multi) || ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI) {
-        cap_set_error("beam_step (banned): no bitmap, or %d multi-token sequences (at most %d)", ban.n_multi, BAN_MAX_MULTI);
+    const int raw = st.mode == BEAM_LEGACY_RAW ? 1 : 0;
+    if (ctl.active() && raw) { cap_set_error("beam_step: the repetition controls go with HF v5 scores only (mode BEAM_LEGACY_RAW)"); return -1; }
+    const BeamLayout lo = beam_layout(st.B, st.K, st.max_len);
+    const int eos_mask = (raw && st.cur_len < st.min_len) ? st.eos : -1;       // MinLengthLogitsProcessor(min_len, eos)
+    const BeamRows a{(char*)st.state, lo, st.logits, st.ld, st.V, st.K, st.cur_len & 1, raw, eos_mask, ban, st.max_len, st.cur_len, ctl};
+    if ((ctl.active() ? launch_beam_rows<ROWS_PROCESSED>(a, st.B, s)
+         : ban.bits   ? launch_beam_rows<ROWS_BANNED>(a, st.B, s)
+                      : launch_beam_rows<ROWS_PLAIN>(a, st.B, s)) != 0)
         return -1;
-    }
-    const BeamLayout lo = beam_layout(B, K, max_len);
-    const int raw = mode == BEAM_LEGACY_RAW ? 1 : 0;
-    const int eos_mask = (raw && cur_len < min_len) ? eos : -1;
-    if (launch_beam_rows_banned(state, lo, logits, ld, V, B, K, cur_len & 1, raw, eos_mask, ban, max_len, cur_len, s) != 0) return -1;
-    return launch_beam_merge(state, lo, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, raw, s);
-}
-
-int launch_beam_step(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len,
-                     int eos, float length_penalty, int* anc, int anc_ld, hipStream_t s, int mode, int min_len) {
-    const BeamLayout lo = beam_layout(B, K, max_len);
-    const int par = cur_len & 1;
-    const int raw = mode == BEAM_LEGACY_RAW ? 1 : 0;
-    const int eos_mask = (raw && cur_len < min_len) ? eos : -1;       // MinLengthLogitsProcessor(min_len, eos)
-    if (launch_beam_rows(state, lo, logits, ld, V, B, K, par, raw, eos_mask, s) != 0) return -1;
-    return launch_beam_merge(state, lo, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, raw, s);
+    return launch_beam_merge(st.state, lo, st.V, st.B, st.K, st.max_len, st.cur_len, st.eos, st.length_penalty, st.anc, st.anc_ld, raw, s);
 }
 
 // The step's second half: merge the rows' candidate lists into the next running beams / finished pool / ancestry.
@@ -720,7 +637,8 @@ int beam_candidates_only(void* state, const float* logits, int ld, int V, int B,
                          int* out_idx, hipStream_t s) {
     const BeamLayout lo = beam_layout(B, K, 4);
     if (launch_beam_init(state, B, K, 4, 1, 0, 2, s, mode) != 0) return -1;
-    if (launch_beam_rows(state, lo, logits, ld, V, B, K, 0, mode == BEAM_LEGACY_RAW ? 1 : 0, eos_mask, s) != 0) return -1;
+    const BeamRows a{(char*)state, lo, logits, ld, V, K, 0, mode == BEAM_LEGACY_RAW ? 1 : 0, eos_mask, BanSet(), 0, 0, RepeatCtl()};
+    if (launch_beam_rows<ROWS_PLAIN>(a, B, s) != 0) return -1;
     CAP_HIP_CHECK(hipMemcpyAsync(out_val, (char*)state + lo.cand_val, (size_t)B * K * 2 * K * 4, hipMemcpyDeviceToDevice, s));
     CAP_HIP_CHECK(hipMemcpyAsync(out_idx, (char*)state + lo.cand_idx, (size_t)B * K * 2 * K * 4, hipMemcpyDeviceToDevice, s));
     return 0;

@@ -795,27 +795,40 @@ int select_greedy_step(Captioner* m, const CapGenerateArgs& a, int R, int step, 
                        hipStream_t s) {
     const CapConfig& c = m->c;
     const bool coca = c.arch == CAP_ARCH_COCA;
-    // a ban in force (cap_set_bad_words): the banned form, over the context HF's processor sees - BLIP's row from its BOS column on;
-    // BLIP-2's BOS and generated tokens: the generated columns and the one before them, which stands for BOS (it holds pad, and
-    // neither id is in any sequence).  validate_generate refused the log-prob / vocabulary outputs and CoCa; with nothing set this is
-    // the launch it has always been.
-    // Repetition controls (cap_set_repeat_controls): the processed form, which also takes the ban set if there is one; its context puts
-    // BLIP-2's image placeholders and BOS in front of the same columns (ops.h, RepeatCtl).
-    // Sampling (cap_set_sampling): the sampled form, which takes whatever else is in force; `step` is the draw's counter word and
-    // the call's sample keys (cap_generate_sampled; null: the row index) name the captions.  With sampling off every launch is the one it was.
-    const int hist0 = c.arch == CAP_ARCH_BLIP2 ? c.num_query_tokens : 0;
-    if (m->sampling)
-        return launch_greedy_select_sampled(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s, 0,
-                                            0, map, m->banned() ? m->ban_set() : BanSet(), hist0, m->repeat_ctl(), m->sample_ctl,
-                                            m->call_keys, step);
-    if (m->repeat_active())
-        return launch_greedy_select_processed(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s, 0,
-                                              0, map, m->banned() ? m->ban_set() : BanSet(), hist0, m->repeat_ctl());
-    if (m->banned())
-        return launch_greedy_select_banned(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s, 0, 0,
-                                           map, m->ban_set(), hist0);
-    return launch_greedy_select(m->logits, m->ldl, c.vocab, m->seq, seq_ld, t, end, c.eos, c.pad, m->finished, m->lens, R, s,
-                                coca ? c.min_len : 0, coca ? 1 : 0, map, a.out_logprobs, cols, step, a.out_scored, a.out_vocab, a.acc_ld);
+    SelectStep st{};
+    st.logits = m->logits; st.ld = m->ldl; st.V = c.vocab;
+    st.seq = m->seq; st.seq_ld = seq_ld; st.t = t; st.max_len = end; st.eos = c.eos; st.pad = c.pad;
+    st.finished = m->finished; st.out_len = m->lens; st.R = R; st.map = map;
+    st.min_len = coca ? c.min_len : 0; st.force_eos = coca ? 1 : 0;
+    // a ban in force (cap_set_bad_words) works over the context HF's processor sees - BLIP's row from its BOS column on; BLIP-2's BOS
+    // and generated tokens: the generated columns and the one before them, which stands for BOS (it holds pad, and neither id is in
+    // any sequence).  The repetition controls (cap_set_repeat_controls) put BLIP-2's image placeholders and BOS in front of the same
+    // columns (ops.h, RepeatCtl).
+    st.hist0 = c.arch == CAP_ARCH_BLIP2 ? c.num_query_tokens : 0;
+    if (m->banned()) st.ban = m->ban_set();
+    st.ctl = m->repeat_ctl();
+    // sampling (cap_set_sampling): `step` is the draw's counter word and the call's sample keys (cap_generate_sampled; null: the row
+    // index) name the captions
+    if (m->sampling) { st.sample = 1; st.sc = m->sample_ctl; st.keys = m->call_keys; st.draw = step; }
+    // validate_generate refused these outputs, and CoCa, beside any of the three; with nothing set this is the plain launch
+    st.logprobs = a.out_logprobs; st.lp_ld = cols; st.lp_col = step; st.scored = a.out_scored;
+    st.vocab_acc = a.out_vocab; st.acc_ld = a.acc_ld;
+    return launch_select_step(st, s);
+}
+
+// One beam step over logits [B * K, ldl] with L token columns (the ancestry table's row length too) and whatever ban set and
+// repetition controls are in force (never CoCa: validate_generate); CoCa: raw-logit scores and the MinLength mask.
+int engine_beam_step(Captioner* m, const CapGenerateArgs& a, void* state, const float* logits, int* anc, int B, int K, int L, int cur_len,
+                     hipStream_t s) {
+    const CapConfig& c = m->c;
+    const bool coca = c.arch == CAP_ARCH_COCA;
+    BeamStep st{};
+    st.state = state; st.logits = logits; st.ld = m->ldl; st.V = c.vocab; st.B = B; st.K = K; st.max_len = L; st.cur_len = cur_len;
+    st.eos = c.eos; st.length_penalty = a.length_penalty; st.anc = anc; st.anc_ld = L;
+    st.mode = coca ? BEAM_LEGACY_RAW : BEAM_HF_V5; st.min_len = coca ? c.min_len : 0;
+    if (m->banned()) st.ban = m->ban_set();
+    st.ctl = m->repeat_ctl();
+    return launch_beam_step(st, s);
 }
 
 // ---------------------------------------------------------------------------------------------- BLIP-2 OPT
@@ -1704,15 +1717,7 @@ int run_generate(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
             TRY(select_greedy_step(m, a, R, t - t0, Lm - 1, Lm, t, Lm, d.map, s));
             if (compact) TRY(launch_compact_rows(d.finished, R, m->live, m->n_live, s));
         } else {
-            if (m->repeat_active())      // (never CoCa: validate_generate)
-                TRY(launch_beam_step_processed(d.beam, d.logits, m->ldl, c.vocab, B, K, Lm, cur_len, c.eos, a.length_penalty, d.anc, Lm, s,
-                                               m->banned() ? m->ban_set() : BanSet(), m->repeat_ctl()));
-            else if (m->banned())
-                TRY(launch_beam_step_banned(d.beam, d.logits, m->ldl, c.vocab, B, K, Lm, cur_len, c.eos, a.length_penalty, d.anc, Lm, s,
-                                            BEAM_HF_V5, 0, m->ban_set()));
-            else
-                TRY(launch_beam_step(d.beam, d.logits, m->ldl, c.vocab, B, K, Lm, cur_len, c.eos, a.length_penalty, d.anc, Lm, s,
-                                     coca ? BEAM_LEGACY_RAW : BEAM_HF_V5, coca ? c.min_len : 0));
+            TRY(engine_beam_step(m, a, d.beam, d.logits, d.anc, B, K, Lm, cur_len, s));
         }
         bool done;
         TRY(poll_all_finished(m, t, Lm - 1, d.finished, R, greedy ? nullptr : beam_active_flag_p(d.beam, B, K, Lm), s, &done));
@@ -1991,14 +1996,7 @@ int run_beams_blip2(Captioner* m, const CapGenerateArgs& a, hipStream_t s) {
         TRY(copy_step_logits(m, a, R, t, s));
         {
             ProfScope ps(m, s, "beam_step", 0, (double)R * c.vocab * 4);
-            if (m->repeat_active())
-                TRY(launch_beam_step_processed(m->beam, m->logits, m->ldl, c.vocab, B, K, Lb, cur_len, c.eos, a.length_penalty, m->anc, Lb, s,
-                                               m->banned() ? m->ban_set() : BanSet(), m->repeat_ctl()));
-            else if (m->banned())
-                TRY(launch_beam_step_banned(m->beam, m->logits, m->ldl, c.vocab, B, K, Lb, cur_len, c.eos, a.length_penalty, m->anc, Lb, s,
-                                            BEAM_HF_V5, 0, m->ban_set()));
-            else
-                TRY(launch_beam_step(m->beam, m->logits, m->ldl, c.vocab, B, K, Lb, cur_len, c.eos, a.length_penalty, m->anc, Lb, s, BEAM_HF_V5, 0));
+            TRY(engine_beam_step(m, a, m->beam, m->logits, m->anc, B, K, Lb, cur_len, s));
         }
         if (t + 1 == max_len) break;
         {
@@ -3382,20 +3380,28 @@ int cap_op_beam_init(void* state, int B, int K, int max_len, int bos, int pad, i
     if (mode != BEAM_HF_V5 && mode != BEAM_LEGACY_RAW) { cap_set_error("cap_op_beam_init: mode = %d (0: HF v5, 1: legacy raw)", mode); return -1; }
     return launch_beam_init(state, B, K, max_len, bos, pad, eos, (hipStream_t)stream, mode);
 }
-int cap_op_beam_step(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
-                     float length_penalty, int32_t* anc, int anc_ld, int mode, int min_len, void* stream) {
-    TRY(beam_op_args("cap_op_beam_step", state, B, K, max_len));
-    if (!logits) { cap_set_error("cap_op_beam_step: logits is null"); return -1; }
-    if (V < 1 || ld < V) { cap_set_error("cap_op_beam_step: ld = %d, V = %d (ld >= V >= 1)", ld, V); return -1; }
+// What the three cap_op_beam_step* forms check alike, and the BeamStep they fill
+static int beam_op_step(const char* f, BeamStep* st, void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len,
+                        int eos, float length_penalty, int32_t* anc, int anc_ld, int mode, int min_len) {
+    TRY(beam_op_args(f, state, B, K, max_len));
+    if (!logits) { cap_set_error("%s: logits is null", f); return -1; }
+    if (V < 1 || ld < V) { cap_set_error("%s: ld = %d, V = %d (ld >= V >= 1)", f, ld, V); return -1; }
     // cur_len is the position the step writes (the running sequences hold cur_len tokens, BOS included): step t = cur_len - 1
     if (cur_len - 1 < 0 || cur_len - 1 >= max_len - 1) {
-        cap_set_error("cap_op_beam_step: cur_len = %d (step cur_len - 1 must satisfy 0 <= step < max_len - 1 = %d)", cur_len, max_len - 1);
+        cap_set_error("%s: cur_len = %d (step cur_len - 1 must satisfy 0 <= step < max_len - 1 = %d)", f, cur_len, max_len - 1);
         return -1;
     }
-    if (anc && anc_ld < 1) { cap_set_error("cap_op_beam_step: anc_ld = %d with an ancestry table (anc_ld >= 1)", anc_ld); return -1; }
-    if (mode != BEAM_HF_V5 && mode != BEAM_LEGACY_RAW) { cap_set_error("cap_op_beam_step: mode = %d (0: HF v5, 1: legacy raw)", mode); return -1; }
-    return launch_beam_step(state, logits, ld, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, (hipStream_t)stream, mode,
-                            min_len);
+    if (anc && anc_ld < 1) { cap_set_error("%s: anc_ld = %d with an ancestry table (anc_ld >= 1)", f, anc_ld); return -1; }
+    if (mode != BEAM_HF_V5 && mode != BEAM_LEGACY_RAW) { cap_set_error("%s: mode = %d (0: HF v5, 1: legacy raw)", f, mode); return -1; }
+    st->state = state; st->logits = logits; st->ld = ld; st->V = V; st->B = B; st->K = K; st->max_len = max_len; st->cur_len = cur_len;
+    st->eos = eos; st->length_penalty = length_penalty; st->anc = anc; st->anc_ld = anc_ld; st->mode = mode; st->min_len = min_len;
+    return 0;
+}
+int cap_op_beam_step(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
+                     float length_penalty, int32_t* anc, int anc_ld, int mode, int min_len, void* stream) {
+    BeamStep st{};
+    TRY(beam_op_step("cap_op_beam_step", &st, state, logits, ld, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, mode, min_len));
+    return launch_beam_step(st, (hipStream_t)stream);
 }
 int cap_op_beam_finalize(void* state, int B, int K, int max_len, int32_t* out_ids, int32_t* out_len, float* out_scores, void* stream) {
     TRY(beam_op_args("cap_op_beam_finalize", state, B, K, max_len));
@@ -3421,89 +3427,71 @@ int cap_op_target_logprob(const float* logits, int ld, int V, int rows, const in
     return launch_target_logprob(logits, ld, V, rows, 0, 1, targets, 1, live, out_target, out_top, out_top_id, 1, (hipStream_t)stream);
 }
 
+// What the five cap_op_select_* forms check alike, and the rows of the SelectStep they fill (seq rows of max_len tokens)
+static int select_op_rows(const char* f, SelectStep* st, const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad,
+                          int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths) {
+    if (!logits || !finished || !seq || !lengths) { cap_set_error("%s: null buffer (logits, finished, seq and lengths are required)", f); return -1; }
+    if (R < 1 || V < 1 || ld < V || t < 0 || t + 1 >= max_len || (live != nullptr) != (n_live != nullptr)) {
+        cap_set_error("%s: bad arguments (R = %d >= 1; ld = %d >= V = %d >= 1; 0 <= t = %d < max_len - 1 = %d; live and n_live together)", f, R, ld,
+                      V, t, max_len - 1);
+        return -1;
+    }
+    st->logits = logits; st->ld = ld; st->V = V; st->seq = seq; st->seq_ld = max_len; st->t = t; st->max_len = max_len; st->eos = eos;
+    st->pad = pad; st->finished = finished; st->out_len = lengths; st->R = R; st->map.live = live; st->map.n = n_live;
+    return 0;
+}
 int cap_op_select_logprob(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int min_len, int force_eos,
                           int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths,
                           float* logprobs, int lp_ld, int32_t* scored, void* stream) {
-    // ld % 4: the kernel reads rows with 16-byte loads (the engine's logits rows are padded the same way)
-    if (!logits || !finished || !seq || !lengths || R < 1 || V < 1 || ld < V || ld % 4 != 0 || t < 0 || t + 1 >= max_len ||
-        (logprobs != nullptr) != (scored != nullptr) || (live != nullptr) != (n_live != nullptr)) {
-        cap_set_error("cap_op_select_logprob: bad arguments");
-        return -1;
-    }
-    RowMap map;
-    map.live = live; map.n = n_live;
-    return launch_greedy_select(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, min_len,
-                                force_eos, map, logprobs, lp_ld, t, scored);
+    const char* f = "cap_op_select_logprob";
+    SelectStep st{};
+    TRY(select_op_rows(f, &st, logits, ld, V, R, t, max_len, eos, pad, finished, live, n_live, seq, lengths));
+    if ((logprobs != nullptr) != (scored != nullptr)) { cap_set_error("%s: logprobs and scored come together (both or neither)", f); return -1; }
+    st.min_len = min_len; st.force_eos = force_eos;
+    st.logprobs = logprobs; st.lp_ld = lp_ld; st.lp_col = t; st.scored = scored;
+    return launch_select_step(st, (hipStream_t)stream);
 }
 int cap_op_select_vocab(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int min_len, int force_eos,
                         int32_t* finished, const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths,
                         float* logprobs, int lp_ld, int32_t* scored, float* vocab_acc, int acc_ld, void* stream) {
-    if (!logits || !finished || !seq || !lengths || R < 1 || V < 1 || ld < V || ld % 4 != 0 || t < 0 || t + 1 >= max_len ||
-        !logprobs || !scored || !vocab_acc || (live != nullptr) != (n_live != nullptr)) {
-        cap_set_error("cap_op_select_vocab: bad arguments");
-        return -1;
-    }
-    RowMap map;
-    map.live = live; map.n = n_live;
-    return launch_greedy_select(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, min_len,
-                                force_eos, map, logprobs, lp_ld, t, scored, vocab_acc, acc_ld);
+    const char* f = "cap_op_select_vocab";
+    SelectStep st{};
+    TRY(select_op_rows(f, &st, logits, ld, V, R, t, max_len, eos, pad, finished, live, n_live, seq, lengths));
+    if (!logprobs || !scored || !vocab_acc) { cap_set_error("%s: null buffer (logprobs, scored and vocab_acc are required)", f); return -1; }
+    st.min_len = min_len; st.force_eos = force_eos;
+    st.logprobs = logprobs; st.lp_ld = lp_ld; st.lp_col = t; st.scored = scored;
+    st.vocab_acc = vocab_acc; st.acc_ld = acc_ld;
+    return launch_select_step(st, (hipStream_t)stream);
 }
-// The banned forms alone (tests/test_bad_words_kernels_gpu.py): the set comes as the device arrays the kernels read (ops.h, BanSet).
+// The banned forms alone (tests/test_bad_words_kernels_gpu.py): the set comes as the device arrays the kernels read (ops.h, BanSet),
+// and ban_bits is required.
 int cap_op_ban_words(int V) { return V < 1 ? -1 : ban_words(V); }
 int cap_op_select_banned(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int32_t* finished,
                          const int32_t* live, const int32_t* n_live, int32_t* seq, int32_t* lengths, const uint32_t* ban_bits,
                          const int32_t* ban_multi, int n_multi, int hist0, void* stream) {
-    if (!logits || !finished || !seq || !lengths || R < 1 || V < 1 || ld < V || ld % 4 != 0 || t < 0 || t + 1 >= max_len ||
-        (live != nullptr) != (n_live != nullptr)) {
-        cap_set_error("cap_op_select_banned: bad arguments");
-        return -1;
-    }
-    if (!ban_bits || n_multi < 0 || n_multi > BAN_MAX_MULTI || (n_multi > 0 && !ban_multi) || hist0 < 0 || hist0 > t + 1) {
-        cap_set_error("cap_op_select_banned: ban_bits is required, n_multi = %d must be in [0, %d] (with ban_multi), hist0 = %d in [0, t + 1 = %d]",
-                      n_multi, BAN_MAX_MULTI, hist0, t + 1);
-        return -1;
-    }
-    RowMap map;
-    map.live = live; map.n = n_live;
-    BanSet ban;
-    ban.bits = ban_bits; ban.multi = ban_multi; ban.n_multi = n_multi;
-    return launch_greedy_select_banned(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, 0, 0, map,
-                                       ban, hist0);
+    const char* f = "cap_op_select_banned";
+    SelectStep st{};
+    TRY(select_op_rows(f, &st, logits, ld, V, R, t, max_len, eos, pad, finished, live, n_live, seq, lengths));
+    if (!ban_bits) { cap_set_error("%s: ban_bits is required", f); return -1; }
+    st.ban.bits = ban_bits; st.ban.multi = ban_multi; st.ban.n_multi = n_multi; st.hist0 = hist0;
+    return launch_select_step(st, (hipStream_t)stream);
 }
 int cap_op_beam_step_banned(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
                             float length_penalty, int32_t* anc, int anc_ld, int mode, int min_len, const uint32_t* ban_bits,
                             const int32_t* ban_multi, int n_multi, void* stream) {
     const char* f = "cap_op_beam_step_banned";
-    TRY(beam_op_args(f, state, B, K, max_len));
-    if (!logits) { cap_set_error("%s: logits is null", f); return -1; }
-    if (V < 1 || ld < V) { cap_set_error("%s: ld = %d, V = %d (ld >= V >= 1)", f, ld, V); return -1; }
-    if (cur_len - 1 < 0 || cur_len - 1 >= max_len - 1) {
-        cap_set_error("%s: cur_len = %d (step cur_len - 1 must satisfy 0 <= step < max_len - 1 = %d)", f, cur_len, max_len - 1);
-        return -1;
-    }
-    if (anc && anc_ld < 1) { cap_set_error("%s: anc_ld = %d with an ancestry table (anc_ld >= 1)", f, anc_ld); return -1; }
-    if (mode != BEAM_HF_V5 && mode != BEAM_LEGACY_RAW) { cap_set_error("%s: mode = %d (0: HF v5, 1: legacy raw)", f, mode); return -1; }
-    if (!ban_bits || n_multi < 0 || n_multi > BAN_MAX_MULTI || (n_multi > 0 && !ban_multi)) {
-        cap_set_error("%s: ban_bits is required and n_multi = %d must be in [0, %d] (with ban_multi)", f, n_multi, BAN_MAX_MULTI);
-        return -1;
-    }
-    BanSet ban;
-    ban.bits = ban_bits; ban.multi = ban_multi; ban.n_multi = n_multi;
-    return launch_beam_step_banned(state, logits, ld, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, (hipStream_t)stream, mode,
-                                   min_len, ban);
+    BeamStep st{};
+    TRY(beam_op_step(f, &st, state, logits, ld, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, mode, min_len));
+    if (!ban_bits) { cap_set_error("%s: ban_bits is required", f); return -1; }
+    st.ban.bits = ban_bits; st.ban.multi = ban_multi; st.ban.n_multi = n_multi;
+    return launch_beam_step(st, (hipStream_t)stream);
 }
 // The processed forms alone (tests/test_repeat_controls_kernels_gpu.py): cap_op_select_banned / cap_op_beam_step_banned with the
-// repetition controls; ban_bits may be NULL (no static bitmap; n_multi must then be 0).
+// repetition controls; ban_bits may be NULL (no static bitmap; n_multi must then be 0).  The launchers check the values; the limit on
+// the virtual context is these entry points' own.
 static int repeat_op_ctl(const char* f, float penalty, int ngram, int vn, int vtok, int vbos, const uint32_t* ban_bits, const int32_t* ban_multi,
                          int n_multi, RepeatCtl* ctl, BanSet* ban) {
-    if (!std::isfinite(penalty) || !(penalty > 0.f) || ngram < 0 || vn < 0 || vn > 4096) {
-        cap_set_error("%s: penalty = %g (finite, > 0), n-gram size = %d (>= 0), %d virtual context tokens (0 .. 4096)", f, (double)penalty, ngram, vn);
-        return -1;
-    }
-    if (n_multi < 0 || n_multi > BAN_MAX_MULTI || (n_multi > 0 && (!ban_multi || !ban_bits))) {
-        cap_set_error("%s: n_multi = %d must be in [0, %d] (with ban_multi and ban_bits)", f, n_multi, BAN_MAX_MULTI);
-        return -1;
-    }
+    if (vn > 4096) { cap_set_error("%s: %d virtual context tokens (0 .. 4096)", f, vn); return -1; }
     ctl->penalty = penalty; ctl->ngram = ngram; ctl->vn = vn; ctl->vtok = vtok; ctl->vbos = vbos;
     ban->bits = ban_bits; ban->multi = ban_multi; ban->n_multi = n_multi;
     return 0;
@@ -3513,17 +3501,11 @@ int cap_op_select_processed(const float* logits, int ld, int V, int R, int t, in
                             const int32_t* ban_multi, int n_multi, int hist0, float penalty, int ngram, int vn, int vtok, int vbos,
                             void* stream) {
     const char* f = "cap_op_select_processed";
-    if (!logits || !finished || !seq || !lengths || R < 1 || V < 1 || ld < V || t < 0 || t + 1 >= max_len ||
-        (live != nullptr) != (n_live != nullptr) || hist0 < 0 || hist0 > t + 1) {
-        cap_set_error("%s: bad arguments (ld = %d >= V = %d >= 1; hist0 = %d in [0, t + 1 = %d])", f, ld, V, hist0, t + 1);
-        return -1;
-    }
-    RepeatCtl ctl; BanSet ban;
-    TRY(repeat_op_ctl(f, penalty, ngram, vn, vtok, vbos, ban_bits, ban_multi, n_multi, &ctl, &ban));
-    RowMap map;
-    map.live = live; map.n = n_live;
-    return launch_greedy_select_processed(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, 0, 0,
-                                          map, ban, hist0, ctl);
+    SelectStep st{};
+    TRY(select_op_rows(f, &st, logits, ld, V, R, t, max_len, eos, pad, finished, live, n_live, seq, lengths));
+    TRY(repeat_op_ctl(f, penalty, ngram, vn, vtok, vbos, ban_bits, ban_multi, n_multi, &st.ctl, &st.ban));
+    st.hist0 = hist0;
+    return launch_select_step(st, (hipStream_t)stream);
 }
 // The sampled form alone (tests/test_sampling_kernels_gpu.py): cap_op_select_processed with the draw in place of the arg-max.
 int cap_op_select_sampled(const float* logits, int ld, int V, int R, int t, int max_len, int eos, int pad, int32_t* finished,
@@ -3532,40 +3514,22 @@ int cap_op_select_sampled(const float* logits, int ld, int V, int R, int t, int 
                           float temperature, int top_k, float top_p, uint64_t seed, const uint64_t* keys, int draw, int32_t* out_kept,
                           void* stream) {
     const char* f = "cap_op_select_sampled";
-    if (!logits || !finished || !seq || !lengths) { cap_set_error("%s: null buffer (logits, finished, seq and lengths are required)", f); return -1; }
-    if (R < 1 || V < 1 || ld < V || t < 0 || t + 1 >= max_len || (live != nullptr) != (n_live != nullptr) || hist0 < 0 || hist0 > t + 1) {
-        cap_set_error("%s: bad arguments (ld = %d >= V = %d >= 1; hist0 = %d in [0, t + 1 = %d])", f, ld, V, hist0, t + 1);
-        return -1;
-    }
-    if (!std::isfinite(temperature) || !(temperature > 0.f)) { cap_set_error("%s: temperature = %g (a finite number above 0)", f, (double)temperature); return -1; }
-    if (top_k < 0) { cap_set_error("%s: top_k = %d (0 = off, or a count >= 1)", f, top_k); return -1; }
-    if (!(top_p > 0.f) || !(top_p <= 1.f)) { cap_set_error("%s: top_p = %g (in (0, 1]; 1 = off)", f, (double)top_p); return -1; }
-    if (draw < 0) { cap_set_error("%s: draw = %d (>= 0)", f, draw); return -1; }
-    RepeatCtl ctl; BanSet ban;
-    TRY(repeat_op_ctl(f, penalty, ngram, vn, vtok, vbos, ban_bits, ban_multi, n_multi, &ctl, &ban));
-    RowMap map;
-    map.live = live; map.n = n_live;
-    SampleCtl sc;
-    sc.temperature = temperature; sc.top_k = top_k; sc.top_p = top_p; sc.seed = seed;
-    return launch_greedy_select_sampled(logits, ld, V, seq, max_len, t, max_len, eos, pad, finished, lengths, R, (hipStream_t)stream, 0, 0,
-                                        map, ban, hist0, ctl, sc, keys, draw, out_kept);
+    SelectStep st{};
+    TRY(select_op_rows(f, &st, logits, ld, V, R, t, max_len, eos, pad, finished, live, n_live, seq, lengths));
+    TRY(repeat_op_ctl(f, penalty, ngram, vn, vtok, vbos, ban_bits, ban_multi, n_multi, &st.ctl, &st.ban));
+    st.hist0 = hist0;
+    st.sample = 1; st.sc.temperature = temperature; st.sc.top_k = top_k; st.sc.top_p = top_p; st.sc.seed = seed;
+    st.keys = keys; st.draw = draw; st.out_kept = out_kept;
+    return launch_select_step(st, (hipStream_t)stream);
 }
 int cap_op_beam_step_processed(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
                                float length_penalty, int32_t* anc, int anc_ld, const uint32_t* ban_bits, const int32_t* ban_multi,
                                int n_multi, float penalty, int ngram, int vn, int vtok, int vbos, void* stream) {
     const char* f = "cap_op_beam_step_processed";
-    TRY(beam_op_args(f, state, B, K, max_len));
-    if (!logits) { cap_set_error("%s: logits is null", f); return -1; }
-    if (V < 1 || ld < V) { cap_set_error("%s: ld = %d, V = %d (ld >= V >= 1)", f, ld, V); return -1; }
-    if (cur_len - 1 < 0 || cur_len - 1 >= max_len - 1) {
-        cap_set_error("%s: cur_len = %d (step cur_len - 1 must satisfy 0 <= step < max_len - 1 = %d)", f, cur_len, max_len - 1);
-        return -1;
-    }
-    if (anc && anc_ld < 1) { cap_set_error("%s: anc_ld = %d with an ancestry table (anc_ld >= 1)", f, anc_ld); return -1; }
-    RepeatCtl ctl; BanSet ban;
-    TRY(repeat_op_ctl(f, penalty, ngram, vn, vtok, vbos, ban_bits, ban_multi, n_multi, &ctl, &ban));
-    return launch_beam_step_processed(state, logits, ld, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, (hipStream_t)stream,
-                                      ban, ctl);
+    BeamStep st{};
+    TRY(beam_op_step(f, &st, state, logits, ld, V, B, K, max_len, cur_len, eos, length_penalty, anc, anc_ld, BEAM_HF_V5, 0));
+    TRY(repeat_op_ctl(f, penalty, ngram, vn, vtok, vbos, ban_bits, ban_multi, n_multi, &st.ctl, &st.ban));
+    return launch_beam_step(st, (hipStream_t)stream);
 }
 int cap_op_vocab_group_threshold(const float* acc, int acc_ld, int V, int N, const int32_t* group_rows, int M, const int32_t* group_off,
                                  int G, float th, int K, int32_t* out_ids, float* out_prob, int32_t* out_count, void* stream) {

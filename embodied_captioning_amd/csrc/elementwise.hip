@@ -379,11 +379,11 @@ __global__ __launch_bounds__(256) void mean_pool_normalize_kernel(const float* _
 // Greedy step (HF:generation/utils.py:2925-2937): next = argmax (first maximal index, like torch.argmax);
 // finished rows emit pad; a row finishes when it emits EOS or reaches max_len.
 //
-// The selection is shared by greedy_select_kernel and its scoring form: block argmax over one logits row (EOS masked while
+// The selection is shared by every arg-max form: block argmax over one logits row (EOS masked while
 // mask_eos): the row's maximum in sv[0] for every thread after the last barrier, its index returned to every thread.
 // A row with no entry above -inf (all -inf, or finite only at a masked EOS) selects index 0, as torch.argmax does; a NaN never
-// compares greater, so it is never selected (ops.h, launch_greedy_select).
-// BAN (the banned form, greedy_select_banned_kernel): bm = the row's ban bitmap in LDS (ban.h), a set bit stands as -inf does.
+// compares greater, so it is never selected (ops.h, SelectStep).
+// BAN (the processed form): bm = the row's ban bitmap in LDS (ban.h), a set bit stands as -inf does.
 // PEN (the processed form with a repetition penalty): seen = the bitmap of the row's context tokens, whose scores are penalised
 // (ban.h, repeat_penalise) before the bans, as HF orders its processors.
 template <bool BAN = false, bool PEN = false>
@@ -450,81 +450,74 @@ __device__ __forceinline__ int greedy_row_argmax(const float* __restrict__ x, in
 }
 
 // One thread appends the row's token and keeps finished / out_len; returns whether the row was open at this step.
-__device__ __forceinline__ bool greedy_row_emit(int row, int best_i, int* __restrict__ seq, int seq_ld, int t, int max_len,
-                                                int eos, int pad, int* __restrict__ finished, int* __restrict__ out_len,
-                                                int force_eos) {
-    int fin = finished[row];
-    int tok = fin ? pad : best_i;
-    if (!fin && force_eos && t + 2 >= max_len) tok = eos;
-    seq[(size_t)row * seq_ld + t + 1] = tok;
+__device__ __forceinline__ bool greedy_row_emit(const SelectRows& a, int row, int best_i) {
+    int fin = a.finished[row];
+    int tok = fin ? a.pad : best_i;
+    if (!fin && a.force_eos && a.t + 2 >= a.max_len) tok = a.eos;
+    a.seq[(size_t)row * a.seq_ld + a.t + 1] = tok;
     if (!fin) {
-        if (tok == eos || t + 2 >= max_len) { finished[row] = 1; out_len[row] = t + 2; }
+        if (tok == a.eos || a.t + 2 >= a.max_len) { a.finished[row] = 1; a.out_len[row] = a.t + 2; }
         // the reference's CoCa loop also stops a row whose newest token IS the pad id (coca_model.py:305: `mask =
         // last == eos | last == pad`; pad id 0 is an ordinary vocabulary entry there): it emits pad from then on and
         // gets no EOS.  The row's length then excludes that pad.
-        else if (force_eos && tok == pad) { finished[row] = 1; out_len[row] = t + 1; }
+        else if (a.force_eos && tok == a.pad) { a.finished[row] = 1; a.out_len[row] = a.t + 1; }
     }
     return !fin;
 }
 
-__global__ __launch_bounds__(256) void greedy_select_kernel(const float* __restrict__ logits, int ld, int V,
-                                                            int* __restrict__ seq, int seq_ld, int t, int max_len,
-                                                            int eos, int pad, int* __restrict__ finished,
-                                                            int* __restrict__ out_len, int min_len, int force_eos, RowMap map) {
+// What every selection kernel starts from (ops.h, SelectRows): block crow's logits row x, the caption `row` it belongs to, whether
+// min_len still masks EOS, and whether x takes 16-byte loads.  False: a compact row past the open ones (uniform over the block, so
+// the kernel returns before any barrier).
+struct SelectRow {
+    int row;
+    bool mask_eos, vec;
+    const float* x;
+};
+__device__ __forceinline__ bool select_row_begin(const SelectRows& a, SelectRow& r) {
+    const int crow = blockIdx.x;
+    if (a.map.n && crow >= *a.map.n) return false;
+    r.row = a.map.live ? a.map.live[crow] : crow;
     // min_len > 0: EOS cannot win while the row has fewer than min_len tokens (HF MinLengthLogitsProcessor, used by the
     // reference's CoCa loop coca_model.py:235-240); force_eos (= "this is the CoCa loop"): the last position is EOS
     // (coca_model.py:317-318) and a sampled pad id ends the row (:305)
-    const int crow = blockIdx.x, tid = threadIdx.x;      // logits row; the caption it belongs to is row map.live[crow]
-    if (map.n && crow >= *map.n) return;                 // (uniform over the block: before any barrier)
-    const int row = map.live ? map.live[crow] : crow;
-    const bool mask_eos = min_len > 0 && t + 1 < min_len;
-    __shared__ float sv[256];
-    __shared__ int si[256];
-    const int imax = greedy_row_argmax(logits + (size_t)crow * ld, V, eos, mask_eos, tid, sv, si);
-    if (tid == 0) greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
+    r.mask_eos = a.min_len > 0 && a.t + 1 < a.min_len;
+    r.vec = (a.ld & 3) == 0 && ((uintptr_t)a.logits & 15) == 0;
+    r.x = a.logits + (size_t)crow * a.ld;
+    return true;
 }
 
-// Banned form (HF NoBadWordsLogitsProcessor ahead of the arg-max; ops.h, BanSet): the block builds the row's ban bitmap in LDS - the
-// static bitmap, then the multi-token sequences matched against the caption's history seq[row][hist0 .. t] - and the selection above
-// runs with it.  Finished rows, the tie rule, RowMap and force_eos are greedy_select_kernel's, from the same two functions.
-__global__ __launch_bounds__(256) void greedy_select_banned_kernel(const float* __restrict__ logits, int ld, int V,
-                                                                   int* __restrict__ seq, int seq_ld, int t, int max_len,
-                                                                   int eos, int pad, int* __restrict__ finished,
-                                                                   int* __restrict__ out_len, int min_len, int force_eos, RowMap map,
-                                                                   BanSet ban, int hist0) {
-    const int crow = blockIdx.x, tid = threadIdx.x;
-    if (map.n && crow >= *map.n) return;
-    const int row = map.live ? map.live[crow] : crow;
-    const bool mask_eos = min_len > 0 && t + 1 < min_len;
-    extern __shared__ unsigned ban_bm[];                 // ban_words(V) words
+__global__ __launch_bounds__(256) void greedy_select_kernel(SelectRows a) {
+    const int tid = threadIdx.x;
+    SelectRow r;
+    if (!select_row_begin(a, r)) return;
     __shared__ float sv[256];
     __shared__ int si[256];
-    ban_bitmap_fill(ban_bm, V, ban, seq + (size_t)row * seq_ld + hist0, max(t + 1 - hist0, 0), tid);
-    const int imax = greedy_row_argmax<true>(logits + (size_t)crow * ld, V, eos, mask_eos, tid, sv, si, ban_bm);
-    if (tid == 0) greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
+    const int imax = greedy_row_argmax(r.x, a.V, a.eos, r.mask_eos, tid, sv, si, nullptr, nullptr, 1.f, r.vec);
+    if (tid == 0) greedy_row_emit(a, r.row, imax);
 }
 
-// Processed form (ops.h, RepeatCtl): the banned form with HF's repetition controls ahead of the ban - the n-gram bans go into the same
-// bitmap, the penalty reads a second one ("seen", behind it in the dynamic LDS when PEN).  The row's context is RowContext's.
-template <bool PEN>
-__global__ __launch_bounds__(256) void greedy_select_processed_kernel(const float* __restrict__ logits, int ld, int V,
-                                                                      int* __restrict__ seq, int seq_ld, int t, int max_len,
-                                                                      int eos, int pad, int* __restrict__ finished,
-                                                                      int* __restrict__ out_len, int min_len, int force_eos, RowMap map,
-                                                                      BanSet ban, int hist0, RepeatCtl ctl) {
-    const int crow = blockIdx.x, tid = threadIdx.x;
-    if (map.n && crow >= *map.n) return;
-    const int row = map.live ? map.live[crow] : crow;
-    const bool mask_eos = min_len > 0 && t + 1 < min_len;
+// Processed form (ops.h, BanSet, RepeatCtl): HF's repetition controls and NoBadWordsLogitsProcessor ahead of the arg-max.  The block
+// builds the row's ban bitmap in LDS - the static bitmap, the multi-token sequences matched against the caption's history
+// seq[row][hist0 .. t], the n-gram bans - and the selection above runs with it; the penalty reads a second bitmap ("seen", behind it in
+// the dynamic LDS when PEN).  The row's context is RowContext's.  Finished rows, the tie rule, RowMap and force_eos are
+// greedy_select_kernel's, from the same functions.
+// CTL = false (a ban set alone, PEN = false): the bitmap is ban_bitmap_fill's - what processed_bitmaps_fill leaves with neutral
+// controls, one barrier sooner.  At 256 rows x 30 524 a ban alone through CTL = true took 0.17 us per launch more than the separate
+// banned kernel this form replaced (10.42 against 10.25 us, spread 0.02 us), and takes none more this way (docs/experiments.md).
+template <bool PEN, bool CTL = true>
+__global__ __launch_bounds__(256) void greedy_select_processed_kernel(SelectRows a, BanSet ban, int hist0, RepeatCtl ctl) {
+    const int tid = threadIdx.x;
+    SelectRow r;
+    if (!select_row_begin(a, r)) return;
     extern __shared__ unsigned ban_bm[];                 // ban_words(V) words, twice with PEN
     __shared__ float sv[256];
     __shared__ int si[256];
-    unsigned* seen = PEN ? ban_bm + ban_words(V) : nullptr;
-    const RowContext cx{seq + (size_t)row * seq_ld + hist0, max(t + 1 - hist0, 0), ctl.vn, ctl.vtok, ctl.vbos};
-    processed_bitmaps_fill(ban_bm, seen, V, ban, ctl.ngram, cx, tid);
-    const int imax = greedy_row_argmax<true, PEN>(logits + (size_t)crow * ld, V, eos, mask_eos, tid, sv, si, ban_bm, seen, ctl.penalty,
-                                                  (ld & 3) == 0);
-    if (tid == 0) greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
+    unsigned* seen = PEN ? ban_bm + ban_words(a.V) : nullptr;
+    const RowContext cx{a.seq + (size_t)r.row * a.seq_ld + hist0, max(a.t + 1 - hist0, 0), ctl.vn, ctl.vtok, ctl.vbos};
+    if (CTL) processed_bitmaps_fill(ban_bm, seen, a.V, ban, ctl.ngram, cx, tid);
+    else ban_bitmap_fill(ban_bm, a.V, ban, cx.real, cx.rlen, tid);
+    const int imax = greedy_row_argmax<true, PEN>(r.x, a.V, a.eos, r.mask_eos, tid, sv, si, ban_bm, seen, ctl.penalty, r.vec);
+    if (tid == 0) greedy_row_emit(a, r.row, imax);
 }
 
 // Sampled form (ops.h, SampleCtl): the processed form with a draw from the row's distribution in place of the arg-max.  On the
@@ -541,23 +534,19 @@ __global__ __launch_bounds__(256) void greedy_select_processed_kernel(const floa
 // sample.h), 1 for the draw's per-thread sums (thread t owns the ids [t * S, (t + 1) * S), S = ceil(V / 256)) and one thread's walk
 // over its S entries: 2 + 1/256 with both cuts off, 10 + 1/256 with both on.  No float atomics; no early return after the bitmaps.
 template <bool PEN>
-__global__ __launch_bounds__(256) void greedy_select_sampled_kernel(const float* __restrict__ logits, int ld, int V,
-                                                                    int* __restrict__ seq, int seq_ld, int t, int max_len,
-                                                                    int eos, int pad, int* __restrict__ finished,
-                                                                    int* __restrict__ out_len, int min_len, int force_eos, RowMap map,
-                                                                    BanSet ban, int hist0, RepeatCtl ctl, SampleCtl sc,
+__global__ __launch_bounds__(256) void greedy_select_sampled_kernel(SelectRows a, BanSet ban, int hist0, RepeatCtl ctl, SampleCtl sc,
                                                                     const unsigned long long* __restrict__ keys, int draw,
                                                                     int* __restrict__ out_kept) {
-    const int crow = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (map.n && crow >= *map.n) return;
-    const int row = map.live ? map.live[crow] : crow;
-    const int mask = (min_len > 0 && t + 1 < min_len) ? eos : -1;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = a.V;
+    SelectRow sr;
+    if (!select_row_begin(a, sr)) return;
+    const int row = sr.row, mask = sr.mask_eos ? a.eos : -1;
     extern __shared__ unsigned ban_bm[];                 // ban_words(V) words, twice with PEN
     __shared__ SampleShared sh;
     unsigned* seen = PEN ? ban_bm + ban_words(V) : nullptr;
-    const RowContext cx{seq + (size_t)row * seq_ld + hist0, max(t + 1 - hist0, 0), ctl.vn, ctl.vtok, ctl.vbos};
+    const RowContext cx{a.seq + (size_t)row * a.seq_ld + hist0, max(a.t + 1 - hist0, 0), ctl.vn, ctl.vtok, ctl.vbos};
     processed_bitmaps_fill(ban_bm, seen, V, ban, ctl.ngram, cx, tid);
-    const float* __restrict__ x = logits + (size_t)crow * ld;
+    const float* __restrict__ x = sr.x;
     const float T = sc.temperature, pen = ctl.penalty;
 
     // the maximum (it is always kept)
@@ -618,7 +607,7 @@ __global__ __launch_bounds__(256) void greedy_select_sampled_kernel(const float*
     }
     __syncthreads();
     if (tid == 0) {
-        greedy_row_emit(row, sh.token, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos);
+        greedy_row_emit(a, row, sh.token);
         if (out_kept) out_kept[row] = sh.kept;
     }
 }
@@ -640,23 +629,19 @@ __global__ __launch_bounds__(256) void greedy_select_sampled_kernel(const float*
 // A masked EOS and a -inf entry give 0.  Elementwise (accurate expf, a true division), float4 loads / stores on the chunks of the
 // sums and the same scalar tail: a value depends on the row's logits and V alone.  Columns V.. of vocab_acc are never touched.
 template <bool VOCAB>
-__device__ __forceinline__ void greedy_select_scored_body(const float* __restrict__ logits, int ld, int V,
-                                                          int* __restrict__ seq, int seq_ld, int t, int max_len,
-                                                          int eos, int pad, int* __restrict__ finished,
-                                                          int* __restrict__ out_len, int min_len, int force_eos,
-                                                          RowMap map, float* __restrict__ logprobs, int lp_ld,
-                                                          int lp_col, int* __restrict__ scored, float* __restrict__ vocab_acc,
-                                                          int acc_ld) {
-    const int crow = blockIdx.x, tid = threadIdx.x;
-    if (map.n && crow >= *map.n) return;
-    const int row = map.live ? map.live[crow] : crow;
-    const bool mask_eos = min_len > 0 && t + 1 < min_len;
-    const float* x = logits + (size_t)crow * ld;
+__device__ __forceinline__ void greedy_select_scored_body(const SelectRows& a, float* __restrict__ logprobs, int lp_ld, int lp_col,
+                                                          int* __restrict__ scored, float* __restrict__ vocab_acc, int acc_ld) {
+    const int tid = threadIdx.x, V = a.V, eos = a.eos;
+    SelectRow r;
+    if (!select_row_begin(a, r)) return;
+    const int row = r.row;
+    const bool mask_eos = r.mask_eos;
+    const float* x = r.x;
     __shared__ float sv[256];
     __shared__ int si[256];
-    const int imax = greedy_row_argmax(x, V, eos, mask_eos, tid, sv, si);
+    const int imax = greedy_row_argmax(x, V, eos, mask_eos, tid, sv, si, nullptr, nullptr, 1.f, r.vec);
     const float zmax = sv[0];
-    const bool open = finished[row] == 0;                // uniform over the block; thread 0 writes it only after the barrier below
+    const bool open = a.finished[row] == 0;              // uniform over the block; thread 0 writes it only after the barrier below
     __syncthreads();                                     // sv[] is reused for the sums
     float total = 0.f;
     if (open) {
@@ -718,32 +703,21 @@ __device__ __forceinline__ void greedy_select_scored_body(const float* __restric
         }
     }
     if (tid == 0) {
-        if (greedy_row_emit(row, imax, seq, seq_ld, t, max_len, eos, pad, finished, out_len, force_eos)) {
+        if (greedy_row_emit(a, row, imax)) {
             logprobs[(size_t)row * lp_ld + lp_col] = -log1pf(total);
             scored[row] += 1;
         }
     }
 }
 
-__global__ __launch_bounds__(256) void greedy_select_logprob_kernel(const float* __restrict__ logits, int ld, int V,
-                                                                    int* __restrict__ seq, int seq_ld, int t, int max_len,
-                                                                    int eos, int pad, int* __restrict__ finished,
-                                                                    int* __restrict__ out_len, int min_len, int force_eos,
-                                                                    RowMap map, float* __restrict__ logprobs, int lp_ld,
-                                                                    int lp_col, int* __restrict__ scored) {
-    greedy_select_scored_body<false>(logits, ld, V, seq, seq_ld, t, max_len, eos, pad, finished, out_len, min_len, force_eos, map,
-                                     logprobs, lp_ld, lp_col, scored, nullptr, 0);
+__global__ __launch_bounds__(256) void greedy_select_logprob_kernel(SelectRows a, float* __restrict__ logprobs, int lp_ld, int lp_col,
+                                                                    int* __restrict__ scored) {
+    greedy_select_scored_body<false>(a, logprobs, lp_ld, lp_col, scored, nullptr, 0);
 }
 
-__global__ __launch_bounds__(256) void greedy_select_vocab_kernel(const float* __restrict__ logits, int ld, int V,
-                                                                  int* __restrict__ seq, int seq_ld, int t, int max_len,
-                                                                  int eos, int pad, int* __restrict__ finished,
-                                                                  int* __restrict__ out_len, int min_len, int force_eos,
-                                                                  RowMap map, float* __restrict__ logprobs, int lp_ld,
-                                                                  int lp_col, int* __restrict__ scored,
-                                                                  float* __restrict__ vocab_acc, int acc_ld) {
-    greedy_select_scored_body<true>(logits, ld, V, seq, seq_ld, t, max_len, eos, pad, finished, out_len, min_len, force_eos, map,
-                                    logprobs, lp_ld, lp_col, scored, vocab_acc, acc_ld);
+__global__ __launch_bounds__(256) void greedy_select_vocab_kernel(SelectRows a, float* __restrict__ logprobs, int lp_ld, int lp_col,
+                                                                  int* __restrict__ scored, float* __restrict__ vocab_acc, int acc_ld) {
+    greedy_select_scored_body<true>(a, logprobs, lp_ld, lp_col, scored, vocab_acc, acc_ld);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1128,101 +1102,64 @@ int launch_init_prompt_seq(int* seq, int* finished, int* out_len, int R, int L, 
     return 0;
 }
 
-int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos,
-                         int pad, int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
-                         float* logprobs, int lp_ld, int lp_col, int* scored, float* vocab_acc, int acc_ld) {
-    if (vocab_acc) {
-        if (!logprobs || !scored || lp_col < 0 || lp_col >= lp_ld) {
-            cap_set_error("greedy_select: the vocabulary accumulator needs the log-prob buffers (column %d of [0, %d), step counter)", lp_col, lp_ld);
+int launch_select_step(const SelectStep& st, hipStream_t s) {
+    const BanSet& ban = st.ban;
+    const RepeatCtl& ctl = st.ctl;
+    const bool processed = ctl.active() || ban.bits;
+    if (ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI || (ban.n_multi && (!ban.multi || !ban.bits)) || st.hist0 < 0 || st.hist0 > st.t + 1) {
+        cap_set_error("select_step: n_multi = %d must be in [0, %d] (with ban_multi and ban_bits), hist0 = %d in [0, t + 1 = %d]", ban.n_multi,
+                      BAN_MAX_MULTI, st.hist0, st.t + 1);
+        return -1;
+    }
+    if (!(ctl.penalty > 0.f) || !std::isfinite(ctl.penalty) || ctl.ngram < 0 || ctl.vn < 0) {
+        cap_set_error("select_step: penalty %g (finite, > 0), n-gram size %d (>= 0), %d virtual context tokens (>= 0)", (double)ctl.penalty,
+                      ctl.ngram, ctl.vn);
+        return -1;
+    }
+    if (st.sample) {
+        const SampleCtl& sc = st.sc;
+        if (!(sc.temperature > 0.f) || !std::isfinite(sc.temperature)) {
+            cap_set_error("select_step: temperature = %g (a finite number above 0)", (double)sc.temperature);
             return -1;
         }
-        if (acc_ld < V || acc_ld % 4 != 0 || ((uintptr_t)vocab_acc & 15) != 0) {
-            cap_set_error("greedy_select: vocab_acc needs acc_ld >= V (%d), acc_ld %% 4 == 0 (got %d) and a 16-byte aligned pointer", V, acc_ld);
+        if (sc.top_k < 0) { cap_set_error("select_step: top_k = %d (0 = off, or >= 1)", sc.top_k); return -1; }
+        if (!(sc.top_p > 0.f) || !(sc.top_p <= 1.f)) { cap_set_error("select_step: top_p = %g (in (0, 1]; 1 = off)", (double)sc.top_p); return -1; }
+        if (st.draw < 0) { cap_set_error("select_step: draw = %d (>= 0)", st.draw); return -1; }
+    }
+    if (st.logprobs || st.vocab_acc) {
+        if (st.sample || processed) {
+            cap_set_error("select_step: the log-prob and vocabulary outputs go with the plain arg-max (no ban, repetition controls or sampling)");
             return -1;
         }
-        hipLaunchKernelGGL(greedy_select_vocab_kernel, dim3(R), dim3(256), 0, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
-                           pad, finished, out_len, min_len, force_eos, map, logprobs, lp_ld, lp_col, scored, vocab_acc, acc_ld);
-    } else if (logprobs) {
-        if (!scored || lp_col < 0 || lp_col >= lp_ld) { cap_set_error("greedy_select: log-prob column %d outside [0, %d) or no step counter", lp_col, lp_ld); return -1; }
-        hipLaunchKernelGGL(greedy_select_logprob_kernel, dim3(R), dim3(256), 0, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
-                           pad, finished, out_len, min_len, force_eos, map, logprobs, lp_ld, lp_col, scored);
+        if (st.ld % 4 != 0) { cap_set_error("select_step: the log-prob and vocabulary forms need ld %% 4 == 0 (got %d)", st.ld); return -1; }
+        if (!st.logprobs || !st.scored || st.lp_col < 0 || st.lp_col >= st.lp_ld) {
+            cap_set_error("select_step: log-prob column %d outside [0, %d), or no log-prob buffer or step counter", st.lp_col, st.lp_ld);
+            return -1;
+        }
+        if (st.vocab_acc && (st.acc_ld < st.V || st.acc_ld % 4 != 0 || ((uintptr_t)st.vocab_acc & 15) != 0)) {
+            cap_set_error("select_step: vocab_acc needs acc_ld >= V (%d), acc_ld %% 4 == 0 (got %d) and a 16-byte aligned pointer", st.V, st.acc_ld);
+            return -1;
+        }
+    }
+    const SelectRows& rows = st;
+    const dim3 grid(st.R), block(256);
+    const bool pen = ctl.penalty != 1.f;
+    const size_t bmb = (size_t)ban_words(st.V) * 4 * (pen ? 2 : 1);      // the ban bitmap, and the penalty's behind it
+    if (st.sample) {
+        const unsigned long long* keys = (const unsigned long long*)st.keys;
+        if (pen) hipLaunchKernelGGL(greedy_select_sampled_kernel<true>, grid, block, bmb, s, rows, ban, st.hist0, ctl, st.sc, keys, st.draw, st.out_kept);
+        else hipLaunchKernelGGL(greedy_select_sampled_kernel<false>, grid, block, bmb, s, rows, ban, st.hist0, ctl, st.sc, keys, st.draw, st.out_kept);
+    } else if (processed) {
+        if (pen) hipLaunchKernelGGL(greedy_select_processed_kernel<true>, grid, block, bmb, s, rows, ban, st.hist0, ctl);
+        else if (ctl.active()) hipLaunchKernelGGL(greedy_select_processed_kernel<false>, grid, block, bmb, s, rows, ban, st.hist0, ctl);
+        else hipLaunchKernelGGL((greedy_select_processed_kernel<false, false>), grid, block, bmb, s, rows, ban, st.hist0, ctl);
+    } else if (st.vocab_acc) {
+        hipLaunchKernelGGL(greedy_select_vocab_kernel, grid, block, 0, s, rows, st.logprobs, st.lp_ld, st.lp_col, st.scored, st.vocab_acc, st.acc_ld);
+    } else if (st.logprobs) {
+        hipLaunchKernelGGL(greedy_select_logprob_kernel, grid, block, 0, s, rows, st.logprobs, st.lp_ld, st.lp_col, st.scored);
     } else {
-        hipLaunchKernelGGL(greedy_select_kernel, dim3(R), dim3(256), 0, s, logits, ld, V, seq, seq_ld, t, max_len, eos, pad,
-                           finished, out_len, min_len, force_eos, map);
+        hipLaunchKernelGGL(greedy_select_kernel, grid, block, 0, s, rows);
     }
-    CAP_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int launch_greedy_select_banned(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
-                                int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
-                                BanSet ban, int hist0) {
-    if (!ban.bits || (ban.n_multi && !ban.multi) || ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI || hist0 < 0 || hist0 > t + 1) {
-        cap_set_error("greedy_select (banned): no bitmap, %d multi-token sequences (at most %d) or a history from column %d at step %d",
-                      ban.n_multi, BAN_MAX_MULTI, hist0, t);
-        return -1;
-    }
-    hipLaunchKernelGGL(greedy_select_banned_kernel, dim3(R), dim3(256), (size_t)ban_words(V) * 4, s, logits, ld, V, seq, seq_ld, t,
-                       max_len, eos, pad, finished, out_len, min_len, force_eos, map, ban, hist0);
-    CAP_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int launch_greedy_select_processed(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
-                                   int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
-                                   BanSet ban, int hist0, RepeatCtl ctl) {
-    if ((ban.n_multi && (!ban.multi || !ban.bits)) || ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI || hist0 < 0 || hist0 > t + 1) {
-        cap_set_error("greedy_select (processed): %d multi-token sequences (at most %d, with a bitmap) or a history from column %d at step %d",
-                      ban.n_multi, BAN_MAX_MULTI, hist0, t);
-        return -1;
-    }
-    if (!(ctl.penalty > 0.f) || !std::isfinite(ctl.penalty) || ctl.ngram < 0 || ctl.vn < 0) {
-        cap_set_error("greedy_select (processed): penalty %g (finite, > 0), n-gram size %d (>= 0), %d virtual context tokens (>= 0)",
-                      (double)ctl.penalty, ctl.ngram, ctl.vn);
-        return -1;
-    }
-    const size_t bmb = (size_t)ban_words(V) * 4;
-    if (ctl.penalty != 1.f)
-        hipLaunchKernelGGL(greedy_select_processed_kernel<true>, dim3(R), dim3(256), 2 * bmb, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
-                           pad, finished, out_len, min_len, force_eos, map, ban, hist0, ctl);
-    else
-        hipLaunchKernelGGL(greedy_select_processed_kernel<false>, dim3(R), dim3(256), bmb, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
-                           pad, finished, out_len, min_len, force_eos, map, ban, hist0, ctl);
-    CAP_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-int launch_greedy_select_sampled(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
-                                 int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
-                                 BanSet ban, int hist0, RepeatCtl ctl, SampleCtl sc, const uint64_t* keys, int draw, int* out_kept) {
-    if ((ban.n_multi && (!ban.multi || !ban.bits)) || ban.n_multi < 0 || ban.n_multi > BAN_MAX_MULTI || hist0 < 0 || hist0 > t + 1) {
-        cap_set_error("greedy_select (sampled): %d multi-token sequences (at most %d, with a bitmap) or a history from column %d at step %d",
-                      ban.n_multi, BAN_MAX_MULTI, hist0, t);
-        return -1;
-    }
-    if (!(ctl.penalty > 0.f) || !std::isfinite(ctl.penalty) || ctl.ngram < 0 || ctl.vn < 0) {
-        cap_set_error("greedy_select (sampled): penalty %g (finite, > 0), n-gram size %d (>= 0), %d virtual context tokens (>= 0)",
-                      (double)ctl.penalty, ctl.ngram, ctl.vn);
-        return -1;
-    }
-    if (!(sc.temperature > 0.f) || !std::isfinite(sc.temperature)) {
-        cap_set_error("greedy_select (sampled): temperature = %g (a finite number above 0)", (double)sc.temperature);
-        return -1;
-    }
-    if (sc.top_k < 0) { cap_set_error("greedy_select (sampled): top_k = %d (0 = off, or >= 1)", sc.top_k); return -1; }
-    if (!(sc.top_p > 0.f) || !(sc.top_p <= 1.f)) {
-        cap_set_error("greedy_select (sampled): top_p = %g (in (0, 1]; 1 = off)", (double)sc.top_p);
-        return -1;
-    }
-    if (draw < 0) { cap_set_error("greedy_select (sampled): draw = %d (>= 0)", draw); return -1; }
-    const size_t bmb = (size_t)ban_words(V) * 4;
-    const unsigned long long* k = (const unsigned long long*)keys;
-    if (ctl.penalty != 1.f)
-        hipLaunchKernelGGL(greedy_select_sampled_kernel<true>, dim3(R), dim3(256), 2 * bmb, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
-                           pad, finished, out_len, min_len, force_eos, map, ban, hist0, ctl, sc, k, draw, out_kept);
-    else
-        hipLaunchKernelGGL(greedy_select_sampled_kernel<false>, dim3(R), dim3(256), bmb, s, logits, ld, V, seq, seq_ld, t, max_len, eos,
-                           pad, finished, out_len, min_len, force_eos, map, ban, hist0, ctl, sc, k, draw, out_kept);
     CAP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -57,25 +57,13 @@ int launch_embed_prompt(int dtype, const int* seq, int seq_ld, int npos, int row
 // seq [R, L] = the prompt (prompt int32 [prompt_rows, P], prompt_rows 1 or R, ids clamped to [0, V)) then pad; finished = 0, len = L
 int launch_init_prompt_seq(int* seq, int* finished, int* out_len, int R, int L, const int* prompt, int prompt_rows, int P, int V,
                            int pad, hipStream_t s);
-// greedy selection: argmax (lowest index wins ties), pad after EOS, append at seq[row][t+1], track finished/len.
-// The token is always inside [0, V), in all three forms (they share the selection).  A NaN logit is never selected: no comparison
-// with it is true, so it stands as -inf does; a row with nothing above -inf (all -inf, all NaN, or finite only at an EOS that
-// min_len still masks) selects index 0, which is what torch.argmax gives for an all -inf row.  (Only the token is defined for
-// such a row or a row holding a NaN: the scoring forms' log-prob of it is NaN in general.)
-int launch_greedy_select(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos,
-                         int pad, int* finished, int* out_len, int R, hipStream_t s, int min_len = 0, int force_eos = 0,
-                         RowMap map = RowMap(),             // logits row c belongs to row map.live[c] (seq / finished / out_len)
-                         // scoring form (launched only when logprobs is given): logprobs[row*lp_ld + lp_col] = log max softmax of
-                         // the row as selected from (EOS mask applied), scored[row] += 1, for the rows open at this step
-                         float* logprobs = nullptr, int lp_ld = 0, int lp_col = 0, int* scored = nullptr,
-                         // vocab form (launched only when vocab_acc is given; needs the scoring buffers): vocab_acc[row*acc_ld + i] =
-                         // max(itself, softmax_i of the row as selected from), i < V, for the rows open at this step
-                         float* vocab_acc = nullptr, int acc_ld = 0);
+// ---- token selection of the greedy loop: one step (SelectStep, launch_select_step) --------------------------------------------
 // Banned tokens and sequences (HF NoBadWordsLogitsProcessor; captioner_hip.h, cap_set_bad_words), as the selection kernels read them:
 //   bits   uint32 [ban_words(V)]: bit i set = token i is banned at every step (the length-1 sequences); bits from V on are 0
 //   multi  int32 [n_multi][BAN_REC]: {n, tok[0 .. n - 1]}, 2 <= n <= BAN_MAX_LEN: tok[n - 1] is banned at a step exactly when the row's
 //          last n - 1 context tokens equal tok[0 .. n - 2]; a sequence longer than the context (n > its length) never matches
-// A block builds the row's bitmap in LDS from both (ban.h) and masks with it; banned = -inf.
+// A block builds the row's bitmap in LDS from both (ban.h) and masks with it; banned = -inf.  bits may be null (no static bitmap;
+// n_multi must then be 0).
 constexpr int BAN_MAX_MULTI = 1024, BAN_MAX_LEN = 8, BAN_REC = BAN_MAX_LEN + 1;
 struct BanSet {
     const unsigned* bits = nullptr;
@@ -83,11 +71,6 @@ struct BanSet {
     int n_multi = 0;
 };
 __host__ __device__ inline int ban_words(int V) { return ((V + 31) / 32 + 3) / 4 * 4; }       // whole 16-byte pieces
-// launch_greedy_select's plain form under a ban: the arg-max is taken over the row with its banned entries at -inf (a row with
-// nothing left selects index 0).  The context of caption `row` is seq[row][hist0 .. t]; everything else as launch_greedy_select.
-int launch_greedy_select_banned(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
-                                int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
-                                BanSet ban, int hist0);
 // Repetition controls (HF RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor; captioner_hip.h, cap_set_repeat_controls), as
 // the processed forms of the selection kernels read them.  The context of a row is what HF's processor sees: `vn` copies of `vtok`
 // (BLIP-2's image placeholders; 0 = none), then the row's stored history, whose FIRST token reads as `vbos` when vbos >= 0 (BLIP-2
@@ -101,11 +84,6 @@ struct RepeatCtl {
     int vn = 0, vtok = 0, vbos = -1;
     bool active() const { return penalty != 1.f || ngram > 0; }
 };
-// launch_greedy_select_banned with the repetition controls: any combination of a ban set (ban.bits may be null: no static bitmap),
-// a penalty and an n-gram size.  The stored history of caption `row` is seq[row][hist0 .. t].
-int launch_greedy_select_processed(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
-                                   int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
-                                   BanSet ban, int hist0, RepeatCtl ctl);
 // Sampling (HF `generate(do_sample=True, temperature=, top_k=, top_p=)`; captioner_hip.h, cap_set_sampling), as the sampled form of
 // the greedy selection reads it: temperature (finite, > 0; 1 leaves the bits), top_k (0 or >= V: off), top_p in (0, 1] (1: off),
 // seed = the Philox key.  The distribution is stated step by step at greedy_select_sampled_kernel (elementwise.hip).
@@ -115,16 +93,47 @@ struct SampleCtl {
     float top_p = 1.f;
     uint64_t seed = 0;
 };
-// launch_greedy_select_processed with a draw in place of the arg-max (ban.bits may be null, ctl may be neutral).  keys = uint64
-// [captions] (device), the per-CAPTION Philox counter words (null: the caption's row index), draw = the index of the generated token
-// (the other counter word); out_kept (null, or int32 [captions]): entries left with a weight above 0 after both cuts.
-int launch_greedy_select_sampled(const float* logits, int ld, int V, int* seq, int seq_ld, int t, int max_len, int eos, int pad,
-                                 int* finished, int* out_len, int R, hipStream_t s, int min_len, int force_eos, RowMap map,
-                                 BanSet ban, int hist0, RepeatCtl ctl, SampleCtl sc, const uint64_t* keys, int draw,
-                                 int* out_kept = nullptr);
+// The rows of a step, as every selection kernel takes them: logits row c (fp32 [., ld], V entries) belongs to caption row = map.live[c]
+// (c without a map), whose token goes to seq[row][t + 1]; pad after EOS, finished / out_len kept per caption.  A row ends on EOS or at
+// max_len tokens.  min_len > 0: EOS cannot win while the row has fewer than min_len tokens (HF MinLengthLogitsProcessor); force_eos
+// (the reference's CoCa loop): the last position is EOS and a selected pad id ends the row.
+struct SelectRows {
+    const float* logits; int ld, V;
+    int* seq; int seq_ld, t, max_len, eos, pad;
+    int* finished; int* out_len;
+    int min_len, force_eos;
+    RowMap map;
+};
+// One step of token selection: `SelectStep st{};`, then fill.  The token is the arg-max (lowest index wins ties) of the row after its
+// processors - penalty, n-grams, bad words, in HF's order, over the context seq[row][hist0 .. t] behind RepeatCtl's virtual prefix - or,
+// with `sample` set, a draw from that row's distribution.  The token is always inside [0, V).  A NaN logit is never selected: no
+// comparison with it is true, so it stands as -inf does; a row with nothing above -inf (all -inf, all NaN, everything banned, or finite
+// only at an EOS that min_len still masks) selects index 0, which is what torch.argmax gives for an all -inf row.  (Only the token is
+// defined for such a row or a row holding a NaN: the scoring forms' log-prob of it is NaN in general.)
+// launch_select_step picks the kernel: sample -> the sampled form; else ctl.active() or ban.bits -> the processed form (a ban set alone:
+// its instantiation without the controls); else the plain,
+// log-prob (logprobs given) or vocabulary (vocab_acc given) form.  The scoring outputs go with the plain arg-max only and need
+// ld % 4 == 0; the arg-max forms read a row with 16-byte loads when ld % 4 == 0 and logits is 16-byte aligned, element-wise otherwise.
+struct SelectStep : SelectRows {
+    int R;                             // logits rows (one block each)
+    BanSet ban; int hist0;
+    RepeatCtl ctl;
+    int sample;                        // 1: draw with sc in place of the arg-max
+    SampleCtl sc;
+    const uint64_t* keys;              // uint64 [captions] (device), the per-CAPTION Philox counter words (null: the caption's row index)
+    int draw;                          // the index of the generated token (the other counter word)
+    int* out_kept;                     // null, or int32 [captions]: entries left with a weight above 0 after both cuts
+    // log-prob form: logprobs[row * lp_ld + lp_col] = log max softmax of the row as selected from (EOS mask applied), scored[row] += 1,
+    // for the rows open at this step
+    float* logprobs; int lp_ld, lp_col; int* scored;
+    // vocabulary form (needs the log-prob buffers): vocab_acc[row * acc_ld + i] = max(itself, softmax_i of the row as selected from),
+    // i < V, for the rows open at this step; acc_ld >= V, acc_ld % 4 == 0, 16-byte aligned
+    float* vocab_acc; int acc_ld;
+};
+int launch_select_step(const SelectStep& st, hipStream_t s);
 // teacher-forced scoring: logits row b of `rows` (fp32 [rows, ld]) is pass row r = r0 + b = position r % npos of caption r / npos; for
 // positions below n_live[caption] the log-softmax at targets[caption * tgt_ld + position] (clamped to [0, V)), log max softmax and the
-// arg-max (launch_greedy_select's selection and tie rule, no EOS mask) go to out_*[caption * out_ld + position], zeros for the others
+// arg-max (launch_select_step's selection and tie rule, no EOS mask) go to out_*[caption * out_ld + position], zeros for the others
 int launch_target_logprob(const float* logits, int ld, int V, int rows, int r0, int npos, const int* targets, int tgt_ld,
                           const int* n_live, float* out_tlp, float* out_top, int* out_top_id, int out_ld, hipStream_t s,
                           int j0 = 0,        // the pass starts at the caption's j0-th position: live = j0 + position < n_live[caption]
@@ -308,16 +317,19 @@ int beam_candidates_only(void* state, const float* logits, int ld, int V, int B,
 // scores, HF's pre-5.x BeamSearchScorer with one group, MinLength(min_len) on EOS) - see beam.hip
 enum { BEAM_HF_V5 = 0, BEAM_LEGACY_RAW = 1 };
 int launch_beam_init(void* state, int B, int K, int max_len, int bos, int pad, int eos, hipStream_t s, int mode = BEAM_HF_V5);
-int launch_beam_step(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len,
-                     int eos, float length_penalty, int* anc, int anc_ld, hipStream_t s, int mode = BEAM_HF_V5, int min_len = 0);
-// launch_beam_step under a ban (BanSet above): the log-softmax statistics see the raw row, a banned candidate's value is -inf.  The
-// history of a row is its LOGICAL one, run_seq[cur_len & 1][row][0 .. cur_len).
-int launch_beam_step_banned(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
-                            float length_penalty, int* anc, int anc_ld, hipStream_t s, int mode, int min_len, BanSet ban);
-// launch_beam_step_banned with the repetition controls (RepeatCtl above; ban.bits may be null): log-softmax of the raw row, the penalty
-// on the log-probs (all <= 0: lp * penalty), the bans, then the running score.  HF v5 scores only.
-int launch_beam_step_processed(void* state, const float* logits, int ld, int V, int B, int K, int max_len, int cur_len, int eos,
-                               float length_penalty, int* anc, int anc_ld, hipStream_t s, BanSet ban, RepeatCtl ctl);
+// One beam step: `BeamStep st{};`, then fill.  The log-softmax statistics see the raw row; with repetition controls (RepeatCtl above;
+// HF v5 scores only) the penalty goes on the log-probs (all <= 0: lp * penalty), then the bans - a banned candidate's value is -inf -
+// then the running score.  The history of a row is its LOGICAL one, run_seq[cur_len & 1][row][0 .. cur_len).  min_len masks EOS in
+// BEAM_LEGACY_RAW mode alone.
+struct BeamStep {
+    void* state; const float* logits; int ld, V, B, K, max_len, cur_len, eos;
+    float length_penalty;
+    int* anc; int anc_ld;
+    int mode, min_len;
+    BanSet ban;
+    RepeatCtl ctl;
+};
+int launch_beam_step(const BeamStep& st, hipStream_t s);
 int launch_beam_finalize(void* state, int B, int K, int max_len, int* out_ids, int* out_len, float* out_scores,
                          hipStream_t s);
 // device pointer: int32, 1 while the beam loop of this state is still running (HF `is_done.all()` not yet true)
