@@ -85,9 +85,22 @@ struct WeightStore {
     int device = 0;
 };
 
+// One projection y = x W^T + b: the weight [N, K] in the GEMM operand type (torch Linear layout, rows ld apart - K everywhere but
+// the patch weight, padded to Kpad), the fp32 bias [N] or null, and with CapConfig.weight_int8 the fp32 row scales [N] of an int8
+// weight in fragment order.  A fused projection (q|k|v, the cross K/V of all layers) is ONE Linear over all its rows.
+struct Linear {
+    void* w = nullptr;
+    float *b = nullptr, *scale = nullptr;
+    int N = 0, K = 0, ld = 0;
+};
+// a bias-less Linear over a buffer someone else owns: a tied head on the fp32 table, the dequantised scratch of an int8 weight
+inline Linear linear_over(void* w, int N, int K) { Linear L; L.w = w; L.N = N; L.K = L.ld = K; return L; }
+struct Norm { float *g = nullptr, *b = nullptr; };   // a LayerNorm's gamma, beta
+enum OutType { OUT_T = 0, OUT_F32 = 1 };             // a GEMM's output: the operand type, or fp32 (GemmParams::out_f32)
+
 struct VLayer {
-    void *w_qkv, *w_proj, *w_fc1, *w_fc2;
-    float *b_qkv, *b_proj, *b_fc1, *b_fc2, *ln1_g, *ln1_b, *ln2_g, *ln2_b;
+    Linear qkv, proj, fc1, fc2;
+    Norm ln1, ln2;
 };
 // int8 weights: up to this many crops per call the prompt pass (crops x 33 rows) runs on the weight-streaming kernels like a decode
 // step; beyond, it is a GEMM proper and goes to the tiled kernels (run_opt).  Within each range a crop's bits do not depend on the
@@ -96,9 +109,9 @@ struct VLayer {
 constexpr int kI8SkinnyPromptCrops = 4;
 
 struct OLayer {            // OPT decoder layer (pre-LN): fused q|k|v, out_proj, fc1 (ReLU), fc2; K/V caches [B][Lmax][T]
-    void *w_qkv, *w_o, *w_f1, *w_f2, *kc, *vc;
-    float *s_qkv = nullptr, *s_o = nullptr, *s_f1 = nullptr, *s_f2 = nullptr;   // CapConfig.weight_int8: row scales of the int8 weights
-    float *b_qkv, *b_o, *b_f1, *b_f2, *ln1_g, *ln1_b, *ln2_g, *ln2_b;
+    Linear qkv, o, f1, f2;     // (CapConfig.weight_int8: int8 weights with row scales)
+    Norm ln1, ln2;
+    void *kc, *vc;
 };
 
 // A sub-layer is two projections around its core, followed by bias + residual + ONE LayerNorm.  The BLIP and CoCa text decoders
@@ -113,9 +126,8 @@ struct OLayer {            // OPT decoder layer (pre-LN): fused q|k|v, out_proj,
 enum { DEC_SELF = 0, DEC_CROSS = 1, DEC_FFN = 2 };
 struct SubLayer {
     int kind = DEC_FFN;
-    void *w_in = nullptr, *w_out = nullptr;
-    float *b_in = nullptr, *b_out = nullptr;
-    float *ln_g = nullptr, *ln_b = nullptr;   // the LayerNorm applied to the sub-layer's result (see above)
+    Linear in, out;
+    Norm ln;                                  // the LayerNorm applied to the sub-layer's result (see above)
     void* cache = nullptr;                    // decoder DEC_SELF: [k|v][R][H][max_len][64] in the activation type (arena)
     int slot = -1;                            // decoder DEC_CROSS: layer index inside the cross K/V cache
 };
@@ -142,22 +154,22 @@ struct DecPlan {
     // the pooler's Q tokens and skips the first (the pooled token)
     int kv_tokens = 0, kv_first = 0, kv_keys = 0;
     // embedding: LayerNorm(word[token] + pos[t]) with the embeddings' own LayerNorm (BLIP) or the first sub-layer's ln_1 (CoCa)
-    float *word = nullptr, *pos = nullptr, *emb_g = nullptr, *emb_b = nullptr;
-    // head: BLIP transform (dense + GELU, LayerNorm) then the vocabulary GEMM with a bias; CoCa the vocabulary GEMM alone (w_tr
-    // null: ln_final is the last sub-layer's LayerNorm)
-    void *w_tr = nullptr, *w_vocab = nullptr;
-    float *b_tr = nullptr, *tr_g = nullptr, *tr_b = nullptr, *b_vocab = nullptr;
+    float *word = nullptr, *pos = nullptr;
+    Norm emb;
+    // head: BLIP transform (dense + GELU, LayerNorm) then the vocabulary GEMM with a bias; CoCa the vocabulary GEMM alone (tr.w
+    // null: ln_final is the last sub-layer's LayerNorm).  vocab is tied: in the fp32 mode BLIP's weight IS the fp32 table
+    Linear tr, vocab;
+    Norm tr_ln;
     const DecTags* tags = nullptr;
 };
 
 // One layer of a post-LN (BERT-style) encoder - the BLIP-2 Q-Former, the sentence encoder - as sub-layers (reg_post_layers fills
 // them, run_qformer / run_text_encoder walk them): self (q|k|v in), on the Q-Former's cross layers cross (query in; the image's
-// k|v projection [2 W, D] is the layer's w_ckv / b_ckv), ffn, and with CAP_ARCH_BLIP2_ITM ffn_text: the text rows' own FFN.
+// k|v projection [2 W, D] is the layer's ckv), ffn, and with CAP_ARCH_BLIP2_ITM ffn_text: the text rows' own FFN.
 struct PostLayer {
     bool has_cross = false;
     SubLayer self, cross, ffn, ffn_text;
-    void* w_ckv = nullptr;
-    float* b_ckv = nullptr;
+    Linear ckv;
 };
 // The activations of a post-LN encoder over R rows of width W, FFN width F (alloc_post_rows)
 struct PostRows {
@@ -202,8 +214,8 @@ struct Captioner {
     int dt; size_t esz;          // storage type of activations / K-V caches that kernels other than the GEMMs read
     int gdt;                     // type of every GEMM operand (A and W): == dt, except CAP_F32_SPLIT: dt = fp32, gdt = G8
                                  // (split fp16, common.h) - there every kernel whose output feeds a GEMM writes G8
-    // out_f32 of a GEMM whose output an attention kernel reads (q, k, v): fp32 in the split mode, where only GEMM operands are G8
-    int attn_f32() const { return gdt == CAP_DT_G8 ? 1 : 0; }
+    // output of a GEMM that an attention kernel reads (q, k, v): fp32 in the split mode, where only GEMM operands are G8
+    OutType attn_out() const { return gdt == CAP_DT_G8 ? OUT_F32 : OUT_T; }
     int NT, P, Kpatch, Kpad;
     bool kv16 = false;           // split mode: the cross-attention K/V cache is KV16 (int16 + one scale per head row, common.h) instead of fp32
     size_t kvrow = 0;            // bytes of one 64-wide head row of that cache (KV16: 132, amortised)
@@ -246,14 +258,13 @@ struct Captioner {
     int last_compacted = 0;      // did the last cap_generate's decode loop run compacted (cap_last_row_compaction)
     int last_score_passes = 0;   // decoder passes of the last cap_score_captions (cap_last_score_passes)
     int *live = nullptr, *n_live = nullptr;       // RowMap storage: int32 [max rows] + the count
-    // vision weights (post_g / post_b: the image tower's final LayerNorm - CoCa: the pooler's ln_k)
-    float *cls, *vpos, *b_patch = nullptr, *post_g, *post_b;
-    float *ln_pre_g = nullptr, *ln_pre_b = nullptr;
-    void* w_patch;
+    // vision weights (patch: [D, Kpatch] in rows of Kpad; post: the image tower's final LayerNorm - CoCa: the pooler's ln_k)
+    float *cls, *vpos;
+    Linear patch; Norm ln_pre, post;
     std::vector<VLayer> vl;
-    // text weights
-    float *word_f32, *tpos, *emb_g, *emb_b, *b_ckv;
-    void* w_ckv;
+    // text weights (ckv: the decoder's cross K/V projections of all layers as one)
+    float *word_f32, *tpos;
+    Norm emb; Linear ckv;
     std::vector<PostLayer> pl;   // post-LN encoder layers: the Q-Former's (BLIP-2, the image-text scorer) or the sentence encoder's
     DecPlan dec;                 // BLIP / CoCa text decoder
     // arena
@@ -270,16 +281,16 @@ struct Captioner {
     size_t head_rows = 0;        // rows the head's buffers (dy, logits) hold: the decode rows, or CapConfig.max_score_rows
     // ---- CoCa (CAP_ARCH_COCA)
     int Q = 0, E = 0;
-    float *lnpost_g = nullptr, *lnpost_b = nullptr, *pool_q = nullptr, *b_pool_kv = nullptr, *b_pool_o = nullptr, *ones = nullptr,
-          *zeros = nullptr, *pool_o = nullptr, *img_tokens = nullptr;
-    void *w_pool_kv = nullptr, *w_pool_o = nullptr, *pool_kvbuf = nullptr, *pool_ctx = nullptr, *xhat = nullptr;
+    Norm lnpost; Linear pool_kv, pool_out;
+    float *pool_q = nullptr, *ones = nullptr, *zeros = nullptr, *pool_o = nullptr, *img_tokens = nullptr;
+    void *pool_kvbuf = nullptr, *pool_ctx = nullptr, *xhat = nullptr;
     int ldl;
     // ---- BLIP-2 (CAP_ARCH_BLIP2)
     std::vector<OLayer> ol;
     bool wq8 = false;            // CapConfig.weight_int8: the OPT decoder's Linear weights are row-quantised int8 (gemm_skinny.hip)
     void* w8_scratch = nullptr;  // one weight matrix as row-major bf16 integers: the prompt pass of more than kI8SkinnyPromptCrops crops
-    float *q_x0 = nullptr, *b_lproj = nullptr, *o_tok = nullptr, *o_pos = nullptr, *o_lnf_g = nullptr, *o_lnf_b = nullptr;
-    void *w_lproj = nullptr, *o_tok_t = nullptr;
+    float *q_x0 = nullptr, *o_tok = nullptr, *o_pos = nullptr;
+    Norm o_lnf; Linear lproj, o_head;        // o_head: the tied LM head [vocab, T], no bias - the token table o_tok in the operand type
     PostRows qr;                 // the Q-Former's query rows [max_batch * num_query_tokens, .] (the image-text scorer's too)
     float *lm_proj = nullptr, *ox = nullptr;      // activations
     void *qkvimg = nullptr, *oh_t = nullptr, *oqkv = nullptr, *octx = nullptr, *off = nullptr;
@@ -290,13 +301,13 @@ struct Captioner {
     // rows; projections fp32 [embed_dim, width] for the pooled head kernel
     std::vector<VLayer> ctl;
     Tower ct;
-    float *c_vproj = nullptr, *c_tproj = nullptr, *c_tok = nullptr, *c_lnf_g = nullptr, *c_lnf_b = nullptr, *c_logit = nullptr;
+    float *c_vproj = nullptr, *c_tproj = nullptr, *c_tok = nullptr, *c_logit = nullptr; Norm c_lnf;
     // ---- BLIP-2 image-text scorer (CAP_ARCH_BLIP2_ITM): image tower on (vl, vt), Q-Former layers in pl with both FFN sets; the
     // text rows tr [max_batch * max_len, .] beside the query rows qr; heads fp32 for the head kernels.  itm_ckv holds the cross
     // K/V of every cross-attention layer for the itm_B images of the last cap_blip2_itm_encode_images: [layer][B * NT, 2 Q]
     // (itm_ckv_slot).
-    float *i_word = nullptr, *i_pos = nullptr, *i_ln_g = nullptr, *i_ln_b = nullptr, *i_vproj = nullptr, *i_vproj_b = nullptr,
-          *i_tproj = nullptr, *i_tproj_b = nullptr, *i_head = nullptr, *i_head_b = nullptr;
+    float *i_word = nullptr, *i_pos = nullptr, *i_vproj = nullptr, *i_vproj_b = nullptr, *i_tproj = nullptr, *i_tproj_b = nullptr,
+          *i_head = nullptr, *i_head_b = nullptr; Norm i_ln;
     PostRows tr;
     void* itm_ckv = nullptr;
     int itm_B = 0;
@@ -352,39 +363,51 @@ int reg_f32(Captioner* m, const std::string& name, float** p, int64_t n) {
     TRY(walloc(m, (void**)p, n * 4));
     return add_slot(m, name, *p, CAP_DT_F32, 1, n);
 }
-// allocate a compute-dtype matrix [rows, ld] and register it
-int reg_mat(Captioner* m, const std::string& name, void** p, int64_t rows, int64_t cols, int ld = 0) {
-    if (!ld) ld = (int)cols;
-    TRY(walloc(m, p, (size_t)rows * ld * m->esz));
-    if (ld != cols && !m->replay) CAP_HIP_CHECK(hipMemset(*p, 0, (size_t)rows * ld * m->esz));
-    return add_slot(m, name, *p, m->gdt, rows, cols, ld);
+// allocate a compute-dtype weight [N, K] and register it.  ld > K (the patch weight): rows of ld columns, zero from K on - the
+// product runs over all of them, so the Linear's K is ld
+int reg_mat(Captioner* m, const std::string& name, Linear& L, int N, int K, int ld = 0) {
+    L.N = N; L.K = L.ld = ld ? ld : K;
+    TRY(walloc(m, &L.w, (size_t)N * L.ld * m->esz));
+    if (L.ld != K && !m->replay) CAP_HIP_CHECK(hipMemset(L.w, 0, (size_t)N * L.ld * m->esz));
+    return add_slot(m, name, L.w, m->gdt, N, K, L.ld);
+}
+// allocate an int8 weight [N, K] in fragment order + its row scales and register it (CapConfig.weight_int8)
+int reg_mat_i8(Captioner* m, const std::string& name, Linear& L, int N, int K) {
+    L.N = N; L.K = L.ld = K;
+    TRY(walloc(m, &L.w, (size_t)N * K));
+    TRY(walloc(m, (void**)&L.scale, (size_t)N * 4));
+    return add_slot(m, name, L.w, CAP_DT_I8W, N, K, 0, L.scale);
+}
+// the plain projection: p + "weight" [N, K] and p + "bias" [N]
+int reg_linear(Captioner* m, const std::string& p, Linear& L, int N, int K, int ld = 0) {
+    TRY(reg_mat(m, p + "weight", L, N, K, ld));
+    return reg_f32(m, p + "bias", &L.b, N);
 }
 
-// allocate an int8 weight [rows, cols] in fragment order + its row scales and register it (CapConfig.weight_int8)
-int reg_mat_i8(Captioner* m, const std::string& name, void** p, float** scale, int64_t rows, int64_t cols) {
-    TRY(walloc(m, p, (size_t)rows * cols));
-    TRY(walloc(m, (void**)scale, (size_t)rows * 4));
-    return add_slot(m, name, *p, CAP_DT_I8W, rows, cols, 0, *scale);
-}
-
-// register the checkpoint tensors p + names[j] + "weight" / "bias" as the row ranges [j * rows, (j + 1) * rows) of one fused
-// compute-dtype weight w [n * rows, cols] and its fp32 bias b
-void reg_rows(Captioner* m, const std::string& p, const char* const* names, int n, void* w, float* b, int64_t rows, int64_t cols) {
+// register the checkpoint tensors p + names[j] + "weight" / "bias" as the row ranges [row0 + j * rows, row0 + (j + 1) * rows) of
+// the fused compute-dtype weight and fp32 bias of L
+void reg_rows(Captioner* m, const std::string& p, const char* const* names, int n, const Linear& L, int64_t rows, int64_t row0 = 0) {
     for (int j = 0; j < n; ++j) {
-        add_slot(m, p + names[j] + "weight", (char*)w + (size_t)j * rows * cols * m->esz, m->gdt, rows, cols);
-        add_slot(m, p + names[j] + "bias", b + (size_t)j * rows, CAP_DT_F32, 1, rows);
+        const size_t r = (size_t)(row0 + j * rows);
+        add_slot(m, p + names[j] + "weight", (char*)L.w + r * L.K * m->esz, m->gdt, rows, L.K);
+        add_slot(m, p + names[j] + "bias", L.b + r, CAP_DT_F32, 1, rows);
     }
 }
-// allocate such a fused weight + bias and register its n parts (n = 1: one Linear layer)
-int reg_fused(Captioner* m, const std::string& p, const char* const* names, int n, void** w, float** b, int64_t rows, int64_t cols) {
-    TRY(walloc(m, w, (size_t)n * rows * cols * m->esz));
-    TRY(walloc(m, (void**)b, (size_t)n * rows * 4));
-    reg_rows(m, p, names, n, *w, *b, rows, cols);
+// allocate a fused weight [total, K] + bias; its row ranges are registered by reg_rows
+int alloc_fused(Captioner* m, Linear& L, int64_t total, int K) {
+    L.N = (int)total; L.K = L.ld = K;
+    TRY(walloc(m, &L.w, (size_t)total * K * m->esz));
+    return walloc(m, (void**)&L.b, (size_t)total * 4);
+}
+// allocate such a fused weight + bias of n parts of `rows` rows and register them (n = 1: one Linear layer)
+int reg_fused(Captioner* m, const std::string& p, const char* const* names, int n, Linear& L, int64_t rows, int K) {
+    TRY(alloc_fused(m, L, n * rows, K));
+    reg_rows(m, p, names, n, L, rows);
     return 0;
 }
-int reg_ln(Captioner* m, const std::string& p, float** g, float** b, int64_t n) {
-    TRY(reg_f32(m, p + "weight", g, n));
-    return reg_f32(m, p + "bias", b, n);
+int reg_ln(Captioner* m, const std::string& p, Norm& n, int64_t D) {
+    TRY(reg_f32(m, p + "weight", &n.g, D));
+    return reg_f32(m, p + "bias", &n.b, D);
 }
 
 // Checkpoint names of a pre-LN transformer tower; every name below ends in the separator before "weight" / "bias".  qkv: one
@@ -419,34 +442,33 @@ int reg_stem(Captioner* m, const TowerNames& n) {
     const std::string r = n.root;
     TRY(reg_f32(m, r + n.cls, &m->cls, D));
     TRY(reg_f32(m, r + n.pos, &m->vpos, (int64_t)m->NT * D));
-    TRY(reg_mat(m, r + n.patch + "weight", &m->w_patch, D, m->Kpatch, m->Kpad));
-    if (n.patch_bias) TRY(reg_f32(m, r + n.patch + "bias", &m->b_patch, D));
-    if (n.ln_pre) TRY(reg_ln(m, r + n.ln_pre, &m->ln_pre_g, &m->ln_pre_b, D));
+    if (n.patch_bias) TRY(reg_linear(m, r + n.patch, m->patch, D, m->Kpatch, m->Kpad));
+    else TRY(reg_mat(m, r + n.patch + "weight", m->patch, D, m->Kpatch, m->Kpad));
+    if (n.ln_pre) TRY(reg_ln(m, r + n.ln_pre, m->ln_pre, D));
     return 0;
 }
 
 // the blocks of a pre-LN tower (width D, MLP F) and its final LayerNorm
-int reg_tower(Captioner* m, const TowerNames& n, std::vector<VLayer>& layers, int count, int D, int F, float** lnf_g, float** lnf_b) {
+int reg_tower(Captioner* m, const TowerNames& n, std::vector<VLayer>& layers, int count, int D, int F, Norm& lnf) {
     const int nqkv = n.qkv[1] ? 3 : 1;
     layers.resize(count);
     for (int i = 0; i < count; ++i) {
         VLayer& L = layers[i];
         const std::string p = std::string(n.root) + n.layers + std::to_string(i) + ".";
-        TRY(reg_fused(m, p, n.qkv, nqkv, &L.w_qkv, &L.b_qkv, 3 * D / nqkv, D));
-        TRY(reg_fused(m, p, &n.proj, 1, &L.w_proj, &L.b_proj, D, D));
-        TRY(reg_ln(m, p + n.ln1, &L.ln1_g, &L.ln1_b, D));
-        TRY(reg_fused(m, p, &n.fc1, 1, &L.w_fc1, &L.b_fc1, F, D));
-        TRY(reg_fused(m, p, &n.fc2, 1, &L.w_fc2, &L.b_fc2, D, F));
-        TRY(reg_ln(m, p + n.ln2, &L.ln2_g, &L.ln2_b, D));
+        TRY(reg_fused(m, p, n.qkv, nqkv, L.qkv, 3 * D / nqkv, D));
+        TRY(reg_linear(m, p + n.proj, L.proj, D, D));
+        TRY(reg_ln(m, p + n.ln1, L.ln1, D));
+        TRY(reg_linear(m, p + n.fc1, L.fc1, F, D));
+        TRY(reg_linear(m, p + n.fc2, L.fc2, D, F));
+        TRY(reg_ln(m, p + n.ln2, L.ln2, D));
     }
-    return reg_ln(m, std::string(n.root) + n.ln_final, lnf_g, lnf_b, D);
+    return reg_ln(m, std::string(n.root) + n.ln_final, lnf, D);
 }
 
 // a BERT-style output block into a sub-layer: p + "dense." -> the output projection [N, K], p + "LayerNorm." -> its LayerNorm
 int reg_out_ln(Captioner* m, const std::string& p, SubLayer& u, int N, int K) {
-    TRY(reg_mat(m, p + "dense.weight", &u.w_out, N, K));
-    TRY(reg_f32(m, p + "dense.bias", &u.b_out, N));
-    return reg_ln(m, p + "LayerNorm.", &u.ln_g, &u.ln_b, N);
+    TRY(reg_linear(m, p + "dense.", u.out, N, K));
+    return reg_ln(m, p + "LayerNorm.", u.ln, N);
 }
 
 // Checkpoint names of a post-LN encoder's layers.  Layer i: layers + i + "."; below it attn holds query. / key. / value. (and
@@ -457,7 +479,7 @@ const PostNames kBertNames = {"encoder.layer.", "attention.self.", "intermediate
 
 int reg_post_ffn(Captioner* m, const std::string& p, const char* fc, const char* out, SubLayer& u, int W, int F) {
     u.kind = DEC_FFN;
-    TRY(reg_fused(m, p, &fc, 1, &u.w_in, &u.b_in, F, W));
+    TRY(reg_linear(m, p + fc, u.in, F, W));
     return reg_out_ln(m, p + out, u, W, F);
 }
 // `count` post-LN layers of width W, FFN width F.  cross_freq > 0: every cross_freq-th layer cross-attends rows of width D.
@@ -469,13 +491,13 @@ int reg_post_layers(Captioner* m, const PostNames& n, int count, int W, int F, i
         PostLayer& L = m->pl[i];
         const std::string p = n.layers + std::to_string(i) + ".";
         L.self.kind = DEC_SELF; L.cross.kind = DEC_CROSS;
-        TRY(reg_fused(m, p + n.attn, nm, 3, &L.self.w_in, &L.self.b_in, W, W));
+        TRY(reg_fused(m, p + n.attn, nm, 3, L.self.in, W, W));
         TRY(reg_out_ln(m, p + "attention.output.", L.self, W, W));
         L.has_cross = cross_freq > 0 && i % cross_freq == 0;
         if (L.has_cross) {
             const std::string cp = p + "cross" + n.attn;
-            TRY(reg_fused(m, cp, nm, 1, &L.cross.w_in, &L.cross.b_in, W, W));
-            TRY(reg_fused(m, cp, nm + 1, 2, &L.w_ckv, &L.b_ckv, W, D));
+            TRY(reg_linear(m, cp + nm[0], L.cross.in, W, W));
+            TRY(reg_fused(m, cp, nm + 1, 2, L.ckv, W, D));
             TRY(reg_out_ln(m, p + "crossattention.output.", L.cross, W, W));
         }
         TRY(reg_post_ffn(m, p, n.fc, n.out, L.ffn, W, F));
@@ -497,7 +519,7 @@ int build_blip(Captioner* m) {
     const CapConfig& c = m->c;
     const int D = c.v_hidden, T = c.t_hidden, F = c.t_ffn, V = c.vocab;
     TRY(reg_stem(m, kBlipVision));
-    TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
+    TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, m->post));
 
     DecPlan& P = m->dec;
     P.W = T; P.skip_finished = true; P.kv_tokens = P.kv_keys = m->NT; P.tags = &kBlipDecTags;
@@ -506,62 +528,47 @@ int build_blip(Captioner* m) {
     TRY(walloc(m, (void**)&m->word_f32, (size_t)V * T * 4));
     add_slot(m, tb + "embeddings.word_embeddings.weight", m->word_f32, CAP_DT_F32, V, T);
     if (m->gdt == CAP_DT_F32) {
-        P.w_vocab = m->word_f32;
+        P.vocab = linear_over(m->word_f32, V, T);
     } else {
-        TRY(walloc(m, &P.w_vocab, (size_t)V * T * m->esz));
-        add_slot(m, tb + "embeddings.word_embeddings.weight", P.w_vocab, m->gdt, V, T);
+        TRY(reg_mat(m, tb + "embeddings.word_embeddings.weight", P.vocab, V, T));
     }
     TRY(reg_f32(m, tb + "embeddings.position_embeddings.weight", &m->tpos, (int64_t)c.max_pos * T));
-    TRY(reg_ln(m, tb + "embeddings.LayerNorm.", &m->emb_g, &m->emb_b, T));
-    P.word = m->word_f32; P.pos = m->tpos; P.emb_g = m->emb_g; P.emb_b = m->emb_b;
+    TRY(reg_ln(m, tb + "embeddings.LayerNorm.", P.emb, T));
+    P.word = m->word_f32; P.pos = m->tpos;
     // cross-attention K/V projections of all layers fused into one [L*2*T, D] weight (one GEMM per image batch)
-    TRY(walloc(m, &m->w_ckv, (size_t)c.t_layers * 2 * T * D * m->esz));
-    TRY(walloc(m, (void**)&m->b_ckv, (size_t)c.t_layers * 2 * T * 4));
+    TRY(alloc_fused(m, m->ckv, (int64_t)c.t_layers * 2 * T, D));
     P.subs.resize(3 * c.t_layers);
     const char* nm[3] = {"query.", "key.", "value."};
     for (int i = 0; i < c.t_layers; ++i) {
         SubLayer &sa = P.subs[3 * i], &ca = P.subs[3 * i + 1], &ff = P.subs[3 * i + 2];
         sa.kind = DEC_SELF; ca.kind = DEC_CROSS; ca.slot = i; ff.kind = DEC_FFN;
         const std::string p = tb + "encoder.layer." + std::to_string(i) + ".";
-        TRY(reg_fused(m, p + "attention.self.", nm, 3, &sa.w_in, &sa.b_in, T, T));
+        TRY(reg_fused(m, p + "attention.self.", nm, 3, sa.in, T, T));
         TRY(reg_out_ln(m, p + "attention.output.", sa, T, T));
-        TRY(reg_fused(m, p + "crossattention.self.", nm, 1, &ca.w_in, &ca.b_in, T, T));
-        reg_rows(m, p + "crossattention.self.", nm + 1, 2, (char*)m->w_ckv + (size_t)i * 2 * T * D * m->esz, m->b_ckv + (size_t)i * 2 * T, T, D);
+        TRY(reg_linear(m, p + "crossattention.self.query.", ca.in, T, T));
+        reg_rows(m, p + "crossattention.self.", nm + 1, 2, m->ckv, T, (int64_t)i * 2 * T);
         TRY(reg_out_ln(m, p + "crossattention.output.", ca, T, T));
-        const char* fc = "intermediate.dense.";
-        TRY(reg_fused(m, p, &fc, 1, &ff.w_in, &ff.b_in, F, T));
+        TRY(reg_linear(m, p + "intermediate.dense.", ff.in, F, T));
         TRY(reg_out_ln(m, p + "output.", ff, T, F));
     }
     const std::string cp = "text_decoder.cls.predictions.";
-    TRY(reg_mat(m, cp + "transform.dense.weight", &P.w_tr, T, T));
-    TRY(reg_f32(m, cp + "transform.dense.bias", &P.b_tr, T));
-    TRY(reg_ln(m, cp + "transform.LayerNorm.", &P.tr_g, &P.tr_b, T));
-    TRY(reg_f32(m, cp + "bias", &P.b_vocab, V));
-    return 0;
+    TRY(reg_linear(m, cp + "transform.dense.", P.tr, T, T));
+    TRY(reg_ln(m, cp + "transform.LayerNorm.", P.tr_ln, T));
+    return reg_f32(m, cp + "bias", &P.vocab.b, V);
 }
 
 // One CoCa text block = an attention sub-layer (causal self-attention, or cross-attention over cache slot `slot` >= 0) and an FFN
-// sub-layer.  Pre-LN: the block's ln_1 is the LayerNorm of whatever comes BEFORE it (ln1_g / ln1_b: the previous FFN sub-layer's,
-// the embedding's for the first block), its ln_2 the attention sub-layer's; the FFN sub-layer's is left to the next block.
-int reg_block(Captioner* m, const std::string& p, SubLayer& at, SubLayer& ff, float** ln1_g, float** ln1_b, int E, int F, int slot) {
+// sub-layer.  Pre-LN: the block's ln_1 is the LayerNorm of whatever comes BEFORE it (ln1: the previous FFN sub-layer's, the
+// embedding's for the first block), its ln_2 the attention sub-layer's; the FFN sub-layer's is left to the next block.
+int reg_block(Captioner* m, const std::string& p, SubLayer& at, SubLayer& ff, Norm& ln1, int E, int F, int slot) {
     at.kind = slot < 0 ? DEC_SELF : DEC_CROSS; at.slot = slot; ff.kind = DEC_FFN;
-    TRY(reg_ln(m, p + ".ln_1.", ln1_g, ln1_b, E));
-    if (slot < 0) {
-        TRY(reg_mat(m, p + ".attn.in_proj_weight", &at.w_in, 3 * E, E));
-        TRY(reg_f32(m, p + ".attn.in_proj_bias", &at.b_in, 3 * E));
-    } else {
-        const std::string d = "derived.cross_q." + std::to_string(slot);
-        TRY(reg_mat(m, d + ".weight", &at.w_in, E, E));
-        TRY(reg_f32(m, d + ".bias", &at.b_in, E));
-    }
-    TRY(reg_mat(m, p + ".attn.out_proj.weight", &at.w_out, E, E));
-    TRY(reg_f32(m, p + ".attn.out_proj.bias", &at.b_out, E));
-    TRY(reg_ln(m, p + ".ln_2.", &at.ln_g, &at.ln_b, E));
-    TRY(reg_mat(m, p + ".mlp.c_fc.weight", &ff.w_in, F, E));
-    TRY(reg_f32(m, p + ".mlp.c_fc.bias", &ff.b_in, F));
-    TRY(reg_mat(m, p + ".mlp.c_proj.weight", &ff.w_out, E, F));
-    TRY(reg_f32(m, p + ".mlp.c_proj.bias", &ff.b_out, E));
-    return 0;
+    TRY(reg_ln(m, p + ".ln_1.", ln1, E));
+    if (slot < 0) TRY(reg_linear(m, p + ".attn.in_proj_", at.in, 3 * E, E));
+    else TRY(reg_linear(m, "derived.cross_q." + std::to_string(slot) + ".", at.in, E, E));
+    TRY(reg_linear(m, p + ".attn.out_proj.", at.out, E, E));
+    TRY(reg_ln(m, p + ".ln_2.", at.ln, E));
+    TRY(reg_linear(m, p + ".mlp.c_fc.", ff.in, F, E));
+    return reg_linear(m, p + ".mlp.c_proj.", ff.out, E, F);
 }
 
 // open_clip CoCa state-dict names (SURVEY.md section 5 "Checkpoint / resume"); `derived.*` tensors are computed once by
@@ -571,14 +578,11 @@ int build_coca(Captioner* m) {
     const int D = c.v_hidden, E = c.embed_dim, F = c.t_ffn, V = c.vocab, Q = c.pool_queries;
     m->Q = Q; m->E = E;
     TRY(reg_stem(m, kCocaVision));
-    TRY(reg_tower(m, kCocaVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
+    TRY(reg_tower(m, kCocaVision, m->vl, c.v_layers, D, c.v_mlp, m->post));
     TRY(reg_f32(m, "derived.pool_q", &m->pool_q, (int64_t)Q * E));
-    TRY(reg_mat(m, "derived.pool_kv.weight", &m->w_pool_kv, 2 * E, D));
-    TRY(reg_f32(m, "derived.pool_kv.bias", &m->b_pool_kv, 2 * E));
-    TRY(reg_mat(m, "visual.attn_pool.attn.out_proj.weight", &m->w_pool_o, E, E));
-    TRY(reg_f32(m, "visual.attn_pool.attn.out_proj.bias", &m->b_pool_o, E));
-    TRY(reg_f32(m, "visual.ln_post.weight", &m->lnpost_g, E));
-    TRY(reg_f32(m, "visual.ln_post.bias", &m->lnpost_b, E));
+    TRY(reg_linear(m, "derived.pool_kv.", m->pool_kv, 2 * E, D));
+    TRY(reg_linear(m, "visual.attn_pool.attn.out_proj.", m->pool_out, E, E));
+    TRY(reg_ln(m, "visual.ln_post.", m->lnpost, E));
     DecPlan& P = m->dec;
     P.W = E; P.pre_ln = true; P.kv_tokens = Q; P.kv_first = 1; P.kv_keys = Q - 1; P.tags = &kCocaDecTags;
     TRY(reg_f32(m, "text.token_embedding.weight", &P.word, (int64_t)V * E));
@@ -587,12 +591,12 @@ int build_coca(Captioner* m) {
     // unimodal blocks, then per multimodal layer i a self block and the cross block over slot i
     P.subs.resize(2 * (c.t_layers + 2 * c.mm_layers));
     int n = 0;
-    float **g = &P.emb_g, **b = &P.emb_b;          // where the next block's ln_1 goes
+    Norm* ln1 = &P.emb;                            // where the next block's ln_1 goes
     auto block = [&](const std::string& p, int slot) {
         SubLayer &at = P.subs[n], &ff = P.subs[n + 1];
         n += 2;
-        const int rc = reg_block(m, p, at, ff, g, b, E, F, slot);
-        g = &ff.ln_g; b = &ff.ln_b;
+        const int rc = reg_block(m, p, at, ff, *ln1, E, F, slot);
+        ln1 = &ff.ln;
         return rc;
     };
     for (int i = 0; i < c.t_layers; ++i) TRY(block("text.transformer.resblocks." + std::to_string(i), -1));
@@ -600,10 +604,9 @@ int build_coca(Captioner* m) {
         TRY(block("text_decoder.resblocks." + std::to_string(i), -1));
         TRY(block("text_decoder.cross_attn." + std::to_string(i), i));
     }
-    TRY(reg_mat(m, "derived.cross_kv.weight", &m->w_ckv, (int64_t)c.mm_layers * 2 * E, E));
-    TRY(reg_f32(m, "derived.cross_kv.bias", &m->b_ckv, (int64_t)c.mm_layers * 2 * E));
-    TRY(reg_ln(m, "text_decoder.ln_final.", g, b, E));
-    TRY(reg_mat(m, "derived.vocab.weight", &P.w_vocab, V, E));
+    TRY(reg_linear(m, "derived.cross_kv.", m->ckv, c.mm_layers * 2 * E, E));
+    TRY(reg_ln(m, "text_decoder.ln_final.", *ln1, E));
+    TRY(reg_mat(m, "derived.vocab.weight", P.vocab, V, E));
     // constant vectors for the affine-free LayerNorm that feeds the folded cross-K/V projection
     TRY(walloc(m, (void**)&m->ones, (size_t)E * 4));
     TRY(walloc(m, (void**)&m->zeros, (size_t)E * 4));
@@ -709,7 +712,7 @@ int build_arena(Captioner* m) {
 struct ProfScope {
     Captioner* m; hipStream_t s; int idx = -1;
     ProfScope(Captioner* m_, hipStream_t s_, const char* tag, double flops, double bytes) : m(m_), s(s_) {
-        if (!m->prof) return;
+        if (!m->prof || !tag) return;     // (a null tag: the caller's pass does not record this launch)
         ProfTag t; t.tag = tag; t.flops = flops; t.bytes = bytes;
         if (hipEventCreate(&t.e0) != hipSuccess || hipEventCreate(&t.e1) != hipSuccess) return;
         (void)hipEventRecord(t.e0, s);
@@ -719,20 +722,47 @@ struct ProfScope {
     ~ProfScope() { if (idx >= 0) (void)hipEventRecord(m->prof_recs[idx].e1, s); }
 };
 
-int gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, int lda, const void* W, int ldw, void* C, int ldc,
-         const float* bias, const float* resid, int M, int N, int K, int gelu, int out_f32, int epi = EPI_STORE,
-         int p0 = 0, int p1 = 0, int p2 = 0, int p3 = 0, const float* aux = nullptr, void* C2 = nullptr,
-         const int* m_live = nullptr) {      // m_live: GemmParams::m_live (the head of the compacted greedy loop)
+// ---------------------------------------------------------------------------------------------- GEMM calls
+// A GEMM's profile record: 2 M N K flops (+ a fused attention's), one read of the operand and the weight, and out_bytes per output
+// element - a store its element (+ 4 with a residual read), a split-K GEMM 4 for each of its S slabs
+struct GemmScope : ProfScope {
+    GemmScope(Captioner* m, hipStream_t s, const char* tag, double M, double N, double K, double out_bytes, double more_flops = 0)
+        : ProfScope(m, s, tag, 2.0 * M * N * K + more_flops, (M * K + N * K) * m->esz + M * N * out_bytes) {}
+};
+// The one place a GemmParams is filled: operand, weight, bias, output, shape, activation and epilogue; everything else zero
+// (the callers set the extras they have by name)
+GemmParams gemm_params(const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc, int M, int N, int K,
+                       int act, int out_f32, int epi = EPI_STORE, int splitk = 1) {
     GemmParams p;
     memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.C = C; p.ldc = ldc; p.bias = bias; p.resid = resid; p.ldr = ldc;
-    p.M = M; p.N = N; p.K = K; p.gelu = gelu; p.out_f32 = out_f32; p.epi = epi;
-    p.p0 = p0; p.p1 = p1; p.p2 = p2; p.p3 = p3; p.aux = aux; p.C2 = C2; p.splitk = 1;
-    p.kv16 = epi == EPI_CROSSKV && m->kv16 ? 1 : 0;
-    p.m_live = m_live;
-    const double osz = out_f32 ? 4.0 : (double)m->esz;
-    ProfScope ps(m, s, tag, 2.0 * M * N * K, ((double)M * K + (double)N * K) * m->esz + (double)M * N * (osz + (resid ? 4.0 : 0.0)));
-    return launch_gemm(m->gdt, p, 0, s);   // tile 0 = auto (stream kernel for encoder-sized problems without residual)
+    p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.bias = bias; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
+    p.gelu = act; p.out_f32 = out_f32; p.epi = epi; p.splitk = splitk;
+    return p;
+}
+int run_gemm(Captioner* m, hipStream_t s, const char* tag, const GemmParams& p, int tile) {
+    GemmScope ps(m, s, tag, p.M, p.N, p.K, p.epi == EPI_PARTIAL ? 4.0 * p.splitk : (p.out_f32 ? 4.0 : (double)m->esz) + (p.resid ? 4.0 : 0.0));
+    return launch_gemm(m->gdt, p, tile, s);
+}
+
+// The rare extras of a gemm() call, by name
+struct GemmOpt {
+    const float* resid = nullptr;                          // fp32 [M, N] in C's layout, may alias C
+    int epi = EPI_STORE, p0 = 0, p1 = 0, p2 = 0, p3 = 0;   // another epilogue with what it reads (gemm.h), aux and C2 too
+    const float* aux = nullptr; void* C2 = nullptr;
+    const int* m_live = nullptr;                           // the compacted greedy loop's count of live rows (GemmParams::m_live)
+    int tile = 0;                                          // 0 = auto (the stream kernel for encoder-sized problems without residual)
+    static GemmOpt residual(const float* r) { GemmOpt o; o.resid = r; return o; }
+    static GemmOpt live(const int* n) { GemmOpt o; o.m_live = n; return o; }
+};
+// C [M, L.N] (rows ldc apart, fp32 or the operand type) = act(A [M, L.K] (rows lda apart) . L.w^T + L.b)
+int gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, int lda, const Linear& L, void* C, int ldc, OutType out, int M,
+         GemmAct act = ACT_NONE, const GemmOpt& o = GemmOpt()) {
+    GemmParams p = gemm_params(A, lda, L.w, L.ld, L.b, C, ldc, M, L.N, L.K, act, out, o.epi);
+    p.resid = o.resid; p.ldr = ldc;
+    p.p0 = o.p0; p.p1 = o.p1; p.p2 = o.p2; p.p3 = o.p3; p.aux = o.aux; p.C2 = o.C2;
+    p.kv16 = o.epi == EPI_CROSSKV && m->kv16 ? 1 : 0;
+    p.m_live = o.m_live;
+    return run_gemm(m, s, tag, p, o.tile);
 }
 
 // Decode loops stop when every caption is finished, as HF generate does (`unfinished_sequences.max() == 0` /
@@ -852,56 +882,51 @@ int build_blip2(Captioner* m) {
     const CapConfig& c = m->c;
     const int D = c.v_hidden, Q = c.q_hidden, F = c.q_ffn, T = c.t_hidden, G = c.t_ffn, V = c.vocab, nq = c.num_query_tokens;
     TRY(reg_stem(m, kBlipVision));
-    TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
+    TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, m->post));
 
     TRY(reg_qformer(m, false));
-    TRY(reg_mat(m, "language_projection.weight", &m->w_lproj, T, Q));
-    TRY(reg_f32(m, "language_projection.bias", &m->b_lproj, T));
+    TRY(reg_linear(m, "language_projection.", m->lproj, T, Q));
 
     const std::string lm = "language_model.model.decoder.";
     // token table twice: fp32 rows for the lookup, compute dtype as the tied LM head
     TRY(walloc(m, (void**)&m->o_tok, (size_t)V * T * 4));
     add_slot(m, lm + "embed_tokens.weight", m->o_tok, CAP_DT_F32, V, T);
-    if (m->gdt == CAP_DT_F32) m->o_tok_t = m->o_tok;
-    else { TRY(walloc(m, &m->o_tok_t, (size_t)V * T * m->esz)); add_slot(m, lm + "embed_tokens.weight", m->o_tok_t, m->gdt, V, T); }
+    if (m->gdt == CAP_DT_F32) m->o_head = linear_over(m->o_tok, V, T);
+    else TRY(reg_mat(m, lm + "embed_tokens.weight", m->o_head, V, T));
     TRY(reg_f32(m, lm + "embed_positions.weight", &m->o_pos, (int64_t)(c.max_pos + 2) * T));
     // Rm: the decode step's rows (image x beam); the prompt pass runs over the Bm images whatever the beam count
     const size_t Bm = c.max_batch, Rm = Bm * c.max_beams, Lmax = nq + 1 + c.max_len;
     m->ol.resize(c.t_layers);
     const char* pn[3] = {"q_proj", "k_proj", "v_proj"};
+    // a decoder projection: in the operand type, or with CapConfig.weight_int8 int8 + row scales
+    auto linear = [&](const std::string& q, Linear& L, int N, int K) {
+        if (!m->wq8) return reg_linear(m, q, L, N, K);
+        TRY(reg_mat_i8(m, q + "weight", L, N, K));
+        return reg_f32(m, q + "bias", &L.b, N);
+    };
     for (int i = 0; i < c.t_layers; ++i) {
         OLayer& L = m->ol[i];
         const std::string p = lm + "layers." + std::to_string(i) + ".";
-        TRY(walloc(m, &L.w_qkv, (size_t)3 * T * T * (m->wq8 ? 1 : m->esz)));
-        if (m->wq8) TRY(walloc(m, (void**)&L.s_qkv, (size_t)3 * T * 4));
-        TRY(walloc(m, (void**)&L.b_qkv, (size_t)3 * T * 4));
+        Linear& q = L.qkv;
+        q.N = 3 * T; q.K = q.ld = T;
+        TRY(walloc(m, &q.w, (size_t)3 * T * T * (m->wq8 ? 1 : m->esz)));
+        if (m->wq8) TRY(walloc(m, (void**)&q.scale, (size_t)3 * T * 4));
+        TRY(walloc(m, (void**)&q.b, (size_t)3 * T * 4));
         for (int j = 0; j < 3; ++j) {
             // (int8: a 16-row tile's blocks are contiguous, so rows j T .. of the fused matrix start at byte j T T)
-            if (m->wq8) add_slot(m, p + "self_attn." + pn[j] + ".weight", (char*)L.w_qkv + (size_t)j * T * T, CAP_DT_I8W, T, T, 0, L.s_qkv + (size_t)j * T);
-            else add_slot(m, p + "self_attn." + pn[j] + ".weight", (char*)L.w_qkv + (size_t)j * T * T * m->esz, m->gdt, T, T);
-            add_slot(m, p + "self_attn." + pn[j] + ".bias", L.b_qkv + (size_t)j * T, CAP_DT_F32, 1, T);
+            if (m->wq8) add_slot(m, p + "self_attn." + pn[j] + ".weight", (char*)q.w + (size_t)j * T * T, CAP_DT_I8W, T, T, 0, q.scale + (size_t)j * T);
+            else add_slot(m, p + "self_attn." + pn[j] + ".weight", (char*)q.w + (size_t)j * T * T * m->esz, m->gdt, T, T);
+            add_slot(m, p + "self_attn." + pn[j] + ".bias", q.b + (size_t)j * T, CAP_DT_F32, 1, T);
         }
-        if (m->wq8) {
-            TRY(reg_mat_i8(m, p + "self_attn.out_proj.weight", &L.w_o, &L.s_o, T, T));
-            TRY(reg_mat_i8(m, p + "fc1.weight", &L.w_f1, &L.s_f1, G, T));
-            TRY(reg_mat_i8(m, p + "fc2.weight", &L.w_f2, &L.s_f2, T, G));
-        } else {
-            TRY(reg_mat(m, p + "self_attn.out_proj.weight", &L.w_o, T, T));
-            TRY(reg_mat(m, p + "fc1.weight", &L.w_f1, G, T));
-            TRY(reg_mat(m, p + "fc2.weight", &L.w_f2, T, G));
-        }
-        TRY(reg_f32(m, p + "self_attn.out_proj.bias", &L.b_o, T));
-        TRY(reg_f32(m, p + "self_attn_layer_norm.weight", &L.ln1_g, T));
-        TRY(reg_f32(m, p + "self_attn_layer_norm.bias", &L.ln1_b, T));
-        TRY(reg_f32(m, p + "fc1.bias", &L.b_f1, G));
-        TRY(reg_f32(m, p + "fc2.bias", &L.b_f2, T));
-        TRY(reg_f32(m, p + "final_layer_norm.weight", &L.ln2_g, T));
-        TRY(reg_f32(m, p + "final_layer_norm.bias", &L.ln2_b, T));
+        TRY(linear(p + "self_attn.out_proj.", L.o, T, T));
+        TRY(reg_ln(m, p + "self_attn_layer_norm.", L.ln1, T));
+        TRY(linear(p + "fc1.", L.f1, G, T));
+        TRY(linear(p + "fc2.", L.f2, T, G));
+        TRY(reg_ln(m, p + "final_layer_norm.", L.ln2, T));
         TRY(dev_alloc(m, &L.kc, Rm * Lmax * T * m->esz));
         TRY(dev_alloc(m, &L.vc, Rm * Lmax * T * m->esz));
     }
-    TRY(reg_f32(m, lm + "final_layer_norm.weight", &m->o_lnf_g, T));
-    TRY(reg_f32(m, lm + "final_layer_norm.bias", &m->o_lnf_b, T));
+    TRY(reg_ln(m, lm + "final_layer_norm.", m->o_lnf, T));
 
     // arena
     const size_t NT = m->NT, M = Bm * NT, e = m->esz, P = nq + 1;
@@ -945,19 +970,18 @@ int build_blip2(Captioner* m) {
 // The pieces of a post-LN layer over the R rows of one row set r.  Every launch takes m->gdt as its type selector; the sentence
 // encoder's kernels are m->dt kernels, the same thing there: cap_create refuses CAP_F32_SPLIT for CAP_ARCH_MINILM.
 int post_qkv(Captioner* m, hipStream_t s, const PostTags& tg, const SubLayer& u, const PostRows& r, int R, const PostDims& d) {
-    return gemm(m, s, tg.qkv, r.x_t, d.W, u.w_in, d.W, r.qkv, 3 * d.W, u.b_in, nullptr, R, 3 * d.W, d.W, 0, m->attn_f32());
+    return gemm(m, s, tg.qkv, r.x_t, d.W, u.in, r.qkv, 3 * d.W, m->attn_out(), R);
 }
 // the tail of a sub-layer: y = A W_out^T + b_out + x; x, x_t = LayerNorm(y)
-int post_out_ln(Captioner* m, hipStream_t s, const char* tag, const char* ln_tag, const void* A, int K, const SubLayer& u,
-                const PostRows& r, int R, const PostDims& d) {
-    TRY(gemm(m, s, tag, A, K, u.w_out, K, r.y, d.W, u.b_out, r.x, R, d.W, K, 0, 1));
-    if (!ln_tag) return launch_layernorm(m->gdt, r.y, d.W, u.ln_g, u.ln_b, d.eps, r.x_t, r.x, R, d.W, s);
+int post_out_ln(Captioner* m, hipStream_t s, const char* tag, const char* ln_tag, const void* A, const SubLayer& u, const PostRows& r,
+                int R, const PostDims& d) {
+    TRY(gemm(m, s, tag, A, u.out.K, u.out, r.y, d.W, OUT_F32, R, ACT_NONE, GemmOpt::residual(r.x)));
     ProfScope ps(m, s, ln_tag, 0, (double)R * d.W * (8 + m->esz));
-    return launch_layernorm(m->gdt, r.y, d.W, u.ln_g, u.ln_b, d.eps, r.x_t, r.x, R, d.W, s);
+    return launch_layernorm(m->gdt, r.y, d.W, u.ln.g, u.ln.b, d.eps, r.x_t, r.x, R, d.W, s);
 }
 int post_ffn(Captioner* m, hipStream_t s, const PostTags& tg, const SubLayer& u, const PostRows& r, int R, const PostDims& d) {
-    TRY(gemm(m, s, tg.f1, r.x_t, d.W, u.w_in, d.W, r.h, d.F, u.b_in, nullptr, R, d.F, d.W, 1, 0));
-    return post_out_ln(m, s, tg.f2, tg.ln, r.h, d.F, u, r, R, d);
+    TRY(gemm(m, s, tg.f1, r.x_t, d.W, u.in, r.h, d.F, OUT_T, R, ACT_GELU));
+    return post_out_ln(m, s, tg.f2, tg.ln, r.h, u, r, R, d);
 }
 
 // the image-text scorer's resident cross K/V of the slot-th cross layer: [max_batch * NT, 2 Q]
@@ -986,7 +1010,7 @@ int run_qformer(Captioner* m, const QformerPass& ps, int B, int nq, int L, const
     if (nq) TRY(launch_rows_broadcast(m->gdt, m->q_x0, q.x, q.x_t, B, nq, Q, s));
     if (L) {
         ProfScope p(m, s, "itm_embed_text", 0, (double)Rt * Q * (8 + 4 + e));
-        TRY(launch_itm_embed_text(m->gdt, ids, L, m->i_word, m->i_pos, m->i_ln_g, m->i_ln_b, c.q_eps, t.x, t.x_t, Rt, Q, c.vocab, s));
+        TRY(launch_itm_embed_text(m->gdt, ids, L, m->i_word, m->i_pos, m->i_ln.g, m->i_ln.b, c.q_eps, t.x, t.x_t, Rt, Q, c.vocab, s));
     }
     size_t slot = 0;
     for (const PostLayer& Ly : m->pl) {
@@ -1001,20 +1025,19 @@ int run_qformer(Captioner* m, const QformerPass& ps, int B, int nq, int L, const
                 TRY(launch_generic_attention(m->dt, base, 3 * Q, (long)nq * 3 * Q, base + Q * e, 3 * Q, (long)nq * 3 * Q, base + 2 * Q * e,
                                              3 * Q, (long)nq * 3 * Q, q.ctx, Q, (long)nq * Q, B, nq, nq, H, hd, -1, s, m->gdt));
         }
-        if (nq) TRY(post_out_ln(m, s, ps.qt->so, nullptr, q.ctx, Q, Ly.self, q, Rq, d));
-        if (L) TRY(post_out_ln(m, s, ps.tt->so, nullptr, t.ctx, Q, Ly.self, t, Rt, d));
+        if (nq) TRY(post_out_ln(m, s, ps.qt->so, nullptr, q.ctx, Ly.self, q, Rq, d));
+        if (L) TRY(post_out_ln(m, s, ps.tt->so, nullptr, t.ctx, Ly.self, t, Rt, d));
         if (Ly.has_cross) {
             const char* kv = ps.resident_kv ? itm_ckv_slot(m, slot++) : (const char*)m->qkvimg;
             if (nq) {
-                TRY(gemm(m, s, ps.qt->cq, q.x_t, Q, Ly.cross.w_in, Q, q.qkv, Q, Ly.cross.b_in, nullptr, Rq, Q, Q, 0, m->attn_f32()));
-                if (!ps.resident_kv)
-                    TRY(gemm(m, s, ps.qt->ckv, m->emb_t, D, Ly.w_ckv, D, m->qkvimg, 2 * Q, Ly.b_ckv, nullptr, B * NT, 2 * Q, D, 0, m->attn_f32()));
+                TRY(gemm(m, s, ps.qt->cq, q.x_t, Q, Ly.cross.in, q.qkv, Q, m->attn_out(), Rq));
+                if (!ps.resident_kv) TRY(gemm(m, s, ps.qt->ckv, m->emb_t, D, Ly.ckv, m->qkvimg, 2 * Q, m->attn_out(), B * NT));
                 {
                     ProfScope p(m, s, ps.qt->cross_attn, 4.0 * B * H * (double)nq * NT * hd, (double)B * NT * 2 * Q * e);
                     TRY(launch_generic_attention(m->dt, q.qkv, Q, (long)nq * Q, kv, 2 * Q, (long)NT * 2 * Q, kv + Q * e, 2 * Q, (long)NT * 2 * Q,
                                                  q.ctx, Q, (long)nq * Q, B, nq, NT, H, hd, -1, s, m->gdt));
                 }
-                TRY(post_out_ln(m, s, ps.qt->co, nullptr, q.ctx, Q, Ly.cross, q, Rq, d));
+                TRY(post_out_ln(m, s, ps.qt->co, nullptr, q.ctx, Ly.cross, q, Rq, d));
             }
         }
         if (nq) TRY(post_ffn(m, s, *ps.qt, Ly.ffn, q, Rq, d));
@@ -1030,11 +1053,11 @@ int build_blip2_itm(Captioner* m) {
     const CapConfig& c = m->c;
     const int D = c.v_hidden, Q = c.q_hidden, F = c.q_ffn, P = c.embed_dim, nq = c.num_query_tokens;
     TRY(reg_stem(m, kBlipVision));
-    TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
+    TRY(reg_tower(m, kBlipVision, m->vl, c.v_layers, D, c.v_mlp, m->post));
     TRY(reg_qformer(m, true));
     TRY(reg_f32(m, "embeddings.word_embeddings.weight", &m->i_word, (int64_t)c.vocab * Q));
     TRY(reg_f32(m, "embeddings.position_embeddings.weight", &m->i_pos, (int64_t)c.max_pos * Q));
-    TRY(reg_ln(m, "qformer.layernorm.", &m->i_ln_g, &m->i_ln_b, Q));
+    TRY(reg_ln(m, "qformer.layernorm.", m->i_ln, Q));
     TRY(reg_f32(m, "vision_projection.weight", &m->i_vproj, (int64_t)P * Q));
     TRY(reg_f32(m, "vision_projection.bias", &m->i_vproj_b, P));
     TRY(reg_f32(m, "text_projection.weight", &m->i_tproj, (int64_t)P * Q));
@@ -1064,8 +1087,7 @@ int build_minilm(Captioner* m) {
     TRY(reg_f32(m, "embeddings.position_embeddings.weight", &m->tpos, (int64_t)c.max_pos * T));
     TRY(walloc(m, (void**)&m->tok_type, (size_t)2 * T * 4));
     add_slot(m, "embeddings.token_type_embeddings.weight", m->tok_type, CAP_DT_F32, 2, T);
-    TRY(reg_f32(m, "embeddings.LayerNorm.weight", &m->emb_g, T));
-    TRY(reg_f32(m, "embeddings.LayerNorm.bias", &m->emb_b, T));
+    TRY(reg_ln(m, "embeddings.LayerNorm.", m->emb, T));
     TRY(reg_post_layers(m, kBertNames, c.t_layers, T, F, 0, 0, false));
     return alloc_post_rows(m, m->te, (size_t)c.max_batch * c.max_len, T, F);
 }
@@ -1080,7 +1102,7 @@ int run_text_encoder(Captioner* m, const int* ids, const int* lens, int B, int L
     const PostRows& r = m->te;
     {
         ProfScope ps(m, s, "te_embed", 0, (double)M * T * (12 + m->esz));
-        TRY(launch_embed_tokens(m->dt, ids, L, m->word_f32, m->tpos, m->tok_type, m->emb_g, m->emb_b, c.t_eps, r.x_t, r.x, M, T, s,
+        TRY(launch_embed_tokens(m->dt, ids, L, m->word_f32, m->tpos, m->tok_type, m->emb.g, m->emb.b, c.t_eps, r.x_t, r.x, M, T, s,
                                 c.vocab));
     }
     for (const PostLayer& Ly : m->pl) {
@@ -1089,7 +1111,7 @@ int run_text_encoder(Captioner* m, const int* ids, const int* lens, int B, int L
             ProfScope ps(m, s, tg.self_attn, 4.0 * B * H * (double)L * L * (T / H), (double)M * 4 * T * m->esz);
             TRY(launch_text_attention(m->dt, r.qkv, lens, r.ctx, B, L, H, T / H, s));
         }
-        TRY(post_out_ln(m, s, tg.so, tg.ln, r.ctx, T, Ly.self, r, M, d));
+        TRY(post_out_ln(m, s, tg.so, tg.ln, r.ctx, Ly.self, r, M, d));
         TRY(post_ffn(m, s, tg, Ly.ffn, r, M, d));
     }
     ProfScope ps(m, s, "te_pool", 0, (double)M * T * 4);
@@ -1107,51 +1129,52 @@ int run_stem(Captioner* m, const void* pixels, int fmt, int B, const TowerTags& 
         ProfScope ps(m, s, tg.patchify, 0, (double)B * 3 * c.image_size * c.image_size * (fmt ? 1 : 4) + (double)B * m->P * m->Kpad * m->esz);
         TRY(launch_patchify(m->gdt, pixels, fmt, B, c.image_size, c.patch_size, m->Kpad, m->patches, c.pix_mean, c.pix_std, s));
     }
-    TRY(gemm(m, s, tg.patch, m->patches, m->Kpad, m->w_patch, m->Kpad, X, D, m->b_patch, nullptr, B * m->P, D, m->Kpad, 0, 1,
-             EPI_PATCH, m->P, 0, 0, 0, m->vpos));
+    GemmOpt patch;
+    patch.epi = EPI_PATCH; patch.p0 = m->P; patch.aux = m->vpos;
+    TRY(gemm(m, s, tg.patch, m->patches, m->Kpad, m->patch, X, D, OUT_F32, B * m->P, ACT_NONE, patch));
     TRY(launch_cls_rows(m->cls, m->vpos, X, B, NT, D, s));
-    if (!m->ln_pre_g) return 0;
+    if (!m->ln_pre.g) return 0;
     ProfScope ps(m, s, tg.ln, 0, (double)B * NT * D * 8);
-    return launch_layernorm(m->dt, X, D, m->ln_pre_g, m->ln_pre_b, c.v_eps, nullptr, X, B * NT, D, s);
+    return launch_layernorm(m->dt, X, D, m->ln_pre.g, m->ln_pre.b, c.v_eps, nullptr, X, B * NT, D, s);
 }
 
-// The pre-LN blocks of a tower over the fp32 residual stream t.X [B * N, D], then its final step: the LayerNorm (fin_g, fin_b)
-// of the last hidden states to fin_t (compute type) / fin_f (fp32, optional), or with fin_g == null no LayerNorm - X is left
+// The pre-LN blocks of a tower over the fp32 residual stream t.X [B * N, D], then its final step: the LayerNorm `fin`
+// of the last hidden states to fin_t (compute type) / fin_f (fp32, optional), or with fin == null no LayerNorm - X is left
 // holding the last hidden states (CLIP: the head kernel normalises the pooled rows).  act: fc1's activation (gemm.h).  causal:
 // the text tower's mask - the generic attention kernel, which in the split mode reads fp32 q|k|v (the G8 kernel takes no mask).
 // Exact fp32 mode: the two branch GEMMs (proj, fc2) write their output to t.delta; the next LayerNorm kernel folds it into X in
 // the same pass that normalises it, so the GEMM epilogues are store-only.  Other modes: they add into X themselves.
 int run_tower(Captioner* m, hipStream_t s, const std::vector<VLayer>& layers, const Tower& t, int B, int N, int D, int H, int F,
-              float eps, int act, bool causal, const TowerTags& tg, const float* fin_g, const float* fin_b, void* fin_t, float* fin_f) {
+              float eps, GemmAct act, bool causal, const TowerTags& tg, const Norm* fin, void* fin_t, float* fin_f) {
     const int M = B * N;
     const bool in_place = vit_adds_in_place(m->gdt);
     float* branch_out = in_place ? t.X : t.delta;
-    const float* branch_resid = in_place ? t.X : nullptr;
+    const GemmOpt branch = GemmOpt::residual(in_place ? t.X : nullptr);
     // split mode: q|k|v stay G8 when the split-fp16 MFMA attention kernel covers this token count, else the GEMM writes fp32
     // for the fp32 attention kernels; either way the context comes out as G8 (the proj GEMM's operand)
     const bool g8_attn = !causal && m->gdt == CAP_DT_G8 && D / H == 64 && vit_attention_takes_g8(N);
     bool pending = false;                                  // delta holds a branch output not yet added to X
-    auto add_ln = [&](const float* g, const float* b, void* out_t, float* out_f) -> int {
+    auto add_ln = [&](const Norm& n, void* out_t, float* out_f) -> int {
         ProfScope ps(m, s, tg.ln, 0, (double)M * D * ((pending ? 12 : 4) + (out_t ? m->esz : 0) + (out_f ? 4 : 0)));
-        if (pending) return launch_reduce_layernorm(m->gdt, t.delta, 1, nullptr, t.X, g, b, eps, out_t, out_f, t.X, M, D, s);
-        return launch_layernorm(m->gdt, t.X, D, g, b, eps, out_t, out_f, M, D, s);
+        if (pending) return launch_reduce_layernorm(m->gdt, t.delta, 1, nullptr, t.X, n.g, n.b, eps, out_t, out_f, t.X, M, D, s);
+        return launch_layernorm(m->gdt, t.X, D, n.g, n.b, eps, out_t, out_f, M, D, s);
     };
     for (const VLayer& L : layers) {
-        TRY(add_ln(L.ln1_g, L.ln1_b, t.ln, nullptr));
-        TRY(gemm(m, s, tg.qkv, t.ln, D, L.w_qkv, D, t.qkv, 3 * D, L.b_qkv, nullptr, M, 3 * D, D, 0, (m->gdt == CAP_DT_G8 && !g8_attn) ? 1 : 0));
+        TRY(add_ln(L.ln1, t.ln, nullptr));
+        TRY(gemm(m, s, tg.qkv, t.ln, D, L.qkv, t.qkv, 3 * D, (m->gdt == CAP_DT_G8 && !g8_attn) ? OUT_F32 : OUT_T, M));
         {
             ProfScope ps(m, s, tg.attn, (causal ? 2.0 : 4.0) * B * H * (double)N * N * 64, (double)M * 4 * D * m->esz);
             TRY(launch_vit_attention(g8_attn ? CAP_DT_G8 : m->dt, t.qkv, t.ctx, B, N, H, 0, s, D / H, causal ? 1 : 0, m->gdt));
         }
-        TRY(gemm(m, s, tg.proj, t.ctx, D, L.w_proj, D, branch_out, D, L.b_proj, branch_resid, M, D, D, 0, 1));
+        TRY(gemm(m, s, tg.proj, t.ctx, D, L.proj, branch_out, D, OUT_F32, M, ACT_NONE, branch));
         pending = !in_place;
-        TRY(add_ln(L.ln2_g, L.ln2_b, t.ln, nullptr));
-        TRY(gemm(m, s, tg.fc1, t.ln, D, L.w_fc1, D, t.mlp, F, L.b_fc1, nullptr, M, F, D, act, 0));
-        TRY(gemm(m, s, tg.fc2, t.mlp, F, L.w_fc2, F, branch_out, D, L.b_fc2, branch_resid, M, D, F, 0, 1));
+        TRY(add_ln(L.ln2, t.ln, nullptr));
+        TRY(gemm(m, s, tg.fc1, t.ln, D, L.fc1, t.mlp, F, OUT_T, M, act));
+        TRY(gemm(m, s, tg.fc2, t.mlp, F, L.fc2, branch_out, D, OUT_F32, M, ACT_NONE, branch));
     }
-    if (fin_g) return add_ln(fin_g, fin_b, fin_t, fin_f);
+    if (fin) return add_ln(*fin, fin_t, fin_f);
     // no LayerNorm outputs: the pass only folds the last fc2 output into X (gamma / beta: any valid vectors)
-    return pending ? add_ln(layers.back().ln2_g, layers.back().ln2_b, nullptr, nullptr) : 0;
+    return pending ? add_ln(layers.back().ln2, nullptr, nullptr) : 0;
 }
 
 // BLIP / BLIP-2: final LayerNorm = post_layernorm -> image_embeds (fp32 to the caller + T for the cross-K/V GEMM).
@@ -1160,8 +1183,8 @@ int run_encoder(Captioner* m, const void* pixels, int fmt, int B, float* out_emb
     const CapConfig& c = m->c;
     float* emb_f = c.arch == CAP_ARCH_COCA ? nullptr : out_embeds ? out_embeds : m->emb_f;
     TRY(run_stem(m, pixels, fmt, B, kEncoderTags, s));
-    return run_tower(m, s, m->vl, m->vt, B, m->NT, c.v_hidden, c.v_heads, c.v_mlp, c.v_eps, 1, false, kEncoderTags, m->post_g,
-                     m->post_b, m->emb_t, emb_f);
+    return run_tower(m, s, m->vl, m->vt, B, m->NT, c.v_hidden, c.v_heads, c.v_mlp, c.v_eps, ACT_GELU, false, kEncoderTags, &m->post,
+                     m->emb_t, emb_f);
 }
 
 // ViT-g over B images -> emb_t [B * NT, D] (post_layernorm on every token), then the cross-attention K/V of every cross layer of
@@ -1174,8 +1197,7 @@ int run_itm_images(Captioner* m, const void* pixels, int fmt, int B, hipStream_t
     size_t slot = 0;
     for (const PostLayer& L : m->pl) {
         if (!L.has_cross) continue;
-        TRY(gemm(m, s, kItmQueryTags.ckv, m->emb_t, D, L.w_ckv, D, itm_ckv_slot(m, slot++), 2 * Q, L.b_ckv, nullptr, B * NT, 2 * Q, D, 0,
-                 m->attn_f32()));
+        TRY(gemm(m, s, kItmQueryTags.ckv, m->emb_t, D, L.ckv, itm_ckv_slot(m, slot++), 2 * Q, m->attn_out(), B * NT));
     }
     m->itm_B = B;
     return 0;
@@ -1188,12 +1210,12 @@ int build_clip(Captioner* m) {
     const CapConfig& c = m->c;
     const int D = c.v_hidden, T = c.t_hidden, P = c.embed_dim;
     TRY(reg_stem(m, kClipVision));
-    TRY(reg_tower(m, kClipVision, m->vl, c.v_layers, D, c.v_mlp, &m->post_g, &m->post_b));
+    TRY(reg_tower(m, kClipVision, m->vl, c.v_layers, D, c.v_mlp, m->post));
     TRY(walloc(m, (void**)&m->c_vproj, (size_t)P * D * 4));
     add_slot(m, "visual_projection.weight", m->c_vproj, CAP_DT_F32, P, D);
     TRY(reg_f32(m, "text_model.embeddings.token_embedding.weight", &m->c_tok, (int64_t)c.vocab * T));
     TRY(reg_f32(m, "text_model.embeddings.position_embedding.weight", &m->tpos, (int64_t)c.max_pos * T));
-    TRY(reg_tower(m, kClipText, m->ctl, c.t_layers, T, c.t_ffn, &m->c_lnf_g, &m->c_lnf_b));
+    TRY(reg_tower(m, kClipText, m->ctl, c.t_layers, T, c.t_ffn, m->c_lnf));
     TRY(walloc(m, (void**)&m->c_tproj, (size_t)P * T * 4));
     add_slot(m, "text_projection.weight", m->c_tproj, CAP_DT_F32, P, T);
     TRY(reg_f32(m, "logit_scale", &m->c_logit, 1));
@@ -1202,16 +1224,16 @@ int build_clip(Captioner* m) {
     return alloc_tower(m, m->ct, (size_t)c.max_batch * c.max_len, T, c.t_ffn);
 }
 
-int clip_act(const Captioner* m) { return m->c.hidden_act == CAP_ACT_GELU ? 1 : 3; }
+GemmAct clip_act(const Captioner* m) { return m->c.hidden_act == CAP_ACT_GELU ? ACT_GELU : ACT_QUICK_GELU; }
 
 int run_clip_images(Captioner* m, const void* pixels, int fmt, int B, float* out, hipStream_t s) {
     const CapConfig& c = m->c;
     const int D = c.v_hidden, NT = m->NT;
     TRY(run_stem(m, pixels, fmt, B, kClipImageTags, s));
     TRY(run_tower(m, s, m->vl, m->vt, B, NT, D, c.v_heads, c.v_mlp, c.v_eps, clip_act(m), false, kClipImageTags, nullptr, nullptr,
-                  nullptr, nullptr));
+                  nullptr));
     ProfScope ps(m, s, "clip_v_head", 2.0 * B * D * c.embed_dim, (double)B * D * 4 + (double)c.embed_dim * D * 4);
-    return launch_clip_head(m->vt.X, NT, nullptr, m->post_g, m->post_b, c.v_eps, m->c_vproj, out, B, D, c.embed_dim, s);
+    return launch_clip_head(m->vt.X, NT, nullptr, m->post.g, m->post.b, c.v_eps, m->c_vproj, out, B, D, c.embed_dim, s);
 }
 
 int run_clip_text(Captioner* m, const int* ids, const int* lens, int B, int L, float* out, hipStream_t s) {
@@ -1222,9 +1244,9 @@ int run_clip_text(Captioner* m, const int* ids, const int* lens, int B, int L, f
         TRY(launch_clip_embed_text(ids, L, m->c_tok, m->tpos, m->ct.X, B * L, T, c.vocab, s));
     }
     TRY(run_tower(m, s, m->ctl, m->ct, B, L, T, c.t_heads, c.t_ffn, c.t_eps, clip_act(m), true, kClipTextTags, nullptr, nullptr,
-                  nullptr, nullptr));
+                  nullptr));
     ProfScope ps(m, s, "clip_t_head", 2.0 * B * T * c.embed_dim, (double)B * T * 4 + (double)c.embed_dim * T * 4);
-    return launch_clip_head(m->ct.X, L, lens, m->c_lnf_g, m->c_lnf_b, c.t_eps, m->c_tproj, out, B, T, c.embed_dim, s);
+    return launch_clip_head(m->ct.X, L, lens, m->c_lnf.g, m->c_lnf.b, c.t_eps, m->c_tproj, out, B, T, c.embed_dim, s);
 }
 
 // CoCa attentional pooler + ln_post, then the affine-free normalisation that feeds the folded cross-K/V projection.
@@ -1234,15 +1256,14 @@ int run_coca_pool(Captioner* m, int B, float* tokens_out, hipStream_t s) {
     const CapConfig& c = m->c;
     const int D = c.v_hidden, E = m->E, Q = m->Q, NT = m->NT;
     // split mode: k | v of the pooler are read by the attention kernel as fp32; its context is the out_proj GEMM's G8 operand
-    TRY(gemm(m, s, "gemm_pool_kv", m->emb_t, D, m->w_pool_kv, D, m->pool_kvbuf, 2 * E, m->b_pool_kv, nullptr, B * NT, 2 * E, D, 0,
-             m->gdt == CAP_DT_G8 ? 1 : 0));
+    TRY(gemm(m, s, "gemm_pool_kv", m->emb_t, D, m->pool_kv, m->pool_kvbuf, 2 * E, m->attn_out(), B * NT));
     {
         ProfScope ps(m, s, "pool_attention", 4.0 * B * Q * (double)NT * E, (double)B * NT * 2 * E * m->esz);
         TRY(launch_pool_attention(m->dt, m->pool_q, m->pool_kvbuf, m->pool_ctx, B, NT, Q, E, c.pool_heads, s, m->gdt));
     }
-    TRY(gemm(m, s, "gemm_pool_o", m->pool_ctx, E, m->w_pool_o, E, m->pool_o, E, m->b_pool_o, nullptr, B * Q, E, E, 0, 1));
+    TRY(gemm(m, s, "gemm_pool_o", m->pool_ctx, E, m->pool_out, m->pool_o, E, OUT_F32, B * Q));
     float* tok = tokens_out ? tokens_out : m->img_tokens;
-    TRY(launch_layernorm(m->dt, m->pool_o, E, m->lnpost_g, m->lnpost_b, c.v_eps, nullptr, tok, B * Q, E, s));
+    TRY(launch_layernorm(m->dt, m->pool_o, E, m->lnpost.g, m->lnpost.b, c.v_eps, nullptr, tok, B * Q, E, s));
     TRY(launch_layernorm(m->gdt, tok, E, m->ones, m->zeros, c.v_eps, m->xhat, nullptr, B * Q, E, s));
     return 0;
 }
@@ -1292,46 +1313,32 @@ int decode_splitk(const Captioner* m, int N, int K, int max_S) {
 }
 inline int decode_tile(const Captioner* m) { return m->gdt == CAP_DT_F32 ? 2 : 6; }
 
-int gemm_partial(Captioner* m, hipStream_t s, const char* tag, const void* A, const void* W, float* part, int R, int N,
-                 int K, int max_S, int* S_out, const int* m_live = nullptr) {
-    const int S = decode_splitk(m, N, K, max_S);
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.C = part; p.ldc = N; p.M = R; p.N = N; p.K = K;
-    p.out_f32 = 1; p.epi = EPI_PARTIAL; p.splitk = S; p.m_live = m_live;
-    *S_out = S;
-    ProfScope ps(m, s, tag, 2.0 * R * N * K, ((double)R * K + (double)N * K) * m->esz + (double)S * R * N * 4);
-    return launch_gemm(m->gdt, p, decode_tile(m), s);
+int gemm_partial(Captioner* m, hipStream_t s, const char* tag, const void* A, const Linear& L, float* part, int R, int max_S, int* S_out,
+                 const int* m_live = nullptr) {
+    *S_out = decode_splitk(m, L.N, L.K, max_S);
+    GemmParams p = gemm_params(A, L.K, L.w, L.ld, nullptr, part, L.N, R, L.N, L.K, ACT_NONE, OUT_F32, EPI_PARTIAL, *S_out);
+    p.m_live = m_live;
+    return run_gemm(m, s, tag, p, decode_tile(m));
 }
 
-// A finished decode projection (bias + activation -> operand type): fc1 of the text layers.  Same kernel family as the
-// split-K ones at every row count.
-int gemm_rows(Captioner* m, hipStream_t s, const char* tag, const void* A, const void* W, void* C, const float* bias, int R, int N,
-              int K, int act, const int* m_live = nullptr) {
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.C = C; p.ldc = N; p.bias = bias; p.ldr = N; p.M = R; p.N = N; p.K = K;
-    p.gelu = act; p.out_f32 = 0; p.epi = EPI_STORE; p.splitk = 1; p.m_live = m_live;
-    ProfScope ps(m, s, tag, 2.0 * R * N * K, ((double)R * K + (double)N * K + (double)R * N) * m->esz);
-    return launch_gemm(m->gdt, p, m->gdt == CAP_DT_F32 ? 0 : 6, s);
+// A finished decode projection over dense rows (bias + activation -> operand type): fc1 of the text layers.  Same kernel family
+// as the split-K ones at every row count.
+int gemm_rows(Captioner* m, hipStream_t s, const char* tag, const void* A, const Linear& L, void* C, int R, GemmAct act,
+              const int* m_live = nullptr) {
+    GemmOpt o = GemmOpt::live(m_live);
+    o.tile = m->gdt == CAP_DT_F32 ? 0 : 6;
+    return gemm(m, s, tag, A, L.K, L, C, L.N, OUT_T, R, act, o);
 }
 
 // Decode-sized GEMM whose consumer is a LayerNorm: split K over S blocks per tile (every block's slabs are all in flight
 // at once -> one memory round trip), partial sums to dpart, then the block-per-row kernel: y = sum + bias + d.dx (-> y_out)
 // and LayerNorm(y) -> out_t / out_f.  (Running the consumer inside the GEMM kernel behind arrival counters cost more than the
 // launch it saves - cross-XCD hand-over, DESIGN.md section 4 - and was removed.)
-int gemm_splitk_reduce_ln(Captioner* m, hipStream_t s, const Dec& d, const char* tag, const void* A, const void* W,
-                          const float* bias, const float* g, const float* b, float eps, int N, int K, void* out_t,
-                          float* out_f, float* y_out) {
-    const int S = decode_splitk(m, N, K, 4);
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.C = d.dpart; p.ldc = N; p.M = d.R; p.N = N; p.K = K;
-    p.out_f32 = 1; p.epi = EPI_PARTIAL; p.splitk = S; p.m_live = d.map.n;
-    {
-        ProfScope ps(m, s, tag, 2.0 * d.R * N * K, ((double)d.R * K + (double)N * K) * m->esz + (double)S * d.R * N * 4);
-        TRY(launch_gemm(m->gdt, p, decode_tile(m), s));
-    }
+int gemm_splitk_reduce_ln(Captioner* m, hipStream_t s, const Dec& d, const char* tag, const void* A, const Linear& L, const Norm& ln,
+                          float eps, void* out_t, float* out_f, float* y_out) {
+    const int N = L.N;
+    int S = 1;
+    TRY(gemm_partial(m, s, tag, A, L, d.dpart, d.R, 4, &S, d.map.n));
     const bool per_row_block = d.R < (d.map.n ? 512 : 832) || N > 1024;
     ProfScope ps(m, s, per_row_block ? "dec_reduce_ln" : "dec_reduce_ln_wave", 0, (double)(S + 2) * d.R * N * 4 + (double)d.R * N * m->esz);
     // one 256-thread block per row up to several hundred rows (one memory round trip, latency-bound); at the pool's 1 024-row
@@ -1344,7 +1351,7 @@ int gemm_splitk_reduce_ln(Captioner* m, hipStream_t s, const Dec& d, const char*
     // keeps its round-5 threshold of 512 rows: a dead row costs it one wave's dispatch instead of four, and most steps of a 768-row
     // pass have far fewer live rows than that - same box, `bench.py --lite`, three interleaved pairs, 512 / 832: 6 476 / 6 460, 6 511 /
     // 6 476, 6 525 / 6 491 captions/s (+0.4 %).
-    return launch_reduce_layernorm(m->gdt, d.dpart, S, bias, d.dx, g, b, eps, out_t, out_f, y_out, d.R, N, s, per_row_block, d.map.n);
+    return launch_reduce_layernorm(m->gdt, d.dpart, S, L.b, d.dx, ln.g, ln.b, eps, out_t, out_f, y_out, d.R, N, s, per_row_block, d.map.n);
 }
 
 // Cross K/V of cache slot `slot` in a call over B images (the slots are packed for the CALL's B).  by_row: the bases of the slot's k /
@@ -1355,6 +1362,19 @@ CrossKV cross_kv(const Captioner* m, int slot, int B, bool by_row) {
     const size_t blk = cross_slot_bytes(m, B) / 2, first = m->dec.kv_first;
     const char* k = (const char*)m->cross + (size_t)slot * 2 * blk + (by_row ? 0 : first * m->kvrow);
     return {k, k + blk, by_row ? first : 0};
+}
+
+// The head over R rows whose operand is x_t: BLIP's transform (dense + GELU -> d.dy, its LayerNorm back to x_t / x_f), then the
+// vocabulary GEMM -> d.logits
+int run_head(Captioner* m, hipStream_t s, const Dec& d, void* x_t, float* x_f, int R, const int* m_live) {
+    const DecPlan& P = m->dec;
+    const int W = P.W;
+    if (P.tr.w) {
+        TRY(gemm(m, s, P.tags->tr, x_t, W, P.tr, d.dy, W, OUT_F32, R, ACT_GELU, GemmOpt::live(m_live)));
+        ProfScope ps(m, s, P.tags->ln, 0, (double)R * W * (8 + m->esz));
+        TRY(launch_layernorm(m->gdt, d.dy, W, P.tr_ln.g, P.tr_ln.b, m->c.t_eps, x_t, x_f, R, W, s, m_live));
+    }
+    return gemm(m, s, P.tags->vocab, x_t, W, P.vocab, d.logits, m->ldl, OUT_F32, R, ACT_NONE, GemmOpt::live(m_live));
 }
 
 // One KV-cached decoder step on the batch kernels: embedding, the plan's sub-layers, head -> d.logits.  Per sub-layer: the input
@@ -1369,7 +1389,7 @@ int run_step(Captioner* m, const Dec& d, const int* tokens, int tok_ld, int t, i
     const CapConfig& c = m->c;
     const DecPlan& P = m->dec;
     const DecTags& tg = *P.tags;
-    const int W = P.W, F = c.t_ffn, H = c.t_heads, R = d.R;
+    const int W = P.W, H = c.t_heads, R = d.R;
     const size_t e = m->esz;
     // greedy: a caption that has ended (d.finished, set by greedy_select one step before) is not computed any more.  Compacted
     // (d.map, the merged passes of ~1 000 rows: at that size the projections are no longer a weight stream - 47 % of the decode
@@ -1379,14 +1399,14 @@ int run_step(Captioner* m, const Dec& d, const int* tokens, int tok_ld, int t, i
     // wanted, forced off): the attention kernels skip ended rows in place and the GEMMs cover every row.
     const bool cm = d.map.n != nullptr;
     const int* skip = (P.skip_finished && K == 1 && !cm) ? d.finished : nullptr;
-    TRY(launch_embed(m->gdt, tokens, tok_ld, t, P.word, P.pos, P.emb_g, P.emb_b, c.t_eps, d.dx_t, P.pre_ln ? nullptr : d.dx, R, W, s,
+    TRY(launch_embed(m->gdt, tokens, tok_ld, t, P.word, P.pos, P.emb.g, P.emb.b, c.t_eps, d.dx_t, P.pre_ln ? nullptr : d.dx, R, W, s,
                      P.pre_ln ? d.dx : nullptr, d.map));
     for (const SubLayer& u : P.subs) {
-        const void* A = d.dctx;      // the output projection's operand [R, Kout]
-        int Kout = W, S = 1;
+        const void* A = d.dctx;      // the output projection's operand [R, u.out.K]
+        int S = 1;
         if (u.kind == DEC_FFN) {
-            TRY(gemm_rows(m, s, tg.in[DEC_FFN], d.dx_t, u.w_in, d.dh, u.b_in, R, F, W, 1, d.map.n));
-            A = d.dh; Kout = F;
+            TRY(gemm_rows(m, s, tg.in[DEC_FFN], d.dx_t, u.in, d.dh, R, ACT_GELU, d.map.n));
+            A = d.dh;
         } else {
             DecodeAttn a;
             memset(&a, 0, sizeof(a));
@@ -1400,34 +1420,29 @@ int run_step(Captioner* m, const Dec& d, const int* tokens, int tok_ld, int t, i
                 a.kbase = kv.k; a.vbase = kv.v; a.kv16 = m->kv16 ? 1 : 0; a.kv_row0 = kv.row0;
                 a.rows_per_kv = K; a.kv_ld = P.kv_tokens; a.n_keys = P.kv_keys;
             }
-            const int self = u.kind == DEC_SELF, Nin = self ? 3 * W : W;
+            const int self = u.kind == DEC_SELF, Nin = u.in.N;
             double bytes = self ? 2.0 * R * H * a.n_keys * 64 * e : 2.0 * d.B * H * a.n_keys * m->kvrow;
             // (positions beyond 32: BLIP's un-fused branch.  CoCa has none: its step fails the attention launcher's 32-position check)
             if (!self || t + 1 <= 32 || P.pre_ln) {
-                TRY(gemm_partial(m, s, tg.in[u.kind], d.dx_t, u.w_in, d.dpart, R, Nin, W, 4, &S, d.map.n));
-                a.q_part = d.dpart; a.q_S = S; a.q_bias = u.b_in; a.q_ld = Nin; a.append_kv = self;   // self: k / v finished and appended too
+                TRY(gemm_partial(m, s, tg.in[u.kind], d.dx_t, u.in, d.dpart, R, 4, &S, d.map.n));
+                a.q_part = d.dpart; a.q_S = S; a.q_bias = u.in.b; a.q_ld = Nin; a.append_kv = self;   // self: k / v finished and appended too
                 if (self && !P.pre_ln) bytes += (double)S * R * Nin * 4;     // (the figure CoCa reports has never counted the partial sums)
             } else {
                 if (cm) { cap_set_error("run_step: the compacted loop takes up to 32 positions"); return -1; }   // (run_generate never asks)
-                TRY(gemm(m, s, tg.in[DEC_SELF], d.dx_t, W, u.w_in, W, d.dq, W, u.b_in, nullptr, R, 3 * W, W, 0, 0, EPI_QKVCACHE,
-                         R, H, Lm, t, nullptr, u.cache));
+                GemmOpt qkv;         // q -> d.dq, k / v of position t -> the cache rows [R][H][Lm][64]
+                qkv.epi = EPI_QKVCACHE; qkv.p0 = R; qkv.p1 = H; qkv.p2 = Lm; qkv.p3 = t; qkv.C2 = u.cache;
+                TRY(gemm(m, s, tg.in[DEC_SELF], d.dx_t, W, u.in, d.dq, W, OUT_T, R, ACT_NONE, qkv));
                 a.q = d.dq;
             }
             ProfScope ps(m, s, tg.attn[u.kind], 4.0 * R * H * a.n_keys * 64, bytes);
             TRY(launch_decode_attention(m->dt, a, s));
         }
-        TRY(gemm_splitk_reduce_ln(m, s, d, tg.out[u.kind], A, u.w_out, u.b_out, u.ln_g, u.ln_b, c.t_eps, W, Kout, d.dx_t,
-                                  P.pre_ln ? nullptr : d.dx, P.pre_ln ? d.dx : nullptr));
+        TRY(gemm_splitk_reduce_ln(m, s, d, tg.out[u.kind], A, u.out, u.ln, c.t_eps, d.dx_t, P.pre_ln ? nullptr : d.dx,
+                                  P.pre_ln ? d.dx : nullptr));
     }
     // the head: compacted, its row tiles and rows from the open count on return too (the split / bf16 kernels of these shapes take
     // GemmParams::m_live; an fp32-mode vocabulary GEMM covers every row of the pass - the dead rows' logits are never read)
-    if (P.w_tr) {
-        TRY(gemm(m, s, tg.tr, d.dx_t, W, P.w_tr, W, d.dy, W, P.b_tr, nullptr, R, W, W, 1, 1, EPI_STORE, 0, 0, 0, 0, nullptr, nullptr, d.map.n));
-        ProfScope ps(m, s, tg.ln, 0, (double)R * W * (8 + e));
-        TRY(launch_layernorm(m->gdt, d.dy, W, P.tr_g, P.tr_b, c.t_eps, d.dx_t, d.dx, R, W, s, d.map.n));
-    }
-    return gemm(m, s, tg.vocab, d.dx_t, W, P.w_vocab, W, d.logits, m->ldl, P.b_vocab, nullptr, R, c.vocab, W, 0, 1, EPI_STORE, 0, 0, 0, 0,
-                nullptr, nullptr, d.map.n);
+    return run_head(m, s, d, d.dx_t, d.dx, R, d.map.n);
 }
 
 // ---------------------------------------------------------------------------------------------- small-batch decoder step
@@ -1453,22 +1468,24 @@ int run_step_small(Captioner* m, const Dec& d, const int* tokens, int tok_ld, in
     const CapConfig& c = m->c;
     const DecPlan& P = m->dec;
     const DecTags& tg = *P.tags;
-    const int W = P.W, F = c.t_ffn, H = c.t_heads, R = d.R, V = c.vocab, nk = P.kv_keys;
+    const int W = P.W, H = c.t_heads, R = d.R, nk = P.kv_keys;
     const size_t e = m->esz;
     const int* skip = (P.skip_finished && K == 1) ? d.finished : nullptr;
     float* xb[2] = {d.dx, d.dx2};
     int cur = 0;                                   // xb[cur]: the row the next consumer adds as its residual
     float* qkvp = d.dpart + (size_t)4 * R * W;     // q|k|v partial sums, beside the [<= 4][R][W] slabs of the other GEMMs
-    const int S_qkv = decode_splitk(m, 3 * W, W, 4), S_ww = decode_splitk(m, W, W, 4), S_f2 = decode_splitk(m, W, F, 4);
     const int kv_kind = m->kv16 ? SMALL_KV_KV16 : (m->dt == CAP_DT_BF16 ? SMALL_KV_BF16 : SMALL_KV_F32);
-    TRY(launch_embed(m->gdt, tokens, tok_ld, t, P.word, P.pos, P.emb_g, P.emb_b, c.t_eps, d.dx_t, P.pre_ln ? nullptr : xb[0], R, W, s,
+    TRY(launch_embed(m->gdt, tokens, tok_ld, t, P.word, P.pos, P.emb.g, P.emb.b, c.t_eps, d.dx_t, P.pre_ln ? nullptr : xb[0], R, W, s,
                      P.pre_ln ? xb[0] : nullptr));
     SmallLN pend;                                  // the consumer of the last sub-layer: the next kernel's prologue runs it
     memset(&pend, 0, sizeof(pend));
-    auto base = [&](const void* Wt, int N, int Kk, int S, int pro, int epi) {
+    // one projection of the step: the batch path's K slices as partial sums (the consumer adds the bias), or finished in one
+    auto base = [&](const Linear& L, int pro, int epi) {
         SmallGemm g;
         memset(&g, 0, sizeof(g));
-        g.W = Wt; g.R = R; g.N = N; g.K = Kk; g.S = S; g.pro = pro; g.epi = epi; g.nchain = 4;
+        g.W = L.w; g.R = R; g.N = L.N; g.K = L.K; g.pro = pro; g.epi = epi; g.nchain = 4;
+        g.S = epi == SMALL_EPI_PARTIAL ? decode_splitk(m, L.N, L.K, 4) : 1;
+        if (epi != SMALL_EPI_PARTIAL) g.bias = L.b;
         return g;
     };
     auto consume = [&](bool keep) {                // bind the pending consumer to the current residual row / the other buffer
@@ -1478,29 +1495,29 @@ int run_step_small(Captioner* m, const Dec& d, const int* tokens, int tok_ld, in
         if (keep) cur ^= 1;
         return ln;
     };
-    auto launch = [&](const char* tag, const SmallGemm& g, double flops, double bytes) {
-        ProfScope ps(m, s, tag, flops, bytes);
+    auto launch = [&](const char* tag, const SmallGemm& g, double attn_flops = 0) {
+        GemmScope ps(m, s, tag, R, g.N, g.K, g.epi == SMALL_EPI_PARTIAL ? 4.0 * g.S : g.epi == SMALL_EPI_ACT_T ? (double)e : 4.0, attn_flops);
         return launch_small_gemm(m->gdt, g, s);
     };
     bool first = true;                             // the first kernel reads the embedding's LayerNorm from d.dx_t
     for (const SubLayer& u : P.subs) {
         const char *t_in = tg.s_in[u.kind], *t_out = tg.s_out[u.kind];
-        int S_out = S_ww;
+        SmallGemm g;
         if (u.kind == DEC_SELF) {
-            SmallGemm g = base(u.w_in, 3 * W, W, S_qkv, first ? SMALL_PRO_GLOBAL : SMALL_PRO_LN, SMALL_EPI_PARTIAL);
+            g = base(u.in, first ? SMALL_PRO_GLOBAL : SMALL_PRO_LN, SMALL_EPI_PARTIAL);
             if (first) g.A = d.dx_t; else g.ln = consume(true);
             g.out_part = qkvp;
-            TRY(launch(t_in, g, 2.0 * R * 3 * W * W, ((double)R * W + 3.0 * W * W) * e + (double)S_qkv * R * 3 * W * 4));
-            g = base(u.w_out, W, W, S_ww, SMALL_PRO_SELFATTN, SMALL_EPI_PARTIAL);
-            g.sa.qkv_part = qkvp; g.sa.qkv_bias = u.b_in; g.sa.qkv_S = S_qkv; g.sa.kc = u.cache;
+            TRY(launch(t_in, g));
+            g = base(u.out, SMALL_PRO_SELFATTN, SMALL_EPI_PARTIAL);
+            g.sa.qkv_part = qkvp; g.sa.qkv_bias = u.in.b; g.sa.qkv_S = decode_splitk(m, u.in.N, u.in.K, 4); g.sa.kc = u.cache;
             g.sa.vc = (char*)u.cache + (size_t)R * H * Lm * 64 * e; g.sa.anc = anc; g.sa.anc_ld = Lm;
             g.sa.kv_ld = Lm; g.sa.n_keys = t + 1; g.sa.H = H; g.sa.skip = skip;
             g.out_part = d.dpart;
-            TRY(launch(t_out, g, 2.0 * R * W * W + 4.0 * R * H * (t + 1) * 64, ((double)R * W + (double)W * W) * e + (double)S_ww * R * W * 4));
+            TRY(launch(t_out, g, 4.0 * R * H * (t + 1) * 64));
         } else if (u.kind == DEC_CROSS) {
             SmallCross x;
             memset(&x, 0, sizeof(x));
-            x.W = u.w_in; x.bias = u.b_in; x.R = R; x.D = W; x.H = H; x.S = S_ww;
+            x.W = u.in.w; x.bias = u.in.b; x.R = R; x.D = W; x.H = H; x.S = decode_splitk(m, W, W, 4);
             x.ln = consume(true);
             const CrossKV kv = cross_kv(m, u.slot, d.B, true);
             x.kbase = kv.k; x.vbase = kv.v; x.kv_row0 = kv.row0;
@@ -1509,38 +1526,37 @@ int run_step_small(Captioner* m, const Dec& d, const int* tokens, int tok_ld, in
                 ProfScope ps(m, s, t_in, 2.0 * R * W * W + 4.0 * R * H * nk * 64, (double)W * W * e + 2.0 * R * H * nk * m->kvrow);
                 TRY(launch_small_cross(m->gdt, x, s));
             }
-            SmallGemm g = base(u.w_out, W, W, S_ww, SMALL_PRO_GLOBAL, SMALL_EPI_PARTIAL);
+            g = base(u.out, SMALL_PRO_GLOBAL, SMALL_EPI_PARTIAL);
             g.A = d.dctx; g.out_part = d.dpart;
-            TRY(launch(t_out, g, 2.0 * R * W * W, ((double)R * W + (double)W * W) * e + (double)S_ww * R * W * 4));
+            TRY(launch(t_out, g));
         } else {
-            SmallGemm g = base(u.w_in, F, W, 1, SMALL_PRO_LN, SMALL_EPI_ACT_T);
+            g = base(u.in, SMALL_PRO_LN, SMALL_EPI_ACT_T);
             g.ln = consume(true);
-            g.bias = u.b_in; g.act = 1; g.out = d.dh; g.ldc = F;
-            TRY(launch(t_in, g, 2.0 * R * F * W, ((double)R * W + (double)F * W + (double)R * F) * e));
-            g = base(u.w_out, W, F, S_f2, SMALL_PRO_GLOBAL, SMALL_EPI_PARTIAL);
+            g.act = ACT_GELU; g.out = d.dh; g.ldc = u.in.N;
+            TRY(launch(t_in, g));
+            g = base(u.out, SMALL_PRO_GLOBAL, SMALL_EPI_PARTIAL);
             g.A = d.dh; g.out_part = d.dpart;
-            TRY(launch(t_out, g, 2.0 * R * W * F, ((double)R * F + (double)W * F) * e + (double)S_f2 * R * W * 4));
-            S_out = S_f2;
+            TRY(launch(t_out, g));
         }
-        memset(&pend, 0, sizeof(pend));
-        pend.part = d.dpart; pend.S = S_out; pend.bias = u.b_out; pend.gamma = u.ln_g; pend.beta = u.ln_b; pend.eps = c.t_eps;
+        memset(&pend, 0, sizeof(pend));          // (g: the sub-layer's output projection)
+        pend.part = d.dpart; pend.S = g.S; pend.bias = u.out.b; pend.gamma = u.ln.g; pend.beta = u.ln.b; pend.eps = c.t_eps;
         pend.x_is_sum = P.pre_ln ? 1 : 0;
         first = false;
     }
-    if (P.w_tr) {   // prediction head transform: LayerNorm of the last FFN in the prologue, bias + GELU -> fp32
-        SmallGemm g = base(P.w_tr, W, W, 1, SMALL_PRO_LN, SMALL_EPI_ACT_F32);
+    if (P.tr.w) {   // prediction head transform: LayerNorm of the last FFN in the prologue, bias + GELU -> fp32
+        SmallGemm g = base(P.tr, SMALL_PRO_LN, SMALL_EPI_ACT_F32);
         g.nchain = 1;
         g.ln = consume(false);
-        g.bias = P.b_tr; g.act = 1; g.out = d.dy; g.ldc = W;
-        TRY(launch(tg.s_tr, g, 2.0 * R * W * W, ((double)R * W + (double)W * W) * e + (double)R * W * 4));
+        g.act = ACT_GELU; g.out = d.dy; g.ldc = W;
+        TRY(launch(tg.s_tr, g));
     }
     // vocabulary GEMM with the last LayerNorm in the prologue: the transform's over d.dy, else the pending consumer's (ln_final)
-    SmallGemm g = base(P.w_vocab, V, W, 1, SMALL_PRO_LN, SMALL_EPI_ACT_F32);
+    SmallGemm g = base(P.vocab, SMALL_PRO_LN, SMALL_EPI_ACT_F32);
     g.nchain = 1;
-    if (P.w_tr) { g.ln.part = d.dy; g.ln.S = 1; g.ln.gamma = P.tr_g; g.ln.beta = P.tr_b; g.ln.eps = c.t_eps; }
+    if (P.tr.w) { g.ln.part = d.dy; g.ln.S = 1; g.ln.gamma = P.tr_ln.g; g.ln.beta = P.tr_ln.b; g.ln.eps = c.t_eps; }
     else g.ln = consume(false);
-    g.bias = P.b_vocab; g.act = 0; g.out = d.logits; g.ldc = m->ldl;
-    return launch(tg.s_vocab, g, 2.0 * R * V * W, ((double)R * W + (double)V * W) * e + (double)R * V * 4);
+    g.act = ACT_NONE; g.out = d.logits; g.ldc = m->ldl;
+    return launch(tg.s_vocab, g);
 }
 
 // ---------------------------------------------------------------------------------------------- prompt prefill
@@ -1557,7 +1573,7 @@ int run_step_small(Captioner* m, const Dec& d, const int* tokens, int tok_ld, in
 int run_prefill(Captioner* m, const Dec& d, int c0, int nc, int npos, int Lm, hipStream_t s, int kv_rows = 0, int img0 = -1) {
     const CapConfig& c = m->c;
     const DecPlan& P = m->dec;
-    const int W = P.W, F = c.t_ffn, H = c.t_heads, Rp = nc * npos;
+    const int W = P.W, H = c.t_heads, Rp = nc * npos;
     const size_t e = m->esz;
     if (P.pre_ln || c.arch != CAP_ARCH_BLIP) { cap_set_error("run_prefill: the prompt prefill is built for the BLIP text decoder"); return -1; }
     if ((size_t)Rp > m->ws_rows || c0 < 0 || c0 + nc > d.R) {
@@ -1570,18 +1586,18 @@ int run_prefill(Captioner* m, const Dec& d, int c0, int nc, int npos, int Lm, hi
     pd.map = RowMap();
     {
         ProfScope ps(m, s, "prefill_embed", 0, (double)Rp * W * (8 + e));
-        TRY(launch_embed_prompt(m->gdt, d.seq, Lm, npos, c0, P.word, P.pos, P.emb_g, P.emb_b, c.t_eps, pd.dx_t, pd.dx, nc, W, s));
+        TRY(launch_embed_prompt(m->gdt, d.seq, Lm, npos, c0, P.word, P.pos, P.emb.g, P.emb.b, c.t_eps, pd.dx_t, pd.dx, nc, W, s));
     }
     for (const SubLayer& u : P.subs) {
         const void* A = pd.dctx;
-        int Kout = W, S = 1;
+        int S = 1;
         if (u.kind == DEC_FFN) {
-            TRY(gemm_rows(m, s, "prefill_gemm_f1", pd.dx_t, u.w_in, pd.dh, u.b_in, Rp, F, W, 1));
-            A = pd.dh; Kout = F;
+            TRY(gemm_rows(m, s, "prefill_gemm_f1", pd.dx_t, u.in, pd.dh, Rp, ACT_GELU));
+            A = pd.dh;
         } else if (u.kind == DEC_SELF) {
-            TRY(gemm_partial(m, s, "prefill_gemm_qkv", pd.dx_t, u.w_in, pd.dpart, Rp, 3 * W, W, 4, &S, nullptr));
+            TRY(gemm_partial(m, s, "prefill_gemm_qkv", pd.dx_t, u.in, pd.dpart, Rp, 4, &S));
             ProfScope ps(m, s, "prefill_self_attn", 2.0 * Rp * H * (npos + 1) * 64, (double)(S + 2) * Rp * 3 * W * 4);
-            TRY(launch_prefill_self_attention(m->dt, pd.dpart, S, u.b_in, 3 * W, u.cache, (char*)u.cache + (size_t)d.R * H * Lm * 64 * e, Lm,
+            TRY(launch_prefill_self_attention(m->dt, pd.dpart, S, u.in.b, 3 * W, u.cache, (char*)u.cache + (size_t)d.R * H * Lm * 64 * e, Lm,
                                               pd.dctx, m->gdt, nc, npos, c0, H, s));
         } else {
             DecodeAttn a;
@@ -1593,13 +1609,13 @@ int run_prefill(Captioner* m, const Dec& d, int c0, int nc, int npos, int Lm, hi
             a.kbase = m->kv16 ? kv.k : kv.k + hr0 * m->kvrow; a.vbase = m->kv16 ? kv.v : kv.v + hr0 * m->kvrow;
             a.kv16 = m->kv16 ? 1 : 0; a.kv_row0 = m->kv16 ? kv.row0 + hr0 : 0;
             a.rows_per_kv = kv_rows > 0 ? kv_rows : npos; a.kv_ld = P.kv_tokens; a.n_keys = P.kv_keys;
-            TRY(gemm_partial(m, s, "prefill_gemm_cq", pd.dx_t, u.w_in, pd.dpart, Rp, W, W, 4, &S, nullptr));
-            a.q_part = pd.dpart; a.q_S = S; a.q_bias = u.b_in; a.q_ld = W;
+            TRY(gemm_partial(m, s, "prefill_gemm_cq", pd.dx_t, u.in, pd.dpart, Rp, 4, &S));
+            a.q_part = pd.dpart; a.q_S = S; a.q_bias = u.in.b; a.q_ld = W;
             ProfScope ps(m, s, "prefill_cross_attn", 4.0 * Rp * H * a.n_keys * 64, 2.0 * nc * H * a.n_keys * m->kvrow);
             TRY(launch_decode_attention(m->dt, a, s));
         }
         const char* tag = u.kind == DEC_FFN ? "prefill_gemm_f2" : u.kind == DEC_SELF ? "prefill_gemm_so" : "prefill_gemm_co";
-        TRY(gemm_splitk_reduce_ln(m, s, pd, tag, A, u.w_out, u.b_out, u.ln_g, u.ln_b, c.t_eps, W, Kout, pd.dx_t, pd.dx, nullptr));
+        TRY(gemm_splitk_reduce_ln(m, s, pd, tag, A, u.out, u.ln, c.t_eps, pd.dx_t, pd.dx, nullptr));
     }
     return 0;
 }
@@ -1640,18 +1656,17 @@ int import_image_state(Captioner* m, const void* state, int B, hipStream_t s) {
 
 static int run_image_side(Captioner* m, const void* pixels, int fmt, int B, hipStream_t s) {
     const CapConfig& c = m->c;
-    const int NT = m->NT, D = c.v_hidden, T = c.t_hidden, H = c.t_heads;
     if (fmt == CAP_PIX_IMAGE_STATE) return import_image_state(m, pixels, B, s);
     TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
+    GemmOpt kv;              // every layer's k | v of the image's tokens -> the cross cache: p0 tokens an image, heads, images
+    kv.epi = EPI_CROSSKV; kv.p1 = c.t_heads; kv.p2 = B;
     if (c.arch == CAP_ARCH_COCA) {
         TRY(run_coca_pool(m, B, nullptr, s));
-        TRY(gemm(m, s, "gemm_crosskv", m->xhat, m->E, m->w_ckv, m->E, m->cross, 0, m->b_ckv, nullptr, B * m->Q,
-                 c.mm_layers * 2 * m->E, m->E, 0, 0, EPI_CROSSKV, m->Q, H, B));
-    } else {
-        TRY(gemm(m, s, "gemm_crosskv", m->emb_t, D, m->w_ckv, D, m->cross, 0, m->b_ckv, nullptr, B * NT, c.t_layers * 2 * T, D,
-                 0, 0, EPI_CROSSKV, NT, H, B));
+        kv.p0 = m->Q;
+        return gemm(m, s, "gemm_crosskv", m->xhat, m->E, m->ckv, m->cross, 0, OUT_T, B * m->Q, ACT_NONE, kv);
     }
-    return 0;
+    kv.p0 = m->NT;
+    return gemm(m, s, "gemm_crosskv", m->emb_t, c.v_hidden, m->ckv, m->cross, 0, OUT_T, B * m->NT, ACT_NONE, kv);
 }
 
 // Rows of one beam search of the request.  A group search (num_beam_groups given): the reference's loop runs its groups one after
@@ -1780,9 +1795,7 @@ int init_score_outputs(const ScoreArgs& a, hipStream_t s) {
 // as zeros: attention is causal, so they reach no row that is reported.
 int run_score(Captioner* m, const ScoreArgs& a, hipStream_t s) {
     const CapConfig& c = m->c;
-    const DecPlan& P = m->dec;
-    const DecTags& tg = *P.tags;
-    const int N = a.B * a.C, L = a.L, npos = L - 1, W = P.W;
+    const int N = a.B * a.C, L = a.L, npos = L - 1, W = m->dec.W;
     const size_t e = m->esz;
     TRY(init_score_outputs(a, s));
     TRY(run_image_side(m, a.pixels, a.pixel_fmt, a.B, s));
@@ -1797,12 +1810,7 @@ int run_score(Captioner* m, const ScoreArgs& a, hipStream_t s) {
         for (int r0 = 0; r0 < Rp; r0 += (int)m->head_rows) {
             const int hr = std::min((int)m->head_rows, Rp - r0);
             const char* x_t = (const char*)d.dx_t + (size_t)r0 * W * e;
-            TRY(gemm(m, s, tg.tr, x_t, W, P.w_tr, W, d.dy, W, P.b_tr, nullptr, hr, W, W, 1, 1));
-            {
-                ProfScope ps(m, s, tg.ln, 0, (double)hr * W * (8 + e));
-                TRY(launch_layernorm(m->gdt, d.dy, W, P.tr_g, P.tr_b, c.t_eps, (void*)x_t, nullptr, hr, W, s));
-            }
-            TRY(gemm(m, s, tg.vocab, x_t, W, P.w_vocab, W, d.logits, m->ldl, P.b_vocab, nullptr, hr, c.vocab, W, 0, 1));
+            TRY(run_head(m, s, d, (void*)x_t, nullptr, hr, nullptr));
             ProfScope ps(m, s, "target_logprob", 0, 2.0 * hr * c.vocab * 4);
             TRY(launch_target_logprob(d.logits, m->ldl, c.vocab, hr, r0, npos, a.ids + (size_t)n0 * L + 1, L, a.out_scored + n0,
                                       a.out_tlp + (size_t)n0 * npos, a.out_top + (size_t)n0 * npos, a.out_top_ids + (size_t)n0 * npos, npos, s));
@@ -1817,7 +1825,7 @@ int run_score(Captioner* m, const ScoreArgs& a, hipStream_t s) {
 // ---- The OPT decoder (pre-LN blocks: what follows a residual add is always a LayerNorm).
 // One projection over `rows` rows, left for a consumer to finish: in place (ln == false: bias + act -> out_t, of type out_dt -
 // split mode: fp32 for q|k|v, G8 for a GEMM operand) or as *S_out slice sums in m->dpart for the reduce + LayerNorm consumer.
-//   int8 weights (W = fragment-ordered bytes, wscale = row scales), tiled: a batch's prompt pass, B x 33 rows, is a GEMM proper.
+//   int8 weights (L.w = fragment-ordered bytes, L.scale = row scales), tiled: a batch's prompt pass, B x 33 rows, is a GEMM proper.
 //     The matrix is unpacked into a row-major bf16 scratch of its INTEGERS (exact), multiplied by the tiled kernel into fp32 and
 //     the row scales applied to that output (S = 1): (A . q^T) * scale + bias as in the weight-streaming kernel, the sums in the
 //     tiled kernel's order.  Measured at 32 crops (us per fc1 GEMM): 365 on the rows-walking weight-stream kernel, ~135 here.
@@ -1826,29 +1834,31 @@ int run_score(Captioner* m, const ScoreArgs& a, hipStream_t s) {
 //   bf16 at a shape the weight-streaming kernel takes: that kernel - at a few dozen rows every GEMM is a weight stream, so K is
 //     split over blocks (all slabs of a block in flight at once).  Otherwise the tiled split-K GEMM with a reduce kernel.
 // Apart from `tiled` the choice depends on dtype and (N, K) only - never on the row count.
-int opt_gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, const void* W, const float* bias, int act, void* out_t,
-             int rows, int N, int K, bool ln, int* S_out, int out_dt, const float* wscale, bool tiled) {
+int opt_gemm(Captioner* m, hipStream_t s, const char* tag, const void* A, const Linear& L, GemmAct act, void* out_t, int rows, bool ln,
+             int* S_out, int out_dt, bool tiled) {
+    const int N = L.N, K = L.K;
+    const float* bias = ln ? nullptr : L.b;       // (the reduce + LayerNorm consumer adds it)
     if (m->wq8 && !tiled) {
         const int S8 = skinny_i8_plan(N, K, !ln);
         ProfScope ps(m, s, tag, 2.0 * rows * N * K,
                      (double)rows * K * 2 + (double)N * K + (ln ? (double)S8 * rows * N * 4 : (double)rows * N * 2));
         *S_out = S8;
-        return launch_gemm_skinny_i8(A, K, W, wscale, bias, act, out_t, N, ln ? m->dpart : nullptr, rows, N, K, s) == S8 ? 0 : -1;
+        return launch_gemm_skinny_i8(A, K, L.w, L.scale, bias, act, out_t, N, ln ? m->dpart : nullptr, rows, N, K, s) == S8 ? 0 : -1;
     }
     const int S = !m->wq8 && m->dt == CAP_DT_BF16 ? skinny_plan(N, K, !ln) : 0;
     if (S >= 1) {
         ProfScope ps(m, s, tag, 2.0 * rows * N * K,
                      ((double)rows * K + (double)N * K) * 2 + (ln ? (double)S * rows * N * 4 : (double)rows * N * 2));
         *S_out = S;
-        return launch_gemm_skinny(A, K, W, K, bias, act, out_t, N, ln ? m->dpart : nullptr, rows, N, K, s) == S ? 0 : -1;
+        return launch_gemm_skinny(A, K, L.w, K, bias, act, out_t, N, ln ? m->dpart : nullptr, rows, N, K, s) == S ? 0 : -1;
     }
     if (m->wq8) {
-        TRY(launch_dequant_i8_rowmajor(W, m->w8_scratch, N, K, s));
-        TRY(gemm(m, s, tag, A, K, m->w8_scratch, K, m->dpart, N, nullptr, nullptr, rows, N, K, 0, 1));
-        TRY(launch_scale_cols(m->dpart, wscale, rows, N, s));
+        TRY(launch_dequant_i8_rowmajor(L.w, m->w8_scratch, N, K, s));
+        TRY(gemm(m, s, tag, A, K, linear_over(m->w8_scratch, N, K), m->dpart, N, OUT_F32, rows));
+        TRY(launch_scale_cols(m->dpart, L.scale, rows, N, s));
         *S_out = 1;
     } else {
-        TRY(gemm_partial(m, s, tag, A, W, m->dpart, rows, N, K, 8, S_out));
+        TRY(gemm_partial(m, s, tag, A, L, m->dpart, rows, 8, S_out));
     }
     if (!ln) TRY(launch_reduce_bias_act(out_dt, m->dpart, *S_out, bias, out_t, rows, N, act, s));
     return 0;
@@ -1904,25 +1914,25 @@ int opt_attention(Captioner* m, const OLayer& Ly, int B, int L, int past, hipStr
 // kI8SkinnyPromptCrops prompts, the tiled GEMM beyond, as the prompt pass does.
 int run_opt(Captioner* m, int B, int L, int past, hipStream_t s, const OptRows& rw) {
     const CapConfig& c = m->c;
-    const int T = c.t_hidden, G = c.t_ffn, R = B * L;
+    const int T = c.t_hidden, R = B * L;
     const bool sc = rw.kind == OptRows::CAPTIONS;
     const bool tiled = sc ? R > kI8SkinnyPromptCrops * (c.num_query_tokens + 1) : L > 1 && B > kI8SkinnyPromptCrops;
     int S = 1;
     for (int i = 0; i < c.t_layers; ++i) {
         const OLayer& Ly = m->ol[i];
         const bool last = i + 1 == c.t_layers;
-        TRY(opt_gemm(m, s, "opt_gemm_qkv", m->oh_t, Ly.w_qkv, Ly.b_qkv, 0, m->oqkv, R, 3 * T, T, false, &S, m->dt, Ly.s_qkv, tiled));
+        TRY(opt_gemm(m, s, "opt_gemm_qkv", m->oh_t, Ly.qkv, ACT_NONE, m->oqkv, R, false, &S, m->dt, tiled));
         TRY(opt_attention(m, Ly, B, L, past, s, rw));
-        TRY(opt_gemm(m, s, "opt_gemm_o", m->octx, Ly.w_o, nullptr, 0, nullptr, R, T, T, true, &S, m->gdt, Ly.s_o, tiled));
-        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_o, m->ox, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
-        TRY(opt_gemm(m, s, "opt_gemm_f1", m->oh_t, Ly.w_f1, Ly.b_f1, 2, m->off, R, G, T, false, &S, m->gdt, Ly.s_f1, tiled));
-        TRY(opt_gemm(m, s, "opt_gemm_f2", m->off, Ly.w_f2, nullptr, 0, nullptr, R, T, G, true, &S, m->gdt, Ly.s_f2, tiled));
-        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.b_f2, m->ox, last ? m->o_lnf_g : m->ol[i + 1].ln1_g,
-                                    last ? m->o_lnf_b : m->ol[i + 1].ln1_b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
+        TRY(opt_gemm(m, s, "opt_gemm_o", m->octx, Ly.o, ACT_NONE, nullptr, R, true, &S, m->gdt, tiled));
+        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.o.b, m->ox, Ly.ln2.g, Ly.ln2.b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
+        TRY(opt_gemm(m, s, "opt_gemm_f1", m->oh_t, Ly.f1, ACT_RELU, m->off, R, false, &S, m->gdt, tiled));
+        TRY(opt_gemm(m, s, "opt_gemm_f2", m->off, Ly.f2, ACT_NONE, nullptr, R, true, &S, m->gdt, tiled));
+        const Norm& next = last ? m->o_lnf : m->ol[i + 1].ln1;
+        TRY(launch_reduce_layernorm(m->gdt, m->dpart, S, Ly.f2.b, m->ox, next.g, next.b, c.t_eps, m->oh_t, nullptr, m->ox, R, T, s, true));
     }
     if (sc) return 0;
-    return gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)(L - 1) * T * m->esz, L * T, m->o_tok_t, T, m->logits,
-                (L > 1 ? rw.K : 1) * m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
+    return gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)(L - 1) * T * m->esz, L * T, m->o_head, m->logits,
+                (L > 1 ? rw.K : 1) * m->ldl, OUT_F32, B);
 }
 
 // A pass (L > 1) with plain weights (f32 / f32s / bf16): B * L rows are GEMMs proper, so bias and residual ride the tiled GEMM's
@@ -1932,19 +1942,19 @@ int run_opt(Captioner* m, int B, int L, int past, hipStream_t s, const OptRows& 
 int run_opt_prompt_plain(Captioner* m, int B, int L, int past, hipStream_t s, const OptRows& rw) {
     const CapConfig& c = m->c;
     const int T = c.t_hidden, G = c.t_ffn, R = B * L;
-    const int af = m->gdt == CAP_DT_G8 ? 1 : 0;     // split mode: q | k | v for the attention kernels and the caches are fp32
     for (const OLayer& Ly : m->ol) {
-        TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln1_g, Ly.ln1_b, c.t_eps, m->oh_t, nullptr, R, T, s));
-        TRY(gemm(m, s, "opt_gemm_qkv", m->oh_t, T, Ly.w_qkv, T, m->oqkv, 3 * T, Ly.b_qkv, nullptr, R, 3 * T, T, 0, af));
+        TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln1.g, Ly.ln1.b, c.t_eps, m->oh_t, nullptr, R, T, s));
+        // (split mode: q | k | v for the attention kernels and the caches are fp32)
+        TRY(gemm(m, s, "opt_gemm_qkv", m->oh_t, T, Ly.qkv, m->oqkv, 3 * T, m->attn_out(), R));
         TRY(opt_attention(m, Ly, B, L, past, s, rw));
-        TRY(gemm(m, s, "opt_gemm_o", m->octx, T, Ly.w_o, T, m->ox, T, Ly.b_o, m->ox, R, T, T, 0, 1));
-        TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln2_g, Ly.ln2_b, c.t_eps, m->oh_t, nullptr, R, T, s));
-        TRY(gemm(m, s, "opt_gemm_f1", m->oh_t, T, Ly.w_f1, T, m->off, G, Ly.b_f1, nullptr, R, G, T, 2, 0));
-        TRY(gemm(m, s, "opt_gemm_f2", m->off, G, Ly.w_f2, G, m->ox, T, Ly.b_f2, m->ox, R, T, G, 0, 1));
+        TRY(gemm(m, s, "opt_gemm_o", m->octx, T, Ly.o, m->ox, T, OUT_F32, R, ACT_NONE, GemmOpt::residual(m->ox)));
+        TRY(launch_layernorm(m->gdt, m->ox, T, Ly.ln2.g, Ly.ln2.b, c.t_eps, m->oh_t, nullptr, R, T, s));
+        TRY(gemm(m, s, "opt_gemm_f1", m->oh_t, T, Ly.f1, m->off, G, OUT_T, R, ACT_RELU));
+        TRY(gemm(m, s, "opt_gemm_f2", m->off, G, Ly.f2, m->ox, T, OUT_F32, R, ACT_NONE, GemmOpt::residual(m->ox)));
     }
-    if (rw.kind == OptRows::CAPTIONS) return launch_layernorm(m->gdt, m->ox, T, m->o_lnf_g, m->o_lnf_b, c.t_eps, m->oh_t, nullptr, R, T, s);
-    TRY(launch_layernorm(m->gdt, m->ox + (size_t)(L - 1) * T, L * T, m->o_lnf_g, m->o_lnf_b, c.t_eps, m->oh_t, nullptr, B, T, s));
-    return gemm(m, s, "opt_gemm_vocab", m->oh_t, T, m->o_tok_t, T, m->logits, rw.K * m->ldl, nullptr, nullptr, B, c.vocab, T, 0, 1);
+    if (rw.kind == OptRows::CAPTIONS) return launch_layernorm(m->gdt, m->ox, T, m->o_lnf.g, m->o_lnf.b, c.t_eps, m->oh_t, nullptr, R, T, s);
+    TRY(launch_layernorm(m->gdt, m->ox + (size_t)(L - 1) * T, L * T, m->o_lnf.g, m->o_lnf.b, c.t_eps, m->oh_t, nullptr, B, T, s));
+    return gemm(m, s, "opt_gemm_vocab", m->oh_t, T, m->o_head, m->logits, rw.K * m->ldl, OUT_F32, B);
 }
 
 // The layers over a pass of B x L rows whose inputs are in ox: the prompt (nothing cached), or captions' new positions behind it.
@@ -1953,7 +1963,7 @@ int run_opt_pass(Captioner* m, int B, int L, hipStream_t s, const OptRows& rw) {
     const CapConfig& c = m->c;
     const int past = rw.kind == OptRows::CAPTIONS ? c.num_query_tokens + 1 : 0;
     if (!m->wq8) return run_opt_prompt_plain(m, B, L, past, s, rw);
-    TRY(launch_layernorm(m->gdt, m->ox, c.t_hidden, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B * L, c.t_hidden, s));
+    TRY(launch_layernorm(m->gdt, m->ox, c.t_hidden, m->ol[0].ln1.g, m->ol[0].ln1.b, c.t_eps, m->oh_t, nullptr, B * L, c.t_hidden, s));
     return run_opt(m, B, L, past, s, rw);
 }
 
@@ -1962,7 +1972,7 @@ int run_opt_step(Captioner* m, const int* tokens, int ld, int col, int at, int B
     const CapConfig& c = m->c;
     const int T = c.t_hidden;
     TRY(launch_opt_token_inputs(tokens, ld, col, m->o_tok, m->o_pos, m->ox, B, T, c.vocab, s, at));
-    TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1_g, m->ol[0].ln1_b, c.t_eps, m->oh_t, nullptr, B, T, s));
+    TRY(launch_layernorm(m->gdt, m->ox, T, m->ol[0].ln1.g, m->ol[0].ln1.b, c.t_eps, m->oh_t, nullptr, B, T, s));
     return run_opt(m, B, 1, at, s, rw);
 }
 
@@ -2020,7 +2030,7 @@ int run_blip2_image_side(Captioner* m, const void* pixels, int fmt, int B, hipSt
     const int T = c.t_hidden, nq = c.num_query_tokens;
     TRY(run_encoder(m, pixels, fmt, B, nullptr, s));
     TRY(run_qformer(m, kCaptionPass, B, nq, 0, nullptr, nullptr, s));
-    return gemm(m, s, "b2_gemm_lproj", m->qr.x_t, c.q_hidden, m->w_lproj, c.q_hidden, m->lm_proj, T, m->b_lproj, nullptr, B * nq, T, c.q_hidden, 0, 1);
+    return gemm(m, s, "b2_gemm_lproj", m->qr.x_t, c.q_hidden, m->lproj, m->lm_proj, T, OUT_F32, B * nq);
 }
 
 // BLIP-2's front half over the B images of a call: the image side (or the import of its state), and the prompt pass
@@ -2091,8 +2101,7 @@ int run_score_blip2(Captioner* m, const ScoreArgs& a, hipStream_t s) {
         TRY(run_opt_pass(m, nc, n, s, OptRows::captions(C, n0)));
         for (int r0 = 0; r0 < Rp; r0 += head_rows) {
             const int hr = std::min(head_rows, Rp - r0);
-            TRY(gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)r0 * T * e, T, m->o_tok_t, T, m->logits, m->ldl, nullptr, nullptr, hr,
-                     c.vocab, T, 0, 1));
+            TRY(gemm(m, s, "opt_gemm_vocab", (const char*)m->oh_t + (size_t)r0 * T * e, T, m->o_head, m->logits, m->ldl, OUT_F32, hr));
             ProfScope ps(m, s, "target_logprob", 0, 2.0 * hr * c.vocab * 4);
             TRY(launch_target_logprob(m->logits, m->ldl, c.vocab, hr, r0, n, a.ids + (size_t)n0 * L + 2, L, a.out_scored + n0,
                                       a.out_tlp + (size_t)n0 * npos + 1, a.out_top + (size_t)n0 * npos + 1, a.out_top_ids + (size_t)n0 * npos + 1, npos,
@@ -3047,10 +3056,8 @@ static int dt_of(int dtype) { return dtype == CAP_BF16 ? CAP_DT_BF16 : dtype == 
 static int in_dt_of(int dtype) { return dtype == CAP_BF16 ? CAP_DT_BF16 : CAP_DT_F32; }
 int cap_op_gemm(int dtype, const void* A, const void* W, const float* bias, const float* resid, void* C, int M, int N,
                 int K, int gelu, int out_f32, int tile, void* stream) {
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.C = C; p.ldc = N; p.bias = bias; p.resid = resid; p.ldr = N;
-    p.M = M; p.N = N; p.K = K; p.gelu = gelu; p.out_f32 = out_f32; p.epi = EPI_STORE; p.splitk = 1;
+    GemmParams p = gemm_params(A, K, W, K, bias, C, N, M, N, K, gelu, out_f32);
+    p.resid = resid; p.ldr = N;
 #ifdef CAP_EXPERIMENTS
     if (tile == 9 || tile == 13 || tile == 14 || tile == 21) { p.aux = resid; p.resid = nullptr; }   // instrumented kernels: `resid` is the cycle-count buffer
 #endif
@@ -3058,10 +3065,7 @@ int cap_op_gemm(int dtype, const void* A, const void* W, const float* bias, cons
 }
 int cap_op_gemm_partial(int dtype, const void* A, const void* W, float* part, int M, int N, int K, int splitk, int tile,
                         void* stream) {
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.C = part; p.ldc = N; p.M = M; p.N = N; p.K = K;
-    p.out_f32 = 1; p.epi = EPI_PARTIAL; p.splitk = splitk;
+    const GemmParams p = gemm_params(A, K, W, K, nullptr, part, N, M, N, K, ACT_NONE, OUT_F32, EPI_PARTIAL, splitk);
     return launch_gemm(dt_of(dtype), p, tile, (hipStream_t)stream);
 }
 int cap_op_layernorm(int dtype, const float* in, const float* gamma, const float* beta, float eps, void* out_t,
@@ -3217,10 +3221,8 @@ int cap_op_decode_attention_fused(int dtype, const float* q_part, int q_S, const
 /* the row-wise decode kernels with the compacted loop's live-row count (tests/test_pass_size_decode_kernels_gpu.py) */
 int cap_op_gemm_live(int dtype, const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int gelu, int out_f32,
                      int tile, const int32_t* n_live, void* stream) {
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.C = C; p.ldc = N; p.bias = bias; p.ldr = N;
-    p.M = M; p.N = N; p.K = K; p.gelu = gelu; p.out_f32 = out_f32; p.epi = EPI_STORE; p.splitk = 1; p.m_live = n_live;
+    GemmParams p = gemm_params(A, K, W, K, bias, C, N, M, N, K, gelu, out_f32);
+    p.ldr = N; p.m_live = n_live;
     return launch_gemm(dt_of(dtype), p, tile, (hipStream_t)stream);
 }
 int cap_op_layernorm_live(int dtype, const float* in, const float* gamma, const float* beta, float eps, void* out_t, float* out_f, int M,
@@ -3278,10 +3280,7 @@ int cap_op_small_cross(int dtype, const CapSmallCross* a, void* stream) {
 }
 int cap_op_gemm_crosskv(int dtype, const void* A, const void* W, const float* bias, void* cache, int n_img, int tokens, int heads,
                         int layers, int K, int kv16, void* stream) {
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.C = cache; p.ldc = 0; p.bias = bias;
-    p.M = n_img * tokens; p.N = layers * 2 * heads * 64; p.K = K; p.out_f32 = 1; p.epi = EPI_CROSSKV; p.splitk = 1;
+    GemmParams p = gemm_params(A, K, W, K, bias, cache, 0, n_img * tokens, layers * 2 * heads * 64, K, ACT_NONE, OUT_F32, EPI_CROSSKV);
     p.p0 = tokens; p.p1 = heads; p.p2 = n_img; p.kv16 = kv16;
     return launch_gemm(dt_of(dtype), p, 0, (hipStream_t)stream);
 }
@@ -3323,11 +3322,8 @@ int cap_op_gemm_epi(int dtype, const CapGemmEpi* a, void* stream) {
             cap_set_error("cap_op_gemm_epi: unknown epi %d (0 store, 1 patch, 2 cross K/V, 3 q|k|v, 4 split-K)", a->epi);
             return -1;
     }
-    GemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = a->A; p.lda = a->lda; p.W = a->W; p.ldw = a->ldw; p.bias = a->bias; p.C = a->C; p.ldc = a->ldc; p.C2 = a->C2; p.aux = a->aux;
-    p.M = a->M; p.N = a->N; p.K = a->K; p.gelu = a->gelu; p.out_f32 = a->out_f32; p.epi = a->epi; p.splitk = a->splitk;
-    p.p0 = a->p0; p.p1 = a->p1; p.p2 = a->p2; p.p3 = a->p3; p.kv16 = a->kv16; p.m_live = a->m_live;
+    GemmParams p = gemm_params(a->A, a->lda, a->W, a->ldw, a->bias, a->C, a->ldc, a->M, a->N, a->K, a->gelu, a->out_f32, a->epi, a->splitk);
+    p.C2 = a->C2; p.aux = a->aux; p.p0 = a->p0; p.p1 = a->p1; p.p2 = a->p2; p.p3 = a->p3; p.kv16 = a->kv16; p.m_live = a->m_live;
     return launch_gemm(dt_of(dtype), p, a->tile, (hipStream_t)stream);
 }
 int cap_op_pack_kv16(const float* src, void* dst, size_t n_rows, void* stream) {

@@ -11,6 +11,8 @@ enum GemmEpi {
                        // applied by the consumer (launch_reduce_layernorm), in a fixed order -> deterministic
 };
 
+enum GemmAct { ACT_NONE = 0, ACT_GELU = 1, ACT_RELU = 2, ACT_QUICK_GELU = 3 };   // GemmParams::gelu
+
 struct GemmParams {
     const void* A; int lda;        // activations, element type T, row-major [M,K]
     const void* W; int ldw;        // weights, element type T, row-major [N,K] (torch Linear layout)
