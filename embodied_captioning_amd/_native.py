@@ -211,6 +211,10 @@ _SIGNATURES = {
     "cap_clip_embed_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cap_clip_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     "cap_clip_logit_scale": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "cap_cosine_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "cap_group_similarity_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "cap_group_similarity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "cap_blip2_itm_encode_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "cap_blip2_itc_image_features": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cap_blip2_itc_text_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -78,6 +78,10 @@ class SentenceEncoder:
     def eval(self):
         return self
 
+    def close(self) -> None:
+        """Free the engine's device memory (the scorers' name for it); the encoder cannot be used afterwards."""
+        self.engine.close()
+
     @property
     def device(self):
         return self._device
@@ -133,3 +137,41 @@ class SentenceEncoder:
         if convert_to_tensor:
             return emb
         return emb.cpu().numpy() if convert_to_numpy else list(emb.cpu())
+
+    # --- similarity: the sentence-transformers names, on the device (similarity.py)
+    def similarity(self, a, b) -> torch.Tensor:
+        """sentence-transformers `model.similarity(a, b)` (cosine): fp32 [len(a), len(b)] on the device."""
+        from ..similarity import cosine_matrix
+        return cosine_matrix(self._as_rows(a), self._as_rows(b))
+
+    def similarity_pairwise(self, a, b) -> torch.Tensor:
+        """sentence-transformers `model.similarity_pairwise(a, b)`: fp32 [n] = cos(a_i, b_i), the diagonal of `similarity`."""
+        from ..similarity import cosine_matrix
+        return cosine_matrix(self._as_rows(a), self._as_rows(b), paired=True)
+
+    def _as_rows(self, x) -> torch.Tensor:
+        x = torch.as_tensor(x)
+        if x.dim() == 1:
+            x = x[None]
+        return x.to(self._device)
+
+    @torch.no_grad()
+    def caption_statistics(self, freq: dict) -> dict:
+        """freq: the output of `distributed.captions_frequency`.  Every DISTINCT caption of every group is embedded once and the counts
+        go in as weights -> {key: {'disagreement' (the reference's per-object `_cosine_distance`), 'mean', 'std' (pairwise cosine over
+        the object's captions, repeats included), 'pairs', 'medoid_caption' (None for an empty group), 'row_mean': [per distinct
+        caption, in the group's order]}}."""
+        from ..similarity import caption_groups, group_similarity
+        keys, sentences, offsets, weights = caption_groups(freq)
+        if sentences:
+            emb = self.encode(sentences, convert_to_tensor=True)
+        else:
+            emb = torch.empty((0, self.arch.hidden), dtype=torch.float32, device=self._device)
+        st = group_similarity(emb, offsets, torch.tensor(weights, dtype=torch.float32))
+        dis, mean, var, pairs, med, rm = (t.cpu().numpy() for t in st)
+        out = {}
+        for g, key in enumerate(keys):
+            out[key] = {"disagreement": float(dis[g]), "mean": float(mean[g]), "std": float(np.sqrt(var[g])), "pairs": int(pairs[g]),
+                        "medoid_caption": sentences[int(med[g])] if med[g] >= 0 else None,
+                        "row_mean": [float(v) for v in rm[offsets[g]:offsets[g + 1]]]}
+        return out

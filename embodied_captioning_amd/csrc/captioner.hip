@@ -2672,6 +2672,20 @@ int cap_clip_logits(const float* img, const float* txt, int Ni, int Nt, int pair
     return launch_clip_logits(img, txt, Ni, Nt, embed_dim, paired, logit_scale, out, (hipStream_t)stream);
 }
 
+int cap_cosine_matrix(const float* a, const float* b, int Na, int Nb, int D, int paired, float* out, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+    return launch_cosine_matrix(a, b, Na, Nb, D, paired, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t cap_group_similarity_workspace(int N, int G, int D, const int32_t* offsets) { return sim_group_workspace(N, G, D, offsets); }
+
+int cap_group_similarity(const float* e, const int32_t* offsets, const float* weights, int N, int G, int D, float* disagreement,
+                         float* pair_mean, float* pair_var, int64_t* pairs, int32_t* medoid, float* row_mean, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    return launch_group_similarity(e, offsets, weights, N, G, D, disagreement, pair_mean, pair_var, (long long*)pairs, medoid, row_mean,
+                                   workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int cap_clip_logit_scale(CapHandle h, float* out) {
     Captioner* m = (Captioner*)h;
     if (!out) { cap_set_error("cap_clip_logit_scale: null output"); return -1; }

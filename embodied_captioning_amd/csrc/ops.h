@@ -292,6 +292,19 @@ int launch_clip_head(const float* x, int rows_per, const int* lens, const float*
 // exp(logit_scale) * img . txt^T: paired -> out [Ni] (row i against row i), else out [Ni, Nt]
 int launch_clip_logits(const float* img, const float* txt, int Ni, int Nt, int P, int paired, float logit_scale, float* out, hipStream_t s);
 
+// ---- similarity.hip ----------------------------------------------------------------------------
+// cos(a_i, b_j) of fp32 rows [., D] (not assumed normalised; a zero row has cosine 0 with everything): out [Na, Nb], or with paired
+// out [Na] = cos(a_i, b_i), bit for bit the matrix's diagonal.  ws: (Na + Nb) floats, caller-owned.
+int launch_cosine_matrix(const float* a, const float* b, int Na, int Nb, int D, int paired, float* out, void* ws, size_t ws_bytes,
+                         hipStream_t s);
+// bytes of workspace launch_group_similarity needs for this grouping (0 + cap_set_error when the grouping is refused)
+size_t sim_group_workspace(int N, int G, int D, const int* offsets);
+// per-group caption disagreement / pair statistics / medoid and per-row mean similarity (include/captioner_hip.h,
+// cap_group_similarity); offsets is a HOST array of G + 1 row bounds, everything else device memory
+int launch_group_similarity(const float* e, const int* offsets, const float* weights, int N, int G, int D, float* disagreement,
+                            float* pair_mean, float* pair_var, long long* pairs, int* medoid, float* row_mean, void* ws, size_t ws_bytes,
+                            hipStream_t s);
+
 // ---- blip2_itm.hip -----------------------------------------------------------------------------
 // Q-Former text embeddings: x = qformer.layernorm(word[ids[r]] + pos[r % L]) -> x_f fp32 and x_t (dtype) [M, D] (ids clamped to [0, V))
 int launch_itm_embed_text(int dtype, const int* ids, int L, const float* word, const float* pos, const float* gamma, const float* beta,

@@ -289,3 +289,18 @@ def consensus_caption(freq_list):
     merge step, pseudocaptioner.py:364-447, which stays out of scope)."""
     best = max(freq_list, key=lambda fc: fc[0])
     return best[1]
+
+
+def medoid_caption(freq_list, row_mean):
+    """The caption most similar to the rest of its object's captions: freq_list as `captions_frequency` builds it, row_mean[i] the
+    mean cosine of caption i to the other members (`similarity.group_similarity(...).row_mean` of the group, or
+    `SentenceEncoder.caption_statistics(...)[key]['row_mean']`); ties go to the first seen."""
+    if len(freq_list) != len(row_mean):
+        raise ValueError(f"{len(freq_list)} captions but {len(row_mean)} row means")
+    if not freq_list:
+        raise ValueError("no captions")
+    best = 0
+    for i in range(1, len(freq_list)):
+        if float(row_mean[i]) > float(row_mean[best]):
+            best = i
+    return freq_list[best][1]

@@ -10,6 +10,9 @@ batched device calls (captioner/clip_scorer.py, captioner/blip2_itm_scorer.py) i
 
 `--method blip_ll` has no counterpart in the reference: the selector is the BLIP captioner's OWN likelihood of each caption given each
 crop of the object (captioner/likelihood_scorer.py), so no second model is needed; `--method blip2_ll` is the same under BLIP-2.
+`--method sbert [--model all-MiniLM-L6-v2]` has none either: no image is read, the pseudo-caption of an object is the MEDOID of its captions
+under the sentence encoder - the caption with the largest mean cosine to the object's other captions, repeats counted
+(captioner/sentence_encoder.py `caption_statistics`, csrc/similarity.hip).
 The reference's other methods (`llm`, `mobileclip`, `openclip` ViT-bigG-14) are refused by name.
 """
 from __future__ import annotations
@@ -30,7 +33,7 @@ BLIP2_METHODS = {"blip2_itm": "itm", "blip2_itc": "itc"}          # --method -> 
 LIKELIHOOD_METHODS = {"blip_ll": "blip", "blip2_ll": "blip2"}     # --method -> the captioner family whose likelihood selects
 DEFAULT_MODELS = {"clip": "openai/clip-vit-base-patch32", "blip2_itm": "Salesforce/blip2-itm-vit-g-coco",
                   "blip2_itc": "Salesforce/blip2-itm-vit-g-coco", "blip_ll": "Salesforce/blip-image-captioning-base",
-                  "blip2_ll": "Salesforce/blip2-opt-2.7b"}
+                  "blip2_ll": "Salesforce/blip2-opt-2.7b", "sbert": "all-MiniLM-L6-v2"}
 REFERENCE_FRAME = (1280, 1280)       # the reference's hard-coded image size for expand_box (:346)
 
 
@@ -179,6 +182,22 @@ def likelihood_pseudo_captions(grouped: Dict, scorer, expand_factor: float = 0.1
     return out
 
 
+def sbert_pseudo_captions(grouped: Dict, encoder) -> Dict[str, dict]:
+    """grouped as for `clip_pseudo_captions` (only 'caption' is read); encoder: a `SentenceEncoder`.  Per object, every DISTINCT caption
+    (first occurrence order) with its mean cosine to the object's other captions, repeats counted -> `clip_pseudo_captions`'
+    structure: {str(key): {'captions_list': [[score, caption], ...] (by score, descending, stable), 'pseudocaption': [score,
+    caption] = the medoid}}."""
+    from .distributed import captions_frequency
+    freq = captions_frequency({k: [inst["caption"] for inst in v] for k, v in grouped.items() if v})
+    stats = encoder.caption_statistics(freq)
+    out: Dict[str, dict] = {}
+    for k, lst in freq.items():
+        scored = [[float(s), c] for s, (_, c) in zip(stats[k]["row_mean"], lst)]
+        scored.sort(key=lambda x: x[0], reverse=True)    # list.sort is stable: equal scores keep first-occurrence order
+        out[str(k)] = {"captions_list": scored, "pseudocaption": list(scored[0])}
+    return out
+
+
 def _instances_fields(inst, idx):
     if isinstance(inst, dict):
         info, box, cap = inst["infos"][idx], inst["pred_boxes"][idx], inst["captions"][idx]
@@ -221,11 +240,14 @@ def main(argv=None) -> int:
     if args.method in REFUSED_METHODS:
         raise SystemExit(f"--method {args.method} is not supported here (it needs models this project does not run); "
                          f"use --method clip, blip2_itm or blip2_itc")
-    if args.method != "clip" and args.method not in BLIP2_METHODS and args.method not in LIKELIHOOD_METHODS:
-        raise SystemExit(f"unknown --method {args.method!r}; supported: clip, blip2_itm, blip2_itc")
+    if args.method not in ("clip", "sbert") and args.method not in BLIP2_METHODS and args.method not in LIKELIHOOD_METHODS:
+        raise SystemExit(f"unknown --method {args.method!r}; supported: clip, blip2_itm, blip2_itc, blip_ll, blip2_ll, sbert")
     model = args.model or DEFAULT_MODELS[args.method]
     grouped = group_records(sorted(glob.glob(os.path.join(args.file_path, "*.npz"))))
-    if args.method in LIKELIHOOD_METHODS:
+    if args.method == "sbert":
+        from .captioner.sentence_encoder import SentenceEncoder
+        scorer = SentenceEncoder(model, device=args.device, dtype="f32", batch_size=min(args.batch_size, 64))
+    elif args.method in LIKELIHOOD_METHODS:
         from .captioner.likelihood_scorer import CaptionLikelihoodScorer
         scorer = CaptionLikelihoodScorer(model, device=args.device, dtype=args.dtype, batch_size=min(args.batch_size, 32),
                                          family=LIKELIHOOD_METHODS[args.method])
@@ -236,7 +258,9 @@ def main(argv=None) -> int:
         from .captioner.blip2_itm_scorer import Blip2ItmScorer
         scorer = Blip2ItmScorer(model, device=args.device, dtype=args.dtype, batch_size=args.batch_size)
     try:
-        if args.method in LIKELIHOOD_METHODS:
+        if args.method == "sbert":
+            result = sbert_pseudo_captions(grouped, scorer)
+        elif args.method in LIKELIHOOD_METHODS:
             result = likelihood_pseudo_captions(grouped, scorer)
         else:
             result = clip_pseudo_captions(grouped, scorer) if args.method == "clip" else blip2_pseudo_scores(grouped, scorer, BLIP2_METHODS[args.method])

@@ -47,6 +47,10 @@
  *   pseudo-caption      :193-308 `model({"image", "text_input"}, match_head="itm" | "itc")` (one call and one    cap_blip2_itc_image_features,
  *   scores              ViT-g pass per (crop, caption) pair; here: batches of pairs, CAP_ARCH_BLIP2_ITM,        cap_blip2_itc_text_features,
  *                       arithmetic of HF `Blip2ForImageTextRetrieval.forward`)                                 cap_blip2_itc_scores, cap_blip2_itm_logits
+ *   caption             experimenting_env/utils/projection_utils.py `_cosine_distance` (per object, every map update:   cap_group_similarity,
+ *   disagreement,       mean of 1 - cos over the n x n matrix of its caption embeddings); scripts/compute_cosine_sim.py  cap_group_similarity_workspace,
+ *   cosine statistics   (mean pairwise cosine over i < j per (episode, object)); captioner/test_cosine_similarity.py     cap_cosine_matrix
+ *                       (its mean and std); scripts/compute_performance_measures.py `diag(cos_sim(proposed, reference))`
  *   device move/free    predictor_utils.py:187 `.to(...)`; object lifetime            cap_destroy
  *   errors              Python exceptions (utils_captioner.py:6, factory.py:231,309)  int return codes + cap_last_error
  *
@@ -482,6 +486,33 @@ int cap_clip_embed_text(CapHandle h, const int32_t* ids, const int32_t* lens, in
 int cap_clip_logits(const float* img, const float* txt, int Ni, int Nt, int paired, float logit_scale, float* out, int embed_dim,
                     void* stream);
 int cap_clip_logit_scale(CapHandle h, float* out);
+
+/* Cosine similarity of sentence embeddings (no handle; fp32 throughout, exact fp32 products on v_mfma_f32_32x32x2_f32).  Rows are NOT
+ * assumed normalised: e^_i = e_i / max(||e_i||, 1e-12) (F.normalize), s_ij = e^_i . e^_j - so a zero row has cosine 0 with everything
+ * (itself included).  D % 4 == 0, D <= 1024; e / a / b / workspace 16-byte aligned device pointers.  Refusals name what is wrong: null
+ * buffers, D % 4 != 0, D > 1024, negative counts, offsets that do not start at 0 / decrease / do not end at N, a workspace too small.
+ *   cap_cosine_matrix: a [Na, D], b [Nb, D] -> out [Na, Nb] = s(a_i, b_j); paired = 1 (Na == Nb) -> out [Na] = s(a_i, b_i), bit for bit
+ *     the matrix's diagonal.  workspace: (Na + Nb) * 4 bytes, caller-owned.
+ *   cap_group_similarity: e [N, D]; G groups of contiguous rows offsets[g] .. offsets[g + 1] - `offsets` is a HOST array of G + 1 ints (it
+ *     is checked, sizes the grid and is copied during the call: it may be freed on return when it is pageable memory); weights fp32 [N]
+ *     of positive integer counts (captions_frequency's freq) or null = ones.  A weighted statistic is by definition the unweighted
+ *     statistic of the group with row i repeated w_i times; W = sum w_i.  Per group g:
+ *       disagreement[g] fp32   sum_ij w_i w_j (1 - s_ij) / W^2, diagonal included (the reference's per-object value); empty group: 0
+ *       pairs[g]        int64  W (W - 1) / 2
+ *       pair_mean[g], pair_var[g] fp32   mean and population variance of s over the unordered pairs of the expanded group (pairs of two
+ *                       copies of one row included); 0 when pairs == 0
+ *       medoid[g]       int32  the row (index within the call) with the largest row_mean, first index on equal values; empty group: -1
+ *     and per row i: row_mean[i] fp32 = (sum_j w_j s_ij - s_ii) / (W - 1), 0 when W == 1.
+ *     No floating-point atomics; partial sums are combined in fp64 in a fixed order, so a group's outputs are the same bits wherever the
+ *     group sits in the call and whatever other groups the call holds.  Nothing is allocated inside the call:
+ *   cap_group_similarity_workspace: the bytes of caller-owned device workspace cap_group_similarity needs for (N, G, D, offsets);
+ *     0 (and cap_last_error) when the grouping is refused. */
+int cap_cosine_matrix(const float* a, const float* b, int Na, int Nb, int D, int paired, float* out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+size_t cap_group_similarity_workspace(int N, int G, int D, const int32_t* offsets);
+int cap_group_similarity(const float* e, const int32_t* offsets, const float* weights, int N, int G, int D, float* disagreement,
+                         float* pair_mean, float* pair_var, int64_t* pairs, int32_t* medoid, float* row_mean, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* BLIP-2 image-text scorer (CAP_ARCH_BLIP2_ITM handle; weights by HF `Blip2ForImageTextRetrieval` names: vision_model.*,
  * derived.qformer_x0 [= qformer.layernorm(query_tokens), host-derived], embeddings.word_embeddings.weight,
